@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """Benchmark of the whole-volume nuclei-detection hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config c3|c2|c5]
+    python bench.py --gpus N --steps K --warmup W [--config c3|c2|c5] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints its line; ``--full`` adds everything the headline figure
+does not need: the CPU baselines and the parity check of a sample against the oracle, the compact c2 / c5
+sub-records of the default command, the device copy and host -> device rates, and per-kernel times that take steps
+of their own after the timed region.  ``--dump-outputs DIR``: rank 0 writes what the last timed step returned (the
+final blob table, float64, and the co-localisation flags, float32) as ``DIR/<name>.npy``.
 
 ``python bench.py --gpus N`` with N > 1 and no ``WORLD_SIZE`` in the environment starts its N ranks itself (a child
 ``torch.distributed.run``, before this process touches the GPU) and relays rank 0's line.
@@ -21,10 +27,10 @@ Rank 0 prints ONE JSON line with the contract fields plus
   roofline      dominant kernel: algorithmic bytes (per VOLUME voxel) / HIP-event time on its
                 launch stream against the 8 TB/s peak; the bytes it really moves and its VALU / MFMA busy fractions
                 from the committed counter passes of this same code (null when the kernels changed since)
-  cpu_baseline  the oracle (NumPy/SciPy restatement of the reference) on this box's host cores over a bounded
-                sample of the same workload, detection and pruning seconds apart
+  cpu_baseline  (--full) the oracle (NumPy/SciPy restatement of the reference) on this box's host cores over a
+                bounded sample of the same workload, detection and pruning seconds apart
   ranks         per-rank kernel / exchange / prune milliseconds (N > 1)
-  sub_records   (default command on one GPU only) compact c2 and c5 results: value, ms_per_step, roofline
+  sub_records   (--full, default command on one GPU only) compact c2 and c5 results: value, ms_per_step, roofline
                 fraction, parity of a sample against the oracle
 """
 from __future__ import annotations
@@ -79,6 +85,8 @@ B_ALG_PER_SIGMA = 50                # SURVEY.md section 8d contract figure
 MAIN_STREAM = ("zpass", "ypass", "xpass", "generic", "peaks", "zxpass", "y2pass", "preproc", "zxpack", "rescore")
 #: committed counter passes of this command (tools/profile_round.sh): HBM bytes per launch, VALU / MFMA busy
 PMC_FILE = "profiles/r06_pmc_counters.json"
+#: --dump-outputs: what the files of one run may hold in all; larger outputs keep a fixed, seeded sample of their rows
+DUMP_LIMIT_BYTES = 64 << 20
 ZX_DTYPES = {7: "f16x2 MFMA (f32 accumulate) + 16-bit fixed-point intermediates; f64 re-score of every candidate",
              6: "f16x2 MFMA (f32 accumulate), f32 intermediates; f64 re-score of every candidate",
              2: "f32 (packed VALU); f64 re-score of every candidate",
@@ -248,6 +256,26 @@ def run_cpu_baseline(name, args, host_vol):
 
 def volume_sha1(vol: np.ndarray) -> str:
     return hashlib.sha1(np.ascontiguousarray(vol).tobytes()).hexdigest()
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> dict:
+    """``--dump-outputs``: every array as ``out_dir/<name>.npy`` (float64 stays float64, everything else becomes float32).
+    Above ``DUMP_LIMIT_BYTES`` in all, each array keeps the same share of its rows, picked by a generator of fixed
+    seed -- arrays with as many rows (a table and its flags) keep the same rows.  Returns what was written."""
+    conv = {k: np.asarray(a, dtype=np.float64 if np.asarray(a).dtype == np.float64 else np.float32)
+            for k, a in arrays.items()}
+    total = sum(a.nbytes for a in conv.values())
+    keep = 1.0 if total <= DUMP_LIMIT_BYTES else DUMP_LIMIT_BYTES / total
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for k, a in conv.items():
+        n = len(a) if a.ndim else 0
+        if keep < 1.0 and n:
+            rows = np.sort(np.random.default_rng(0).choice(n, int(n * keep), replace=False))
+            a = a[rows]
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+        written[k] = {"shape": list(a.shape), "dtype": str(a.dtype), "rows_of": n}
+    return written
 
 
 def load_parity_sample(path, name, args):
@@ -484,14 +512,16 @@ def run_gpu(name, args, host_vol, baseline, steps, warmup, ctx):
     bl.PRE_WAITS.clear()
     if events != "all":
         timed = nat.timing_read() if events == "dominant" else {}
-        extra = max(1, min(steps, 10))
-        nat.timing_enable(True)
-        for _ in range(extra):
-            one_step()
-        torch.cuda.synchronize()
-        ktimes = {k: (ms * steps / extra, n * steps // extra) for k, (ms, n) in nat.timing_read().items()}
-        if dominant is not None and timed.get(dominant, (0.0, 0))[1]:
-            ktimes[dominant] = timed[dominant]          # (the timed region's own events)
+        ktimes = dict(timed)
+        if args.full:               # (the families not timed in the region: extra steps of their own)
+            extra = max(1, min(steps, 10))
+            nat.timing_enable(True)
+            for _ in range(extra):
+                one_step()
+            torch.cuda.synchronize()
+            ktimes = {k: (ms * steps / extra, n * steps // extra) for k, (ms, n) in nat.timing_read().items()}
+            if dominant is not None and timed.get(dominant, (0.0, 0))[1]:
+                ktimes[dominant] = timed[dominant]          # (the timed region's own events)
     else:
         ktimes = nat.timing_read()
     nat.timing_enable(False)
@@ -627,11 +657,12 @@ def run_gpu(name, args, host_vol, baseline, steps, warmup, ctx):
     main_ms = sum(ms for k, (ms, n) in ktimes.items() if k in MAIN_STREAM and k not in overlapped) / steps
     b_alg = B_ALG_PER_SIGMA * ns * n_chl
     vol_bytes = nvox * n_chl * 2
-    frac_kernels = b_alg * (nvox / eff_world) / (gpu_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
+    # (no kernel timed: a plain run whose timed region records no events, e.g. graph replays without --full)
+    frac_kernels = b_alg * (nvox / eff_world) / (gpu_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if gpu_ms else None
     frac_wall = b_alg * nvox / (elapsed / steps) / 1e9 / HBM_PEAK_GBS / eff_world
     for key, val in (("pipeline_roofline.frac_kernels", frac_kernels), ("pipeline_roofline.frac_wall", frac_wall),
                      ("roofline.frac", roof["frac"] if roof else 0)):
-        if val > 1:
+        if val is not None and val > 1:
             flags.append(key)
     h2d_gbps = ctx.get("h2d_gbps")
     out = {
@@ -674,8 +705,8 @@ def run_gpu(name, args, host_vol, baseline, steps, warmup, ctx):
             "alg_bytes_per_voxel": b_alg,
             "gpu_kernel_ms_per_step_rank0": round(gpu_ms, 2),
             "main_stream_kernel_ms_per_step_rank0": round(main_ms, 2),
-            "achieved_GBps_kernels": round(frac_kernels * HBM_PEAK_GBS, 1),
-            "frac_kernels": round(frac_kernels, 4),
+            "achieved_GBps_kernels": None if frac_kernels is None else round(frac_kernels * HBM_PEAK_GBS, 1),
+            "frac_kernels": None if frac_kernels is None else round(frac_kernels, 4),
             "achieved_GBps_wall": round(frac_wall * HBM_PEAK_GBS * world, 1),
             "frac_wall": round(frac_wall, 4),
             # wall clock not covered by a kernel on the stream the LoG passes run on: start-up before the first
@@ -743,6 +774,11 @@ def run_gpu(name, args, host_vol, baseline, steps, warmup, ctx):
     if args.dump and name == args.config:
         np.savez(args.dump, final=np.zeros((0, 8)) if final is None else final,
                  colocs=np.zeros((0, n_chl), dtype=np.uint8) if colocs is None else colocs)
+    if args.dump_outputs and name == args.config:
+        arrays = {"final": np.zeros((0, 8)) if final is None else final}
+        if coloc:
+            arrays["colocs"] = np.zeros((0, n_chl)) if colocs is None else colocs
+        out["dumped_outputs"] = dump_outputs(args.dump_outputs, arrays)
     return out
 
 
@@ -846,7 +882,7 @@ def run_gpu_tiles(args, baseline, steps, warmup, ctx):
     elapsed = time.perf_counter() - t0
     ktimes = nat.timing_read()
     nat.timing_enable(False)
-    if args.kernel_events == "none":
+    if args.kernel_events == "none" and args.full:
         nat.timing_enable(True)
         one_step()
         torch.cuda.synchronize()
@@ -904,6 +940,14 @@ def run_gpu_tiles(args, baseline, steps, warmup, ctx):
     ms_tile = elapsed / steps * 1e3 / max(1, per_rank)
     b_alg = B_ALG_PER_SIGMA * ns * n_chl
     tile0 = next((d for d in digests if d[0] == 0), None)
+    dumped = None
+    if args.dump_outputs:         # (every tile of the stack: the last step's tables of all ranks, as gathered above)
+        arrays = {}
+        for g, b in sorted(everything, key=lambda e: e[0]):
+            arrays[f"tile{g}_final"] = np.zeros((0, 8)) if b.blobs is None else b.blobs
+            if coloc:
+                arrays[f"tile{g}_colocs"] = np.zeros((0, n_chl)) if b.colocalizations is None else b.colocalizations
+        dumped = dump_outputs(args.dump_outputs, arrays)
     return {
         "metric": cfg["metric"] + f"; tiled stack, {per_rank} tile(s) per GPU sharded by tile",
         "value": round(nvox * total * steps / elapsed / 1e6, 2), "unit": "Mvoxels/s",
@@ -939,6 +983,7 @@ def run_gpu_tiles(args, baseline, steps, warmup, ctx):
             "committed oracle table " + baseline["committed"] if baseline.get("committed") else
             "the oracle, run in this process before the GPU was initialised"),
         "scipy": ctx.get("scipy"), "volume_gen_s": round(t_gen, 2),
+        "dumped_outputs": dumped,
     }
 
 
@@ -1047,8 +1092,15 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", choices=sorted(CONFIGS), default=None,
-                    help="workload (default c3; the default command on one GPU also appends compact c2 and c5 sub-records)")
-    ap.add_argument("--no-sub-records", action="store_true", help="default command: c3 only")
+                    help="workload (default c3; the default command on one GPU with --full also appends compact c2 and c5 sub-records)")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline figure does not need: CPU baselines and the parity sample against the "
+                         "oracle, the default command's c2 / c5 sub-records, the device copy and host -> device rates, "
+                         "per-kernel times from extra steps after the timed region")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step returned as DIR/<name>.npy (float64 / float32; a fixed, "
+                         "seeded sample of the rows above 64 MB in all)")
+    ap.add_argument("--no-sub-records", action="store_true", help="default command with --full: c3 only")
     ap.add_argument("--shape", type=int, nargs=3, default=None, help="z y x (default: the named config's)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--kernel-events", choices=("all", "dominant", "none"), default="all",
@@ -1066,7 +1118,8 @@ def main():
     ap.add_argument("--dump", default=None, metavar="NPZ", help="rank 0 writes the final table (and colocs) here")
     ap.add_argument("--segment-size", type=int, default=0, help="profile segment_size (default 256; parity tests use smaller blocks)")
     ap.add_argument("--cpu-full", action="store_true",
-                    help="CPU baseline (and the parity check) on the WHOLE volume of --config instead of the bounded sample")
+                    help="CPU baseline (and the parity check) on the WHOLE volume of --config instead of the bounded sample "
+                         "(implies --full)")
     ap.add_argument("--cpu-cores", type=int, default=0, help="pool size of the CPU baseline (default: all physical cores)")
     ap.add_argument("--from-host", choices=("pinned", "pageable", "mmap"), default=None,
                     help="after the timed region: steps that start from a HOST copy of the volume (upload overlapped "
@@ -1110,6 +1163,7 @@ def main():
                     help="check the parity sample against this committed oracle table (tests/golden/make_bench_samples.py) "
                          "instead of running the oracle: no cpu_baseline timing, seconds instead of minutes")
     args = ap.parse_args()
+    args.full = args.full or args.cpu_full
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # N ranks wanted, none launched: launch them (before anything here touches the GPU)
         raise SystemExit(self_launch(sys.argv[1:], args.gpus))
@@ -1127,7 +1181,7 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch one rank per GPU")
     # before anything touches the GPU runtime (the host driver only supports dmabuf IPC)
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    subs = [] if (explicit or args.no_sub_records or world > 1 or args.volume or args.shape or args.denoise
+    subs = [] if (not args.full or explicit or args.no_sub_records or world > 1 or args.volume or args.shape or args.denoise
                   or args.segment_size or args.dump or by_tile or args.share) else list(SUB_RECORDS)
 
     import torch
@@ -1143,7 +1197,7 @@ def main():
     # tools/steptrace.py)
     from magellanmapper_amd import _native as nat
     nat.keep_host_heap()
-    if rank == 0 and world > 1 and not args.parity_sample and not args.no_cpu_baseline and not args.cpu_full and not (
+    if rank == 0 and world > 1 and args.full and not args.parity_sample and not args.no_cpu_baseline and not args.cpu_full and not (
             args.volume or args.shape or args.denoise or args.segment_size):
         # the CPU baseline is timed at N = 1 only (the contract's wording): the lines of N > 1 check parity against the
         # COMMITTED oracle table of the same sample instead (no minute of oracle work with N - 1 ranks waiting)
@@ -1154,7 +1208,7 @@ def main():
         got = load_parity_sample(args.parity_sample, args.config, args)
         if got is not None:
             baselines[args.config] = got
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         for name in [args.config] + subs:
             if name not in baselines:
                 baselines[name] = run_cpu_baseline(name, args, host_vol)
@@ -1219,8 +1273,9 @@ def main():
                # overlap prune: blob_log._reference_pair_order); fixtures were made with 1.7.1, tests run with this one
                scipy=scipy.__version__)
 
-    # ---------------- measured beside the roofline peak: a device copy and the host -> device link
-    if rank == 0:
+    # ---------------- measured beside the roofline peak: a device copy and the host -> device link (--full; --from-host
+    # quotes its steps against the link's rate)
+    if rank == 0 and (args.full or args.from_host):
         n = 1 << 28                                   # 1 GiB in + 1 GiB out: far beyond the 256 MiB Infinity Cache
         a = torch.empty(n, dtype=torch.float32, device=dev).normal_()
         b = torch.empty_like(a)

@@ -3,12 +3,12 @@
 
     python tests/golden/make_bench_samples.py            # writes tests/golden/bench_sample_{c3,c5}.npz
 
-``bench.py`` checks the HIP path against the oracle on a sample of its workload at every run, which costs about a
+``bench.py --full`` checks the HIP path against the oracle on a sample of its workload at every run, which costs about a
 minute of CPU work on all cores of the box.  The ``-m gpu`` tests that run the full-size workloads only want the
 check, not the CPU timing, so the oracle's answer for a FIXED sample is committed here: the sample's shape and seed,
 the SHA-1 of the generated voxels (``bench.make_host_sample``: bench.py regenerates the sample and refuses the table if
 the voxels differ), the profile, and the oracle's final table (+ co-localisation flags).  Data only; the oracle is
-``oracle/magmap_oracle.py`` through ``bench.cpu_baseline``, i.e. exactly what a bench run without the option computes.
+``oracle/magmap_oracle.py`` through ``bench.cpu_baseline``, i.e. exactly what a ``--full`` run without the option computes.
 """
 import argparse
 import json

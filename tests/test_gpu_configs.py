@@ -119,7 +119,7 @@ def test_c2_single_sigma_volume_matches_oracle(gpu, tmp_path):
     vol = _host_volume(shape, 2)
     np.save(tmp_path / "c2.npy", vol)
     line = _run_bench(tmp_path, 1, "--config", "c2", "--volume", str(tmp_path / "c2.npy"), "--dump",
-                      str(tmp_path / "c2.npz"))
+                      str(tmp_path / "c2.npz"), "--full")
     assert line["config"]["blocks_per_rank"] == 4 and line["roofline"]["kernel"] in ("zxpass", "y2pass")
     profile = _bench_profile(min_sigma_factor=3, max_sigma_factor=3, num_sigma=1)
     want, _ = mmo.detect_blobs_blocks(vol, None, [profile], RES)
@@ -138,7 +138,7 @@ def test_kernel_event_modes_of_the_bench_line(gpu, tmp_path):
     lines = {}
     for mode in ("all", "dominant", "none"):
         lines[mode] = _run_bench(tmp_path, 1, "--config", "c3", "--segment-size", "64", "--volume", str(tmp_path / "ke.npy"),
-                                 "--steps", "2", "--warmup", "1", "--kernel-events", mode)
+                                 "--steps", "2", "--warmup", "1", "--kernel-events", mode, "--full")
     ref = lines["all"]
     assert ref["config"]["blocks_per_rank"] > 8 and ref["graph_replay"] is None        # (not the small-volume graph path)
     assert ref["kernel_events"]["in_timed_region"] == "all" and lines["none"]["kernel_events"]["in_timed_region"] == "none"
@@ -152,6 +152,36 @@ def test_kernel_event_modes_of_the_bench_line(gpu, tmp_path):
         assert set(line["kernels"]) == set(ref["kernels"]), mode
         for fam, rec in line["kernels"].items():
             assert rec["launches_per_step"] == ref["kernels"][fam]["launches_per_step"] and rec["ms_per_step"] > 0, (mode, fam)
+
+
+def test_plain_line_dumps_the_last_steps_outputs(gpu, tmp_path):
+    """A plain ``bench.py`` run (no ``--full``) times exactly ``--steps`` steps, measures nothing beside them (no CPU
+    baseline, parity sample, sub-records or link rates) and with ``--dump-outputs`` writes the last step's table and
+    flags: the ``--dump`` table, and the same files from a second run of the same command."""
+    common = ("--config", "c5", "--shape", "56", "150", "160", "--segment-size", "64", "--steps", "3", "--warmup", "1")
+    lines = []
+    for k in range(2):
+        lines.append(_run_bench(tmp_path, 1, *common, "--dump", str(tmp_path / f"c5_{k}.npz"),
+                                "--dump-outputs", str(tmp_path / f"out{k}")))
+    line = lines[0]
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["step_ms_percentiles"]["max"] > 0
+    assert line["cpu_baseline"] is None and line["parity_sample_identical"] is None and "sub_records" not in line
+    assert line["h2d"] is None
+    dump = np.load(tmp_path / "c5_0.npz")
+    final, colocs = np.load(tmp_path / "out0" / "final.npy"), np.load(tmp_path / "out0" / "colocs.npy")
+    assert final.dtype == np.float64 and colocs.dtype == np.float32 and len(final) == line["blobs"] > 50
+    np.testing.assert_array_equal(final, dump["final"])
+    np.testing.assert_array_equal(colocs, dump["colocs"].astype(np.float32))
+    assert sorted(os.listdir(tmp_path / "out1")) == ["colocs.npy", "final.npy"]
+    for name in ("final.npy", "colocs.npy"):
+        np.testing.assert_array_equal(np.load(tmp_path / "out1" / name), np.load(tmp_path / "out0" / name))
+    # a volume of one block replays its batch from a captured graph: no kernel events in the timed region, and a plain
+    # line takes no extra steps to time the kernels
+    small = _run_bench(tmp_path, 1, "--config", "c2", "--shape", "64", "128", "128", "--steps", "3", "--warmup", "3",
+                       "--dump-outputs", str(tmp_path / "c2"))
+    assert small["steps"] == 3 and small["kernel_events"]["in_timed_region"] == "none" and small["kernels"] == {}
+    assert small["roofline"] is None and small["pipeline_roofline"]["frac_kernels"] is None
+    assert len(np.load(tmp_path / "c2" / "final.npy")) == small["blobs"]
 
 
 @pytest.mark.parametrize("ranks", [2, 3])
@@ -230,7 +260,7 @@ def test_full_size_c3_volume_properties_and_digest(gpu, tmp_path):
     """BASELINE.json configs[2] at FULL size (2048 x 2048 x 1024, 256 blocks, 5 sigmas) through ``bench.py``: too
     large for the float64 oracle, so the result is pinned by what does not depend on size -- the digest of the final
     table (the same for every kernel path, batch size and rank count since it was first recorded, and equal to the
-    oracle on the sample ``bench.py`` checks at every run), and properties of a correctly pruned table."""
+    oracle on the sample ``bench.py --full`` checks at every run), and properties of a correctly pruned table."""
     from magellanmapper_amd import detector
     line = _run_bench(tmp_path, 1, "--dump", str(tmp_path / "c3.npz"), timeout=1200)
     assert line["config"]["blocks_per_rank"] == 256 and line["n_gpus"] == 1
@@ -267,7 +297,8 @@ def test_tiled_stack_sharded_by_tile_is_a_weak_scaling_line(gpu, tmp_path):
     per-rank tile times, and the parity sample (rank 0, by itself) equals the oracle run in that process."""
     args = ("--config", "c5", "--shape", "56", "150", "160", "--segment-size", "64", "--cpu-cores", "4")
     env = dict(os.environ, MMX_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", *args, "--tiles", "4"],
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", *args, "--tiles", "4",
+                          "--full"],
                          capture_output=True, text=True, timeout=900, env=env, cwd=str(tmp_path))
     assert run.returncode == 0, run.stderr[-3000:]
     one = json.loads([l for l in run.stdout.splitlines() if l.startswith("{")][-1])

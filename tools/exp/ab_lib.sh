@@ -6,7 +6,7 @@ OLD=$PWD/magellanmapper_amd/libmmx_old.so
 for rep in 1 2; do
   for lib in old new; do
     if [ $lib = old ]; then export MMX_LIB_PATH=$OLD; else unset MMX_LIB_PATH; fi
-    python bench.py --no-cpu-baseline 2>/dev/null | python -c "
+    python bench.py --full --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

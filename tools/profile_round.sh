@@ -8,8 +8,8 @@ out=gpurun_out/prof_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 # the driver's command (c3 with the compact c2 / c5 sub-records and the CPU baselines), then the configs on their own
-timeout 900 python bench.py --steps 10 --warmup 3 > $out/bench_default.json 2> $out/bench_default.err
-timeout 300 python bench.py --config c2 --steps 40 --warmup 5 --no-cpu-baseline > $out/bench_c2.json 2> $out/bench_c2.err
+timeout 900 python bench.py --steps 10 --warmup 3 --full > $out/bench_default.json 2> $out/bench_default.err
+timeout 300 python bench.py --config c2 --steps 40 --warmup 5 --no-cpu-baseline --full > $out/bench_c2.json 2> $out/bench_c2.err
 timeout 600 python bench.py --config c5 --steps 3 --warmup 1 --no-cpu-baseline > $out/bench_c5.json 2> $out/bench_c5.err
 timeout 600 python bench.py --denoise 25 --steps 4 --warmup 1 --no-cpu-baseline > $out/bench_denoise25.json 2> $out/bench_denoise25.err
 timeout 600 python bench.py --config c5 --tiles 2 --steps 4 --warmup 1 --parity-sample tests/golden/bench_sample_c5.npz > $out/bench_c5_tiles2.json 2> $out/bench_c5_tiles2.err
