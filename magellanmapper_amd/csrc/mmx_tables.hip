@@ -734,8 +734,8 @@ extern "C" int mmx_calib_stream(int kind, const void* d_in, void* d_out, int64_t
 // ------------------------------------------------------------------------------------------------ cdist
 // Euclidean distance matrix of two small point sets (blobs of two channels in one ROI), float64, as
 // scipy.spatial.distance.cdist computes it: s = 0; for k: d = a[k] - b[k]; s += d * d; sqrt(s) -- this file is
-// compiled with -ffp-contract=off, so no FMA changes a bit.  One lane per (row, column) pair; rows of `b` go
-// through LDS (every lane of a row block reads all of them).
+// compiled with -ffp-contract=off, so no FMA changes a bit.  One lane per (row, column) pair, both rows read from
+// global memory: row i of `a` is the same for the whole workgroup (grid.y), row j of `b` is the lane's own.
 __global__ void __launch_bounds__(MMX_WG)
 cdist_kernel(const double* __restrict__ a, int64_t n, const double* __restrict__ b, int64_t m, int dim,
              double* __restrict__ out)
