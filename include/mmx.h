@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MMX_ABI_VERSION 16
+#define MMX_ABI_VERSION 17
 
 typedef enum {
     MMX_OK = 0,
@@ -512,6 +512,31 @@ int mmx_gauss_axis_batch(const mmx_volume* vol, const mmx_block* d_blocks, const
                          int n_blocks, int axis, const double* d_weights, const int32_t* d_radius,
                          int w_pitch, int nearest, int64_t dst_slot, int64_t dst_sy, int64_t dst_sz,
                          void* d_out, void* stream);
+
+/* ---- B1: exact order statistics of z-ranges of one channel (ABI v17)
+ * replaces: the sort behind `np.percentile(plane, (0.5, 99.5))` of the reference's import loop and of
+ * importer.calc_intensity_bounds (magmap/io/importer.py:1367-1377, 1415-1444), which measure config.near_min /
+ * config.near_max: the host assembles each percentile from the two order statistics either side of its virtual
+ * index, as NumPy does.
+ * A *group* is the voxels of planes [z0, z1) of the (nz, ny, nx) channel and four 0-based ranks into their sorted
+ * order (prev / next of the lower and of the upper percentile; ranks may coincide).  Per-plane bounds are nz groups of
+ * one plane, whole-image bounds one group.
+ *   vol      : any mmx_dtype, any strides (a (z, y, x, c) image passes stride_x = n_channels)
+ *   d_groups / h_groups : the table on the device and on the host (validation, launch geometry)
+ *   d_stats  : out [n_groups][4] float64, the voxel VALUES at those ranks (exact for every voxel type); floats sort as
+ *              np.sort sorts them (-0.0 and 0.0 count as equal, every NaN last)
+ *   d_nan    : out [n_groups], 1 when the group holds a NaN (float voxels)
+ *   d_work   : mmx_order_stats_workspace(n_groups) bytes, 16-byte aligned
+ * MMX_ERR_ARG (nothing written) for an empty group, a z-range outside the volume or a rank outside
+ * [0, voxels of the group); MMX_ERR_WORKSPACE for a short workspace.  Most-significant-byte-first radix select, one
+ * streaming pass over the groups' voxels per key byte (1 for uint8, 2 for uint16, 4 for float32, 8 for float64), all
+ * queued on `stream` without a host round trip; counts are 64-bit (a group may exceed 2^32 voxels). */
+typedef struct { int32_t z0, z1; int64_t rank[4]; } mmx_rank_group;   /* 40 bytes */
+size_t mmx_order_stats_workspace(int n_groups);
+int mmx_order_stats(const mmx_volume* vol, int64_t nz, int64_t ny, int64_t nx,
+                    const mmx_rank_group* d_groups, const mmx_rank_group* h_groups, int n_groups,
+                    double* d_stats /*[n_groups][4]*/, int32_t* d_nan /*[n_groups]*/,
+                    void* d_work, size_t work_bytes, void* stream);
 
 /* ---- measurement helpers (bench.py): HIP-event timing on the caller's stream.
  * mmx_timing_enable(1) makes every kernel launch of this library record a HIP event

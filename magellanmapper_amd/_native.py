@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 #: ``MMX_LIB_PATH`` selects an experimental build of the same ABI (kernel tuning only)
 LIB_PATH = os.environ.get("MMX_LIB_PATH") or os.path.join(_HERE, "libmmx_hip.so")
 
-MMX_ABI_VERSION = 16
+MMX_ABI_VERSION = 17
 MMX_U8, MMX_U16, MMX_F32, MMX_F64 = 0, 1, 2, 3
 MMX_MAX_RADIUS_FAST = 24
 MMX_MAX_RADIUS_GENERIC = 255
@@ -56,6 +56,9 @@ RESIZE_DTYPE = np.dtype([("src_off", "<i8"), ("in_nz", "<i4"), ("in_ny", "<i4"),
                          ("out_nz", "<i4"), ("out_ny", "<i4"), ("out_nx", "<i4"), ("slot", "<i4"),
                          ("tz", "<i4"), ("ty", "<i4"), ("tx", "<i4")], align=True)
 assert RESIZE_DTYPE.itemsize == 48
+#: NumPy mirror of ``mmx_rank_group`` (40 bytes): planes ``[z0, z1)`` and four 0-based ranks into their sorted voxels
+RANK_GROUP_DTYPE = np.dtype([("z0", "<i4"), ("z1", "<i4"), ("rank", "<i8", (4,))], align=True)
+assert RANK_GROUP_DTYPE.itemsize == 40
 
 
 class Volume(Structure):
@@ -131,6 +134,7 @@ SYMBOLS = (
     "mmx_coloc_means", "mmx_coloc_voxels", "mmx_host_take_rows", "mmx_host_map_columns", "mmx_resize_batch_as", "mmx_gauss_axis_batch", "mmx_unmix_batch", "mmx_minmax_batch", "mmx_resize_batch",
     "mmx_cdist_f64", "mmx_host_lsap", "mmx_expand_probes", "mmx_host_resolve_peaks", "mmx_host_overlap_prune",
     "mmx_host_emit_tables", "mmx_host_prune_region", "mmx_host_prune_parts", "mmx_host_rows_in_boxes", "mmx_host_append_rows", "mmx_host_emit_survivors", "mmx_host_merge_by_key", "mmx_host_merge_parts_by_key", "mmx_host_gather_by_key", "mmx_host_take_rows_final", "mmx_host_emit_survivors_final", "mmx_host_emit_parts_final", "mmx_host_gather_parts_by_key_final", "mmx_host_take_rows_split", "mmx_host_gather_parts_by_key_split", "mmx_host_emit_tables_multi", "mmx_host_coloc_flags", "mmx_host_finish_stack", "mmx_copy_rect_h2d", "mmx_host_stage_upload", "mmx_event_query",
+    "mmx_order_stats_workspace", "mmx_order_stats",
 )
 KERNEL_KINDS = ("zpass", "ypass", "xpass", "generic", "peaks", "rescore", "overlap_pairs",
                 "close_pairs", "zxpass", "y2pass", "preproc", "coloc", "zxpack")
@@ -262,12 +266,17 @@ def lib() -> ctypes.CDLL:
                                                      c_int32, vp, c_int64, c_int32, vp]
     L.mmx_host_emit_tables.argtypes = [vp, vp, vp, c_int, vp, c_int, c_double, vp, vp, vp, vp, c_int64, vp, vp, vp,
                                        c_int64, c_int64, vp]
+    L.mmx_order_stats_workspace.argtypes = [c_int]
+    L.mmx_order_stats_workspace.restype = ctypes.c_size_t
+    L.mmx_order_stats.argtypes = [POINTER(Volume), c_int64, c_int64, c_int64, vp, vp, c_int, vp, vp, vp, ctypes.c_size_t, vp]
+    L.mmx_order_stats.restype = c_int
     L.mmx_preprocess_batch.restype = c_int
     L.mmx_preprocess_batch_mode.restype = c_int
     L.mmx_preprocess_batch_generic.restype = c_int
     for name in SYMBOLS:
         fn = getattr(L, name)
-        if name in ("mmx_preprocess_fast_lds", "mmx_workspace_bytes", "mmx_preprocess_work_bytes"):
+        if name in ("mmx_preprocess_fast_lds", "mmx_workspace_bytes", "mmx_preprocess_work_bytes",
+                    "mmx_order_stats_workspace"):
             continue
         if fn.restype is None or name.startswith(("mmx_log", "mmx_peaks", "mmx_rescore",
                                                   "mmx_overlap", "mmx_close", "mmx_event", "mmx_timing", "mmx_calib", "mmx_host")):

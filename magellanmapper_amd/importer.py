@@ -12,6 +12,10 @@ goes through before ``stack_detect.detect_blobs_stack`` (reference magmap/io/imp
   ``zoom``, ``near_min`` and ``near_max`` into :mod:`config`, which is where the detection path and
   the preprocessing read them.
 
+* :func:`measure_near_bounds` / :func:`calc_intensity_bounds` / :func:`calc_near_intensity_bounds` (:1367-1377,
+  1415-1468) measure ``near_min`` / ``near_max`` of an image that carries no metadata, the order statistics on the
+  device.
+
 Importing from TIFF / Bio-Formats, metadata version upgrades and ROI loading stay in the reference.
 The device side: :class:`blob_log.DeviceVolume` uploads a memory-mapped image plane block by plane
 block through a pinned staging buffer, so the host never holds a second copy of the stack.
@@ -160,3 +164,202 @@ def read_file(filename: str, series: Optional[int] = None, offset=None, size=Non
     except OSError as err:
         _logger.warning("Could not load image files for %s: %s", filename, err)
     return img5d
+
+
+# ---- near_min / near_max: the intensity bounds of the WHOLE image that the preprocessing's contrast stretch reads
+# (config.near_max[chl] * max_thresh_factor, reference plot_3d.py:98-100).  The reference measures them while it
+# imports a stack -- np.percentile of every plane, the smallest low and the largest high per channel
+# (importer.py:1367-1377) -- or when it upgrades old metadata (:572-585, calc_intensity_bounds +
+# calc_near_intensity_bounds).  Here the order statistics come from the device (DeviceVolume.order_stats) and the
+# percentile is assembled from them on the host in NumPy's arithmetic.
+
+#: z-chunk size (bytes) of a host image that `measure_near_bounds` walks in pieces; ``None``: a third of the device
+#: memory free at the call, and no chunking at all for an image below that
+BOUNDS_CHUNK_BYTES = None
+
+_BOUNDS_DTYPES = (np.dtype(np.uint8), np.dtype(np.uint16), np.dtype(np.float64))
+
+
+def percentile_from_order_stats(a_prev, a_next, gamma, dtype):
+    """``np.percentile(a, pct)`` (method "linear") from ``sorted(a)[prev]``, ``sorted(a)[next]`` and ``gamma`` of
+    :func:`preprocess.quantile_ranks`, in float64, as NumPy's ``_lerp`` assembles it
+    (numpy/lib/_function_base_impl.py): ``a + (b - a) * g``, replaced by ``b - (b - a) * (1 - g)`` where
+    ``g >= 0.5``, with ``b - a`` taken in the input type.  Scalars or arrays; returns float64."""
+    dtype = np.dtype(dtype)
+    if dtype not in _BOUNDS_DTYPES:
+        raise NotImplementedError(f"percentiles of {dtype} images (uint8, uint16 and float64 are supported)")
+    a = np.asarray(a_prev).astype(dtype)
+    b = np.asarray(a_next).astype(dtype)
+    g = np.asarray(gamma, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        diff = np.subtract(b, a)
+        out = np.add(a, diff * g, dtype=np.float64)
+        alt = np.subtract(b, diff * (1 - g), dtype=np.float64)
+    out = np.where(g >= 0.5, alt, out)
+    return out[()] if out.ndim == 0 else out
+
+
+def _bounds_ranks(n: int, lower, upper):
+    from .preprocess import quantile_ranks
+    lo_prev, lo_next, lo_g = quantile_ranks(n, lower)
+    hi_prev, hi_next, hi_g = quantile_ranks(n, upper)
+    return np.array([lo_prev, lo_next, hi_prev, hi_next], dtype=np.int64), lo_g, hi_g
+
+
+def _percentiles_of_groups(dv, channel: int, groups, lower, upper):
+    """``np.percentile(group, (lower, upper))`` of z-ranges of one channel of a device volume: ``(lows, highs)``."""
+    if dv.np_dtype not in _BOUNDS_DTYPES:
+        raise NotImplementedError(f"percentiles of {dv.np_dtype} images (uint8, uint16 and float64 are supported)")
+    plane = int(dv.shape[1]) * int(dv.shape[2])
+    ranks, gammas = [], []
+    for z0, z1 in groups:
+        rk, lo_g, hi_g = _bounds_ranks((z1 - z0) * plane, lower, upper)
+        ranks.append(rk)
+        gammas.append((lo_g, hi_g))
+    stats, has_nan = dv.order_stats(channel, np.array(ranks, dtype=np.int64).reshape(-1, 4), groups)
+    gam = np.array(gammas, dtype=np.float64).reshape(-1, 2)
+    lows = percentile_from_order_stats(stats[:, 0], stats[:, 1], gam[:, 0], dv.np_dtype)
+    highs = percentile_from_order_stats(stats[:, 2], stats[:, 3], gam[:, 1], dv.np_dtype)
+    lows = np.where(has_nan, np.nan, lows)      # (NumPy: a slice that holds a NaN yields NaN)
+    highs = np.where(has_nan, np.nan, highs)
+    return lows, highs
+
+
+def _as_zyxc(arr, multichannel: bool):
+    """An image of any rank as ``(z, y, x[, c])`` without copying: the leading spatial axes are folded into z."""
+    spatial = arr.shape[:-1] if multichannel else arr.shape
+    if len(spatial) == 0:
+        raise ValueError("image without spatial axes")
+    lead = int(np.prod(spatial[:-2], dtype=np.int64)) if len(spatial) > 2 else 1
+    zyx = (lead, spatial[-2] if len(spatial) > 1 else 1, spatial[-1])
+    return arr.reshape(zyx + ((arr.shape[-1],) if multichannel else ()))
+
+
+def _free_device_bytes() -> int:
+    import torch
+    return int(torch.cuda.mem_get_info()[0])
+
+
+def calc_intensity_bounds(image5d, lower=0.5, upper=99.5, dim_channel=4):
+    """Percentiles of each channel over the WHOLE image (importer.py:1415-1444): ``(lows, highs)``, one entry per
+    channel.  The image -- a NumPy array, a memory map or a ``DeviceVolume`` -- is multichannel when it has more than
+    ``dim_channel`` axes (the channel is the last one), as ``plot_3d.setup_channels`` decides it.  One order-statistics
+    group spans the image, so it has to fit the device: ``ValueError`` otherwise (per-plane bounds,
+    :func:`measure_near_bounds`, walk an image of any size)."""
+    from .volume import DeviceVolume
+    if isinstance(image5d, DeviceVolume):
+        dv = image5d
+        multichannel = dv.multichannel
+    else:
+        arr = image5d if isinstance(image5d, np.ndarray) else np.asarray(image5d)
+        multichannel = arr.ndim > dim_channel
+        if arr.dtype not in _BOUNDS_DTYPES:
+            raise NotImplementedError(f"percentiles of {arr.dtype} images (uint8, uint16 and float64 are supported)")
+        if arr.size == 0:
+            raise ValueError("empty image")
+        if arr.nbytes > 0.9 * _free_device_bytes():
+            raise ValueError(
+                f"whole-image bounds need the image on the device at once: {arr.nbytes} bytes do not fit "
+                f"({_free_device_bytes()} free); measure_near_bounds walks a larger image plane by plane")
+        dv = DeviceVolume(_as_zyxc(arr, multichannel), streamed=False)
+    z0 = dv.z_off
+    group = [(z0, z0 + int(dv.tensor.shape[0]))]
+    lows, highs = [], []
+    for c in range(dv.n_channels):
+        lo, hi = _percentiles_of_groups(dv, c, group, lower, upper)
+        lows.append(lo[0])
+        highs.append(hi[0])
+    return lows, highs
+
+
+def calc_near_intensity_bounds(near_mins, near_maxs, lows, highs):
+    """Near min / max from lists of per-plane ``lows`` / ``highs`` (importer.py:1447-1468; no device): with one
+    channel the extremes are APPENDED to the lists given, with several the per-channel minima / maxima come back as
+    new arrays."""
+    if lows:
+        if len(lows[0]) <= 1:
+            near_mins.append(min(lows)[0])
+            near_maxs.append(max(highs)[0])
+        else:
+            near_mins = np.amin(np.array(lows), 0)
+            near_maxs = np.amax(np.array(highs), 0)
+    return near_mins, near_maxs
+
+
+def measure_near_bounds(img, lower=0.5, upper=99.5, assign=False):
+    """``(near_min, near_max)``, one entry per channel, as the reference's import loop measures them
+    (importer.py:1367-1377): ``np.percentile(plane, (lower, upper))`` of every z-plane, the smallest low and the
+    largest high per channel.
+
+    ``img``: a ``(z, y, x[, c])`` array, memory map or ``DeviceVolume``, a ``(t, z, y, x, c)`` array, or an
+    ``Image5d`` (``(t, z, y, x[, c])``); of a time series the first time point is measured, as the reference does.
+    A bare four-axis array is read as ``(z, y, x, c)``, like everywhere in this package: a single-channel
+    ``(t, z, y, x)`` array goes in as ``Image5d(arr)`` or ``arr[0]``.
+    A host image larger than the device (or than ``BOUNDS_CHUNK_BYTES``) is walked in z-chunks of whole planes, the
+    next chunk on its way up while the current one is counted.  ``assign``: also store the result in
+    ``config.near_min`` / ``config.near_max`` -- what a caller does before ``detect_blobs_stack`` when the image carries
+    no reference metadata."""
+    from .volume import DeviceVolume
+    if isinstance(img, Image5d):
+        arr = img.img
+        if arr is None:
+            raise ValueError("Image5d without an image")
+        if arr.ndim not in (4, 5):
+            raise ValueError("an Image5d holds (t, z, y, x[, c])")
+        arr = arr[0]
+    elif isinstance(img, DeviceVolume):
+        arr = img
+    else:
+        arr = img if isinstance(img, np.ndarray) else np.asarray(img)
+        if arr.ndim == 5:
+            arr = arr[0]
+        if arr.ndim not in (3, 4):
+            raise ValueError("image must be (z, y, x[, c]) or (t, z, y, x, c)")
+
+    lows, highs = None, None
+
+    def measure(dv):
+        z0 = dv.z_off
+        groups = [(z, z + 1) for z in range(z0, z0 + int(dv.tensor.shape[0]))]
+        for c in range(dv.n_channels):
+            lo, hi = _percentiles_of_groups(dv, c, groups, lower, upper)
+            lows[c].extend(lo)
+            highs[c].extend(hi)
+
+    if isinstance(arr, DeviceVolume):
+        lows, highs = [[] for _ in range(arr.n_channels)], [[] for _ in range(arr.n_channels)]
+        measure(arr)
+    else:
+        if arr.dtype not in _BOUNDS_DTYPES:
+            raise NotImplementedError(f"percentiles of {arr.dtype} images (uint8, uint16 and float64 are supported)")
+        if arr.size == 0:
+            raise ValueError("empty image")
+        n_chl = arr.shape[3] if arr.ndim == 4 else 1
+        lows, highs = [[] for _ in range(n_chl)], [[] for _ in range(n_chl)]
+        nz = arr.shape[0]
+        limit = BOUNDS_CHUNK_BYTES if BOUNDS_CHUNK_BYTES is not None else _free_device_bytes() // 3
+        plane_bytes = max(1, arr.nbytes // nz)
+        step = nz if arr.nbytes <= limit else max(1, int(limit // plane_bytes))
+        starts = list(range(0, nz, step))
+
+        def upload(z0):
+            return DeviceVolume(arr[z0:min(z0 + step, nz)], streamed=len(starts) > 1 or None, z_off=z0,
+                                full_shape=arr.shape[:3])
+
+        nxt = upload(starts[0])
+        for k in range(len(starts)):
+            cur, nxt = nxt, (upload(starts[k + 1]) if k + 1 < len(starts) else None)
+            try:
+                measure(cur)
+            except BaseException:
+                if nxt is not None:
+                    nxt.close()
+                raise
+            finally:
+                cur.close()
+    near_min = [min(v) for v in lows]
+    near_max = [max(v) for v in highs]
+    if assign:
+        config.near_min = near_min
+        config.near_max = near_max
+    return near_min, near_max

@@ -223,6 +223,48 @@ class DeviceVolume:
         ptr -= self.z_off * int(sz) * t.element_size()        # (plane z of the whole volume is plane z - z_off here)
         return nat.Volume(ptr, code, 0, int(sz), int(sy), int(sx))
 
+    def order_stats(self, channel: int, ranks, groups=None) -> Tuple[np.ndarray, np.ndarray]:
+        """Exact order statistics of z-ranges of one channel (``mmx_order_stats``: radix select on the device).
+
+        ``groups``: ``(z0, z1)`` plane ranges in the coordinates of the whole volume; ``None``: every plane this object
+        holds as a group of its own.  ``ranks``: four 0-based ranks into the sorted voxels of a group -- ``(4,)`` for
+        every group alike or ``(G, 4)``.  Returns ``(stats, has_nan)``: the ``(G, 4)`` float64 voxel values at those
+        ranks (exact for every voxel type; floats in ``np.sort``'s order) and per group whether it holds a NaN.
+        Waits for the planes it touches when the image is still on its way up, and synchronises once at the end."""
+        nz_held = int(self.tensor.shape[0])
+        ny, nx = int(self.shape[1]), int(self.shape[2])
+        if not 0 <= int(channel) < self.n_channels:
+            raise ValueError(f"channel {channel} of an image with {self.n_channels}")
+        if groups is None:
+            groups = [(z, z + 1) for z in range(self.z_off, self.z_off + nz_held)]
+        table = np.zeros(len(groups), dtype=nat.RANK_GROUP_DTYPE)
+        if len(table) == 0:
+            return np.empty((0, 4)), np.empty(0, dtype=bool)
+        zr = np.asarray(groups, dtype=np.int64).reshape(-1, 2)
+        if np.any(zr[:, 0] < self.z_off) or np.any(zr[:, 1] > self.z_off + nz_held) or np.any(zr[:, 1] <= zr[:, 0]):
+            raise ValueError(f"groups must be non-empty plane ranges within [{self.z_off}, {self.z_off + nz_held})")
+        rk = np.asarray(ranks)
+        if rk.dtype.kind not in "iu" or rk.shape not in ((4,), (len(table), 4)):
+            raise ValueError("ranks must be four integers, or four per group")
+        rk = np.broadcast_to(rk.astype(np.int64), (len(table), 4))
+        if np.any(rk < 0) or np.any(rk >= ((zr[:, 1] - zr[:, 0]) * ny * nx)[:, None]):
+            raise ValueError("a rank lies outside [0, voxels of its group)")
+        table["z0"], table["z1"], table["rank"] = zr[:, 0], zr[:, 1], rk
+        dev = self.tensor.device
+        L = nat.lib()
+        self.stream_wait(boxes=[(int(a), int(b), 0, ny) for a, b in zr])
+        vol = self.view(channel, False)
+        d_groups = torch.from_numpy(table.view(np.uint8).reshape(-1)).to(dev)
+        d_stats = torch.empty((len(table), 4), dtype=torch.float64, device=dev)
+        d_nan = torch.empty(len(table), dtype=torch.int32, device=dev)
+        work_bytes = int(L.mmx_order_stats_workspace(len(table)))
+        d_work = torch.empty(work_bytes, dtype=torch.uint8, device=dev)
+        nat.check(L.mmx_order_stats(vol, int(self.shape[0]), ny, nx, d_groups.data_ptr(), table.ctypes.data, len(table),
+                                    d_stats.data_ptr(), d_nan.data_ptr(), d_work.data_ptr(), work_bytes,
+                                    torch.cuda.current_stream(dev).cuda_stream), "mmx_order_stats")
+        stats = d_stats.cpu().numpy()           # (the one synchronisation)
+        return stats, d_nan.cpu().numpy() != 0
+
 
 #: host images above this size go to the device z-slab by z-slab on a copy stream (`_SlabUpload`) when the caller allows
 #: it (`DeviceVolume(streamed=...)`); 0 / False keeps the one synchronous copy (tests compare the two)
