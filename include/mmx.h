@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MMX_ABI_VERSION 17
+#define MMX_ABI_VERSION 18
 
 typedef enum {
     MMX_OK = 0,
@@ -140,9 +140,8 @@ int mmx_device_count(void);
  *                measurements.  Float voxels take the tiled path when the volume states its value range
  *                (mmx_volume.value_range) or when MMX_ZX_TILED is asked for by name: its copy holds every voxel as
  *                two float16 pieces (22 significant bits, like the weights), which covers |v| < 65504.  All agree within float32 rounding, and the peak decisions are taken on exact
- *                float64 values either way (mmx_rescore_f64).  With entries requested and nms_eps at least four times
- *                mmx_tiled_q16_error_bound(), AUTO hands the intermediates over as 16-bit fixed point
- *                (MMX_ZX_TILED_Q16).  MMX_ZX_TILED works from an operand-ordered copy of
+ *                float64 values either way (mmx_rescore_f64).  When AUTO hands the intermediates over as 16-bit fixed
+ *                point (MMX_ZX_TILED_Q16): MMX_LOG_ABS_TOL below.  MMX_ZX_TILED works from an operand-ordered copy of
  *                the blocks' voxels inside d_work, which does not depend on sigma: mmx_zx_pack makes it once per
  *                batch, and MMX_ZX_TILED | MMX_ZX_PREPACKED then skips making it again for every sigma.
  *   h_zx_path  : optional out (host): the MMX_ZX_* kernel this call actually ran (MMX_ZX_SEPARATE when the
@@ -156,8 +155,7 @@ typedef enum {
     MMX_ZX_TILED = 6,     /* zx4's arithmetic on an operand-ordered copy of the voxels (zx6_pack_kernel), P / Q
                              handed to the Y pass (y6_kernel) as 16 x 16 tiles: every access one contiguous KiB */
     MMX_ZX_TILED_Q16 = 7  /* the same with the tiles as 16-bit fixed point (half the intermediate bytes): the LoG
-                             values carry a rounding error of at most mmx_tiled_q16_error_bound(); AUTO picks it
-                             only when entries are asked for with nms_eps >= 4 x that bound                     */
+                             values carry a rounding error of at most mmx_tiled_q16_error_bound()               */
 } mmx_zx_mode;
 #define MMX_ZX_PREPACKED 0x100   /* or-ed into MMX_ZX_TILED / MMX_ZX_TILED_Q16: mmx_zx_pack ran on this d_work for these blocks */
 #define MMX_ZX_Y_VALU    0x200   /* or-ed into MMX_ZX_TILED_Q16 (any zx_mode >= 0 accepts it): the Y pass of the 16-bit tiles on the
@@ -171,9 +169,9 @@ int mmx_log_batch_f32(const mmx_volume* vol, const mmx_block* d_blocks, const mm
                       int* h_mask_written, int zx_mode, int* h_zx_path, void* stream);
 
 /* The LoG contract: nominated (float32 / 16-bit) cube values stay within this ABSOLUTE distance of the reference's
- * float64 values.  Under MMX_ZX_AUTO 16-bit intermediates are chosen only when their error bound in value units
- * (mmx_tiled_q16_error_bound x the stated value range) is below it AND the caller's NMS band covers it fourfold;
- * MMX_ZX_TILED_Q16 by name takes them regardless (tests, experiments). */
+ * float64 values.  Under MMX_ZX_AUTO 16-bit intermediates are chosen only when entries are asked for, their error bound
+ * in value units (mmx_tiled_q16_error_bound x the stated value range) is below it AND the caller's NMS band (nms_eps)
+ * covers it fourfold; MMX_ZX_TILED_Q16 by name takes them regardless (tests, experiments). */
 #define MMX_LOG_ABS_TOL 1e-4
 
 /* Largest deviation of an MMX_ZX_TILED_Q16 LoG value from the float32 paths' (which are within a few 1e-7 of the
@@ -296,6 +294,22 @@ typedef struct {
 } mmx_detect_info;
 int mmx_detect_batch(const mmx_detect_args* args, mmx_detect_info* info);
 const char* mmx_detect_last_error(void);
+/* The first half of mmx_detect_batch as an entry of its own: the voxel copy and every scale, no tail.  Reads stream,
+ * pack_stream, ev_work_free, vol32, the blocks, the host scale tables, d_work / work_bytes, thr, eps, zx_mode and
+ * zx_flags; ignores the tail's fields (d_cands, d_count, cap, vol_exact, the device tables, tail_stream, the other
+ * events).  Leaves d_log at d_work + 4 n_blocks slot_elems floats and the entries behind it (mmx_workspace_bytes'
+ * layout) and fills `info` as mmx_detect_batch does: pass info->mask_layout on to mmx_peaks_batch.
+ * THE RULES by which a batch takes its kernel path (this function is their one statement in code):
+ *   - per scale: the tiled matrix-core path, else the packed-VALU kernel, else the three separate passes -- zx_mode
+ *     and the geometry decide, as for mmx_log_batch_f32;
+ *   - float32 or 16-bit tiles: MMX_LOG_ABS_TOL's rule with the largest mmx_tiled_q16_error_bound over the scales;
+ *   - the voxel copy of the tiled path is made once per round and trusted (MMX_ZX_PREPACKED) only while every scale
+ *     so far ran the tiled path: any other path uses that part of d_work for something else;
+ *   - with entries the Y pass leaves whole segments of the cube unwritten, so it is all scales in one entry layout or
+ *     none: when the scales disagree (a radius outside the fused kernels, tiny blocks) every scale is computed again
+ *     -- with MMX_ZX_PACKED when the layouts were rows and quads mixed, then without entries if they still differ
+ *     (info->n_pass_rounds: 1 to 3). */
+int mmx_log_scales_f32(const mmx_detect_args* args, mmx_detect_info* info);
 /* the same launches captured as a hipGraph (every argument frozen; refused with MMX_ERR_UNSUPPORTED while per-kernel
  * timing is on: its events cannot live inside a capture) and replayed with one launch on `stream` */
 int mmx_detect_batch_capture(const mmx_detect_args* args, mmx_detect_info* info, void** graph);

@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 #: ``MMX_LIB_PATH`` selects an experimental build of the same ABI (kernel tuning only)
 LIB_PATH = os.environ.get("MMX_LIB_PATH") or os.path.join(_HERE, "libmmx_hip.so")
 
-MMX_ABI_VERSION = 17
+MMX_ABI_VERSION = 18
 MMX_U8, MMX_U16, MMX_F32, MMX_F64 = 0, 1, 2, 3
 MMX_MAX_RADIUS_FAST = 24
 MMX_MAX_RADIUS_GENERIC = 255
@@ -124,7 +124,7 @@ _lib = None
 #: every symbol ``include/mmx.h`` declares
 SYMBOLS = (
     "mmx_abi_version", "mmx_strerror", "mmx_last_hip_error", "mmx_device_count",
-    "mmx_detect_batch", "mmx_detect_batch_capture", "mmx_graph_launch", "mmx_graph_destroy", "mmx_detect_last_error",
+    "mmx_detect_batch", "mmx_log_scales_f32", "mmx_detect_batch_capture", "mmx_graph_launch", "mmx_graph_destroy", "mmx_detect_last_error",
     "mmx_event_synchronize", "mmx_stream_wait_event", "mmx_timing_is_enabled",
     "mmx_log_batch_f32", "mmx_log_batch_f32_generic", "mmx_zx_pack", "mmx_tiled_q16_error_bound", "mmx_workspace_bytes", "mmx_peaks_batch", "mmx_rescore_f64",
     "mmx_overlap_pairs", "mmx_close_pairs", "mmx_event_create", "mmx_event_destroy",
@@ -181,6 +181,7 @@ def lib() -> ctypes.CDLL:
     L.mmx_overlap_pairs.argtypes = [vp, vp, c_int, c_double, c_double, c_double, vp, vp, c_uint32, vp, vp]
     L.mmx_close_pairs.argtypes = [vp, c_int, vp, c_int, POINTER(c_int32), vp, vp, vp]
     L.mmx_detect_batch.argtypes = [POINTER(DetectArgs), POINTER(DetectInfo)]
+    L.mmx_log_scales_f32.argtypes = [POINTER(DetectArgs), POINTER(DetectInfo)]
     L.mmx_detect_batch_capture.argtypes = [POINTER(DetectArgs), POINTER(DetectInfo), POINTER(vp)]
     L.mmx_graph_launch.argtypes = [vp, vp, vp, POINTER(DetectInfo)]
     L.mmx_graph_destroy.argtypes = [vp]

@@ -63,8 +63,8 @@ if 0.0 < EPS_REL_Q16 < 4.0 * Q16_BOUND_ANY_SIGMA:
     raise ValueError(f"MMX_EPS_REL_Q16={EPS_REL_Q16:g} is narrower than 4 x the 16-bit intermediates' error bound "
                      f"({4.0 * Q16_BOUND_ANY_SIGMA:g}); use 0 to keep float32 intermediates")
 #: raw volumes on the native host path: one ``mmx_detect_batch`` call enqueues a whole batch (voxel copy, the passes of
-#: every scale, NMS, probes, exact re-score, copies) instead of a dozen calls from here (``False``: the call-by-call
-#: form, which tests keep as a cross-check)
+#: every scale, NMS, probes, exact re-score, copies); ``False``: the call-by-call form every other batch takes (the
+#: scales by ``mmx_log_scales_f32``, the tail call by call from here), which tests keep as a cross-check
 NATIVE_BATCH = True
 #: batches of at most this many blocks that come back with the very same arguments (a small volume detected step
 #: after step) are captured as a hipGraph and replayed with one launch (0: never)
@@ -714,7 +714,7 @@ def _enqueue_detect(dvol, channel, origins, shapes, space: ScaleSpace, thr: floa
             #  Letting the first batches' preprocessing start at once instead measured nothing on C3 --denoise 25
             #  and +10 ms on C5, round 5.)
             main = torch.cuda.current_stream()
-            bufs.pre_stream.wait_stream(main) if buffer_free is None else bufs.pre_stream.wait_event(buffer_free)
+            bufs.pre_stream.wait_stream(main) if buffer_free is None else _stream_wait(bufs.pre_stream, buffer_free)
             with torch.cuda.stream(bufs.pre_stream):
                 dvol.stream_wait(None, [torch.cuda.current_stream(), bufs.side], boxes)     # (side: co-localisation means)
                 blocks, slot, vol32, vol_exact = pre.run(dvol, channel, origins, shapes, which)
@@ -736,7 +736,6 @@ def _enqueue_detect(dvol, channel, origins, shapes, space: ScaleSpace, thr: floa
     nb, ns = len(blocks), len(space.sigmas)
     if slot >= (1 << 29):
         raise nat.MmxError("block too large for one workspace slot (>= 2^29 voxels)")
-    mask_words = (nb * slot) >> 5            # 16-byte entries per sigma (include/mmx.h: d_nms_mask)
     # raw volumes: the batches alternate between two workspaces, and everything after a batch's last LoG kernel -- NMS,
     # probe expansion, exact re-score, copies -- runs on a second stream beside the next batch's LoG kernels
     # (preprocessed batches too with PRE_SIDE_TAIL -- measured and left off; their two workspaces are sized by
@@ -747,152 +746,78 @@ def _enqueue_detect(dvol, channel, origins, shapes, space: ScaleSpace, thr: floa
     ws = bufs.workspace(-(-int(L.mmx_workspace_bytes(nb, slot, ns, 1)) // 4), ws_i)
     # ... and the voxel copy of the tiled path, the first kernel of a batch, on a third: it only needs the workspace
     pack_side = side_tail and PACK_STREAM and bufs.ws2 is not None
-    native_batch = bool(NATIVE_BATCH and pre is None and exact and HOST_PATH == "native")
-    if bufs.ws_free[ws_i] is not None and not native_batch:   # (also a batch that is nominated again, on the main stream: same workspace)
-        _stream_wait(bufs.pack_stream if pack_side else torch.cuda.current_stream(), bufs.ws_free[ws_i])
     if d_blocks is None:
         d_blocks = _to_device_bytes(blocks, dev)
     stream = _stream_ptr()
-    log_base = ws.data_ptr() + 4 * nb * slot * 4
-    # NMS pre-filter masks, [ns][nb][slot / 32] uint64: written by the Y pass of the fused path
-    mask_base = (log_base + ns * nb * slot * 4 + 15) & ~15
-    if native_batch:
-        # ---- the whole batch in one native call (mmx_detect_batch): voxel copy, every scale, NMS, probes, re-score, copies
-        global LAST_ZX_PATH, LAST_Q16_BOUND, LAST_NMS_BAND
-        is_float = vol32.dtype == nat.MMX_F32
-        if is_float:
-            float_ok = vrange is not None and max(abs(vrange[0]), abs(vrange[1])) <= FLOAT_TILED_RANGE[1]
-            vol32.value_range = 0.0 if not float_ok else (max(vrange[1], 1e-30) if vrange[0] >= 0.0
-                                                          else -max(abs(vrange[0]), abs(vrange[1])))
-        n_vox = int(sum(int(np.prod(s)) for s in shapes))
-        if cap is None:
-            cap = max(4096, min(n_vox * ns, n_vox // 2000 * ns + 65536))
-        table = bufs.cand_table(which, cap)
-        count = bufs.counts[which]
-        ev_read, ev_done = bufs.events(which)
-        side = bufs.rescore_stream if side_tail else None
-        a = nat.DetectArgs()
-        a.vol32, a.vol_exact = ctypes.pointer(vol32), ctypes.pointer(vol_exact)
-        a.d_blocks, a.h_blocks = d_blocks.data_ptr(), blocks.ctypes.data
-        a.n_blocks, a.n_sigma, a.slot_elems = nb, ns, slot
-        a.h_w0, a.h_w2 = space.w0_tab.ctypes.data, space.w2_tab.ctypes.data
-        a.d_w0, a.d_w2 = d_w0.data_ptr(), d_w2.data_ptr()
-        a.h_radius, a.h_norm = space.radii.ctypes.data, space.norms.ctypes.data
-        a.d_work, a.work_bytes = ws.data_ptr(), ws.numel() * 4
-        a.thr, a.eps = thr, eps
-        a.d_cands, a.cap, a.d_count = table.data_ptr(), cap, count.data_ptr()
-        a.h_count = bufs.host_counts[which].data_ptr()
-        a.h_cands, a.h_prefix = bufs.host_table(which).data_ptr(), min(cap, _PREFIX_ENTRIES)
-        a.zx_mode, a.zx_flags, a.store_f32, a.exact, a.expand = ZX_MODE, ZX_FLAGS, store_f32, 1, 1
-        a.stream = stream
-        a.tail_stream = side.cuda_stream if side is not None else stream
-        a.pack_stream = bufs.pack_stream.cuda_stream if pack_side else stream
-        prev = bufs.ws_free[ws_i]
-        if prev is not None and not isinstance(prev, _NativeEvent):     # (left by the call-by-call form)
-            _stream_wait(bufs.pack_stream if pack_side else torch.cuda.current_stream(), prev)
-            prev = None
-        a.ev_work_free = prev.handle if prev is not None else None
-        a.ev_work_read = ev_read.handle if side_tail else None
-        a.ev_done = ev_done.handle
-        info = nat.DetectInfo()
-        rc = _launch_batch(L, a, info, bufs, nb, blocks, space, vol32, vol_exact)
-        if rc != 0:
-            detail = L.mmx_detect_last_error().decode()
-            nat.check(rc, "mmx_detect_batch" + (f" [{detail}]" if detail and rc == 2 else ""))
-        LAST_ZX_PATH = info.zx_path
-        if info.zx_path == nat.MMX_ZX_TILED_Q16:
-            LAST_Q16_BOUND, LAST_NMS_BAND = info.q16_bound, eps
-        if side_tail:
-            bufs.ws_free[ws_i] = ev_read
-        return dict(blocks=blocks, d_blocks=d_blocks, shapes=shapes, origins=origins, channel=channel,
-                    nb=nb, ns=ns, n_vox=n_vox, cap=cap, which=which, done=ev_done, store_f32=store_f32,
-                    vol_exact=vol_exact, pre=pre, exact=exact, eps=eps, native=True, vscale=vscale, vrange=vrange)
-    written = ctypes.c_int(0)
-    path = ctypes.c_int(0)
-
-    def passes(with_mask: bool, mode: int):
-        """Every scale of the batch -> the set of entry layouts the calls reported (0 = no entries)."""
-        global LAST_ZX_PATH, LAST_Q16_BOUND, LAST_NMS_BAND
-        layouts = set()
-        # the tiled path works from an operand-ordered copy of the voxels that does not depend on sigma: made
-        # once here, trusted by the calls below for as long as every call so far ran the tiled path (any other
-        # path uses the same part of the workspace for something else)
-        packed = False
-        tiled_mode = nat.MMX_ZX_TILED
-        is_float = vol32.dtype == nat.MMX_F32
+    if vol32.dtype == nat.MMX_F32:
         # float voxels (float images, preprocessed blocks): the tiled path holds each as two float16 pieces, which
         # suits values of ordinary magnitude -- the range is known here, not in the library (mmx_volume.value_range)
-        float_ok = is_float and vrange is not None and max(abs(vrange[0]), abs(vrange[1])) <= FLOAT_TILED_RANGE[1]
-        nonneg = not is_float or (float_ok and vrange[0] >= 0.0)
-        if is_float:
-            vol32.value_range = 0.0 if not float_ok else (max(vrange[1], 1e-30) if vrange[0] >= 0.0
-                                                          else -max(abs(vrange[0]), abs(vrange[1])))
-        if mode in (nat.MMX_ZX_AUTO, nat.MMX_ZX_TILED_Q16) and nonneg:
-            # 16-bit intermediates when the band covers their rounding error fourfold (or when asked for by name)
-            bound = max(float(L.mmx_tiled_q16_error_bound(nat.as_double_ptr(space.w0[s]), nat.as_double_ptr(space.w2[s]),
-                                                          int(space.radii[s]), float(space.norms[s]))) for s in range(ns))
-            bound *= 1.0 if not is_float else float(vol32.value_range)
-            # (by name: taken whatever the band -- kernel experiments and the band-retry tests ask for it with narrow
-            #  bands; the run-time check |float32 - float64| < eps / 4 on every re-scored candidate then widens the band)
-            if mode == nat.MMX_ZX_TILED_Q16 or (0 <= 4.0 * bound <= eps and bound <= LOG_ABS_TOL):
-                tiled_mode = nat.MMX_ZX_TILED_Q16
-                LAST_Q16_BOUND, LAST_NMS_BAND = bound, eps
-        if (mode in (nat.MMX_ZX_AUTO, nat.MMX_ZX_TILED, nat.MMX_ZX_TILED_Q16) and not is_float) or \
-                (mode in (nat.MMX_ZX_AUTO, nat.MMX_ZX_TILED) and float_ok):
-            nonlocal pack_side
-            if pack_side:
-                with torch.cuda.stream(bufs.pack_stream):
-                    rc = L.mmx_zx_pack(ctypes.byref(vol32), d_blocks.data_ptr(), blocks.ctypes.data, nb, slot,
-                                       ws.data_ptr(), bufs.pack_stream.cuda_stream)
-                torch.cuda.current_stream().wait_stream(bufs.pack_stream)
-                pack_side = False                # (a second round of passes, should one be needed: in stream order)
-            else:
-                rc = L.mmx_zx_pack(ctypes.byref(vol32), d_blocks.data_ptr(), blocks.ctypes.data, nb, slot,
-                                   ws.data_ptr(), stream)
-            if rc not in (0, 5):                 # MMX_OK, MMX_ERR_UNSUPPORTED (float voxels, workspace shape)
-                nat.check(rc, "mmx_zx_pack")
-            packed = rc == 0
-        for s in range(ns):
-            nat.check(L.mmx_log_batch_f32(
-                ctypes.byref(vol32), d_blocks.data_ptr(), blocks.ctypes.data, nb, slot,
-                nat.as_double_ptr(space.w0[s]), nat.as_double_ptr(space.w2[s]), int(space.radii[s]),
-                float(space.norms[s]), log_base + s * nb * slot * 4, ws.data_ptr(),
-                (mask_base + s * mask_words * 16) if with_mask else None, thr - eps, eps,
-                ctypes.byref(written), (tiled_mode | nat.MMX_ZX_PREPACKED | ZX_FLAGS) if packed else mode,
-                ctypes.byref(path), stream),
-                "mmx_log_batch_f32")
-            LAST_ZX_PATH = path.value
-            packed = packed and path.value == tiled_mode
-            layouts.add(written.value if with_mask else 0)
-        return layouts
-
-    # With the entries the Y pass leaves whole segments of the cube unwritten, so it is all scales, in one
-    # layout, or none: if one scale cannot produce them (a radius outside the fused kernels, tiny blocks) or
-    # the scales ran different kernels, every scale is computed again -- with the packed kernel's entries if a
-    # scale produced those, else in full.
-    layouts = passes(True, ZX_MODE)
-    if layouts == {nat.MMX_MASK_ROWS, nat.MMX_MASK_QUADS}:
-        layouts = passes(True, nat.MMX_ZX_PACKED)
-    if len(layouts) > 1:
-        layouts = passes(False, ZX_MODE)
-    mask_layout = layouts.pop()
-    mask_ok = mask_layout > 0
+        float_ok = vrange is not None and max(abs(vrange[0]), abs(vrange[1])) <= FLOAT_TILED_RANGE[1]
+        vol32.value_range = 0.0 if not float_ok else (max(vrange[1], 1e-30) if vrange[0] >= 0.0
+                                                      else -max(abs(vrange[0]), abs(vrange[1])))
     n_vox = int(sum(int(np.prod(s)) for s in shapes))
     if cap is None:
         cap = max(4096, min(n_vox * ns, n_vox // 2000 * ns + 65536))
     table = bufs.cand_table(which, cap)
     count = bufs.counts[which]
+    ev_read, ev_done = bufs.events(which)
+    side = bufs.rescore_stream if side_tail else None
     native = bool(exact and HOST_PATH == "native")
+    a = nat.DetectArgs()
+    a.vol32, a.vol_exact = ctypes.pointer(vol32), ctypes.pointer(vol_exact)
+    a.d_blocks, a.h_blocks = d_blocks.data_ptr(), blocks.ctypes.data
+    a.n_blocks, a.n_sigma, a.slot_elems = nb, ns, slot
+    a.h_w0, a.h_w2 = space.w0_tab.ctypes.data, space.w2_tab.ctypes.data
+    a.d_w0, a.d_w2 = d_w0.data_ptr(), d_w2.data_ptr()
+    a.h_radius, a.h_norm = space.radii.ctypes.data, space.norms.ctypes.data
+    a.d_work, a.work_bytes = ws.data_ptr(), ws.numel() * 4
+    a.thr, a.eps = thr, eps
+    a.d_cands, a.cap, a.d_count = table.data_ptr(), cap, count.data_ptr()
+    a.h_count = bufs.host_counts[which].data_ptr()
+    if native:
+        a.h_cands, a.h_prefix = bufs.host_table(which).data_ptr(), min(cap, _PREFIX_ENTRIES)
+    a.zx_mode, a.zx_flags, a.store_f32, a.exact, a.expand = ZX_MODE, ZX_FLAGS, store_f32, int(exact), int(native)
+    a.stream = stream
+    a.tail_stream = side.cuda_stream if side is not None else stream
+    a.pack_stream = bufs.pack_stream.cuda_stream if pack_side else stream
+    # (the last reader of this workspace; also a batch that is nominated again, on the main stream: same workspace)
+    a.ev_work_free = bufs.ws_free[ws_i].handle if bufs.ws_free[ws_i] is not None else None
+    a.ev_work_read = ev_read.handle if side_tail else None
+    a.ev_done = ev_done.handle
+    info = nat.DetectInfo()
+    one_call = bool(NATIVE_BATCH and pre is None and native)
+    if one_call:
+        # ---- the whole batch in one native call (mmx_detect_batch): voxel copy, every scale, NMS, probes, re-score, copies
+        rc = _launch_batch(L, a, info, bufs, nb, blocks, space, vol32, vol_exact)
+    else:
+        # ---- call by call: every scale by the library's rules (mmx_log_scales_f32), the tail from here
+        rc = L.mmx_log_scales_f32(ctypes.byref(a), ctypes.byref(info))
+    if rc != 0:
+        detail = L.mmx_detect_last_error().decode()
+        nat.check(rc, ("mmx_detect_batch" if one_call else "mmx_log_scales_f32") + (f" [{detail}]" if detail and rc == 2 else ""))
+    global LAST_ZX_PATH, LAST_Q16_BOUND, LAST_NMS_BAND
+    LAST_ZX_PATH = info.zx_path
+    if info.zx_path == nat.MMX_ZX_TILED_Q16:
+        LAST_Q16_BOUND, LAST_NMS_BAND = info.q16_bound, eps
+    if side_tail:
+        bufs.ws_free[ws_i] = ev_read
+    job = dict(blocks=blocks, d_blocks=d_blocks, shapes=shapes, origins=origins, channel=channel,
+               nb=nb, ns=ns, n_vox=n_vox, cap=cap, which=which, done=ev_done, store_f32=store_f32,
+               vol_exact=vol_exact, pre=pre, exact=exact, eps=eps, native=native, vscale=vscale, vrange=vrange)
+    if one_call:
+        return job
+    log_base = ws.data_ptr() + 4 * nb * slot * 4
+    # NMS entries, [ns][(nb * slot) >> 5] 16-byte entries: written by the Y pass of the fused path
+    mask_base = (log_base + ns * nb * slot * 4 + 15) & ~15
 
     def tail(stream_ptr):
         count.zero_()
-        nat.check(L.mmx_peaks_batch(log_base, mask_base if mask_ok else None, mask_layout, ns, d_blocks.data_ptr(),
-                                    blocks.ctypes.data, nb, slot, thr, eps, table.data_ptr(), cap,
+        nat.check(L.mmx_peaks_batch(log_base, mask_base if info.mask_layout else None, info.mask_layout, ns,
+                                    d_blocks.data_ptr(), blocks.ctypes.data, nb, slot, thr, eps, table.data_ptr(), cap,
                                     count.data_ptr(), stream_ptr),
                   "mmx_peaks_batch")
         if side_tail:                    # (the workspace may be written again once the NMS has read it)
-            bufs.ws_free[ws_i] = torch.cuda.Event()
-            bufs.ws_free[ws_i].record()
+            nat.check(L.mmx_event_record(ev_read.handle, stream_ptr), "mmx_event_record")
         if native:
             # the neighbours that can out-vote the contested candidates join the table: one re-score, one copy
             nat.check(L.mmx_expand_probes(table.data_ptr(), cap, count.data_ptr(), count.data_ptr() + 4,
@@ -906,20 +831,15 @@ def _enqueue_detect(dvol, channel, origins, shapes, space: ScaleSpace, thr: floa
         if native:
             n_pre = min(cap, _PREFIX_ENTRIES) * nat.CAND_DTYPE.itemsize
             bufs.host_table(which)[:n_pre].copy_(table[:n_pre], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        return ev
+        nat.check(L.mmx_event_record(ev_done.handle, stream_ptr), "mmx_event_record")
     if side_tail:
         # (every batch of a raw volume owns its candidate table; the volume is never written)
-        side = bufs.rescore_stream
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
-            done = tail(side.cuda_stream)
+            tail(side.cuda_stream)
     else:
-        done = tail(stream)
-    return dict(blocks=blocks, d_blocks=d_blocks, shapes=shapes, origins=origins, channel=channel,
-                nb=nb, ns=ns, n_vox=n_vox, cap=cap, which=which, done=done, store_f32=store_f32,
-                vol_exact=vol_exact, pre=pre, exact=exact, eps=eps, native=native, vscale=vscale, vrange=vrange)
+        tail(stream)
+    return job
 
 
 def _launch_batch(L, a, info, bufs: _Buffers, nb: int, blocks, space, vol32, vol_exact) -> int:

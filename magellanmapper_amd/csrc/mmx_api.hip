@@ -199,182 +199,249 @@ double mmx_tiled_q16_error_bound(const double* h_w0, const double* h_w2, int rad
     return err;
 }
 
+}  // extern "C"
+
+void mmx_batch_geom_make(const mmx_volume* vol, const mmx_block* h_blocks, int n_blocks, int64_t slot_elems,
+                         mmx_batch_geom* g)
+{
+    *g = mmx_batch_geom{};
+    g->min_nz = g->min_ny = g->min_nx = 1 << 30;
+    g->plan_status = MMX_ERR_UNSUPPORTED;
+    g->rows_fit = g->quads_fit = true;
+    if (n_blocks < 1 || n_blocks > MMX_MAX_BLOCKS) {       // (the callers' own checks come first: the table is not read)
+        g->status = n_blocks < 1 ? MMX_ERR_ARG : MMX_ERR_UNSUPPORTED;
+        return;
+    }
+    for (int i = 0; i < n_blocks; ++i) {
+        const mmx_block& b = h_blocks[i];
+        if (b.nz < 1 || b.ny < 1 || b.nx < 1 || b.slot != i || b.px < b.nx || b.px % MMX_ROW_ALIGN) {
+            if (g->status == MMX_OK) g->status = MMX_ERR_ARG;
+            g->bad_block = true;
+            return;
+        }
+        if ((int64_t)b.nz * b.ny * b.px > slot_elems && g->status == MMX_OK) g->status = MMX_ERR_WORKSPACE;
+        if (b.nz < g->min_nz) g->min_nz = b.nz;
+        if (b.ny < g->min_ny) g->min_ny = b.ny;
+        if (b.nx < g->min_nx) g->min_nx = b.nx;
+        if (b.ny > g->max_ny) g->max_ny = b.ny;
+        if (b.nx > g->max_nx) g->max_nx = b.nx;
+        if (b.px > g->max_px) g->max_px = b.px;
+        if (b.ny * b.px > g->max_zcols) g->max_zcols = b.ny * b.px;
+        if (b.nz * b.px > g->max_ycols) g->max_ycols = b.nz * b.px;
+        if (b.nz * b.ny > g->max_rows) g->max_rows = b.nz * b.ny;
+        if (b.nz * b.ny * b.px > g->max_vox) g->max_vox = b.nz * b.ny * b.px;
+        // the entries of a block (ny rows of ceil(nz * px / 64) words, or ny ceil(nz / 4) ceil(nx / 16) quads)
+        if ((int64_t)b.ny * (((int64_t)b.nz * b.px + 63) >> 6) > (slot_elems >> 5) - 1) g->rows_fit = false;
+        if ((int64_t)b.ny * ((b.nz + 3) >> 2) * ((b.nx + 15) >> 4) > (slot_elems >> 5) - 1) g->quads_fit = false;
+        if (vol) {
+            const int64_t lane = (int64_t)(b.ny - 1) * vol->stride_y + (int64_t)(b.nx - 1) * vol->stride_x;
+            if (lane > g->max_lane_in) g->max_lane_in = lane;
+        }
+    }
+    if (vol) g->plan_status = mmx_zx6_plan_make(h_blocks, n_blocks, slot_elems, vol->dtype, &g->plan);
+}
+
+namespace {
+
+// weights per pass: input scale into the z pass, -norm into the x pass
+struct pass_weights {
+    float z0[MMX_MAX_RADIUS_GENERIC + 1], z2[MMX_MAX_RADIUS_GENERIC + 1];
+    float y0[MMX_MAX_RADIUS_GENERIC + 1], y2[MMX_MAX_RADIUS_GENERIC + 1];
+    float x0[MMX_MAX_RADIUS_GENERIC + 1], x2[MMX_MAX_RADIUS_GENERIC + 1];
+};
+void make_weights(const mmx_volume* vol, const double* h_w0, const double* h_w2, int radius, double norm, pass_weights* w)
+{
+    double in_scale = 1.0;
+    if (vol->dtype == MMX_U8) in_scale = 1.0 / 255.0;        // skimage img_as_float: x * (1/imax)
+    else if (vol->dtype == MMX_U16) in_scale = 1.0 / 65535.0;
+    for (int k = 0; k <= radius; ++k) {
+        w->z0[k] = (float)(h_w0[k] * in_scale);
+        w->z2[k] = (float)(h_w2[k] * in_scale);
+        w->y0[k] = (float)h_w0[k];
+        w->y2[k] = (float)h_w2[k];
+        w->x0[k] = (float)(-norm * h_w0[k]);
+        w->x2[k] = (float)(-norm * h_w2[k]);
+    }
+}
+mmx_taps_f32 taps(const float* a, const float* b, int radius)
+{
+    mmx_taps_f32 t;
+    for (int k = 0; k <= MMX_MAX_RADIUS_FAST; ++k) {
+        t.w0[k] = k <= radius ? a[k] : 0.f;
+        t.w2[k] = k <= radius ? b[k] : 0.f;
+    }
+    return t;
+}
+
+// The argument checks of mmx_log_batch_f32, everything but the blocks; takes the flags off c->zx_mode.
+int check_log_args(mmx_log_call* c, bool* y_valu, bool* prepacked)
+{
+    *y_valu = c->zx_mode >= 0 && (c->zx_mode & MMX_ZX_Y_VALU);
+    if (*y_valu) c->zx_mode &= ~MMX_ZX_Y_VALU;
+    *prepacked = c->zx_mode == (MMX_ZX_TILED | MMX_ZX_PREPACKED) || c->zx_mode == (MMX_ZX_TILED_Q16 | MMX_ZX_PREPACKED);
+    if (*prepacked) c->zx_mode &= ~MMX_ZX_PREPACKED;
+    if (c->zx_mode < MMX_ZX_AUTO || c->zx_mode > MMX_ZX_TILED_Q16 || c->zx_mode == 1 || (c->zx_mode >= 3 && c->zx_mode <= 5))
+        return MMX_ERR_ARG;             // (3, 4, 5: retired experiment kernels)
+    if (!c->vol || !c->vol->d_data || !c->d_blocks || !c->h_blocks || !c->h_w0 || !c->h_w2 || !c->d_log || !c->d_work)
+        return MMX_ERR_ARG;
+    if (c->n_blocks < 1 || c->radius < 0 || c->slot_elems < 1) return MMX_ERR_ARG;
+    if (c->n_blocks > MMX_MAX_BLOCKS) return MMX_ERR_UNSUPPORTED;
+    if (c->radius > MMX_MAX_RADIUS_GENERIC) return MMX_ERR_UNSUPPORTED;
+    if (c->slot_elems >= (int64_t(1) << 29)) return MMX_ERR_UNSUPPORTED;  // 32-bit byte offsets in a slot
+    if (c->slot_elems % MMX_ROW_ALIGN) return MMX_ERR_ARG;
+    if (c->vol->dtype != MMX_U8 && c->vol->dtype != MMX_U16 && c->vol->dtype != MMX_F32)
+        return MMX_ERR_UNSUPPORTED;     // float64 volumes: pass a float32 copy
+    return MMX_OK;
+}
+
+// Fused path: Z and X in one kernel (Gz / Gzz never touch HBM), then Y.  MMX_ERR_UNSUPPORTED: not for this geometry
+// (or this mode) -- the separate passes take the call.
+int fused_passes(const mmx_log_call& c, bool y_valu, bool prepacked, const mmx_batch_geom& g, const pass_weights& w)
+{
+    const mmx_volume* vol = c.vol;
+    const int radius = c.radius, n_blocks = c.n_blocks;
+    const int64_t slot_elems = c.slot_elems;
+    hipStream_t s = c.stream;
+    const bool fast_r = radius >= 1 && radius <= MMX_MAX_RADIUS_FAST;
+    const bool lane_ok = g.max_lane_in * 8 < (int64_t(1) << 31);
+    const bool fused = c.zx_mode != MMX_ZX_SEPARATE && fast_r && lane_ok && g.min_ny >= radius + kColPrefetch &&
+                       g.min_nz >= radius + 1 && g.min_nx >= radius && g.max_px <= 512 && vol->stride_y < (1 << 30);
+    if (!fused) return MMX_ERR_UNSUPPORTED;
+    float* t0 = c.d_work;                                   // P
+    float* t1 = c.d_work + (int64_t)n_blocks * slot_elems;  // Q
+    mmx_taps_f32 tzz = taps(w.z0, w.z2, radius), txx = taps(w.y0, w.y2, radius), tyy = taps(w.x0, w.x2, radius);
+    int rc, path = MMX_ZX_PACKED;
+    // AUTO = the tiled matrix-core path for integer voxels, else the packed-VALU kernel.
+    // float32 or 16-bit tiles: mmx_tiles_q16, from this call's sigma and whether it wants entries
+    double q_bp = 0, q_bq = 0, q_err = 0, vscale = 0;
+    q16_bounds(c.h_w0, c.h_w2, radius, c.norm, &q_bp, &q_bq, &q_err);
+    // float voxels: the tiled path when the volume states its value range (or when asked for by name: the float16
+    // pieces of its copy cover |v| < 65504), 16-bit tiles when that range is [0, m]: their bounds scale with m
+    const bool integer = vol->dtype == MMX_U8 || vol->dtype == MMX_U16;
+    const bool ranged = vol->dtype == MMX_F32 && vol->value_range != 0.f && fabsf(vol->value_range) < 60000.f;
+    const bool wants_entries = c.d_nms_mask && c.h_mask_written;
+    const bool q16 = mmx_tiles_q16(c.zx_mode, vol, q_err, c.nms_eps, wants_entries, &vscale);
+    const bool nonneg = vscale > 0.0;
+    if (q16) { q_bp *= vscale; q_bq *= vscale; }
+    bool tiled = (c.zx_mode == MMX_ZX_TILED || (c.zx_mode == MMX_ZX_TILED_Q16 && nonneg) ||
+                  (c.zx_mode == MMX_ZX_AUTO && (integer || ranged))) && g.plan_status == MMX_OK;
+    const mmx_zx6_plan& plan = g.plan;
+    if (tiled && !prepacked) {
+        mmx_timed_scope ts(MMX_K_ZXPACK, s);
+        rc = mmx_launch_zx6_pack(vol, c.d_blocks, c.h_blocks, n_blocks, plan, c.d_work, s);
+        if (rc == MMX_ERR_HIP) return hip_fail(hipGetLastError(), "voxel copy of the tiled path");
+        tiled = rc == MMX_OK;
+    }
+    { mmx_timed_scope ts(MMX_K_ZX, s);
+      rc = MMX_ERR_UNSUPPORTED;
+      if (tiled) {
+          path = q16 ? MMX_ZX_TILED_Q16 : MMX_ZX_TILED;
+          rc = mmx_launch_zx6(vol, c.d_blocks, c.h_blocks, n_blocks, plan, txx, radius, c.d_work,
+                              q16 ? (float)(1.0 / q_bp) : 0.f, q16 ? (float)(1.0 / q_bq) : 0.f, s);
+          tiled = rc == MMX_OK;
+      }
+      if (rc == MMX_ERR_UNSUPPORTED) {
+          path = MMX_ZX_PACKED;
+          rc = mmx_launch_zx2(vol, c.d_blocks, n_blocks, g.max_ny, g.max_px, slot_elems, tzz, txx, radius, t0, t1, s);
+      } }
+    if (rc == MMX_OK && c.h_zx_path) *c.h_zx_path = path;
+    if (rc == MMX_OK) {
+        mmx_timed_scope ts(MMX_K_Y2, s);
+        const bool want_mask = wants_entries && (tiled ? g.quads_fit : g.rows_fit);    // (`tiled`: the kernel that ran)
+        unsigned long long* d_mask = want_mask ? (unsigned long long*)c.d_nms_mask : nullptr;
+        rc = MMX_ERR_UNSUPPORTED;
+        if (tiled && q16 && !y_valu)
+            rc = mmx_launch_ym(c.d_blocks, n_blocks, plan, slot_elems, tyy, radius, c.d_work,
+                               (float)(q_bp / 65535.0), (float)(q_bq / 32767.0), c.d_log, d_mask, c.nms_lo, c.nms_eps, s);
+        if (rc != MMX_ERR_UNSUPPORTED) ;
+        else if (tiled)
+            rc = mmx_launch_y6(c.d_blocks, n_blocks, plan, slot_elems, tyy, radius, c.d_work,
+                               reinterpret_cast<const float*>(reinterpret_cast<const char*>(c.d_work) + plan.q_off),
+                               q16 ? (float)(q_bp / 65535.0) : 0.f, q16 ? (float)(q_bq / 32767.0) : 0.f, c.d_log,
+                               d_mask, c.nms_lo, c.nms_eps, s);
+        else
+            rc = mmx_launch_y2(c.d_blocks, n_blocks, g.max_ycols, slot_elems, tyy, radius, t0, t1, c.d_log,
+                               d_mask, c.nms_lo, c.nms_eps, s);
+        if (rc == MMX_OK && want_mask) *c.h_mask_written = tiled ? MMX_MASK_QUADS : MMX_MASK_ROWS;
+    }
+    return rc == MMX_ERR_HIP ? hip_fail(hipGetLastError(), "fused passes") : rc;
+}
+
+// The three separate passes: per pass the register-ring kernel where the geometry allows it, else the generic one.
+int separate_passes(const mmx_log_call& c, const mmx_batch_geom& g, const pass_weights& w)
+{
+    const mmx_volume* vol = c.vol;
+    const int radius = c.radius, n_blocks = c.n_blocks;
+    const int64_t slot_elems = c.slot_elems;
+    hipStream_t s = c.stream;
+    float* t0 = c.d_work;                                   // Gz
+    float* t1 = t0 + (int64_t)n_blocks * slot_elems;        // Gzz
+    float* t2 = t1 + (int64_t)n_blocks * slot_elems;        // A
+    float* t3 = t2 + (int64_t)n_blocks * slot_elems;        // BC
+    const bool fast_r = radius >= 1 && radius <= MMX_MAX_RADIUS_FAST;
+    const bool lane_ok = g.max_lane_in * 8 < (int64_t(1) << 31);
+    const bool fast_z = fast_r && lane_ok && g.min_nz >= radius + kColPrefetch && vol->stride_y < (1 << 30);
+    const bool fast_y = fast_r && g.min_ny >= radius + kColPrefetch;
+    const bool fast_x = fast_r && g.min_nx >= radius;
+    int rc;
+    { mmx_timed_scope ts(fast_z ? MMX_K_ZPASS : MMX_K_GENERIC, s);
+    if (fast_z) rc = mmx_launch_zpass(vol, c.d_blocks, n_blocks, g.max_zcols, slot_elems, taps(w.z0, w.z2, radius), radius, t0, t1, s);
+    else rc = mmx_launch_generic_pass(0, vol, c.d_blocks, n_blocks, g.max_vox, slot_elems, w.z0, w.z2, radius, nullptr, nullptr, t0, t1, s); }
+    if (rc != MMX_OK) return rc == MMX_ERR_HIP ? hip_fail(hipGetLastError(), "z pass") : rc;
+    { mmx_timed_scope ts(fast_y ? MMX_K_YPASS : MMX_K_GENERIC, s);
+    if (fast_y) rc = mmx_launch_ypass(c.d_blocks, n_blocks, g.max_ycols, slot_elems, taps(w.y0, w.y2, radius), radius, t0, t1, t2, t3, s);
+    else rc = mmx_launch_generic_pass(1, vol, c.d_blocks, n_blocks, g.max_vox, slot_elems, w.y0, w.y2, radius, t0, t1, t2, t3, s); }
+    if (rc != MMX_OK) return rc == MMX_ERR_HIP ? hip_fail(hipGetLastError(), "y pass") : rc;
+    { mmx_timed_scope ts(fast_x ? MMX_K_XPASS : MMX_K_GENERIC, s);
+    if (fast_x) rc = mmx_launch_xpass(c.d_blocks, n_blocks, g.max_rows, g.max_nx, slot_elems, taps(w.x0, w.x2, radius), radius, t2, t3, c.d_log, s);
+    else rc = mmx_launch_generic_pass(2, vol, c.d_blocks, n_blocks, g.max_vox, slot_elems, w.x0, w.x2, radius, t2, t3, c.d_log, nullptr, s); }
+    if (rc != MMX_OK) return rc == MMX_ERR_HIP ? hip_fail(hipGetLastError(), "x pass") : rc;
+    return MMX_OK;
+}
+
+}  // namespace
+
+int mmx_log_scale_f32(const mmx_log_call& call, const mmx_batch_geom& g)
+{
+    mmx_log_call c = call;
+    if (c.h_mask_written) *c.h_mask_written = 0;
+    if (c.h_zx_path) *c.h_zx_path = MMX_ZX_SEPARATE;
+    bool y_valu, prepacked;
+    int rc = check_log_args(&c, &y_valu, &prepacked);
+    if (rc != MMX_OK) return rc;
+    if (g.status != MMX_OK) return g.status;
+    pass_weights w;
+    make_weights(c.vol, c.h_w0, c.h_w2, c.radius, c.norm, &w);
+    rc = fused_passes(c, y_valu, prepacked, g, w);
+    if (rc != MMX_ERR_UNSUPPORTED) return rc;       // (unsupported geometry: the separate passes)
+    return separate_passes(c, g, w);
+}
+
+int mmx_zx_pack_geom(const mmx_volume* vol, const mmx_block* d_blocks, const mmx_block* h_blocks, int n_blocks,
+                     int64_t slot_elems, const mmx_batch_geom& g, float* d_work, hipStream_t stream)
+{
+    if (!vol || !vol->d_data || !d_blocks || !h_blocks || !d_work || n_blocks < 1 || slot_elems < 1) return MMX_ERR_ARG;
+    if (n_blocks > MMX_MAX_BLOCKS) return MMX_ERR_UNSUPPORTED;
+    if (vol->dtype != MMX_U8 && vol->dtype != MMX_U16 && vol->dtype != MMX_F32) return MMX_ERR_UNSUPPORTED;
+    if (g.bad_block) return MMX_ERR_ARG;
+    if (g.plan_status != MMX_OK) return g.plan_status;
+    mmx_timed_scope ts(MMX_K_ZXPACK, stream);
+    const int rc = mmx_launch_zx6_pack(vol, d_blocks, h_blocks, n_blocks, g.plan, d_work, stream);
+    return rc == MMX_ERR_HIP ? hip_fail(hipGetLastError(), "voxel copy of the tiled path") : rc;
+}
+
+extern "C" {
+
 int mmx_log_batch_f32(const mmx_volume* vol, const mmx_block* d_blocks, const mmx_block* h_blocks,
                       int n_blocks, int64_t slot_elems,
                       const double* h_w0, const double* h_w2, int radius, double norm,
                       float* d_log, float* d_work, uint64_t* d_nms_mask, float nms_lo, float nms_eps,
                       int* h_mask_written, int zx_mode, int* h_zx_path, void* stream)
 {
-    if (h_mask_written) *h_mask_written = 0;
-    if (h_zx_path) *h_zx_path = MMX_ZX_SEPARATE;
-    const bool y_valu = zx_mode >= 0 && (zx_mode & MMX_ZX_Y_VALU);
-    if (y_valu) zx_mode &= ~MMX_ZX_Y_VALU;
-    const bool prepacked = zx_mode == (MMX_ZX_TILED | MMX_ZX_PREPACKED) || zx_mode == (MMX_ZX_TILED_Q16 | MMX_ZX_PREPACKED);
-    if (prepacked) zx_mode &= ~MMX_ZX_PREPACKED;
-    if (zx_mode < MMX_ZX_AUTO || zx_mode > MMX_ZX_TILED_Q16 || zx_mode == 1 || (zx_mode >= 3 && zx_mode <= 5))
-        return MMX_ERR_ARG;             // (3, 4, 5: retired experiment kernels)
-    if (!vol || !vol->d_data || !d_blocks || !h_blocks || !h_w0 || !h_w2 || !d_log || !d_work)
-        return MMX_ERR_ARG;
-    if (n_blocks < 1 || radius < 0 || slot_elems < 1) return MMX_ERR_ARG;
-    if (n_blocks > MMX_MAX_BLOCKS) return MMX_ERR_UNSUPPORTED;
-    if (radius > MMX_MAX_RADIUS_GENERIC) return MMX_ERR_UNSUPPORTED;
-    if (slot_elems >= (int64_t(1) << 29)) return MMX_ERR_UNSUPPORTED;  // 32-bit byte offsets in a slot
-    if (slot_elems % MMX_ROW_ALIGN) return MMX_ERR_ARG;
-    double in_scale = 1.0;
-    if (vol->dtype == MMX_U8) in_scale = 1.0 / 255.0;        // skimage img_as_float: x * (1/imax)
-    else if (vol->dtype == MMX_U16) in_scale = 1.0 / 65535.0;
-    else if (vol->dtype != MMX_F32) return MMX_ERR_UNSUPPORTED;  // float64 volumes: pass a float32 copy
-
-    int min_nz = 1 << 30, min_ny = 1 << 30, min_nx = 1 << 30;
-    int max_zcols = 0, max_ycols = 0, max_rows = 0, max_nx = 0, max_vox = 0;
-    int64_t max_lane_in = 0;
-    for (int i = 0; i < n_blocks; ++i) {
-        const mmx_block& b = h_blocks[i];
-        if (b.nz < 1 || b.ny < 1 || b.nx < 1 || b.slot != i) return MMX_ERR_ARG;
-        if (b.px < b.nx || b.px % MMX_ROW_ALIGN) return MMX_ERR_ARG;
-        if ((int64_t)b.nz * b.ny * b.px > slot_elems) return MMX_ERR_WORKSPACE;
-        if (b.nz < min_nz) min_nz = b.nz;
-        if (b.ny < min_ny) min_ny = b.ny;
-        if (b.nx < min_nx) min_nx = b.nx;
-        if (b.ny * b.px > max_zcols) max_zcols = b.ny * b.px;
-        if (b.nz * b.px > max_ycols) max_ycols = b.nz * b.px;
-        if (b.nz * b.ny > max_rows) max_rows = b.nz * b.ny;
-        if (b.nx > max_nx) max_nx = b.nx;
-        if (b.nz * b.ny * b.px > max_vox) max_vox = b.nz * b.ny * b.px;
-        const int64_t lane = (int64_t)(b.ny - 1) * vol->stride_y + (int64_t)(b.nx - 1) * vol->stride_x;
-        if (lane > max_lane_in) max_lane_in = lane;
-    }
-    const int64_t n_slots = n_blocks;
-    float* t0 = d_work;                          // Gz
-    float* t1 = d_work + n_slots * slot_elems;   // Gzz
-    float* t2 = t1 + n_slots * slot_elems;       // A
-    float* t3 = t2 + n_slots * slot_elems;       // BC
-    hipStream_t s = (hipStream_t)stream;
-
-    // weights per pass: input scale into the z pass, -norm into the x pass
-    float wz0[MMX_MAX_RADIUS_GENERIC + 1], wz2[MMX_MAX_RADIUS_GENERIC + 1];
-    float wy0[MMX_MAX_RADIUS_GENERIC + 1], wy2[MMX_MAX_RADIUS_GENERIC + 1];
-    float wx0[MMX_MAX_RADIUS_GENERIC + 1], wx2[MMX_MAX_RADIUS_GENERIC + 1];
-    for (int k = 0; k <= radius; ++k) {
-        wz0[k] = (float)(h_w0[k] * in_scale);
-        wz2[k] = (float)(h_w2[k] * in_scale);
-        wy0[k] = (float)h_w0[k];
-        wy2[k] = (float)h_w2[k];
-        wx0[k] = (float)(-norm * h_w0[k]);
-        wx2[k] = (float)(-norm * h_w2[k]);
-    }
-    const bool fast_r = radius >= 1 && radius <= MMX_MAX_RADIUS_FAST;
-    const bool lane_ok = max_lane_in * 8 < (int64_t(1) << 31);
-    const bool fast_z = fast_r && lane_ok && min_nz >= radius + kColPrefetch && vol->stride_y < (1 << 30);
-    const bool fast_y = fast_r && min_ny >= radius + kColPrefetch;
-    const bool fast_x = fast_r && min_nx >= radius;
-    auto taps = [&](const float* a, const float* b) {
-        mmx_taps_f32 t;
-        for (int k = 0; k <= MMX_MAX_RADIUS_FAST; ++k) {
-            t.w0[k] = k <= radius ? a[k] : 0.f;
-            t.w2[k] = k <= radius ? b[k] : 0.f;
-        }
-        return t;
-    };
-    int rc;
-    // Fused path: Z and X in one kernel (Gz / Gzz never touch HBM), then Y.
-    int max_ny = 0, max_px = 0;
-    for (int i = 0; i < n_blocks; ++i) {
-        if (h_blocks[i].ny > max_ny) max_ny = h_blocks[i].ny;
-        if (h_blocks[i].px > max_px) max_px = h_blocks[i].px;
-    }
-    const bool fused = zx_mode != MMX_ZX_SEPARATE && fast_r && lane_ok && fast_y && min_nz >= radius + 1 &&
-                       min_nx >= radius && max_px <= 512 && vol->stride_y < (1 << 30);
-    if (fused) {
-        mmx_taps_f32 tzz = taps(wz0, wz2), txx = taps(wy0, wy2), tyy = taps(wx0, wx2);
-        int path = MMX_ZX_PACKED;
-        // AUTO = the tiled matrix-core path for integer voxels, else the packed-VALU kernel.  (The register-only
-        // and LDS-staged matrix-core kernels are correct and selectable, but no faster than the packed one:
-        // DESIGN.md section 4b -- their 16 planes x 64 bytes accesses were the limit, which the tiled form removes.)
-        mmx_zx6_plan plan;
-        // Q16 tiles when asked for, or under AUTO when the caller's NMS band covers their rounding error fourfold and
-        // that error, in value units, is inside the LoG contract (MMX_LOG_ABS_TOL)
-        // (the condition under which every true maximum is still nominated)
-        double q_bp = 0, q_bq = 0, q_err = 0;
-        q16_bounds(h_w0, h_w2, radius, norm, &q_bp, &q_bq, &q_err);
-        // float voxels: the tiled path when the volume states its value range (or when asked for by name: the float16
-        // pieces of its copy cover |v| < 65504), 16-bit tiles when that range is [0, m]: their bounds scale with m
-        const bool integer = vol->dtype == MMX_U8 || vol->dtype == MMX_U16;
-        const bool ranged = vol->dtype == MMX_F32 && vol->value_range != 0.f && fabsf(vol->value_range) < 60000.f;
-        const bool nonneg = integer || (ranged && vol->value_range > 0.f);
-        if (!integer && nonneg) { q_bp *= vol->value_range; q_bq *= vol->value_range; q_err *= vol->value_range; }
-        const bool q16 = nonneg && (zx_mode == MMX_ZX_TILED_Q16 ||
-                         (zx_mode == MMX_ZX_AUTO && d_nms_mask && h_mask_written && (double)nms_eps >= 4.0 * q_err &&
-                          q_err <= MMX_LOG_ABS_TOL));
-        bool tiled = (zx_mode == MMX_ZX_TILED || (zx_mode == MMX_ZX_TILED_Q16 && nonneg) ||
-                      (zx_mode == MMX_ZX_AUTO && (integer || ranged))) &&
-                     mmx_zx6_plan_make(h_blocks, n_blocks, slot_elems, vol->dtype, &plan) == MMX_OK;
-        if (tiled && !prepacked) {
-            mmx_timed_scope ts(MMX_K_ZXPACK, s);
-            rc = mmx_launch_zx6_pack(vol, d_blocks, h_blocks, n_blocks, plan, d_work, s);
-            if (rc == MMX_ERR_HIP) return hip_fail(hipGetLastError(), "voxel copy of the tiled path");
-            tiled = rc == MMX_OK;
-        }
-        // the mask rows of a block (ny rows of ceil(nz * px / 64) words) must fit its slot / 32 words
-        auto mask_fits = [&](bool tiles) {
-            bool ok = d_nms_mask != nullptr && h_mask_written != nullptr;
-            for (int b = 0; ok && b < n_blocks; ++b) {
-                const mmx_block& hb = h_blocks[b];
-                const int64_t need = tiles ? (int64_t)hb.ny * ((hb.nz + 3) >> 2) * ((hb.nx + 15) >> 4)
-                                           : (int64_t)hb.ny * (((int64_t)hb.nz * hb.px + 63) >> 6);
-                if (need > (slot_elems >> 5) - 1) ok = false;
-            }
-            return ok;
-        };
-        { mmx_timed_scope ts(MMX_K_ZX, s);
-          rc = MMX_ERR_UNSUPPORTED;
-          if (tiled) {
-              path = q16 ? MMX_ZX_TILED_Q16 : MMX_ZX_TILED;
-              rc = mmx_launch_zx6(vol, d_blocks, h_blocks, n_blocks, plan, txx, radius, d_work,
-                                  q16 ? (float)(1.0 / q_bp) : 0.f, q16 ? (float)(1.0 / q_bq) : 0.f, s);
-              tiled = rc == MMX_OK;
-          }
-          if (rc == MMX_ERR_UNSUPPORTED) {
-              path = MMX_ZX_PACKED;
-              rc = mmx_launch_zx2(vol, d_blocks, n_blocks, max_ny, max_px, slot_elems, tzz, txx, radius, t0, t1, s);
-          } }
-        if (rc == MMX_OK && h_zx_path) *h_zx_path = path;
-        if (rc == MMX_OK) {
-            mmx_timed_scope ts(MMX_K_Y2, s);
-            const bool want_mask = mask_fits(tiled);      // (after the Z+X launch: `tiled` says which kernel ran)
-            rc = MMX_ERR_UNSUPPORTED;
-            if (tiled && q16 && !y_valu)
-                rc = mmx_launch_ym(d_blocks, n_blocks, plan, slot_elems, tyy, radius, d_work,
-                                   (float)(q_bp / 65535.0), (float)(q_bq / 32767.0), d_log,
-                                   want_mask ? (unsigned long long*)d_nms_mask : nullptr, nms_lo, nms_eps, s);
-            if (rc != MMX_ERR_UNSUPPORTED) ;
-            else if (tiled)
-                rc = mmx_launch_y6(d_blocks, n_blocks, plan, slot_elems, tyy, radius, d_work,
-                                   reinterpret_cast<const float*>(reinterpret_cast<const char*>(d_work) + plan.q_off),
-                                   q16 ? (float)(q_bp / 65535.0) : 0.f, q16 ? (float)(q_bq / 32767.0) : 0.f, d_log,
-                                   want_mask ? (unsigned long long*)d_nms_mask : nullptr, nms_lo, nms_eps, s);
-            else
-                rc = mmx_launch_y2(d_blocks, n_blocks, max_ycols, slot_elems, tyy, radius, t0, t1, d_log,
-                                   want_mask ? (unsigned long long*)d_nms_mask : nullptr, nms_lo, nms_eps, s);
-            if (rc == MMX_OK && want_mask) *h_mask_written = tiled ? MMX_MASK_QUADS : MMX_MASK_ROWS;
-        }
-        if (rc == MMX_ERR_HIP) return hip_fail(hipGetLastError(), "fused passes");
-        if (rc == MMX_OK) return MMX_OK;
-        if (rc != MMX_ERR_UNSUPPORTED) return rc;   // unsupported geometry: separate passes below
-    }
-    { mmx_timed_scope ts(fast_z ? MMX_K_ZPASS : MMX_K_GENERIC, s);
-    if (fast_z) rc = mmx_launch_zpass(vol, d_blocks, n_blocks, max_zcols, slot_elems, taps(wz0, wz2), radius, t0, t1, s);
-    else rc = mmx_launch_generic_pass(0, vol, d_blocks, n_blocks, max_vox, slot_elems, wz0, wz2, radius, nullptr, nullptr, t0, t1, s); }
-    if (rc != MMX_OK) return rc == MMX_ERR_HIP ? hip_fail(hipGetLastError(), "z pass") : rc;
-    { mmx_timed_scope ts(fast_y ? MMX_K_YPASS : MMX_K_GENERIC, s);
-    if (fast_y) rc = mmx_launch_ypass(d_blocks, n_blocks, max_ycols, slot_elems, taps(wy0, wy2), radius, t0, t1, t2, t3, s);
-    else rc = mmx_launch_generic_pass(1, vol, d_blocks, n_blocks, max_vox, slot_elems, wy0, wy2, radius, t0, t1, t2, t3, s); }
-    if (rc != MMX_OK) return rc == MMX_ERR_HIP ? hip_fail(hipGetLastError(), "y pass") : rc;
-    { mmx_timed_scope ts(fast_x ? MMX_K_XPASS : MMX_K_GENERIC, s);
-    if (fast_x) rc = mmx_launch_xpass(d_blocks, n_blocks, max_rows, max_nx, slot_elems, taps(wx0, wx2), radius, t2, t3, d_log, s);
-    else rc = mmx_launch_generic_pass(2, vol, d_blocks, n_blocks, max_vox, slot_elems, wx0, wx2, radius, t2, t3, d_log, nullptr, s); }
-    if (rc != MMX_OK) return rc == MMX_ERR_HIP ? hip_fail(hipGetLastError(), "x pass") : rc;
-    return MMX_OK;
+    mmx_batch_geom g{};
+    if (vol && h_blocks) mmx_batch_geom_make(vol, h_blocks, n_blocks, slot_elems, &g);     // (NULL: refused below, g unread)
+    return mmx_log_scale_f32({vol, d_blocks, h_blocks, n_blocks, slot_elems, h_w0, h_w2, radius, norm, d_log, d_work,
+                              d_nms_mask, nms_lo, nms_eps, h_mask_written, zx_mode, h_zx_path, (hipStream_t)stream}, g);
 }
 
 // Same as mmx_log_batch_f32 but always through the generic kernels (tests cross-check the
@@ -388,52 +455,30 @@ int mmx_log_batch_f32_generic(const mmx_volume* vol, const mmx_block* d_blocks, 
         return MMX_ERR_ARG;
     if (n_blocks < 1 || radius < 0 || radius > MMX_MAX_RADIUS_GENERIC || slot_elems < 1) return MMX_ERR_ARG;
     if (n_blocks > MMX_MAX_BLOCKS) return MMX_ERR_UNSUPPORTED;
-    double in_scale = 1.0;
-    if (vol->dtype == MMX_U8) in_scale = 1.0 / 255.0;
-    else if (vol->dtype == MMX_U16) in_scale = 1.0 / 65535.0;
-    int max_vox = 0;
-    for (int i = 0; i < n_blocks; ++i) {
-        const mmx_block& b = h_blocks[i];
-        if (b.nz < 1 || b.ny < 1 || b.nx < 1 || b.slot != i) return MMX_ERR_ARG;
-        if (b.px < b.nx || b.px % MMX_ROW_ALIGN) return MMX_ERR_ARG;
-        if ((int64_t)b.nz * b.ny * b.px > slot_elems) return MMX_ERR_WORKSPACE;
-        if (b.nz * b.ny * b.px > max_vox) max_vox = b.nz * b.ny * b.px;
-    }
+    mmx_batch_geom g;
+    mmx_batch_geom_make(vol, h_blocks, n_blocks, slot_elems, &g);
+    if (g.status != MMX_OK) return g.status;
+    pass_weights w;
+    make_weights(vol, h_w0, h_w2, radius, norm, &w);
     const int64_t n_slots = n_blocks;
     float* t0 = d_work;
     float* t1 = d_work + n_slots * slot_elems;
     float* t2 = t1 + n_slots * slot_elems;
     float* t3 = t2 + n_slots * slot_elems;
     hipStream_t s = (hipStream_t)stream;
-    float a[MMX_MAX_RADIUS_GENERIC + 1], b[MMX_MAX_RADIUS_GENERIC + 1];
-    int rc;
-    for (int k = 0; k <= radius; ++k) { a[k] = (float)(h_w0[k] * in_scale); b[k] = (float)(h_w2[k] * in_scale); }
-    rc = mmx_launch_generic_pass(0, vol, d_blocks, n_blocks, max_vox, slot_elems, a, b, radius, nullptr, nullptr, t0, t1, s);
+    int rc = mmx_launch_generic_pass(0, vol, d_blocks, n_blocks, g.max_vox, slot_elems, w.z0, w.z2, radius, nullptr, nullptr, t0, t1, s);
     if (rc != MMX_OK) return rc;
-    for (int k = 0; k <= radius; ++k) { a[k] = (float)h_w0[k]; b[k] = (float)h_w2[k]; }
-    rc = mmx_launch_generic_pass(1, vol, d_blocks, n_blocks, max_vox, slot_elems, a, b, radius, t0, t1, t2, t3, s);
+    rc = mmx_launch_generic_pass(1, vol, d_blocks, n_blocks, g.max_vox, slot_elems, w.y0, w.y2, radius, t0, t1, t2, t3, s);
     if (rc != MMX_OK) return rc;
-    for (int k = 0; k <= radius; ++k) { a[k] = (float)(-norm * h_w0[k]); b[k] = (float)(-norm * h_w2[k]); }
-    return mmx_launch_generic_pass(2, vol, d_blocks, n_blocks, max_vox, slot_elems, a, b, radius, t2, t3, d_log, nullptr, s);
+    return mmx_launch_generic_pass(2, vol, d_blocks, n_blocks, g.max_vox, slot_elems, w.x0, w.x2, radius, t2, t3, d_log, nullptr, s);
 }
 
 int mmx_zx_pack(const mmx_volume* vol, const mmx_block* d_blocks, const mmx_block* h_blocks, int n_blocks,
                 int64_t slot_elems, float* d_work, void* stream)
 {
-    if (!vol || !vol->d_data || !d_blocks || !h_blocks || !d_work || n_blocks < 1 || slot_elems < 1) return MMX_ERR_ARG;
-    if (n_blocks > MMX_MAX_BLOCKS) return MMX_ERR_UNSUPPORTED;
-    if (vol->dtype != MMX_U8 && vol->dtype != MMX_U16 && vol->dtype != MMX_F32) return MMX_ERR_UNSUPPORTED;
-    for (int i = 0; i < n_blocks; ++i) {
-        const mmx_block& b = h_blocks[i];
-        if (b.nz < 1 || b.ny < 1 || b.nx < 1 || b.slot != i) return MMX_ERR_ARG;
-        if (b.px < b.nx || b.px % MMX_ROW_ALIGN) return MMX_ERR_ARG;
-    }
-    mmx_zx6_plan plan;
-    int rc = mmx_zx6_plan_make(h_blocks, n_blocks, slot_elems, vol->dtype, &plan);
-    if (rc != MMX_OK) return rc;
-    mmx_timed_scope ts(MMX_K_ZXPACK, (hipStream_t)stream);
-    rc = mmx_launch_zx6_pack(vol, d_blocks, h_blocks, n_blocks, plan, d_work, (hipStream_t)stream);
-    return rc == MMX_ERR_HIP ? hip_fail(hipGetLastError(), "voxel copy of the tiled path") : rc;
+    mmx_batch_geom g{};
+    if (vol && h_blocks) mmx_batch_geom_make(vol, h_blocks, n_blocks, slot_elems, &g);     // (NULL: refused below, g unread)
+    return mmx_zx_pack_geom(vol, d_blocks, h_blocks, n_blocks, slot_elems, g, d_work, (hipStream_t)stream);
 }
 
 int mmx_peaks_batch(const float* d_log, const uint64_t* d_nms_mask, int mask_layout, int n_sigma, const mmx_block* d_blocks,
@@ -446,14 +491,10 @@ int mmx_peaks_batch(const float* d_log, const uint64_t* d_nms_mask, int mask_lay
     if (n_blocks > MMX_MAX_BLOCKS) return MMX_ERR_UNSUPPORTED;
     if (slot_elems % MMX_ROW_ALIGN) return MMX_ERR_ARG;
     if (d_nms_mask && mask_layout != MMX_MASK_ROWS && mask_layout != MMX_MASK_QUADS) return MMX_ERR_ARG;
-    int max_vox = 0;
-    for (int i = 0; i < n_blocks; ++i) {
-        const mmx_block& b = h_blocks[i];
-        if (b.nz < 1 || b.ny < 1 || b.nx < 1 || b.slot != i) return MMX_ERR_ARG;
-        if (b.px < b.nx || b.px % MMX_ROW_ALIGN) return MMX_ERR_ARG;
-        if ((int64_t)b.nz * b.ny * b.px > slot_elems) return MMX_ERR_WORKSPACE;
-        if (b.nz * b.ny * b.px > max_vox) max_vox = b.nz * b.ny * b.px;
-    }
+    mmx_batch_geom g;
+    mmx_batch_geom_make(nullptr, h_blocks, n_blocks, slot_elems, &g);
+    if (g.status != MMX_OK) return g.status;
+    const int max_vox = g.max_vox;
     mmx_timed_scope ts(MMX_K_PEAKS, (hipStream_t)stream);
     int rc;
     if (d_nms_mask)

@@ -72,6 +72,41 @@ int mmx_launch_y2(const mmx_block* d_blocks, int n_blocks, int max_cols, int64_t
                   const mmx_taps_f32& taps, int radius, const float* d_p, const float* d_q,
                   float* d_log, unsigned long long* d_mask, float nms_lo, float nms_eps, hipStream_t stream);
 
+// What the entry points derive from a batch's block table (mmx_batch_geom_make): nothing in it depends on sigma, so
+// a whole batch (mmx_log_scales_f32) fills it once.
+struct mmx_batch_geom {
+    // the blocks checked in table order: MMX_ERR_ARG for an extent < 1, a slot other than the block's index or a row
+    // pitch below nx / off MMX_ROW_ALIGN (bad_block: one was found, whatever came before it), MMX_ERR_WORKSPACE for a
+    // block larger than its slot; entry points return it where their own checks of the blocks stood
+    int status;
+    bool bad_block;
+    int min_nz, min_ny, min_nx, max_ny, max_nx, max_px;
+    int max_zcols, max_ycols, max_rows, max_vox;        // ny px, nz px, nz ny, nz ny px
+    int64_t max_lane_in;                                // largest (y, x) offset inside a block's input plane, in voxels
+    bool rows_fit, quads_fit;                           // every block's NMS entries fit its slot / 32 words, per layout
+    mmx_zx6_plan plan;                                  // the tiled path's share of d_work
+    int plan_status;                                    // MMX_OK: it fits
+};
+// (vol: NULL for callers that read no voxels -- no plan, no input offsets)
+void mmx_batch_geom_make(const mmx_volume* vol, const mmx_block* h_blocks, int n_blocks, int64_t slot_elems, mmx_batch_geom* g);
+
+// mmx_log_batch_f32 and mmx_zx_pack behind their mmx_batch_geom_make (mmx_api.hip): what mmx_log_scales_f32 calls.
+struct mmx_log_call {       // (the arguments of mmx_log_batch_f32)
+    const mmx_volume* vol; const mmx_block* d_blocks; const mmx_block* h_blocks; int n_blocks; int64_t slot_elems;
+    const double* h_w0; const double* h_w2; int radius; double norm;
+    float* d_log; float* d_work; uint64_t* d_nms_mask; float nms_lo, nms_eps; int* h_mask_written;
+    int zx_mode; int* h_zx_path; hipStream_t stream;
+};
+int mmx_log_scale_f32(const mmx_log_call& c, const mmx_batch_geom& g);
+int mmx_zx_pack_geom(const mmx_volume* vol, const mmx_block* d_blocks, const mmx_block* h_blocks, int n_blocks,
+                     int64_t slot_elems, const mmx_batch_geom& g, float* d_work, hipStream_t stream);
+
+// The tile choice of the tiled path, float32 or 16-bit (mmx_detect.hip, with the rest of the rules): unit_bound =
+// mmx_tiled_q16_error_bound of the scale(s) the answer is for, band = the nomination band.  *value_scale: value units
+// per unit of the [0, 1] range that bound is stated for -- 1 for integer voxels (img_as_float), m for float voxels that
+// state a range [0, m], 0 when 16-bit tiles cannot hold the voxels.
+bool mmx_tiles_q16(int zx_mode, const mmx_volume* vol, double unit_bound, double band, bool entries_wanted, double* value_scale);
+
 // ---- optional per-kernel-family timing with HIP events on the launch stream (bench.py) ----
 enum mmx_kernel_kind {
     MMX_K_ZPASS = 0, MMX_K_YPASS, MMX_K_XPASS, MMX_K_GENERIC, MMX_K_PEAKS, MMX_K_RESCORE,

@@ -1,11 +1,13 @@
-// mmx_detect_batch: one batch of blocks from voxels to the re-scored candidate table in ONE call (SURVEY.md section
-// 8b: "mmx_detect_block -- fused A0-A4").  Replaces, for the blocks of a batch, everything between the reference's
-// call `blob_log(roi, ...)` (magmap/cv/detector.py:931-933) and the point where its float64 cube values are compared:
-// img_as_float + gaussian_laplace per sigma + scale normalisation (A0-A3) and the nomination half of peak_local_max
-// (A4).  What the Python host (blob_log._enqueue_detect) used to enqueue call by call -- the voxel copy of the tiled
-// path, (Z+X, Y) per sigma with the fall-back rules between kernel paths, the counter reset, the sparse NMS, the probe
-// expansion, the exact float64 re-score, the copies of the counters and of the table's head to pinned host memory --
-// is enqueued here by native code on the caller's streams.  Nothing in it waits for the GPU.
+// The one home of a batch's kernel-path rules, and the batch in ONE call on top of them (SURVEY.md section 8b:
+// "mmx_detect_block -- fused A0-A4").  Replaces, for the blocks of a batch, everything between the reference's call
+// `blob_log(roi, ...)` (magmap/cv/detector.py:931-933) and the point where its float64 cube values are compared:
+// img_as_float + gaussian_laplace per sigma + scale normalisation (A0-A3) and the nomination half of peak_local_max (A4).
+//   mmx_log_scales_f32 : the voxel copy of the tiled path and (Z+X, Y) per sigma -- which kernel path, which tiles,
+//                        when the copy is trusted, one NMS entry layout for all scales (the rules: include/mmx.h);
+//                        mmx_tiles_q16 is the tile choice, shared with the per-call MMX_ZX_AUTO of mmx_log_batch_f32
+//   mmx_detect_batch   : that, then the tail -- counter reset, sparse NMS, probe expansion, exact float64 re-score,
+//                        the copies of the counters and of the table's head to pinned host memory, the events
+// Everything is enqueued by native code on the caller's streams.  Nothing in it waits for the GPU.
 //
 // A batch the caller runs again and again with the same arguments (a small volume detected once per step) can be
 // captured as a hipGraph by the caller (mmx_graph_*): every node's arguments are then fixed at capture time.
@@ -64,43 +66,48 @@ int after(hipStream_t a, hipStream_t b, const char* what)
     return r == hipSuccess ? MMX_OK : fail(r, what);
 }
 
-// Every scale of the batch through mmx_log_batch_f32; `layouts`: bit (1 << layout) for every NMS entry layout a call
-// reported (bit 0: none).  The rules are blob_log.py's (round 3), moved here unchanged:
-//   * the tiled path works from an operand-ordered copy of the voxels that does not depend on sigma: made once, trusted
-//     by the calls below for as long as every call so far ran the tiled path;
-//   * 16-bit intermediates when the nomination band covers their rounding error fourfold and the error in value units
-//     is inside the LoG contract (MMX_LOG_ABS_TOL) -- or when asked for by name.
-int passes(const mmx_detect_args* a, bool with_mask, int mode, float* d_log, uint64_t* d_mask, size_t mask_words,
-           unsigned* layouts, int* zx_path, double* q16_bound, bool* pack_side)
+// where the LoG arrays ([ns][nb * slot], behind the four intermediate arrays) and the NMS entries ([ns][(nb * slot) >> 5]
+// 16-byte entries, behind the LoG arrays) of a batch live in its workspace (mmx_workspace_bytes' layout)
+float* log_arrays(const mmx_detect_args* a) { return a->d_work + (size_t)4 * a->n_blocks * a->slot_elems; }
+uint64_t* nms_entries(const mmx_detect_args* a)
+{
+    const float* end = log_arrays(a) + (size_t)a->n_sigma * a->n_blocks * a->slot_elems;
+    return reinterpret_cast<uint64_t*>((reinterpret_cast<uintptr_t>(end) + 15) & ~(uintptr_t)15);
+}
+
+// One round of the rules (include/mmx.h, mmx_log_scales_f32): the voxel copy when `mode` can take the tiled path, then
+// every scale.  `layouts`: bit (1 << layout) for every NMS entry layout a scale reported (bit 0: none).
+int passes(const mmx_detect_args* a, const mmx_batch_geom& g, bool with_mask, int mode, unsigned* layouts, int* zx_path,
+           double* q16_bound, bool* pack_side)
 {
     *layouts = 0;
     const mmx_volume* vol = a->vol32;
     const bool is_float = vol->dtype == MMX_F32;
     const bool float_ok = is_float && vol->value_range != 0.f;
-    const bool nonneg = !is_float || (float_ok && vol->value_range > 0.f);
-    int tiled_mode = MMX_ZX_TILED;
     const int nb = a->n_blocks, ns = a->n_sigma;
     const int64_t slot = a->slot_elems;
     const size_t tab = MMX_MAX_RADIUS_GENERIC + 1;
-    if ((mode == MMX_ZX_AUTO || mode == MMX_ZX_TILED_Q16) && nonneg) {
+    float* d_log = log_arrays(a);
+    uint64_t* d_mask = nms_entries(a);
+    const size_t mask_words = ((size_t)nb * slot) >> 5;
+    // float32 or 16-bit tiles: one answer for the batch, from the largest bound over its scales
+    int tiled_mode = MMX_ZX_TILED;
+    if (mode == MMX_ZX_AUTO || mode == MMX_ZX_TILED_Q16) {
         double bound = 0.0;
         for (int s = 0; s < ns; ++s) {
             const double b = mmx_tiled_q16_error_bound(a->h_w0 + s * tab, a->h_w2 + s * tab, a->h_radius[s], a->h_norm[s]);
             if (b < 0) { bound = -1.0; break; }
             if (b > bound) bound = b;
         }
-        if (is_float) bound *= (double)vol->value_range;
-        const bool covers = bound >= 0.0 && 4.0 * bound <= (double)a->eps && bound <= MMX_LOG_ABS_TOL;
-        // (by name: taken whatever the band; the caller's run-time check of |float32 - float64| against eps / 4 on the
-        //  re-scored candidates is what then widens it)
-        if (mode == MMX_ZX_TILED_Q16 || covers) { tiled_mode = MMX_ZX_TILED_Q16; if (q16_bound) *q16_bound = bound; }
+        double vscale;
+        if (mmx_tiles_q16(mode, vol, bound, a->eps, true, &vscale)) { tiled_mode = MMX_ZX_TILED_Q16; *q16_bound = bound * vscale; }
     }
     bool packed = false;
     hipStream_t main = (hipStream_t)a->stream;
     if (((mode == MMX_ZX_AUTO || mode == MMX_ZX_TILED || mode == MMX_ZX_TILED_Q16) && !is_float) ||
         ((mode == MMX_ZX_AUTO || mode == MMX_ZX_TILED) && float_ok)) {
         hipStream_t ps = (*pack_side && a->pack_stream) ? (hipStream_t)a->pack_stream : main;
-        int rc = mmx_zx_pack(vol, a->d_blocks, a->h_blocks, nb, slot, a->d_work, ps);
+        int rc = mmx_zx_pack_geom(vol, a->d_blocks, a->h_blocks, nb, slot, g, a->d_work, ps);
         if (rc != MMX_OK && rc != MMX_ERR_UNSUPPORTED) return rc;
         if (ps != main) {
             const int st = after(ps, main, "voxel copy -> main stream");
@@ -111,11 +118,13 @@ int passes(const mmx_detect_args* a, bool with_mask, int mode, float* d_log, uin
     }
     for (int s = 0; s < ns; ++s) {
         int written = 0, path = 0;
-        const int rc = mmx_log_batch_f32(vol, a->d_blocks, a->h_blocks, nb, slot, a->h_w0 + s * tab, a->h_w2 + s * tab,
-                                         a->h_radius[s], a->h_norm[s], d_log + (size_t)s * nb * slot, a->d_work,
-                                         with_mask ? d_mask + (size_t)s * mask_words * 2 : nullptr, a->thr - a->eps, a->eps,
-                                         &written, packed ? (tiled_mode | MMX_ZX_PREPACKED | a->zx_flags) : mode, &path,
-                                         (void*)main);
+        // (the copy is trusted while every scale so far ran the tiled path: any other path uses that part of the
+        //  workspace for something else)
+        const int rc = mmx_log_scale_f32({vol, a->d_blocks, a->h_blocks, nb, slot, a->h_w0 + s * tab, a->h_w2 + s * tab,
+                                          a->h_radius[s], a->h_norm[s], d_log + (size_t)s * nb * slot, a->d_work,
+                                          with_mask ? d_mask + (size_t)s * mask_words * 2 : nullptr, a->thr - a->eps, a->eps,
+                                          &written, packed ? (tiled_mode | MMX_ZX_PREPACKED | a->zx_flags) : mode, &path,
+                                          main}, g);
         if (rc != MMX_OK) return rc;
         *zx_path = path;
         packed = packed && path == tiled_mode;
@@ -126,54 +135,55 @@ int passes(const mmx_detect_args* a, bool with_mask, int mode, float* d_log, uin
 
 }  // namespace
 
+bool mmx_tiles_q16(int zx_mode, const mmx_volume* vol, double unit_bound, double band, bool entries, double* value_scale)
+{
+    const bool ranged = vol->dtype == MMX_F32 && vol->value_range > 0.f && vol->value_range < 60000.f;
+    *value_scale = vol->dtype == MMX_U8 || vol->dtype == MMX_U16 ? 1.0 : (ranged ? (double)vol->value_range : 0.0);
+    if (!(*value_scale > 0.0)) return false;
+    // (by name: taken whatever the band; the caller's run-time check of |float32 - float64| against eps / 4 on the
+    //  re-scored candidates is what then widens it)
+    if (zx_mode == MMX_ZX_TILED_Q16) return true;
+    const double bound = unit_bound * *value_scale;
+    return zx_mode == MMX_ZX_AUTO && entries && bound >= 0.0 && 4.0 * bound <= band && bound <= MMX_LOG_ABS_TOL;
+}
+
 extern "C" {
 
 const char* mmx_detect_last_error(void) { return g_detect_err; }
 
-int mmx_detect_batch(const mmx_detect_args* a, mmx_detect_info* info)
+int mmx_log_scales_f32(const mmx_detect_args* a, mmx_detect_info* info)
 {
     if (!a || !info) return MMX_ERR_ARG;
     memset(info, 0, sizeof *info);
     if (!a->vol32 || !a->d_blocks || !a->h_blocks || !a->h_w0 || !a->h_w2 || !a->h_radius || !a->h_norm || !a->d_work ||
-        !a->d_cands || !a->d_count || a->n_blocks < 1 || a->n_sigma < 1 || a->slot_elems < 1 || a->cap < 1 || !(a->eps >= 0.f))
+        a->n_blocks < 1 || a->n_sigma < 1 || a->slot_elems < 1 || !(a->eps >= 0.f))
         return MMX_ERR_ARG;
-    if (a->exact && (!a->vol_exact || !a->d_w0 || !a->d_w2)) return MMX_ERR_ARG;
-    const int nb = a->n_blocks, ns = a->n_sigma;
-    const int64_t slot = a->slot_elems;
-    if (mmx_workspace_bytes(nb, slot, ns, 1) > a->work_bytes) return MMX_ERR_WORKSPACE;
+    if (mmx_workspace_bytes(a->n_blocks, a->slot_elems, a->n_sigma, 1) > a->work_bytes) return MMX_ERR_WORKSPACE;
     hipStream_t main = (hipStream_t)a->stream;
-    hipStream_t tail = a->tail_stream ? (hipStream_t)a->tail_stream : main;
-    hipError_t r;
     // the workspace may still be read by the tail of the batch that used it before
     bool pack_side = a->pack_stream != nullptr && a->pack_stream != a->stream;
     if (a->ev_work_free) {
         // (both: the voxel copy is the first writer when there is one, the passes when there is none)
-        r = hipStreamWaitEvent(main, (hipEvent_t)a->ev_work_free, 0);
+        hipError_t r = hipStreamWaitEvent(main, (hipEvent_t)a->ev_work_free, 0);
         if (r == hipSuccess && pack_side) r = hipStreamWaitEvent((hipStream_t)a->pack_stream, (hipEvent_t)a->ev_work_free, 0);
         if (r != hipSuccess) return fail(r, "wait for the workspace");
     }
-    float* d_log = a->d_work + (size_t)4 * nb * slot;
-    // NMS entries, [ns][(nb * slot) >> 5] 16-byte entries behind the LoG arrays (mmx_workspace_bytes' layout)
-    const size_t mask_words = ((size_t)nb * slot) >> 5;
-    uint64_t* d_mask = reinterpret_cast<uint64_t*>(
-        (reinterpret_cast<uintptr_t>(d_log + (size_t)ns * nb * slot) + 15) & ~(uintptr_t)15);
+    mmx_batch_geom g;
+    mmx_batch_geom_make(a->vol32, a->h_blocks, a->n_blocks, a->slot_elems, &g);
 
-    // With the entries the Y pass leaves whole segments of the cube unwritten, so it is all scales, in one layout, or
-    // none: if one scale cannot produce them (a radius outside the fused kernels, tiny blocks) or the scales ran
-    // different kernels, every scale is computed again -- with the packed kernel's entries if a scale produced those,
-    // else in full.
+    // all scales in one entry layout, or none: up to three rounds
     unsigned layouts = 0;
     int zx_path = 0;
     double q16_bound = 0.0;
-    int rc = passes(a, true, a->zx_mode, d_log, d_mask, mask_words, &layouts, &zx_path, &q16_bound, &pack_side);
+    int rc = passes(a, g, true, a->zx_mode, &layouts, &zx_path, &q16_bound, &pack_side);
     if (rc != MMX_OK) return rc;
     if (layouts == ((1u << MMX_MASK_ROWS) | (1u << MMX_MASK_QUADS))) {
-        rc = passes(a, true, MMX_ZX_PACKED, d_log, d_mask, mask_words, &layouts, &zx_path, &q16_bound, &pack_side);
+        rc = passes(a, g, true, MMX_ZX_PACKED, &layouts, &zx_path, &q16_bound, &pack_side);
         if (rc != MMX_OK) return rc;
         info->n_pass_rounds++;
     }
     if (layouts & (layouts - 1)) {       // more than one kind
-        rc = passes(a, false, a->zx_mode, d_log, d_mask, mask_words, &layouts, &zx_path, &q16_bound, &pack_side);
+        rc = passes(a, g, false, a->zx_mode, &layouts, &zx_path, &q16_bound, &pack_side);
         if (rc != MMX_OK) return rc;
         info->n_pass_rounds++;
     }
@@ -183,14 +193,30 @@ int mmx_detect_batch(const mmx_detect_args* a, mmx_detect_info* info)
     info->mask_layout = mask_layout;
     info->q16_bound = zx_path == MMX_ZX_TILED_Q16 ? q16_bound : 0.0;
     info->n_pass_rounds++;
+    return MMX_OK;
+}
+
+int mmx_detect_batch(const mmx_detect_args* a, mmx_detect_info* info)
+{
+    if (!a || !info) return MMX_ERR_ARG;
+    memset(info, 0, sizeof *info);
+    // (the tail's own arguments, before anything is enqueued)
+    if (!a->d_cands || !a->d_count || a->cap < 1) return MMX_ERR_ARG;
+    if (a->exact && (!a->vol_exact || !a->d_w0 || !a->d_w2)) return MMX_ERR_ARG;
+    int rc = mmx_log_scales_f32(a, info);
+    if (rc != MMX_OK) return rc;
+    const int nb = a->n_blocks, ns = a->n_sigma;
+    hipStream_t main = (hipStream_t)a->stream;
+    hipStream_t tail = a->tail_stream ? (hipStream_t)a->tail_stream : main;
+    hipError_t r;
 
     // ---- the tail: NMS, probes, exact values, copies (on its own stream when the caller gives one)
     rc = after(main, tail, "LoG passes -> tail stream");
     if (rc != MMX_OK) return rc;
     r = hipMemsetAsync(a->d_count, 0, 2 * sizeof(uint32_t), tail);
     if (r != hipSuccess) return fail(r, "reset of the candidate counters");
-    rc = mmx_peaks_batch(d_log, mask_layout ? d_mask : nullptr, mask_layout, ns, a->d_blocks, a->h_blocks, nb, slot,
-                         a->thr, a->eps, a->d_cands, a->cap, a->d_count, (void*)tail);
+    rc = mmx_peaks_batch(log_arrays(a), info->mask_layout ? nms_entries(a) : nullptr, info->mask_layout, ns, a->d_blocks, a->h_blocks,
+                         nb, a->slot_elems, a->thr, a->eps, a->d_cands, a->cap, a->d_count, (void*)tail);
     if (rc != MMX_OK) return rc;
     if (a->ev_work_read) {               // the workspace may be written again once the NMS has read it
         r = hipEventRecord((hipEvent_t)a->ev_work_read, tail);

@@ -45,6 +45,7 @@
 // workspace the fused path does not use) and live in registers in the main kernel, except the Z fragments of
 // the first and last z tiles, which are reloaded when the march reaches them.
 
+#include <algorithm>
 #include <type_traits>
 
 #include "mmx_common.h"
@@ -97,13 +98,6 @@ __device__ __forceinline__ rsrc4_t make_rsrc4(const void* p)
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7fffffff, 0x00020000);
 }
 
-template <int R> struct geom4 {
-    static constexpr int R8 = (R + 7) & ~7;                       // x halo rounded to the 8-voxel chunks
-    static constexpr int NKX = (16 + 2 * R8 + 31) / 32;           // k-steps of the X pass
-    static constexpr int LA = (R + 15) / 16;                      // z tiles of look-ahead / look-back
-    static constexpr int NKZ = LA + 1;                            // k-steps of the Z pass (pairs of z tiles)
-    static constexpr int NT = 2 * NKZ;                            // window tiles: U - LA .. U + LA + 1
-};
 // geometry classes actually compiled: (NKX, LA) = (1, 1) for R <= 8, (2, 1) for R <= 16, (2, 2) for R <= 24
 template <int NKX, int LA> struct cls4 {
     static constexpr int R8 = NKX == 1 ? 8 : (LA == 1 ? 16 : 24);
@@ -217,7 +211,6 @@ template <typename InT> struct pieces4;
 //   0x4400 | b  =  4 + b / 256      (float16, exponent 2^2, ulp 2^-8)
 //   0x2400 | b  =  2^-6 + b / 65536 (exponent 2^-6, ulp 2^-16)
 template <> struct pieces4<uint16_t> {
-    static constexpr int NP = 2;
     using raw_t = u4_4;
     static __device__ __forceinline__ raw_t load(rsrc4_t r, unsigned off, unsigned soff = 0)
     {
@@ -255,7 +248,6 @@ template <> struct pieces4<uint16_t> {
 // float16 pieces (256 bytes) then the low ones, v = hi + lo / 2048 -- two 16-byte loads per k-step, no unpacking
 struct presplit_t { u4_4 h, l; };
 template <> struct pieces4<float> {
-    [[maybe_unused]] static constexpr int NP = 2;
     using raw_t = presplit_t;
     static __device__ __forceinline__ raw_t load(rsrc4_t r, unsigned off, unsigned soff = 0)
     {
@@ -401,8 +393,8 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
                     sl[k] = mfma16(ones, xw[i][m][k][1], sl[k]);
                 }
             // a0 takes (hi + lo pieces) x high fragments, a1 hi pieces x low fragments (scaled by 2048), v = a0 + a1 / 2048
-            const float ca = -((pc::kBiasHi + (pc::NP == 2 ? pc::kBiasLo : 0.f)) * sh[0][0] + pc::kBiasHi * sl[0][0] * kLoInv);
-            const float cb = -((pc::kBiasHi + (pc::NP == 2 ? pc::kBiasLo : 0.f)) * sh[1][0] + pc::kBiasHi * sl[1][0] * kLoInv);
+            const float ca = -((pc::kBiasHi + pc::kBiasLo) * sh[0][0] + pc::kBiasHi * sl[0][0] * kLoInv);
+            const float cb = -((pc::kBiasHi + pc::kBiasLo) * sh[1][0] + pc::kBiasHi * sl[1][0] * kLoInv);
             a_start[i] = (f4_4){ca, ca, ca, ca};
             b_start[i] = (f4_4){cb, cb, cb, cb};
         }
@@ -525,7 +517,7 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
                         // (float voxels: the low piece carries x 2048 like the low fragments; low x low is 2^-22 of a product)
                         a1 = mfma16(dl[m], xw[w][m][0][0], a1);
                         b1 = mfma16(dl[m], xw[w][m][1][0], b1);
-                    } else if constexpr (pc::NP == 2) {
+                    } else {
                         a0 = mfma16(dl[m], xw[w][m][0][0], a0);
                         b0 = mfma16(dl[m], xw[w][m][1][0], b0);
                         // (low voxel byte x low weight piece: <= 2^-19 of a product.  The float32 tiles keep it; the 16-bit
@@ -882,6 +874,28 @@ zx6_pack_f32_kernel(const float* __restrict__ vol, int64_t stride_z, int64_t str
     }
 }
 
+// The distinct block widths / depths of a batch (the Toeplitz tables hold one set of fragments per class) and its
+// tile extents; false: more classes than MMX_ZX4_MAXCLS.
+struct zx_classes {
+    int ncw, ncz, wcls[MMX_ZX4_MAXCLS], zcls[MMX_ZX4_MAXCLS];
+    int maxcol, maxu;       // column tiles / z tiles of the widest / deepest block
+};
+bool collect_classes(const mmx_block* h_blocks, int n_blocks, zx_classes* c)
+{
+    c->ncw = c->ncz = c->maxcol = c->maxu = 0;
+    for (int i = 0; i < n_blocks; ++i) {
+        const mmx_block& b = h_blocks[i];
+        int j;
+        for (j = 0; j < c->ncw && c->wcls[j] != b.nx; ++j) {}
+        if (j == c->ncw) { if (j == MMX_ZX4_MAXCLS) return false; c->wcls[c->ncw++] = b.nx; }
+        for (j = 0; j < c->ncz && c->zcls[j] != b.nz; ++j) {}
+        if (j == c->ncz) { if (j == MMX_ZX4_MAXCLS) return false; c->zcls[c->ncz++] = b.nz; }
+        c->maxcol = std::max(c->maxcol, (b.nx + 15) / 16);
+        c->maxu = std::max(c->maxu, (b.nz + 15) / 16);
+    }
+    return true;
+}
+
 template <int NKX, int LA>
 int launch_zx6(const mmx_volume* vol, const mmx_block* d_blocks, const mmx_block* h_blocks, int n_blocks,
                const mmx_zx6_plan& plan, const mmx_taps_f32& tx, int radius, void* d_work, float qp, float qq, hipStream_t s)
@@ -893,31 +907,26 @@ int launch_zx6(const mmx_volume* vol, const mmx_block* d_blocks, const mmx_block
     // the pieces carry v / 2^16 of the widened voxel: skimage's img_as_float scale on top
     cfg.xscale = vol->dtype == MMX_U16 ? (float)(65536.0 / 65535.0) :
                  (vol->dtype == MMX_U8 ? (float)(65536.0 / (255.0 * 256.0)) : 1.f);      // (float voxels: as they are)
-    cfg.ncw = cfg.ncz = 0;
     cfg.staged = 2;
     cfg.qp = qp; cfg.qq = qq;
-    cfg.maxcol = cfg.maxu = 0;
     // two column tiles per wave (zx4_kernel's NTW): 16-bit tiles of integer voxels, 8 < radius <= 16; tile rows past
     // the block are not stored (the A/B runs of both: profiles/r04_zx_experiments.txt)
     const bool pair = NKX == 2 && LA == 1 && qp > 0.f && vol->dtype != MMX_F32;
     cfg.ntw = pair ? 2 : 1;
+    zx_classes cl;
+    if (!collect_classes(h_blocks, n_blocks, &cl)) return MMX_ERR_UNSUPPORTED;
+    cfg.ncw = cl.ncw; cfg.ncz = cl.ncz; cfg.maxcol = cl.maxcol; cfg.maxu = cl.maxu;
+    for (int j = 0; j < MMX_ZX4_MAXCLS; ++j) {
+        cfg.wcls[j] = j < cl.ncw ? cl.wcls[j] : -1;
+        cfg.zcls[j] = j < cl.ncz ? cl.zcls[j] : -1;
+    }
     int max_waves = 0;
     for (int i = 0; i < n_blocks; ++i) {
         const mmx_block& b = h_blocks[i];
         if (b.nx < radius || b.nz < radius) return MMX_ERR_UNSUPPORTED;       // single reflection
-        int j;
-        for (j = 0; j < cfg.ncw && cfg.wcls[j] != b.nx; ++j) {}
-        if (j == cfg.ncw) { if (j == MMX_ZX4_MAXCLS) return MMX_ERR_UNSUPPORTED; cfg.wcls[cfg.ncw++] = b.nx; }
-        for (j = 0; j < cfg.ncz && cfg.zcls[j] != b.nz; ++j) {}
-        if (j == cfg.ncz) { if (j == MMX_ZX4_MAXCLS) return MMX_ERR_UNSUPPORTED; cfg.zcls[cfg.ncz++] = b.nz; }
-        const int ntx = (b.nx + 15) / 16, ntz = (b.nz + 15) / 16;
-        if (ntx > cfg.maxcol) cfg.maxcol = ntx;
-        if (ntz > cfg.maxu) cfg.maxu = ntz;
-        const int per_row = pair ? (ntx + 1) / 2 : ntx;
-        if (b.ny * per_row > max_waves) max_waves = b.ny * per_row;
+        const int ntx = (b.nx + 15) / 16;
+        max_waves = std::max(max_waves, b.ny * (pair ? (ntx + 1) / 2 : ntx));
     }
-    for (int j = cfg.ncw; j < MMX_ZX4_MAXCLS; ++j) cfg.wcls[j] = -1;
-    for (int j = cfg.ncz; j < MMX_ZX4_MAXCLS; ++j) cfg.zcls[j] = -1;
     const int nx_entries = cfg.ncw * cfg.maxcol * NKX * 2;
     const int nz_entries = cfg.ncz * cfg.maxu * cg::NKZ * 2;
     const size_t xbytes = (size_t)nx_entries * 2 * 64 * sizeof(u4_4);
@@ -964,24 +973,18 @@ int mmx_zx6_plan_make(const mmx_block* h_blocks, int n_blocks, int64_t slot_elem
 {
     const int pieces = voxel_dtype == MMX_F32 ? 2 : 1;        // float voxels: two float16 pieces per voxel in the copy
     int64_t tile = 0, pk = 0;
-    int max_tiles = 0, max_rowtiles = 0, maxcol = 0, maxu = 0;
-    int wcls[MMX_ZX4_MAXCLS], zcls[MMX_ZX4_MAXCLS], ncw = 0, ncz = 0;
+    int max_tiles = 0, max_rowtiles = 0;
+    zx_classes cl;
+    if (!collect_classes(h_blocks, n_blocks, &cl)) return MMX_ERR_UNSUPPORTED;
     for (int i = 0; i < n_blocks; ++i) {
         const mmx_block& b = h_blocks[i];
         if (b.px > 512) return MMX_ERR_UNSUPPORTED;
-        int j;
-        for (j = 0; j < ncw && wcls[j] != b.nx; ++j) {}
-        if (j == ncw) { if (j == MMX_ZX4_MAXCLS) return MMX_ERR_UNSUPPORTED; wcls[ncw++] = b.nx; }
-        for (j = 0; j < ncz && zcls[j] != b.nz; ++j) {}
-        if (j == ncz) { if (j == MMX_ZX4_MAXCLS) return MMX_ERR_UNSUPPORTED; zcls[ncz++] = b.nz; }
         const int ntx = (b.nx + 15) / 16, ntz = (b.nz + 15) / 16, nch8 = (b.nx + 7) / 8;
         const int64_t te = (int64_t)ntx * ntz * b.ny * 256, pe = (int64_t)b.ny * ntz * nch8 * 128 * pieces;
         if (te > tile) tile = te;
         if (pe > pk) pk = pe;
         if (ntx * ntz > max_tiles) max_tiles = ntx * ntz;
         if (b.ny * ntz > max_rowtiles) max_rowtiles = b.ny * ntz;
-        if (ntx > maxcol) maxcol = ntx;
-        if (ntz > maxu) maxu = ntz;
     }
     if (tile * 4 >= (int64_t(1) << 31) || pk * 2 >= (int64_t(1) << 31)) return MMX_ERR_UNSUPPORTED;   // 32-bit offsets in a block
     plan->tile_stride = tile;
@@ -989,7 +992,7 @@ int mmx_zx6_plan_make(const mmx_block* h_blocks, int n_blocks, int64_t slot_elem
     plan->q_off = (int64_t)n_blocks * tile * 4;
     plan->tab_off = 2 * plan->q_off;
     // the largest tables any radius class needs: widths x columns x 2 k-steps, depths x z tiles x 3, two kernels each
-    plan->tab_bytes = (int64_t)(ncw * maxcol * 2 * 2 + ncz * maxu * 3 * 2) * 2 * 64 * 16;
+    plan->tab_bytes = (int64_t)(cl.ncw * cl.maxcol * 2 * 2 + cl.ncz * cl.maxu * 3 * 2) * 2 * 64 * 16;
     plan->pack_off = (plan->tab_off + plan->tab_bytes + 255) & ~int64_t(255);
     plan->max_tiles = max_tiles;
     plan->max_rowtiles = max_rowtiles;

@@ -1165,8 +1165,10 @@ def _peaks_of(bl, dvol, g, stats=None):
 @pytest.mark.parametrize("case", ["u16_5sigma", "u8_3sigma", "f32_2sigma", "f64_2sigma", "u16_thin", "u16_empty"])
 def test_one_native_call_per_batch_equals_the_call_by_call_form(gpu, case, monkeypatch):
     """``mmx_detect_batch`` (SURVEY.md 8b's fused A0-A4 entry: voxel copy, every scale, NMS, probes, exact re-score and
-    the copies enqueued by native code) against the same launches made one ctypes call at a time from Python, and
-    against the real scikit-image: ordered peaks, bit-equal float64 values, pruned blobs."""
+    the copies enqueued by native code) against the call-by-call form, and against the real scikit-image: ordered
+    peaks, bit-equal float64 values, pruned blobs.  Both forms take the scales' kernel paths from the same native rules
+    (``mmx_log_scales_f32``); what this still cross-checks independently is the tail, the events and the streams, which
+    the call-by-call form enqueues one ctypes call at a time from Python."""
     from magellanmapper_amd import blob_log as bl
     g = load_golden("bloblog_%s.npz" % case)
     dvol = bl.DeviceVolume(g["volume"])
@@ -1272,6 +1274,15 @@ def test_detect_batch_through_the_abi(gpu):
     ev.synchronize()
     assert info.zx_path == nat.MMX_ZX_TILED_Q16 and info.mask_layout == nat.MMX_MASK_QUADS and info.n_pass_rounds == 1
     assert 0 < info.q16_bound <= 3.0e-5
+    # its first half as an entry of its own (no table, no counters, no exact volume): the same report
+    half = args(cap)
+    half.vol_exact = half.d_w0 = half.d_w2 = half.d_cands = half.d_count = half.h_count = half.h_cands = None
+    half.cap = half.exact = half.expand = 0
+    half.ev_done = None
+    info2 = nat.DetectInfo()
+    nat.check(L.mmx_log_scales_f32(ctypes.byref(half), ctypes.byref(info2)), "mmx_log_scales_f32")
+    assert ((info2.zx_path, info2.mask_layout, info2.n_pass_rounds, info2.q16_bound) ==
+            (info.zx_path, info.mask_layout, info.n_pass_rounds, info.q16_bound))
     n_all, n_cands = (int(v) for v in h_count.numpy().view(np.uint32))
     assert 0 < n_cands <= n_all <= cap
     cands = h_table.numpy()[:n_all * nat.CAND_DTYPE.itemsize].view(nat.CAND_DTYPE)

@@ -44,6 +44,38 @@ def test_argument_validation_without_gpu():
                                  _native.as_double_ptr(w), 2, 1.0, None, None, None, 0.0, 0.0, None, -1, None, None) == 1
 
 
+def test_log_scales_argument_validation_without_gpu():
+    """``mmx_log_scales_f32`` refuses what ``mmx_detect_batch`` refuses, with the same statuses, before anything is
+    dereferenced or enqueued -- and does not ask for the tail's fields (table, counters, exact volume, device tables)."""
+    lib = _native.lib()
+    info = _native.DetectInfo()
+    assert lib.mmx_log_scales_f32(None, ctypes.byref(info)) == 1
+    assert lib.mmx_log_scales_f32(ctypes.byref(_native.DetectArgs()), None) == 1
+    vol = _native.Volume(0, 1, 0, 1, 1, 1)
+    mem = np.zeros(64)                              # (never read: every case below fails a check first)
+
+    def args(**changed):
+        a = _native.DetectArgs()
+        a.vol32 = ctypes.pointer(vol)
+        for name in ("d_blocks", "h_blocks", "h_w0", "h_w2", "h_radius", "h_norm", "d_work"):
+            setattr(a, name, mem.ctypes.data)
+        a.n_blocks, a.n_sigma, a.slot_elems, a.work_bytes = 1, 2, 64, 1 << 20
+        a.thr, a.eps, a.zx_mode = 0.1, 1e-4, -1
+        for name, value in changed.items():
+            setattr(a, name, value)
+        return a
+    for both in (lib.mmx_log_scales_f32, lib.mmx_detect_batch):
+        for name in ("h_w0", "h_w2", "h_radius", "h_norm", "h_blocks", "d_blocks", "d_work"):
+            assert both(ctypes.byref(args(**{name: None})), ctypes.byref(info)) == 1, name
+        assert both(ctypes.byref(args(n_sigma=0)), ctypes.byref(info)) == 1
+        assert both(ctypes.byref(args(n_blocks=0)), ctypes.byref(info)) == 1
+    # (the tail's fields are all NULL above: mmx_detect_batch stops at them, the scales alone go on to the workspace)
+    small = lib.mmx_workspace_bytes(1, 64, 2, 1) - 1
+    assert lib.mmx_log_scales_f32(ctypes.byref(args(work_bytes=small)), ctypes.byref(info)) == 4
+    full = args(work_bytes=small, d_cands=mem.ctypes.data, d_count=mem.ctypes.data, cap=8)
+    assert lib.mmx_detect_batch(ctypes.byref(full), ctypes.byref(info)) == 4
+
+
 def test_product_path_never_imports_the_oracle():
     pkg = os.path.join(ROOT, "magellanmapper_amd")
     for fn in os.listdir(pkg):
