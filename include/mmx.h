@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MMX_ABI_VERSION 18
+#define MMX_ABI_VERSION 19
 
 typedef enum {
     MMX_OK = 0,
@@ -603,37 +603,39 @@ int mmx_host_prune_axis(const int32_t* zyx, const int32_t* tag, double* abs_zyx,
                         int64_t* out_cur, int64_t* out_n,
                         int64_t* n_slab, int64_t* n_after, int64_t* n_next);
 
-/* Output assembly of the same step: out[i] = table[rows[i]][:n_cols] with the three absolute-coordinate
- * columns taken from the compact (n_table, 3) array the axis steps updated (the reference's
- * `blobs_all[:, :-3]` after pruning, stack_detect.py:858-861).  table: float64, row pitch ld. */
-int mmx_host_take_rows(const double* table, int64_t ld, const int64_t* rows, int64_t n,
-                       int64_t n_cols, const double* abs_zyx, const int32_t abs_cols[3], double* out);
-/* ... and with the reference's last two steps on the pruned table folded in (magmap/cv/stack_detect.py:455-470:
+/* ---- Rows out of the merged table: what ends every step (ABI v19: four entry points over one layout).
+ * Which columns of a source row leave, and where its three absolute coordinates go:
+ *   src_cols : n_out source columns, each inside the row; NULL = columns 0 .. n_out - 1 as they are (a plain copy of
+ *              the row's head, n_out <= ld)
+ *   abs_dst  : the three output columns the absolute coordinates are written to AFTER the copy, each < n_main
+ *   n_main   : read where an entry is given a second table (`out_rest` not NULL) only: columns [0, n_main) of the
+ *              layout go to `out` (row pitch n_main), the other n_out - n_main >= 1 to `out_rest` (row pitch
+ *              n_out - n_main); one table: `out` has row pitch n_out.
+ * Two layouts are in use.  The plain one -- src_cols NULL, n_out = the table's columns without its three tag columns,
+ * abs_dst = the registry's abs columns -- is the reference's `blobs_all[:, :-3]` after pruning (magmap/cv/
+ * stack_detect.py:858-861).  The final one folds the reference's last two steps on the pruned table in (:455-470:
  * `replace_rel_with_abs_blob_coords`, `remove_abs_blob_coords(True)` -- two more passes over the whole table when made
- * afterwards): out[i][j] = table[rows[i]][src_cols[j]], j < n_out (3..64), then out[i][abs_dst0 .. abs_dst0 + 3] =
- * abs_zyx[rows[i]].  mmx_host_gather_parts_by_key_final: the same for mmx_host_gather_by_key, on the concatenation of
- * n_parts survivor lists (ids[p], keys[p], abs_rows[p]: n_rows[p] entries each) that nobody has to concatenate;
- * out_rows must equal their total. */
-int mmx_host_take_rows_final(const double* table, int64_t ld, const int64_t* rows, int64_t n,
-                             const int32_t* src_cols, int32_t n_out, const double* abs_zyx, int32_t abs_dst0,
-                             double* out);
-int mmx_host_gather_parts_by_key_final(const double* table, int64_t ld, int32_t n_parts, const int64_t* const* ids,
-                                       const int64_t* const* keys, const double* const* abs_rows,
-                                       const int64_t* n_rows, int64_t n_keys, const int32_t* src_cols, int32_t n_out,
-                                       int32_t abs_dst0, double* out, int64_t out_rows);
-/* ... with the output in TWO tables (ABI v16): columns [0, n_main) of the layout into `out` (row pitch n_main,
- * abs_dst0 + 3 <= n_main), the other n_out - n_main into `out_rest` (row pitch n_out - n_main).  A stack detected with
- * co-localisation ends as eight final columns plus the columns its flags are read from -- `segments_all[:, 10:10 + C]`,
- * magmap/cv/stack_detect.py:463-464 -- and both leave the one pass that gathers the surviving rows.  out_rest NULL:
- * the plain form above. */
-int mmx_host_take_rows_split(const double* table, int64_t ld, const int64_t* rows, int64_t n,
-                             const int32_t* src_cols, int32_t n_out, const double* abs_zyx, int32_t abs_dst0,
-                             double* out, int32_t n_main, double* out_rest);
-int mmx_host_gather_parts_by_key_split(const double* table, int64_t ld, int32_t n_parts, const int64_t* const* ids,
-                                       const int64_t* const* keys, const double* const* abs_rows,
-                                       const int64_t* n_rows, int64_t n_keys, const int32_t* src_cols, int32_t n_out,
-                                       int32_t abs_dst0, double* out, int64_t out_rows, int32_t n_main,
-                                       double* out_rest);
+ * afterwards): src_cols = the named columns without the abs ones, abs_dst = where the rel columns are among them; a
+ * stack detected with co-localisation adds the columns its flags are read from (`segments_all[:, 10:10 + C]`, :463-464)
+ * behind them, n_main = 8, and they leave beside the table in the one pass that gathers the surviving rows. */
+typedef struct {
+    const int32_t* src_cols;
+    int64_t n_out, n_main;
+    int32_t abs_dst[3];
+} mmx_row_layout;
+/* mmx_host_take_rows: out[i] = row rows[i] of `table` (float64, row pitch ld) in `layout`, the absolute coordinates from
+ *   abs_zyx[rows[i]] -- the compact (n_table, 3) array the axis passes updated.
+ * mmx_host_gather_parts_by_key: the same for survivors in n_parts lists that nobody has to concatenate (ids[p], keys[p],
+ *   abs_rows[p][..][3]: n_rows[p] entries each; one list: n_parts = 1): row ids[p][i] with the coordinates abs_rows[p][i]
+ *   lands at its place in the stable sort of the concatenated lists by key (0 <= key < n_keys <= 2^26); out_rows must
+ *   equal the lists' total.
+ * Negative row ids are refused. */
+int mmx_host_take_rows(const double* table, int64_t ld, const int64_t* rows, int64_t n, const double* abs_zyx,
+                       const mmx_row_layout* layout, double* out, double* out_rest);
+int mmx_host_gather_parts_by_key(const double* table, int64_t ld, int32_t n_parts, const int64_t* const* ids,
+                                 const int64_t* const* keys, const double* const* abs_rows, const int64_t* n_rows,
+                                 int64_t n_keys, const mmx_row_layout* layout, double* out, int64_t out_rows,
+                                 double* out_rest);
 
 /* All three axis passes of the pruning for one REGION of the stack (the whole stack, one rank's blocks, or a group
  * of blocks pruned while the GPU still works on later ones): a table holding the region's own rows (ids
@@ -645,11 +647,7 @@ int mmx_host_gather_parts_by_key_split(const double* table, int64_t ld, int32_t 
  *   cur[n_cur]: rows of one channel (own and halo), table order; n_sections[a] <= 1: no pass on axis a
  *   bounds / nxt_lo / nxt_hi / last_end / tol: as for mmx_host_prune_axis, per axis
  *   out_rows / out_keys / *out_n: own survivors in final order; abs_zyx updated in place
- *   n_slab / n_after / n_next: [3][stat_ld] statistics over OWN rows
- * mmx_host_merge_by_key: out = the stable sort by key of rows[n][ld] (first n_cols columns), keys < n_keys; keys == NULL:
- *   a row's key is the value in its column n_cols.
- * mmx_host_gather_by_key: the same for survivors still in the merged table: row ids[i], its three abs columns
- *   replaced by abs_rows[i][3]. */
+ *   n_slab / n_after / n_next: [3][stat_ld] statistics over OWN rows */
 int mmx_host_prune_region(const int32_t* zyx, const int32_t* tag, double* abs_zyx, const int64_t* cur, int64_t n_cur,
                           int64_t own_lo, int64_t own_hi, const int32_t n_sections[3], const double* const bounds[3],
                           const double last_end[3], const int32_t tol[3], const double* const nxt_lo[3],
@@ -660,7 +658,8 @@ int mmx_host_prune_region(const int32_t* zyx, const int32_t* tag, double* abs_zy
  * [box_lo, box_hi) take part; every channel of `channels` in turn (chan: the table's channel column, pitch chan_ld
  * doubles, or NULL = all rows are channels[0]); out_ids: the region's survivors as rows of the merged table,
  * out_keys: channel position x n_keys + key, out_abs: their averaged coordinates [..][3]; the merged table itself is
- * not written to.  Statistics [n_channels][3][stat_ld].  (out_keys of mmx_host_prune_region may be NULL.) */
+ * not written to -- one of the lists mmx_host_gather_parts_by_key and mmx_host_emit_parts take.  Statistics
+ * [n_channels][3][stat_ld].  (out_keys of mmx_host_prune_region may be NULL.) */
 int mmx_host_prune_parts(const int32_t* zyx, const int32_t* tag, const double* abs_zyx, const double* chan,
                          int64_t chan_ld, const int64_t* parts, int n_parts, int own_part, const int32_t box_lo[3],
                          const int32_t box_hi[3], const double* channels, int n_channels,
@@ -673,8 +672,11 @@ int mmx_host_prune_parts(const int32_t* zyx, const int32_t* tag, const double* a
  *   row (zyx, block tag, abs zyx, channel) -- the payload of the first exchange; *out_n keeps counting past cap;
  * mmx_host_append_rows: the rows of a received payload inside this rank's box, appended to its compact columns from row
  *   `at` on (MMX_ERR_WORKSPACE when they do not fit `cap` rows; *out_n says how many there are);
- * mmx_host_emit_survivors: rows ids[i] of the merged table with their averaged abs columns and their sort key as an
- *   extra last column -- the payload of the second exchange.
+ * mmx_host_emit_parts: the survivor lists of a rank's regions (as for mmx_host_gather_parts_by_key) in the lists' order,
+ *   in `layout` (one table) with the sort key appended: out[out_rows][n_out + 1] -- the payload of the second exchange;
+ * mmx_host_merge_parts_by_key: the stable sort by key of the concatenation of n_parts row blocks that nobody has to
+ *   concatenate (parts[p]: n_rows[p] rows of pitch ld; the first n_cols columns leave, the key is the value in column
+ *   n_cols < ld) -- what an all_gather of those payloads, padded to the longest, leaves: out[out_rows][n_cols].
  * (mmx_host_prune_parts takes its parts in LOCAL order: a rank lists the halo rows of earlier ranks, its own rows, the
  *  halo rows of later ranks, wherever they sit in its arrays.) */
 int mmx_host_rows_in_boxes(const int32_t* zyx, const int32_t* tag, const double* abs_zyx, const double* chan,
@@ -683,25 +685,11 @@ int mmx_host_rows_in_boxes(const int32_t* zyx, const int32_t* tag, const double*
 int mmx_host_append_rows(const double* payload, int64_t n, const int32_t lo[3], const int32_t hi[3], int32_t* zyx,
                          int32_t* tag, double* abs_zyx, double* chan, int64_t chan_ld, int64_t at, int64_t cap,
                          int64_t* out_n);
-int mmx_host_emit_survivors(const double* table, int64_t ld, const int64_t* ids, const int64_t* keys, int64_t n,
-                            int64_t n_cols, const double* abs_rows, const int32_t abs_cols[3], double* out);
-/* ... in the final columns (src_cols / abs_dst0 as for mmx_host_take_rows_final): out[i][n_out + 1], the key last. */
-int mmx_host_emit_survivors_final(const double* table, int64_t ld, const int64_t* ids, const int64_t* keys, int64_t n,
-                                  const int32_t* src_cols, int32_t n_out, const double* abs_rows, int32_t abs_dst0,
-                                  double* out);
-/* ... for n_parts survivor lists at once, in order (a rank's regions): out[out_rows][n_out + 1]. */
-int mmx_host_emit_parts_final(const double* table, int64_t ld, int32_t n_parts, const int64_t* const* ids,
-                              const int64_t* const* keys, const double* const* abs_rows, const int64_t* n_rows,
-                              const int32_t* src_cols, int32_t n_out, int32_t abs_dst0, double* out, int64_t out_rows);
-int mmx_host_merge_by_key(const double* rows, int64_t ld, const int64_t* keys, int64_t n, int64_t n_keys,
-                          int64_t n_cols, double* out);
-/* ... on the concatenation of n_parts row blocks (parts[p]: n_rows[p] rows of pitch ld, the key in column n_cols) that
- * nobody has to concatenate -- what an all_gather of the ranks' survivors, padded to the longest block, leaves. */
+int mmx_host_emit_parts(const double* table, int64_t ld, int32_t n_parts, const int64_t* const* ids,
+                        const int64_t* const* keys, const double* const* abs_rows, const int64_t* n_rows,
+                        const mmx_row_layout* layout, double* out, int64_t out_rows);
 int mmx_host_merge_parts_by_key(const double* const* parts, const int64_t* n_rows, int32_t n_parts, int64_t ld,
                                 int64_t n_keys, int64_t n_cols, double* out, int64_t out_rows);
-int mmx_host_gather_by_key(const double* table, int64_t ld, const int64_t* ids, const int64_t* keys, int64_t n,
-                           int64_t n_keys, int64_t n_cols, const double* abs_rows, const int32_t abs_cols[3],
-                           double* out);
 
 /* out[i][dst_col0 + j] = table[i][src_cols[j]], i < n, j < n_map (<= 64), threaded.  The column shuffles that
  * end a stack detection (reference magmap/cv/stack_detect.py:461-467 -> detector.py
@@ -762,12 +750,13 @@ int mmx_host_coloc_flags(const double* means, const int32_t* mean_channels, int3
 /* A small stack -- all blocks in ONE batch: the GUI's ROI, a grid-search step (magmap/cv/detector.py:931-933 once per
  * ROI; gui/visualizer.py:2758, io/cli.py:1111-1151) -- from the re-scored candidate table to the final table in one call
  * (ABI v16): mmx_host_resolve_peaks -> mmx_host_overlap_prune -> mmx_host_emit_tables (rows from 0 on) ->
- * mmx_host_prune_region over the whole table -> mmx_host_take_rows_final, each with the meaning of its own entry point.
+ * mmx_host_prune_region over the whole table -> mmx_host_take_rows, each with the meaning of its own entry point.
  *   cands .. n_sigma, thr : as for mmx_host_resolve_peaks; eps: the nomination band (max |f32 - f64| must stay < eps / 4)
  *   sigmas, overlap, overlap_band : as for mmx_host_overlap_prune
  *   channel .. any_before : as for mmx_host_emit_tables[_multi] (one channel; capacity rows in store / zyx / tag / abs)
  *   n_sections .. stat_ld : as for mmx_host_prune_region (own rows = all rows)
- *   src_cols, n_out, abs_dst0, out[out_capacity][n_out], *out_rows : as for mmx_host_take_rows_final
+ *   src_cols, n_out, abs_dst0 : a layout of final columns for mmx_host_take_rows (one table, abs_dst = abs_dst0 .. + 2);
+ *   out[out_capacity][n_out], *out_rows : the table and its rows
  *   stats[8] : contested candidates, peaks, max |f32 - f64|, constant cubes, overlap pairs, blobs after the per-block
  *              prune, and [6] = why the call returned MMX_DEFERRED: 1 equal peak values in a block (NumPy's argsort
  *              order decides), 2 the band is too narrow (or a non-finite value), 3 a knife-edge overlap fraction or a

@@ -530,256 +530,210 @@ extern "C" int mmx_host_prune_parts(const int32_t* zyx, const int32_t* tag, cons
     return MMX_OK;
 }
 
-// Final table of a stack from the survivors of its regions: the stable sort of the concatenated rows (regions in
-// order) by key.  `keys` are small (the product of the three group counts): a counting sort.
-//   rows : [n][ld] float64, the first n_cols columns are copied; out : [n][n_cols]
-extern "C" int mmx_host_merge_by_key(const double* rows, int64_t ld, const int64_t* keys, int64_t n, int64_t n_keys,
-                                     int64_t n_cols, double* out)
+// ------------------------------------------------------------------------------------------------------------------
+// Rows out of the merged table -- what ends every step.  Four entry points (rows by id; survivor lists in key order;
+// survivor lists in their own order, the key appended; dense row blocks in key order) over ONE column layout with ONE
+// check and ONE row writer, ONE threaded walk over the concatenation of several lists and ONE stable counting sort.
+namespace {
+// The one check of an mmx_row_layout against a table of row pitch `ld`; L = the layout with n_main settled (without
+// a second table every column belongs to the first).
+int check_layout(const mmx_row_layout* in, int64_t ld, bool two_tables, mmx_row_layout& L)
 {
-    // keys == nullptr: a row's key is the value in its column n_cols (how the ranks' survivors arrive: the key rides
-    // behind the columns) -- no separate key array has to be pulled out of the table first
-    if (n < 0 || n_keys < 1 || n_cols < 1 || n_cols > ld || (!keys && n_cols >= ld) || (n && (!rows || !out)))
-        return MMX_ERR_ARG;
-    if (n_keys > (int64_t(1) << 26)) return MMX_ERR_UNSUPPORTED;
-    if (n == 0) return MMX_OK;
-    // threaded counting sort: every thread counts the keys of one contiguous run of rows, the runs' counts are laid end
-    // to end per key, every thread places its own rows (rows of one key keep their order)
-    int T = host_threads(n);
-    if ((int64_t)T * n_keys > (int64_t(1) << 24)) T = 1;
-    std::vector<int64_t> at((size_t)T * (size_t)n_keys, 0);
-    std::vector<int> bad((size_t)T, 0);
-    auto key_of = [&](int64_t i) -> int64_t {
-        if (keys) return keys[i];
-        const double v = rows[i * ld + n_cols];
-        return (v >= 0.0 && v < 9.0e15) ? (int64_t)v : -1;
-    };
-    parallel(T, [&](int t, int) {
-        int64_t* h = at.data() + (size_t)t * (size_t)n_keys;
-        for (int64_t i = n * t / T; i < n * (t + 1) / T; ++i) {
-            const int64_t k = key_of(i);
-            if (k < 0 || k >= n_keys) { bad[(size_t)t] = 1; break; }
-            ++h[k];
-        }
-    });
-    for (int t = 0; t < T; ++t)
-        if (bad[(size_t)t]) return MMX_ERR_ARG;
-    {
-        int64_t run = 0;
-        for (int64_t k = 0; k < n_keys; ++k)
-            for (int t = 0; t < T; ++t) {
-                int64_t& c = at[(size_t)t * (size_t)n_keys + (size_t)k];
-                const int64_t here = c;
-                c = run;
-                run += here;
-            }
-    }
-    parallel(T, [&](int t, int) {
-        int64_t* pos = at.data() + (size_t)t * (size_t)n_keys;
-        for (int64_t i = n * t / T; i < n * (t + 1) / T; ++i)
-            std::memcpy(out + pos[key_of(i)]++ * n_cols, rows + i * ld, (size_t)n_cols * sizeof(double));
-    });
+    if (!in || in->n_out < 1 || (!in->src_cols && in->n_out > ld)) return MMX_ERR_ARG;
+    L = *in;
+    if (!two_tables) L.n_main = L.n_out;
+    else if (L.n_main >= L.n_out) return MMX_ERR_ARG;          // (a second table with no column of its own)
+    for (int a = 0; a < 3; ++a)
+        if (L.abs_dst[a] < 0 || L.abs_dst[a] >= L.n_main) return MMX_ERR_ARG;
+    if (L.src_cols)
+        for (int64_t j = 0; j < L.n_out; ++j)
+            if (L.src_cols[j] < 0 || L.src_cols[j] >= ld) return MMX_ERR_ARG;
     return MMX_OK;
 }
 
-// mmx_host_merge_by_key on the CONCATENATION of n_parts row blocks (every rank's survivors as an all_gather leaves
-// them: padded to the longest block, so not contiguous), keys in column n_cols of each row -- without the 20 MB copy
-// that would make them one array.  Blocks are cut into segments so that every thread has work whatever their number.
+// The one writer of an output row: `src` in the columns of L, the absolute coordinates from abs3[3]; columns from
+// n_main on into o_rest where there is a second table.
+inline void write_row(const mmx_row_layout& L, const double* src, const double* abs3, double* o, double* o_rest)
+{
+    const int64_t n_rest = o_rest ? L.n_out - L.n_main : 0;
+    if (!L.src_cols) {
+        std::memcpy(o, src, (size_t)L.n_main * sizeof(double));
+        if (n_rest) std::memcpy(o_rest, src + L.n_main, (size_t)n_rest * sizeof(double));
+    } else {
+        for (int64_t j = 0; j < L.n_main; ++j) o[j] = src[L.src_cols[j]];
+        for (int64_t j = 0; j < n_rest; ++j) o_rest[j] = src[L.src_cols[L.n_main + j]];
+    }
+    for (int a = 0; a < 3; ++a) o[L.abs_dst[a]] = abs3[a];
+}
+
+// n_parts lists taken as their concatenation, which nobody has to make (12 MB of copies for the survivors of a
+// 3e5-row table, a millisecond of the step's tail): first[p] = rows before list p, first[n_parts] = all rows.
+int list_starts(const int64_t* n_rows, int32_t n_parts, std::vector<int64_t>& first)
+{
+    if (n_parts < 0 || (n_parts && !n_rows)) return MMX_ERR_ARG;
+    first.assign((size_t)n_parts + 1, 0);
+    for (int p = 0; p < n_parts; ++p) {
+        if (n_rows[p] < 0) return MMX_ERR_ARG;
+        first[(size_t)p + 1] = first[(size_t)p] + n_rows[p];
+    }
+    return MMX_OK;
+}
+
+// The one walk over such a concatenation, on up to T threads: thread t of nt takes rows [n t / nt, n (t + 1) / nt)
+// whatever the lists' lengths -- a single long list is shared by all threads, many short ones (a region's few thousand
+// rows are too few for a call of their own to thread itself) cost no hand-off each.
+//   fn(thread, list, row in the list, row in the concatenation) -> false: the row is refused, MMX_ERR_ARG
+template <typename F>
+int each_row(const std::vector<int64_t>& first, int T, F fn)
+{
+    const int64_t n = first.back();
+    std::vector<int> bad((size_t)T, 0);
+    parallel(T, [&](int t, int nt) {
+        const int64_t lo = n * t / nt, hi = n * (t + 1) / nt;
+        int p = (int)(std::upper_bound(first.begin(), first.end(), lo) - first.begin()) - 1;
+        for (int64_t g = lo; g < hi; ++p)
+            for (const int64_t end = std::min(hi, first[(size_t)p + 1]); g < end; ++g)
+                if (!fn(t, p, g - first[(size_t)p], g)) { bad[(size_t)t] = 1; return; }
+    });
+    return std::count(bad.begin(), bad.end(), 1) ? MMX_ERR_ARG : MMX_OK;
+}
+
+// The one stable counting sort of such a concatenation by key_of(list, row) in [0, n_keys) -- anything else is
+// refused -- (the keys are small: the product of the three group counts): put(list, row, destination row).  Every
+// thread counts the keys of its run of rows, the runs' counts are laid end to end per key, and every thread places its
+// own rows: rows of one key keep the order of the concatenation.
+template <typename K, typename P>
+int sort_rows(const std::vector<int64_t>& first, int64_t n_keys, K key_of, P put)
+{
+    if (n_keys < 1) return MMX_ERR_ARG;
+    if (n_keys > (int64_t(1) << 26)) return MMX_ERR_UNSUPPORTED;
+    int T = host_threads(first.back());
+    if ((int64_t)T * n_keys > (int64_t(1) << 24)) T = 1;          // (the threads' counters: 128 MB at the most)
+    std::vector<int64_t> at((size_t)T * (size_t)n_keys, 0);
+    const int rc = each_row(first, T, [&](int t, int p, int64_t i, int64_t) {
+        const int64_t k = key_of(p, i);
+        if (k < 0 || k >= n_keys) return false;
+        ++at[(size_t)t * (size_t)n_keys + (size_t)k];
+        return true;
+    });
+    if (rc != MMX_OK) return rc;
+    int64_t run = 0;
+    for (int64_t k = 0; k < n_keys; ++k)
+        for (int t = 0; t < T; ++t) {
+            int64_t& c = at[(size_t)t * (size_t)n_keys + (size_t)k];
+            const int64_t here = c;
+            c = run;
+            run += here;
+        }
+    return each_row(first, T, [&](int t, int p, int64_t i, int64_t) {
+        put(p, i, at[(size_t)t * (size_t)n_keys + (size_t)key_of(p, i)]++);
+        return true;
+    });
+}
+
+// Survivor lists as the pruning of a region leaves them: row ids into the merged table, sort keys, averaged
+// absolute coordinates [..][3] -- n_rows[p] entries each; the output has a row for every entry.
+struct survivor_lists {
+    const int64_t* const* ids; const int64_t* const* keys; const double* const* abs_rows;
+    std::vector<int64_t> first;
+};
+int check_lists(int32_t n_parts, const int64_t* const* ids, const int64_t* const* keys, const double* const* abs_rows,
+                const int64_t* n_rows, const void* table, const void* out, int64_t out_rows, survivor_lists& S)
+{
+    if (list_starts(n_rows, n_parts, S.first) != MMX_OK || (n_parts && (!ids || !keys || !abs_rows))) return MMX_ERR_ARG;
+    for (int p = 0; p < n_parts; ++p)
+        if (n_rows[p] && (!ids[p] || !keys[p] || !abs_rows[p])) return MMX_ERR_ARG;
+    if (S.first.back() != out_rows || (out_rows && (!table || !out))) return MMX_ERR_ARG;
+    S.ids = ids; S.keys = keys; S.abs_rows = abs_rows;
+    return MMX_OK;
+}
+}  // namespace
+
+// Rows rows[i] of the merged table in the columns of `layout`, the absolute coordinates from the compact (n_table, 3)
+// array the axis passes updated: the output of prune_blobs_mp (`merged[rows][:, :-3]` with the averaged coordinates put
+// back, magmap/cv/stack_detect.py:858-861) -- or, with a layout of final columns, what the reference's next two steps
+// (:455-470: rel <- abs, abs and unnamed columns dropped -- two more passes over a 3e5-row table when made afterwards)
+// leave of it; with `out_rest` in two tables: a stack detected with co-localisation ends as the eight final columns in
+// one contiguous table and the columns its flags are read from (:463-464: columns 10 .. 10 + C) beside it.
+extern "C" int mmx_host_take_rows(const double* table, int64_t ld, const int64_t* rows, int64_t n, const double* abs_zyx,
+                                  const mmx_row_layout* layout, double* out, double* out_rest)
+{
+    mmx_row_layout L;
+    if (n < 0 || (n && (!table || !rows || !abs_zyx || !out)) || check_layout(layout, ld, out_rest != nullptr, L) != MMX_OK)
+        return MMX_ERR_ARG;
+    const int64_t n_rest = L.n_out - L.n_main;
+    return each_row({0, n}, host_threads(n), [&](int, int, int64_t i, int64_t) {
+        const int64_t r = rows[i];
+        if (r < 0) return false;
+        write_row(L, table + r * ld, abs_zyx + 3 * r, out + i * L.n_main, out_rest ? out_rest + i * n_rest : nullptr);
+        return true;
+    });
+}
+
+// Final table of a stack from the survivor lists of its regions (pruned one by one, in order): row ids[p][i] of the
+// merged table in the columns of `layout`, the absolute coordinates from abs_rows[p][i], at its place in the stable sort
+// by key -- equal keys in the order of the lists.  Tables as for mmx_host_take_rows.
+extern "C" int mmx_host_gather_parts_by_key(const double* table, int64_t ld, int32_t n_parts, const int64_t* const* ids,
+                                            const int64_t* const* keys, const double* const* abs_rows,
+                                            const int64_t* n_rows, int64_t n_keys, const mmx_row_layout* layout,
+                                            double* out, int64_t out_rows, double* out_rest)
+{
+    mmx_row_layout L;
+    survivor_lists S;
+    if (check_layout(layout, ld, out_rest != nullptr, L) != MMX_OK ||
+        check_lists(n_parts, ids, keys, abs_rows, n_rows, table, out, out_rows, S) != MMX_OK)
+        return MMX_ERR_ARG;
+    const int64_t n_rest = L.n_out - L.n_main;
+    return sort_rows(S.first, n_keys,
+                     [&](int p, int64_t i) { return ids[p][i] < 0 ? (int64_t)-1 : keys[p][i]; },    // (a bad id: no key)
+                     [&](int p, int64_t i, int64_t at) {
+                         write_row(L, table + ids[p][i] * ld, abs_rows[p] + 3 * i, out + at * L.n_main,
+                                   out_rest ? out_rest + at * n_rest : nullptr);
+                     });
+}
+
+// Survivors of a rank in the form the distributed pruning's second exchange carries: the lists' rows in the lists'
+// order (a rank's regions, in turn), in the columns of `layout` with the sort key appended as column n_out -- in final
+// columns a quarter less travels, and the merge after it is as much smaller.   out : [out_rows][n_out + 1]
+extern "C" int mmx_host_emit_parts(const double* table, int64_t ld, int32_t n_parts, const int64_t* const* ids,
+                                   const int64_t* const* keys, const double* const* abs_rows, const int64_t* n_rows,
+                                   const mmx_row_layout* layout, double* out, int64_t out_rows)
+{
+    mmx_row_layout L;
+    survivor_lists S;
+    if (check_layout(layout, ld, false, L) != MMX_OK ||
+        check_lists(n_parts, ids, keys, abs_rows, n_rows, table, out, out_rows, S) != MMX_OK)
+        return MMX_ERR_ARG;
+    return each_row(S.first, host_threads(out_rows), [&](int, int p, int64_t i, int64_t g) {
+        if (ids[p][i] < 0) return false;
+        double* o = out + g * (L.n_out + 1);
+        write_row(L, table + ids[p][i] * ld, abs_rows[p] + 3 * i, o, nullptr);
+        o[L.n_out] = (double)keys[p][i];
+        return true;
+    });
+}
+
+// The stable sort by key of the CONCATENATION of n_parts dense row blocks that are the rows themselves (every rank's
+// survivors as an all_gather leaves them: padded to the longest block, so not contiguous -- making them one array
+// would be a 20 MB copy): a row's first n_cols columns leave, its key is the value in its column n_cols (how
+// mmx_host_emit_parts sent it), so there must be such a column.
 extern "C" int mmx_host_merge_parts_by_key(const double* const* parts, const int64_t* n_rows, int32_t n_parts, int64_t ld,
                                            int64_t n_keys, int64_t n_cols, double* out, int64_t out_rows)
 {
-    if (n_parts < 0 || n_keys < 1 || n_cols < 1 || n_cols >= ld || (n_parts && (!parts || !n_rows))) return MMX_ERR_ARG;
-    if (n_keys > (int64_t(1) << 26)) return MMX_ERR_UNSUPPORTED;
-    int64_t n = 0;
-    for (int p = 0; p < n_parts; ++p) {
-        if (n_rows[p] < 0 || (n_rows[p] && !parts[p])) return MMX_ERR_ARG;
-        n += n_rows[p];
-    }
-    if (n != out_rows || (n && !out)) return MMX_ERR_ARG;
-    if (n == 0) return MMX_OK;
-    int T = host_threads(n);
-    if ((int64_t)T * n_keys > (int64_t(1) << 24)) T = 1;
-    struct seg { const double* rows; int64_t n; };
-    std::vector<seg> segs;
-    const int64_t piece = std::max<int64_t>(1, (n + 4 * T - 1) / (4 * T));
+    std::vector<int64_t> first;
+    if (n_cols < 1 || n_cols >= ld || (n_parts && !parts) || list_starts(n_rows, n_parts, first) != MMX_OK)
+        return MMX_ERR_ARG;
     for (int p = 0; p < n_parts; ++p)
-        for (int64_t a = 0; a < n_rows[p]; a += piece)
-            segs.push_back(seg{parts[p] + a * ld, std::min(piece, n_rows[p] - a)});
-    const int S = (int)segs.size();
-    std::vector<int> first((size_t)T + 1, S);
-    {
-        int64_t seen = 0;
-        int t = 0;
-        first[0] = 0;
-        for (int q = 0; q < S; ++q) {
-            while (t + 1 < T && seen >= n * (t + 1) / T) first[(size_t)++t] = q;
-            seen += segs[(size_t)q].n;
-        }
-    }
-    auto key_of = [&](const double* row) -> int64_t {
-        const double v = row[n_cols];
-        return (v >= 0.0 && v < 9.0e15) ? (int64_t)v : -1;
-    };
-    std::vector<int64_t> at((size_t)T * (size_t)n_keys, 0);
-    std::vector<int> bad((size_t)T, 0);
-    parallel(T, [&](int t, int) {
-        int64_t* h = at.data() + (size_t)t * (size_t)n_keys;
-        for (int q = first[(size_t)t]; q < first[(size_t)t + 1] && !bad[(size_t)t]; ++q)
-            for (int64_t i = 0; i < segs[(size_t)q].n; ++i) {
-                const int64_t k = key_of(segs[(size_t)q].rows + i * ld);
-                if (k < 0 || k >= n_keys) { bad[(size_t)t] = 1; break; }
-                ++h[k];
-            }
-    });
-    for (int t = 0; t < T; ++t)
-        if (bad[(size_t)t]) return MMX_ERR_ARG;
-    {
-        int64_t run = 0;
-        for (int64_t k = 0; k < n_keys; ++k)
-            for (int t = 0; t < T; ++t) {
-                int64_t& c = at[(size_t)t * (size_t)n_keys + (size_t)k];
-                const int64_t here = c;
-                c = run;
-                run += here;
-            }
-    }
-    parallel(T, [&](int t, int) {
-        int64_t* pos = at.data() + (size_t)t * (size_t)n_keys;
-        for (int q = first[(size_t)t]; q < first[(size_t)t + 1]; ++q)
-            for (int64_t i = 0; i < segs[(size_t)q].n; ++i) {
-                const double* row = segs[(size_t)q].rows + i * ld;
-                std::memcpy(out + pos[key_of(row)]++ * n_cols, row, (size_t)n_cols * sizeof(double));
-            }
-    });
-    return MMX_OK;
-}
-
-// The same for survivors that still live in the merged table: row ids[i] of `table` (its first n_cols columns), the
-// three abs columns replaced by abs_rows[i], written to its place by key.
-extern "C" int mmx_host_gather_by_key(const double* table, int64_t ld, const int64_t* ids, const int64_t* keys,
-                                      int64_t n, int64_t n_keys, int64_t n_cols, const double* abs_rows,
-                                      const int32_t abs_cols[3], double* out)
-{
-    if (n < 0 || n_keys < 1 || n_cols < 1 || n_cols > ld || !abs_cols || (n && (!table || !ids || !keys || !out || !abs_rows)))
-        return MMX_ERR_ARG;
-    if (n_keys > (int64_t(1) << 26)) return MMX_ERR_UNSUPPORTED;
-    for (int a = 0; a < 3; ++a)
-        if (abs_cols[a] < 0 || abs_cols[a] >= n_cols) return MMX_ERR_ARG;
-    std::vector<int64_t> at((size_t)n_keys + 1, 0);
-    for (int64_t i = 0; i < n; ++i) {
-        if (keys[i] < 0 || keys[i] >= n_keys || ids[i] < 0) return MMX_ERR_ARG;
-        ++at[(size_t)keys[i] + 1];
-    }
-    for (int64_t k = 0; k < n_keys; ++k) at[(size_t)k + 1] += at[(size_t)k];
-    std::vector<int64_t> dst((size_t)n);
-    for (int64_t i = 0; i < n; ++i) dst[(size_t)i] = at[(size_t)keys[i]]++;
-    parallel(host_threads(n), [&](int t, int nt) {
-        const int64_t lo = n * t / nt, hi = n * (t + 1) / nt;
-        for (int64_t i = lo; i < hi; ++i) {
-            double* o = out + dst[(size_t)i] * n_cols;
-            std::memcpy(o, table + ids[i] * ld, (size_t)n_cols * sizeof(double));
-            for (int a = 0; a < 3; ++a) o[abs_cols[a]] = abs_rows[3 * i + a];
-        }
-    });
-    return MMX_OK;
-}
-
-// The merge of the regions' survivor lists with the table leaving in the caller's FINAL column layout (the reference's
-// last two steps on the pruned table, magmap/cv/stack_detect.py:455-470: rel <- abs, abs and unnamed columns dropped --
-// two more passes over a 3e5-row table when done afterwards): out[k][j] = table[ids][src_cols[j]], then
-// out[k][abs_dst0 .. +3] = abs_rows; rows in key order, equal keys in the order of the lists.  The `n_parts` lists (the
-// regions of a stack pruned one by one) are taken as they are
-// -- concatenating them is 12 MB of copies for 3e5 rows, a millisecond of the step's tail -- and
-// the counting sort itself threaded: every thread counts the keys of a contiguous run of parts, the runs' counts are
-// laid end to end per key, and every thread places its own rows (the order within a key stays the lists' order).
-extern "C" int mmx_host_gather_parts_by_key_final(const double* table, int64_t ld, int32_t n_parts,
-                                                  const int64_t* const* ids, const int64_t* const* keys,
-                                                  const double* const* abs_rows, const int64_t* n_rows, int64_t n_keys,
-                                                  const int32_t* src_cols, int32_t n_out, int32_t abs_dst0,
-                                                  double* out, int64_t out_rows)
-{
-    return mmx_host_gather_parts_by_key_split(table, ld, n_parts, ids, keys, abs_rows, n_rows, n_keys, src_cols, n_out,
-                                              abs_dst0, out, out_rows, n_out, nullptr);
-}
-
-// ... with the output in TWO tables: columns [0, n_main) of the layout into `out` (row pitch n_main), the remaining
-// n_out - n_main into `out_rest` (row pitch n_out - n_main) -- a stack detected with co-localisation: the eight final
-// columns as one contiguous table, the columns its flags are read from (magmap/cv/stack_detect.py:463-464: columns 10
-// .. 10 + C of the pruned table) beside it, in the one pass that gathers the rows.  out_rest NULL: n_main = n_out.
-extern "C" int mmx_host_gather_parts_by_key_split(const double* table, int64_t ld, int32_t n_parts,
-                                                  const int64_t* const* ids, const int64_t* const* keys,
-                                                  const double* const* abs_rows, const int64_t* n_rows, int64_t n_keys,
-                                                  const int32_t* src_cols, int32_t n_out, int32_t abs_dst0,
-                                                  double* out, int64_t out_rows, int32_t n_main, double* out_rest)
-{
-    if (n_parts < 0 || n_keys < 1 || n_out < 3 || n_out > 64 || !src_cols || abs_dst0 < 0 || abs_dst0 + 3 > n_out ||
-        (n_parts && (!ids || !keys || !abs_rows || !n_rows)))
-        return MMX_ERR_ARG;
-    if (!out_rest) n_main = n_out;
-    if (n_main < abs_dst0 + 3 || n_main > n_out || (out_rest && n_main == n_out)) return MMX_ERR_ARG;
-    const int n_rest = n_out - n_main;
-    if (n_keys > (int64_t(1) << 26)) return MMX_ERR_UNSUPPORTED;
-    for (int j = 0; j < n_out; ++j)
-        if (src_cols[j] < 0 || src_cols[j] >= ld) return MMX_ERR_ARG;
-    int64_t n = 0;
-    for (int p = 0; p < n_parts; ++p) {
-        if (n_rows[p] < 0 || (n_rows[p] && (!ids[p] || !keys[p] || !abs_rows[p]))) return MMX_ERR_ARG;
-        n += n_rows[p];
-    }
-    if (n != out_rows || (n && (!table || !out))) return MMX_ERR_ARG;
-    if (n == 0) return MMX_OK;
-    // runs of parts with about the same number of rows each (a thread's run may be empty)
-    int T = host_threads(n);
-    if ((int64_t)T * n_keys > (int64_t(1) << 24)) T = 1;
-    std::vector<int> first((size_t)T + 1, n_parts);
-    {
-        int64_t seen = 0;
-        int t = 0;
-        first[0] = 0;
-        for (int p = 0; p < n_parts; ++p) {
-            while (t + 1 < T && seen >= n * (t + 1) / T) first[(size_t)++t] = p;
-            seen += n_rows[p];
-        }
-        for (++t; t <= T; ++t) first[(size_t)t] = n_parts;
-    }
-    std::vector<int64_t> at((size_t)T * (size_t)n_keys, 0);
-    std::vector<int> bad((size_t)T, 0);
-    parallel(T, [&](int t, int) {
-        int64_t* h = at.data() + (size_t)t * (size_t)n_keys;
-        for (int p = first[(size_t)t]; p < first[(size_t)t + 1]; ++p)
-            for (int64_t i = 0; i < n_rows[p]; ++i) {
-                const int64_t k = keys[p][i];
-                if (k < 0 || k >= n_keys || ids[p][i] < 0) { bad[(size_t)t] = 1; break; }
-                ++h[k];
-            }
-    });
-    for (int t = 0; t < T; ++t)
-        if (bad[(size_t)t]) return MMX_ERR_ARG;
-    {
-        int64_t run = 0;
-        for (int64_t k = 0; k < n_keys; ++k)
-            for (int t = 0; t < T; ++t) {
-                int64_t& c = at[(size_t)t * (size_t)n_keys + (size_t)k];
-                const int64_t here = c;
-                c = run;
-                run += here;
-            }
-    }
-    parallel(T, [&](int t, int) {
-        int64_t* pos = at.data() + (size_t)t * (size_t)n_keys;
-        for (int p = first[(size_t)t]; p < first[(size_t)t + 1]; ++p)
-            for (int64_t i = 0; i < n_rows[p]; ++i) {
-                const int64_t at_row = pos[keys[p][i]]++;
-                double* o = out + at_row * n_main;
-                const double* src = table + ids[p][i] * ld;
-                for (int j = 0; j < n_main; ++j) o[j] = src[src_cols[j]];
-                for (int a = 0; a < 3; ++a) o[abs_dst0 + a] = abs_rows[p][3 * i + a];
-                if (n_rest) {
-                    double* o2 = out_rest + at_row * n_rest;
-                    for (int j = 0; j < n_rest; ++j) o2[j] = src[src_cols[n_main + j]];
-                }
-            }
-    });
-    return MMX_OK;
+        if (n_rows[p] && !parts[p]) return MMX_ERR_ARG;
+    if (first.back() != out_rows || (out_rows && !out)) return MMX_ERR_ARG;
+    return sort_rows(first, n_keys,
+                     [&](int p, int64_t i) {          // (negative, NaN and huge values: no key)
+                         const double v = parts[p][i * ld + n_cols];
+                         return (v >= 0.0 && v < 9.0e15) ? (int64_t)v : (int64_t)-1;
+                     },
+                     [&](int p, int64_t i, int64_t at) {
+                         std::memcpy(out + at * n_cols, parts[p] + i * ld, (size_t)n_cols * sizeof(double));
+                     });
 }
 
 // Rows of a table that lie inside ANY of `n_boxes` boxes [lo, hi): what a rank sends to the ranks whose blocks its
@@ -854,103 +808,6 @@ extern "C" int mmx_host_append_rows(const double* payload, int64_t n, const int3
     return at + k <= cap ? MMX_OK : MMX_ERR_WORKSPACE;
 }
 
-// Survivors of a rank in the form the second exchange carries: row ids[i] of `table` (its first n_cols columns), the
-// three abs columns replaced by abs_rows[i], the sort key appended as column n_cols -- in the order given.
-//   out : [n][n_cols + 1]
-extern "C" int mmx_host_emit_survivors(const double* table, int64_t ld, const int64_t* ids, const int64_t* keys,
-                                       int64_t n, int64_t n_cols, const double* abs_rows, const int32_t abs_cols[3],
-                                       double* out)
-{
-    if (n < 0 || n_cols < 1 || n_cols > ld || !abs_cols || (n && (!table || !ids || !keys || !out || !abs_rows)))
-        return MMX_ERR_ARG;
-    for (int a = 0; a < 3; ++a)
-        if (abs_cols[a] < 0 || abs_cols[a] >= n_cols) return MMX_ERR_ARG;
-    for (int64_t i = 0; i < n; ++i)
-        if (ids[i] < 0) return MMX_ERR_ARG;
-    parallel(host_threads(n), [&](int t, int nt) {
-        const int64_t lo = n * t / nt, hi = n * (t + 1) / nt;
-        for (int64_t i = lo; i < hi; ++i) {
-            double* o = out + i * (n_cols + 1);
-            std::memcpy(o, table + ids[i] * ld, (size_t)n_cols * sizeof(double));
-            for (int a = 0; a < 3; ++a) o[abs_cols[a]] = abs_rows[3 * i + a];
-            o[n_cols] = (double)keys[i];
-        }
-    });
-    return MMX_OK;
-}
-
-// mmx_host_emit_survivors with the rows leaving in the caller's final column layout (see
-// mmx_host_gather_parts_by_key_final): out[i] = table[ids[i]][src_cols[0 .. n_out)], abs_rows[i] at abs_dst0, then the
-// key -- what travels in the distributed pruning's second exchange is a quarter smaller, and so is the merge after it.
-extern "C" int mmx_host_emit_survivors_final(const double* table, int64_t ld, const int64_t* ids, const int64_t* keys,
-                                             int64_t n, const int32_t* src_cols, int32_t n_out, const double* abs_rows,
-                                             int32_t abs_dst0, double* out)
-{
-    if (n < 0 || n_out < 3 || n_out > 64 || !src_cols || abs_dst0 < 0 || abs_dst0 + 3 > n_out ||
-        (n && (!table || !ids || !keys || !out || !abs_rows)))
-        return MMX_ERR_ARG;
-    for (int j = 0; j < n_out; ++j)
-        if (src_cols[j] < 0 || src_cols[j] >= ld) return MMX_ERR_ARG;
-    for (int64_t i = 0; i < n; ++i)
-        if (ids[i] < 0) return MMX_ERR_ARG;
-    parallel(host_threads(n), [&](int t, int nt) {
-        const int64_t lo = n * t / nt, hi = n * (t + 1) / nt;
-        for (int64_t i = lo; i < hi; ++i) {
-            double* o = out + i * (n_out + 1);
-            const double* src = table + ids[i] * ld;
-            for (int j = 0; j < n_out; ++j) o[j] = src[src_cols[j]];
-            for (int a = 0; a < 3; ++a) o[abs_dst0 + a] = abs_rows[3 * i + a];
-            o[n_out] = (double)keys[i];
-        }
-    });
-    return MMX_OK;
-}
-
-// mmx_host_emit_survivors_final for n_parts survivor lists at once (a rank's regions, in order): one threaded pass over
-// all of them -- a region's few thousand rows are too few for a call of their own to thread itself, and sixteen calls
-// from Python threads cost more in hand-offs than in copying.
-extern "C" int mmx_host_emit_parts_final(const double* table, int64_t ld, int32_t n_parts, const int64_t* const* ids,
-                                         const int64_t* const* keys, const double* const* abs_rows,
-                                         const int64_t* n_rows, const int32_t* src_cols, int32_t n_out, int32_t abs_dst0,
-                                         double* out, int64_t out_rows)
-{
-    if (n_parts < 0 || n_out < 3 || n_out > 64 || !src_cols || abs_dst0 < 0 || abs_dst0 + 3 > n_out ||
-        (n_parts && (!ids || !keys || !abs_rows || !n_rows)))
-        return MMX_ERR_ARG;
-    for (int j = 0; j < n_out; ++j)
-        if (src_cols[j] < 0 || src_cols[j] >= ld) return MMX_ERR_ARG;
-    std::vector<int64_t> first((size_t)n_parts + 1, 0);
-    for (int p = 0; p < n_parts; ++p) {
-        if (n_rows[p] < 0 || (n_rows[p] && (!ids[p] || !keys[p] || !abs_rows[p]))) return MMX_ERR_ARG;
-        first[(size_t)p + 1] = first[(size_t)p] + n_rows[p];
-    }
-    const int64_t n = first[(size_t)n_parts];
-    if (n != out_rows || (n && (!table || !out))) return MMX_ERR_ARG;
-    if (n == 0) return MMX_OK;
-    const int T = host_threads(n);
-    std::vector<int> bad((size_t)T, 0);
-    parallel(T, [&](int t, int) {
-        // rows [lo, hi) of the concatenation: walk the parts they fall into
-        const int64_t lo = n * t / T, hi = n * (t + 1) / T;
-        int p = (int)(std::upper_bound(first.begin(), first.end(), lo) - first.begin()) - 1;
-        for (int64_t g = lo; g < hi; ++p) {
-            const int64_t end = std::min(hi, first[(size_t)p + 1]);
-            for (; g < end; ++g) {
-                const int64_t i = g - first[(size_t)p];
-                if (ids[p][i] < 0) { bad[(size_t)t] = 1; return; }
-                double* o = out + g * (n_out + 1);
-                const double* src = table + ids[p][i] * ld;
-                for (int j = 0; j < n_out; ++j) o[j] = src[src_cols[j]];
-                for (int a = 0; a < 3; ++a) o[abs_dst0 + a] = abs_rows[p][3 * i + a];
-                o[n_out] = (double)keys[p][i];
-            }
-        }
-    });
-    for (int t = 0; t < T; ++t)
-        if (bad[(size_t)t]) return MMX_ERR_ARG;
-    return MMX_OK;
-}
-
 // out[i][dst_col0 + j] = table[i][src_cols[j]] for every row: the column shuffles that end a stack
 // detection (Blobs.replace_rel_with_abs_blob_coords: out = table, columns 7..9 -> 0..2;
 // Blobs.remove_abs_blob_coords: the kept columns into a new table).  `out` may be `table` itself (a row is
@@ -969,68 +826,6 @@ extern "C" int mmx_host_map_columns(const double* table, int64_t ld, int64_t n, 
             const double* r = table + i * ld;
             for (int j = 0; j < n_map; ++j) tmp[j] = r[src_cols[j]];
             std::memcpy(out + i * out_ld + dst_col0, tmp, (size_t)n_map * sizeof(double));
-        }
-    });
-    return MMX_OK;
-}
-
-// Rows `rows[0..n)` of a float64 table (row pitch `ld`), first `n_cols` columns, with three of the
-// columns replaced from a compact (n_table, 3) array -- the output of prune_blobs_mp
-// (`merged[rows][:, :-3]` with the updated absolute coordinates put back).
-extern "C" int mmx_host_take_rows(const double* table, int64_t ld, const int64_t* rows, int64_t n,
-                                  int64_t n_cols, const double* abs_zyx, const int32_t abs_cols[3],
-                                  double* out)
-{
-    if (!table || (!rows && n) || !out || n < 0 || n_cols < 1 || n_cols > ld || !abs_zyx || !abs_cols)
-        return MMX_ERR_ARG;
-    for (int a = 0; a < 3; ++a)
-        if (abs_cols[a] < 0 || abs_cols[a] >= n_cols) return MMX_ERR_ARG;
-    parallel(host_threads(n), [&](int t, int nt) {
-        const int64_t lo = n * t / nt, hi = n * (t + 1) / nt;
-        for (int64_t i = lo; i < hi; ++i) {
-            const int64_t r = rows[i];
-            double* o = out + i * n_cols;
-            std::memcpy(o, table + r * ld, (size_t)n_cols * sizeof(double));
-            for (int a = 0; a < 3; ++a) o[abs_cols[a]] = abs_zyx[3 * r + a];
-        }
-    });
-    return MMX_OK;
-}
-
-// mmx_host_take_rows with the table leaving in the caller's final column layout (see mmx_host_gather_parts_by_key_final):
-// out[i][j] = table[rows[i]][src_cols[j]], then out[i][abs_dst0 .. +3] = abs_zyx[rows[i]].
-extern "C" int mmx_host_take_rows_final(const double* table, int64_t ld, const int64_t* rows, int64_t n,
-                                        const int32_t* src_cols, int32_t n_out, const double* abs_zyx,
-                                        int32_t abs_dst0, double* out)
-{
-    return mmx_host_take_rows_split(table, ld, rows, n, src_cols, n_out, abs_zyx, abs_dst0, out, n_out, nullptr);
-}
-
-// ... with the output in two tables (see mmx_host_gather_parts_by_key_split).
-extern "C" int mmx_host_take_rows_split(const double* table, int64_t ld, const int64_t* rows, int64_t n,
-                                        const int32_t* src_cols, int32_t n_out, const double* abs_zyx,
-                                        int32_t abs_dst0, double* out, int32_t n_main, double* out_rest)
-{
-    if (!table || (!rows && n) || !out || n < 0 || n_out < 3 || n_out > 64 || !src_cols || !abs_zyx || abs_dst0 < 0 ||
-        abs_dst0 + 3 > n_out)
-        return MMX_ERR_ARG;
-    if (!out_rest) n_main = n_out;
-    if (n_main < abs_dst0 + 3 || n_main > n_out || (out_rest && n_main == n_out)) return MMX_ERR_ARG;
-    const int n_rest = n_out - n_main;
-    for (int j = 0; j < n_out; ++j)
-        if (src_cols[j] < 0 || src_cols[j] >= ld) return MMX_ERR_ARG;
-    parallel(host_threads(n), [&](int t, int nt) {
-        const int64_t lo = n * t / nt, hi = n * (t + 1) / nt;
-        for (int64_t i = lo; i < hi; ++i) {
-            const int64_t r = rows[i];
-            double* o = out + i * n_main;
-            const double* src = table + r * ld;
-            for (int j = 0; j < n_main; ++j) o[j] = src[src_cols[j]];
-            for (int a = 0; a < 3; ++a) o[abs_dst0 + a] = abs_zyx[3 * r + a];
-            if (n_rest) {
-                double* o2 = out_rest + i * n_rest;
-                for (int j = 0; j < n_rest; ++j) o2[j] = src[src_cols[n_main + j]];
-            }
         }
     });
     return MMX_OK;
@@ -1625,7 +1420,7 @@ extern "C" int mmx_host_coloc_flags(const double* means, const int32_t* mean_cha
 // once per ROI) -- from the re-scored candidate table to the final table in ONE call: peak decisions
 // (mmx_host_resolve_peaks), per-block overlap prune (mmx_host_overlap_prune), block tables into the merged table
 // (mmx_host_emit_tables), the three pruning passes over the whole table (mmx_host_prune_region) and the gather in the
-// final columns (mmx_host_take_rows_final).  Each piece is the entry point of its own name; what this saves is the
+// final columns (mmx_host_take_rows).  Each piece is the entry point of its own name; what this saves is the
 // host language between them -- five calls' worth of array set-up, as long as the kernels of such a stack.
 // MMX_DEFERRED (not an error; stats[6] says why): a decision needs the caller -- two equal peak values in a block
 // (NumPy's argsort order: 1), float32 values further than eps / 4 from the exact ones (a wider band: 2), an overlap
@@ -1700,8 +1495,8 @@ extern "C" int mmx_host_finish_stack(const mmx_finish_stack_args* a)
                                a->bounds, a->last_end, a->tol, a->nxt_lo, a->nxt_hi, keep.data(), nullptr, &kept,
                                a->n_slab, a->n_after, a->n_next, a->stat_ld);
     if (rc != MMX_OK) return rc;
-    rc = mmx_host_take_rows_final(a->store, a->ld, keep.data(), kept, a->src_cols, a->n_out, abs_cur.data(), a->abs_dst0,
-                                  a->out);
+    const mmx_row_layout final_cols = {a->src_cols, a->n_out, a->n_out, {a->abs_dst0, a->abs_dst0 + 1, a->abs_dst0 + 2}};
+    rc = mmx_host_take_rows(a->store, a->ld, keep.data(), kept, abs_cur.data(), &final_cols, a->out, nullptr);
     if (rc != MMX_OK) return rc;
     *a->out_rows = kept;
     return MMX_OK;

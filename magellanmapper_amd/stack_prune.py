@@ -60,6 +60,65 @@ def _region_workers():
     return _REGION_POOL[0]
 
 
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+class _RowLayout:
+    """The columns in which surviving rows leave the merged table -- a value of the library's ``mmx_row_layout``, passed
+    around whole.  ``src``: the source columns (``None``: the first ``n_out`` as they are -- the plain table,
+    ``merged[:, :-3]``); ``abs_dst``: the three columns the averaged absolute coordinates are written to; ``n_main``: how
+    many of the columns are the table itself (the others -- the columns co-localisation flags are read from -- leave
+    beside it); ``names``: the names of the table's columns where they are the reference's final ones
+    (``StackPruner._final_columns``), ``None`` for the plain table."""
+
+    def __init__(self, n_out, abs_dst, src=None, n_main=None, names=None):
+        self.n_out = int(n_out)
+        self.abs_dst = [int(v) for v in abs_dst]
+        self.src = None if src is None else [int(v) for v in src]
+        self.n_main = self.n_out if n_main is None else int(n_main)
+        self.names = names
+        #: the source columns as the library reads them (kept alive here), and the layout itself
+        self.src_c = None if src is None else (ctypes.c_int32 * len(self.src))(*self.src)
+        self._c = nat.RowLayout(self.src_c, self.n_out, self.n_main, (ctypes.c_int32 * 3)(*self.abs_dst))
+
+    def __eq__(self, other):
+        """The same columns in the same tables (whatever they are called)."""
+        if not isinstance(other, _RowLayout):
+            return NotImplemented
+        return (self.src, self.n_out, self.abs_dst, self.n_main) == (other.src, other.n_out, other.abs_dst, other.n_main)
+
+    __hash__ = None
+
+    @property
+    def c(self):
+        """What a native call takes for its ``layout`` argument."""
+        return ctypes.byref(self._c)
+
+    def tables(self, n_rows: int):
+        """Room for ``n_rows`` rows: ``(table, the columns beside it or None)``."""
+        out = np.empty((n_rows, self.n_main))
+        return out, (np.empty((n_rows, self.n_out - self.n_main)) if self.n_main < self.n_out else None)
+
+    def dress(self, out, rest=None):
+        """``out`` as the :class:`_FinalTable` of these columns, ``rest`` beside it (the plain table stays an array)."""
+        if self.names is None:
+            return out
+        out = out.view(_FinalTable)
+        out.col_names, out.coloc_cols = self.names, rest
+        return out
+
+
+def _survivor_lists(done):
+    """The arguments of the native gathers for a set of survivor lists ``(ids, keys, abs_rows, ...)`` -- the regions' of
+    a stack or a rank, in order, as the pruning left them; empty ones are left out: ``(number of lists, pointers to
+    their ids, to their keys, to their coordinates, rows per list)``.  The lists have to outlive the call."""
+    live = [d for d in done if len(d[0])]
+    n_rows = np.array([len(d[0]) for d in live], dtype=np.int64)
+    ptrs = [(ctypes.c_void_p * max(1, len(live)))(*[d[c].ctypes.data for d in live]) for c in range(3)]
+    return len(live), ptrs[0], ptrs[1], ptrs[2], n_rows
+
+
 class _RegionPruner:
     """The overlap pruning of one process' table done region by region while later blocks are still being detected.
 
@@ -203,44 +262,22 @@ class _RegionPruner:
         if failure is not None:
             raise failure
 
-    def finish(self, abs_inds, final=None, _lap=lambda what: None):
-        """Whatever is left, then the merge: ``(final table, counts)``.  ``final = (source columns, place of the abs
-        coordinates)``: the table in those columns (``StackPruner._final_columns``)."""
+    def finish(self, abs_inds, layout, _lap=lambda what: None):
+        """Whatever is left, then the merge: ``(the table in the columns of layout, counts)`` (``abs_inds``, the
+        registry's abs columns, is not read: the layout says where the coordinates go)."""
         self.run_all()              # (everything has landed by now)
         _lap("  regions: the last ones done")
         ar = self.arena
         counts = sum(d[3] for d in self.done)
-        ncol = ar.store.shape[1] - 3
-        if final is not None:
-            # the regions' survivor lists go to the merge as they are (no concatenation: 12 MB of copies for 3e5 rows)
-            src, dst0, n_main = final
-            parts = [d for d in self.done if len(d[0])]
-            n_rows = np.array([len(d[0]) for d in parts], dtype=np.int64)
-            ptrs = [(ctypes.c_void_p * max(1, len(parts)))(*[d[c].ctypes.data for d in parts]) for c in range(3)]
-            total = int(n_rows.sum())
-            out = np.empty((total, n_main))
-            rest = np.empty((total, len(src) - n_main)) if n_main < len(src) else None
-            nat.check(nat.lib().mmx_host_gather_parts_by_key_split(
-                ar.store.ctypes.data, ar.store.strides[0] // 8, len(parts), ptrs[0], ptrs[1], ptrs[2],
-                n_rows.ctypes.data, self.plan["n_keys"] * len(self.channels), (ctypes.c_int32 * len(src))(*src),
-                len(src), dst0, out.ctypes.data, total, n_main, None if rest is None else rest.ctypes.data),
-                "mmx_host_gather_parts_by_key_split")
-            _lap("  regions: merge by key, final columns")
-            if rest is not None:
-                out = out.view(_FinalTable)
-                out.coloc_cols = rest
-            return out, counts
-        ids = np.ascontiguousarray(np.concatenate([d[0] for d in self.done]), dtype=np.int64)
-        keys = np.ascontiguousarray(np.concatenate([d[1] for d in self.done]), dtype=np.int64)
-        abs_rows = np.ascontiguousarray(np.concatenate([d[2] for d in self.done]), dtype=np.float64)
-        _lap("  regions: survivors concatenated")
-        out = np.empty((len(ids), ncol))
-        cols3 = (ctypes.c_int32 * 3)(*[int(v) for v in abs_inds])
-        nat.check(nat.lib().mmx_host_gather_by_key(
-            ar.store.ctypes.data, ar.store.strides[0] // 8, ids.ctypes.data, keys.ctypes.data, len(ids),
-            self.plan["n_keys"] * len(self.channels), ncol, abs_rows.ctypes.data, cols3, out.ctypes.data),
-            "mmx_host_gather_by_key")
-        return out, counts
+        # the regions' survivor lists go to the merge as they are (no concatenation: 12 MB of copies for 3e5 rows)
+        n_parts, ids, keys, abs_rows, n_rows = _survivor_lists(self.done)
+        out, rest = layout.tables(int(n_rows.sum()))
+        nat.check(nat.lib().mmx_host_gather_parts_by_key(
+            ar.store.ctypes.data, ar.store.strides[0] // 8, n_parts, ids, keys, abs_rows, n_rows.ctypes.data,
+            self.plan["n_keys"] * len(self.channels), layout.c, out.ctypes.data, len(out), _ptr(rest)),
+            "mmx_host_gather_parts_by_key")
+        _lap("  regions: merge by key")
+        return layout.dress(out, rest), counts
 
 
 class _FinalTable(np.ndarray):
@@ -492,9 +529,9 @@ class StackPruner:
     def _final_columns(merged, abs_inds, n_flag_cols: int = 0):
         """What the reference's last steps on the pruned table (``replace_rel_with_abs_blob_coords``, [the flags read
         from ``[:, 10:10 + C]``,] ``remove_abs_blob_coords(True)``, :455-470) leave of the merged table's columns, for
-        the gather to write directly: ``(source columns, place of the abs coordinates among them, names of the final
-        columns, how many of the source columns they are)`` -- with ``n_flag_cols`` = C co-localisation columns behind the
-        named ones the source columns end with the C columns the flags are read from -- or ``None`` where the steps do not
+        the gather to write directly, as a :class:`_RowLayout` -- with ``n_flag_cols`` = C co-localisation columns behind
+        the named ones the source columns end with the C columns the flags are read from, which leave beside the table
+        (``n_main`` = the final columns alone) -- or ``None`` where the steps do not
         reduce to that (columns beyond the named ones that were not announced, an unusual registry, a table the native
         gather does not take)."""
         if not (merged.dtype == np.float64 and merged.strides[1] == 8 and merged.strides[0] % 8 == 0):
@@ -516,45 +553,38 @@ class StackPruner:
         if n_flag_cols and len(named) != 11:
             return None                 # (the reference's literal `10:10 + C` is only what it means with the 11 standard columns)
         flag_src = list(range(10, 10 + n_flag_cols))        # (the literal columns of stack_detect.py:464, region first)
-        return src + flag_src, dst0, [c.value for c, _ in keep], len(src)
+        return _RowLayout(len(src) + n_flag_cols, range(dst0, dst0 + 3), src + flag_src, len(src), [c.value for c, _ in keep])
+
+    @classmethod
+    def _layout(cls, merged, abs_inds, final_form: bool, n_flag_cols: int = 0) -> _RowLayout:
+        """The columns a pruned table leaves in: the reference's final ones where asked for and possible
+        (:meth:`_final_columns`), else the plain table -- every column but the three tags, the abs columns in place."""
+        layout = cls._final_columns(merged, abs_inds, n_flag_cols) if final_form else None
+        return layout if layout is not None else _RowLayout(merged.shape[1] - 3, abs_inds)
 
     @staticmethod
-    def _take_rows(merged, rows, abs_cur, abs_inds, final=None):
-        """``merged[rows][:, :-3]`` with the three abs columns taken from ``abs_cur[rows]``; with ``final = (source
-        columns, place of the abs coordinates)`` the table in those columns instead (:meth:`_final_columns`)."""
-        ncol = merged.shape[1]
-        if final is not None:
-            src, dst0, n_main = final
-            out = np.empty((len(rows), n_main))
-            rest = np.empty((len(rows), len(src) - n_main)) if n_main < len(src) else None
-            nat.check(nat.lib().mmx_host_take_rows_split(
-                merged.ctypes.data, merged.strides[0] // 8, rows.ctypes.data, len(rows),
-                (ctypes.c_int32 * len(src))(*src), len(src), abs_cur.ctypes.data, dst0, out.ctypes.data, n_main,
-                None if rest is None else rest.ctypes.data), "mmx_host_take_rows_split")
-            if rest is not None:
-                out = out.view(_FinalTable)
-                out.coloc_cols = rest
-            return out
+    def _take_rows(merged, rows, abs_cur, layout):
+        """``merged[rows]`` in the columns of ``layout``, the three abs columns taken from ``abs_cur[rows]``."""
         if merged.dtype == np.float64 and merged.strides[1] == 8 and merged.strides[0] % 8 == 0:
-            out = np.empty((len(rows), ncol - 3))
-            cols3 = (ctypes.c_int32 * 3)(*[int(v) for v in abs_inds])
+            out, rest = layout.tables(len(rows))
             nat.check(nat.lib().mmx_host_take_rows(
-                merged.ctypes.data, merged.strides[0] // 8, rows.ctypes.data, len(rows), ncol - 3,
-                abs_cur.ctypes.data, cols3, out.ctypes.data), "mmx_host_take_rows")
-            return out
+                merged.ctypes.data, merged.strides[0] // 8, rows.ctypes.data, len(rows), abs_cur.ctypes.data, layout.c,
+                out.ctypes.data, _ptr(rest)), "mmx_host_take_rows")
+            return layout.dress(out, rest)
+        # (a table the native gather does not take: _final_columns has said so, the layout is the plain one)
         out = np.take(merged, rows, axis=0)[:, :-3]
-        out[:, abs_inds] = np.take(abs_cur, rows, axis=0)
+        out[:, layout.abs_dst] = np.take(abs_cur, rows, axis=0)
         return out
 
     @classmethod
-    def _prune_distributed(cls, seg_rois, shape3, plan, sub_roi_slices, channels, final=None):
+    def _prune_distributed(cls, seg_rois, shape3, plan, sub_roi_slices, channels, layout):
         """Several ranks, each holding the tables of its own blocks (``seg_rois.local_only``): every rank prunes
         its own rows -- the three passes on its rows plus the other ranks' rows within reach of its blocks
         (``mmx_host_prune_region``) -- and the survivors are merged by key on every rank.  Collective: all ranks
         call it, all get the same ``(table, counts)``; ``(None, None)`` when no rank holds a table.
 
         Two exchanges (RCCL all_gather over xGMI on GPUs): the rows near another rank's blocks -- a few per cent of
-        the table: 10 values a row --, then the surviving rows in their final form with their keys."""
+        the table: 10 values a row --, then the surviving rows in the columns of ``layout`` (one table) with their keys."""
         from . import dist
         ar = seg_rois.arena
         world, me = dist.world_size(), dist.rank()
@@ -573,12 +603,10 @@ class StackPruner:
         grid = sub_roi_slices.shape
         coords = grid_coords(grid)
         n = ar.n
-        ncol = ar.store.shape[1]
-        failure, payload, boxes, reach, abs_inds = None, None, None, None, None
+        failure, payload, boxes, reach = None, None, None, None
         has_table = False
         try:
             has_table = any(seg_rois[c] is not None and not isinstance(seg_rois[c], (int, np.integer)) for c in coords)
-            abs_inds = detector.Blobs._get_abs_inds()
             reach = _region_reach(plan["tol"])
             boxes = cls._rank_boxes(len(coords), world, coords, sub_roi_slices, shape3, reach)
             payload = cls._seam_rows(ar, boxes, me, reach)
@@ -596,11 +624,11 @@ class StackPruner:
         _lap("exchange 1 (seam rows)")
         mine, counts = None, None
         try:
-            mine, counts = cls._prune_own_rows(ar, parts, boxes[me], me, channels, plan, abs_inds, _lap, final,
+            mine, counts = cls._prune_own_rows(ar, parts, boxes[me], me, channels, plan, layout, _lap,
                                                (sub_roi_slices, shape3, dist.my_share(len(coords))))
         except Exception as exc:
             failure = exc
-        width = (ncol - 3) if final is None else len(final[0])          # columns of a survivor's row; its key follows
+        width = layout.n_out            # columns of a survivor's row; its key follows
         blocks_, n_per_rank, _ = dist.all_gather_rows_padded(mine, width + 1, failure, "distributed pruning (own rows)")
         _lap("exchange 2 (survivors)")
         out = None
@@ -681,15 +709,14 @@ class StackPruner:
         return payload[:k.value]
 
     @classmethod
-    def _prune_own_rows(cls, ar, parts, mine_box, me, channels, plan, abs_inds, _lap=lambda what: None, final=None,
-                        geometry=None):
+    def _prune_own_rows(cls, ar, parts, mine_box, me, channels, plan, layout, _lap=lambda what: None, geometry=None):
         """The three passes on this rank's rows between the seam rows received from the ranks before and after it:
-        ``(own survivors in their final form + one column with the key that places them, statistics)``.
+        ``(own survivors in the columns of layout + one column with the key that places them, statistics)``.
 
         The received rows are appended to the arena's compact columns behind the rank's own rows
         (``mmx_host_append_rows``) and ``mmx_host_prune_parts`` is told the order of the local table -- earlier
         ranks' halo, own rows, later ranks' halo: what the whole-table passes would see of them -- so that no table is
-        put together in Python; the survivors leave through ``mmx_host_emit_survivors``.
+        put together in Python; the survivors leave through ``mmx_host_emit_parts``.
 
         ``geometry = (sub_roi_slices, shape3, this rank's block indices)``: with enough rows the rank's blocks are
         pruned region by region on a few threads, as one process does while it detects (:class:`_RegionPruner`), every
@@ -697,7 +724,6 @@ class StackPruner:
         single thread's 4-6 ms at two to four ranks."""
         lib = nat.lib()
         n = ar.n
-        ncol = ar.store.shape[1]
         halo = [(q, p) for q, p in enumerate(parts) if q != me and mine_box is not None and len(p)]
         room = n + sum(len(p) for _, p in halo)
         if room > ar.cap:
@@ -731,28 +757,7 @@ class StackPruner:
                 rp.run_all()
                 _lap(f"three passes on own + halo rows ({len(rp.regions)} regions)")
                 counts = np.ascontiguousarray(sum(d[3] for d in rp.done))
-                width = (ncol - 3) if final is None else len(final[0])
-                mine = np.empty((sum(len(d[0]) for d in rp.done), width + 1))
-                row = 0
-                csrc = None if final is None else (ctypes.c_int32 * width)(*final[0])
-                cols3 = (ctypes.c_int32 * 3)(*[int(v) for v in abs_inds])
-                # (regions in order: the merge by key is stable)
-                live = [d for d in rp.done if len(d[0])]
-                if final is not None:       # one threaded pass over all the regions' lists
-                    if live:
-                        n_rows = np.array([len(d[0]) for d in live], dtype=np.int64)
-                        ptrs = [(ctypes.c_void_p * len(live))(*[d[c].ctypes.data for d in live]) for c in range(3)]
-                        nat.check(lib.mmx_host_emit_parts_final(
-                            ar.store.ctypes.data, ar.store.strides[0] // 8, len(live), ptrs[0], ptrs[1], ptrs[2],
-                            n_rows.ctypes.data, csrc, width, final[1], mine.ctypes.data, len(mine)),
-                            "mmx_host_emit_parts_final")
-                else:                       # (tables with co-localisation columns: region by region)
-                    for r_ids, r_keys, r_abs, _ in live:
-                        k = len(r_ids)
-                        nat.check(lib.mmx_host_emit_survivors(
-                            ar.store.ctypes.data, ar.store.strides[0] // 8, r_ids.ctypes.data, r_keys.ctypes.data, k,
-                            width, r_abs.ctypes.data, cols3, mine[row:row + k].ctypes.data), "mmx_host_emit_survivors")
-                        row += k
+                mine = cls._emit_survivors(ar, rp.done, layout)         # (regions in order: the merge by key is stable)
                 _lap("own survivors in final form")
                 return mine, counts
         ids = np.empty(max(1, n), dtype=np.int64)
@@ -774,24 +779,21 @@ class StackPruner:
         k = out_n.value
         counts = np.ascontiguousarray(np.moveaxis(stat, 0, -1))
         _lap("three passes on own + halo rows")
-        if final is not None:       # (the survivors leave in the table's final columns: fewer values to exchange and merge)
-            src, dst0 = final
-            mine = np.empty((k, len(src) + 1))
-            if k:
-                nat.check(lib.mmx_host_emit_survivors_final(
-                    ar.store.ctypes.data, ar.store.strides[0] // 8, ids.ctypes.data, keys.ctypes.data, k,
-                    (ctypes.c_int32 * len(src))(*src), len(src), abs_rows.ctypes.data, dst0, mine.ctypes.data),
-                    "mmx_host_emit_survivors_final")
-            _lap("own survivors in final form")
-            return mine, counts
-        mine = np.empty((k, ncol - 2))
-        if k:
-            cols3 = (ctypes.c_int32 * 3)(*[int(v) for v in abs_inds])
-            nat.check(lib.mmx_host_emit_survivors(
-                ar.store.ctypes.data, ar.store.strides[0] // 8, ids.ctypes.data, keys.ctypes.data, k, ncol - 3,
-                abs_rows.ctypes.data, cols3, mine.ctypes.data), "mmx_host_emit_survivors")
+        mine = cls._emit_survivors(ar, [(ids[:k], keys[:k], abs_rows[:k])], layout)
         _lap("own survivors in final form")
         return mine, counts
+
+    @staticmethod
+    def _emit_survivors(ar, lists, layout):
+        """The survivors of ``lists`` (a rank's regions, in order) as the second exchange carries them: their rows of the
+        arena in the columns of ``layout`` -- in the table's final columns there are fewer values to exchange and merge
+        -- and the key behind them; one threaded native pass over all the lists."""
+        n_parts, ids, keys, abs_rows, n_rows = _survivor_lists(lists)
+        mine = np.empty((int(n_rows.sum()), layout.n_out + 1))
+        nat.check(nat.lib().mmx_host_emit_parts(
+            ar.store.ctypes.data, ar.store.strides[0] // 8, n_parts, ids, keys, abs_rows, n_rows.ctypes.data, layout.c,
+            mine.ctypes.data, len(mine)), "mmx_host_emit_parts")
+        return mine
 
     @classmethod
     def prune_blobs_mp(cls, img, seg_rois, overlap, tol, sub_roi_slices, sub_rois_offsets,
@@ -836,20 +838,15 @@ class StackPruner:
             if plan is None:            # (cannot be: the tables stay on their ranks only for a regular geometry)
                 plan = cls._axis_plan(shape3, overlap, tol, overlap_padding, sub_roi_slices, sub_rois_offsets)
             # (the same decision on every rank: it follows from the arena's width and the registry alone)
-            final = (cls._final_columns(seg_rois.arena.store, detector.Blobs._get_abs_inds(), n_flag_cols)
-                     if final_form else None)
-            out, counts = cls._prune_distributed(seg_rois, shape3, plan, sub_roi_slices, channels,
-                                                 None if final is None else final[:2])
+            layout = cls._layout(seg_rois.arena.store, detector.Blobs._get_abs_inds(), final_form, n_flag_cols)
+            out, counts = cls._prune_distributed(seg_rois, shape3, plan, sub_roi_slices, channels, layout)
             if out is None:
                 return None, None
-            if final is not None:
-                rest = None
-                if final[3] < len(final[0]):        # (the merge leaves one table: final columns | the flags' columns)
-                    rest = np.ascontiguousarray(out[:, final[3]:])
-                    out = np.ascontiguousarray(out[:, :final[3]])
-                out = out.view(_FinalTable)
-                out.col_names, out.coloc_cols = final[2], rest
-            return out, cls._ratio_frame(cls._ratios_from_counts(counts, plan))
+            rest = None
+            if layout.n_main < layout.n_out:        # (the merge leaves one table: final columns | the flags' columns)
+                rest = np.ascontiguousarray(out[:, layout.n_main:])
+                out = np.ascontiguousarray(out[:, :layout.n_main])
+            return layout.dress(out, rest), cls._ratio_frame(cls._ratios_from_counts(counts, plan))
         arena = getattr(seg_rois, "arena", None)
         if arena is not None and not arena.intact(seg_rois, sample_columns=not untouched):
             arena = None
@@ -881,13 +878,12 @@ class StackPruner:
         ncol = merged.shape[1]
         detector.Blobs(merged)      # bind the class-level column registry to the 11 standard columns
         abs_inds = detector.Blobs._get_abs_inds()
-        final = cls._final_columns(merged, abs_inds, n_flag_cols) if final_form else None
-        gather_as = None if final is None else (final[0], final[1], final[3])
+        layout = cls._layout(merged, abs_inds, final_form, n_flag_cols)
         # regions of this very call finished while the GPU was still detecting (StackDetector.plan_pruning)
         if early is not None and arena is not None and early.matches(arena, plan, channels) and \
-                getattr(early, "serves", lambda g: True)(gather_as):
+                getattr(early, "serves", lambda g: True)(layout):
             _lap("set-up (arena check, geometry, registry)")
-            out, counts = early.finish(abs_inds, gather_as, _lap)
+            out, counts = early.finish(abs_inds, layout, _lap)
             _lap("regions pruned during detection: the rest + merge")
         else:
             if early is not None:       # other parameters than planned for, or tables edited since: not usable
@@ -909,12 +905,8 @@ class StackPruner:
             rows, _, counts = cls._prune_table(zyx, tags, abs_cur, None if one_channel else chan, 0, len(zyx),
                                                channels, plan)
             _lap("three axis passes")
-            out = cls._take_rows(merged, rows, abs_cur, abs_inds, gather_as)
+            out = cls._take_rows(merged, rows, abs_cur, layout)
             _lap("gather of the output table")
-        if final is not None:
-            rest = getattr(out, "coloc_cols", None)
-            out = out.view(_FinalTable)
-            out.col_names, out.coloc_cols = final[2], rest
         df = cls._ratio_frame(cls._ratios_from_counts(counts, plan))
         _lap("ratio frame")
         return out, df

@@ -278,7 +278,7 @@ class _StackFinisher:
 
     def __init__(self, sink: "_ArenaSink", plan, channels):
         self.sink, self.arena, self.plan, self.channels = sink, sink.arena, plan, list(channels)
-        self.layout = None          # (source columns, place of the abs coordinates, names, n_main) of the table made
+        self.layout = None          # the columns of the table made (a _RowLayout)
         self.result = None          # (final table, counts)
         self.deferred = 0           # why the last run was left to the caller (mmx_host_finish_stack's stats[6])
 
@@ -289,7 +289,7 @@ class _StackFinisher:
         if ar.n or self.result is not None or len(self.channels) != 1 or chl != self.channels[0]:
             return None
         layout = StackPruner._final_columns(ar.store, detector.Blobs._get_abs_inds())
-        if layout is None or layout[3] != len(layout[0]):
+        if layout is None or layout.n_main != layout.n_out:
             return None
         nb = len(indices)
         if max(n_cands, 1) > ar.cap:
@@ -303,12 +303,10 @@ class _StackFinisher:
         any_before = np.zeros(nb, dtype=np.uint8)
         ld = self.plan["max_slabs"]
         stat = np.zeros((3, 3, ld), dtype=np.int64)           # [kind][axis][slab]
-        src = layout[0]
-        out = np.empty((max(n_cands, 1), len(src)))
+        out = np.empty((max(n_cands, 1), layout.n_out))
         out_rows = ctypes.c_int64(0)
         st = np.zeros(8)
         n_sec, bounds, last_end, tol3, nxt_lo, nxt_hi = self.plan["c_args"]
-        src_c = (ctypes.c_int32 * len(src))(*src)
         a = nat.FinishStackArgs()
         a.cands, a.n_cands, a.n_total = (cands.ctypes.data if len(cands) else None), int(n_cands), len(cands)
         a.blocks, a.n_blocks, a.n_sigma = blocks.ctypes.data, nb, len(sig)
@@ -325,7 +323,7 @@ class _StackFinisher:
         a.tol = ctypes.cast(tol3, ctypes.c_void_p)
         a.nxt_lo, a.nxt_hi = ctypes.cast(nxt_lo, ctypes.c_void_p), ctypes.cast(nxt_hi, ctypes.c_void_p)
         a.n_slab, a.n_after, a.n_next, a.stat_ld = stat[0].ctypes.data, stat[1].ctypes.data, stat[2].ctypes.data, ld
-        a.src_cols, a.n_out, a.abs_dst0 = ctypes.cast(src_c, ctypes.c_void_p), len(src), layout[1]
+        a.src_cols, a.n_out, a.abs_dst0 = ctypes.cast(layout.src_c, ctypes.c_void_p), layout.n_out, layout.abs_dst[0]
         a.out, a.out_capacity = out.ctypes.data, len(out)
         a.out_rows = ctypes.cast(ctypes.pointer(out_rows), ctypes.c_void_p)
         a.stats = st.ctypes.data
@@ -345,19 +343,17 @@ class _StackFinisher:
         counts = np.zeros((1, 3, ld, 3), dtype=np.int64)
         counts[0] = np.moveaxis(stat, 0, -1)
         self.layout = layout
-        self.result = (out[:out_rows.value], counts)
+        self.result = (layout.dress(out[:out_rows.value]), counts)
         return tables
 
     # ---- towards prune_blobs_mp: the part of a _RegionPruner
     def matches(self, arena, plan, channels) -> bool:
         return self.result is not None and _RegionPruner.matches(self, arena, plan, channels)
 
-    def serves(self, gather_as) -> bool:
-        lay = self.layout
-        return (gather_as is not None and lay is not None and list(gather_as[0]) == list(lay[0])
-                and gather_as[1] == lay[1] and gather_as[2] == lay[3])
+    def serves(self, layout) -> bool:
+        return self.layout is not None and self.layout == layout
 
-    def finish(self, abs_inds, final=None, _lap=lambda what: None):
+    def finish(self, abs_inds, layout, _lap=lambda what: None):
         return self.result
 
     def advance(self) -> None:

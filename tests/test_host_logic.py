@@ -551,10 +551,26 @@ def test_map_columns_native_matches_numpy():
     assert lib.mmx_host_map_columns(t.ctypes.data, 4, 4, cols, 2, t.ctypes.data, 4, 0) == 1     # bad column
 
 
+def _row_layout(n_out, abs_dst, src=None, n_main=0):
+    """An ``mmx_row_layout`` for a native call (the structure keeps its source columns alive)."""
+    from magellanmapper_amd import _native as nat
+    csrc = None if src is None else (ctypes.c_int32 * len(src))(*src)
+    return ctypes.byref(nat.RowLayout(csrc, n_out, n_main, (ctypes.c_int32 * 3)(*abs_dst)))
+
+
+def _list_args(lists):
+    """``n_parts, ids, keys, abs_rows, n_rows`` of a native call for survivor lists ``(ids, keys, abs_rows)``; empty
+    lists are passed as such, with null pointers."""
+    ptrs = [(ctypes.c_void_p * max(1, len(lists)))(*[(d[c].ctypes.data if len(d[0]) else None) for d in lists])
+            for c in range(3)]
+    return len(lists), ptrs[0], ptrs[1], ptrs[2], np.array([len(d[0]) for d in lists], dtype=np.int64)
+
+
 def test_native_gathers_in_final_columns():
-    """mmx_host_take_rows_final / mmx_host_gather_parts_by_key_final: out[i][j] = table[row][src_cols[j]], the abs
-    coordinates written at abs_dst0 -- against NumPy, on a table large enough for the threaded path; bad arguments
-    are refused."""
+    """mmx_host_take_rows / mmx_host_gather_parts_by_key with a layout of final columns: out[i][j] =
+    table[row][src_cols[j]], the abs coordinates written at abs_dst -- against NumPy, on a table large enough for the
+    threaded path; the plain layout (also wider than 64 columns) and the two-table form likewise; bad arguments are
+    refused."""
     from magellanmapper_amd import _native as nat
     L = nat.lib()
     rng = np.random.default_rng(21)
@@ -563,72 +579,138 @@ def test_native_gathers_in_final_columns():
     rows = rng.permutation(n_table)[:n].astype(np.int64)
     absz = rng.random((n_table, 3))
     src = [0, 1, 2, 3, 4, 5, 6, 10]
-    csrc = (ctypes.c_int32 * len(src))(*src)
+    final = _row_layout(len(src), (0, 1, 2), src)
+    plain = _row_layout(ld - 3, (7, 8, 9))
     out = np.empty((n, len(src)))
-    nat.check(L.mmx_host_take_rows_final(table.ctypes.data, ld, rows.ctypes.data, n, csrc, len(src), absz.ctypes.data, 0,
-                                         out.ctypes.data), "take_rows_final")
+    nat.check(L.mmx_host_take_rows(table.ctypes.data, ld, rows.ctypes.data, n, absz.ctypes.data, final, out.ctypes.data,
+                                   None), "take_rows, final columns")
     want = table[rows][:, src]
     want[:, 0:3] = absz[rows]
     np.testing.assert_array_equal(out, want)
+    full = np.empty((n, ld - 3))
+    nat.check(L.mmx_host_take_rows(table.ctypes.data, ld, rows.ctypes.data, n, absz.ctypes.data, plain, full.ctypes.data,
+                                   None), "take_rows, plain")
+    want_full = table[rows][:, :ld - 3]
+    want_full[:, 7:10] = absz[rows]
+    np.testing.assert_array_equal(full, want_full)
     # by key, from several lists: rows land in key order, equal keys in the order of the concatenated lists
     keys = rng.integers(0, 97, n).astype(np.int64)
     abs_rows = rng.random((n, 3))
 
-    def gather(cuts, n_keys=97):
+    def gather(cuts, n_keys=97, layout=final, width=len(src), n_rest=0, ids=rows):
         edges = [0] + list(cuts) + [n]
-        parts = [(rows[a:b], keys[a:b], abs_rows[a:b]) for a, b in zip(edges[:-1], edges[1:])]
-        n_rows = np.array([len(p_[0]) for p_ in parts], dtype=np.int64)
-        ptrs = [(ctypes.c_void_p * len(parts))(*[p_[c].ctypes.data for p_ in parts]) for c in range(3)]
-        out2 = np.full((n, len(src)), np.nan)
-        rc = L.mmx_host_gather_parts_by_key_final(table.ctypes.data, ld, len(parts), ptrs[0], ptrs[1], ptrs[2],
-                                                  n_rows.ctypes.data, n_keys, csrc, len(src), 0, out2.ctypes.data, n)
-        return rc, out2
+        parts = [(ids[a:b], keys[a:b], abs_rows[a:b]) for a, b in zip(edges[:-1], edges[1:])]
+        n_parts, p_ids, p_keys, p_abs, n_rows = _list_args(parts)
+        out2 = np.full((n, width), np.nan)
+        rest2 = np.full((n, n_rest), np.nan) if n_rest else None
+        rc = L.mmx_host_gather_parts_by_key(table.ctypes.data, ld, n_parts, p_ids, p_keys, p_abs, n_rows.ctypes.data,
+                                            n_keys, layout, out2.ctypes.data, n, None if rest2 is None else rest2.ctypes.data)
+        return rc, out2, rest2
     order = np.argsort(keys, kind="stable")
     want2 = table[rows[order]][:, src]
     want2[:, 0:3] = abs_rows[order]
+    want2_full = table[rows[order]][:, :ld - 3]
+    want2_full[:, 7:10] = abs_rows[order]
     for cuts in ([], [1], [0, 0, 7000, 7001, 29999], sorted(rng.integers(0, n, 40))):
-        rc, out2 = gather(cuts)
+        rc, out2, _ = gather(cuts)
         assert rc == 0
         np.testing.assert_array_equal(out2, want2)
+        rc, full2, _ = gather(cuts, layout=plain, width=ld - 3)
+        assert rc == 0
+        np.testing.assert_array_equal(full2, want2_full)
     # ... and equal to the two-step form: gather in the table's columns, then the column shuffles
-    cols3 = (ctypes.c_int32 * 3)(7, 8, 9)
-    full = np.empty((n, ld - 3))
-    nat.check(L.mmx_host_gather_by_key(table.ctypes.data, ld, rows.ctypes.data, keys.ctypes.data, n, 97, ld - 3,
-                                       abs_rows.ctypes.data, cols3, full.ctypes.data), "gather_by_key")
-    full[:, 0:3] = full[:, 7:10]
-    np.testing.assert_array_equal(out2, full[:, src])
-    bad = (ctypes.c_int32 * 3)(0, 1, 99)
-    assert L.mmx_host_take_rows_final(table.ctypes.data, ld, rows.ctypes.data, n, bad, 3, absz.ctypes.data, 0,
-                                      out.ctypes.data) == 1
-    assert L.mmx_host_take_rows_final(table.ctypes.data, ld, rows.ctypes.data, n, csrc, len(src), absz.ctypes.data, 6,
-                                      out.ctypes.data) == 1                    # abs columns past the row
+    full2[:, 0:3] = full2[:, 7:10]
+    np.testing.assert_array_equal(out2, full2[:, src])
+    # the two-table form: n_main at both ends of its range (the abs columns' end, one column left for the second table)
+    src2 = src + [11, 12]
+    want_t = table[rows][:, src2]
+    want_t[:, 0:3] = absz[rows]
+    want_g = table[rows[order]][:, src2]
+    want_g[:, 0:3] = abs_rows[order]
+    for lay_src, width, w_take, w_gather in ((src2, len(src2), want_t, want_g), (None, ld - 3, None, None)):
+        if lay_src is None:         # (the plain layout in two tables: its abs columns 7..9 have to be in the first)
+            first_main, abs_dst = 10, (7, 8, 9)
+            w_take, w_gather = want_full, want2_full
+        else:
+            first_main, abs_dst = 3, (0, 1, 2)
+        for n_main in (first_main, width - 1):
+            lay = _row_layout(width, abs_dst, lay_src, n_main)
+            main, rest = np.full((n, n_main), np.nan), np.full((n, width - n_main), np.nan)
+            assert L.mmx_host_take_rows(table.ctypes.data, ld, rows.ctypes.data, n, absz.ctypes.data, lay,
+                                        main.ctypes.data, rest.ctypes.data) == 0
+            np.testing.assert_array_equal(np.hstack((main, rest)), w_take)
+            rc, main, rest = gather(sorted(rng.integers(0, n, 5)), layout=lay, width=n_main, n_rest=width - n_main)
+            assert rc == 0
+            np.testing.assert_array_equal(np.hstack((main, rest)), w_gather)
+        for n_main in (first_main - 1, width, width + 1):     # abs columns cut off; nothing left for the second table
+            lay = _row_layout(width, abs_dst, lay_src, n_main)
+            main, rest = np.empty((n, width + 1)), np.empty((n, width + 1))
+            assert L.mmx_host_take_rows(table.ctypes.data, ld, rows.ctypes.data, n, absz.ctypes.data, lay,
+                                        main.ctypes.data, rest.ctypes.data) == 1
+            assert gather([100], layout=lay, width=width + 1, n_rest=width + 1)[0] == 1
+    # a plain layout wider than 64 columns
+    wide = rng.random((3000, 80))
+    w_rows = rng.permutation(3000)[:2000].astype(np.int64)
+    w_out = np.empty((2000, 77))
+    assert L.mmx_host_take_rows(wide.ctypes.data, 80, w_rows.ctypes.data, 2000, absz.ctypes.data,
+                                _row_layout(77, (70, 3, 76)), w_out.ctypes.data, None) == 0
+    w_want = wide[w_rows][:, :77]
+    w_want[:, [70, 3, 76]] = absz[w_rows]
+    np.testing.assert_array_equal(w_out, w_want)
+    w_lists = [(w_rows, keys[:2000], abs_rows[:2000])]
+    w_order = np.argsort(keys[:2000], kind="stable")
+    n_parts, p_ids, p_keys, p_abs, n_rows = _list_args(w_lists)
+    assert L.mmx_host_gather_parts_by_key(wide.ctypes.data, 80, n_parts, p_ids, p_keys, p_abs, n_rows.ctypes.data, 97,
+                                          _row_layout(77, (70, 3, 76)), w_out.ctypes.data, 2000, None) == 0
+    w_want = wide[w_rows[w_order]][:, :77]
+    w_want[:, [70, 3, 76]] = abs_rows[:2000][w_order]
+    np.testing.assert_array_equal(w_out, w_want)
+    # refusals
+    assert L.mmx_host_take_rows(table.ctypes.data, ld, rows.ctypes.data, n, absz.ctypes.data,
+                                _row_layout(3, (0, 1, 2), [0, 1, 99]), out.ctypes.data, None) == 1
+    assert L.mmx_host_take_rows(table.ctypes.data, ld, rows.ctypes.data, n, absz.ctypes.data,
+                                _row_layout(len(src), (6, 7, 8), src), out.ctypes.data, None) == 1    # abs columns past the row
+    assert L.mmx_host_take_rows(table.ctypes.data, ld, rows.ctypes.data, n, absz.ctypes.data,
+                                _row_layout(ld + 1, (7, 8, 9)), out.ctypes.data, None) == 1           # wider than the table
     assert gather([100], n_keys=5)[0] == 1                                       # key >= n_keys
+    assert gather([100], n_keys=(1 << 26) + 1)[0] == 5                           # MMX_ERR_UNSUPPORTED
+    neg = rows.copy()
+    neg[n - 7] = -1
+    assert L.mmx_host_take_rows(table.ctypes.data, ld, neg.ctypes.data, n, absz.ctypes.data, final, out.ctypes.data,
+                                None) == 1
+    assert gather([100], ids=neg)[0] == 1
+    assert gather([100], ids=neg, layout=plain, width=ld - 3)[0] == 1
 
 
 def test_native_merge_by_key_reads_keys_in_place():
-    """mmx_host_merge_by_key: the stable sort of rows by key (threaded counting sort), keys from an array or from the
-    column behind the rows' own (how the ranks' survivors arrive); keys out of range are refused."""
+    """mmx_host_merge_parts_by_key with one block: the stable sort of rows by key (threaded counting sort), keys from
+    the column behind the rows' own (how the ranks' survivors arrive); keys out of range are refused."""
     from magellanmapper_amd import _native as nat
     L = nat.lib()
     rng = np.random.default_rng(8)
+
+    def merge(rows, n_keys, n_cols, out):
+        n = ctypes.c_int64(len(rows))
+        block = (ctypes.c_void_p * 1)(rows.ctypes.data)
+        return L.mmx_host_merge_parts_by_key(block, ctypes.byref(n), 1, rows.shape[1], n_keys, n_cols, out.ctypes.data,
+                                             len(rows))
     for n in (0, 1, 777, 60000):
         n_cols, n_keys = 8, 500
         rows = rng.random((n, n_cols + 1))
         keys = rng.integers(0, n_keys, n).astype(np.int64)
         rows[:, n_cols] = keys
         want = rows[np.argsort(keys, kind="stable"), :n_cols]
-        for kp in (keys.ctypes.data, None):
-            out = np.full((n, n_cols), np.nan)
-            assert L.mmx_host_merge_by_key(rows.ctypes.data, n_cols + 1, kp, n, n_keys, n_cols, out.ctypes.data) == 0
-            np.testing.assert_array_equal(out, want)
+        out = np.full((n, n_cols), np.nan)
+        assert merge(rows, n_keys, n_cols, out) == 0
+        np.testing.assert_array_equal(out, want)
     out = np.empty((n, n_cols))
-    assert L.mmx_host_merge_by_key(rows.ctypes.data, n_cols + 1, None, n, 100, n_cols, out.ctypes.data) == 1     # key >= n_keys
+    assert merge(rows, 100, n_cols, out) == 1     # key >= n_keys
     rows[5, n_cols] = -1.0
-    assert L.mmx_host_merge_by_key(rows.ctypes.data, n_cols + 1, None, n, n_keys, n_cols, out.ctypes.data) == 1
+    assert merge(rows, n_keys, n_cols, out) == 1
     rows[5, n_cols] = np.nan
-    assert L.mmx_host_merge_by_key(rows.ctypes.data, n_cols + 1, None, n, n_keys, n_cols, out.ctypes.data) == 1
-    # (no room for a key column behind the rows' own: a key array is required)
-    assert L.mmx_host_merge_by_key(rows.ctypes.data, n_cols + 1, None, n, n_keys, n_cols + 1, out.ctypes.data) == 1
+    assert merge(rows, n_keys, n_cols, out) == 1
+    # (no room for a key column behind the rows' own)
+    assert merge(rows, n_keys, n_cols + 1, out) == 1
 
 
 def test_native_merge_of_padded_blocks_by_key():
@@ -657,34 +739,45 @@ def test_native_merge_of_padded_blocks_by_key():
 
 
 def test_native_emit_of_several_survivor_lists_at_once():
-    """mmx_host_emit_parts_final == mmx_host_emit_survivors_final list by list, back to back (threaded over the
-    concatenation: lists of any length, empty ones included)."""
+    """mmx_host_emit_parts: the lists' rows back to back in the columns of the layout, the key appended -- against NumPy
+    and against one call per list (threaded over the concatenation: lists of any length, empty ones included)."""
     from magellanmapper_amd import _native as nat
     L = nat.lib()
     rng = np.random.default_rng(10)
     n_table, ld = 90000, 14
     table = rng.random((n_table, ld))
     src = [0, 1, 2, 3, 4, 5, 6, 10]
-    csrc = (ctypes.c_int32 * len(src))(*src)
-    for counts in ([7], [0, 0], [4000, 0, 1, 25000, 9000, 12000]):
-        lists = [(rng.integers(0, n_table, c).astype(np.int64), rng.integers(0, 500, c).astype(np.int64), rng.random((c, 3)))
-                 for c in counts]
-        want = []
-        for ids, keys, ab in lists:
-            o = np.empty((len(ids), len(src) + 1))
-            if len(ids):
-                nat.check(L.mmx_host_emit_survivors_final(table.ctypes.data, ld, ids.ctypes.data, keys.ctypes.data, len(ids),
-                                                          csrc, len(src), ab.ctypes.data, 0, o.ctypes.data), "emit")
-            want.append(o)
-        want = np.concatenate(want)
-        n_rows = np.array(counts, dtype=np.int64)
-        ptrs = [(ctypes.c_void_p * len(lists))(*[(d[c].ctypes.data if len(d[0]) else None) for d in lists]) for c in range(3)]
-        out = np.full((len(want), len(src) + 1), np.nan)
-        assert L.mmx_host_emit_parts_final(table.ctypes.data, ld, len(lists), ptrs[0], ptrs[1], ptrs[2], n_rows.ctypes.data,
-                                           csrc, len(src), 0, out.ctypes.data, len(want)) == 0
-        np.testing.assert_array_equal(out, want)
-    assert L.mmx_host_emit_parts_final(table.ctypes.data, ld, len(lists), ptrs[0], ptrs[1], ptrs[2], n_rows.ctypes.data,
-                                       csrc, len(src), 0, out.ctypes.data, len(want) + 1) == 1
+
+    def emit(lists, layout, width, out_rows=None):
+        n_parts, p_ids, p_keys, p_abs, n_rows = _list_args(lists)
+        total = int(n_rows.sum())
+        out = np.full((total, width + 1), np.nan)
+        rc = L.mmx_host_emit_parts(table.ctypes.data, table.shape[1], n_parts, p_ids, p_keys, p_abs, n_rows.ctypes.data,
+                                   layout, out.ctypes.data, total if out_rows is None else out_rows)
+        return rc, out
+    # final columns, the plain layout, and a plain layout wider than 64 columns (of a table of 80)
+    for lay_src, width, abs_dst in ((src, len(src), (0, 1, 2)), (None, 11, (7, 8, 9)), (None, 77, (70, 3, 76))):
+        layout = _row_layout(width, abs_dst, lay_src)
+        if width > ld:
+            table = rng.random((n_table, 80))
+        for counts in ([7], [0, 0], [4000, 0, 1, 25000, 9000, 12000]):
+            lists = [(rng.integers(0, n_table, c).astype(np.int64), rng.integers(0, 500, c).astype(np.int64),
+                      rng.random((c, 3))) for c in counts]
+            want, single = [], []
+            for ids, keys, ab in lists:
+                o = table[ids][:, list(range(width)) if lay_src is None else lay_src]
+                o[:, list(abs_dst)] = ab
+                want.append(np.column_stack((o, keys.astype(np.float64))))
+                rc, o1 = emit([(ids, keys, ab)], layout, width)         # (n_parts = 1)
+                assert rc == 0
+                single.append(o1)
+            rc, out = emit(lists, layout, width)
+            assert rc == 0
+            np.testing.assert_array_equal(out, np.concatenate(want))
+            np.testing.assert_array_equal(out, np.concatenate(single))
+        assert emit(lists, layout, width, out_rows=len(out) + 1)[0] == 1
+        lists[3][0][11] = -1                                            # a negative row id
+        assert emit(lists, layout, width)[0] == 1
 
 
 def test_native_prune_works_in_a_forked_child():
@@ -697,12 +790,11 @@ def test_native_prune_works_in_a_forked_child():
     table = rng.random((n, 6))
     rows = np.arange(n, dtype=np.int64)[::-1].copy()
     absz = rng.random((n, 3))
-    cols = (ctypes.c_int32 * 3)(0, 1, 2)
 
     def take():
         out = np.empty((n, 5))
-        nat.check(nat.lib().mmx_host_take_rows(table.ctypes.data, 6, rows.ctypes.data, n, 5, absz.ctypes.data, cols,
-                                               out.ctypes.data), "take")
+        nat.check(nat.lib().mmx_host_take_rows(table.ctypes.data, 6, rows.ctypes.data, n, absz.ctypes.data,
+                                               _row_layout(5, (0, 1, 2)), out.ctypes.data, None), "take")
         return out
 
     want = take()                      # builds the pool (threads) in this process
@@ -1469,7 +1561,7 @@ def test_save_subimage_writes_the_roi_unless_it_is_the_open_memmap(tmp_path, cap
 
 
 def test_rank_table_plumbing_natives():
-    """``mmx_host_rows_in_boxes`` / ``mmx_host_append_rows`` / ``mmx_host_emit_survivors`` (the table plumbing of the
+    """``mmx_host_rows_in_boxes`` / ``mmx_host_append_rows`` / ``mmx_host_emit_parts`` (the table plumbing of the
     distributed pruning, host code only) against their NumPy statements, incl. the overflow counts and bad arguments."""
     from magellanmapper_amd import _native as nat
     lib = nat.lib()
@@ -1529,15 +1621,15 @@ def test_rank_table_plumbing_natives():
     keys = rng.integers(0, 99, len(ids)).astype(np.int64)
     abs_rows = rng.normal(size=(len(ids), 3))
     got = np.empty((len(ids), 12))
-    cols3 = (ctypes.c_int32 * 3)(7, 8, 9)
-    nat.check(lib.mmx_host_emit_survivors(store.ctypes.data, ncol, ids.ctypes.data, keys.ctypes.data, len(ids), 11,
-                                          abs_rows.ctypes.data, cols3, got.ctypes.data), "emit_survivors")
+    n_parts, p_ids, p_keys, p_abs, n_rows = _list_args([(ids, keys, abs_rows)])
+    nat.check(lib.mmx_host_emit_parts(store.ctypes.data, ncol, n_parts, p_ids, p_keys, p_abs, n_rows.ctypes.data,
+                                      _row_layout(11, (7, 8, 9)), got.ctypes.data, len(ids)), "emit_parts")
     ref = store[ids, :11].copy()
     ref[:, 7:10] = abs_rows
     np.testing.assert_array_equal(got[:, :11], ref)
     np.testing.assert_array_equal(got[:, 11], keys)
-    assert lib.mmx_host_emit_survivors(store.ctypes.data, ncol, ids.ctypes.data, keys.ctypes.data, len(ids), 15,
-                                       abs_rows.ctypes.data, cols3, got.ctypes.data) == 1
+    assert lib.mmx_host_emit_parts(store.ctypes.data, ncol, n_parts, p_ids, p_keys, p_abs, n_rows.ctypes.data,
+                                   _row_layout(15, (7, 8, 9)), got.ctypes.data, len(ids)) == 1
 
 
 def test_geometry_memo_and_ratio_frame():

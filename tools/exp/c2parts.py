@@ -67,8 +67,8 @@ class _Timed:
 
 _L = nat.lib()
 for _n in ("mmx_host_resolve_peaks", "mmx_host_overlap_prune", "mmx_host_emit_tables", "mmx_host_prune_region",
-           "mmx_host_prune_axis", "mmx_host_take_rows", "mmx_host_map_columns", "mmx_detect_batch", "mmx_graph_launch",
-           "mmx_event_synchronize"):
+           "mmx_host_prune_axis", "mmx_host_take_rows", "mmx_host_gather_parts_by_key", "mmx_host_map_columns",
+           "mmx_detect_batch", "mmx_graph_launch", "mmx_event_synchronize"):
     if hasattr(_L, _n):
         setattr(_L, _n, _Timed(getattr(_L, _n), "    native " + _n))
 
