@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MMX_ABI_VERSION 19
+#define MMX_ABI_VERSION 20
 
 typedef enum {
     MMX_OK = 0,
@@ -580,6 +580,15 @@ int mmx_host_stage_upload(const void* h_src, void* d_dst, const int64_t* regions
                           int64_t ny, int64_t row_bytes, void* const* h_staging, int64_t staging_bytes, int32_t depth,
                           void* const* events, void* stream, int32_t device, int64_t* n_queued, const int32_t* cancel,
                           int32_t n_threads);
+/* The same with a source PLANE PITCH (ABI v20): h_src is the first voxel of a box of a larger host image -- planes
+ * [z_lo, z_hi) and rows [y_lo, y_hi) of it, x and channels whole, e.g. `img[z_lo:z_hi, y_lo:y_hi]` of a memory map --
+ * whose nz planes of ny * row_bytes packed bytes lie src_pitch bytes apart (the larger image's plane; MMX_ERR_ARG when
+ * src_pitch < ny * row_bytes).  The box is read where it lies: no packed host copy of it is needed.  regions, d_dst and
+ * everything else are relative to the box, as above; mmx_host_stage_upload is the src_pitch = ny * row_bytes case. */
+int mmx_host_stage_upload_pitched(const void* h_src, int64_t src_pitch, void* d_dst, const int64_t* regions,
+                                  int32_t n_regions, int64_t nz, int64_t ny, int64_t row_bytes, void* const* h_staging,
+                                  int64_t staging_bytes, int32_t depth, void* const* events, void* stream, int32_t device,
+                                  int64_t* n_queued, const int32_t* cancel, int32_t n_threads);
 int mmx_event_query(void* ev);      /* 0: completed, 1: not yet, else an mmx_status */
 int mmx_event_create(void** ev);
 int mmx_event_destroy(void* ev);

@@ -419,6 +419,9 @@ def _make_blocks(dvol: DeviceVolume, channel: int, origins, shapes):
     shp = np.asarray(shapes, dtype=np.int64).reshape(-1, 3)
     if (o < 0).any() or (shp < 1).any() or (o + shp > np.asarray(dvol.shape[:3], dtype=np.int64)).any():
         raise ValueError("block outside the volume")
+    held_lo = np.array([dvol.z_off, dvol.y_off, 0], dtype=np.int64)
+    if (o < held_lo).any() or (o[:, :2] + shp[:, :2] > held_lo[:2] + np.asarray(t.shape[:2], dtype=np.int64)).any():
+        raise ValueError("block outside the planes and rows this volume holds")
     px = -(-shp[:, 2] // nat.MMX_ROW_ALIGN) * nat.MMX_ROW_ALIGN      # 128-B aligned rows
     blocks["src_off"] = o @ strides
     blocks["nz"], blocks["ny"], blocks["nx"] = shp[:, 0], shp[:, 1], shp[:, 2]

@@ -344,6 +344,9 @@ int mmx_graph_destroy(void* graph)
 // time -- 413 against 289 ms for a C5 tile from a memory map.  *cancel != 0 ends the loop at the next region.  The
 // caller owns every buffer and event and keeps them alive until the call has returned AND the last recorded event has
 // completed.  Returns MMX_OK also when cancelled (n_queued says how far it came).
+// The source may be a box of a larger host image (planes and rows of it, x and channels whole): its planes are packed
+// (ny * row_bytes each) but lie src_pitch bytes apart -- the larger image's plane -- and are read where they are
+// (mmx_host_stage_upload_pitched; the unpitched entry is its src_pitch = ny * row_bytes case).
 namespace {
 struct spin_barrier {
     std::atomic<int> count{0};
@@ -366,14 +369,15 @@ struct spin_barrier {
 };
 }  // namespace
 
-int mmx_host_stage_upload(const void* h_src, void* d_dst, const int64_t* regions, int32_t n_regions, int64_t nz,
-                          int64_t ny, int64_t row_bytes, void* const* h_staging, int64_t staging_bytes, int32_t depth,
-                          void* const* events, void* stream, int32_t device, int64_t* n_queued, const int32_t* cancel,
-                          int32_t n_threads)
+int mmx_host_stage_upload_pitched(const void* h_src, int64_t src_pitch, void* d_dst, const int64_t* regions,
+                                  int32_t n_regions, int64_t nz, int64_t ny, int64_t row_bytes, void* const* h_staging,
+                                  int64_t staging_bytes, int32_t depth, void* const* events, void* stream, int32_t device,
+                                  int64_t* n_queued, const int32_t* cancel, int32_t n_threads)
 {
     if (!h_src || !d_dst || !regions || n_regions < 0 || nz < 0 || ny < 1 || row_bytes < 1 || !h_staging || depth < 1 ||
         !events || !n_queued || !cancel)
         return MMX_ERR_ARG;
+    if (row_bytes > INT64_MAX / ny || src_pitch < ny * row_bytes) return MMX_ERR_ARG;       // (planes must not overlap)
     for (int k = 0; k < n_regions; ++k) {
         const int64_t* r = regions + 4 * (int64_t)k;
         if (r[0] < 0 || r[1] > nz || r[0] >= r[1] || r[2] < 0 || r[3] > ny || r[2] >= r[3] ||
@@ -409,9 +413,9 @@ int mmx_host_stage_upload(const void* h_src, void* d_dst, const int64_t* regions
             if (stop.load()) return;
             const int64_t planes = r[1] - r[0], width = (r[3] - r[2]) * row_bytes;
             const int64_t a = planes * t / T, b = planes * (t + 1) / T;
-            const char* src = (const char*)h_src + r[0] * plane + r[2] * row_bytes;
+            const char* src = (const char*)h_src + r[0] * src_pitch + r[2] * row_bytes;
             char* dst = (char*)h_staging[which];
-            for (int64_t z = a; z < b; ++z) std::memcpy(dst + z * width, src + z * plane, (size_t)width);
+            for (int64_t z = a; z < b; ++z) std::memcpy(dst + z * width, src + z * src_pitch, (size_t)width);
             filled.wait();
             if (t == 0) {
                 if (prof) { const double t1 = now(); t_fill += t1 - t0; t0 = t1; }
@@ -434,4 +438,14 @@ int mmx_host_stage_upload(const void* h_src, void* d_dst, const int64_t* regions
         fprintf(stderr, "mmx_host_stage_upload: %d regions, %d threads, %.1f ms: waiting for staging buffers %.1f, filling %.1f, "
                 "queueing copies %.1f\n", n_regions, T, now() - t_begin, t_wait, t_fill, t_queue);
     return status.load();
+}
+
+int mmx_host_stage_upload(const void* h_src, void* d_dst, const int64_t* regions, int32_t n_regions, int64_t nz,
+                          int64_t ny, int64_t row_bytes, void* const* h_staging, int64_t staging_bytes, int32_t depth,
+                          void* const* events, void* stream, int32_t device, int64_t* n_queued, const int32_t* cancel,
+                          int32_t n_threads)
+{
+    if (ny < 1 || row_bytes < 1 || row_bytes > INT64_MAX / ny) return MMX_ERR_ARG;
+    return mmx_host_stage_upload_pitched(h_src, ny * row_bytes, d_dst, regions, n_regions, nz, ny, row_bytes, h_staging,
+                                         staging_bytes, depth, events, stream, device, n_queued, cancel, n_threads);
 }

@@ -84,7 +84,7 @@ class Image5d:
         from . import dist
         if self.device_volume is None and self.img is not None:
             if _image_bytes(self.img[0]) > _resident_limit():
-                return self             # (too large to be resident: detected z-chunk by z-chunk from the host)
+                return self             # (too large to be resident: detected chunk by chunk from the host)
             shape3 = tuple(int(v) for v in self.img.shape[1:4])
             cells = blocks = None
             try:        # (where the first channel's profile puts the block rows: only the upload ORDER depends on it)
@@ -114,10 +114,11 @@ class Image5d:
             dv.close()
 
 
-#: a HOST image larger than this many bytes is detected z-chunk by z-chunk -- whole layers of blocks, each chunk a device
-#: volume of its own with the next one on its way up meanwhile -- instead of going to the device whole (the reference
-#: reads any size through its memory map, importer.py:794); the tables land in the one arena and are pruned once, as
-#: always.  ``None``: a third of the device memory that is free when the call starts.
+#: a HOST image larger than this many bytes is detected chunk by chunk -- whole layers of blocks or, where one layer
+#: alone takes more than half of it, runs of whole block rows of that layer (``_zy_chunks``); each chunk a device volume
+#: of its own with the next one on its way up meanwhile -- instead of going to the device whole (the reference reads any
+#: size through its memory map, importer.py:794); the tables land in the one arena and are pruned once, as always.
+#: ``None``: a third of the device memory that is free when the call starts.
 MAX_RESIDENT_BYTES = None
 
 
@@ -155,6 +156,40 @@ def _z_chunks(coords, mine, origins, shapes, plane_bytes: int, limit: int):
             chunks[-1] = (c[0], k_hi, c[2], max(c[3], z_hi))
         else:
             chunks.append((k_lo, k_hi, z_lo, z_hi))
+    return chunks
+
+
+def _zy_chunks(coords, mine, origins, shapes, plane_bytes: int, row_bytes: int, limit: int):
+    """``_z_chunks``, and a chunk that is a single layer and STILL takes more than ``limit / 2`` bytes cut along y into
+    runs of whole block rows (the blocks of ``mine`` with the same (z, y) grid coordinate: contiguous, ``mine`` being
+    z-major): each run holds the rows its blocks touch, runs are merged while the box stays within ``limit / 2``, and a
+    single block row that does not fit stands alone, as a layer does in ``_z_chunks``.  Rows in the overlap of two
+    neighbouring block rows are part of both runs.  ``[(k_lo, k_hi, z_lo, z_hi, y_lo, y_hi)]``; chunks that are not cut
+    hold all ``plane_bytes // row_bytes`` rows."""
+    n_rows = int(plane_bytes) // max(1, int(row_bytes))
+    chunks = []
+    for k_lo, k_hi, z_lo, z_hi in _z_chunks(coords, mine, origins, shapes, plane_bytes, limit):
+        one_layer = coords[mine[k_lo]][0] == coords[mine[k_hi - 1]][0]
+        if not one_layer or (z_hi - z_lo) * plane_bytes <= limit // 2:
+            chunks.append((k_lo, k_hi, z_lo, z_hi, 0, n_rows))
+            continue
+        first = len(chunks)
+        row = None                                    # grid y of the block row being collected
+        for k in range(k_lo, k_hi):
+            y0, y1 = int(origins[k][1]), int(origins[k][1]) + int(shapes[k][1])
+            c = chunks[-1] if len(chunks) > first else None
+            if c is not None and coords[mine[k]][1] == row:
+                chunks[-1] = (c[0], k + 1, z_lo, z_hi, min(c[4], y0), max(c[5], y1))
+            else:
+                chunks.append((k, k + 1, z_lo, z_hi, y0, y1))
+                row = coords[mine[k]][1]
+        rows, chunks[first:] = chunks[first:], []
+        for r in rows:
+            c = chunks[-1] if len(chunks) > first else None
+            if c is not None and (max(c[5], r[5]) - min(c[4], r[4])) * (z_hi - z_lo) * row_bytes <= limit // 2:
+                chunks[-1] = (c[0], r[1], z_lo, z_hi, min(c[4], r[4]), max(c[5], r[5]))
+            else:
+                chunks.append(r)
     return chunks
 
 
@@ -359,15 +394,19 @@ class StackDetector:
             chunks = None
             if isinstance(img, bl.DeviceVolume):
                 dvol = img
-                held = (int(dvol.z_off), int(dvol.z_off) + int(dvol.tensor.shape[0]))
-                if held != (0, int(shape3[0])):
-                    # a volume that holds some planes only (Image5d.prefetch(own_planes=True), a rank's slab): they
-                    # must be the ones this rank's blocks touch
+                held = (int(dvol.z_off), int(dvol.z_off) + int(dvol.tensor.shape[0]),
+                        int(dvol.y_off), int(dvol.y_off) + int(dvol.tensor.shape[1]))
+                if held != (0, int(shape3[0]), 0, int(shape3[1])):
+                    # a volume that holds some planes (Image5d.prefetch(own_planes=True), a rank's slab) or some rows
+                    # only: they must be the ones this rank's blocks touch
                     z_lo = min(int(o[0]) for o in origins)
                     z_hi = max(int(o[0]) + int(s_[0]) for o, s_ in zip(origins, shapes))
-                    if z_lo < held[0] or z_hi > held[1]:
-                        raise nat.MmxError(f"the device volume holds planes [{held[0]}, {held[1]}) but this rank's blocks "
-                                           f"touch [{z_lo}, {z_hi})")
+                    y_lo = min(int(o[1]) for o in origins)
+                    y_hi = max(int(o[1]) + int(s_[1]) for o, s_ in zip(origins, shapes))
+                    if z_lo < held[0] or z_hi > held[1] or y_lo < held[2] or y_hi > held[3]:
+                        raise nat.MmxError(f"the device volume holds planes [{held[0]}, {held[1]}) and rows [{held[2]}, "
+                                           f"{held[3]}) but this rank's blocks touch planes [{z_lo}, {z_hi}) and rows "
+                                           f"[{y_lo}, {y_hi})")
             else:
                 # the planes this rank's blocks touch (all of them without torch.distributed)
                 z_lo = min(int(o[0]) for o in origins)
@@ -377,12 +416,14 @@ class StackDetector:
                 on_host = getattr(getattr(img, "device", None), "type", "cpu") == "cpu"     # (not a tensor on a device)
                 if not on_host:
                     pass
-                elif (z_hi - z_lo) * plane > _resident_limit() and len({coords[i][0] for i in mine}) > 1:
-                    # too large to be resident: whole layers of blocks at a time, each from a device volume of its own
-                    chunks = _z_chunks(coords, mine, origins, shapes, plane, _resident_limit())
+                elif (z_hi - z_lo) * plane > _resident_limit() and len({coords[i][:2] for i in mine}) > 1:
+                    # too large to be resident: whole layers of blocks at a time -- block rows of a layer that does not
+                    # fit by itself, which a share of ONE layer may well be -- each from a device volume of its own
+                    chunks = _zy_chunks(coords, mine, origins, shapes, plane, plane // max(1, int(shape3[1])),
+                                        _resident_limit())
                 elif z_lo > 0 or z_hi < int(shape3[0]):
-                    # a rank's share of a host image: only its planes go up (over this rank's own link)
-                    chunks = [(0, len(mine), z_lo, z_hi)]
+                    # a rank's share of a host image: only its planes go up (over this rank's own link), every row of them
+                    chunks = [(0, len(mine), z_lo, z_hi, 0, int(shape3[1]))]
             if chunks is None and dvol is None:
                 # a host image handed over for the length of this call: it goes up beside the detection of the blocks
                 # that have landed, and whatever of it this rank's blocks never touched is cancelled before returning
@@ -447,23 +488,26 @@ class StackDetector:
     @classmethod
     def _detect_chunks(cls, img, chunks, sub_roi_slices, shape3, channel, origins, shapes, stats, finish,
                        denoise_max_shape, exclude_of, coloc, sink):
-        """The blocks of this rank's share chunk by chunk (``_z_chunks``): planes ``[z_lo, z_hi)`` of the host image as
-        a device volume that answers for the whole image (``DeviceVolume(z_off=...)``), the next chunk's upload started
-        before this one is detected, the tables through per-chunk sinks into the ONE arena (same pruner, same order of
-        landing as the resident path).  Returns the tables of all blocks, in order."""
+        """The blocks of this rank's share chunk by chunk (``_zy_chunks``): planes ``[z_lo, z_hi)`` and rows
+        ``[y_lo, y_hi)`` of the host image -- a view of it, read where it lies -- as a device volume that answers for the
+        whole image (``DeviceVolume(z_off=..., y_off=...)``), the next chunk's upload started before this one is
+        detected, the tables through per-chunk sinks into the ONE arena (same pruner, same order of landing as the
+        resident path).  Returns the tables of all blocks, in order."""
         from . import blob_log as bl
-        z_ends_all, y_ends = _upload_cells(sub_roi_slices, shape3)
+        z_ends_all, y_ends_all = _upload_cells(sub_roi_slices, shape3)
 
         def volume(c):
-            k_lo, k_hi, z_lo, z_hi = c
-            cells = ([z - z_lo for z in z_ends_all if z_lo < z < z_hi] + [z_hi - z_lo], y_ends)
-            return bl.DeviceVolume(img[z_lo:z_hi], streamed=True, cells=cells, z_off=z_lo, full_shape=shape3)
+            k_lo, k_hi, z_lo, z_hi, y_lo, y_hi = c
+            cells = ([z - z_lo for z in z_ends_all if z_lo < z < z_hi] + [z_hi - z_lo],
+                     [y - y_lo for y in y_ends_all if y_lo < y < y_hi] + [y_hi - y_lo])
+            box = img[z_lo:z_hi] if (y_lo, y_hi) == (0, int(shape3[1])) else img[z_lo:z_hi, y_lo:y_hi]
+            return bl.DeviceVolume(box, streamed=True, cells=cells, z_off=z_lo, y_off=y_lo, full_shape=shape3)
 
         tables = []
         nxt = volume(chunks[0])
         cur = None
         try:
-            for ci, (k_lo, k_hi, z_lo, z_hi) in enumerate(chunks):
+            for ci, (k_lo, k_hi) in enumerate(c[:2] for c in chunks):
                 cur, nxt = nxt, None
                 if ci + 1 < len(chunks):
                     nxt = volume(chunks[ci + 1])     # (its staging starts once this chunk has queued its last region)

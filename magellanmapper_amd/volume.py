@@ -1,5 +1,6 @@
-"""The image on the device: ``DeviceVolume`` (a resident ``(z, y, x[, c])`` tensor, or a host image on its way up z-slab by
-z-slab beside the detection: ``_SlabUpload``) and the host-side ``img_as_float`` for the dtypes the kernels do not read.
+"""The image on the device: ``DeviceVolume`` (a resident ``(z, y, x[, c])`` tensor -- the whole image or a box of its planes
+and rows -- or a host image on its way up z-slab by z-slab beside the detection: ``_SlabUpload``) and the host-side
+``img_as_float`` for the dtypes the kernels do not read.
 Split out of ``blob_log.py`` (round 5); ``blob_log`` re-exports the public names."""
 from __future__ import annotations
 
@@ -55,18 +56,25 @@ class DeviceVolume:
     (optional, streamed uploads only): the image then goes up y-band by y-band within each z-layer of blocks instead of
     in whole z-slabs, and a block can start once the bands it touches have landed.
 
-    ``z_off`` / ``full_shape``: ``image`` holds planes ``[z_off, z_off + nz)`` of a larger ``full_shape = (Z, Y, X)``
-    volume and the object answers for the WHOLE volume -- ``shape`` is the full one, blocks are addressed by their
-    coordinates in it (the views' base pointers are shifted back by ``z_off`` planes), and touching a plane it does not
-    hold is the caller's error.  What a rank's share of a stack (``bench.py``) and a z-chunk of an image too large for
-    the device (``stack_detect``) are.  ``cells`` are then relative to ``image``.
+    ``z_off`` / ``y_off`` / ``full_shape``: ``image`` holds planes ``[z_off, z_off + nz)`` and rows
+    ``[y_off, y_off + ny)`` of a larger ``full_shape = (Z, Y, X)`` volume (x and the channels whole) and the object
+    answers for the WHOLE volume -- ``shape`` is the full one, blocks are addressed by their coordinates in it (the
+    views' base pointers are shifted back by ``z_off`` planes and ``y_off`` rows OF THE BOX: a row is ``stride_y``
+    elements, a plane ``stride_z = ny * stride_y``, so voxel ``(z, y, x)`` of the whole volume is where the kernels'
+    ``z * stride_z + y * stride_y + x * stride_x`` looks for it), and touching a plane or a row it does not hold is the
+    caller's error.  What a rank's share of a stack (``bench.py``) and a chunk of an image too large for the device
+    (``stack_detect``: whole layers of blocks, or block rows of a layer that does not fit) are.  A box of a host
+    image (``img[z_lo:z_hi, y_lo:y_hi]`` of an array or a memory map: a view whose planes lie a whole image plane
+    apart) is streamed from where it is, without a packed host copy.  ``cells`` are then relative to ``image``.
+    :meth:`order_stats` takes whole planes and refuses a volume that holds some rows only.
     """
 
     _upload = None          # the z-slab upload still in flight (`_SlabUpload`), if any
     z_off = 0
+    y_off = 0
 
     def __init__(self, image, device: Optional["torch.device"] = None, streamed: Optional[bool] = None, cells=None,
-                 z_off: int = 0, full_shape=None):
+                 z_off: int = 0, y_off: int = 0, full_shape=None):
         dev = device or _require_gpu()
         want_stream = STREAM_UPLOAD and streamed is not False
         if isinstance(image, torch.Tensor):
@@ -104,12 +112,16 @@ class DeviceVolume:
             raise ValueError("image must be (z, y, x) or (z, y, x, c)")
         self.np_dtype = np_dtype
         self.shape = tuple(self.tensor.shape)
-        if z_off or full_shape is not None:
+        if z_off or y_off or full_shape is not None:
             full = tuple(int(v) for v in (full_shape if full_shape is not None else self.shape[:3]))
-            if len(full) != 3 or full[1:] != self.shape[1:3] or z_off < 0 or z_off + self.shape[0] > full[0]:
-                raise ValueError(f"planes [{z_off}, {z_off + self.shape[0]}) of shape {self.shape[:3]} do not lie in a "
-                                 f"volume of shape {full}")
-            self.z_off = int(z_off)
+            if len(full) == 4 and full[3:] == self.shape[3:]:
+                full = full[:3]             # (the whole image's shape, channels included: they must be the box's)
+            if (len(full) != 3 or full[2] != self.shape[2] or z_off < 0 or z_off + self.shape[0] > full[0]
+                    or y_off < 0 or y_off + self.shape[1] > full[1]):
+                self.close()
+                raise ValueError(f"planes [{z_off}, {z_off + self.shape[0]}) and rows [{y_off}, {y_off + self.shape[1]}) "
+                                 f"of shape {self.shape[:3]} do not lie in a volume of shape {full}")
+            self.z_off, self.y_off = int(z_off), int(y_off)
             self.shape = full + self.shape[3:]
         self.n_channels = self.shape[3] if self.tensor.ndim == 4 else 1
         self._f32 = None
@@ -147,10 +159,11 @@ class DeviceVolume:
         return up is None or up.queued_for_boxes(self._local_boxes(boxes))
 
     def _local_boxes(self, boxes):
-        """``(z_lo, z_hi, y_lo, y_hi)`` extents in the whole volume -> in the planes this object holds."""
-        if not self.z_off:
+        """``(z_lo, z_hi, y_lo, y_hi)`` extents in the whole volume -> in the planes and rows this object holds."""
+        dz, dy = self.z_off, self.y_off
+        if not dz and not dy:
             return boxes
-        return [(b[0] - self.z_off, b[1] - self.z_off, b[2], b[3]) for b in boxes]
+        return [(b[0] - dz, b[1] - dz, b[2] - dy, b[3] - dy) for b in boxes]
 
     def wait_all(self) -> None:
         """Host-side wait for the whole upload (readers of the voxels outside the batched detection); from here on the
@@ -220,7 +233,8 @@ class DeviceVolume:
             code = _NP_TO_MMX[self.np_dtype]
         sz, sy, sx = self._strides(t)
         ptr = int(t.data_ptr()) + (int(channel) if self.multichannel else 0) * t.element_size()
-        ptr -= self.z_off * int(sz) * t.element_size()        # (plane z of the whole volume is plane z - z_off here)
+        # (plane z, row y of the whole volume are plane z - z_off, row y - y_off here)
+        ptr -= (self.z_off * int(sz) + self.y_off * int(sy)) * t.element_size()
         return nat.Volume(ptr, code, 0, int(sz), int(sy), int(sx))
 
     def order_stats(self, channel: int, ranks, groups=None) -> Tuple[np.ndarray, np.ndarray]:
@@ -233,6 +247,9 @@ class DeviceVolume:
         Waits for the planes it touches when the image is still on its way up, and synchronises once at the end."""
         nz_held = int(self.tensor.shape[0])
         ny, nx = int(self.shape[1]), int(self.shape[2])
+        if self.y_off or int(self.tensor.shape[1]) != ny:
+            raise ValueError(f"order statistics are taken over whole planes: this volume holds rows [{self.y_off}, "
+                             f"{self.y_off + int(self.tensor.shape[1])}) of {ny}")
         if not 0 <= int(channel) < self.n_channels:
             raise ValueError(f"channel {channel} of an image with {self.n_channels}")
         if groups is None:
@@ -357,7 +374,9 @@ class _SlabUpload:
     band j of that layer has landed instead of the whole layer, and behind the LAST band only one row of blocks is left
     to detect instead of a whole layer (a quarter of the benchmark volume).  A pinned source is read by the DMA engine
     directly -- every copy is queued at once; a pageable or memory-mapped one goes through a small ring of pinned
-    staging buffers filled by a few host threads.
+    staging buffers filled by a few host threads.  The source may be a BOX of a larger host image
+    (``img[z_lo:z_hi, y_lo:y_hi]``: every plane packed, the planes a whole image plane apart -- :func:`_plane_pitch`):
+    the staging reads it where it lies, plane pitch in hand, and no packed host copy of the box is ever made.
 
     Lifetime: the device allocation is recorded on the copy stream (``record_stream``), so dropping the volume while
     copies are in flight cannot hand the block to another allocation before they have run; :meth:`cancel` drops the
@@ -528,8 +547,9 @@ class _SlabUpload:
             if prev is not None:
                 prev._wait_queued(self)
             torch.cuda.set_device(self.dev)
-            if NATIVE_STAGING and type(arr) in (np.ndarray, np.memmap) and arr.flags.c_contiguous:
-                return self._stage_native(arr)
+            pitch = _plane_pitch(arr)
+            if NATIVE_STAGING and type(arr) in (np.ndarray, np.memmap) and pitch is not None:
+                return self._stage_native(arr, pitch)
             inner = tuple(arr.shape[2:])
             itemsize = self.itemsize
             need = max((z1 - z0) * (y1 - y0) for z0, z1, y0, y1 in self.regions) * self.row_bytes
@@ -549,6 +569,7 @@ class _SlabUpload:
                     if done[which] is not None:
                         done[which].synchronize()          # the DMA that last used this buffer
                     host = buf.numpy()
+                    # (`arr[z, y0:y1]` carries the source's own plane pitch: a box of a larger image is read in place)
                     cuts = np.linspace(0, z1 - z0, min(n_thr, z1 - z0) + 1).astype(int)
                     list(pool.map(lambda ab: np.copyto(host[ab[0]:ab[1]], arr[z0 + ab[0]:z0 + ab[1], y0:y1]),
                                   zip(cuts[:-1], cuts[1:])))
@@ -568,10 +589,12 @@ class _SlabUpload:
             except BaseException:                  # (interpreter shutdown / a lost device: the buffers are dropped)
                 pass
 
-    def _stage_native(self, arr) -> None:
-        """The whole staging loop in ONE native call (``mmx_host_stage_upload``): nothing in it needs the interpreter lock,
-        which a busy detection holds most of the time -- the Python loop above waited for it between every two regions
-        (a two-channel tile from a memory map: 413 against 289 ms from pinned memory)."""
+    def _stage_native(self, arr, src_pitch: int) -> None:
+        """The whole staging loop in ONE native call (``mmx_host_stage_upload_pitched``): nothing in it needs the
+        interpreter lock, which a busy detection holds most of the time -- the Python loop above waited for it between
+        every two regions (a two-channel tile from a memory map: 413 against 289 ms from pinned memory).  ``src_pitch``:
+        bytes from one plane of ``arr`` to the next (``ny * row_bytes`` for a whole image, the larger image's plane for a
+        box of it)."""
         from .buffers import _NativeEvent
         need = max((z1 - z0) * (y1 - y0) for z0, z1, y0, y1 in self.regions) * self.row_bytes
         depth = max(2, min(int(_STAGE_DEPTH), len(self.regions)))
@@ -590,13 +613,13 @@ class _SlabUpload:
                 import sys, time
                 print(f"_SlabUpload: {(time.perf_counter() - self._t0) * 1e3:.2f} ms from the constructor to the staging call",
                       file=sys.stderr)
-            rc = nat.lib().mmx_host_stage_upload(
-                arr.ctypes.data, self.out.data_ptr(), regions.ctypes.data, len(regions), self.nz, self.ny, self.row_bytes,
-                (ctypes.c_void_p * depth)(*[b.data_ptr() for b in stage]), need, depth,
+            rc = nat.lib().mmx_host_stage_upload_pitched(
+                arr.ctypes.data, int(src_pitch), self.out.data_ptr(), regions.ctypes.data, len(regions), self.nz, self.ny,
+                self.row_bytes, (ctypes.c_void_p * depth)(*[b.data_ptr() for b in stage]), need, depth,
                 (ctypes.c_void_p * len(events))(*[e.handle for e in events]), self.stream.cuda_stream,
                 self.dev.index if self.dev.index is not None else torch.cuda.current_device(),
                 nq.ctypes.data, self._cancel.ctypes.data, _stage_threads())
-            nat.check(rc, "mmx_host_stage_upload")
+            nat.check(rc, "mmx_host_stage_upload_pitched")
         finally:
             try:
                 for ev in self.events[-depth:]:
@@ -650,6 +673,22 @@ class _SlabUpload:
                     raise nat.MmxError("upload of the image was cancelled (DeviceVolume.close) before these planes went up")
                 # (the native staging loop publishes its progress in a counter, not through this condition: polled)
                 self.cv.wait(0.5 if (self._nq is None and self.thread is None) else 0.0003)
+
+
+def _plane_pitch(arr) -> Optional[int]:
+    """Bytes from one plane of a host ``(z, y, x[, c])`` array to the next when every plane is packed (rows, voxels and
+    channels contiguous) and the planes do not overlap -- a whole C-ordered image, or a box ``img[z_lo:z_hi, y_lo:y_hi]``
+    of one; ``None`` for any other layout (the Python staging loop reads those element by element through NumPy)."""
+    if arr.ndim < 2:
+        return None
+    want = arr.itemsize
+    for n, st in zip(arr.shape[:0:-1], arr.strides[:0:-1]):
+        if n > 1 and st != want:
+            return None
+        want *= n
+    if arr.shape[0] <= 1:
+        return int(want)
+    return int(arr.strides[0]) if arr.strides[0] >= want else None
 
 
 def _advise_sequential(arr) -> None:
