@@ -80,7 +80,6 @@ class Image5d:
         must stay as it is until the detection has returned or :meth:`release` has been called (the upload reads it in
         the background).  ``own_planes``: with a process group, only the planes the blocks of THIS rank's share touch
         (the block split of a whole-image detection; not for a tile a rank detects alone)."""
-        from . import blob_log as bl
         from . import dist
         if self.device_volume is None and self.img is not None:
             if _image_bytes(self.img[0]) > _resident_limit():
@@ -92,19 +91,13 @@ class Image5d:
                 cells = _upload_cells(blocks.sub_roi_slices, shape3)
             except Exception:
                 pass
+            z_lo, z_hi = 0, shape3[0]
             if own_planes and blocks is not None and dist.world_size() > 1:
-                grid = blocks.sub_roi_slices.shape
-                coords = grid_coords(grid)
-                mine = dist.my_share(len(coords))
+                mine = dist.my_share(blocks.sub_roi_slices.size)
                 if not mine:
                     return self
-                ext = [blocks.sub_roi_slices[coords[i]][0].indices(shape3[0])[:2] for i in mine]
-                z_lo, z_hi = min(e[0] for e in ext), max(e[1] for e in ext)
-                cells = ([z - z_lo for z in cells[0] if z_lo < z < z_hi] + [z_hi - z_lo], cells[1])
-                self.device_volume = bl.DeviceVolume(self.img[0][z_lo:z_hi], streamed=True, cells=cells, z_off=z_lo,
-                                                     full_shape=shape3)
-            else:
-                self.device_volume = bl.DeviceVolume(self.img[0], streamed=True, cells=cells)
+                z_lo, z_hi = _share_box(*StackDetector._block_extents(blocks.sub_roi_slices, shape3, mine))[:2]
+            self.device_volume = _chunk_volume(self.img[0], _Chunk(0, 0, z_lo, z_hi, 0, shape3[1]), cells, shape3)
         return self
 
     def release(self):
@@ -159,38 +152,68 @@ def _z_chunks(coords, mine, origins, shapes, plane_bytes: int, limit: int):
     return chunks
 
 
+class _Chunk(NamedTuple):
+    """Blocks ``[k_lo, k_hi)`` of a rank's share and the box of the host image that goes to the device for them: planes
+    ``[z_lo, z_hi)``, rows ``[y_lo, y_hi)``, x and the channels whole."""
+    k_lo: int
+    k_hi: int
+    z_lo: int
+    z_hi: int
+    y_lo: int
+    y_hi: int
+
+
 def _zy_chunks(coords, mine, origins, shapes, plane_bytes: int, row_bytes: int, limit: int):
     """``_z_chunks``, and a chunk that is a single layer and STILL takes more than ``limit / 2`` bytes cut along y into
     runs of whole block rows (the blocks of ``mine`` with the same (z, y) grid coordinate: contiguous, ``mine`` being
     z-major): each run holds the rows its blocks touch, runs are merged while the box stays within ``limit / 2``, and a
     single block row that does not fit stands alone, as a layer does in ``_z_chunks``.  Rows in the overlap of two
-    neighbouring block rows are part of both runs.  ``[(k_lo, k_hi, z_lo, z_hi, y_lo, y_hi)]``; chunks that are not cut
-    hold all ``plane_bytes // row_bytes`` rows."""
+    neighbouring block rows are part of both runs.  A list of :class:`_Chunk`; chunks that are not cut hold all
+    ``plane_bytes // row_bytes`` rows."""
     n_rows = int(plane_bytes) // max(1, int(row_bytes))
     chunks = []
     for k_lo, k_hi, z_lo, z_hi in _z_chunks(coords, mine, origins, shapes, plane_bytes, limit):
         one_layer = coords[mine[k_lo]][0] == coords[mine[k_hi - 1]][0]
         if not one_layer or (z_hi - z_lo) * plane_bytes <= limit // 2:
-            chunks.append((k_lo, k_hi, z_lo, z_hi, 0, n_rows))
+            chunks.append(_Chunk(k_lo, k_hi, z_lo, z_hi, 0, n_rows))
             continue
-        first = len(chunks)
-        row = None                                    # grid y of the block row being collected
+        rows = []                                   # the layer's block rows: blocks of one grid y, the rows they touch
         for k in range(k_lo, k_hi):
             y0, y1 = int(origins[k][1]), int(origins[k][1]) + int(shapes[k][1])
-            c = chunks[-1] if len(chunks) > first else None
-            if c is not None and coords[mine[k]][1] == row:
-                chunks[-1] = (c[0], k + 1, z_lo, z_hi, min(c[4], y0), max(c[5], y1))
+            if rows and coords[mine[k]][1] == coords[mine[k - 1]][1]:
+                r = rows[-1]
+                rows[-1] = _Chunk(r.k_lo, k + 1, z_lo, z_hi, min(r.y_lo, y0), max(r.y_hi, y1))
             else:
-                chunks.append((k, k + 1, z_lo, z_hi, y0, y1))
-                row = coords[mine[k]][1]
-        rows, chunks[first:] = chunks[first:], []
-        for r in rows:
-            c = chunks[-1] if len(chunks) > first else None
-            if c is not None and (max(c[5], r[5]) - min(c[4], r[4])) * (z_hi - z_lo) * row_bytes <= limit // 2:
-                chunks[-1] = (c[0], r[1], z_lo, z_hi, min(c[4], r[4]), max(c[5], r[5]))
+                rows.append(_Chunk(k, k + 1, z_lo, z_hi, y0, y1))
+        runs = rows[:1]                               # merged greedily while the box stays within half the limit
+        for r in rows[1:]:
+            c = runs[-1]
+            y_lo, y_hi = min(c.y_lo, r.y_lo), max(c.y_hi, r.y_hi)
+            if (y_hi - y_lo) * (z_hi - z_lo) * row_bytes <= limit // 2:
+                runs[-1] = _Chunk(c.k_lo, r.k_hi, z_lo, z_hi, y_lo, y_hi)
             else:
-                chunks.append(r)
+                runs.append(r)
+        chunks.extend(runs)
     return chunks
+
+
+def _share_box(origins, shapes):
+    """``(z_lo, z_hi, y_lo, y_hi)``: the planes and rows the blocks of a share touch (``_block_extents``' lists)."""
+    return (min(o[0] for o in origins), max(o[0] + s[0] for o, s in zip(origins, shapes)),
+            min(o[1] for o in origins), max(o[1] + s[1] for o, s in zip(origins, shapes)))
+
+
+def _host_chunks(img, coords, mine, origins, shapes, shape3):
+    """The boxes in which a HOST image goes to the device for the blocks of this rank's share (``mine``, not empty), in
+    order: a share too large to be resident in whole layers of blocks -- block rows of a layer that does not fit by
+    itself, which a share of ONE layer may well be (``_zy_chunks``); otherwise ONE chunk of the planes the share touches
+    -- a rank's share of the image goes up over this rank's own link; all planes without torch.distributed: the whole
+    image -- with every row of them."""
+    z_lo, z_hi = _share_box(origins, shapes)[:2]
+    plane = _image_bytes(img) // max(1, int(shape3[0]))
+    if (z_hi - z_lo) * plane > _resident_limit() and len({coords[i][:2] for i in mine}) > 1:
+        return _zy_chunks(coords, mine, origins, shapes, plane, plane // max(1, int(shape3[1])), _resident_limit())
+    return [_Chunk(0, len(mine), z_lo, z_hi, 0, int(shape3[1]))]
 
 
 def _upload_cells(sub_roi_slices, shape3):
@@ -202,12 +225,148 @@ def _upload_cells(sub_roi_slices, shape3):
     return z_ends, y_ends
 
 
+def _chunk_cells(cells_all, chunk):
+    """The upload cells of the whole image (``_upload_cells``; ``None``: none) as those of a chunk's box: the ends that
+    lie strictly inside it, relative to it, then the box's own extent."""
+    if cells_all is None:
+        return None
+    _, _, z_lo, z_hi, y_lo, y_hi = chunk
+    return ([z - z_lo for z in cells_all[0] if z_lo < z < z_hi] + [z_hi - z_lo],
+            [y - y_lo for y in cells_all[1] if y_lo < y < y_hi] + [y_hi - y_lo])
+
+
+def _chunk_volume(img, chunk, cells_all, shape3):
+    """A chunk's box of the host image ``img`` -- a view of it, read where it lies: no host copy -- on its way to the
+    device as a volume that answers for the whole image (``DeviceVolume(z_off=..., y_off=...)``; the whole image is the
+    box without offsets), block row by block row (``cells_all``).  The caller leaves ``img`` as it is until the volume
+    has been closed, and closes it."""
+    from . import blob_log as bl
+    _, _, z_lo, z_hi, y_lo, y_hi = chunk
+    box = img[z_lo:z_hi] if (y_lo, y_hi) == (0, int(shape3[1])) else img[z_lo:z_hi, y_lo:y_hi]
+    return bl.DeviceVolume(box, streamed=True, cells=_chunk_cells(cells_all, chunk), z_off=z_lo, y_off=y_lo,
+                           full_shape=shape3)
+
+
 class _SegRois(np.ndarray):
     """Object array of per-block tables that remembers the arena its tables live in, the regions already pruned
     while the detection ran, and whether it holds this rank's blocks only."""
     arena = None
     pruner = None
     local_only = False
+
+
+class _TableLanding:
+    """Where the block tables of one ``detect_blobs_sub_rois`` call land, and who prunes them: the arena of this rank's
+    share (none where the tables are gathered on rank 0), the sink the native host path writes them through, the pruner
+    of finished regions that the first batch to land makes and, for a small stack detected in one pass (``one_pass``: a
+    resident volume, or a host image that goes up as exactly one chunk), the finisher that does all of it in one native
+    call.  :meth:`detect` runs blocks of the share with their tables landing here; :meth:`pruner` then says who holds
+    what was pruned meanwhile."""
+
+    def __init__(self, hint, coords, mine, shapes, shape3, sub_roi_slices, sub_rois_offsets, *, channel,
+                 denoise_max_shape, exclude_border, coloc, n_extra, one_pass, stats):
+        from . import blob_log as bl
+        from . import dist
+        grid = sub_roi_slices.shape
+        self.coords, self.mine, self.shapes, self.offsets, self.stats = coords, mine, shapes, sub_rois_offsets, stats
+        self.last_coord, self.exclude_border = np.subtract(grid, 1), exclude_border
+        self.channel, self.denoise_max_shape, self.coloc = channel, denoise_max_shape, coloc
+        ov, tl, pad, prune_channels = hint or (None, None, None, None)
+        plan_, regular = (None, False) if hint is None else StackPruner._geometry(
+            shape3, ov, tl, tl if pad is None else pad, sub_roi_slices, sub_rois_offsets)
+        # several ranks: with the pruning planned (plan_pruning) and a regular block geometry every rank keeps its
+        # own tables and the pruning itself is distributed; otherwise the tables are gathered on rank 0
+        self.local_only = dist.world_size() > 1 and regular and DIST_PRUNE
+        self.arena = arena = None
+        if dist.world_size() == 1 or self.local_only:
+            self.arena = arena = _TableArena(11 + n_extra, len(mine))
+        if self.local_only:
+            arena.headroom = 0.35       # (seam rows of the neighbouring ranks: ~10 % of a rank's rows per neighbour)
+        # (PRUNE_AHEAD "1" / "0" / "": always / never / for stacks of 64 blocks and more.  On the benchmark volume it
+        #  moves ~4 ms of pruning under the GPU's last batches and adds most of that in the merge: 0.8-1.0 ms per volume
+        #  in four alternating pairs of bench.py runs; it costs small stacks 0.6 ms: DESIGN.md.  With per-block
+        #  preprocessing on: tail after the last kernel 11.4 -> 6.3 ms, tools/steptrace.py --denoise 25 -- once the
+        #  host no longer waited for the tile tables' staging buffer, round 5; 218.9 against 216.6 ms before that)
+        make_pruner = None
+        if regular and dist.world_size() == 1 and mine and (
+                PRUNE_AHEAD == "1" or (PRUNE_AHEAD != "0" and len(mine) >= 64)):
+            def make_pruner():
+                return _RegionPruner(arena, StackPruner._axis_plan(shape3, ov, tl, tl if pad is None else pad,
+                                                                   sub_roi_slices, sub_rois_offsets),
+                                     prune_channels, sub_roi_slices, shape3, mine,
+                                     min_regions=-(-len(mine) // max(1, int(grid[2]))) * int(
+                                         REGION_SPLIT or max(1, len(prune_channels))))
+        self.sink = self.finisher = None
+        if mine and arena is not None:
+            # finished tables go straight from the native host path into the arena where the detection can hand
+            # over peak arrays (one channel; several channels with co-localisation: the tables then land during the
+            # LAST channel's pass, flags included); tables it has to build itself come through finish() -- both ways
+            # the regions of the stack are pruned as their blocks land.  (Round 4 measured pruning ahead at +35-55 ms
+            # per C5 volume with tables landing block by block -- the regions were pruned by Python then; with the
+            # native region step and the final columns written by the merge it is 246.2 -> 240.5 ms, pruning + final
+            # columns 15.9 -> 5.8 ms: profiles/r06_experiments.txt)
+            flat_offsets = np.asarray(sub_rois_offsets, dtype=np.float64).reshape(-1, 3)    # (C order: coords' order)
+            self.sink = _ArenaSink(arena, np.asarray(coords, dtype=np.int32)[mine[0]:mine[-1] + 1],
+                                   flat_offsets[mine[0]:mine[-1] + 1],
+                                   shapes, self.exclude_of if exclude_border is not None else None)
+            # (the pruner's set-up -- 0.7 ms for 256 blocks -- waits until the first batch has landed: by then every
+            #  batch is queued and the GPU busy)
+            self.sink.pruner_factory = make_pruner
+            # a small stack of one channel (all blocks in one batch: the GUI's ROI, a grid-search step): the whole
+            # host chain behind its kernels as one native call.  (one_pass: all blocks in ONE detect() call.  A single
+            # chunk of a host image counts because the finisher is for one process only -- world_size() == 1 below --
+            # and there a single chunk holds every plane and row the blocks touch, as a resident volume does)
+            if (plan_ is not None and dist.world_size() == 1 and make_pruner is None and n_extra == 0 and STACK_FINISHER
+                    and one_pass and len(list(channel or [0])) == 1 and len(mine) <= bl.GRAPH_BLOCKS
+                    and denoise_max_shape is None and list(prune_channels) == list(channel or [0])):
+                self.finisher = _StackFinisher(self.sink, plan_, prune_channels)
+
+    def exclude_of(self, k):
+        return StackDetector._exclude_matrix(self.coords[self.mine[k]], self.last_coord, self.exclude_border)
+
+    def finish(self, k, tbl):
+        # shift to ROI coordinates as soon as the block's batch is done (border exclusion and
+        # co-localisation have happened on the block-relative table, in the reference's order)
+        coord = self.coords[self.mine[k]]
+        tbl = StackDetector._finish_block(tbl, self.shapes[k], None, self.offsets[coord])
+        if self.arena is not None:
+            ahead_of_time = None if self.sink is None else self.sink.ensure_pruner()
+            if tbl is not None and len(tbl):
+                self.arena.add(coord, tbl)
+            self.arena.landed()
+            if ahead_of_time is not None:
+                ahead_of_time.advance()
+        return tbl
+
+    def detect(self, dvol, origins, k_lo, k_hi):
+        """Blocks ``[k_lo, k_hi)`` of the share (``origins``: of all its blocks), which ``dvol`` holds: their tables, in
+        order.  A part of the share lands through a sink of its own into the same arena (``_ArenaSinkPart``); all blocks
+        at once through the sink itself, as the very lists of extents that the device pipeline recognises, and only they
+        are ever offered the finisher."""
+        part = (k_lo, k_hi) != (0, len(self.mine))
+        shapes = self.shapes
+        if part:
+            origins, shapes = origins[k_lo:k_hi], shapes[k_lo:k_hi]
+        return detector.detect_blobs_blocks_device(
+            dvol, self.channel, origins, shapes, self.stats, lambda j, tbl: self.finish(k_lo + j, tbl),
+            denoise_max_shape=self.denoise_max_shape, exclude=lambda j: self.exclude_of(k_lo + j), coloc=self.coloc,
+            sink=_ArenaSinkPart(self.sink, k_lo, k_hi) if part and self.sink is not None else self.sink,
+            stack_finisher=self.finisher)
+
+    def cancel(self) -> None:
+        """The detection failed: the regions pruned ahead have nobody to collect them."""
+        if self.sink is not None and self.sink.pruner is not None:
+            try:
+                self.sink.pruner.cancel()
+            except Exception:           # (the detection's own exception is the one to report)
+                pass
+
+    def pruner(self):
+        """After the detection: who has pruned regions of the stack already, if anybody -- the finisher (its table is
+        what prune_blobs_mp hands out, asked the planned way), else the regions' pruner."""
+        if self.finisher is not None and self.finisher.result is not None:
+            return self.finisher
+        return None if self.sink is None else self.sink.pruner
 
 
 class StackDetector:
@@ -291,7 +450,9 @@ class StackDetector:
         """``(origins, shapes)`` of the blocks ``mine`` (indices in C order of the grid): every slice resolved against the
         ROI with Python's rules.  Remembered per slice array and share (the entry keeps the array alive): a stack
         detected step after step pays the 256-block loop once, and the device pipeline recognises the SAME lists and
-        reuses the block tables it uploaded for them."""
+        reuses the block tables it uploaded for them.  ``Image5d.prefetch(own_planes=True)`` asks too, with the slice
+        array of a ``setup_blocks`` of its own: one more of the 8 entries per tile prefetched by a rank, and a full
+        cache is cleared whole -- the stack being detected then pays its loop once more, with the same numbers."""
         key = (id(sub_roi_slices), tuple(int(v) for v in shape3), len(mine), mine[0] if mine else -1,
                mine[-1] if mine else -1)
         hit = cls._extent_cache.get(key)
@@ -329,200 +490,76 @@ class StackDetector:
         from . import dist
         cls.img5d, cls.img, cls.channel, cls.coloc = img5d, img, channel, coloc
         cls.denoise_max_shape, cls.exclude_border = denoise_max_shape, exclude_border
+        hint, cls.prune_hint = cls.prune_hint, None
+        # this rank's share of the blocks, and how the image reaches them
         grid = sub_roi_slices.shape
-        last_coord = np.subtract(grid, 1)
-        cls.last_coord = last_coord
+        cls.last_coord = np.subtract(grid, 1)
         coords = cls._grid_coords(grid)
         mine = dist.my_share(len(coords))            # all of them without torch.distributed
         shape3 = img.shape[:3]
         origins, shapes = cls._block_extents(sub_roi_slices, shape3, mine)
-        stats = bl.BatchStats()
-        tables = []
+        if not isinstance(img, bl.DeviceVolume) and getattr(getattr(img, "device", None), "type", "cpu") != "cpu":
+            img = bl.DeviceVolume(img)               # (a tensor already on a device)
+        chunks = None
+        if mine and isinstance(img, bl.DeviceVolume):
+            held = (int(img.z_off), int(img.z_off) + int(img.tensor.shape[0]),
+                    int(img.y_off), int(img.y_off) + int(img.tensor.shape[1]))
+            if held != (0, int(shape3[0]), 0, int(shape3[1])):
+                # a volume that holds some planes (Image5d.prefetch(own_planes=True), a rank's slab) or some rows
+                # only: they must be the ones this rank's blocks touch
+                z_lo, z_hi, y_lo, y_hi = _share_box(origins, shapes)
+                if z_lo < held[0] or z_hi > held[1] or y_lo < held[2] or y_hi > held[3]:
+                    raise nat.MmxError(f"the device volume holds planes [{held[0]}, {held[1]}) and rows [{held[2]}, "
+                                       f"{held[3]}) but this rank's blocks touch planes [{z_lo}, {z_hi}) and rows "
+                                       f"[{y_lo}, {y_hi})")
+        elif mine:
+            # a host image handed over for the length of this call: it goes up beside the detection of the blocks that
+            # have landed, and whatever of it this rank's blocks never touched is cancelled before returning
+            chunks = _host_chunks(img, coords, mine, origins, shapes, shape3)
+        # where the tables land
         n_extra = (img.shape[3] if len(img.shape) > 3 else 0) if coloc else 0
-        hint, cls.prune_hint = cls.prune_hint, None
-        regular = hint is not None and StackPruner._geometry(
-            shape3, hint[0], hint[1], hint[1] if hint[2] is None else hint[2], sub_roi_slices, sub_rois_offsets)[1]
-        # several ranks: with the pruning planned (plan_pruning) and a regular block geometry every rank keeps its
-        # own tables and the pruning itself is distributed; otherwise the tables are gathered on rank 0
-        local_only = dist.world_size() > 1 and regular and DIST_PRUNE
-        arena = _TableArena(11 + n_extra, len(mine)) if (dist.world_size() == 1 or local_only) else None
-        if local_only:
-            arena.headroom = 0.35       # (seam rows of the neighbouring ranks: ~10 % of a rank's rows per neighbour)
-        pos = {i: k for k, i in enumerate(mine)}
-
-        def exclude_of(k):
-            return cls._exclude_matrix(coords[mine[k]], last_coord, exclude_border)
-
-        pruner = None
-        # (PRUNE_AHEAD "1" / "0" / "": always / never / for stacks of 64 blocks and more.  On the benchmark volume it
-        #  moves ~4 ms of pruning under the GPU's last batches and adds most of that in the merge: 0.8-1.0 ms per volume
-        #  in four alternating pairs of bench.py runs; it costs small stacks 0.6 ms: DESIGN.md.  With per-block
-        #  preprocessing on: tail after the last kernel 11.4 -> 6.3 ms, tools/steptrace.py --denoise 25 -- once the
-        #  host no longer waited for the tile tables' staging buffer, round 5; 218.9 against 216.6 ms before that)
-        ahead = PRUNE_AHEAD
-        make_pruner = None
-        if regular and dist.world_size() == 1 and mine and (
-                ahead == "1" or (ahead != "0" and len(mine) >= 64)):
-            ov, tl, pad, prune_channels = hint
-
-            def make_pruner():
-                return _RegionPruner(arena, StackPruner._axis_plan(shape3, ov, tl, tl if pad is None else pad,
-                                                                   sub_roi_slices, sub_rois_offsets),
-                                     prune_channels, sub_roi_slices, shape3, mine,
-                                     min_regions=-(-len(mine) // max(1, int(grid[2]))) * int(
-                                         REGION_SPLIT or max(1, len(prune_channels))))
-
-        sink = None
-        finisher = None
-
-        def finish(k, tbl):
-            # shift to ROI coordinates as soon as the block's batch is done (border exclusion and
-            # co-localisation have happened on the block-relative table, in the reference's order)
-            coord = coords[mine[k]]
-            tbl = cls._finish_block(tbl, shapes[k], None, sub_rois_offsets[coord])
-            if arena is not None:
-                ahead_of_time = pruner if sink is None else sink.ensure_pruner()
-                if tbl is not None and len(tbl):
-                    arena.add(coord, tbl)
-                arena.landed()
-                if ahead_of_time is not None:
-                    ahead_of_time.advance()
-            return tbl
-
-        own_dvol = None
+        stats = bl.BatchStats()
+        landing = _TableLanding(hint, coords, mine, shapes, shape3, sub_roi_slices, sub_rois_offsets, channel=channel,
+                                denoise_max_shape=denoise_max_shape, exclude_border=exclude_border, coloc=coloc,
+                                n_extra=n_extra, one_pass=chunks is None or len(chunks) == 1, stats=stats)
+        # the detection: of a resident volume, or chunk by chunk of a host image
+        tables = []
         if mine:
-            chunks = None
-            if isinstance(img, bl.DeviceVolume):
-                dvol = img
-                held = (int(dvol.z_off), int(dvol.z_off) + int(dvol.tensor.shape[0]),
-                        int(dvol.y_off), int(dvol.y_off) + int(dvol.tensor.shape[1]))
-                if held != (0, int(shape3[0]), 0, int(shape3[1])):
-                    # a volume that holds some planes (Image5d.prefetch(own_planes=True), a rank's slab) or some rows
-                    # only: they must be the ones this rank's blocks touch
-                    z_lo = min(int(o[0]) for o in origins)
-                    z_hi = max(int(o[0]) + int(s_[0]) for o, s_ in zip(origins, shapes))
-                    y_lo = min(int(o[1]) for o in origins)
-                    y_hi = max(int(o[1]) + int(s_[1]) for o, s_ in zip(origins, shapes))
-                    if z_lo < held[0] or z_hi > held[1] or y_lo < held[2] or y_hi > held[3]:
-                        raise nat.MmxError(f"the device volume holds planes [{held[0]}, {held[1]}) and rows [{held[2]}, "
-                                           f"{held[3]}) but this rank's blocks touch planes [{z_lo}, {z_hi}) and rows "
-                                           f"[{y_lo}, {y_hi})")
-            else:
-                # the planes this rank's blocks touch (all of them without torch.distributed)
-                z_lo = min(int(o[0]) for o in origins)
-                z_hi = max(int(o[0]) + int(s_[0]) for o, s_ in zip(origins, shapes))
-                plane = _image_bytes(img) // max(1, int(img.shape[0]))
-                dvol = None
-                on_host = getattr(getattr(img, "device", None), "type", "cpu") == "cpu"     # (not a tensor on a device)
-                if not on_host:
-                    pass
-                elif (z_hi - z_lo) * plane > _resident_limit() and len({coords[i][:2] for i in mine}) > 1:
-                    # too large to be resident: whole layers of blocks at a time -- block rows of a layer that does not
-                    # fit by itself, which a share of ONE layer may well be -- each from a device volume of its own
-                    chunks = _zy_chunks(coords, mine, origins, shapes, plane, plane // max(1, int(shape3[1])),
-                                        _resident_limit())
-                elif z_lo > 0 or z_hi < int(shape3[0]):
-                    # a rank's share of a host image: only its planes go up (over this rank's own link), every row of them
-                    chunks = [(0, len(mine), z_lo, z_hi, 0, int(shape3[1]))]
-            if chunks is None and dvol is None:
-                # a host image handed over for the length of this call: it goes up beside the detection of the blocks
-                # that have landed, and whatever of it this rank's blocks never touched is cancelled before returning
-                dvol = own_dvol = bl.DeviceVolume(img, streamed=True, cells=_upload_cells(sub_roi_slices, shape3))
-            if arena is not None:
-                # finished tables go straight from the native host path into the arena where the detection can hand
-                # over peak arrays (one channel; several channels with co-localisation: the tables then land during the
-                # LAST channel's pass, flags included); tables it has to build itself come through finish() -- both ways
-                # the regions of the stack are pruned as their blocks land.  (Round 4 measured pruning ahead at +35-55 ms
-                # per C5 volume with tables landing block by block -- the regions were pruned by Python then; with the
-                # native region step and the final columns written by the merge it is 246.2 -> 240.5 ms, pruning + final
-                # columns 15.9 -> 5.8 ms: profiles/r06_experiments.txt)
-                flat_offsets = np.asarray(sub_rois_offsets, dtype=np.float64).reshape(-1, 3)    # (C order: coords' order)
-                sink = _ArenaSink(arena, np.asarray(coords, dtype=np.int32)[mine[0]:mine[-1] + 1],
-                                  flat_offsets[mine[0]:mine[-1] + 1],
-                                  shapes, exclude_of if exclude_border is not None else None)
-                # (the pruner's set-up -- 0.7 ms for 256 blocks -- waits until the first batch has landed: by then every
-                #  batch is queued and the GPU busy)
-                sink.pruner_factory = make_pruner
-                # a small stack of one channel (all blocks in one batch: the GUI's ROI, a grid-search step): the whole
-                # host chain behind its kernels as one native call
-                if (regular and dist.world_size() == 1 and make_pruner is None and n_extra == 0 and STACK_FINISHER
-                        and chunks is None and len(list(channel or [0])) == 1 and len(mine) <= bl.GRAPH_BLOCKS
-                        and denoise_max_shape is None and list(hint[3]) == list(channel or [0])):
-                    ov, tl, pad, _ = hint
-                    plan_ = StackPruner._geometry(shape3, ov, tl, tl if pad is None else pad, sub_roi_slices,
-                                                  sub_rois_offsets)[0]
-                    if plan_ is not None:
-                        finisher = _StackFinisher(sink, plan_, hint[3])
             try:
                 if chunks is None:
-                    tables = detector.detect_blobs_blocks_device(dvol, channel, origins, shapes, stats, finish,
-                                                                 denoise_max_shape=denoise_max_shape,
-                                                                 exclude=exclude_of, coloc=coloc, sink=sink,
-                                                                 stack_finisher=finisher)
+                    tables = landing.detect(img, origins, 0, len(mine))
                 else:
-                    tables = cls._detect_chunks(img, chunks, sub_roi_slices, shape3, channel, origins, shapes, stats,
-                                                finish, denoise_max_shape, exclude_of, coloc, sink)
+                    tables = cls._detect_chunks(img, chunks, _upload_cells(sub_roi_slices, shape3), shape3, origins,
+                                                landing)
             except BaseException:
-                # the detection failed: the regions pruned ahead have nobody to collect them
-                for p_ in (pruner, None if sink is None else sink.pruner):
-                    if p_ is not None:
-                        try:
-                            p_.cancel()
-                        except Exception:       # (the detection's own exception is the one to report)
-                            pass
+                landing.cancel()
                 raise
-            finally:
-                if own_dvol is not None:
-                    own_dvol.close()
-            if sink is not None and sink.pruner is not None:
-                pruner = sink.pruner
-            if finisher is not None and finisher.result is not None:
-                pruner = finisher           # (its table is what prune_blobs_mp hands out, asked the planned way)
         cls.last_stats = stats
-        local = [(i, tbl) for i, tbl in zip(mine, tables)]
-        seg_rois = cls.assemble_seg_rois(local, grid, n_extra, arena, local_only=local_only)
-        if pruner is not None and seg_rois.arena is arena:
+        seg_rois = cls.assemble_seg_rois(list(zip(mine, tables)), grid, n_extra, landing.arena,
+                                         local_only=landing.local_only)
+        pruner = landing.pruner()
+        if pruner is not None and seg_rois.arena is landing.arena:
             seg_rois.pruner = pruner
         return seg_rois
 
-    @classmethod
-    def _detect_chunks(cls, img, chunks, sub_roi_slices, shape3, channel, origins, shapes, stats, finish,
-                       denoise_max_shape, exclude_of, coloc, sink):
-        """The blocks of this rank's share chunk by chunk (``_zy_chunks``): planes ``[z_lo, z_hi)`` and rows
-        ``[y_lo, y_hi)`` of the host image -- a view of it, read where it lies -- as a device volume that answers for the
-        whole image (``DeviceVolume(z_off=..., y_off=...)``), the next chunk's upload started before this one is
-        detected, the tables through per-chunk sinks into the ONE arena (same pruner, same order of landing as the
-        resident path).  Returns the tables of all blocks, in order."""
-        from . import blob_log as bl
-        z_ends_all, y_ends_all = _upload_cells(sub_roi_slices, shape3)
-
-        def volume(c):
-            k_lo, k_hi, z_lo, z_hi, y_lo, y_hi = c
-            cells = ([z - z_lo for z in z_ends_all if z_lo < z < z_hi] + [z_hi - z_lo],
-                     [y - y_lo for y in y_ends_all if y_lo < y < y_hi] + [y_hi - y_lo])
-            box = img[z_lo:z_hi] if (y_lo, y_hi) == (0, int(shape3[1])) else img[z_lo:z_hi, y_lo:y_hi]
-            return bl.DeviceVolume(box, streamed=True, cells=cells, z_off=z_lo, y_off=y_lo, full_shape=shape3)
-
+    @staticmethod
+    def _detect_chunks(img, chunks, cells_all, shape3, origins, landing):
+        """The blocks of this rank's share chunk by chunk (``_host_chunks``): each chunk's box of the host image as a
+        device volume of its own (``_chunk_volume``), the next chunk's upload started before this one is detected, the
+        tables into the ONE arena (same pruner, same order of landing as the resident path).  The one owner of these
+        volumes: each is closed when its chunk is done or the detection has failed.  Returns the tables of all blocks,
+        in order."""
         tables = []
-        nxt = volume(chunks[0])
-        cur = None
+        open_ = [_chunk_volume(img, chunks[0], cells_all, shape3)]       # this chunk's volume, then the next one's
         try:
-            for ci, (k_lo, k_hi) in enumerate(c[:2] for c in chunks):
-                cur, nxt = nxt, None
-                if ci + 1 < len(chunks):
-                    nxt = volume(chunks[ci + 1])     # (its staging starts once this chunk has queued its last region)
-                part = None if sink is None else _ArenaSinkPart(sink, k_lo, k_hi)
-                tables.extend(detector.detect_blobs_blocks_device(
-                    cur, channel, origins[k_lo:k_hi], shapes[k_lo:k_hi], stats,
-                    lambda j, tbl, k0=k_lo: finish(k0 + j, tbl), denoise_max_shape=denoise_max_shape,
-                    exclude=None if exclude_of is None else (lambda j, k0=k_lo: exclude_of(k0 + j)),
-                    coloc=coloc, sink=part, stack_finisher=None))
-                cur.close()
-                cur = None
+            for ci, c in enumerate(chunks):
+                if ci + 1 < len(chunks):             # (its staging starts once this chunk has queued its last region)
+                    open_.append(_chunk_volume(img, chunks[ci + 1], cells_all, shape3))
+                tables.extend(landing.detect(open_[0], origins, c.k_lo, c.k_hi))
+                open_.pop(0).close()
         finally:
-            for v in (cur, nxt):
-                if v is not None:
-                    v.close()
+            for v in open_:
+                v.close()
         return tables
 
     @staticmethod

@@ -62,6 +62,50 @@ def test_streamed_upload_gives_the_resident_volumes_table(gpu, monkeypatch, tmp_
         config.setup_roi_profiles(None)
 
 
+def test_a_small_host_stack_in_one_chunk_still_runs_the_stack_finisher(gpu, monkeypatch, tmp_path):
+    """A small host image -- all its blocks one batch of at most ``GRAPH_BLOCKS`` -- handed over as a read-only memory map
+    goes up streamed and is STILL finished by the one native call (``_StackFinisher.run`` ran and made the table): a stack
+    that lost it would take the call-by-call path and give the same table, so the call is counted.  The table equals the
+    one of the same image resident on the device (``DeviceVolume``) row for row, and the oracle's.
+    ``synth.make_volume(23, (40, 72, 80), 40)``: seed 23, 40 blobs asked for."""
+    from magellanmapper_amd import blob_log as bl, config, stack_detect, stack_tables, synth, volume
+    from oracle import magmap_oracle as mmo
+    vol = synth.make_volume(23, (40, 72, 80), 40)
+    assert vol.dtype == np.uint16 and vol.ndim == 3
+    np.save(tmp_path / "small.npy", vol[None])
+    monkeypatch.setattr(volume, "_STREAM_MIN_BYTES", 0)
+    config.setup_roi_profiles(None)
+    config.roi_profile.update(dict(num_sigma=3, denoise_size=None, segment_size=40))
+    config.resolutions = np.array([[1.0, 1.0, 1.0]])
+    config.filename = "small"
+    ran = []
+    real = stack_tables._StackFinisher.run
+
+    def counted(self, *a, **k):
+        out = real(self, *a, **k)
+        ran.append((self, out))
+        return out
+    monkeypatch.setattr(stack_tables._StackFinisher, "run", counted)
+    try:
+        n_blocks = stack_detect.setup_blocks(config.roi_profile, vol.shape).sub_roi_slices.size
+        assert 1 < n_blocks <= bl.GRAPH_BLOCKS
+        img5d = stack_detect.Image5d(np.load(tmp_path / "small.npy", mmap_mode="r"))
+        assert not img5d.img.flags.writeable
+        _, _, got = stack_detect.detect_blobs_blocks("small", img5d, None, None, None, False, False, full_roi=True)
+        assert len(ran) == 1 and ran[0][1] is not None and ran[0][0].result is not None
+        del ran[:]
+        held = stack_detect.Image5d(vol[None])
+        held.device_volume = bl.DeviceVolume(vol)
+        _, _, want = stack_detect.detect_blobs_blocks("small", held, None, None, None, False, False, full_roi=True)
+        assert want.blobs is not None and got.blobs is not None and len(want.blobs) >= 20
+        np.testing.assert_array_equal(got.blobs, want.blobs)
+        ref, _ = mmo.detect_blobs_blocks(vol, None, [dict(config.roi_profile)], config.resolutions)
+        key = lambda t: t[np.lexsort(tuple(t[:, i] for i in range(t.shape[1] - 1, -1, -1)))]
+        np.testing.assert_array_equal(key(got.blobs), key(ref))
+    finally:
+        config.setup_roi_profiles(None)
+
+
 def test_pinned_source_is_copied_without_staging_and_partial_waits_work(gpu, monkeypatch):
     """A pinned tensor: every slab copy is queued at construction (no thread); `stream_wait(z)` orders a stream after the
     slabs below z only, `wait_all` after everything; the device copy equals the source."""
