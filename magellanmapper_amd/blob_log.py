@@ -10,8 +10,8 @@ row    reference step                              here
 A0     ``img_as_float`` (skimage dtype.py:310-328)  folded into the Z-pass weights
 A1     sigma ladder (skimage blob.py:473-497)       :func:`kernels1d.sigma_ladder`
 A2,A3  ``-gaussian_laplace * sigma**2`` per scale   ``mmx_log_batch_f32`` (HIP)
-A4     ``peak_local_max`` 3^4 NMS (peak.py)         ``mmx_peaks_batch`` (HIP) +
-                                                    ``mmx_rescore_f64`` (HIP, exact)
+A4     ``peak_local_max`` 3^4 NMS (peak.py)         the tail of ``mmx_detect_batch`` (HIP:
+                                                    NMS, probes, exact re-score)
                                                     + tie resolution below
 A5     ``_prune_blobs`` (blob.py:146-187)           ``mmx_overlap_pairs`` (HIP) +
                                                     the sequential rule below
@@ -62,9 +62,9 @@ if 0.0 < EPS_REL_Q16 < 4.0 * Q16_BOUND_ANY_SIGMA:
     # 16-bit intermediates off (0), not narrow it below what the bound needs
     raise ValueError(f"MMX_EPS_REL_Q16={EPS_REL_Q16:g} is narrower than 4 x the 16-bit intermediates' error bound "
                      f"({4.0 * Q16_BOUND_ANY_SIGMA:g}); use 0 to keep float32 intermediates")
-#: raw volumes on the native host path: one ``mmx_detect_batch`` call enqueues a whole batch (voxel copy, the passes of
-#: every scale, NMS, probes, exact re-score, copies); ``False``: the call-by-call form every other batch takes (the
-#: scales by ``mmx_log_scales_f32``, the tail call by call from here), which tests keep as a cross-check
+#: EVERY batch is enqueued by one ``mmx_detect_batch`` call (voxel copy, the passes of every scale, NMS, probes, exact
+#: re-score, copies).  This switch only says whether small raw batches on the native host path may be captured as a
+#: hipGraph and replayed (``GRAPH_BLOCKS``); ``False``: plain ``mmx_detect_batch`` calls, never a graph
 NATIVE_BATCH = True
 #: batches of at most this many blocks that come back with the very same arguments (a small volume detected step
 #: after step) are captured as a hipGraph and replayed with one launch (0: never)
@@ -227,6 +227,18 @@ RAMP = 16
 FORCED_BATCH_SIZES: list = []
 
 
+def _row_elems(nx):
+    """Elements of a workspace row that holds ``nx`` voxels: rows are ``MMX_ROW_ALIGN`` elements (128 bytes) aligned."""
+    return -(-nx // nat.MMX_ROW_ALIGN) * nat.MMX_ROW_ALIGN
+
+
+def _slot_elems(shapes):
+    """Workspace elements a block of ``(nz, ny, nx)`` voxels takes, its rows padded (:func:`_row_elems`).  One shape
+    gives one number, an ``(n, 3)`` list of shapes an array of ``n``."""
+    shp = np.asarray(shapes, dtype=np.int64)
+    return shp[..., 0] * shp[..., 1] * _row_elems(shp[..., 2])
+
+
 def plan_batches(shapes: Sequence[Tuple[int, int, int]], num_sigma: int,
                  budget_bytes: int, extra_bytes_per_voxel: int = 0) -> List[List[int]]:
     """Group block indices into batches whose workspace fits ``budget_bytes``.
@@ -241,11 +253,11 @@ def plan_batches(shapes: Sequence[Tuple[int, int, int]], num_sigma: int,
     if FORCED_BATCH_SIZES and sum(FORCED_BATCH_SIZES) == len(shapes):       # (experiments: bench.py --batches)
         cuts = np.concatenate(([0], np.cumsum(FORCED_BATCH_SIZES)))
         return [list(range(int(a), int(b))) for a, b in zip(cuts[:-1], cuts[1:])]
+    slots = _slot_elems(np.asarray(shapes).reshape(-1, 3)).tolist()
     batches: List[List[int]] = []
     cur: List[int] = []
     cur_slot = 0
-    for i, shp in enumerate(shapes):
-        vox = int(shp[0]) * int(shp[1]) * (-(-int(shp[2]) // nat.MMX_ROW_ALIGN) * nat.MMX_ROW_ALIGN)
+    for i, vox in enumerate(slots):
         slot = max(cur_slot, vox)
         if cur and ((len(cur) + 1) * slot * per_vox > budget_bytes or len(cur) >= _MAX_BATCH):
             batches.append(cur)
@@ -265,9 +277,7 @@ def plan_batches(shapes: Sequence[Tuple[int, int, int]], num_sigma: int,
     vox = [int(s_[0]) * int(s_[1]) * int(s_[2]) for s_ in shapes]
 
     def fits(batch):
-        slot = max(int(shapes[i][0]) * int(shapes[i][1]) * (-(-int(shapes[i][2]) // nat.MMX_ROW_ALIGN) * nat.MMX_ROW_ALIGN)
-                   for i in batch)
-        return len(batch) == 1 or (len(batch) * slot * per_vox <= budget_bytes and len(batch) <= _MAX_BATCH)
+        return len(batch) == 1 or (len(batch) * max(slots[i] for i in batch) * per_vox <= budget_bytes and len(batch) <= _MAX_BATCH)
 
     full = max(len(b_) for b_ in batches)
     tail = batches.pop()
@@ -422,12 +432,11 @@ def _make_blocks(dvol: DeviceVolume, channel: int, origins, shapes):
     held_lo = np.array([dvol.z_off, dvol.y_off, 0], dtype=np.int64)
     if (o < held_lo).any() or (o[:, :2] + shp[:, :2] > held_lo[:2] + np.asarray(t.shape[:2], dtype=np.int64)).any():
         raise ValueError("block outside the planes and rows this volume holds")
-    px = -(-shp[:, 2] // nat.MMX_ROW_ALIGN) * nat.MMX_ROW_ALIGN      # 128-B aligned rows
     blocks["src_off"] = o @ strides
     blocks["nz"], blocks["ny"], blocks["nx"] = shp[:, 0], shp[:, 1], shp[:, 2]
     blocks["slot"] = np.arange(len(shp))
-    blocks["px"] = px
-    return blocks, max(1, int((shp[:, 0] * shp[:, 1] * px).max()))
+    blocks["px"] = _row_elems(shp[:, 2])
+    return blocks, max(1, int(_slot_elems(shp).max()))
 
 
 def blob_log_blocks(dvol: DeviceVolume, channel: int, origins: Sequence[Sequence[int]],
@@ -616,8 +625,7 @@ def blob_log_lanes(dvol: DeviceVolume, lanes: Sequence[Lane], origins: Sequence[
         # the next batch's passes): both at their final size before anything is queued on them
         need = 0
         for b in batches:
-            slot_b = max(int(shapes[i][0]) * int(shapes[i][1]) * (-(-int(shapes[i][2]) // nat.MMX_ROW_ALIGN) * nat.MMX_ROW_ALIGN)
-                         for i in b)
+            slot_b = int(_slot_elems([shapes[i] for i in b]).max())
             need = max(need, -(-int(nat.lib().mmx_workspace_bytes(len(b), slot_b, ns_max, 1)) // 4))
         bufs.workspace(need)
         bufs.workspace(need, 1)
@@ -630,7 +638,7 @@ def blob_log_lanes(dvol: DeviceVolume, lanes: Sequence[Lane], origins: Sequence[
             if RESCORE_STREAM and n_items > 1:
                 bufs.workspace(need, 1)
             bufs.ws_free = [None, None]
-    jobs: List[Optional[dict]] = [None] * n_items
+    jobs: List[Optional[_Batch]] = [None] * n_items
     done_events: List = []
     enq = 0
     uploading = dvol._upload is not None
@@ -644,14 +652,12 @@ def blob_log_lanes(dvol: DeviceVolume, lanes: Sequence[Lane], origins: Sequence[
                 # would block the host until they are -- with finished batches waiting for their host work (all of it
                 # then piled up behind the upload's last region: 30 ms at the end of a from-host step).  Item k first.
                 break
-            jobs[enq] = _enqueue_detect(dvol, ln.channel, [origins[i] for i in batch], [shapes[i] for i in batch],
-                                        ln.space, ln.threshold, ln.eps, bufs, enq % (ahead + 1), ln.d_w0, ln.d_w2,
-                                        pre=ln.pre, exact=ln.exact, prepared=None if prepared is None else prepared[b_e],
-                                        vscale=ln.vscale, vrange=ln.vrange,
+            jobs[enq] = _enqueue_detect(dvol, ln, [origins[i] for i in batch], [shapes[i] for i in batch], bufs,
+                                        enq % (ahead + 1), prepared=None if prepared is None else prepared[b_e],
                                         buffer_free=(None if enq < ahead + 1 else done_events[enq - (ahead + 1)])
                                         if ln.pre is not None else False, parity=enq)
-            done_events.append(jobs[enq]["done"])
-            jobs[enq]["batch"] = batch
+            done_events.append(jobs[enq].done)
+            jobs[enq].indices = batch
             if enq == 0:
                 global FIRST_ENQUEUED_T, LAST_BATCH_SIZES
                 FIRST_ENQUEUED_T, LAST_BATCH_SIZES = time.perf_counter(), [len(b_) for b_ in batches]
@@ -659,39 +665,64 @@ def blob_log_lanes(dvol: DeviceVolume, lanes: Sequence[Lane], origins: Sequence[
         pending, jobs[k] = jobs[k], None
         ln = lanes[l_k]
         # host + side-stream work of item k, the GPU busy with the items behind it
-        peaks = _finish_detect(pending, dvol, ln.space, ln.threshold, ln.eps, bufs, ln.d_w0, ln.d_w2, ln.stats,
-                               finisher=ln.finisher if n_items == 1 else None, overlap=ln.overlap)
+        peaks = _finish_detect(pending, dvol, bufs, ln.finisher if n_items == 1 else None)
         if peaks is _FINISHED:
             continue
         if isinstance(peaks, PeakBatch):
             pb = _prune_batch_native(peaks, ln.space, ln.overlap, ln.stats)
             if ln.sink is not None:        # the caller builds its tables from the arrays (native, no per-block lists)
                 with torch.cuda.stream(bufs.side):      # (whatever it launches -- co-localisation means -- beside the next batch)
-                    ln.sink(pending["batch"], pb)
+                    ln.sink(pending.indices, pb)
                 continue
             pruned = [pb.blobs(b) for b in range(len(pb))]
             peaks = [pb.block(b) for b in range(len(pb))] if return_peaks else [None] * len(pb)
         else:
             with torch.cuda.stream(bufs.side):
                 pruned = _prune_batch(peaks, ln.space, ln.overlap, dvol.tensor.device, ln.stats)
-        for i, pk, res in zip(pending["batch"], peaks, pruned):
+        for i, pk, res in zip(pending.indices, peaks, pruned):
             ln.results[i] = res
             ln.peaks_out[i] = pk
         if ln.on_batch is not None:    # caller's per-block post-processing, still overlapped: whatever it launches
             with torch.cuda.stream(bufs.side):           # (co-localisation means) runs beside the next batch's kernels
-                ln.on_batch(pending["batch"], pruned)
+                ln.on_batch(pending.indices, pruned)
     results = [ln.results for ln in lanes]
     return (results, [ln.peaks_out for ln in lanes]) if return_peaks else results
 
 
 # --------------------------------------------------------------------------- A0-A4
-def _enqueue_detect(dvol, channel, origins, shapes, space: ScaleSpace, thr: float, eps: float,
-                    bufs: _Buffers, which: int, d_w0, d_w2, cap: Optional[int] = None, pre=None,
-                    exact: bool = False, prepared=None, vscale: Optional[float] = None, vrange=None,
-                    buffer_free=False, parity: Optional[int] = None):
-    """Enqueue (P1-P3,) A0-A4 of one batch on the current stream; nothing here waits for the GPU.
-    ``exact``: also re-score every candidate in float64 (otherwise ``_resolve_peaks`` re-scores the few
-    whose decision depends on it)."""
+@dataclass
+class _Batch:
+    """One batch in flight: what :func:`_enqueue_detect` hands to :func:`_finish_detect` (and to :func:`_redo`)."""
+    lane: "Lane"
+    origins: list
+    shapes: list
+    blocks: np.ndarray
+    d_blocks: "torch.Tensor"
+    nb: int
+    ns: int
+    n_vox: int
+    cap: int
+    which: int                  # the slot of `bufs` (candidate table, counters, events) it owns
+    done: _NativeEvent
+    store_f32: int
+    vol_exact: object           # the `mmx_volume` record of the voxels the exact re-score reads
+    eps: float
+    exact: bool
+    native: bool
+    indices: Optional[list] = None      # its blocks' places in the call's block lists (the pipeline's)
+    retries: int = 0                    # times it has been nominated again with a wider band
+
+
+def _enqueue_detect(dvol, lane: "Lane", origins, shapes, bufs: _Buffers, which: int, *, cap: Optional[int] = None,
+                    eps: Optional[float] = None, exact: Optional[bool] = None, prepared=None, buffer_free=False,
+                    parity: Optional[int] = None) -> _Batch:
+    """Enqueue (P1-P3,) A0-A4 of one batch of ``lane`` on the current stream: the preprocessing, then ONE
+    ``mmx_detect_batch`` call (or the replay of its captured graph); nothing here waits for the GPU.
+    ``eps`` / ``exact`` (default: the lane's): the nomination band, and whether every candidate is also re-scored in
+    float64 (otherwise ``_resolve_peaks`` re-scores the few whose decision depends on it)."""
+    channel, space, pre, thr, vrange = lane.channel, lane.space, lane.pre, lane.threshold, lane.vrange
+    eps = lane.eps if eps is None else eps
+    exact = lane.exact if exact is None else exact
     L = nat.lib()
     dev = dvol.tensor.device
     d_blocks = None
@@ -764,14 +795,13 @@ def _enqueue_detect(dvol, channel, origins, shapes, space: ScaleSpace, thr: floa
     table = bufs.cand_table(which, cap)
     count = bufs.counts[which]
     ev_read, ev_done = bufs.events(which)
-    side = bufs.rescore_stream if side_tail else None
     native = bool(exact and HOST_PATH == "native")
     a = nat.DetectArgs()
     a.vol32, a.vol_exact = ctypes.pointer(vol32), ctypes.pointer(vol_exact)
     a.d_blocks, a.h_blocks = d_blocks.data_ptr(), blocks.ctypes.data
     a.n_blocks, a.n_sigma, a.slot_elems = nb, ns, slot
     a.h_w0, a.h_w2 = space.w0_tab.ctypes.data, space.w2_tab.ctypes.data
-    a.d_w0, a.d_w2 = d_w0.data_ptr(), d_w2.data_ptr()
+    a.d_w0, a.d_w2 = lane.d_w0.data_ptr(), lane.d_w2.data_ptr()
     a.h_radius, a.h_norm = space.radii.ctypes.data, space.norms.ctypes.data
     a.d_work, a.work_bytes = ws.data_ptr(), ws.numel() * 4
     a.thr, a.eps = thr, eps
@@ -781,71 +811,33 @@ def _enqueue_detect(dvol, channel, origins, shapes, space: ScaleSpace, thr: floa
         a.h_cands, a.h_prefix = bufs.host_table(which).data_ptr(), min(cap, _PREFIX_ENTRIES)
     a.zx_mode, a.zx_flags, a.store_f32, a.exact, a.expand = ZX_MODE, ZX_FLAGS, store_f32, int(exact), int(native)
     a.stream = stream
-    a.tail_stream = side.cuda_stream if side is not None else stream
+    a.tail_stream = bufs.rescore_stream.cuda_stream if side_tail else stream      # (the library forks and joins it)
     a.pack_stream = bufs.pack_stream.cuda_stream if pack_side else stream
     # (the last reader of this workspace; also a batch that is nominated again, on the main stream: same workspace)
     a.ev_work_free = bufs.ws_free[ws_i].handle if bufs.ws_free[ws_i] is not None else None
     a.ev_work_read = ev_read.handle if side_tail else None
     a.ev_done = ev_done.handle
     info = nat.DetectInfo()
-    one_call = bool(NATIVE_BATCH and pre is None and native)
-    if one_call:
-        # ---- the whole batch in one native call (mmx_detect_batch): voxel copy, every scale, NMS, probes, re-score, copies
-        rc = _launch_batch(L, a, info, bufs, nb, blocks, space, vol32, vol_exact)
+    # a small raw batch that comes by again and again: captured once, then replayed
+    if NATIVE_BATCH and pre is None and native:
+        rc = _launch_batch(L, a, info, bufs, nb, blocks, space, vol32, vol_exact, ev_read if side_tail else None)
     else:
-        # ---- call by call: every scale by the library's rules (mmx_log_scales_f32), the tail from here
-        rc = L.mmx_log_scales_f32(ctypes.byref(a), ctypes.byref(info))
+        rc = L.mmx_detect_batch(ctypes.byref(a), ctypes.byref(info))
     if rc != 0:
         detail = L.mmx_detect_last_error().decode()
-        nat.check(rc, ("mmx_detect_batch" if one_call else "mmx_log_scales_f32") + (f" [{detail}]" if detail and rc == 2 else ""))
+        nat.check(rc, "mmx_detect_batch" + (f" [{detail}]" if detail and rc == 2 else ""))
     global LAST_ZX_PATH, LAST_Q16_BOUND, LAST_NMS_BAND
     LAST_ZX_PATH = info.zx_path
     if info.zx_path == nat.MMX_ZX_TILED_Q16:
         LAST_Q16_BOUND, LAST_NMS_BAND = info.q16_bound, eps
     if side_tail:
         bufs.ws_free[ws_i] = ev_read
-    job = dict(blocks=blocks, d_blocks=d_blocks, shapes=shapes, origins=origins, channel=channel,
-               nb=nb, ns=ns, n_vox=n_vox, cap=cap, which=which, done=ev_done, store_f32=store_f32,
-               vol_exact=vol_exact, pre=pre, exact=exact, eps=eps, native=native, vscale=vscale, vrange=vrange)
-    if one_call:
-        return job
-    log_base = ws.data_ptr() + 4 * nb * slot * 4
-    # NMS entries, [ns][(nb * slot) >> 5] 16-byte entries: written by the Y pass of the fused path
-    mask_base = (log_base + ns * nb * slot * 4 + 15) & ~15
-
-    def tail(stream_ptr):
-        count.zero_()
-        nat.check(L.mmx_peaks_batch(log_base, mask_base if info.mask_layout else None, info.mask_layout, ns,
-                                    d_blocks.data_ptr(), blocks.ctypes.data, nb, slot, thr, eps, table.data_ptr(), cap,
-                                    count.data_ptr(), stream_ptr),
-                  "mmx_peaks_batch")
-        if side_tail:                    # (the workspace may be written again once the NMS has read it)
-            nat.check(L.mmx_event_record(ev_read.handle, stream_ptr), "mmx_event_record")
-        if native:
-            # the neighbours that can out-vote the contested candidates join the table: one re-score, one copy
-            nat.check(L.mmx_expand_probes(table.data_ptr(), cap, count.data_ptr(), count.data_ptr() + 4,
-                                          d_blocks.data_ptr(), nb, ns, stream_ptr), "mmx_expand_probes")
-        if exact:
-            nat.check(L.mmx_rescore_f64(
-                ctypes.byref(vol_exact), d_blocks.data_ptr(), nb, table.data_ptr(), cap,
-                count.data_ptr(), d_w0.data_ptr(), d_w2.data_ptr(), nat.as_int32_ptr(space.radii),
-                nat.as_double_ptr(space.norms), ns, store_f32, stream_ptr), "mmx_rescore_f64")
-        bufs.host_counts[which].copy_(count, non_blocking=True)
-        if native:
-            n_pre = min(cap, _PREFIX_ENTRIES) * nat.CAND_DTYPE.itemsize
-            bufs.host_table(which)[:n_pre].copy_(table[:n_pre], non_blocking=True)
-        nat.check(L.mmx_event_record(ev_done.handle, stream_ptr), "mmx_event_record")
-    if side_tail:
-        # (every batch of a raw volume owns its candidate table; the volume is never written)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            tail(side.cuda_stream)
-    else:
-        tail(stream)
-    return job
+    return _Batch(lane=lane, origins=origins, shapes=shapes, blocks=blocks, d_blocks=d_blocks, nb=nb, ns=ns, n_vox=n_vox,
+                  cap=cap, which=which, done=ev_done, store_f32=store_f32, vol_exact=vol_exact, eps=eps, exact=exact,
+                  native=native)
 
 
-def _launch_batch(L, a, info, bufs: _Buffers, nb: int, blocks, space, vol32, vol_exact) -> int:
+def _launch_batch(L, a, info, bufs: _Buffers, nb: int, blocks, space, vol32, vol_exact, ev_read) -> int:
     """``mmx_detect_batch(a)`` -- or, for a small batch that has come by with the very same arguments before (a small
     volume detected step after step: same buffers, geometry, scales, band), the replay of its captured hipGraph: one
     launch instead of a dozen.  The second sighting of a key captures, later ones replay; a capture is refused while
@@ -867,13 +859,13 @@ def _launch_batch(L, a, info, bufs: _Buffers, nb: int, blocks, space, vol32, vol
             if getattr(a, name) == origin:
                 setattr(a, name, gs.cuda_stream)
         gs.wait_stream(caller)
-    rc = _launch_batch_graph(L, a, info, bufs, blocks, space, vol32, vol_exact)
+    rc = _launch_batch_graph(L, a, info, bufs, blocks, space, vol32, vol_exact, ev_read)
     if caller is not None:
         caller.wait_stream(bufs.graph_stream)
     return rc
 
 
-def _launch_batch_graph(L, a, info, bufs: _Buffers, blocks, space, vol32, vol_exact) -> int:
+def _launch_batch_graph(L, a, info, bufs: _Buffers, blocks, space, vol32, vol_exact, ev_read) -> int:
     # everything a node of the graph would freeze (the two volume records by content: their addresses change per call)
     key = (bytes(vol32), bytes(vol_exact), blocks.tobytes(), space.sigmas.tobytes(), a.d_blocks, a.slot_elems, a.d_w0,
            a.d_w2, a.d_work, a.work_bytes, a.thr, a.eps, a.d_cands, a.cap, a.h_prefix, a.d_count, a.h_count, a.h_cands,
@@ -900,44 +892,48 @@ def _launch_batch_graph(L, a, info, bufs: _Buffers, blocks, space, vol32, vol_ex
     GRAPH_REPLAYS += 1
     ctypes.memmove(ctypes.byref(info), ctypes.byref(saved), ctypes.sizeof(info))
     rc = L.mmx_graph_launch(graph, a.stream, a.ev_done, None)
-    if rc == 0 and a.ev_work_read:
+    if rc == 0 and ev_read is not None:
         # (the graph is ordered as a whole on `stream`: "the NMS has read the workspace" holds once it is through)
-        rc = L.mmx_event_record(a.ev_work_read, a.stream)
+        ev_read.record(a.stream)
     return rc
 
 
 _FINISHED = object()        # what `_finish_detect` returns when a finisher has taken the whole batch
 
 
-def _finish_detect(job, dvol, space: ScaleSpace, thr: float, eps: float, bufs: _Buffers, d_w0, d_w2,
-                   stats: BatchStats, finisher=None, overlap: float = 0.5):
+def _redo(batch: _Batch, dvol, bufs: _Buffers, *, cap: Optional[int], eps: float, exact: bool):
+    """Nominate ``batch`` again -- its candidate table overflowed, or its band proved too narrow -- and finish it.  The
+    pipeline has reused the workspace, so the passes run again.  The main stream is synchronised first; the batch then
+    goes up without its prepared block table (``prepared=None``: no side tail, workspace 0, everything in stream order
+    on the main stream) and with ``buffer_free=False`` (preprocessing on the main stream too).  It keeps its slot
+    ``which``, its ``indices`` and its count of ``retries``, and is never offered to a ``finisher``."""
+    torch.cuda.current_stream().synchronize()
+    again = _enqueue_detect(dvol, batch.lane, batch.origins, batch.shapes, bufs, batch.which, cap=cap, eps=eps, exact=exact)
+    again.indices, again.retries = batch.indices, batch.retries
+    return _finish_detect(again, dvol, bufs)
+
+
+def _finish_detect(batch: _Batch, dvol, bufs: _Buffers, finisher=None):
     """Wait for one batch's candidates and turn them into ordered raw peaks
     ``(coords int64 (n, 4), values float64 (n,))`` per block."""
-    job["done"].synchronize()
+    batch.done.synchronize()
     global LAST_BATCH_DONE_T
     LAST_BATCH_DONE_T = time.perf_counter()      # (bench.py: what a step still does after its last kernel)
-    eps = job.get("eps", eps)
-    which, cap, ns = job["which"], job["cap"], job["ns"]
-    native = job.get("native", False)
+    lane, eps, which, cap, ns, native = batch.lane, batch.eps, batch.which, batch.cap, batch.ns, batch.native
+    space, thr, stats = lane.space, lane.threshold, lane.stats
     words = bufs.host_counts[which].numpy().view(np.uint32)
     count = int(words[0])
     n_cands = int(words[1]) if native else count
-    if native and n_cands >= job["n_vox"] * ns:
+    if native and n_cands >= batch.n_vox * ns:
         count = n_cands = 0                 # constant cubes (below)
     if count > cap:
-        if count >= job["n_vox"] * ns and not native:
+        if count >= batch.n_vox * ns and not native:
             # every voxel of every block "equals its maximum": only possible for constant
             # cubes, which scikit-image treats as having no peaks (peak.py:41-43)
             count = 0
         else:
-            # table overflow (rare): redo this batch with a table that fits; the pipeline
-            # already reused the workspace, so the passes run again
-            torch.cuda.current_stream().synchronize()
-            redo = _enqueue_detect(dvol, job["channel"], job["origins"], job["shapes"], space, thr,
-                                   eps, bufs, which, d_w0, d_w2, cap=count + 1024, pre=job.get("pre"),
-                                   exact=job.get("exact", False), vscale=job.get("vscale"), vrange=job.get("vrange"))
-            redo["batch"] = job.get("batch")
-            return _finish_detect(redo, dvol, space, thr, eps, bufs, d_w0, d_w2, stats)
+            # table overflow (rare): redo this batch with a table that fits
+            return _redo(batch, dvol, bufs, cap=count + 1024, eps=eps, exact=batch.exact)
     with torch.cuda.stream(bufs.side):
         table = bufs.cands[which]
         try:
@@ -946,40 +942,33 @@ def _finish_detect(job, dvol, space: ScaleSpace, thr: float, eps: float, bufs: _
                     cands = bufs.host_table(which).numpy()[:count * nat.CAND_DTYPE.itemsize].view(nat.CAND_DTYPE)
                 else:
                     cands = table[:count * nat.CAND_DTYPE.itemsize].cpu().numpy().view(nat.CAND_DTYPE)
-                if finisher is not None and not job.get("retries") and finisher(
-                        job.get("batch"), cands, n_cands, job["blocks"], space, thr, eps, overlap, stats):
-                    stats.n_blocks += job["nb"]
-                    stats.n_voxels += job["n_vox"]
+                if finisher is not None and finisher(batch.indices, cands, n_cands, batch.blocks, space, thr, eps,
+                                                     lane.overlap, stats):
+                    stats.n_blocks += batch.nb
+                    stats.n_voxels += batch.n_vox
                     stats.n_candidates += n_cands
                     return _FINISHED
-                out = _resolve_peaks_native(cands, n_cands, job["blocks"], ns, thr, stats, eps)
+                out = _resolve_peaks_native(cands, n_cands, batch.blocks, ns, thr, stats, eps)
             else:
                 cands = (table[:count * nat.CAND_DTYPE.itemsize].cpu().numpy().view(nat.CAND_DTYPE)
                          if count else np.zeros(0, dtype=nat.CAND_DTYPE))
-                out = _resolve_peaks(cands, job["blocks"], job["shapes"], ns, thr, dvol, job["vol_exact"],
-                                     job["d_blocks"], d_w0, d_w2, space, job["store_f32"], stats, eps,
-                                     job.get("exact", False))
+                out = _resolve_peaks(cands, batch.blocks, batch.shapes, ns, thr, dvol, batch.vol_exact, batch.d_blocks,
+                                     lane.d_w0, lane.d_w2, space, batch.store_f32, stats, eps, batch.exact)
         except _BandTooNarrow as exc:
             out = None
             err = exc.err
-            wider = max(2.0 * eps, 8.0 * err)
         if out is not None:
-            stats.n_blocks += job["nb"]
-            stats.n_voxels += job["n_vox"]
+            stats.n_blocks += batch.nb
+            stats.n_voxels += batch.n_vox
             stats.n_candidates += n_cands
             return out
     # the float32 values were further from the exact ones than the band allows: nominate this batch again
-    # with a band of 8 x the deviation found (the exact re-score then decides as always).  The pipeline has
-    # reused the workspace, so the passes run again.
-    if job.get("retries", 0) >= 6:
+    # with a band of 8 x the deviation found (the exact re-score then decides as always)
+    if batch.retries >= 6:
         raise nat.MmxError(f"float32 LoG deviates from the exact values by {err:.3g}: no usable band")
     stats.n_band_retries += 1
-    torch.cuda.current_stream().synchronize()
-    redo = _enqueue_detect(dvol, job["channel"], job["origins"], job["shapes"], space, thr, wider, bufs, which,
-                           d_w0, d_w2, cap=None, pre=job.get("pre"), exact=True, vscale=job.get("vscale"), vrange=job.get("vrange"))
-    redo["batch"] = job.get("batch")
-    redo["retries"] = job.get("retries", 0) + 1
-    return _finish_detect(redo, dvol, space, thr, wider, bufs, d_w0, d_w2, stats)
+    batch.retries += 1
+    return _redo(batch, dvol, bufs, cap=None, eps=max(2.0 * eps, 8.0 * err), exact=True)
 
 
 def blob_log(image, min_sigma=1, max_sigma=50, num_sigma=10, threshold=.2, overlap=.5):

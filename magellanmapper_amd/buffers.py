@@ -28,7 +28,8 @@ _PREFIX_ENTRIES = 1 << 16
 
 class _NativeEvent:
     """A HIP event the library records (``mmx_detect_batch``: ``ev_done`` / ``ev_work_read``); what this host needs of
-    ``torch.cuda.Event``: ``synchronize`` and being waited for by a stream (:func:`_stream_wait`)."""
+    ``torch.cuda.Event``: ``synchronize``, ``record`` (behind a replayed graph, which holds no events) and being
+    waited for by a stream (:func:`_stream_wait`)."""
     __slots__ = ("handle",)
 
     def __init__(self):
@@ -38,6 +39,9 @@ class _NativeEvent:
 
     def synchronize(self) -> None:
         nat.check(nat.lib().mmx_event_synchronize(self.handle), "mmx_event_synchronize")
+
+    def record(self, stream_ptr) -> None:
+        nat.check(nat.lib().mmx_event_record(self.handle, stream_ptr), "mmx_event_record")
 
     def query(self) -> bool:
         rc = nat.lib().mmx_event_query(self.handle)

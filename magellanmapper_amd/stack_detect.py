@@ -52,7 +52,8 @@ PRUNE_AHEAD = ""
 #: rows per block: its last regions, pruned after the last kernel, are halved -- bench.py --region-split has the A/B)
 REGION_SPLIT = 0
 #: small one-batch stacks: the host chain behind the kernels as ONE native call (``_StackFinisher``); False keeps the
-#: call-by-call form (what tests compare it with)
+#: host chain step by step -- resolve, prune, emit, region prune, gather -- which tests compare it with (this is about
+#: the HOST steps: the kernels of every batch are enqueued by one ``mmx_detect_batch`` call either way)
 STACK_FINISHER = True
 
 

@@ -274,7 +274,7 @@ class _StackFinisher:
     ``detect_blobs_sub_rois`` from the planned pruning parameters, it hands its table over when ``prune_blobs_mp`` is
     called with those very parameters and ``final_form`` -- otherwise the arena it filled is pruned as always.  Where a
     decision needs the reference's own calls (equal peak values, a knife-edge overlap, a pruning chain, a band that
-    proved too narrow) the native call changes nothing and the batch takes the call-by-call path."""
+    proved too narrow) the native call changes nothing and the batch takes the usual host steps one by one."""
 
     def __init__(self, sink: "_ArenaSink", plan, channels):
         self.sink, self.arena, self.plan, self.channels = sink, sink.arena, plan, list(channels)

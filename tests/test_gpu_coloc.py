@@ -223,7 +223,7 @@ def test_channels_as_lanes_of_one_pipeline_equal_channel_after_channel(gpu, monk
             monkeypatch.setattr(bl, "BATCH_MAJOR", batch_major)
             sizes = []
             real = bl._enqueue_detect
-            monkeypatch.setattr(bl, "_enqueue_detect", lambda *a, **k: (sizes.append((a[1], len(a[2]))), real(*a, **k))[1])
+            monkeypatch.setattr(bl, "_enqueue_detect", lambda *a, **k: (sizes.append((a[1].channel, len(a[2]))), real(*a, **k))[1])
             _, _, blobs = stack_detect.detect_blobs_blocks("lanes", stack_detect.Image5d(vol[None]), None, None, None,
                                                            False, False, True, True)
             monkeypatch.setattr(bl, "_enqueue_detect", real)

@@ -1162,29 +1162,154 @@ def _peaks_of(bl, dvol, g, stats=None):
     return res[0], peaks[0]
 
 
+_TAIL_FIELDS = ("slot", "s", "z", "y", "x", "v", "flags", "band", "v64")
+
+
+def _tail_both_ways(bl, nat, g, exact):
+    """One batch (the golden volume as one block) enqueued twice on the same ``mmx_detect_args``: piece by piece through
+    the public entries -- ``mmx_log_scales_f32``, a zeroed counter, ``mmx_peaks_batch`` on the workspace layout worked out
+    HERE, ``mmx_expand_probes``, ``mmx_rescore_f64`` -- and by ``mmx_detect_batch`` into a second table.
+    ``exact``: the value of both ``exact`` and ``expand``.  Returns ``(words, table)`` of each form, as the device holds
+    them, the cap, and what ``mmx_detect_batch`` copied to the host."""
+    import ctypes
+    import torch
+    L = nat.lib()
+    dvol = bl.DeviceVolume(g["volume"])
+    dev = dvol.tensor.device
+    lane = bl.Lane(0, float(g["min_sigma"]), float(g["max_sigma"]), int(g["num_sigma"]), float(g["threshold"]),
+                   float(g["overlap"]))
+    lane.bind(dvol, 1)
+    space = lane.space
+    shape = tuple(int(v) for v in g["volume"].shape)
+    blocks, slot = bl._make_blocks(dvol, 0, [(0, 0, 0)], [shape])
+    d_blocks = bl._to_device_bytes(blocks, dev)
+    nb, ns = 1, len(space.sigmas)
+    vol32, vol_exact = dvol.view(0, True), dvol.view(0, False)
+    if vol32.dtype == nat.MMX_F32:          # (float voxels of ordinary magnitude, all >= 0 or not: mmx_volume.value_range)
+        lo, hi = lane.vrange
+        assert max(abs(lo), abs(hi)) <= bl.FLOAT_TILED_RANGE[1]
+        vol32.value_range = max(hi, 1e-30) if lo >= 0.0 else -max(abs(lo), abs(hi))
+    store_f32 = 1 if dvol.np_dtype == np.float32 else 0
+    ws = torch.empty(-(-int(L.mmx_workspace_bytes(nb, slot, ns, 1)) // 4), dtype=torch.float32, device=dev)
+    n_vox = int(np.prod(shape))
+    cap = max(4096, min(n_vox * ns, n_vox // 2000 * ns + 65536))
+    item = nat.CAND_DTYPE.itemsize
+    tables = [torch.zeros(cap * item, dtype=torch.uint8, device=dev) for _ in range(2)]
+    counts = [torch.full((2,), 12345, dtype=torch.int32, device=dev) for _ in range(2)]     # (garbage: the reset is the tail's)
+    h_count = torch.full((2,), 12345, dtype=torch.int32).pin_memory()
+    n_prefix = min(cap, bl._PREFIX_ENTRIES)
+    h_cands = torch.zeros(n_prefix * item, dtype=torch.uint8).pin_memory()
+    ev_done = bl._NativeEvent()
+    stream = bl._stream_ptr()
+    a = nat.DetectArgs()
+    a.vol32, a.vol_exact = ctypes.pointer(vol32), ctypes.pointer(vol_exact)
+    a.d_blocks, a.h_blocks = d_blocks.data_ptr(), blocks.ctypes.data
+    a.n_blocks, a.n_sigma, a.slot_elems = nb, ns, slot
+    a.h_w0, a.h_w2 = space.w0_tab.ctypes.data, space.w2_tab.ctypes.data
+    a.d_w0, a.d_w2 = lane.d_w0.data_ptr(), lane.d_w2.data_ptr()
+    a.h_radius, a.h_norm = space.radii.ctypes.data, space.norms.ctypes.data
+    a.d_work, a.work_bytes = ws.data_ptr(), ws.numel() * 4
+    a.thr, a.eps = lane.threshold, lane.eps
+    a.d_cands, a.cap, a.d_count = tables[0].data_ptr(), cap, counts[0].data_ptr()
+    a.zx_mode, a.zx_flags, a.store_f32, a.exact, a.expand = bl.ZX_MODE, bl.ZX_FLAGS, store_f32, int(exact), int(exact)
+    a.stream = a.tail_stream = a.pack_stream = stream
+    info = nat.DetectInfo()
+    # ---- piece by piece
+    nat.check(L.mmx_log_scales_f32(ctypes.byref(a), ctypes.byref(info)), "mmx_log_scales_f32")
+    # the workspace (mmx_workspace_bytes): four intermediate arrays, the LoG arrays [ns][nb * slot], then -- 16-byte
+    # aligned -- the NMS entries the Y pass wrote, in the layout the scales report
+    log_base = ws.data_ptr() + 4 * nb * slot * 4
+    mask_base = (log_base + ns * nb * slot * 4 + 15) & ~15
+    counts[0].zero_()
+    nat.check(L.mmx_peaks_batch(log_base, mask_base if info.mask_layout else None, info.mask_layout, ns,
+                                d_blocks.data_ptr(), blocks.ctypes.data, nb, slot, lane.threshold, lane.eps,
+                                tables[0].data_ptr(), cap, counts[0].data_ptr(), stream), "mmx_peaks_batch")
+    if exact:
+        nat.check(L.mmx_expand_probes(tables[0].data_ptr(), cap, counts[0].data_ptr(), counts[0].data_ptr() + 4,
+                                      d_blocks.data_ptr(), nb, ns, stream), "mmx_expand_probes")
+        nat.check(L.mmx_rescore_f64(ctypes.byref(vol_exact), d_blocks.data_ptr(), nb, tables[0].data_ptr(), cap,
+                                    counts[0].data_ptr(), lane.d_w0.data_ptr(), lane.d_w2.data_ptr(),
+                                    nat.as_int32_ptr(space.radii), nat.as_double_ptr(space.norms), ns, store_f32, stream),
+                  "mmx_rescore_f64")
+    torch.cuda.synchronize()
+    path_a, layout_a = info.zx_path, info.mask_layout
+    # ---- the one call, same arguments, second table
+    a.d_cands, a.d_count = tables[1].data_ptr(), counts[1].data_ptr()
+    a.h_count = h_count.data_ptr()
+    if exact:
+        a.h_cands, a.h_prefix = h_cands.data_ptr(), n_prefix
+    a.ev_done = ev_done.handle
+    rc = L.mmx_detect_batch(ctypes.byref(a), ctypes.byref(info))
+    nat.check(rc, "mmx_detect_batch [%s]" % L.mmx_detect_last_error().decode())
+    ev_done.synchronize()
+    host = (h_count.numpy().view(np.uint32).copy(), h_cands.numpy().view(nat.CAND_DTYPE).copy())
+    torch.cuda.synchronize()
+    assert (info.zx_path, info.mask_layout) == (path_a, layout_a)
+    out = [(c.cpu().numpy().view(np.uint32), t.cpu().numpy().view(nat.CAND_DTYPE)) for c, t in zip(counts, tables)]
+    return out[0], out[1], cap, host
+
+
+def _assert_same_entries(nat, got, want, n, fields):
+    """The first ``n`` entries of two candidate tables hold the same records.  Entries land by atomic append, so the
+    tables are compared sorted by ``(slot, s, z, y, x)``; and a probe's ``band`` is the TABLE INDEX of the candidate it
+    belongs to (include/mmx.h, ``MMX_CAND_PROBE``), which is a position, not a value: it is followed to that
+    candidate, whose ``(slot, s, z, y, x)`` must be equal instead (a voxel can be the probe of several candidates:
+    those records are ordered by their candidates)."""
+    keys = ("slot", "s", "z", "y", "x")
+
+    def ordered(t):
+        t = t[:n]
+        probe = (t["flags"] & 4) != 0                       # MMX_CAND_PROBE
+        owner_at = np.where(probe, t["band"], np.arange(n, dtype=np.uint64)).astype(np.int64)
+        assert ((0 <= owner_at) & (owner_at < n)).all() and not probe[owner_at].any()
+        owner = np.stack([t[k][owner_at] for k in keys], axis=1).astype(np.int64)
+        band = np.where(probe, np.uint64(0), t["band"])
+        order = np.lexsort((band, t["flags"]) + tuple(owner[:, j] for j in range(4, -1, -1))
+                           + tuple(t[k] for k in keys[::-1]))
+        return t[order], owner[order], band[order]
+    (got, got_owner, got_band), (want, want_owner, want_band) = ordered(got), ordered(want)
+    for f in fields:
+        if f == "band":
+            np.testing.assert_array_equal(got_band, want_band, err_msg="band (candidates)")
+            np.testing.assert_array_equal(got_owner, want_owner, err_msg="band (probes: the candidate it names)")
+        else:
+            np.testing.assert_array_equal(got[f], want[f], err_msg=f)
+
+
 @pytest.mark.parametrize("case", ["u16_5sigma", "u8_3sigma", "f32_2sigma", "f64_2sigma", "u16_thin", "u16_empty"])
 def test_one_native_call_per_batch_equals_the_call_by_call_form(gpu, case, monkeypatch):
     """``mmx_detect_batch`` (SURVEY.md 8b's fused A0-A4 entry: voxel copy, every scale, NMS, probes, exact re-score and
-    the copies enqueued by native code) against the call-by-call form, and against the real scikit-image: ordered
-    peaks, bit-equal float64 values, pruned blobs.  Both forms take the scales' kernel paths from the same native rules
-    (``mmx_log_scales_f32``); what this still cross-checks independently is the tail, the events and the streams, which
-    the call-by-call form enqueues one ctypes call at a time from Python."""
-    from magellanmapper_amd import blob_log as bl
+    the copies enqueued by native code) -- the form EVERY batch of the product takes -- against the tail enqueued piece
+    by piece through the public entries by this test (``_tail_both_ways``: its own statement of the workspace layout,
+    of the counter reset and of the order of the calls): the two counter words and every entry of the table equal, the
+    pinned copies equal to the device's.  Then the product against the real scikit-image: ordered peaks, pruned blobs,
+    the peak values bit-equal to the float64 values of the piece-by-piece table."""
+    from magellanmapper_amd import _native as nat, blob_log as bl
     g = load_golden("bloblog_%s.npz" % case)
+    (words_a, table_a), (words_b, table_b), cap, (h_words, h_table) = _tail_both_ways(bl, nat, g, True)
+    assert cap > words_a[0] and cap > words_b[0]
+    np.testing.assert_array_equal(words_b, words_a)
+    assert words_a[1] <= words_a[0]
+    _assert_same_entries(nat, table_b, table_a, int(words_a[0]), _TAIL_FIELDS)
+    np.testing.assert_array_equal(h_words, words_b)
+    n_head = min(int(words_b[0]), len(h_table))
+    assert h_table[:n_head].tobytes() == table_b[:n_head].tobytes()
+    keep = table_a[:int(words_a[0])].copy()
+    if case == "u16_5sigma":
+        # the shape of `exact_values=False`: nominations only (no probes, nobody writes v64)
+        (words_a, table_a), (words_b, table_b), cap, (h_words, _) = _tail_both_ways(bl, nat, g, False)
+        assert cap > words_a[0] and cap > words_b[0]
+        np.testing.assert_array_equal(words_b, words_a)
+        _assert_same_entries(nat, table_b, table_a, int(words_a[0]), _TAIL_FIELDS[:-1])
+        np.testing.assert_array_equal(h_words, words_b)
     dvol = bl.DeviceVolume(g["volume"])
     monkeypatch.setattr(bl, "GRAPH_BLOCKS", 0)
-    monkeypatch.setattr(bl, "NATIVE_BATCH", False)
-    res_a, (coords_a, vals_a) = _peaks_of(bl, dvol, g)
-    path_a = bl.LAST_ZX_PATH
-    monkeypatch.setattr(bl, "NATIVE_BATCH", True)
-    st = bl.BatchStats()
-    res_b, (coords_b, vals_b) = _peaks_of(bl, dvol, g, st)
-    assert bl.LAST_ZX_PATH == path_a
-    np.testing.assert_array_equal(coords_b, coords_a)
-    np.testing.assert_array_equal(vals_b, vals_a)
-    np.testing.assert_array_equal(res_b, res_a)
-    np.testing.assert_array_equal(coords_b, g["peaks"].reshape(-1, 4))            # real skimage
-    np.testing.assert_array_equal(res_b, g["pruned"])
+    res, (coords, vals) = _peaks_of(bl, dvol, g)
+    np.testing.assert_array_equal(coords, g["peaks"].reshape(-1, 4))            # real skimage
+    np.testing.assert_array_equal(res, g["pruned"])
+    # ... whose values are the float64 values of the test's own tail, bit for bit
+    exact = {(int(c["z"]), int(c["y"]), int(c["x"]), int(c["s"])): float(c["v64"]) for c in keep}
+    np.testing.assert_array_equal(vals, np.array([exact[tuple(int(v) for v in c)] for c in coords], dtype=np.float64))
 
 
 def test_small_batches_replay_a_captured_graph(gpu, monkeypatch):

@@ -956,6 +956,37 @@ def test_plan_batches_ramp_and_taper():
     assert [len(x) for x in bl.plan_batches([(40, 40, 40)] * 9, 3, 1 << 30)] == [9]      # tiny blocks: one batch
 
 
+def test_slot_elems_is_the_one_padded_block_size():
+    """``_slot_elems``: ``nz * ny * roundup(nx, MMX_ROW_ALIGN)``, the one statement of what the planner, the workspace
+    sizing and the block records each spelt out before -- and ``plan_batches`` cuts the same batches with it as it did
+    with its own two copies (the batches below were recorded before the expressions were folded)."""
+    from magellanmapper_amd import blob_log as bl
+    align = _native.MMX_ROW_ALIGN
+    shapes = [(1, 1, 1), (3, 5, 31), (3, 5, 32), (3, 5, 33), (261, 261, 261)]
+    for shp in shapes:
+        got = bl._slot_elems(shp)
+        # plan_batches' loop and its fits(), blob_log_lanes' workspace sizing: on Python ints
+        assert got == int(shp[0]) * int(shp[1]) * (-(-int(shp[2]) // align) * align)
+        # _make_blocks: on int64 arrays
+        a = np.asarray([shp], dtype=np.int64)
+        px = -(-a[:, 2] // align) * align
+        assert got == int((a[:, 0] * a[:, 1] * px).max())
+        assert int(bl._row_elems(shp[2])) == int(px[0])
+    many = bl._slot_elems(shapes)
+    assert many.shape == (5,) and many.tolist() == [int(bl._slot_elems(s)) for s in shapes]
+    assert many.tolist() == [32, 480, 480, 960, 261 * 261 * 288]
+
+    def runs(batches):          # batches of consecutive blocks as (first, count)
+        assert all(b == list(range(b[0], b[0] + len(b))) for b in batches)
+        return [(b[0], len(b)) for b in batches]
+
+    assert runs(bl.plan_batches([(261, 261, 261)] * 256, 5, 16 << 30)) == \
+        [(0, 22), (22, 22), (44, 22), (66, 22), (88, 22), (110, 22), (132, 22), (154, 22), (176, 22), (198, 22),
+         (220, 16), (236, 10), (246, 6), (252, 4)]
+    assert runs(bl.plan_batches([(44, 44, 44)] * 48, 3, 96 << 20)) == [(0, 24), (24, 24)]
+    assert runs(bl.plan_batches([(50, 60, 70)] * 3 + [(20, 20, 20)] * 4, 5, 64 << 20)) == [(0, 3), (3, 4)]
+
+
 def test_q16_error_bound_is_a_function_of_the_weights():
     """``mmx_tiled_q16_error_bound`` (host code, no GPU): the bound the 16-bit intermediates of the default path carry
     -- norm * (sum|w2| bound_P / 65535 + sum w0 bound_Q / 32767) / 2 plus the dropped low x low products of the X and of

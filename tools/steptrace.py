@@ -57,8 +57,8 @@ def wrap(mod, name, tag):
         out = fn(*args, **kw)
         extra = ""
         if name == "_enqueue_detect":
-            extra = f"{out['nb']} blocks"
-            ev = torch.cuda.Event(enable_timing=True); ev.record(); out["_ev"] = ev; evs.append(ev)
+            extra = f"{out.nb} blocks"
+            ev = torch.cuda.Event(enable_timing=True); ev.record(); evs.append(ev)
         log.append((t - T0[0], time.perf_counter() - T0[0], tag, extra))
         return out
     setattr(mod, name, inner)
