@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MMX_ABI_VERSION 20
+#define MMX_ABI_VERSION 21
 
 typedef enum {
     MMX_OK = 0,
@@ -53,6 +53,9 @@ typedef enum { MMX_U8 = 0, MMX_U16 = 1, MMX_F32 = 2, MMX_F64 = 3 } mmx_dtype;
  * larger radii take the generic path.  radius = int(4*sigma + 0.5)
  * (scipy/ndimage/_filters.py:313-315). */
 #define MMX_MAX_RADIUS_FAST 24
+/* largest kernel radius of the wide passes (mmx_wide.hip: LDS-staged tiles, radius a run-time value): what
+ * MMX_ZX_AUTO takes between MMX_MAX_RADIUS_FAST and here when every block extent is at least the radius */
+#define MMX_MAX_RADIUS_WIDE 64
 #define MMX_MAX_RADIUS_GENERIC 255
 /* most blocks one call takes (a launch puts the block on grid.y): MMX_ERR_UNSUPPORTED beyond; callers split batches */
 #define MMX_MAX_BLOCKS 65535
@@ -115,7 +118,9 @@ int mmx_device_count(void);
  * replaces: skimage.feature.blob_log's
  *     -gaussian_laplace(img_as_float(image), sigma) * sigma**2
  * (skimage/feature/blob.py:470, 501-502 -> scipy/ndimage/_filters.py:644-707),
- * computed in float32 (3 separable passes, shared order-0 passes).
+ * computed in float32 (3 separable passes, shared order-0 passes).  Radii above MMX_MAX_RADIUS_FAST up to
+ * MMX_MAX_RADIUS_WIDE take the wide passes (MMX_ZX_WIDE: Z, X, Y on LDS-staged tiles, row entries from the Y pass) when
+ * every block extent is at least the radius; beyond that -- larger radii, thinner blocks -- the generic passes.
  *   h_w0, h_w2 : float64 half kernels, index k = 0..radius (k = distance from centre),
  *                computed by the caller exactly as scipy's _gaussian_kernel1d does
  *   norm       : mean(sigma)**2
@@ -127,8 +132,8 @@ int mmx_device_count(void);
  *                more than nms_eps -- a superset of the local maxima, the only voxels mmx_peaks_batch visits.
  *                Word 1: the response exceeds nms_lo.  WITH A MASK, 64-VOXEL SEGMENTS WHOSE WORD 1 IS ZERO ARE
  *                NOT WRITTEN TO d_log (a response below the threshold can neither be a peak nor out-vote
- *                one): d_log is then only meaningful together with the entries.  Only the fused path produces
- *                the entries, and only when every block's rows fit its share (tiny blocks do not):
+ *                one): d_log is then only meaningful together with the entries.  Only the fused and the wide paths
+ *                produce the entries, and only when every block's rows fit its share (tiny blocks do not):
  *                *h_mask_written (host) says whether this call did (0: no, d_log is complete) and in which
  *                layout: MMX_MASK_ROWS (1) as above; MMX_MASK_QUADS (2, left by MMX_ZX_TILED): per row y one entry
  *                per 4 planes x 16 columns, entry y * ceil(nz/4) * ceil(nx/16) + (z >> 2) * ceil(nx/16) + (x >> 4),
@@ -154,8 +159,13 @@ typedef enum {
        profiles/HISTORY.md): MMX_ERR_ARG */
     MMX_ZX_TILED = 6,     /* zx4's arithmetic on an operand-ordered copy of the voxels (zx6_pack_kernel), P / Q
                              handed to the Y pass (y6_kernel) as 16 x 16 tiles: every access one contiguous KiB */
-    MMX_ZX_TILED_Q16 = 7  /* the same with the tiles as 16-bit fixed point (half the intermediate bytes): the LoG
+    MMX_ZX_TILED_Q16 = 7, /* the same with the tiles as 16-bit fixed point (half the intermediate bytes): the LoG
                              values carry a rounding error of at most mmx_tiled_q16_error_bound()               */
+    MMX_ZX_WIDE = 8       /* the wide passes (wide_z / wide_x / wide_y): radius 1 .. MMX_MAX_RADIUS_WIDE, u8 / u16 / f32
+                             voxels, every extent of every block >= radius, any row width; float32 throughout, entries
+                             in MMX_MASK_ROWS.  AUTO takes them for radii above MMX_MAX_RADIUS_FAST; by name they take
+                             any radius from 1 (cross-checks).  A geometry they do not accept falls through to the
+                             other paths as under AUTO */
 } mmx_zx_mode;
 #define MMX_ZX_PREPACKED 0x100   /* or-ed into MMX_ZX_TILED / MMX_ZX_TILED_Q16: mmx_zx_pack ran on this d_work for these blocks */
 #define MMX_ZX_Y_VALU    0x200   /* or-ed into MMX_ZX_TILED_Q16 (any zx_mode >= 0 accepts it): the Y pass of the 16-bit tiles on the
@@ -308,7 +318,13 @@ const char* mmx_detect_last_error(void);
  *   - with entries the Y pass leaves whole segments of the cube unwritten, so it is all scales in one entry layout or
  *     none: when the scales disagree (a radius outside the fused kernels, tiny blocks) every scale is computed again
  *     -- with MMX_ZX_PACKED when the layouts were rows and quads mixed, then without entries if they still differ
- *     (info->n_pass_rounds: 1 to 3). */
+ *     (info->n_pass_rounds: 1 to 3);
+ *   - under MMX_ZX_AUTO a ladder that holds a radius above MMX_MAX_RADIUS_FAST which the wide passes accept is laid out
+ *     BEFORE the first launch, so that there is one round: radii above MMX_MAX_RADIUS_FAST go MMX_ZX_WIDE, the others
+ *     MMX_ZX_PACKED where the fused path takes them on this geometry and MMX_ZX_WIDE where it does not (rows wider than
+ *     its limit), all with row entries; if any scale would end without entries (a radius above MMX_MAX_RADIUS_WIDE,
+ *     entries that do not fit) the one round runs without entries from the start.  Ladders without such a radius run
+ *     the rounds above unchanged. */
 int mmx_log_scales_f32(const mmx_detect_args* args, mmx_detect_info* info);
 /* the same launches captured as a hipGraph (every argument frozen; refused with MMX_ERR_UNSUPPORTED while per-kernel
  * timing is on: its events cannot live inside a capture) and replayed with one launch on `stream` */
@@ -558,10 +574,10 @@ int mmx_order_stats(const mmx_volume* vol, int64_t nz, int64_t ny, int64_t nx,
  * events, returns summed milliseconds and launch counts per kernel family (index =
  * MMX_K_*: 0 z pass, 1 y pass, 2 x pass, 3 generic passes, 4 peaks, 5 rescore,
  * 6 overlap pairs, 7 close pairs, 8 fused z+x pass, 9 y pass of the fused path, 10 preprocessing,
- * 11 co-localisation means, 12 operand-ordered voxel copy of the tiled path) and starts a new window.
+ * 11 co-localisation means, 12 operand-ordered voxel copy of the tiled path, 13 the wide passes) and starts a new window.
  * mmx_timing_enable(m), m > 1: only the families whose bit (k + 1) is set in m record events (an event between two
  * kernels keeps the second from starting under the first one's tail: timing one family perturbs a step less). */
-#define MMX_K_COUNT 13
+#define MMX_K_COUNT 14
 int mmx_timing_enable(int on);
 int mmx_timing_read(double* ms, int64_t* launches, int n);
 

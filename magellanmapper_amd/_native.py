@@ -17,9 +17,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 #: ``MMX_LIB_PATH`` selects an experimental build of the same ABI (kernel tuning only)
 LIB_PATH = os.environ.get("MMX_LIB_PATH") or os.path.join(_HERE, "libmmx_hip.so")
 
-MMX_ABI_VERSION = 20
+MMX_ABI_VERSION = 21
 MMX_U8, MMX_U16, MMX_F32, MMX_F64 = 0, 1, 2, 3
 MMX_MAX_RADIUS_FAST = 24
+MMX_MAX_RADIUS_WIDE = 64
 MMX_MAX_RADIUS_GENERIC = 255
 MMX_CAND_CONTESTED = 1
 MMX_CAND_BAND = 2
@@ -27,6 +28,7 @@ MMX_CAND_PROBE = 4
 #: ``mmx_zx_mode``: how mmx_log_batch_f32 runs its Z and X passes (a per-call argument)
 MMX_ZX_AUTO, MMX_ZX_SEPARATE, MMX_ZX_PACKED, MMX_ZX_MFMA_F32, MMX_ZX_MFMA_F16, MMX_ZX_MFMA_F16_LDS = -1, 0, 2, 3, 4, 5
 MMX_ZX_TILED, MMX_ZX_TILED_Q16, MMX_ZX_PREPACKED, MMX_ZX_Y_VALU = 6, 7, 0x100, 0x200
+MMX_ZX_WIDE = 8
 #: NMS entry layouts ``mmx_log_batch_f32`` reports and ``mmx_peaks_batch`` takes
 MMX_MASK_ROWS, MMX_MASK_QUADS = 1, 2
 MMX_MAX_BLOCKS = 65535
@@ -143,7 +145,7 @@ SYMBOLS = (
     "mmx_order_stats_workspace", "mmx_order_stats",
 )
 KERNEL_KINDS = ("zpass", "ypass", "xpass", "generic", "peaks", "rescore", "overlap_pairs",
-                "close_pairs", "zxpass", "y2pass", "preproc", "coloc", "zxpack")
+                "close_pairs", "zxpass", "y2pass", "preproc", "coloc", "zxpack", "widepass")
 
 
 def lib() -> ctypes.CDLL:

@@ -91,6 +91,10 @@ ZX_MODE = int(os.environ.get("MMX_FUSE", nat.MMX_ZX_AUTO))
 ZX_FLAGS = 0
 #: the ``mmx_zx_mode`` the most recent ``mmx_log_batch_f32`` call of this process actually ran
 LAST_ZX_PATH = None
+#: of the most recent batch (``mmx_detect_info``): how many times its scales were computed (1, or more when they had
+#: to be computed again on another path) and the NMS entry layout its peaks were nominated from (0: the full cube)
+LAST_PASS_ROUNDS = None
+LAST_MASK_LAYOUT = None
 #: who takes the per-batch decisions on the re-scored candidates: "native" (``mmx_host_resolve_peaks`` /
 #: ``mmx_host_overlap_prune``: threaded, outside the GIL, no second device round trip) or "numpy" (the same rules as
 #: array expressions; kept as a cross-check -- tests run both -- and for ``exact_values=False``)
@@ -826,8 +830,9 @@ def _enqueue_detect(dvol, lane: "Lane", origins, shapes, bufs: _Buffers, which: 
     if rc != 0:
         detail = L.mmx_detect_last_error().decode()
         nat.check(rc, "mmx_detect_batch" + (f" [{detail}]" if detail and rc == 2 else ""))
-    global LAST_ZX_PATH, LAST_Q16_BOUND, LAST_NMS_BAND
+    global LAST_ZX_PATH, LAST_PASS_ROUNDS, LAST_MASK_LAYOUT, LAST_Q16_BOUND, LAST_NMS_BAND
     LAST_ZX_PATH = info.zx_path
+    LAST_PASS_ROUNDS, LAST_MASK_LAYOUT = info.n_pass_rounds, info.mask_layout
     if info.zx_path == nat.MMX_ZX_TILED_Q16:
         LAST_Q16_BOUND, LAST_NMS_BAND = info.q16_bound, eps
     if side_tail:

@@ -47,7 +47,7 @@ int hip_fail(hipError_t e, const char* what)
 }
 
 // The register-ring column kernels prefetch kPrefetch (= 4) steps ahead and reflect once.
-constexpr int kColPrefetch = 4;
+constexpr int kColPrefetch = MMX_COL_PREFETCH;
 }  // namespace
 
 void mmx_time_begin(int kind, hipStream_t s)
@@ -280,7 +280,7 @@ int check_log_args(mmx_log_call* c, bool* y_valu, bool* prepacked)
     if (*y_valu) c->zx_mode &= ~MMX_ZX_Y_VALU;
     *prepacked = c->zx_mode == (MMX_ZX_TILED | MMX_ZX_PREPACKED) || c->zx_mode == (MMX_ZX_TILED_Q16 | MMX_ZX_PREPACKED);
     if (*prepacked) c->zx_mode &= ~MMX_ZX_PREPACKED;
-    if (c->zx_mode < MMX_ZX_AUTO || c->zx_mode > MMX_ZX_TILED_Q16 || c->zx_mode == 1 || (c->zx_mode >= 3 && c->zx_mode <= 5))
+    if (c->zx_mode < MMX_ZX_AUTO || c->zx_mode > MMX_ZX_WIDE || c->zx_mode == 1 || (c->zx_mode >= 3 && c->zx_mode <= 5))
         return MMX_ERR_ARG;             // (3, 4, 5: retired experiment kernels)
     if (!c->vol || !c->vol->d_data || !c->d_blocks || !c->h_blocks || !c->h_w0 || !c->h_w2 || !c->d_log || !c->d_work)
         return MMX_ERR_ARG;
@@ -302,11 +302,7 @@ int fused_passes(const mmx_log_call& c, bool y_valu, bool prepacked, const mmx_b
     const int radius = c.radius, n_blocks = c.n_blocks;
     const int64_t slot_elems = c.slot_elems;
     hipStream_t s = c.stream;
-    const bool fast_r = radius >= 1 && radius <= MMX_MAX_RADIUS_FAST;
-    const bool lane_ok = g.max_lane_in * 8 < (int64_t(1) << 31);
-    const bool fused = c.zx_mode != MMX_ZX_SEPARATE && fast_r && lane_ok && g.min_ny >= radius + kColPrefetch &&
-                       g.min_nz >= radius + 1 && g.min_nx >= radius && g.max_px <= 512 && vol->stride_y < (1 << 30);
-    if (!fused) return MMX_ERR_UNSUPPORTED;
+    if (c.zx_mode == MMX_ZX_SEPARATE || !mmx_fused_accepts(vol, g, radius)) return MMX_ERR_UNSUPPORTED;
     float* t0 = c.d_work;                                   // P
     float* t1 = c.d_work + (int64_t)n_blocks * slot_elems;  // Q
     mmx_taps_f32 tzz = taps(w.z0, w.z2, radius), txx = taps(w.y0, w.y2, radius), tyy = taps(w.x0, w.x2, radius);
@@ -367,6 +363,41 @@ int fused_passes(const mmx_log_call& c, bool y_valu, bool prepacked, const mmx_b
     return rc == MMX_ERR_HIP ? hip_fail(hipGetLastError(), "fused passes") : rc;
 }
 
+// The wide passes (mmx_wide.hip): Z, X, Y on LDS-staged tiles, radius 1 .. MMX_MAX_RADIUS_WIDE, row entries from the Y
+// pass.  MMX_ERR_UNSUPPORTED: not for this geometry -- the call goes on to the paths it took before there was this one.
+int wide_passes(const mmx_log_call& c, const mmx_batch_geom& g, const pass_weights& w)
+{
+    if (!mmx_wide_accepts(c.vol, g, c.radius)) return MMX_ERR_UNSUPPORTED;
+    const int radius = c.radius, n_blocks = c.n_blocks;
+    const int64_t slot_elems = c.slot_elems;
+    hipStream_t s = c.stream;
+    float* t0 = c.d_work;                                   // P
+    float* t1 = t0 + (int64_t)n_blocks * slot_elems;        // Q
+    float* t2 = t1 + (int64_t)n_blocks * slot_elems;        // Gz
+    float* t3 = t2 + (int64_t)n_blocks * slot_elems;        // Gzz
+    const bool want_mask = c.d_nms_mask && c.h_mask_written && g.rows_fit;
+    unsigned long long* d_mask = want_mask ? (unsigned long long*)c.d_nms_mask : nullptr;
+    int rc;
+    { mmx_timed_scope ts(MMX_K_WIDE, s);
+      rc = mmx_launch_wide_pass(0, c.vol, c.d_blocks, c.h_blocks, n_blocks, slot_elems, w.z0, w.z2, radius, nullptr, nullptr,
+                                t2, t3, nullptr, 0.f, 0.f, s); }
+    if (rc == MMX_OK) {
+        mmx_timed_scope ts(MMX_K_WIDE, s);
+        rc = mmx_launch_wide_pass(1, c.vol, c.d_blocks, c.h_blocks, n_blocks, slot_elems, w.y0, w.y2, radius, t2, t3, t0, t1,
+                                  nullptr, 0.f, 0.f, s);
+    }
+    if (rc == MMX_OK) {
+        mmx_timed_scope ts(MMX_K_WIDE, s);
+        rc = mmx_launch_wide_pass(2, c.vol, c.d_blocks, c.h_blocks, n_blocks, slot_elems, w.x0, w.x2, radius, t0, t1, c.d_log,
+                                  nullptr, d_mask, c.nms_lo, c.nms_eps, s);
+    }
+    if (rc == MMX_OK) {
+        if (c.h_zx_path) *c.h_zx_path = MMX_ZX_WIDE;
+        if (want_mask) *c.h_mask_written = MMX_MASK_ROWS;
+    }
+    return rc == MMX_ERR_HIP ? hip_fail(hipGetLastError(), "wide passes") : rc;
+}
+
 // The three separate passes: per pass the register-ring kernel where the geometry allows it, else the generic one.
 int separate_passes(const mmx_log_call& c, const mmx_batch_geom& g, const pass_weights& w)
 {
@@ -412,6 +443,11 @@ int mmx_log_scale_f32(const mmx_log_call& call, const mmx_batch_geom& g)
     if (g.status != MMX_OK) return g.status;
     pass_weights w;
     make_weights(c.vol, c.h_w0, c.h_w2, c.radius, c.norm, &w);
+    // the wide passes: by name at any radius they take, under AUTO above the register-resident radii
+    if (c.zx_mode == MMX_ZX_WIDE || (c.zx_mode == MMX_ZX_AUTO && c.radius > MMX_MAX_RADIUS_FAST)) {
+        rc = wide_passes(c, g, w);
+        if (rc != MMX_ERR_UNSUPPORTED) return rc;
+    }
     rc = fused_passes(c, y_valu, prepacked, g, w);
     if (rc != MMX_ERR_UNSUPPORTED) return rc;       // (unsupported geometry: the separate passes)
     return separate_passes(c, g, w);

@@ -72,6 +72,13 @@ int mmx_launch_y2(const mmx_block* d_blocks, int n_blocks, int max_cols, int64_t
                   const mmx_taps_f32& taps, int radius, const float* d_p, const float* d_q,
                   float* d_log, unsigned long long* d_mask, float nms_lo, float nms_eps, hipStream_t stream);
 
+// The wide passes (mmx_wide.hip): radius 1 .. MMX_MAX_RADIUS_WIDE.  pass 0 = Z (the volume -> out1, out2 = Gz, Gzz),
+// 1 = X (in1, in2 -> out1, out2 = P, Q), 2 = Y (in1, in2 = P, Q -> out1 = the LoG array; d_mask: row entries or NULL).
+int mmx_launch_wide_pass(int pass, const mmx_volume* vol, const mmx_block* d_blocks, const mmx_block* h_blocks, int n_blocks,
+                         int64_t slot_elems, const float* w0, const float* w2, int radius,
+                         const float* in1, const float* in2, float* out1, float* out2,
+                         unsigned long long* d_mask, float nms_lo, float nms_eps, hipStream_t s);
+
 // What the entry points derive from a batch's block table (mmx_batch_geom_make): nothing in it depends on sigma, so
 // a whole batch (mmx_log_scales_f32) fills it once.
 struct mmx_batch_geom {
@@ -89,6 +96,9 @@ struct mmx_batch_geom {
 };
 // (vol: NULL for callers that read no voxels -- no plan, no input offsets)
 void mmx_batch_geom_make(const mmx_volume* vol, const mmx_block* h_blocks, int n_blocks, int64_t slot_elems, mmx_batch_geom* g);
+
+// Host-only predicates of the kernel paths and the layout of a ladder with wide radii (no launch, no device state)
+#include "mmx_route.h"
 
 // mmx_log_batch_f32 and mmx_zx_pack behind their mmx_batch_geom_make (mmx_api.hip): what mmx_log_scales_f32 calls.
 struct mmx_log_call {       // (the arguments of mmx_log_batch_f32)
@@ -110,7 +120,7 @@ bool mmx_tiles_q16(int zx_mode, const mmx_volume* vol, double unit_bound, double
 // ---- optional per-kernel-family timing with HIP events on the launch stream (bench.py) ----
 enum mmx_kernel_kind {
     MMX_K_ZPASS = 0, MMX_K_YPASS, MMX_K_XPASS, MMX_K_GENERIC, MMX_K_PEAKS, MMX_K_RESCORE,
-    MMX_K_PAIRS, MMX_K_CLOSE, MMX_K_ZX, MMX_K_Y2, MMX_K_PREPROC, MMX_K_COLOC, MMX_K_ZXPACK, MMX_K_END
+    MMX_K_PAIRS, MMX_K_CLOSE, MMX_K_ZX, MMX_K_Y2, MMX_K_PREPROC, MMX_K_COLOC, MMX_K_ZXPACK, MMX_K_WIDE, MMX_K_END
 };
 void mmx_time_begin(int kind, hipStream_t s);
 void mmx_time_end(int kind, hipStream_t s);

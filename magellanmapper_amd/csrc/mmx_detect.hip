@@ -78,7 +78,7 @@ uint64_t* nms_entries(const mmx_detect_args* a)
 // One round of the rules (include/mmx.h, mmx_log_scales_f32): the voxel copy when `mode` can take the tiled path, then
 // every scale.  `layouts`: bit (1 << layout) for every NMS entry layout a scale reported (bit 0: none).
 int passes(const mmx_detect_args* a, const mmx_batch_geom& g, bool with_mask, int mode, unsigned* layouts, int* zx_path,
-           double* q16_bound, bool* pack_side)
+           double* q16_bound, bool* pack_side, const int32_t* modes = nullptr)
 {
     *layouts = 0;
     const mmx_volume* vol = a->vol32;
@@ -104,7 +104,8 @@ int passes(const mmx_detect_args* a, const mmx_batch_geom& g, bool with_mask, in
     }
     bool packed = false;
     hipStream_t main = (hipStream_t)a->stream;
-    if (((mode == MMX_ZX_AUTO || mode == MMX_ZX_TILED || mode == MMX_ZX_TILED_Q16) && !is_float) ||
+    if (modes) ;            // (no scale of a laid-out ladder runs the tiled path)
+    else if (((mode == MMX_ZX_AUTO || mode == MMX_ZX_TILED || mode == MMX_ZX_TILED_Q16) && !is_float) ||
         ((mode == MMX_ZX_AUTO || mode == MMX_ZX_TILED) && float_ok)) {
         hipStream_t ps = (*pack_side && a->pack_stream) ? (hipStream_t)a->pack_stream : main;
         int rc = mmx_zx_pack_geom(vol, a->d_blocks, a->h_blocks, nb, slot, g, a->d_work, ps);
@@ -118,6 +119,16 @@ int passes(const mmx_detect_args* a, const mmx_batch_geom& g, bool with_mask, in
     }
     for (int s = 0; s < ns; ++s) {
         int written = 0, path = 0;
+        if (modes) {        // (a ladder laid out beforehand: no voxel copy was made, every scale has its own mode)
+            const int rc = mmx_log_scale_f32({vol, a->d_blocks, a->h_blocks, nb, slot, a->h_w0 + s * tab, a->h_w2 + s * tab,
+                                              a->h_radius[s], a->h_norm[s], d_log + (size_t)s * nb * slot, a->d_work,
+                                              with_mask ? d_mask + (size_t)s * mask_words * 2 : nullptr, a->thr - a->eps,
+                                              a->eps, &written, modes[s], &path, main}, g);
+            if (rc != MMX_OK) return rc;
+            *zx_path = path;
+            *layouts |= 1u << (with_mask ? written : 0);
+            continue;
+        }
         // (the copy is trusted while every scale so far ran the tiled path: any other path uses that part of the
         //  workspace for something else)
         const int rc = mmx_log_scale_f32({vol, a->d_blocks, a->h_blocks, nb, slot, a->h_w0 + s * tab, a->h_w2 + s * tab,
@@ -171,11 +182,33 @@ int mmx_log_scales_f32(const mmx_detect_args* a, mmx_detect_info* info)
     mmx_batch_geom g;
     mmx_batch_geom_make(a->vol32, a->h_blocks, a->n_blocks, a->slot_elems, &g);
 
-    // all scales in one entry layout, or none: up to three rounds
     unsigned layouts = 0;
     int zx_path = 0;
     double q16_bound = 0.0;
-    int rc = passes(a, g, true, a->zx_mode, &layouts, &zx_path, &q16_bound, &pack_side);
+    int rc;
+    // a ladder with a radius for the wide passes: laid out before the first launch, one round (the rules: include/mmx.h)
+    std::vector<int32_t> modes(a->n_sigma);
+    bool entries = false;
+    if (a->zx_mode == MMX_ZX_AUTO && g.status == MMX_OK &&
+        mmx_ladder_layout(a->vol32, g, a->h_radius, a->n_sigma, modes.data(), &entries)) {
+        rc = passes(a, g, entries, MMX_ZX_AUTO, &layouts, &zx_path, &q16_bound, &pack_side, modes.data());
+        if (rc != MMX_OK) return rc;
+        if (layouts & (layouts - 1)) {      // (a scale left its laid-out path after all: the cube in full, as ever)
+            for (auto& m : modes) m = MMX_ZX_AUTO;
+            rc = passes(a, g, false, MMX_ZX_AUTO, &layouts, &zx_path, &q16_bound, &pack_side, modes.data());
+            if (rc != MMX_OK) return rc;
+            info->n_pass_rounds++;
+        }
+        int layout = 0;
+        while (!(layouts & (1u << layout))) ++layout;
+        info->zx_path = zx_path;
+        info->mask_layout = layout;
+        info->n_pass_rounds++;
+        return MMX_OK;
+    }
+
+    // all scales in one entry layout, or none: up to three rounds
+    rc = passes(a, g, true, a->zx_mode, &layouts, &zx_path, &q16_bound, &pack_side);
     if (rc != MMX_OK) return rc;
     if (layouts == ((1u << MMX_MASK_ROWS) | (1u << MMX_MASK_QUADS))) {
         rc = passes(a, g, true, MMX_ZX_PACKED, &layouts, &zx_path, &q16_bound, &pack_side);

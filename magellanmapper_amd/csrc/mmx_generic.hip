@@ -1,10 +1,12 @@
 // Generic (any radius, any extent) separable LoG passes: the slow, always-valid path.
 //
-// Used when the kernel radius exceeds MMX_MAX_RADIUS_FAST (sigma > 6 px) or when a block is
-// thinner than the register-ring kernels need (extent < radius + prefetch).  Same math as
-// mmx_colpass.hip / mmx_xpass.hip (scipy/ndimage/_filters.py:644-707 in float32), one thread
-// per output voxel, taps read through L1/L2, weights from the kernarg segment (uniform index
-// -> scalar loads).  Also the in-library cross-check for the fast kernels (tests).
+// What it still serves: kernel radii above MMX_MAX_RADIUS_WIDE (sigma > 16 px), batches with a block thinner than the
+// radius along some axis (the register-ring kernels need extent >= radius + prefetch, the wide passes of mmx_wide.hip
+// extent >= radius; here SciPy's "reflect" may wrap several times), and the float64 cross-checks: it is the in-library
+// reference the tests and blob_log.self_test hold every other kernel to (mmx_log_batch_f32_generic).  Radii 25 .. 64 on
+// blocks at least that thick, which used to come here, take the wide passes.  Same math as mmx_colpass.hip /
+// mmx_xpass.hip (scipy/ndimage/_filters.py:644-707 in float32), one thread per output voxel, taps read through L1/L2,
+// weights from the kernarg segment (uniform index -> scalar loads).
 
 #include "mmx_common.h"
 
