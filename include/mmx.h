@@ -251,6 +251,27 @@ int mmx_rescore_f64(const mmx_volume* vol, const mmx_block* d_blocks, int n_bloc
 int mmx_expand_probes(mmx_cand* d_cands, uint32_t cap, uint32_t* d_count, uint32_t* d_n_cands,
                       const mmx_block* d_blocks, int n_blocks, int n_sigma, void* stream);
 
+/* ---- a block detected as several overlapping parts: the candidates folded back into the block (added to ABI v21: the version number
+ * stays, a library without it lacks the symbol mmx_fold_parts, which callers check for)
+ * replaces: nothing of the reference -- it is what lets a block whose workspace slot would reach 2^29 elements go through
+ * the kernels above as ordinary blocks and still give the table `blob_log` gives for the whole block.  A part is a box of
+ * its parent: its core (the cores partition the parent) plus a halo of max kernel radius + 1 voxels, clipped to the
+ * parent.  Run between mmx_peaks_batch (the parts as blocks) and mmx_expand_probes (the parents as blocks); rewrites the
+ * table IN PLACE:
+ *   - an entry whose (z, y, x) lies outside the core of its part d_parts[slot] (or whose slot is no part) is dropped;
+ *   - a kept entry gets slot = d_parts[slot].parent and (z, y, x) += d_parts[slot].off;
+ *   - the kept entries are moved to the front (their order is not kept) and *d_count becomes their number.
+ * A table that has overflowed (*d_count > cap) is left alone, count included: the caller retries as ever.
+ * d_cands must be 16-byte aligned (any device allocation is): MMX_ERR_ARG otherwise. */
+typedef struct {
+    int32_t parent;        /* index of the block this part belongs to, in the parent table        */
+    int32_t off[3];        /* (z, y, x) of the part's first voxel inside its parent               */
+    int32_t core_lo[3];    /* the part's core, in PART coordinates: [core_lo, core_hi) per axis --  */
+    int32_t core_hi[3];    /* candidates outside it belong to a neighbouring part (or to nobody)  */
+} mmx_part;                /* 40 bytes */
+int mmx_fold_parts(mmx_cand* d_cands, uint32_t cap, uint32_t* d_count, const mmx_part* d_parts, int n_parts,
+                   void* stream);
+
 /* ---- A0-A4 of one batch of blocks in ONE call (the fused `mmx_detect_block`)
  * replaces: everything between the reference's call `blob_log(roi, min_sigma, max_sigma, num_sigma, threshold, overlap)`
  * (magmap/cv/detector.py:931-933 -> skimage/feature/blob.py:470-504, peak.py:28-50) and the comparison of float64 cube
@@ -271,7 +292,13 @@ int mmx_expand_probes(mmx_cand* d_cands, uint32_t cap, uint32_t* d_count, uint32
  *   stream      : the LoG passes;  tail_stream (NULL = stream): NMS, probes, re-score, copies -- beside the next batch's
  *                 passes when it is another stream;  pack_stream (NULL = stream): the voxel copy
  *   ev_work_free: NULL or an event to wait for before d_work is written (its previous reader);
- *   ev_work_read: NULL or an event recorded once the NMS has read d_work;  ev_done: NULL or recorded at the very end. */
+ *   ev_work_read: NULL or an event recorded once the NMS has read d_work;  ev_done: NULL or recorded at the very end.
+ *   d_parts / n_parts, d_parents / h_parents / n_parents (appended to the v21 record; NULL / 0: an ordinary batch): the blocks of the batch
+ *                 are PARTS of larger blocks (mmx_part, mmx_fold_parts below).  The passes and the NMS run on the parts;
+ *                 mmx_fold_parts then rewrites the table into parent coordinates, and the probe expansion, the exact
+ *                 re-score (vol_exact read with the parents' src_off and extents) and the host see the n_parents blocks
+ *                 of d_parents / h_parents only.  Such a batch is not captured (mmx_detect_batch_capture:
+ *                 MMX_ERR_UNSUPPORTED). */
 typedef struct {
     const mmx_volume* vol32;
     const mmx_volume* vol_exact;
@@ -294,6 +321,10 @@ typedef struct {
     int32_t zx_mode, zx_flags, store_f32, exact, expand, _pad;
     void* stream; void* tail_stream; void* pack_stream;
     void* ev_work_free; void* ev_work_read; void* ev_done;
+    const mmx_part* d_parts;
+    const mmx_block* d_parents;
+    const mmx_block* h_parents;
+    int32_t n_parts, n_parents;
 } mmx_detect_args;
 typedef struct {
     int32_t zx_path;        /* mmx_zx_mode the last scale ran */

@@ -43,6 +43,10 @@ CAND_DTYPE = np.dtype([("slot", "<i4"), ("s", "<i4"), ("z", "<i4"), ("y", "<i4")
                        ("flags", "<u4"), ("v", "<f4"), ("nbr_max", "<f4"), ("v64", "<f8"),
                        ("band", "<u8")], align=True)
 assert BLOCK_DTYPE.itemsize == 32 and CAND_DTYPE.itemsize == 48
+#: NumPy mirror of ``mmx_part`` (40 bytes): one part of a block that is detected as several (``mmx_fold_parts``)
+PART_DTYPE = np.dtype([("parent", "<i4"), ("off", "<i4", (3,)), ("core_lo", "<i4", (3,)), ("core_hi", "<i4", (3,))],
+                      align=True)
+assert PART_DTYPE.itemsize == 40
 #: NumPy mirrors of ``mmx_subblock`` (40 bytes), ``mmx_quantile_class`` (32), ``mmx_subblock_info`` (32)
 SUBBLOCK_DTYPE = np.dtype([("src_off", "<i8"), ("dst_off", "<i8"), ("scratch_off", "<i8"),
                            ("nz", "<i4"), ("ny", "<i4"), ("nx", "<i4"), ("qclass", "<i4")], align=True)
@@ -80,7 +84,9 @@ class DetectArgs(Structure):
                 ("zx_mode", c_int32), ("zx_flags", c_int32), ("store_f32", c_int32), ("exact", c_int32),
                 ("expand", c_int32), ("_pad", c_int32),
                 ("stream", c_void_p), ("tail_stream", c_void_p), ("pack_stream", c_void_p),
-                ("ev_work_free", c_void_p), ("ev_work_read", c_void_p), ("ev_done", c_void_p)]
+                ("ev_work_free", c_void_p), ("ev_work_read", c_void_p), ("ev_done", c_void_p),
+                ("d_parts", c_void_p), ("d_parents", c_void_p), ("h_parents", c_void_p),
+                ("n_parts", c_int32), ("n_parents", c_int32)]
 
 
 class FinishStackArgs(Structure):
@@ -140,7 +146,7 @@ SYMBOLS = (
     "mmx_calib_stream", "mmx_host_prune_axis",
     "mmx_preprocess_fast_lds", "mmx_preprocess_batch", "mmx_preprocess_batch_mode", "mmx_preprocess_work_bytes", "mmx_preprocess_batch_generic",
     "mmx_coloc_means", "mmx_coloc_voxels", "mmx_host_take_rows", "mmx_host_map_columns", "mmx_resize_batch_as", "mmx_gauss_axis_batch", "mmx_unmix_batch", "mmx_minmax_batch", "mmx_resize_batch",
-    "mmx_cdist_f64", "mmx_host_lsap", "mmx_expand_probes", "mmx_host_resolve_peaks", "mmx_host_overlap_prune",
+    "mmx_cdist_f64", "mmx_host_lsap", "mmx_expand_probes", "mmx_fold_parts", "mmx_host_resolve_peaks", "mmx_host_overlap_prune",
     "mmx_host_emit_tables", "mmx_host_prune_region", "mmx_host_prune_parts", "mmx_host_rows_in_boxes", "mmx_host_append_rows", "mmx_host_emit_parts", "mmx_host_merge_parts_by_key", "mmx_host_gather_parts_by_key", "mmx_host_emit_tables_multi", "mmx_host_coloc_flags", "mmx_host_finish_stack", "mmx_copy_rect_h2d", "mmx_host_stage_upload", "mmx_host_stage_upload_pitched", "mmx_event_query",
     "mmx_order_stats_workspace", "mmx_order_stats",
 )
@@ -167,6 +173,11 @@ def lib() -> ctypes.CDLL:
     except ImportError:
         pass
     L = ctypes.CDLL(LIB_PATH)
+    # (entry points added without a new version number -- mmx_fold_parts and the fields it appended to mmx_detect_args --
+    #  are told by their symbols: a library built before them must not be handed the longer record)
+    missing = [name for name in SYMBOLS if not hasattr(L, name)]
+    if missing:
+        raise MmxError(f"{LIB_PATH} lacks {', '.join(missing)}: it was built from older sources; rebuild it")
     vp = c_void_p
     L.mmx_abi_version.restype = c_int
     L.mmx_strerror.restype = c_char_p
@@ -240,6 +251,8 @@ def lib() -> ctypes.CDLL:
     L.mmx_coloc_voxels.restype = c_int
     L.mmx_expand_probes.argtypes = [vp, c_uint32, vp, vp, vp, c_int, c_int, vp]
     L.mmx_expand_probes.restype = c_int
+    L.mmx_fold_parts.argtypes = [vp, c_uint32, vp, vp, c_int, vp]
+    L.mmx_fold_parts.restype = c_int
     L.mmx_host_resolve_peaks.argtypes = [vp, c_uint32, c_uint32, vp, c_int, c_int, c_double, vp, vp, vp, vp, vp, vp, vp]
     L.mmx_host_overlap_prune.argtypes = [vp, vp, c_int, vp, c_int, c_double, c_double, vp, vp, vp, vp, c_int64,
                                          POINTER(c_int64), POINTER(c_int64)]

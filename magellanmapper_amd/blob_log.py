@@ -209,6 +209,7 @@ class BatchStats:
     """Counters of one :func:`blob_log_blocks` call (also feeds bench.py)."""
     n_blocks: int = 0
     n_voxels: int = 0
+    n_part_voxels: int = 0      # voxels the kernels processed: n_voxels, plus the halos of blocks detected in parts
     n_candidates: int = 0
     n_contested: int = 0
     n_probes: int = 0
@@ -241,6 +242,214 @@ def _slot_elems(shapes):
     gives one number, an ``(n, 3)`` list of shapes an array of ``n``."""
     shp = np.asarray(shapes, dtype=np.int64)
     return shp[..., 0] * shp[..., 1] * _row_elems(shp[..., 2])
+
+
+#: a block whose workspace slot (:func:`_slot_elems`) reaches this many elements is detected as several overlapping parts
+#: (:func:`split_oversized`; DESIGN.md section 4f).  The library refuses such a slot itself (its kernels address a slot
+#: with 32-bit byte offsets), so a value above ``LIB_MAX_SLOT_ELEMS`` counts as that; tests lower it
+MAX_SLOT_ELEMS = 1 << 29
+LIB_MAX_SLOT_ELEMS = 1 << 29
+#: most parts one block is cut into (the search for the smallest grid stops there)
+MAX_PARTS = 4096
+#: experiments and tests only: cut every oversized block into this ``(gz, gy, gx)`` grid instead of the smallest one (a
+#: grid the search would never pick -- a cut that saves no padded row -- or the cost of a split on blocks that need none,
+#: tools/partsbench.py); its boxes must still stay below the limit
+FORCED_PART_GRID: Optional[Tuple[int, int, int]] = None
+
+
+def _slot_limit() -> int:
+    return max(1, min(int(MAX_SLOT_ELEMS), LIB_MAX_SLOT_ELEMS))
+
+
+@dataclass
+class PartSplit:
+    """One block (the *parent*) cut into parts: ``grid`` parts per axis, ``cuts[axis]`` the ``grid[axis] + 1`` planes
+    between the cores (0 and the extent included), and per part, in C order of the grid, ``cores`` and ``boxes`` as
+    ``[lo, hi)`` corners in parent coordinates, shape ``(n, 2, 3)``.  The cores partition the parent; a box is its core
+    extended by the halo on every side, out to the next multiple of ``align`` where one is asked for, clipped to the
+    parent."""
+    shape: Tuple[int, int, int]
+    halo: int
+    grid: Tuple[int, int, int]
+    cuts: Tuple[np.ndarray, np.ndarray, np.ndarray]
+    cores: np.ndarray
+    boxes: np.ndarray
+
+    def __len__(self) -> int:
+        return len(self.cores)
+
+    @property
+    def box_shapes(self) -> np.ndarray:
+        return self.boxes[:, 1] - self.boxes[:, 0]
+
+    def records(self, parent: int = 0) -> np.ndarray:
+        """The ``mmx_part`` records (``mmx_fold_parts``): cores in part coordinates."""
+        rec = np.zeros(len(self), dtype=nat.PART_DTYPE)
+        rec["parent"] = parent
+        rec["off"] = self.boxes[:, 0]
+        rec["core_lo"] = self.cores[:, 0] - self.boxes[:, 0]
+        rec["core_hi"] = self.cores[:, 1] - self.boxes[:, 0]
+        return rec
+
+
+def _axis_pieces(n: int, g: int, halo: int, a: int):
+    """``g`` cores along an axis of ``n`` voxels and their boxes: ``(cuts, box_lo, box_hi)``, or None when ``n`` voxels
+    do not make ``g`` cores."""
+    if g > n:
+        return None
+    cuts = (np.arange(g + 1, dtype=np.int64) * n) // g
+    lo = np.maximum(cuts[:-1] - halo, 0) // a * a
+    hi = np.minimum(-(-(cuts[1:] + halo) // a) * a, n)
+    return cuts, lo, hi
+
+
+def split_oversized(shape: Sequence[int], max_slot_elems: int, halo: int, align: Sequence[int] = (1, 1, 1),
+                    grid: Optional[Sequence[int]] = None) -> PartSplit:
+    """Cut a block of ``shape`` whose workspace slot would reach ``max_slot_elems`` elements into the fewest parts whose
+    slots stay below it (:class:`PartSplit`).  A pure function of its arguments.
+
+    The cores are a grid of near-equal boxes that partition the block; every part's box is its core plus ``halo``
+    voxels on every side (``halo`` = largest kernel radius of the ladder + 1: a LoG value needs the voxels within the
+    radius, and the 3^4 NMS needs valid values one voxel around the core), clipped to the block.  With ``align`` (the
+    profile's ``denoise_max_shape`` when the blocks are preprocessed tile by tile) box faces that are not faces of the
+    block are moved outwards to the next multiple of ``align`` from the block's origin, so that a part's tile grid is
+    the block's.  Among the grids with the fewest parts the one whose largest box is smallest is taken -- the longest
+    axis is cut first, since that adds the least halo -- and of equals the one that cuts the later axes.  ``grid``
+    (experiments): that ``(gz, gy, gx)`` grid and no other.
+    ``MmxError`` when no such grid exists: the halo alone fills a slot."""
+    shape = tuple(int(v) for v in shape)
+    align = tuple(max(1, int(v)) for v in align)
+    halo, limit = int(halo), int(max_slot_elems)
+    if len(shape) != 3 or min(shape) < 1 or halo < 0 or len(align) != 3:
+        raise ValueError("split_oversized takes a (z, y, x) extent, a halo >= 0 and a per-axis alignment")
+    refuse = "block too large for one workspace slot (>= 2^29 voxels)" if limit >= LIB_MAX_SLOT_ELEMS else \
+        f"block too large for one workspace slot (>= {limit} elements)"
+    # the smallest box any grid can give: a core of one voxel and its halo, rounded out to the alignment
+    least = [min(n, -(-(1 + 2 * halo) // a) * a) for n, a in zip(shape, align)]
+    if int(_slot_elems(least)) >= limit:
+        raise nat.MmxError(f"{refuse} and it cannot be cut into parts: a part's halo of {halo} voxels on every side "
+                           f"(largest kernel radius + 1) alone takes {int(_slot_elems(least))} elements; detect with a "
+                           "smaller segment_size")
+    only = None if grid is None else tuple(int(v) for v in grid)
+    if only is not None and (len(only) != 3 or min(only) < 1):
+        raise ValueError("a grid of parts is (gz, gy, gx), each at least 1")
+    # per axis the piece counts worth trying -- those that make the largest box (along x: its padded row) smaller than
+    # every smaller count does -- and what they make it; the grids are their combinations
+    counts, sizes, pieces = [], [], {}
+    for ax in range(3):
+        tries = range(1, min(shape[ax], MAX_PARTS) + 1) if only is None else [only[ax]]
+        gs, es, least_e = [], [], None
+        for g in tries:
+            pc = _axis_pieces(shape[ax], g, halo, align[ax])
+            if pc is None:
+                continue
+            e = int((pc[2] - pc[1]).max())
+            e = int(_row_elems(e)) if ax == 2 else e
+            if least_e is None or e < least_e:
+                gs.append(g)
+                es.append(e)
+                pieces[(ax, g)] = pc
+                least_e = e
+            if e <= least[ax]:          # (it gets no smaller)
+                break
+        counts.append(np.asarray(gs, dtype=np.int64))
+        sizes.append(np.asarray(es, dtype=np.int64))
+    if all(len(c) for c in counts):
+        n_parts = counts[0][:, None, None] * counts[1][None, :, None] * counts[2][None, None, :]
+        worst = sizes[0][:, None, None] * sizes[1][None, :, None] * sizes[2][None, None, :]
+        ok = (worst < limit) & (n_parts <= MAX_PARTS)
+        if ok.any():
+            # fewest parts, then the smallest largest box, then the grid that cuts the later axes (C order of the grids)
+            key = np.where(ok, n_parts, np.iinfo(np.int64).max)
+            cand = np.argwhere(key == key.min())
+            cand = cand[np.argsort(worst[tuple(cand.T)], kind="stable")]
+            iz, iy, ix = (int(v) for v in cand[0])
+            grid3 = (int(counts[0][iz]), int(counts[1][iy]), int(counts[2][ix]))
+            axes = [pieces[(ax, g)] for ax, g in enumerate(grid3)]
+            idx = np.stack(np.meshgrid(*(np.arange(g) for g in grid3), indexing="ij"), axis=-1).reshape(-1, 3)
+            cores = np.empty((len(idx), 2, 3), dtype=np.int64)
+            boxes = np.empty_like(cores)
+            for ax in range(3):
+                cuts, lo, hi = axes[ax]
+                cores[:, 0, ax], cores[:, 1, ax] = cuts[idx[:, ax]], cuts[idx[:, ax] + 1]
+                boxes[:, 0, ax], boxes[:, 1, ax] = lo[idx[:, ax]], hi[idx[:, ax]]
+            return PartSplit(shape, halo, grid3, tuple(a_[0] for a_ in axes), cores, boxes)
+    how = f"{MAX_PARTS} parts or fewer" if only is None else f"a {only[0]} x {only[1]} x {only[2]} grid of parts"
+    raise nat.MmxError(f"{refuse} and it cannot be cut into {how} with a halo of {halo} voxels; detect with a smaller "
+                       "segment_size")
+
+
+def _split_blocks(lanes, shapes, limit: int) -> Dict[int, PartSplit]:
+    """The splits of the blocks whose slot reaches ``limit``, by block index.  One split serves every lane: its halo is
+    that of the widest ladder.  What a block in parts cannot go through raises ``NotImplementedError`` here."""
+    big = np.nonzero(_slot_elems(np.asarray(shapes, dtype=np.int64).reshape(-1, 3)) >= limit)[0]
+    if not len(big):
+        return {}
+    align = (1, 1, 1)
+    for lane in lanes:
+        pre = lane.pre
+        if pre is None:
+            continue
+        from . import preprocess
+        if isinstance(pre, preprocess.Rescaler) or getattr(pre, "rescale", None) is not None:
+            raise NotImplementedError("a block too large for one workspace slot is detected in parts, which the "
+                                      "isotropic rescale does not take; detect with a smaller segment_size")
+        if isinstance(pre, preprocess.Unmixer):
+            raise NotImplementedError("a block too large for one workspace slot is detected in parts, which spectral "
+                                      "unmixing does not take; detect with a smaller segment_size")
+        if not isinstance(pre, preprocess.Preprocessor):
+            raise NotImplementedError(f"a block detected in parts cannot take its voxels from a {type(pre).__name__}")
+        if pre.retains(lane.channel):
+            raise NotImplementedError("a block too large for one workspace slot is detected in parts, which the "
+                                      "intensity co-localisation (coloc=True) does not take; detect with a smaller "
+                                      "segment_size")
+        # (the parent is preprocessed WHOLE, tile by tile as ever, and its parts are boxes of that result: their faces
+        #  need not lie on tile planes, so no alignment -- which a halo of half a block would not survive)
+    halo = max(int(lane.space.radii.max(initial=0)) for lane in lanes) + 1
+    return {int(i): split_oversized(shapes[int(i)], limit, halo, align, FORCED_PART_GRID) for i in big}
+
+
+def _isolate_parents(batches: List[List[int]], splits: Dict[int, PartSplit]) -> List[List[int]]:
+    """``batches`` with every block that is detected in parts in a batch of its own (its parts are that batch's blocks)."""
+    out: List[List[int]] = []
+    for b in batches:
+        cur: List[int] = []
+        for i in b:
+            if i in splits:
+                if cur:
+                    out.append(cur)
+                out.append([i])
+                cur = []
+            else:
+                cur.append(i)
+        if cur:
+            out.append(cur)
+    return out
+
+
+def _part_blocks(parent, split: PartSplit, strides) -> Tuple[np.ndarray, int]:
+    """``mmx_block`` records of the parts of ``parent`` (one ``mmx_block`` record), which lies in a volume of element
+    ``strides`` (z, y, x): part i owns slot i.  Returns them and the slot size they need."""
+    lo, shp = split.boxes[:, 0], split.box_shapes
+    blocks = np.zeros(len(split), dtype=nat.BLOCK_DTYPE)
+    blocks["src_off"] = int(parent["src_off"]) + lo @ np.asarray(strides, dtype=np.int64)
+    blocks["nz"], blocks["ny"], blocks["nx"] = shp[:, 0], shp[:, 1], shp[:, 2]
+    blocks["slot"] = np.arange(len(split))
+    blocks["px"] = _row_elems(shp[:, 2])
+    return blocks, max(1, int(_slot_elems(shp).max()))
+
+
+def _workspace(bufs, n_floats: int, which: int, split: Optional[PartSplit]):
+    """``bufs.workspace`` -- and for a block in parts, whose workspace holds all of them at once, an error that says what
+    was needed and what to do about it."""
+    try:
+        return bufs.workspace(n_floats, which)
+    except torch.cuda.OutOfMemoryError as exc:
+        if split is None:
+            raise
+        raise nat.MmxError(f"a block of {split.shape[0]} x {split.shape[1]} x {split.shape[2]} voxels is detected as "
+                           f"{len(split)} parts in one batch, whose workspace needs {4 * int(n_floats)} bytes of device "
+                           "memory that could not be allocated; detect with a smaller segment_size") from exc
 
 
 def plan_batches(shapes: Sequence[Tuple[int, int, int]], num_sigma: int,
@@ -560,18 +769,22 @@ def blob_log_lanes(dvol: DeviceVolume, lanes: Sequence[Lane], origins: Sequence[
     immutable = type(origins) is tuple and type(shapes) is tuple
     seen = bufs.plan_lists.get((id(origins), id(shapes))) if immutable else None
     if seen is not None and seen[0] is origins and seen[1] is shapes:
-        _, _, lists_key, origins, shapes = seen
+        _, _, lists_key, origins, shapes, slot_max = seen
     else:
         given = (origins, shapes)
         shapes = [tuple(int(v) for v in s) for s in shapes]
         origins = [tuple(int(v) for v in o) for o in origins]
         lists_key = (tuple(origins), tuple(shapes))
+        slot_max = int(_slot_elems(np.asarray(shapes, dtype=np.int64).reshape(-1, 3)).max()) if shapes else 0
         if immutable:
             if len(bufs.plan_lists) >= 8:
                 bufs.plan_lists.clear()
-            bufs.plan_lists[(id(given[0]), id(given[1]))] = (given[0], given[1], lists_key, origins, shapes)   # (kept alive: ids stay theirs)
+            bufs.plan_lists[(id(given[0]), id(given[1]))] = (given[0], given[1], lists_key, origins, shapes, slot_max)   # (kept alive: ids stay theirs)
     for lane in lanes:
         lane.bind(dvol, len(shapes))
+    # blocks too large for one workspace slot go through as several overlapping parts, each in a batch of its own
+    # (DESIGN.md section 4f); without one -- every call so far -- nothing below takes another path
+    splits = _split_blocks(lanes, shapes, _slot_limit()) if slot_max >= _slot_limit() else {}
     n_sig = [len(lane.space.sigmas) for lane in lanes]
     ns_max = max(n_sig + [int(plan_num_sigma or 0)])
     # the batches and their block tables on the device: remembered for the same block lists, volume layout and budget (a
@@ -579,7 +792,7 @@ def blob_log_lanes(dvol: DeviceVolume, lanes: Sequence[Lane], origins: Sequence[
     # the first kernel can start
     plan_key = None
     planned = None
-    if not any_pre:
+    if not any_pre and not splits:
         t_ = dvol.tensor
         # (block records hold element offsets, not addresses: any volume of this layout can use them; the block lists
         #  are compared by content -- `lists_key` above -- so that a caller who builds them afresh finds the same device
@@ -592,6 +805,18 @@ def blob_log_lanes(dvol: DeviceVolume, lanes: Sequence[Lane], origins: Sequence[
     else:
         batches = plan_batches(shapes, ns_max, budget_bytes,
                                0 if not any_pre else max(lane.pre.bytes_per_voxel() for lane in lanes))
+        if splits:
+            batches = _isolate_parents(batches, splits)
+    split_of = [splits.get(b[0]) if len(b) == 1 else None for b in batches] if splits else [None] * len(batches)
+
+    def geometry(k):
+        """Blocks and slot size of batch ``k`` as the library will see it."""
+        if split_of[k] is not None:
+            return len(split_of[k]), int(_slot_elems(split_of[k].box_shapes).max())
+        if prepared is not None:
+            return len(prepared[k][0]), prepared[k][1]
+        return len(batches[k]), int(_slot_elems([shapes[i] for i in batches[k]]).max())
+
     n_b = len(batches)
     n_l = len(lanes)
     items = [(b, l) for b in range(n_b) for l in range(n_l)]       # batch-major
@@ -614,33 +839,42 @@ def blob_log_lanes(dvol: DeviceVolume, lanes: Sequence[Lane], origins: Sequence[
     elif not any_pre:
         # block tables of every batch go to the device BEFORE the first kernel: a pageable host -> device copy
         # waits for everything queued on the stream before it
-        prepared = [_make_blocks(dvol, lanes[0].channel, [origins[i] for i in b], [shapes[i] for i in b]) for b in batches]
-        if prepared:        # (one upload for all of them: fourteen small copies were 0.4 ms of idle GPU at the start of a step)
-            sizes = [blk.nbytes for blk, _ in prepared]
-            allrec = _to_device_bytes(np.concatenate([blk.view(np.uint8).reshape(-1) for blk, _ in prepared]),
+        # (a block in parts: its tables are made when it is enqueued, `prepared` holds None in its place)
+        prepared = [None if split_of[k] is not None else
+                    _make_blocks(dvol, lanes[0].channel, [origins[i] for i in b], [shapes[i] for i in b])
+                    for k, b in enumerate(batches)]
+        ready = [k for k, p_ in enumerate(prepared) if p_ is not None]
+        if ready:           # (one upload for all of them: fourteen small copies were 0.4 ms of idle GPU at the start of a step)
+            sizes = [prepared[k][0].nbytes for k in ready]
+            allrec = _to_device_bytes(np.concatenate([prepared[k][0].view(np.uint8).reshape(-1) for k in ready]),
                                       dvol.tensor.device)
             offs = np.concatenate([[0], np.cumsum(sizes)])
-            prepared = [(blk, slot, allrec[int(offs[i]):int(offs[i + 1])]) for i, (blk, slot) in enumerate(prepared)]
-        if len(bufs.plans) >= 8:
-            bufs.plans.clear()
-        bufs.plans[plan_key] = (batches, prepared)
+            for j, k in enumerate(ready):
+                prepared[k] = (prepared[k][0], prepared[k][1], allrec[int(offs[j]):int(offs[j + 1])])
+        if plan_key is not None:
+            if len(bufs.plans) >= 8:
+                bufs.plans.clear()
+            bufs.plans[plan_key] = (batches, prepared)
     if any_pre and PRE_SIDE_TAIL and RESCORE_STREAM and all(lane.exact for lane in lanes) and n_items > 1:
         # preprocessed batches alternate between two workspaces as well (the tail of a batch on the second stream beside
         # the next batch's passes): both at their final size before anything is queued on them
         need = 0
-        for b in batches:
-            slot_b = int(_slot_elems([shapes[i] for i in b]).max())
-            need = max(need, -(-int(nat.lib().mmx_workspace_bytes(len(b), slot_b, ns_max, 1)) // 4))
-        bufs.workspace(need)
-        bufs.workspace(need, 1)
+        for k in range(n_b):
+            need = max(need, -(-int(nat.lib().mmx_workspace_bytes(*geometry(k), ns_max, 1)) // 4))
+        widest = max(splits.values(), key=len) if splits else None
+        _workspace(bufs, need, 0, widest)
+        _workspace(bufs, need, 1, widest)
         bufs.ws_free = [None, None]
     if not any_pre:        # ... and the shared workspace has its final size before anything is queued on it
         if prepared:
-            need = max(-(-int(nat.lib().mmx_workspace_bytes(len(blk), slot, ns_max, 1)) // 4)
-                       for blk, slot, _ in prepared)
-            bufs.workspace(need)
+            need = max(-(-int(nat.lib().mmx_workspace_bytes(*geometry(k), ns_max, 1)) // 4) for k in range(n_b))
+            _workspace(bufs, need, 0, max(splits.values(), key=len) if splits else None)
             if RESCORE_STREAM and n_items > 1:
-                bufs.workspace(need, 1)
+                # (a block in parts works in workspace 0 alone: the second one is as large as the other batches need)
+                need1 = max([-(-int(nat.lib().mmx_workspace_bytes(*geometry(k), ns_max, 1)) // 4)
+                             for k in range(n_b) if split_of[k] is None] or [0])
+                if need1:
+                    bufs.workspace(need1, 1)
             bufs.ws_free = [None, None]
     jobs: List[Optional[_Batch]] = [None] * n_items
     done_events: List = []
@@ -659,7 +893,7 @@ def blob_log_lanes(dvol: DeviceVolume, lanes: Sequence[Lane], origins: Sequence[
             jobs[enq] = _enqueue_detect(dvol, ln, [origins[i] for i in batch], [shapes[i] for i in batch], bufs,
                                         enq % (ahead + 1), prepared=None if prepared is None else prepared[b_e],
                                         buffer_free=(None if enq < ahead + 1 else done_events[enq - (ahead + 1)])
-                                        if ln.pre is not None else False, parity=enq)
+                                        if ln.pre is not None else False, parity=enq, split=split_of[b_e])
             done_events.append(jobs[enq].done)
             jobs[enq].indices = batch
             if enq == 0:
@@ -715,21 +949,42 @@ class _Batch:
     native: bool
     indices: Optional[list] = None      # its blocks' places in the call's block lists (the pipeline's)
     retries: int = 0                    # times it has been nominated again with a wider band
+    # a block detected in parts (`origins` / `shapes` hold that one block, the PARENT; `blocks` / `nb` its parts): the
+    # split, the parent table -- what everything behind the fold works on -- and the voxels of the parts
+    split: Optional[PartSplit] = None
+    parents: Optional[np.ndarray] = None
+    d_parents: Optional["torch.Tensor"] = None
+    d_parts: Optional["torch.Tensor"] = None
+    n_part_vox: int = 0
+
+    @property
+    def table_blocks(self) -> np.ndarray:
+        """The blocks the finished candidate table speaks of."""
+        return self.blocks if self.split is None else self.parents
+
+    @property
+    def d_table_blocks(self):
+        return self.d_blocks if self.split is None else self.d_parents
 
 
 def _enqueue_detect(dvol, lane: "Lane", origins, shapes, bufs: _Buffers, which: int, *, cap: Optional[int] = None,
                     eps: Optional[float] = None, exact: Optional[bool] = None, prepared=None, buffer_free=False,
-                    parity: Optional[int] = None) -> _Batch:
+                    parity: Optional[int] = None, split: Optional[PartSplit] = None) -> _Batch:
     """Enqueue (P1-P3,) A0-A4 of one batch of ``lane`` on the current stream: the preprocessing, then ONE
     ``mmx_detect_batch`` call (or the replay of its captured graph); nothing here waits for the GPU.
     ``eps`` / ``exact`` (default: the lane's): the nomination band, and whether every candidate is also re-scored in
-    float64 (otherwise ``_resolve_peaks`` re-scores the few whose decision depends on it)."""
+    float64 (otherwise ``_resolve_peaks`` re-scores the few whose decision depends on it).
+    ``split``: ``origins`` / ``shapes`` hold ONE block, which goes through the passes and the NMS as the parts of this
+    split; the library folds their candidates back into it (``mmx_fold_parts``) and everything behind sees that block."""
     channel, space, pre, thr, vrange = lane.channel, lane.space, lane.pre, lane.threshold, lane.vrange
     eps = lane.eps if eps is None else eps
     exact = lane.exact if exact is None else exact
     L = nat.lib()
     dev = dvol.tensor.device
     d_blocks = None
+    parents = None
+    if split is not None and (len(shapes) != 1 or tuple(int(v) for v in shapes[0]) != split.shape):
+        raise ValueError("a split belongs to the one block of its batch")
     # a volume still on its way up (`DeviceVolume.stream_wait`): this batch waits for the slabs its blocks touch, on
     # every stream that reads voxels (the passes, the voxel copy of the tiled path, the exact re-score)
     boxes = ([(int(o[0]), int(o[0]) + int(s_[0]), int(o[1]), int(o[1]) + int(s_[1])) for o, s_ in zip(origins, shapes)]
@@ -741,6 +996,9 @@ def _enqueue_detect(dvol, lane: "Lane", origins, shapes, bufs: _Buffers, which: 
             blocks, slot, d_blocks = prepared
         else:
             blocks, slot = _make_blocks(dvol, channel, origins, shapes)
+        if split is not None:
+            parents = blocks
+            blocks, slot = _part_blocks(parents[0], split, dvol.tensor.stride()[:3])
         vol32 = dvol.view(channel, True)
         vol_exact = dvol.view(channel, False)
         store_f32 = 1 if dvol.np_dtype == np.float32 else 0
@@ -771,9 +1029,15 @@ def _enqueue_detect(dvol, lane: "Lane", origins, shapes, bufs: _Buffers, which: 
             dvol.stream_wait(None, [torch.cuda.current_stream(), bufs.side], boxes)
             blocks, slot, vol32, vol_exact = pre.run(dvol, channel, origins, shapes, which)
         store_f32 = int(getattr(pre, "store_f32", 0))
+        if split is not None:
+            # the parent was preprocessed whole, tile by tile as ever: its parts are boxes of that slot (same strides), and
+            # the exact re-score reads the slot with the parent's extent
+            parents = blocks
+            blocks, slot = _part_blocks(parents[0], split, (vol32.stride_z, vol32.stride_y, vol32.stride_x))
     nb, ns = len(blocks), len(space.sigmas)
-    if slot >= (1 << 29):
-        raise nat.MmxError("block too large for one workspace slot (>= 2^29 voxels)")
+    if slot >= _slot_limit():
+        raise nat.MmxError("block too large for one workspace slot (>= 2^29 voxels)" if _slot_limit() == LIB_MAX_SLOT_ELEMS
+                           else f"block too large for one workspace slot (>= {_slot_limit()} elements)")
     # raw volumes: the batches alternate between two workspaces, and everything after a batch's last LoG kernel -- NMS,
     # probe expansion, exact re-score, copies -- runs on a second stream beside the next batch's LoG kernels
     # (preprocessed batches too with PRE_SIDE_TAIL -- measured and left off; their two workspaces are sized by
@@ -781,7 +1045,7 @@ def _enqueue_detect(dvol, lane: "Lane", origins, shapes, bufs: _Buffers, which: 
     side_tail = bool(RESCORE_STREAM and exact and ((pre is None and prepared is not None) or
                                                    (pre is not None and PRE_SIDE_TAIL and bufs.ws2 is not None)))
     ws_i = ((which if parity is None else parity) & 1) if (side_tail and bufs.ws2 is not None) else 0
-    ws = bufs.workspace(-(-int(L.mmx_workspace_bytes(nb, slot, ns, 1)) // 4), ws_i)
+    ws = _workspace(bufs, -(-int(L.mmx_workspace_bytes(nb, slot, ns, 1)) // 4), ws_i, split)
     # ... and the voxel copy of the tiled path, the first kernel of a batch, on a third: it only needs the workspace
     pack_side = side_tail and PACK_STREAM and bufs.ws2 is not None
     if d_blocks is None:
@@ -794,8 +1058,9 @@ def _enqueue_detect(dvol, lane: "Lane", origins, shapes, bufs: _Buffers, which: 
         vol32.value_range = 0.0 if not float_ok else (max(vrange[1], 1e-30) if vrange[0] >= 0.0
                                                       else -max(abs(vrange[0]), abs(vrange[1])))
     n_vox = int(sum(int(np.prod(s)) for s in shapes))
+    n_part_vox = n_vox if split is None else int(split.box_shapes.prod(axis=1).sum())       # (what the NMS nominates from)
     if cap is None:
-        cap = max(4096, min(n_vox * ns, n_vox // 2000 * ns + 65536))
+        cap = max(4096, min(n_part_vox * ns, n_part_vox // 2000 * ns + 65536))
     table = bufs.cand_table(which, cap)
     count = bufs.counts[which]
     ev_read, ev_done = bufs.events(which)
@@ -821,9 +1086,19 @@ def _enqueue_detect(dvol, lane: "Lane", origins, shapes, bufs: _Buffers, which: 
     a.ev_work_free = bufs.ws_free[ws_i].handle if bufs.ws_free[ws_i] is not None else None
     a.ev_work_read = ev_read.handle if side_tail else None
     a.ev_done = ev_done.handle
+    d_parents = d_parts = None
+    if split is not None:
+        lo, hi = split.boxes[:, 0], split.boxes[:, 1]
+        if (lo < 0).any() or (hi > np.asarray(split.shape)).any() or (split.cores[:, 0] < lo).any() or \
+                (split.cores[:, 1] > hi).any():
+            raise ValueError("a part outside its block")           # (the re-score reads the parent at folded coordinates)
+        d_parents = _to_device_bytes(parents, dev)
+        d_parts = _to_device_bytes(split.records(0), dev)
+        a.d_parts, a.n_parts = d_parts.data_ptr(), len(split)
+        a.d_parents, a.h_parents, a.n_parents = d_parents.data_ptr(), parents.ctypes.data, 1
     info = nat.DetectInfo()
-    # a small raw batch that comes by again and again: captured once, then replayed
-    if NATIVE_BATCH and pre is None and native:
+    # a small raw batch that comes by again and again: captured once, then replayed (never a block in parts)
+    if NATIVE_BATCH and pre is None and native and split is None:
         rc = _launch_batch(L, a, info, bufs, nb, blocks, space, vol32, vol_exact, ev_read if side_tail else None)
     else:
         rc = L.mmx_detect_batch(ctypes.byref(a), ctypes.byref(info))
@@ -839,7 +1114,7 @@ def _enqueue_detect(dvol, lane: "Lane", origins, shapes, bufs: _Buffers, which: 
         bufs.ws_free[ws_i] = ev_read
     return _Batch(lane=lane, origins=origins, shapes=shapes, blocks=blocks, d_blocks=d_blocks, nb=nb, ns=ns, n_vox=n_vox,
                   cap=cap, which=which, done=ev_done, store_f32=store_f32, vol_exact=vol_exact, eps=eps, exact=exact,
-                  native=native)
+                  native=native, split=split, parents=parents, d_parents=d_parents, d_parts=d_parts, n_part_vox=n_part_vox)
 
 
 def _launch_batch(L, a, info, bufs: _Buffers, nb: int, blocks, space, vol32, vol_exact, ev_read) -> int:
@@ -911,9 +1186,11 @@ def _redo(batch: _Batch, dvol, bufs: _Buffers, *, cap: Optional[int], eps: float
     pipeline has reused the workspace, so the passes run again.  The main stream is synchronised first; the batch then
     goes up without its prepared block table (``prepared=None``: no side tail, workspace 0, everything in stream order
     on the main stream) and with ``buffer_free=False`` (preprocessing on the main stream too).  It keeps its slot
-    ``which``, its ``indices`` and its count of ``retries``, and is never offered to a ``finisher``."""
+    ``which``, its ``indices`` and its count of ``retries``, and is never offered to a ``finisher``.  A block in parts
+    is nominated again whole: all its parts, the same split."""
     torch.cuda.current_stream().synchronize()
-    again = _enqueue_detect(dvol, batch.lane, batch.origins, batch.shapes, bufs, batch.which, cap=cap, eps=eps, exact=exact)
+    again = _enqueue_detect(dvol, batch.lane, batch.origins, batch.shapes, bufs, batch.which, cap=cap, eps=eps, exact=exact,
+                            split=batch.split)
     again.indices, again.retries = batch.indices, batch.retries
     return _finish_detect(again, dvol, bufs)
 
@@ -929,10 +1206,13 @@ def _finish_detect(batch: _Batch, dvol, bufs: _Buffers, finisher=None):
     words = bufs.host_counts[which].numpy().view(np.uint32)
     count = int(words[0])
     n_cands = int(words[1]) if native else count
-    if native and n_cands >= batch.n_vox * ns:
+    # (a block in parts: the count is that of the folded table -- at most the block's voxels -- unless the table
+    #  overflowed before the fold, which then left the parts' count alone)
+    cube = (batch.n_vox if (batch.split is None or n_cands <= cap) else batch.n_part_vox) * ns
+    if native and n_cands >= cube:
         count = n_cands = 0                 # constant cubes (below)
     if count > cap:
-        if count >= batch.n_vox * ns and not native:
+        if count >= cube and not native:
             # every voxel of every block "equals its maximum": only possible for constant
             # cubes, which scikit-image treats as having no peaks (peak.py:41-43)
             count = 0
@@ -947,24 +1227,28 @@ def _finish_detect(batch: _Batch, dvol, bufs: _Buffers, finisher=None):
                     cands = bufs.host_table(which).numpy()[:count * nat.CAND_DTYPE.itemsize].view(nat.CAND_DTYPE)
                 else:
                     cands = table[:count * nat.CAND_DTYPE.itemsize].cpu().numpy().view(nat.CAND_DTYPE)
-                if finisher is not None and finisher(batch.indices, cands, n_cands, batch.blocks, space, thr, eps,
-                                                     lane.overlap, stats):
+                # (mmx_host_finish_stack takes whole stacks of ordinary blocks: never a block in parts)
+                if finisher is not None and batch.split is None and finisher(batch.indices, cands, n_cands, batch.blocks,
+                                                                             space, thr, eps, lane.overlap, stats):
                     stats.n_blocks += batch.nb
                     stats.n_voxels += batch.n_vox
+                    stats.n_part_voxels += batch.n_part_vox
                     stats.n_candidates += n_cands
                     return _FINISHED
-                out = _resolve_peaks_native(cands, n_cands, batch.blocks, ns, thr, stats, eps)
+                out = _resolve_peaks_native(cands, n_cands, batch.table_blocks, ns, thr, stats, eps)
             else:
                 cands = (table[:count * nat.CAND_DTYPE.itemsize].cpu().numpy().view(nat.CAND_DTYPE)
                          if count else np.zeros(0, dtype=nat.CAND_DTYPE))
-                out = _resolve_peaks(cands, batch.blocks, batch.shapes, ns, thr, dvol, batch.vol_exact, batch.d_blocks,
+                out = _resolve_peaks(cands, batch.table_blocks, batch.shapes, ns, thr, dvol, batch.vol_exact,
+                                     batch.d_table_blocks,
                                      lane.d_w0, lane.d_w2, space, batch.store_f32, stats, eps, batch.exact)
         except _BandTooNarrow as exc:
             out = None
             err = exc.err
         if out is not None:
-            stats.n_blocks += batch.nb
+            stats.n_blocks += len(batch.shapes)
             stats.n_voxels += batch.n_vox
+            stats.n_part_voxels += batch.n_part_vox
             stats.n_candidates += n_cands
             return out
     # the float32 values were further from the exact ones than the band allows: nominate this batch again

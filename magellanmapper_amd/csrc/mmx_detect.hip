@@ -5,8 +5,9 @@
 //   mmx_log_scales_f32 : the voxel copy of the tiled path and (Z+X, Y) per sigma -- which kernel path, which tiles,
 //                        when the copy is trusted, one NMS entry layout for all scales (the rules: include/mmx.h);
 //                        mmx_tiles_q16 is the tile choice, shared with the per-call MMX_ZX_AUTO of mmx_log_batch_f32
-//   mmx_detect_batch   : that, then the tail -- counter reset, sparse NMS, probe expansion, exact float64 re-score,
-//                        the copies of the counters and of the table's head to pinned host memory, the events
+//   mmx_detect_batch   : that, then the tail -- counter reset, sparse NMS, (for a batch of parts: the fold into their
+//                        parent blocks, mmx_parts.hip,) probe expansion, exact float64 re-score, the copies of the
+//                        counters and of the table's head to pinned host memory, the events
 // Everything is enqueued by native code on the caller's streams.  Nothing in it waits for the GPU.
 //
 // A batch the caller runs again and again with the same arguments (a small volume detected once per step) can be
@@ -236,6 +237,20 @@ int mmx_detect_batch(const mmx_detect_args* a, mmx_detect_info* info)
     // (the tail's own arguments, before anything is enqueued)
     if (!a->d_cands || !a->d_count || a->cap < 1) return MMX_ERR_ARG;
     if (a->exact && (!a->vol_exact || !a->d_w0 || !a->d_w2)) return MMX_ERR_ARG;
+    // a batch of parts: the parts table and the parents' table come together, and every parent is a block the re-score
+    // may read whole (its extents are what the exact values reflect at)
+    const bool parts = a->n_parts != 0 || a->d_parts || a->n_parents != 0 || a->d_parents || a->h_parents;
+    if (parts) {
+        if (!a->d_parts || !a->d_parents || !a->h_parents || a->n_parts != a->n_blocks || a->n_parents < 1 ||
+            a->n_parents > a->n_parts)
+            return MMX_ERR_ARG;
+        for (int i = 0; i < a->n_parents; ++i)
+            if (a->h_parents[i].nz < 1 || a->h_parents[i].ny < 1 || a->h_parents[i].nx < 1 || a->h_parents[i].slot != i)
+                return MMX_ERR_ARG;
+    }
+    // (after the fold the table speaks of the parents: they are the blocks of everything behind it)
+    const mmx_block* d_tail_blocks = parts ? a->d_parents : a->d_blocks;
+    const int n_tail_blocks = parts ? a->n_parents : a->n_blocks;
     int rc = mmx_log_scales_f32(a, info);
     if (rc != MMX_OK) return rc;
     const int nb = a->n_blocks, ns = a->n_sigma;
@@ -255,12 +270,16 @@ int mmx_detect_batch(const mmx_detect_args* a, mmx_detect_info* info)
         r = hipEventRecord((hipEvent_t)a->ev_work_read, tail);
         if (r != hipSuccess) return fail(r, "record: workspace read");
     }
+    if (parts) {                         // candidates of the parts -> candidates of their parents (the table alone)
+        rc = mmx_fold_parts(a->d_cands, a->cap, a->d_count, a->d_parts, a->n_parts, (void*)tail);
+        if (rc != MMX_OK) return rc;
+    }
     if (a->expand) {
-        rc = mmx_expand_probes(a->d_cands, a->cap, a->d_count, a->d_count + 1, a->d_blocks, nb, ns, (void*)tail);
+        rc = mmx_expand_probes(a->d_cands, a->cap, a->d_count, a->d_count + 1, d_tail_blocks, n_tail_blocks, ns, (void*)tail);
         if (rc != MMX_OK) return rc;
     }
     if (a->exact) {
-        rc = mmx_rescore_f64(a->vol_exact, a->d_blocks, nb, a->d_cands, a->cap, a->d_count, a->d_w0, a->d_w2,
+        rc = mmx_rescore_f64(a->vol_exact, d_tail_blocks, n_tail_blocks, a->d_cands, a->cap, a->d_count, a->d_w0, a->d_w2,
                              a->h_radius, a->h_norm, ns, a->store_f32, (void*)tail);
         if (rc != MMX_OK) return rc;
     }
@@ -313,6 +332,7 @@ int mmx_detect_batch_capture(const mmx_detect_args* a, mmx_detect_info* info, vo
     hipStream_t main = (hipStream_t)a->stream;
     // (the per-kernel timing scopes record events of their own, which a capture would swallow)
     if (mmx_timing_is_enabled()) return MMX_ERR_UNSUPPORTED;
+    if (a->n_parts || a->d_parts) return MMX_ERR_UNSUPPORTED;         // (a batch of parts is launched call by call)
     hipError_t r = hipStreamBeginCapture(main, hipStreamCaptureModeThreadLocal);
     if (r != hipSuccess) return fail(r, "hipStreamBeginCapture");
     mmx_detect_args b = *a;

@@ -420,6 +420,19 @@ def detect_blobs_blocks_device(dvol, channel, origins, shapes, stats=None,
     iso_factor = None
     pre = None
     keeper = None
+    # a block too large for one workspace slot is detected as several overlapping parts (blob_log.split_oversized),
+    # which these steps around the detection do not take
+    if len(shapes) and int(bl._slot_elems(np.asarray(shapes, dtype=np.int64).reshape(-1, 3)).max()) >= bl._slot_limit():
+        way_out = "detect with a smaller segment_size"
+        if coloc:
+            raise NotImplementedError("intensity co-localisation (coloc=True) of a block that is detected in parts -- it "
+                                      f"is too large for one workspace slot -- is not supported; {way_out}")
+        if isotropic is not None:
+            raise NotImplementedError("the isotropic rescale of a block that is detected in parts -- it is too large for "
+                                      f"one workspace slot -- is not supported; {way_out}")
+        if any(getattr(config.get_roi_profile(c), "spectral_unmixing", None) for c in channels):
+            raise NotImplementedError("spectral unmixing of a block that is detected in parts -- it is too large for one "
+                                      f"workspace slot -- is not supported; {way_out}")
     if denoise_max_shape is not None:
         from . import preprocess
         pre = preprocess.Preprocessor(denoise_max_shape)
