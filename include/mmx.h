@@ -329,7 +329,8 @@ typedef struct {
 typedef struct {
     int32_t zx_path;        /* mmx_zx_mode the last scale ran */
     int32_t mask_layout;    /* 0 = the NMS read the full cube, MMX_MASK_ROWS / MMX_MASK_QUADS */
-    int32_t n_pass_rounds;  /* 1, or more when the scales had to be computed again on another path */
+    int32_t n_pass_rounds;  /* configurations the rules went through before all scales agreed on one entry layout (1 to 3);
+                               they are decided on the host: only the last one is launched */
     int32_t _pad;
     double q16_bound;       /* error bound of the 16-bit intermediates in value units (0: not used) */
 } mmx_detect_info;
@@ -340,22 +341,25 @@ const char* mmx_detect_last_error(void);
  * zx_flags; ignores the tail's fields (d_cands, d_count, cap, vol_exact, the device tables, tail_stream, the other
  * events).  Leaves d_log at d_work + 4 n_blocks slot_elems floats and the entries behind it (mmx_workspace_bytes'
  * layout) and fills `info` as mmx_detect_batch does: pass info->mask_layout on to mmx_peaks_batch.
- * THE RULES by which a batch takes its kernel path (this function is their one statement in code):
+ * THE RULES by which a batch takes its kernel path.  Their one statement in code is csrc/mmx_route.h -- pure host
+ * functions of the volume header, the block table's geometry, the radii and weights, the band and zx_mode;
+ * mmx_route_ladder decides every scale before the first launch, and this function launches what it says:
  *   - per scale: the tiled matrix-core path, else the packed-VALU kernel, else the three separate passes -- zx_mode
- *     and the geometry decide, as for mmx_log_batch_f32;
+ *     and the geometry decide, as for mmx_log_batch_f32 (mmx_route_scale);
  *   - float32 or 16-bit tiles: MMX_LOG_ABS_TOL's rule with the largest mmx_tiled_q16_error_bound over the scales;
- *   - the voxel copy of the tiled path is made once per round and trusted (MMX_ZX_PREPACKED) only while every scale
- *     so far ran the tiled path: any other path uses that part of d_work for something else;
+ *   - the voxel copy of the tiled path is made once and trusted (MMX_ZX_PREPACKED) only while every scale so far ran
+ *     the tiled path: any other path uses that part of d_work for something else;
  *   - with entries the Y pass leaves whole segments of the cube unwritten, so it is all scales in one entry layout or
- *     none: when the scales disagree (a radius outside the fused kernels, tiny blocks) every scale is computed again
- *     -- with MMX_ZX_PACKED when the layouts were rows and quads mixed, then without entries if they still differ
- *     (info->n_pass_rounds: 1 to 3);
+ *     none: when the scales would disagree (a radius outside the fused kernels, tiny blocks) the rules go on to the
+ *     next configuration -- MMX_ZX_PACKED when the layouts were rows and quads mixed, then no entries
+ *     (info->n_pass_rounds counts the configurations gone through, 1 to 3; only the one settled on is launched);
  *   - under MMX_ZX_AUTO a ladder that holds a radius above MMX_MAX_RADIUS_FAST which the wide passes accept is laid out
- *     BEFORE the first launch, so that there is one round: radii above MMX_MAX_RADIUS_FAST go MMX_ZX_WIDE, the others
- *     MMX_ZX_PACKED where the fused path takes them on this geometry and MMX_ZX_WIDE where it does not (rows wider than
- *     its limit), all with row entries; if any scale would end without entries (a radius above MMX_MAX_RADIUS_WIDE,
- *     entries that do not fit) the one round runs without entries from the start.  Ladders without such a radius run
- *     the rounds above unchanged. */
+ *     first: radii above MMX_MAX_RADIUS_FAST go MMX_ZX_WIDE, the others MMX_ZX_PACKED where the fused path takes them on
+ *     this geometry and MMX_ZX_WIDE where it does not (rows wider than its limit), all with row entries; if any scale
+ *     would end without entries (a radius above MMX_MAX_RADIUS_WIDE, entries that do not fit) the ladder has none
+ *     from the start.
+ * A launcher that refuses what its route accepted ends the call with MMX_ERR_UNSUPPORTED -- no other path is tried --
+ * and mmx_detect_last_error names it. */
 int mmx_log_scales_f32(const mmx_detect_args* args, mmx_detect_info* info);
 /* the same launches captured as a hipGraph (every argument frozen; refused with MMX_ERR_UNSUPPORTED while per-kernel
  * timing is on: its events cannot live inside a capture) and replayed with one launch on `stream` */

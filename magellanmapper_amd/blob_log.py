@@ -52,7 +52,7 @@ EPS_REL = float(os.environ.get("MMX_EPS_REL", 2e-5))
 EPS_REL_Q16 = float(os.environ.get("MMX_EPS_REL_Q16", 2.5e-4))
 #: the rounding error of the 16-bit intermediates, relative to the value range, for kernel radii >= 4 (sigma >= 0.875;
 #: largest at radius 5: 2.97e-5 -- swept over sigma in tests/test_host_logic.py; rounds 3-5 carried 5.3e-5: Q was
-#: quantised over twice the range it can take, see ``q16_bounds`` in csrc/mmx_api.hip).  Per call the library states the
+#: quantised over twice the range it can take, see ``mmx_q16_bounds`` in csrc/mmx_route.h).  Per call the library states the
 #: bound of the sigmas at hand (``mmx_tiled_q16_error_bound``); the kernels of radius 1..3 carry up to 5.4e-5.
 Q16_BOUND_ANY_SIGMA = 3.0e-5
 #: ``MMX_LOG_ABS_TOL`` of include/mmx.h: the LoG contract in value units (BASELINE.json: "LoG response within 1e-4")

@@ -45,9 +45,6 @@ int hip_fail(hipError_t e, const char* what)
     snprintf(g_hip_err, sizeof g_hip_err, "%s: %s", what, hipGetErrorString(e));
     return MMX_ERR_HIP;
 }
-
-// The register-ring column kernels prefetch kPrefetch (= 4) steps ahead and reflect once.
-constexpr int kColPrefetch = MMX_COL_PREFETCH;
 }  // namespace
 
 void mmx_time_begin(int kind, hipStream_t s)
@@ -150,53 +147,9 @@ int mmx_device_count(void)
     return ok;
 }
 
-// Q16 tiles (MMX_ZX_TILED_Q16): P in [0, BP] as unorm16, Q in [-BQ, BQ] as snorm16.  For voxels in [0, 1] (integer
-// types after img_as_float) the bounds follow from the weights alone.  |P| <= (sum w0)^2.  Q = sum K I with the 2-D
-// kernel K(i, j) = w2(i) w0(j) + w0(i) w2(j) and every voxel I in [0, 1], so Q lies in [-sum of K's negative taps, sum of
-// its positive taps] -- about HALF of sum|K| <= 2 sum|w2| sum w0 either way, a second-derivative kernel summing to ~0
-// (round 6: BQ is that, the larger of the two one-sided sums; rounds 3-5 quantised Q over the two-sided 2 sum|w2| sum w0
-// and carried twice the rounding error for it).  Folding reflected taps at a block face only merges weights, which
-// can only shrink both one-sided sums.  The error the rounding leaves in the LoG value follows likewise:
-//   norm (sum|w2| BP / 65535 + sum w0 BQ / 32767) / 2,
-// i.e. 2.2e-5 whatever sigma (sum|w2| ~ 0.97 / sigma^2), plus the float32 arithmetic's own few 1e-7, the product
-// term the 16-bit kernel leaves out (0.55e-5) and the rounding of its X accumulators, which run with the voxel
-// pieces' exponent offsets still in them (values up to 8 instead of 1: four roundings of 2^-22 each, 0.2e-5):
-// 3.0e-5; the Y pass on the matrix cores (mmx_ymfma.hip) leaves out its own low x low product -- low byte of a count x
-// (weight - float16(weight)): 255 x 2^-12 = 0.062 counts per unit of weight against the 0.5 of the rounding -- which adds an
-// eighth: 3.3e-5 in all (5.1e-5 with the two-sided BQ).
-static void q16_bounds(const double* w0, const double* w2, int radius, double norm, double* bp, double* bq, double* err)
-{
-    double s0 = w0[0], s2 = fabs(w2[0]);
-    for (int k = 1; k <= radius; ++k) { s0 += 2.0 * w0[k]; s2 += 2.0 * fabs(w2[k]); }
-    *bp = s0 * s0 * (1.0 + 1e-6);
-    // one-sided sums of K over its (2 R + 1)^2 taps (K is symmetric in both indices: a quadrant, weighted)
-    double pos = 0.0, neg = 0.0;
-    for (int i = 0; i <= radius; ++i)
-        for (int j = 0; j <= radius; ++j) {
-            const double k = (w2[i] * w0[j] + w0[i] * w2[j]) * ((i ? 2.0 : 1.0) * (j ? 2.0 : 1.0));
-            if (k > 0.0) pos += k; else neg -= k;
-        }
-    // (1e-4 of slack: the kernel's own float32 / split-float16 arithmetic may land a hair beyond the exact extreme, and
-    //  a value beyond BQ would clamp)
-    *bq = (pos > neg ? pos : neg) * (1.0 + 1e-4);
-    // ... plus what the 16-bit kernel drops in the X pass (low voxel byte x low weight piece: 255 / 65536 x 2^-11 per
-    // unit of weight): P off by 1.9e-6 s0^2, Q by 1.9e-6 x 2 s2 s0
-    const double drop = 255.0 / 65536.0 / 2048.0;
-    // ... and the float32 rounding of X accumulators that carry the pieces' offsets (<= 8: ulp 2^-21, half of it per
-    // MFMA, four MFMAs into each; relative to the bounds, the fragments carry 1 / bound)
-    const double biased = 4.0 * 0x1p-22;
-    // ... and the Y pass's dropped product, in counts of P and of Q
-    const double ydrop = 255.0 / 4096.0;
-    *err = norm * (s2 * (*bp / 65535.0 * (0.5 + ydrop) + drop * s0 * s0 + biased * *bp) +
-                   s0 * (*bq / 32767.0 * (0.5 + ydrop) + drop * 2.0 * s2 * s0 + biased * *bq)) + 1e-6;
-}
-
 double mmx_tiled_q16_error_bound(const double* h_w0, const double* h_w2, int radius, double norm)
 {
-    if (!h_w0 || !h_w2 || radius < 0 || radius > MMX_MAX_RADIUS_GENERIC) return -1.0;
-    double bp, bq, err;
-    q16_bounds(h_w0, h_w2, radius, norm, &bp, &bq, &err);
-    return err;
+    return mmx_q16_error_bound(h_w0, h_w2, radius, norm);      // (mmx_route.h, with the bounds it follows from)
 }
 
 }  // extern "C"
@@ -273,101 +226,72 @@ mmx_taps_f32 taps(const float* a, const float* b, int radius)
     return t;
 }
 
-// The argument checks of mmx_log_batch_f32, everything but the blocks; takes the flags off c->zx_mode.
-int check_log_args(mmx_log_call* c, bool* y_valu, bool* prepacked)
+// A launcher's status where a route sent the call: a refusal means the launcher disagrees with mmx_route.h.
+int launched(int rc, const char* launcher, const char* what)
 {
-    *y_valu = c->zx_mode >= 0 && (c->zx_mode & MMX_ZX_Y_VALU);
-    if (*y_valu) c->zx_mode &= ~MMX_ZX_Y_VALU;
-    *prepacked = c->zx_mode == (MMX_ZX_TILED | MMX_ZX_PREPACKED) || c->zx_mode == (MMX_ZX_TILED_Q16 | MMX_ZX_PREPACKED);
-    if (*prepacked) c->zx_mode &= ~MMX_ZX_PREPACKED;
-    if (c->zx_mode < MMX_ZX_AUTO || c->zx_mode > MMX_ZX_WIDE || c->zx_mode == 1 || (c->zx_mode >= 3 && c->zx_mode <= 5))
-        return MMX_ERR_ARG;             // (3, 4, 5: retired experiment kernels)
-    if (!c->vol || !c->vol->d_data || !c->d_blocks || !c->h_blocks || !c->h_w0 || !c->h_w2 || !c->d_log || !c->d_work)
-        return MMX_ERR_ARG;
-    if (c->n_blocks < 1 || c->radius < 0 || c->slot_elems < 1) return MMX_ERR_ARG;
-    if (c->n_blocks > MMX_MAX_BLOCKS) return MMX_ERR_UNSUPPORTED;
-    if (c->radius > MMX_MAX_RADIUS_GENERIC) return MMX_ERR_UNSUPPORTED;
-    if (c->slot_elems >= (int64_t(1) << 29)) return MMX_ERR_UNSUPPORTED;  // 32-bit byte offsets in a slot
-    if (c->slot_elems % MMX_ROW_ALIGN) return MMX_ERR_ARG;
-    if (c->vol->dtype != MMX_U8 && c->vol->dtype != MMX_U16 && c->vol->dtype != MMX_F32)
-        return MMX_ERR_UNSUPPORTED;     // float64 volumes: pass a float32 copy
-    return MMX_OK;
+    if (rc == MMX_ERR_HIP) return hip_fail(hipGetLastError(), what);
+    if (rc == MMX_ERR_UNSUPPORTED) {
+        char msg[128];
+        snprintf(msg, sizeof msg, "%s refused a call its route accepted", launcher);
+        mmx_detect_set_error(msg);
+    }
+    return rc;
 }
 
-// Fused path: Z and X in one kernel (Gz / Gzz never touch HBM), then Y.  MMX_ERR_UNSUPPORTED: not for this geometry
-// (or this mode) -- the separate passes take the call.
-int fused_passes(const mmx_log_call& c, bool y_valu, bool prepacked, const mmx_batch_geom& g, const pass_weights& w)
+// a timed scope, or none (kind < 0)
+struct pass_scope {
+    int kind; hipStream_t s;
+    pass_scope(int k, hipStream_t st) : kind(k), s(st) { if (k >= 0) mmx_time_begin(k, st); }
+    ~pass_scope() { if (kind >= 0) mmx_time_end(kind, s); }
+};
+
+// Fused path: Z and X in one kernel (Gz / Gzz never touch HBM), then Y -- the tiled matrix-core kernels on the voxel
+// copy (made here unless the route trusts the batch's), or the packed-VALU kernel.
+int fused_passes(const mmx_log_call& c, const mmx_route& r, const mmx_batch_geom& g, const pass_weights& w)
 {
     const mmx_volume* vol = c.vol;
     const int radius = c.radius, n_blocks = c.n_blocks;
     const int64_t slot_elems = c.slot_elems;
     hipStream_t s = c.stream;
-    if (c.zx_mode == MMX_ZX_SEPARATE || !mmx_fused_accepts(vol, g, radius)) return MMX_ERR_UNSUPPORTED;
     float* t0 = c.d_work;                                   // P
     float* t1 = c.d_work + (int64_t)n_blocks * slot_elems;  // Q
     mmx_taps_f32 tzz = taps(w.z0, w.z2, radius), txx = taps(w.y0, w.y2, radius), tyy = taps(w.x0, w.x2, radius);
-    int rc, path = MMX_ZX_PACKED;
-    // AUTO = the tiled matrix-core path for integer voxels, else the packed-VALU kernel.
-    // float32 or 16-bit tiles: mmx_tiles_q16, from this call's sigma and whether it wants entries
-    double q_bp = 0, q_bq = 0, q_err = 0, vscale = 0;
-    q16_bounds(c.h_w0, c.h_w2, radius, c.norm, &q_bp, &q_bq, &q_err);
-    // float voxels: the tiled path when the volume states its value range (or when asked for by name: the float16
-    // pieces of its copy cover |v| < 65504), 16-bit tiles when that range is [0, m]: their bounds scale with m
-    const bool integer = vol->dtype == MMX_U8 || vol->dtype == MMX_U16;
-    const bool ranged = vol->dtype == MMX_F32 && vol->value_range != 0.f && fabsf(vol->value_range) < 60000.f;
-    const bool wants_entries = c.d_nms_mask && c.h_mask_written;
-    const bool q16 = mmx_tiles_q16(c.zx_mode, vol, q_err, c.nms_eps, wants_entries, &vscale);
-    const bool nonneg = vscale > 0.0;
-    if (q16) { q_bp *= vscale; q_bq *= vscale; }
-    bool tiled = (c.zx_mode == MMX_ZX_TILED || (c.zx_mode == MMX_ZX_TILED_Q16 && nonneg) ||
-                  (c.zx_mode == MMX_ZX_AUTO && (integer || ranged))) && g.plan_status == MMX_OK;
+    const bool tiled = r.family == MMX_ROUTE_TILED;
     const mmx_zx6_plan& plan = g.plan;
-    if (tiled && !prepacked) {
+    int rc;
+    if (r.makes_copy) {
         mmx_timed_scope ts(MMX_K_ZXPACK, s);
         rc = mmx_launch_zx6_pack(vol, c.d_blocks, c.h_blocks, n_blocks, plan, c.d_work, s);
-        if (rc == MMX_ERR_HIP) return hip_fail(hipGetLastError(), "voxel copy of the tiled path");
-        tiled = rc == MMX_OK;
+        if (rc != MMX_OK) return launched(rc, "mmx_launch_zx6_pack", "voxel copy of the tiled path");
     }
     { mmx_timed_scope ts(MMX_K_ZX, s);
-      rc = MMX_ERR_UNSUPPORTED;
-      if (tiled) {
-          path = q16 ? MMX_ZX_TILED_Q16 : MMX_ZX_TILED;
+      if (tiled)
           rc = mmx_launch_zx6(vol, c.d_blocks, c.h_blocks, n_blocks, plan, txx, radius, c.d_work,
-                              q16 ? (float)(1.0 / q_bp) : 0.f, q16 ? (float)(1.0 / q_bq) : 0.f, s);
-          tiled = rc == MMX_OK;
-      }
-      if (rc == MMX_ERR_UNSUPPORTED) {
-          path = MMX_ZX_PACKED;
-          rc = mmx_launch_zx2(vol, c.d_blocks, n_blocks, g.max_ny, g.max_px, slot_elems, tzz, txx, radius, t0, t1, s);
-      } }
-    if (rc == MMX_OK && c.h_zx_path) *c.h_zx_path = path;
-    if (rc == MMX_OK) {
-        mmx_timed_scope ts(MMX_K_Y2, s);
-        const bool want_mask = wants_entries && (tiled ? g.quads_fit : g.rows_fit);    // (`tiled`: the kernel that ran)
-        unsigned long long* d_mask = want_mask ? (unsigned long long*)c.d_nms_mask : nullptr;
-        rc = MMX_ERR_UNSUPPORTED;
-        if (tiled && q16 && !y_valu)
-            rc = mmx_launch_ym(c.d_blocks, n_blocks, plan, slot_elems, tyy, radius, c.d_work,
-                               (float)(q_bp / 65535.0), (float)(q_bq / 32767.0), c.d_log, d_mask, c.nms_lo, c.nms_eps, s);
-        if (rc != MMX_ERR_UNSUPPORTED) ;
-        else if (tiled)
-            rc = mmx_launch_y6(c.d_blocks, n_blocks, plan, slot_elems, tyy, radius, c.d_work,
-                               reinterpret_cast<const float*>(reinterpret_cast<const char*>(c.d_work) + plan.q_off),
-                               q16 ? (float)(q_bp / 65535.0) : 0.f, q16 ? (float)(q_bq / 32767.0) : 0.f, c.d_log,
-                               d_mask, c.nms_lo, c.nms_eps, s);
-        else
-            rc = mmx_launch_y2(c.d_blocks, n_blocks, g.max_ycols, slot_elems, tyy, radius, t0, t1, c.d_log,
-                               d_mask, c.nms_lo, c.nms_eps, s);
-        if (rc == MMX_OK && want_mask) *c.h_mask_written = tiled ? MMX_MASK_QUADS : MMX_MASK_ROWS;
-    }
-    return rc == MMX_ERR_HIP ? hip_fail(hipGetLastError(), "fused passes") : rc;
+                              r.q16 ? (float)(1.0 / r.bp) : 0.f, r.q16 ? (float)(1.0 / r.bq) : 0.f, s);
+      else
+          rc = mmx_launch_zx2(vol, c.d_blocks, n_blocks, g.max_ny, g.max_px, slot_elems, tzz, txx, radius, t0, t1, s); }
+    if (rc != MMX_OK) return launched(rc, tiled ? "mmx_launch_zx6" : "mmx_launch_zx2", "fused passes");
+    { mmx_timed_scope ts(MMX_K_Y2, s);
+      unsigned long long* d_mask = r.layout ? (unsigned long long*)c.d_nms_mask : nullptr;
+      const float cp = r.q16 ? (float)(r.bp / 65535.0) : 0.f, cq = r.q16 ? (float)(r.bq / 32767.0) : 0.f;
+      if (r.y_kernel == MMX_Y_YM)
+          rc = mmx_launch_ym(c.d_blocks, n_blocks, plan, slot_elems, tyy, radius, c.d_work, cp, cq, c.d_log, d_mask,
+                             c.nms_lo, c.nms_eps, s);
+      else if (r.y_kernel == MMX_Y_Y6)
+          rc = mmx_launch_y6(c.d_blocks, n_blocks, plan, slot_elems, tyy, radius, c.d_work,
+                             reinterpret_cast<const float*>(reinterpret_cast<const char*>(c.d_work) + plan.q_off), cp, cq,
+                             c.d_log, d_mask, c.nms_lo, c.nms_eps, s);
+      else
+          rc = mmx_launch_y2(c.d_blocks, n_blocks, g.max_ycols, slot_elems, tyy, radius, t0, t1, c.d_log, d_mask, c.nms_lo,
+                             c.nms_eps, s); }
+    return launched(rc, r.y_kernel == MMX_Y_YM ? "mmx_launch_ym" : (r.y_kernel == MMX_Y_Y6 ? "mmx_launch_y6" : "mmx_launch_y2"),
+                    "fused passes");
 }
 
 // The wide passes (mmx_wide.hip): Z, X, Y on LDS-staged tiles, radius 1 .. MMX_MAX_RADIUS_WIDE, row entries from the Y
-// pass.  MMX_ERR_UNSUPPORTED: not for this geometry -- the call goes on to the paths it took before there was this one.
-int wide_passes(const mmx_log_call& c, const mmx_batch_geom& g, const pass_weights& w)
+// pass.
+int wide_passes(const mmx_log_call& c, const mmx_route& r, const pass_weights& w)
 {
-    if (!mmx_wide_accepts(c.vol, g, c.radius)) return MMX_ERR_UNSUPPORTED;
     const int radius = c.radius, n_blocks = c.n_blocks;
     const int64_t slot_elems = c.slot_elems;
     hipStream_t s = c.stream;
@@ -375,8 +299,7 @@ int wide_passes(const mmx_log_call& c, const mmx_batch_geom& g, const pass_weigh
     float* t1 = t0 + (int64_t)n_blocks * slot_elems;        // Q
     float* t2 = t1 + (int64_t)n_blocks * slot_elems;        // Gz
     float* t3 = t2 + (int64_t)n_blocks * slot_elems;        // Gzz
-    const bool want_mask = c.d_nms_mask && c.h_mask_written && g.rows_fit;
-    unsigned long long* d_mask = want_mask ? (unsigned long long*)c.d_nms_mask : nullptr;
+    unsigned long long* d_mask = r.layout ? (unsigned long long*)c.d_nms_mask : nullptr;
     int rc;
     { mmx_timed_scope ts(MMX_K_WIDE, s);
       rc = mmx_launch_wide_pass(0, c.vol, c.d_blocks, c.h_blocks, n_blocks, slot_elems, w.z0, w.z2, radius, nullptr, nullptr,
@@ -391,67 +314,82 @@ int wide_passes(const mmx_log_call& c, const mmx_batch_geom& g, const pass_weigh
         rc = mmx_launch_wide_pass(2, c.vol, c.d_blocks, c.h_blocks, n_blocks, slot_elems, w.x0, w.x2, radius, t0, t1, c.d_log,
                                   nullptr, d_mask, c.nms_lo, c.nms_eps, s);
     }
-    if (rc == MMX_OK) {
-        if (c.h_zx_path) *c.h_zx_path = MMX_ZX_WIDE;
-        if (want_mask) *c.h_mask_written = MMX_MASK_ROWS;
-    }
-    return rc == MMX_ERR_HIP ? hip_fail(hipGetLastError(), "wide passes") : rc;
+    return launched(rc, "mmx_launch_wide_pass", "wide passes");
 }
 
-// The three separate passes: per pass the register-ring kernel where the geometry allows it, else the generic one.
-int separate_passes(const mmx_log_call& c, const mmx_batch_geom& g, const pass_weights& w)
+// The three separate passes, Z, Y, X: per pass the register-ring kernel (ring_*) or the generic one.  `timed`: under the
+// timing scopes of their families.
+int three_passes(const mmx_volume* vol, const mmx_block* d_blocks, int n_blocks, int64_t slot_elems, int radius,
+                 float* d_work, float* d_log, const mmx_batch_geom& g, const pass_weights& w, bool ring_z, bool ring_y,
+                 bool ring_x, bool timed, hipStream_t s)
 {
-    const mmx_volume* vol = c.vol;
-    const int radius = c.radius, n_blocks = c.n_blocks;
-    const int64_t slot_elems = c.slot_elems;
-    hipStream_t s = c.stream;
-    float* t0 = c.d_work;                                   // Gz
+    float* t0 = d_work;                                     // Gz
     float* t1 = t0 + (int64_t)n_blocks * slot_elems;        // Gzz
     float* t2 = t1 + (int64_t)n_blocks * slot_elems;        // A
     float* t3 = t2 + (int64_t)n_blocks * slot_elems;        // BC
-    const bool fast_r = radius >= 1 && radius <= MMX_MAX_RADIUS_FAST;
-    const bool lane_ok = g.max_lane_in * 8 < (int64_t(1) << 31);
-    const bool fast_z = fast_r && lane_ok && g.min_nz >= radius + kColPrefetch && vol->stride_y < (1 << 30);
-    const bool fast_y = fast_r && g.min_ny >= radius + kColPrefetch;
-    const bool fast_x = fast_r && g.min_nx >= radius;
     int rc;
-    { mmx_timed_scope ts(fast_z ? MMX_K_ZPASS : MMX_K_GENERIC, s);
-    if (fast_z) rc = mmx_launch_zpass(vol, c.d_blocks, n_blocks, g.max_zcols, slot_elems, taps(w.z0, w.z2, radius), radius, t0, t1, s);
-    else rc = mmx_launch_generic_pass(0, vol, c.d_blocks, n_blocks, g.max_vox, slot_elems, w.z0, w.z2, radius, nullptr, nullptr, t0, t1, s); }
-    if (rc != MMX_OK) return rc == MMX_ERR_HIP ? hip_fail(hipGetLastError(), "z pass") : rc;
-    { mmx_timed_scope ts(fast_y ? MMX_K_YPASS : MMX_K_GENERIC, s);
-    if (fast_y) rc = mmx_launch_ypass(c.d_blocks, n_blocks, g.max_ycols, slot_elems, taps(w.y0, w.y2, radius), radius, t0, t1, t2, t3, s);
-    else rc = mmx_launch_generic_pass(1, vol, c.d_blocks, n_blocks, g.max_vox, slot_elems, w.y0, w.y2, radius, t0, t1, t2, t3, s); }
-    if (rc != MMX_OK) return rc == MMX_ERR_HIP ? hip_fail(hipGetLastError(), "y pass") : rc;
-    { mmx_timed_scope ts(fast_x ? MMX_K_XPASS : MMX_K_GENERIC, s);
-    if (fast_x) rc = mmx_launch_xpass(c.d_blocks, n_blocks, g.max_rows, g.max_nx, slot_elems, taps(w.x0, w.x2, radius), radius, t2, t3, c.d_log, s);
-    else rc = mmx_launch_generic_pass(2, vol, c.d_blocks, n_blocks, g.max_vox, slot_elems, w.x0, w.x2, radius, t2, t3, c.d_log, nullptr, s); }
-    if (rc != MMX_OK) return rc == MMX_ERR_HIP ? hip_fail(hipGetLastError(), "x pass") : rc;
-    return MMX_OK;
+    { pass_scope ts(!timed ? -1 : (ring_z ? MMX_K_ZPASS : MMX_K_GENERIC), s);
+    if (ring_z) rc = mmx_launch_zpass(vol, d_blocks, n_blocks, g.max_zcols, slot_elems, taps(w.z0, w.z2, radius), radius, t0, t1, s);
+    else rc = mmx_launch_generic_pass(0, vol, d_blocks, n_blocks, g.max_vox, slot_elems, w.z0, w.z2, radius, nullptr, nullptr, t0, t1, s); }
+    if (rc != MMX_OK) return launched(rc, ring_z ? "mmx_launch_zpass" : "mmx_launch_generic_pass", "z pass");
+    { pass_scope ts(!timed ? -1 : (ring_y ? MMX_K_YPASS : MMX_K_GENERIC), s);
+    if (ring_y) rc = mmx_launch_ypass(d_blocks, n_blocks, g.max_ycols, slot_elems, taps(w.y0, w.y2, radius), radius, t0, t1, t2, t3, s);
+    else rc = mmx_launch_generic_pass(1, vol, d_blocks, n_blocks, g.max_vox, slot_elems, w.y0, w.y2, radius, t0, t1, t2, t3, s); }
+    if (rc != MMX_OK) return launched(rc, ring_y ? "mmx_launch_ypass" : "mmx_launch_generic_pass", "y pass");
+    { pass_scope ts(!timed ? -1 : (ring_x ? MMX_K_XPASS : MMX_K_GENERIC), s);
+    if (ring_x) rc = mmx_launch_xpass(d_blocks, n_blocks, g.max_rows, g.max_nx, slot_elems, taps(w.x0, w.x2, radius), radius, t2, t3, d_log, s);
+    else rc = mmx_launch_generic_pass(2, vol, d_blocks, n_blocks, g.max_vox, slot_elems, w.x0, w.x2, radius, t2, t3, d_log, nullptr, s); }
+    return launched(rc, ring_x ? "mmx_launch_xpass" : "mmx_launch_generic_pass", "x pass");
 }
 
 }  // namespace
 
-int mmx_log_scale_f32(const mmx_log_call& call, const mmx_batch_geom& g)
+// The argument checks of mmx_log_batch_f32, everything but the blocks (the mode: the route's parsing).
+int mmx_log_scale_check(const mmx_log_call& c)
 {
-    mmx_log_call c = call;
-    if (c.h_mask_written) *c.h_mask_written = 0;
-    if (c.h_zx_path) *c.h_zx_path = MMX_ZX_SEPARATE;
-    bool y_valu, prepacked;
-    int rc = check_log_args(&c, &y_valu, &prepacked);
-    if (rc != MMX_OK) return rc;
-    if (g.status != MMX_OK) return g.status;
+    mmx_zx_request q;
+    if (mmx_zx_parse(c.zx_mode, &q) != MMX_OK) return MMX_ERR_ARG;
+    if (!c.vol || !c.vol->d_data || !c.d_blocks || !c.h_blocks || !c.h_w0 || !c.h_w2 || !c.d_log || !c.d_work)
+        return MMX_ERR_ARG;
+    if (c.n_blocks < 1 || c.radius < 0 || c.slot_elems < 1) return MMX_ERR_ARG;
+    if (c.n_blocks > MMX_MAX_BLOCKS) return MMX_ERR_UNSUPPORTED;
+    if (c.radius > MMX_MAX_RADIUS_GENERIC) return MMX_ERR_UNSUPPORTED;
+    if (c.slot_elems >= (int64_t(1) << 29)) return MMX_ERR_UNSUPPORTED;  // 32-bit byte offsets in a slot
+    if (c.slot_elems % MMX_ROW_ALIGN) return MMX_ERR_ARG;
+    if (!mmx_voxels_ok(c.vol)) return MMX_ERR_UNSUPPORTED;     // float64 volumes: pass a float32 copy
+    return MMX_OK;
+}
+
+// One scale, launched as its route says: nothing is decided here.
+int mmx_log_scale_run(const mmx_log_call& c, const mmx_batch_geom& g, const mmx_route& r)
+{
     pass_weights w;
     make_weights(c.vol, c.h_w0, c.h_w2, c.radius, c.norm, &w);
-    // the wide passes: by name at any radius they take, under AUTO above the register-resident radii
-    if (c.zx_mode == MMX_ZX_WIDE || (c.zx_mode == MMX_ZX_AUTO && c.radius > MMX_MAX_RADIUS_FAST)) {
-        rc = wide_passes(c, g, w);
-        if (rc != MMX_ERR_UNSUPPORTED) return rc;
-    }
-    rc = fused_passes(c, y_valu, prepacked, g, w);
-    if (rc != MMX_ERR_UNSUPPORTED) return rc;       // (unsupported geometry: the separate passes)
-    return separate_passes(c, g, w);
+    int rc;
+    if (r.family == MMX_ROUTE_WIDE) rc = wide_passes(c, r, w);
+    else if (r.family == MMX_ROUTE_SEPARATE)
+        rc = three_passes(c.vol, c.d_blocks, c.n_blocks, c.slot_elems, c.radius, c.d_work, c.d_log, g, w, r.ring_z, r.ring_y,
+                          r.ring_x, true, c.stream);
+    else rc = fused_passes(c, r, g, w);
+    if (rc != MMX_OK) return rc;
+    if (c.h_zx_path) *c.h_zx_path = r.path;
+    if (c.h_mask_written) *c.h_mask_written = r.layout;
+    return MMX_OK;
 }
+
+namespace {
+// mmx_log_batch_f32 behind its mmx_batch_geom_make: check, route (mmx_route.h), run
+int log_scale(const mmx_log_call& c, const mmx_batch_geom& g)
+{
+    if (c.h_mask_written) *c.h_mask_written = 0;
+    if (c.h_zx_path) *c.h_zx_path = MMX_ZX_SEPARATE;
+    int rc = mmx_log_scale_check(c);
+    if (rc != MMX_OK) return rc;
+    mmx_route r;
+    rc = mmx_route_scale(c.vol, g, c.radius, c.h_w0, c.h_w2, c.norm, c.zx_mode, c.nms_eps, c.d_nms_mask && c.h_mask_written, &r);
+    return rc != MMX_OK ? rc : mmx_log_scale_run(c, g, r);
+}
+}  // namespace
 
 int mmx_zx_pack_geom(const mmx_volume* vol, const mmx_block* d_blocks, const mmx_block* h_blocks, int n_blocks,
                      int64_t slot_elems, const mmx_batch_geom& g, float* d_work, hipStream_t stream)
@@ -476,7 +414,7 @@ int mmx_log_batch_f32(const mmx_volume* vol, const mmx_block* d_blocks, const mm
 {
     mmx_batch_geom g{};
     if (vol && h_blocks) mmx_batch_geom_make(vol, h_blocks, n_blocks, slot_elems, &g);     // (NULL: refused below, g unread)
-    return mmx_log_scale_f32({vol, d_blocks, h_blocks, n_blocks, slot_elems, h_w0, h_w2, radius, norm, d_log, d_work,
+    return log_scale({vol, d_blocks, h_blocks, n_blocks, slot_elems, h_w0, h_w2, radius, norm, d_log, d_work,
                               d_nms_mask, nms_lo, nms_eps, h_mask_written, zx_mode, h_zx_path, (hipStream_t)stream}, g);
 }
 
@@ -496,17 +434,8 @@ int mmx_log_batch_f32_generic(const mmx_volume* vol, const mmx_block* d_blocks, 
     if (g.status != MMX_OK) return g.status;
     pass_weights w;
     make_weights(vol, h_w0, h_w2, radius, norm, &w);
-    const int64_t n_slots = n_blocks;
-    float* t0 = d_work;
-    float* t1 = d_work + n_slots * slot_elems;
-    float* t2 = t1 + n_slots * slot_elems;
-    float* t3 = t2 + n_slots * slot_elems;
-    hipStream_t s = (hipStream_t)stream;
-    int rc = mmx_launch_generic_pass(0, vol, d_blocks, n_blocks, g.max_vox, slot_elems, w.z0, w.z2, radius, nullptr, nullptr, t0, t1, s);
-    if (rc != MMX_OK) return rc;
-    rc = mmx_launch_generic_pass(1, vol, d_blocks, n_blocks, g.max_vox, slot_elems, w.y0, w.y2, radius, t0, t1, t2, t3, s);
-    if (rc != MMX_OK) return rc;
-    return mmx_launch_generic_pass(2, vol, d_blocks, n_blocks, g.max_vox, slot_elems, w.x0, w.x2, radius, t2, t3, d_log, nullptr, s);
+    return three_passes(vol, d_blocks, n_blocks, slot_elems, radius, d_work, d_log, g, w, false, false, false, false,
+                        (hipStream_t)stream);
 }
 
 int mmx_zx_pack(const mmx_volume* vol, const mmx_block* d_blocks, const mmx_block* h_blocks, int n_blocks,

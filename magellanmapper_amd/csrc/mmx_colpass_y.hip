@@ -21,6 +21,7 @@ int mmx_launch_ypass(const mmx_block* d_blocks, int n_blocks, int max_cols, int6
                      const mmx_taps_f32& taps, int radius, const float* d_gz, const float* d_gzz,
                      float* d_a, float* d_bc, hipStream_t stream)
 {
+    if (!mmx_ring_radius(radius)) return MMX_ERR_UNSUPPORTED;
     switch (radius) {
 #define X(R) case R: return launch_y<R>(d_blocks, n_blocks, max_cols, slot_elems, taps, d_gz, d_gzz, d_a, d_bc, stream);
         MMX_FOR_EACH_RADIUS(X)

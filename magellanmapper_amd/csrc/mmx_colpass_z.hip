@@ -34,6 +34,7 @@ int mmx_launch_zpass(const mmx_volume* vol, const mmx_block* d_blocks, int n_blo
                      int64_t slot_elems, const mmx_taps_f32& taps, int radius,
                      float* d_gz, float* d_gzz, hipStream_t stream)
 {
+    if (!mmx_ring_radius(radius) || !mmx_voxels_ok(vol)) return MMX_ERR_UNSUPPORTED;
     switch (radius) {
 #define X(R) case R: return launch_z<R>(vol, d_blocks, n_blocks, max_cols, slot_elems, taps, d_gz, d_gzz, stream);
         MMX_FOR_EACH_RADIUS(X)

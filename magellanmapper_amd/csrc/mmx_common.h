@@ -97,7 +97,7 @@ struct mmx_batch_geom {
 // (vol: NULL for callers that read no voxels -- no plan, no input offsets)
 void mmx_batch_geom_make(const mmx_volume* vol, const mmx_block* h_blocks, int n_blocks, int64_t slot_elems, mmx_batch_geom* g);
 
-// Host-only predicates of the kernel paths and the layout of a ladder with wide radii (no launch, no device state)
+// The kernel-path rules: the launchers' predicates, the route of a scale and of a ladder (host-only, no launch)
 #include "mmx_route.h"
 
 // mmx_log_batch_f32 and mmx_zx_pack behind their mmx_batch_geom_make (mmx_api.hip): what mmx_log_scales_f32 calls.
@@ -107,15 +107,12 @@ struct mmx_log_call {       // (the arguments of mmx_log_batch_f32)
     float* d_log; float* d_work; uint64_t* d_nms_mask; float nms_lo, nms_eps; int* h_mask_written;
     int zx_mode; int* h_zx_path; hipStream_t stream;
 };
-int mmx_log_scale_f32(const mmx_log_call& c, const mmx_batch_geom& g);
+int mmx_log_scale_check(const mmx_log_call& c);                                                 // its argument checks
+int mmx_log_scale_run(const mmx_log_call& c, const mmx_batch_geom& g, const mmx_route& r);     // its launches, as routed
 int mmx_zx_pack_geom(const mmx_volume* vol, const mmx_block* d_blocks, const mmx_block* h_blocks, int n_blocks,
                      int64_t slot_elems, const mmx_batch_geom& g, float* d_work, hipStream_t stream);
-
-// The tile choice of the tiled path, float32 or 16-bit (mmx_detect.hip, with the rest of the rules): unit_bound =
-// mmx_tiled_q16_error_bound of the scale(s) the answer is for, band = the nomination band.  *value_scale: value units
-// per unit of the [0, 1] range that bound is stated for -- 1 for integer voxels (img_as_float), m for float voxels that
-// state a range [0, m], 0 when 16-bit tiles cannot hold the voxels.
-bool mmx_tiles_q16(int zx_mode, const mmx_volume* vol, double unit_bound, double band, bool entries_wanted, double* value_scale);
+// what mmx_detect_last_error returns next on this thread (mmx_detect.hip)
+void mmx_detect_set_error(const char* msg);
 
 // ---- optional per-kernel-family timing with HIP events on the launch stream (bench.py) ----
 enum mmx_kernel_kind {

@@ -1,10 +1,9 @@
-// The one home of a batch's kernel-path rules, and the batch in ONE call on top of them (SURVEY.md section 8b:
-// "mmx_detect_block -- fused A0-A4").  Replaces, for the blocks of a batch, everything between the reference's call
-// `blob_log(roi, ...)` (magmap/cv/detector.py:931-933) and the point where its float64 cube values are compared:
-// img_as_float + gaussian_laplace per sigma + scale normalisation (A0-A3) and the nomination half of peak_local_max (A4).
-//   mmx_log_scales_f32 : the voxel copy of the tiled path and (Z+X, Y) per sigma -- which kernel path, which tiles,
-//                        when the copy is trusted, one NMS entry layout for all scales (the rules: include/mmx.h);
-//                        mmx_tiles_q16 is the tile choice, shared with the per-call MMX_ZX_AUTO of mmx_log_batch_f32
+// A batch in ONE call ("mmx_detect_block -- fused A0-A4").  Replaces, for the blocks of a batch,
+// everything between the reference's call `blob_log(roi, ...)` (magmap/cv/detector.py:931-933) and the point where its
+// float64 cube values are compared: img_as_float + gaussian_laplace per sigma + scale normalisation (A0-A3) and the
+// nomination half of peak_local_max (A4).
+//   mmx_log_scales_f32 : the voxel copy of the tiled path and (Z+X, Y) per sigma, as mmx_route_ladder (mmx_route.h, the
+//                        kernel-path rules) routes them before the first launch: nothing is decided here
 //   mmx_detect_batch   : that, then the tail -- counter reset, sparse NMS, (for a batch of parts: the fold into their
 //                        parent blocks, mmx_parts.hip,) probe expansion, exact float64 re-score, the copies of the
 //                        counters and of the table's head to pinned host memory, the events
@@ -76,88 +75,9 @@ uint64_t* nms_entries(const mmx_detect_args* a)
     return reinterpret_cast<uint64_t*>((reinterpret_cast<uintptr_t>(end) + 15) & ~(uintptr_t)15);
 }
 
-// One round of the rules (include/mmx.h, mmx_log_scales_f32): the voxel copy when `mode` can take the tiled path, then
-// every scale.  `layouts`: bit (1 << layout) for every NMS entry layout a scale reported (bit 0: none).
-int passes(const mmx_detect_args* a, const mmx_batch_geom& g, bool with_mask, int mode, unsigned* layouts, int* zx_path,
-           double* q16_bound, bool* pack_side, const int32_t* modes = nullptr)
-{
-    *layouts = 0;
-    const mmx_volume* vol = a->vol32;
-    const bool is_float = vol->dtype == MMX_F32;
-    const bool float_ok = is_float && vol->value_range != 0.f;
-    const int nb = a->n_blocks, ns = a->n_sigma;
-    const int64_t slot = a->slot_elems;
-    const size_t tab = MMX_MAX_RADIUS_GENERIC + 1;
-    float* d_log = log_arrays(a);
-    uint64_t* d_mask = nms_entries(a);
-    const size_t mask_words = ((size_t)nb * slot) >> 5;
-    // float32 or 16-bit tiles: one answer for the batch, from the largest bound over its scales
-    int tiled_mode = MMX_ZX_TILED;
-    if (mode == MMX_ZX_AUTO || mode == MMX_ZX_TILED_Q16) {
-        double bound = 0.0;
-        for (int s = 0; s < ns; ++s) {
-            const double b = mmx_tiled_q16_error_bound(a->h_w0 + s * tab, a->h_w2 + s * tab, a->h_radius[s], a->h_norm[s]);
-            if (b < 0) { bound = -1.0; break; }
-            if (b > bound) bound = b;
-        }
-        double vscale;
-        if (mmx_tiles_q16(mode, vol, bound, a->eps, true, &vscale)) { tiled_mode = MMX_ZX_TILED_Q16; *q16_bound = bound * vscale; }
-    }
-    bool packed = false;
-    hipStream_t main = (hipStream_t)a->stream;
-    if (modes) ;            // (no scale of a laid-out ladder runs the tiled path)
-    else if (((mode == MMX_ZX_AUTO || mode == MMX_ZX_TILED || mode == MMX_ZX_TILED_Q16) && !is_float) ||
-        ((mode == MMX_ZX_AUTO || mode == MMX_ZX_TILED) && float_ok)) {
-        hipStream_t ps = (*pack_side && a->pack_stream) ? (hipStream_t)a->pack_stream : main;
-        int rc = mmx_zx_pack_geom(vol, a->d_blocks, a->h_blocks, nb, slot, g, a->d_work, ps);
-        if (rc != MMX_OK && rc != MMX_ERR_UNSUPPORTED) return rc;
-        if (ps != main) {
-            const int st = after(ps, main, "voxel copy -> main stream");
-            if (st != MMX_OK) return st;
-            *pack_side = false;           // (a second round of passes, should one be needed: in stream order)
-        }
-        packed = rc == MMX_OK;
-    }
-    for (int s = 0; s < ns; ++s) {
-        int written = 0, path = 0;
-        if (modes) {        // (a ladder laid out beforehand: no voxel copy was made, every scale has its own mode)
-            const int rc = mmx_log_scale_f32({vol, a->d_blocks, a->h_blocks, nb, slot, a->h_w0 + s * tab, a->h_w2 + s * tab,
-                                              a->h_radius[s], a->h_norm[s], d_log + (size_t)s * nb * slot, a->d_work,
-                                              with_mask ? d_mask + (size_t)s * mask_words * 2 : nullptr, a->thr - a->eps,
-                                              a->eps, &written, modes[s], &path, main}, g);
-            if (rc != MMX_OK) return rc;
-            *zx_path = path;
-            *layouts |= 1u << (with_mask ? written : 0);
-            continue;
-        }
-        // (the copy is trusted while every scale so far ran the tiled path: any other path uses that part of the
-        //  workspace for something else)
-        const int rc = mmx_log_scale_f32({vol, a->d_blocks, a->h_blocks, nb, slot, a->h_w0 + s * tab, a->h_w2 + s * tab,
-                                          a->h_radius[s], a->h_norm[s], d_log + (size_t)s * nb * slot, a->d_work,
-                                          with_mask ? d_mask + (size_t)s * mask_words * 2 : nullptr, a->thr - a->eps, a->eps,
-                                          &written, packed ? (tiled_mode | MMX_ZX_PREPACKED | a->zx_flags) : mode, &path,
-                                          main}, g);
-        if (rc != MMX_OK) return rc;
-        *zx_path = path;
-        packed = packed && path == tiled_mode;
-        *layouts |= 1u << (with_mask ? written : 0);
-    }
-    return MMX_OK;
-}
-
 }  // namespace
 
-bool mmx_tiles_q16(int zx_mode, const mmx_volume* vol, double unit_bound, double band, bool entries, double* value_scale)
-{
-    const bool ranged = vol->dtype == MMX_F32 && vol->value_range > 0.f && vol->value_range < 60000.f;
-    *value_scale = vol->dtype == MMX_U8 || vol->dtype == MMX_U16 ? 1.0 : (ranged ? (double)vol->value_range : 0.0);
-    if (!(*value_scale > 0.0)) return false;
-    // (by name: taken whatever the band; the caller's run-time check of |float32 - float64| against eps / 4 on the
-    //  re-scored candidates is what then widens it)
-    if (zx_mode == MMX_ZX_TILED_Q16) return true;
-    const double bound = unit_bound * *value_scale;
-    return zx_mode == MMX_ZX_AUTO && entries && bound >= 0.0 && 4.0 * bound <= band && bound <= MMX_LOG_ABS_TOL;
-}
+void mmx_detect_set_error(const char* msg) { snprintf(g_detect_err, sizeof g_detect_err, "%s", msg); }
 
 extern "C" {
 
@@ -183,50 +103,41 @@ int mmx_log_scales_f32(const mmx_detect_args* a, mmx_detect_info* info)
     mmx_batch_geom g;
     mmx_batch_geom_make(a->vol32, a->h_blocks, a->n_blocks, a->slot_elems, &g);
 
-    unsigned layouts = 0;
-    int zx_path = 0;
-    double q16_bound = 0.0;
-    int rc;
-    // a ladder with a radius for the wide passes: laid out before the first launch, one round (the rules: include/mmx.h)
-    std::vector<int32_t> modes(a->n_sigma);
-    bool entries = false;
-    if (a->zx_mode == MMX_ZX_AUTO && g.status == MMX_OK &&
-        mmx_ladder_layout(a->vol32, g, a->h_radius, a->n_sigma, modes.data(), &entries)) {
-        rc = passes(a, g, entries, MMX_ZX_AUTO, &layouts, &zx_path, &q16_bound, &pack_side, modes.data());
+    // every scale's call, checked; then the routes of the whole ladder (mmx_route.h), before the first launch
+    const mmx_volume* vol = a->vol32;
+    const int nb = a->n_blocks, ns = a->n_sigma;
+    const int64_t slot = a->slot_elems;
+    const size_t tab = MMX_MAX_RADIUS_GENERIC + 1;
+    const size_t mask_words = ((size_t)nb * slot) >> 5;
+    auto call = [&](int s, bool entries) {
+        return mmx_log_call{vol, a->d_blocks, a->h_blocks, nb, slot, a->h_w0 + s * tab, a->h_w2 + s * tab, a->h_radius[s],
+                            a->h_norm[s], log_arrays(a) + (size_t)s * nb * slot, a->d_work,
+                            entries ? nms_entries(a) + (size_t)s * mask_words * 2 : nullptr, a->thr - a->eps, a->eps,
+                            nullptr, a->zx_mode, nullptr, main};
+    };
+    for (int s = 0; s < ns; ++s) {
+        const int rc = mmx_log_scale_check(call(s, false));
         if (rc != MMX_OK) return rc;
-        if (layouts & (layouts - 1)) {      // (a scale left its laid-out path after all: the cube in full, as ever)
-            for (auto& m : modes) m = MMX_ZX_AUTO;
-            rc = passes(a, g, false, MMX_ZX_AUTO, &layouts, &zx_path, &q16_bound, &pack_side, modes.data());
-            if (rc != MMX_OK) return rc;
-            info->n_pass_rounds++;
-        }
-        int layout = 0;
-        while (!(layouts & (1u << layout))) ++layout;
-        info->zx_path = zx_path;
-        info->mask_layout = layout;
-        info->n_pass_rounds++;
-        return MMX_OK;
     }
-
-    // all scales in one entry layout, or none: up to three rounds
-    rc = passes(a, g, true, a->zx_mode, &layouts, &zx_path, &q16_bound, &pack_side);
+    std::vector<mmx_route> routes(ns);
+    mmx_ladder_route ladder;
+    int rc = mmx_route_ladder(vol, g, a->h_radius, a->h_w0, a->h_w2, a->h_norm, ns, a->zx_mode, a->zx_flags, a->eps,
+                              routes.data(), &ladder);
     if (rc != MMX_OK) return rc;
-    if (layouts == ((1u << MMX_MASK_ROWS) | (1u << MMX_MASK_QUADS))) {
-        rc = passes(a, g, true, MMX_ZX_PACKED, &layouts, &zx_path, &q16_bound, &pack_side);
+    if (ladder.copy) {
+        hipStream_t ps = (ladder.copy_on_side && pack_side) ? (hipStream_t)a->pack_stream : main;
+        rc = mmx_zx_pack_geom(vol, a->d_blocks, a->h_blocks, nb, slot, g, a->d_work, ps);
+        if (rc == MMX_OK) rc = after(ps, main, "voxel copy -> main stream");
         if (rc != MMX_OK) return rc;
-        info->n_pass_rounds++;
     }
-    if (layouts & (layouts - 1)) {       // more than one kind
-        rc = passes(a, g, false, a->zx_mode, &layouts, &zx_path, &q16_bound, &pack_side);
+    for (int s = 0; s < ns; ++s) {
+        rc = mmx_log_scale_run(call(s, routes[s].layout != 0), g, routes[s]);
         if (rc != MMX_OK) return rc;
-        info->n_pass_rounds++;
     }
-    int mask_layout = 0;
-    while (!(layouts & (1u << mask_layout))) ++mask_layout;
-    info->zx_path = zx_path;
-    info->mask_layout = mask_layout;
-    info->q16_bound = zx_path == MMX_ZX_TILED_Q16 ? q16_bound : 0.0;
-    info->n_pass_rounds++;
+    info->zx_path = ladder.zx_path;
+    info->mask_layout = ladder.layout;
+    info->q16_bound = ladder.q16_bound;
+    info->n_pass_rounds = ladder.n_configs;
     return MMX_OK;
 }
 

@@ -370,6 +370,7 @@ int mmx_launch_y2(const mmx_block* d_blocks, int n_blocks, int max_cols, int64_t
                   const mmx_taps_f32& taps, int radius, const float* d_p, const float* d_q,
                   float* d_log, unsigned long long* d_mask, float nms_lo, float nms_eps, hipStream_t stream)
 {
+    if (!mmx_ring_radius(radius)) return MMX_ERR_UNSUPPORTED;
     switch (radius) {
 #define X(R) case R: return launch_y2<R>(d_blocks, n_blocks, max_cols, slot_elems, taps, d_p, d_q, d_log, d_mask, nms_lo, nms_eps, stream);
         MMX_FOR_EACH_RADIUS(X)
@@ -382,6 +383,7 @@ int mmx_launch_y6(const mmx_block* d_blocks, int n_blocks, const mmx_zx6_plan& p
                   const mmx_taps_f32& taps, int radius, const float* d_p, const float* d_q, float cp, float cq,
                   float* d_log, unsigned long long* d_mask, float nms_lo, float nms_eps, hipStream_t stream)
 {
+    if (!mmx_ring_radius(radius)) return MMX_ERR_UNSUPPORTED;
     switch (radius) {
 #define X(R) case R: return launch_y6<R>(d_blocks, n_blocks, plan, slot_elems, taps, d_p, d_q, cp, cq, d_log, d_mask, nms_lo, nms_eps, stream);
         MMX_FOR_EACH_RADIUS(X)

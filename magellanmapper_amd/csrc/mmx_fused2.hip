@@ -39,7 +39,7 @@ namespace {
 constexpr int kG = 8;        // z steps (rows) per tile
 constexpr int kT = 4;        // X outputs per consumer item
 constexpr int kCons = 576;   // consumer lanes (9 waves): one round of (row, chunk) items for px = 288
-constexpr int kMaxPx = 320;  // 5 producer waves
+constexpr int kMaxPx = MMX_PACKED_MAX_PX;  // 5 producer waves
 #ifndef ZX2_PF
 #define ZX2_PF 2
 #endif
@@ -320,8 +320,7 @@ int launch_zx2(const mmx_volume* vol, const mmx_block* d_blocks, int n_blocks, i
                int64_t slot_elems, const mmx_taps_f32& tz, const mmx_taps_f32& tx, float* d_p, float* d_q,
                hipStream_t s)
 {
-    if (max_px > kMaxPx) return MMX_ERR_UNSUPPORTED;
-    if (vol->stride_z * 8 * (int64_t)sizeof(double) >= (int64_t(1) << 32)) return MMX_ERR_UNSUPPORTED;   // scalar plane offsets
+    if (!mmx_zx2_launch_accepts(vol, max_px, R)) return MMX_ERR_UNSUPPORTED;     // (row pitch, scalar plane offsets)
     mmx_taps_zx2 T;
     for (int k = 0; k <= MMX_MAX_RADIUS_FAST; ++k) {
         T.zw[k] = (v2f){tz.w0[k], tz.w2[k]};

@@ -923,7 +923,7 @@ int launch_zx6(const mmx_volume* vol, const mmx_block* d_blocks, const mmx_block
     int max_waves = 0;
     for (int i = 0; i < n_blocks; ++i) {
         const mmx_block& b = h_blocks[i];
-        if (b.nx < radius || b.nz < radius) return MMX_ERR_UNSUPPORTED;       // single reflection
+        if (!mmx_zx6_launch_accepts(vol, b.nz, b.nx, radius)) return MMX_ERR_UNSUPPORTED;       // single reflection
         const int ntx = (b.nx + 15) / 16;
         max_waves = std::max(max_waves, b.ny * (pair ? (ntx + 1) / 2 : ntx));
     }
@@ -1004,7 +1004,7 @@ int mmx_launch_zx6_pack(const mmx_volume* vol, const mmx_block* d_blocks, const 
                         const mmx_zx6_plan& plan, void* d_work, hipStream_t stream)
 {
     (void)h_blocks;
-    if (vol->dtype != MMX_U16 && vol->dtype != MMX_U8 && vol->dtype != MMX_F32) return MMX_ERR_UNSUPPORTED;
+    if (!mmx_voxels_ok(vol)) return MMX_ERR_UNSUPPORTED;
     uint16_t* pack = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(d_work) + plan.pack_off);
     dim3 grid(plan.max_rowtiles, n_blocks);
     if (vol->dtype == MMX_F32)
@@ -1024,8 +1024,7 @@ int mmx_launch_zx6(const mmx_volume* vol, const mmx_block* d_blocks, const mmx_b
                    const mmx_zx6_plan& plan, const mmx_taps_f32& tx, int radius, void* d_work, float qp, float qq,
                    hipStream_t stream)
 {
-    if (vol->dtype != MMX_U16 && vol->dtype != MMX_U8 && vol->dtype != MMX_F32) return MMX_ERR_UNSUPPORTED;
-    if (radius < 1 || radius > MMX_MAX_RADIUS_FAST) return MMX_ERR_UNSUPPORTED;
+    if (!mmx_ring_radius(radius) || !mmx_voxels_ok(vol)) return MMX_ERR_UNSUPPORTED;
     if (radius <= 8) return launch_zx6<1, 1>(vol, d_blocks, h_blocks, n_blocks, plan, tx, radius, d_work, qp, qq, stream);
     if (radius <= 16) return launch_zx6<2, 1>(vol, d_blocks, h_blocks, n_blocks, plan, tx, radius, d_work, qp, qq, stream);
     return launch_zx6<2, 2>(vol, d_blocks, h_blocks, n_blocks, plan, tx, radius, d_work, qp, qq, stream);

@@ -293,7 +293,7 @@ int mmx_launch_wide_pass(int pass, const mmx_volume* vol, const mmx_block* d_blo
                          const float* in1, const float* in2, float* out1, float* out2,
                          unsigned long long* d_mask, float nms_lo, float nms_eps, hipStream_t s)
 {
-    if (radius < 1 || radius > MMX_MAX_RADIUS_WIDE) return MMX_ERR_UNSUPPORTED;
+    if (!mmx_wide_launch_accepts(vol, radius)) return MMX_ERR_UNSUPPORTED;
     const int R = radius;
     static_assert(kOff >= kJ - 1 && kTaps >= kOff + run_inputs(MMX_MAX_RADIUS_WIDE) + kJ - 1, "padded kernel too short");
     wide_taps T;

@@ -21,9 +21,9 @@
 
 namespace {
 
-constexpr int kT = 8;        // outputs per thread
-constexpr int kMaxQuads = 2; // 16-byte loads per thread, array and row group (host sizes RG to fit)
-constexpr int kMaxHalo = 2;  // halo loads per thread, array and row group
+constexpr int kT = MMX_X_OUTPUTS;        // outputs per thread
+constexpr int kMaxQuads = MMX_X_MAX_QUADS; // 16-byte loads per thread, array and row group (host sizes RG to fit)
+constexpr int kMaxHalo = MMX_X_MAX_HALO;  // halo loads per thread, array and row group
 
 // LDS row layout: two pad floats after every eight, so that threads reading 8-float-strided
 // windows with ds_read_b64 hit 32 distinct bank pairs.
@@ -178,21 +178,12 @@ template <int R>
 int launch_x(const mmx_block* d_blocks, int n_blocks, int max_rows, int max_nx, int64_t slot_elems,
              const mmx_taps_f32& taps, const float* d_a, const float* d_bc, float* d_log, hipStream_t s)
 {
-    constexpr int LEAD = R & 1;
-    constexpr int S = (R + LEAD + 7) & ~7;
-    const int px = (max_nx + MMX_ROW_ALIGN - 1) / MMX_ROW_ALIGN * MMX_ROW_ALIGN;
-    const int span = S + px + R + LEAD;
-    const int PW = ((span + 2 * (span >> 3)) + 3) & ~1;
-    const int CH = (max_nx + kT - 1) / kT;
-    // rows per group: as many as the threads cover, within the per-thread prefetch registers
-    int rg = MMX_WG / CH;
-    if (rg < 1) rg = 1;
-    while (rg > 1 && (rg * (px / 4) > kMaxQuads * MMX_WG || rg * 2 * R > kMaxHalo * MMX_WG)) --rg;
-    if (px / 4 > kMaxQuads * MMX_WG || 2 * R > kMaxHalo * MMX_WG) return MMX_ERR_UNSUPPORTED;
-    if (CH > MMX_WG) return MMX_ERR_UNSUPPORTED;   // rows wider than 2048 voxels: generic path
-    // narrower blocks of the same batch may pack more rows per group; keep them within rg
-    const size_t lds_bytes = ((size_t)2 * rg * PW + (size_t)rg * px) * sizeof(float);
-    if (lds_bytes > 64 * 1024) return MMX_ERR_UNSUPPORTED;
+    static_assert(MMX_X_THREADS == MMX_WG, "xpass_kernel runs MMX_WG threads");
+    if (!mmx_xpass_launch_accepts(max_nx, R)) return MMX_ERR_UNSUPPORTED;      // (rows wider than 2048 voxels, LDS)
+    // rows per group: narrower blocks of the same batch may pack more rows per group; the kernel keeps them within rg
+    const mmx_xpass_shape x = mmx_xpass_shape_of(max_nx, R);
+    const int rg = x.rg;
+    const size_t lds_bytes = x.lds_bytes;
     int gx = (max_rows + rg - 1) / rg;
     if (gx > 2048) gx = 2048;
     if (gx < 1) gx = 1;

@@ -454,7 +454,7 @@ int mmx_launch_ym(const mmx_block* d_blocks, int n_blocks, const mmx_zx6_plan& p
                   const mmx_taps_f32& taps, int radius, const float* d_p, float cp, float cq,
                   float* d_log, unsigned long long* d_mask, float nms_lo, float nms_eps, hipStream_t stream)
 {
-    if (radius < 1 || radius > 24 || radius > MMX_MAX_RADIUS_FAST || !(cp > 0.f) || !(cq > 0.f)) return MMX_ERR_UNSUPPORTED;
+    if (!mmx_ym_accepts(taps.w0, taps.w2, radius, cp, cq)) return MMX_ERR_UNSUPPORTED;      // (radius, weights in float16's reach)
     ym_cfg cfg;
     float mx = 0.f;
     for (int k = 0; k <= radius; ++k) {
@@ -462,7 +462,6 @@ int mmx_launch_ym(const mmx_block* d_blocks, int n_blocks, const mmx_zx6_plan& p
         cfg.w0[k] = taps.w0[k] * cq;
         mx = fmaxf(mx, fmaxf(fabsf(cfg.w2[k]), fabsf(cfg.w0[k])));
     }
-    if (!(mx > 1e-30f) || !(mx < 1e30f)) return MMX_ERR_UNSUPPORTED;
     int e;
     frexpf(mx, &e);                             // mx = f x 2^e, f in [0.5, 1)
     const float up = ldexpf(1.f, -e - 1);       // largest weight into [0.25, 0.5)

@@ -221,8 +221,8 @@ def test_the_tail_of_a_batch_on_its_own_stream_changes_nothing(gpu, monkeypatch)
             np.testing.assert_array_equal(va, vb)
 
 
-def test_large_sigma_takes_generic_path(gpu):
-    """sigma 7.5 -> radius 30 > MMX_MAX_RADIUS_FAST: generic kernels, same exactness."""
+def test_large_sigma_is_exact_beyond_the_fast_radii(gpu):
+    """sigma 7.5 -> radius 30 > MMX_MAX_RADIUS_FAST (the wide passes on this volume): same exactness."""
     from magellanmapper_amd import blob_log as bl
     from magellanmapper_amd import synth
     from oracle import blob_log_oracle as blo
