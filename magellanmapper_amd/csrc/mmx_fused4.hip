@@ -35,7 +35,10 @@
 //            of the next product once two z tiles are put side by side (k = 8 (l >> 4) + j <-> tile j >> 2,
 //            plane 4 (l >> 4) + (j & 3): the MFMA does not care in which order k runs as long as both
 //            operands agree).  So the X results never leave the registers: they are split into float16 pieces
-//            and kept in a sliding window of 2 LA + 2 z tiles; the Z Toeplitz fragments follow the same k order.
+//            and kept in a sliding window of four z tiles, two k-steps; the Z Toeplitz fragments follow the same k
+//            order.  Radius <= 16 needs z tiles U - 1 .. U + 1 of it; radius 17 .. 24 needs the 64 planes
+//            [16 U - 24, 16 U + 40): z tiles U - 1 .. U + 1 and a split tile, per lane the half of z tile U + 2 or
+//            of z tile U - 2 that the taps reach (cls4 has the map and why it always suffices).
 //            The result has z_out on lane & 15 and four consecutive x in the registers: one 16-byte store per
 //            lane for P and for Q.
 // SciPy's "reflect" boundaries are folded into the Toeplitz fragments (the weight of a mirrored tap is added
@@ -109,8 +112,23 @@ template <int NKX, int LA> struct cls4 {
         const int al = lo & ~31;
         return (al + 32 * NKX >= 16 * c + 16 + R8) ? al : lo;
     }
-    static constexpr int NKZ = LA + 1;
-    static constexpr int NT = 2 * NKZ;
+    // The Z pass of output tile U is two k-steps of two 16-plane operand slots each, in both depths of window.
+    // LA = 1: [U - 1, U] [U + 1, zero weights].
+    // LA = 2: [V, U - 1] [U, U + 1], where the SPLIT tile V holds, lane by lane, the two half tiles that the taps
+    // still reach: planes 16 U + 32 .. 16 U + 39 (the lower half of tile U + 2) in the lanes with lane >> 4 in {0, 1}
+    // and planes 16 U - 24 .. 16 U - 17 (the upper half of tile U - 2) in the lanes with lane >> 4 in {2, 3} -- under
+    // the operand layout (plane 4 (lane >> 4) + (j & 3)) those are the lanes that hold these planes of either tile,
+    // so V is a per-lane choice between two tiles' registers.  Together the 64 planes [16 U - 24, 16 U + 40).
+    // They always suffice, for any block depth nz >= R (R <= 24):
+    //   - the direct taps of a real output zo in [16 U, min(16 U + 15, nz - 1)] lie in [16 U - 24, 16 U + 39];
+    //   - a left mirror image -1 - p of a tap exists only for U <= 1 and lands in [0, 23 - 16 U];
+    //   - a right mirror image 2 nz - 1 - p lands in [nz - R, nz - 1], and nz - R >= 16 U - 24 because tile U has a
+    //     real plane (nz > 16 U);
+    // so every folded tap meets a plane the two k-steps hold, also in blocks of one or two z tiles.  (Five whole
+    // tiles and an always-zero sixth, as this class had them, are three k-steps: 27 Z MFMAs per tile step for 18.)
+    static constexpr bool SPLIT = LA == 2;
+    static constexpr int NKZ = 2;
+    static constexpr int NT = 4;
 };
 
 __device__ __forceinline__ unsigned pack_h2(float a, float b)
@@ -183,9 +201,11 @@ zx4_setup(mmx_zx4_cfg cfg, u4_4* __restrict__ xtab, u4_4* __restrict__ ztab)
         const int zo = 16 * U + col;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const int i = 2 * ks + (j >> 2);                        // window tile of this k
-            const int zi = 16 * (U - LA + i) + 4 * kq + (j & 3);
-            const bool ok = i < cg::NT - 1 && zi >= 0 && zi < nz && zo < nz;
+            const int i = 2 * ks + (j >> 2);                        // operand slot of this k
+            // (LA = 2: slot 0 is the split tile -- this lane's planes of tile U + 2 or of tile U - 2: cls4)
+            const int tile = cg::SPLIT ? (i == 0 ? (kq < 2 ? U + 2 : U - 2) : U - 2 + i) : U - LA + i;
+            const int zi = 16 * tile + 4 * kq + (j & 3);
+            const bool ok = (cg::SPLIT || i < cg::NT - 1) && zi >= 0 && zi < nz && zo < nz;
             wt[j] = ok ? folded_tap(w, R, zi, zo, nz) * (cfg.qp > 0.f && kern ? cfg.qq / cfg.qp : 1.f) : 0.f;
         }
         dst = ztab + (size_t)ez * 2 * 64;
@@ -286,7 +306,7 @@ __device__ __forceinline__ f4_4 mfma16(const u4_4& a, const u4_4& b, const f4_4&
 // independent work per step.  An odd tile count leaves the last wave of a row one tile: it computes the second with
 // zero weights and its stores are dropped by a zero-length buffer descriptor (no branch in the march).
 template <int NKX, int LA, typename InT, bool Q16 = false, int NTW = 1>
-__global__ void __launch_bounds__(256, (NTW == 1 && (LA == 1 || Q16) && !is_f32_4<InT>::value) ? 3 : 2)   // (float32 tiles, LA == 2: 232 registers)
+__global__ void __launch_bounds__(256, (NTW == 1 && (LA == 1 || Q16) && !is_f32_4<InT>::value) ? 3 : 2)   // (float32 tiles, LA == 2: 213 registers)
 zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
            const mmx_block* __restrict__ blocks, int64_t slot_elems,
            float* __restrict__ gp, float* __restrict__ gq,
@@ -295,13 +315,14 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
     using cg = cls4<NKX, LA>;
     using pc = pieces4<InT>;
     constexpr int NKZ = cg::NKZ, NT = cg::NT;
+    constexpr bool SPLIT = cg::SPLIT;                 // radius > 16: operand slot 0 of the Z pass is the split tile (cls4)
     constexpr int kUnit = std::is_same<InT, float>::value ? 512 : 256;      // bytes of a unit of the voxel copy
     constexpr bool LO_SCALED = lo_scaled4<InT>::value;
     static_assert(NTW == 1 || (NTW == 2 && Q16 && NKX == 2 && LA == 1), "two tiles per wave: 16-bit tiles, 8 < radius <= 16");
     // radius <= 16: the Z fragments of the interior z tiles live in LDS, shared by the workgroup's waves, and
-    // two z tiles are in flight instead of three: 154 registers, three waves per SIMD.  (Radius > 16 has three
-    // k-steps of Z fragments: with float32 tiles, which are bound by their stores, fetching them from LDS every step
-    // costs more than the third wave gives -- 4.19 against 3.87 ms --; with 16-bit tiles, 168 registers, it pays:
+    // two z tiles are in flight instead of three: 154 registers, three waves per SIMD.  (Radius > 16, measured when
+    // it still had three k-steps of Z fragments: with float32 tiles, which are bound by their stores, fetching them
+    // from LDS every step cost more than the third wave gave -- 4.19 against 3.87 ms --; with 16-bit tiles it paid:
     // 3.10 against 3.15 ms.)
     constexpr bool ZLDS = LA == 1 || Q16;
     constexpr int PF = ZLDS ? ZX6_PF : kPF4;         // z tiles of voxels in flight per wave
@@ -319,6 +340,7 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
     const int c = (gw - y * ntp) * NTW;                         // (first) column tile of this wave
     const int lane = threadIdx.x & 63;
     const int li = lane & 15, kq = lane >> 4;
+    [[maybe_unused]] const bool lowk = kq < 2;                  // this lane holds planes 0 .. 7 of a tile's 16 as a Z operand
     int cw = 0, cz = 0;
     for (int i = 1; i < cfg.ncw; ++i) cw = cfg.wcls[i] == W ? i : cw;
     for (int i = 1; i < cfg.ncz; ++i) cz = cfg.zcls[i] == nz ? i : cz;
@@ -336,6 +358,10 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
     // faster (tools/kbench.py, 16-bit tiles, ms per 22 blocks: radius 8 0.752 -> 0.70, radius 18 / 20 1.02 -> 0.975);
     // two column tiles per wave spill with it (76 bytes: 0.75 -> 1.20), one tile per wave at radius 9..16 loses to
     // the pair as before (0.845 against 0.74), float32 tiles read +6 %: profiles/r05_experiments.txt, section 6.
+    // Radius > 16 (SPLIT): the four slots hold z tiles t - 4 .. t - 1 whole; the X results of z tile t stay in registers
+    // of their own during the step, the split tile is chosen per lane between them and slot t mod 4 (z tile t - 4),
+    // and they become that slot once the Z pass has read it.  The slot of the split tile goes round with t, the quads
+    // never move, and the shifted table is the cyclic one: F1[k] = [F0[k - 1 mod 2] upper half | F0[k] lower half].
     constexpr bool ROT = ZLDS && Q16 && NTW == 1 && !is_f32_4<InT>::value && (NKX == 1 || LA == 2);
     constexpr int ZL1 = NKZ * 4 * 64;                          // entries of one table
     __shared__ u4_4 zl[ZLDS ? (ROT ? 2 : 1) * ZL1 : 1];
@@ -346,7 +372,8 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
         if constexpr (ROT) {
             for (int e = threadIdx.x; e < ZL1; e += 256) {
                 const u4_4 cur = zl[e];
-                const u4_4 prev = e >= 256 ? zl[e - 256] : (u4_4){0u, 0u, 0u, 0u};  // (k-step before: 4 x 64 entries back)
+                // (k-step before: 4 x 64 entries back; the split tile's window is a ring -- its first k-step follows its last)
+                const u4_4 prev = SPLIT ? zl[(e + ZL1 - 256) % ZL1] : (e >= 256 ? zl[e - 256] : (u4_4){0u, 0u, 0u, 0u});
                 zl[ZL1 + e] = (u4_4){prev.z, prev.w, cur.x, cur.y};
             }
             __syncthreads();
@@ -480,7 +507,15 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
         constexpr int PH = decltype(phase_tag)::value;
         constexpr bool TURN = STEADY && ROT && PH >= 0;
         constexpr int SLOT = TURN ? PH : 2 * LA;                 // where the X results of z tile t go
-        if constexpr (!TURN) {
+        // SPLIT: they go to xr, and into the window after the Z pass; VS = the slot of z tile t - 4, which the split
+        // tile shares with them (0 in the shifting form: the slots hold z tiles t - 4 .. t - 1)
+        constexpr int VS = TURN ? PH : 0;
+        unsigned xr[4][2] = {{0u, 0u}, {0u, 0u}, {0u, 0u}, {0u, 0u}};
+        auto put = [&](int w, int a, int d, unsigned v) __attribute__((always_inline)) {
+            if constexpr (SPLIT) xr[a][d] = v;
+            else win[w][a][SLOT][d] = v;
+        };
+        if constexpr (!TURN && !SPLIT) {
             // shift the window by one z tile
 #pragma unroll
             for (int w = 0; w < NTW; ++w)
@@ -543,25 +578,25 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
                         //  whose register writes the compiler's hazard recogniser does not see: one landed right behind an
                         //  MFMA that still read the register as its C operand -- wrong results for radius <= 8.)
                         const f2_4 ar = {av0 - (float)ah.x, av1 - (float)ah.y}, br = {bv0 - (float)bh.x, bv1 - (float)bh.y};
-                        win[w][0][SLOT][r >> 1] = __builtin_bit_cast(unsigned, ah);
-                        win[w][1][SLOT][r >> 1] = __builtin_bit_cast(unsigned, __builtin_convertvector(ar, h2_4));
-                        win[w][2][SLOT][r >> 1] = __builtin_bit_cast(unsigned, bh);
-                        win[w][3][SLOT][r >> 1] = __builtin_bit_cast(unsigned, __builtin_convertvector(br, h2_4));
+                        put(w, 0, r >> 1, __builtin_bit_cast(unsigned, ah));
+                        put(w, 1, r >> 1, __builtin_bit_cast(unsigned, __builtin_convertvector(ar, h2_4)));
+                        put(w, 2, r >> 1, __builtin_bit_cast(unsigned, bh));
+                        put(w, 3, r >> 1, __builtin_bit_cast(unsigned, __builtin_convertvector(br, h2_4)));
                         continue;
                     }
                     const f2_4 ar = {__builtin_fmaf((float)ah.x, -kLoScale, av0 * kLoScale), __builtin_fmaf((float)ah.y, -kLoScale, av1 * kLoScale)};
                     const f2_4 br = {__builtin_fmaf((float)bh.x, -kLoScale, bv0 * kLoScale), __builtin_fmaf((float)bh.y, -kLoScale, bv1 * kLoScale)};
-                    win[w][0][SLOT][r >> 1] = __builtin_bit_cast(unsigned, ah);
-                    win[w][1][SLOT][r >> 1] = __builtin_bit_cast(unsigned, __builtin_convertvector(ar, h2_4));
-                    win[w][2][SLOT][r >> 1] = __builtin_bit_cast(unsigned, bh);
-                    win[w][3][SLOT][r >> 1] = __builtin_bit_cast(unsigned, __builtin_convertvector(br, h2_4));
+                    put(w, 0, r >> 1, __builtin_bit_cast(unsigned, ah));
+                    put(w, 1, r >> 1, __builtin_bit_cast(unsigned, __builtin_convertvector(ar, h2_4)));
+                    put(w, 2, r >> 1, __builtin_bit_cast(unsigned, bh));
+                    put(w, 3, r >> 1, __builtin_bit_cast(unsigned, __builtin_convertvector(br, h2_4)));
                 }
             }
         } else {
 #pragma unroll
             for (int w = 0; w < NTW; ++w)
 #pragma unroll
-                for (int a = 0; a < 4; ++a) { win[w][a][SLOT][0] = 0u; win[w][a][SLOT][1] = 0u; }
+                for (int a = 0; a < 4; ++a) { put(w, a, 0, 0u); put(w, a, 1, 0u); }
         }
         const int U = t - LA;
         if (STEADY || U >= 0) {
@@ -579,6 +614,17 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
                         }
                 }
             }
+            // the split tile: the lower half of z tile t where this lane holds planes 0 .. 7 of a tile, the upper half of
+            // z tile t - 4 where it holds planes 8 .. 15 (eight selects, nothing crosses lanes)
+            unsigned vsel[4][2];
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                vsel[a][0] = SPLIT ? (lowk ? xr[a][0] : win[0][a][VS][0]) : 0u;
+                vsel[a][1] = SPLIT ? (lowk ? xr[a][1] : win[0][a][VS][1]) : 0u;
+            }
+            auto wv = [&](int w, int a, int s, int d) __attribute__((always_inline)) {
+                return SPLIT && s == VS ? vsel[a][d] : win[w][a][s][d];
+            };
             f4_4 p0[NTW], p1[NTW], q0[NTW], q1[NTW];
 #pragma unroll
             for (int w = 0; w < NTW; ++w) { p0[w] = zero4; p1[w] = zero4; q0[w] = zero4; q1[w] = zero4; }
@@ -590,7 +636,9 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
                 } else if constexpr (STEADY) {
                     // (rotating form: the window starts TR slots after slot 0; quad ks holds the window tiles of k-step
                     //  ks - TR / 2, one tile later when TR is odd)
-                    constexpr int TR = TURN ? (PH - (NT - 2) + NT) % NT : 0;
+                    //  (SPLIT: the split tile's slot is TR itself -- quad ks holds k-step ks + TR / 2 mod 2 of the table, or of
+                    //   the cyclically shifted one when TR is odd)
+                    constexpr int TR = TURN ? (SPLIT ? PH : (PH - (NT - 2) + NT) % NT) : 0;
                     const int KF = ((TR & 1) ? ZL1 : 0) + ((ks - TR / 2 + NKZ) % NKZ) * 256;     // (a constant once unrolled)
                     z00 = zl[KF + 0 * 64 + lane]; z01 = zl[KF + 1 * 64 + lane];
                     z10 = zl[KF + 2 * 64 + lane]; z11 = zl[KF + 3 * 64 + lane];
@@ -598,15 +646,15 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
                     const u4_4* zp = zt + ((size_t)(want * NKZ + ks) * 2) * 128;
                     z00 = zp[0]; z01 = zp[64]; z10 = zp[128]; z11 = zp[192];
                 }
-                // (The window's last tile, U + LA, stands alone in its k-step -- the fragments' other half is zero.  The
-                //  legacy v_mfma_f32_16x16x16_f16 on that half costs what the 16x16x32 form costs on gfx950 and, mixed
-                //  with it on one accumulator chain, gave run-dependent values: profiles/r05_experiments.txt, section 5.)
+                // (Radius <= 16: the window's last tile, U + 1, stands alone in its k-step -- the fragments' other half is
+                //  zero.  The legacy v_mfma_f32_16x16x16_f16 on that half costs what the 16x16x32 form costs on gfx950 and,
+                //  mixed with it on one accumulator chain, gave run-dependent values: profiles/r05_experiments.txt, section 5.)
 #pragma unroll
                 for (int w = 0; w < NTW; ++w) {
-                    const u4_4 ah = {win[w][0][2 * ks][0], win[w][0][2 * ks][1], win[w][0][2 * ks + 1][0], win[w][0][2 * ks + 1][1]};
-                    const u4_4 al = {win[w][1][2 * ks][0], win[w][1][2 * ks][1], win[w][1][2 * ks + 1][0], win[w][1][2 * ks + 1][1]};
-                    const u4_4 bh = {win[w][2][2 * ks][0], win[w][2][2 * ks][1], win[w][2][2 * ks + 1][0], win[w][2][2 * ks + 1][1]};
-                    const u4_4 bl = {win[w][3][2 * ks][0], win[w][3][2 * ks][1], win[w][3][2 * ks + 1][0], win[w][3][2 * ks + 1][1]};
+                    const u4_4 ah = {wv(w, 0, 2 * ks, 0), wv(w, 0, 2 * ks, 1), wv(w, 0, 2 * ks + 1, 0), wv(w, 0, 2 * ks + 1, 1)};
+                    const u4_4 al = {wv(w, 1, 2 * ks, 0), wv(w, 1, 2 * ks, 1), wv(w, 1, 2 * ks + 1, 0), wv(w, 1, 2 * ks + 1, 1)};
+                    const u4_4 bh = {wv(w, 2, 2 * ks, 0), wv(w, 2, 2 * ks, 1), wv(w, 2, 2 * ks + 1, 0), wv(w, 2, 2 * ks + 1, 1)};
+                    const u4_4 bl = {wv(w, 3, 2 * ks, 0), wv(w, 3, 2 * ks, 1), wv(w, 3, 2 * ks + 1, 0), wv(w, 3, 2 * ks + 1, 1)};
                     p0[w] = mfma16(ah, z00, p0[w]);
                     q0[w] = mfma16(bh, z00, q0[w]);
                     p1[w] = mfma16(ah, z01, p1[w]);
@@ -628,8 +676,9 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int w = 0; w < NTW; ++w) asm volatile("" ::"v"(P[w]));     // the slot's previous results stayed in these registers until now
-            asm volatile("" ::"v"(Q));
-            {                                              // (a tile is stored whole: its padding belongs to it)
+            // (16-bit tiles never write Q; at radius > 16 the registers this would pin are the ones the kernel lacks)
+            if constexpr (!(Q16 && SPLIT)) asm volatile("" ::"v"(Q));
+            {                                           // (a tile is stored whole: its padding belongs to it)
                 // the results reach the slot's registers through opaque moves: the stores then read registers
                 // that nothing else may be allocated to before the slot comes round again
                 if constexpr (Q16) {
@@ -670,6 +719,18 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
             }
             obase += 16u * plane_b;
         }
+        if constexpr (SPLIT) {
+            // z tile t takes its place in the window: the slot of z tile t - 4 where the slots stay, the last one where
+            // they shift
+            if constexpr (!TURN) {
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                    for (int i = 0; i < NT - 1; ++i) { win[0][a][i][0] = win[0][a][i + 1][0]; win[0][a][i][1] = win[0][a][i + 1][1]; }
+            }
+#pragma unroll
+            for (int a = 0; a < 4; ++a) { win[0][a][TURN ? PH : NT - 1][0] = xr[a][0]; win[0][a][TURN ? PH : NT - 1][1] = xr[a][1]; }
+        }
         __builtin_amdgcn_sched_barrier(0);
     };
     // tiles [0, tA): generic steps up to the first interior output tile (U = t - LA >= u_lo), rounded up to a
@@ -703,10 +764,11 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
         // nothing may be pending at the loop head: a wait for the fragment loads above, placed inside the loop
         // at their first use, would be a static vmcnt(N) that in steady state waits for the previous step's stores
         __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0)
-        // (rotating form: step j of a turn writes slot NT - 1 + j (mod NT): the generic steps leave tile t in slot NT - 2)
+        // (rotating form: step j of a turn writes slot NT - 1 + j (mod NT): the generic steps leave tile t in slot NT - 2;
+        //  SPLIT: slot j, the generic steps leave z tiles t - 3 .. t in slots 0 .. 3)
         auto turn = [&](int t0, auto... J) __attribute__((always_inline)) {
             (step(t0 + decltype(J)::value, std::true_type{},
-                  std::integral_constant<int, ROT ? (NT - 1 + decltype(J)::value) % NT : -1>{},
+                  std::integral_constant<int, ROT ? ((SPLIT ? 0 : NT - 1) + decltype(J)::value) % NT : -1>{},
                   raw[decltype(J)::value % PF], outP[decltype(J)::value % PF], outQ[decltype(J)::value % PF]), ...);
         };
         if constexpr (!ROT) {
@@ -719,11 +781,8 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
 #pragma unroll 1
             for (int t0 = tA; t0 < tB; t0 += GROUP) {
                 using std::integral_constant;
-                if constexpr (GROUP == 4) turn(t0, integral_constant<int, 0>{}, integral_constant<int, 1>{}, integral_constant<int, 2>{},
-                                               integral_constant<int, 3>{});
-                else turn(t0, integral_constant<int, 0>{}, integral_constant<int, 1>{}, integral_constant<int, 2>{},
-                          integral_constant<int, 3>{}, integral_constant<int, 4>{}, integral_constant<int, 5>{});
-                static_assert(GROUP == 4 || GROUP == 6, "turn lengths built: 4 (radius <= 16), 6 (radius <= 24)");
+                turn(t0, integral_constant<int, 0>{}, integral_constant<int, 1>{}, integral_constant<int, 2>{}, integral_constant<int, 3>{});
+                static_assert(GROUP == 4, "a turn is four steps in every class");
             }
         }
     }
@@ -991,7 +1050,8 @@ int mmx_zx6_plan_make(const mmx_block* h_blocks, int n_blocks, int64_t slot_elem
     plan->pack_stride = pk;
     plan->q_off = (int64_t)n_blocks * tile * 4;
     plan->tab_off = 2 * plan->q_off;
-    // the largest tables any radius class needs: widths x columns x 2 k-steps, depths x z tiles x 3, two kernels each
+    // room for the largest tables any radius class needs: widths x columns x 2 k-steps, depths x z tiles x 3 (every class
+    // has two since radius 17 .. 24 took its split tile; the workspace layout stays as it was), two kernels each
     plan->tab_bytes = (int64_t)(cl.ncw * cl.maxcol * 2 * 2 + cl.ncz * cl.maxu * 3 * 2) * 2 * 64 * 16;
     plan->pack_off = (plan->tab_off + plan->tab_bytes + 255) & ~int64_t(255);
     plan->max_tiles = max_tiles;
