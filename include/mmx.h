@@ -149,6 +149,11 @@ int mmx_device_count(void);
  *                point (MMX_ZX_TILED_Q16): MMX_LOG_ABS_TOL below.  MMX_ZX_TILED works from an operand-ordered copy of
  *                the blocks' voxels inside d_work, which does not depend on sigma: mmx_zx_pack makes it once per
  *                batch, and MMX_ZX_TILED | MMX_ZX_PREPACKED then skips making it again for every sigma.
+ *                Rows of any width take the tiled path (the copy is made in x panels of 512 columns); what bounds a
+ *                block there is that its tiles, tables and copy fit the four intermediate arrays of d_work with
+ *                32-bit offsets -- z tiles are 16 planes deep, so a block of few planes whose rows fill their pitch
+ *                may not fit the slot nz ny px -- and at most 8 distinct widths / depths in a batch; a batch that
+ *                does not fit goes on to MMX_ZX_PACKED (row pitch <= 320 floats) or the separate passes.
  *   h_zx_path  : optional out (host): the MMX_ZX_* kernel this call actually ran (MMX_ZX_SEPARATE when the
  *                geometry fell back to the three separate passes)                                          */
 typedef enum {

@@ -803,93 +803,115 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
 // k-step are one contiguous KiB
 // wherever the window starts.  Planes past the block and columns past the row read as zero.  Any strides, any
 // alignment: the copy is what lifts zx4's 16-byte alignment rules.
-template <typename InT>
+// WIDE: rows of more than 512 voxels, taken in x panels of 512 columns (64 units) through the same LDS tile -- panel p
+// fills units 64 p .. 64 p + 63 of the row tile, the unit order of the copy is the same.  Rows up to 512 voxels run the
+// one-panel form (WIDE = false): the same statements with x0 = 0 and the row's own unit count, no loop and no second
+// barrier (C3's rows are 261 voxels: profiles/r10_c3_ab.txt has its zxpack times against the kernel without panels).
+template <typename InT, bool WIDE>
 __global__ void __launch_bounds__(256)
 zx6_pack_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y, int64_t stride_x,
                 const mmx_block* __restrict__ blocks, uint16_t* __restrict__ pack, int64_t pack_stride)
 {
-    constexpr int PITCH = 512 + 8;                       // uint16 per LDS row (fused paths take px <= 512)
+    constexpr int PITCH = 512 + 8;                       // uint16 per LDS row: one panel of 512 columns
     __shared__ __attribute__((aligned(16))) uint16_t tile[16][PITCH];
     const mmx_block bd = blocks[blockIdx.y];
-    const int ntz = (bd.nz + 15) >> 4, nch8 = (bd.nx + 7) >> 3;
+    const int ntz = (bd.nz + 15) >> 4, nrow8 = (bd.nx + 7) >> 3;
     const int yt = blockIdx.x;
     if (yt >= bd.ny * ntz) return;
     const int y = yt / ntz, t = yt - y * ntz;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const InT* src = vol + bd.src_off + (int64_t)y * stride_y;
+    const InT* src0 = vol + bd.src_off + (int64_t)y * stride_y;
     // rows that start on 8-byte boundaries (the usual case: block origins on multiples of 4 voxels): 4 voxels per
     // lane and load; the last, partial group of a row and everything else one voxel at a time
     bool quads = false;
     if constexpr (sizeof(InT) == 2)
         quads = stride_x == 1 && ((bd.src_off | stride_y | stride_z) & 3) == 0 && (reinterpret_cast<uintptr_t>(vol) & 7) == 0;
-    if (quads) {
-        // All of a wave's loads -- four planes x (up to) two 4-voxel groups per lane -- are issued before the first
-        // LDS write: a workgroup moves 8 KiB in and 8 KiB out and nothing else hides its load latency (the loop form
-        // had one or two loads in flight per wave: 2.8 TB/s).
-        u2_4 v[4][2];
-        bool have[4][2];
+    // panel p: its first column, its units, the voxels the row still holds from there (the zero fill starts at nx)
+    auto panel = [&](int p) __attribute__((always_inline)) {
+        const int x0 = WIDE ? 512 * p : 0;
+        const int nch8 = WIDE ? (nrow8 - 64 * p < 64 ? nrow8 - 64 * p : 64) : nrow8;
+        const int nx = bd.nx - x0;
+        const InT* src = src0 + (int64_t)x0 * stride_x;
+        if (quads) {
+            // All of a wave's loads -- four planes x (up to) two 4-voxel groups per lane -- are issued before the first
+            // LDS write: a workgroup moves 8 KiB in and 8 KiB out and nothing else hides its load latency (the loop form
+            // had one or two loads in flight per wave: 2.8 TB/s).
+            u2_4 v[4][2];
+            bool have[4][2];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int z = 16 * t + 4 * wave + i;
-            const InT* row = src + (int64_t)(z < bd.nz ? z : 0) * stride_z;
+            for (int i = 0; i < 4; ++i) {
+                const int z = 16 * t + 4 * wave + i;
+                const InT* row = src + (int64_t)(z < bd.nz ? z : 0) * stride_z;
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int x = lane * 4 + 256 * h;
-                have[i][h] = x < 8 * nch8;
-                v[i][h] = (u2_4){0u, 0u};
-                if (have[i][h] && z < bd.nz) {
-                    if (x + 3 < bd.nx) {
-                        v[i][h] = *reinterpret_cast<const u2_4*>(row + x);
-                    } else {
-                        unsigned e[4];
+                for (int h = 0; h < 2; ++h) {
+                    const int x = lane * 4 + 256 * h;
+                    have[i][h] = x < 8 * nch8;
+                    v[i][h] = (u2_4){0u, 0u};
+                    if (have[i][h] && z < bd.nz) {
+                        if (x + 3 < nx) {
+                            v[i][h] = *reinterpret_cast<const u2_4*>(row + x);
+                        } else {
+                            unsigned e[4];
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) e[j] = x + j < bd.nx ? (unsigned)row[x + j] : 0u;
-                        v[i][h] = (u2_4){e[0] | (e[1] << 16), e[2] | (e[3] << 16)};
+                            for (int j = 0; j < 4; ++j) e[j] = x + j < nx ? (unsigned)row[x + j] : 0u;
+                            v[i][h] = (u2_4){e[0] | (e[1] << 16), e[2] | (e[3] << 16)};
+                        }
                     }
                 }
             }
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int h = 0; h < 2; ++h)
+                    if (have[i][h]) *reinterpret_cast<u2_4*>(&tile[4 * wave + i][lane * 4 + 256 * h]) = v[i][h];
+        } else
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int r = 4 * wave + i, z = 16 * t + r;
+            if (z >= bd.nz) {
+                for (int x = lane * 4; x < 8 * nch8; x += 256) *reinterpret_cast<u2_4*>(&tile[r][x]) = (u2_4){0u, 0u};
+            } else {
+                for (int x = lane; x < 8 * nch8; x += 64)
+                    tile[r][x] = x < nx ? (uint16_t)((unsigned)src[(int64_t)z * stride_z + (int64_t)x * stride_x] << (sizeof(InT) == 1 ? 8 : 0))
+                                           : (uint16_t)0;     // (uint8 voxels go to the HIGH byte: the exact high float16 piece carries them)
+            }
         }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-                if (have[i][h]) *reinterpret_cast<u2_4*>(&tile[4 * wave + i][lane * 4 + 256 * h]) = v[i][h];
-    } else
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int r = 4 * wave + i, z = 16 * t + r;
-        if (z >= bd.nz) {
-            for (int x = lane * 4; x < 8 * nch8; x += 256) *reinterpret_cast<u2_4*>(&tile[r][x]) = (u2_4){0u, 0u};
-        } else {
-            for (int x = lane; x < 8 * nch8; x += 64)
-                tile[r][x] = x < bd.nx ? (uint16_t)((unsigned)src[(int64_t)z * stride_z + (int64_t)x * stride_x] << (sizeof(InT) == 1 ? 8 : 0))
-                                       : (uint16_t)0;     // (uint8 voxels go to the HIGH byte: the exact high float16 piece carries them)
+        __syncthreads();
+        u4_4* dst = reinterpret_cast<u4_4*>(pack + (int64_t)bd.slot * pack_stride) + (int64_t)yt * nrow8 * 16 + (WIDE ? 1024 * p : 0);
+        for (int u = threadIdx.x; u < nch8 * 16; u += 256) {
+            const int j = u >> 4, r = u & 15;
+            dst[u] = *reinterpret_cast<const u4_4*>(&tile[r][8 * j]);
         }
-    }
-    __syncthreads();
-    u4_4* dst = reinterpret_cast<u4_4*>(pack + (int64_t)bd.slot * pack_stride) + (int64_t)yt * nch8 * 16;
-    for (int u = threadIdx.x; u < nch8 * 16; u += 256) {
-        const int j = u >> 4, r = u & 15;
-        dst[u] = *reinterpret_cast<const u4_4*>(&tile[r][8 * j]);
+    };
+    if constexpr (WIDE) {
+#pragma unroll 1
+        for (int p = 0; p < (nrow8 + 63) >> 6; ++p) {
+            if (p) __syncthreads();                      // (the panel before is out of the tile)
+            panel(p);
+        }
+    } else {
+        panel(0);
     }
 }
 
 // The same copy for float32 voxels, split into float16 pieces on the way (v = hi + lo / 2048: 22 significant bits, what
 // the fragments carry too): per unit the 16 planes' high pieces (256 bytes), then their low pieces.  Valid for
 // |v| < 65504 and loses nothing worth having above ~2^-10: the caller vouches for the range (MMX_ZX_FLOAT_RANGE_OK).
+// (WIDE: x panels of 512 columns, as in zx6_pack_kernel)
+template <bool WIDE>
 __global__ void __launch_bounds__(256)
 zx6_pack_f32_kernel(const float* __restrict__ vol, int64_t stride_z, int64_t stride_y, int64_t stride_x,
                     const mmx_block* __restrict__ blocks, uint16_t* __restrict__ pack, int64_t pack_stride)
 {
-    constexpr int PITCH = 512 + 4;                       // dwords (hi | lo << 16) per LDS row
+    constexpr int PITCH = 512 + 4;                       // dwords (hi | lo << 16) per LDS row: one panel of 512 columns
     __shared__ __attribute__((aligned(16))) unsigned tile[16][PITCH];
     const mmx_block bd = blocks[blockIdx.y];
-    const int ntz = (bd.nz + 15) >> 4, nch8 = (bd.nx + 7) >> 3;
+    const int ntz = (bd.nz + 15) >> 4, nrow8 = (bd.nx + 7) >> 3;
     const int yt = blockIdx.x;
     if (yt >= bd.ny * ntz) return;
     const int y = yt / ntz, t = yt - y * ntz;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const float* src = vol + bd.src_off + (int64_t)y * stride_y;
+    const float* src0 = vol + bd.src_off + (int64_t)y * stride_y;
     auto pieces = [](float v) __attribute__((always_inline)) {
         const _Float16 h = (_Float16)v;
         const _Float16 l = (_Float16)((v - (float)h) * kLoScale);
@@ -897,39 +919,54 @@ zx6_pack_f32_kernel(const float* __restrict__ vol, int64_t stride_z, int64_t str
     };
     // rows that start on 16-byte boundaries (preprocessed slot buffers, most float images): 4 voxels per lane and load
     const bool quads = stride_x == 1 && ((bd.src_off | stride_y | stride_z) & 3) == 0 && (reinterpret_cast<uintptr_t>(vol) & 15) == 0;
+    auto panel = [&](int p) __attribute__((always_inline)) {
+        const int x0 = WIDE ? 512 * p : 0;
+        const int nch8 = WIDE ? (nrow8 - 64 * p < 64 ? nrow8 - 64 * p : 64) : nrow8;
+        const int nx = bd.nx - x0;
+        const float* src = src0 + (int64_t)x0 * stride_x;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int r = 4 * wave + i, z = 16 * t + r;
-        if (quads && z < bd.nz) {
-            const float* row = src + (int64_t)z * stride_z;
-            for (int x = lane * 4; x < 8 * nch8; x += 256) {
-                f4_4 v = {0.f, 0.f, 0.f, 0.f};
-                if (x + 3 < bd.nx) v = *reinterpret_cast<const f4_4*>(row + x);
-                else
-                    for (int j = 0; j < 4; ++j) v[j] = x + j < bd.nx ? row[x + j] : 0.f;
-                *reinterpret_cast<u4_4*>(&tile[r][x]) = (u4_4){pieces(v[0]), pieces(v[1]), pieces(v[2]), pieces(v[3])};
-            }
-        } else {
-            for (int x = lane; x < 8 * nch8; x += 64) {
-                float v = 0.f;
-                if (z < bd.nz && x < bd.nx) v = src[(int64_t)z * stride_z + (int64_t)x * stride_x];
-                tile[r][x] = pieces(v);
+        for (int i = 0; i < 4; ++i) {
+            const int r = 4 * wave + i, z = 16 * t + r;
+            if (quads && z < bd.nz) {
+                const float* row = src + (int64_t)z * stride_z;
+                for (int x = lane * 4; x < 8 * nch8; x += 256) {
+                    f4_4 v = {0.f, 0.f, 0.f, 0.f};
+                    if (x + 3 < nx) v = *reinterpret_cast<const f4_4*>(row + x);
+                    else
+                        for (int j = 0; j < 4; ++j) v[j] = x + j < nx ? row[x + j] : 0.f;
+                    *reinterpret_cast<u4_4*>(&tile[r][x]) = (u4_4){pieces(v[0]), pieces(v[1]), pieces(v[2]), pieces(v[3])};
+                }
+            } else {
+                for (int x = lane; x < 8 * nch8; x += 64) {
+                    float v = 0.f;
+                    if (z < bd.nz && x < nx) v = src[(int64_t)z * stride_z + (int64_t)x * stride_x];
+                    tile[r][x] = pieces(v);
+                }
             }
         }
-    }
-    __syncthreads();
-    u4_4* dst = reinterpret_cast<u4_4*>(pack + (int64_t)bd.slot * pack_stride) + (int64_t)yt * nch8 * 32;
-    for (int u = threadIdx.x; u < nch8 * 16; u += 256) {
-        const int j = u >> 4, r = u & 15;
-        const u4_4 a = *reinterpret_cast<const u4_4*>(&tile[r][8 * j]);
-        const u4_4 b = *reinterpret_cast<const u4_4*>(&tile[r][8 * j + 4]);
-        // dwords (hi | lo << 16) of 8 columns -> 4 dwords of packed high pieces, 4 of packed low pieces
-        const u4_4 hi = {__builtin_amdgcn_perm(a[1], a[0], 0x05040100u), __builtin_amdgcn_perm(a[3], a[2], 0x05040100u),
-                         __builtin_amdgcn_perm(b[1], b[0], 0x05040100u), __builtin_amdgcn_perm(b[3], b[2], 0x05040100u)};
-        const u4_4 lo = {__builtin_amdgcn_perm(a[1], a[0], 0x07060302u), __builtin_amdgcn_perm(a[3], a[2], 0x07060302u),
-                         __builtin_amdgcn_perm(b[1], b[0], 0x07060302u), __builtin_amdgcn_perm(b[3], b[2], 0x07060302u)};
-        dst[j * 32 + r] = hi;
-        dst[j * 32 + 16 + r] = lo;
+        __syncthreads();
+        u4_4* dst = reinterpret_cast<u4_4*>(pack + (int64_t)bd.slot * pack_stride) + (int64_t)yt * nrow8 * 32 + (WIDE ? 2048 * p : 0);
+        for (int u = threadIdx.x; u < nch8 * 16; u += 256) {
+            const int j = u >> 4, r = u & 15;
+            const u4_4 a = *reinterpret_cast<const u4_4*>(&tile[r][8 * j]);
+            const u4_4 b = *reinterpret_cast<const u4_4*>(&tile[r][8 * j + 4]);
+            // dwords (hi | lo << 16) of 8 columns -> 4 dwords of packed high pieces, 4 of packed low pieces
+            const u4_4 hi = {__builtin_amdgcn_perm(a[1], a[0], 0x05040100u), __builtin_amdgcn_perm(a[3], a[2], 0x05040100u),
+                             __builtin_amdgcn_perm(b[1], b[0], 0x05040100u), __builtin_amdgcn_perm(b[3], b[2], 0x05040100u)};
+            const u4_4 lo = {__builtin_amdgcn_perm(a[1], a[0], 0x07060302u), __builtin_amdgcn_perm(a[3], a[2], 0x07060302u),
+                             __builtin_amdgcn_perm(b[1], b[0], 0x07060302u), __builtin_amdgcn_perm(b[3], b[2], 0x07060302u)};
+            dst[j * 32 + r] = hi;
+            dst[j * 32 + 16 + r] = lo;
+        }
+    };
+    if constexpr (WIDE) {
+#pragma unroll 1
+        for (int p = 0; p < (nrow8 + 63) >> 6; ++p) {
+            if (p) __syncthreads();                      // (the panel before is out of the tile)
+            panel(p);
+        }
+    } else {
+        panel(0);
     }
 }
 
@@ -1037,7 +1074,6 @@ int mmx_zx6_plan_make(const mmx_block* h_blocks, int n_blocks, int64_t slot_elem
     if (!collect_classes(h_blocks, n_blocks, &cl)) return MMX_ERR_UNSUPPORTED;
     for (int i = 0; i < n_blocks; ++i) {
         const mmx_block& b = h_blocks[i];
-        if (b.px > 512) return MMX_ERR_UNSUPPORTED;
         const int ntx = (b.nx + 15) / 16, ntz = (b.nz + 15) / 16, nch8 = (b.nx + 7) / 8;
         const int64_t te = (int64_t)ntx * ntz * b.ny * 256, pe = (int64_t)b.ny * ntz * nch8 * 128 * pieces;
         if (te > tile) tile = te;
@@ -1063,19 +1099,26 @@ int mmx_zx6_plan_make(const mmx_block* h_blocks, int n_blocks, int64_t slot_elem
 int mmx_launch_zx6_pack(const mmx_volume* vol, const mmx_block* d_blocks, const mmx_block* h_blocks, int n_blocks,
                         const mmx_zx6_plan& plan, void* d_work, hipStream_t stream)
 {
-    (void)h_blocks;
     if (!mmx_voxels_ok(vol)) return MMX_ERR_UNSUPPORTED;
     uint16_t* pack = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(d_work) + plan.pack_off);
     dim3 grid(plan.max_rowtiles, n_blocks);
-    if (vol->dtype == MMX_F32)
-        hipLaunchKernelGGL(zx6_pack_f32_kernel, grid, dim3(256), 0, stream, (const float*)vol->d_data,
-                           vol->stride_z, vol->stride_y, vol->stride_x, d_blocks, pack, plan.pack_stride);
-    else if (vol->dtype == MMX_U16)
-        hipLaunchKernelGGL((zx6_pack_kernel<uint16_t>), grid, dim3(256), 0, stream, (const uint16_t*)vol->d_data,
-                           vol->stride_z, vol->stride_y, vol->stride_x, d_blocks, pack, plan.pack_stride);
-    else
-        hipLaunchKernelGGL((zx6_pack_kernel<uint8_t>), grid, dim3(256), 0, stream, (const uint8_t*)vol->d_data,
-                           vol->stride_z, vol->stride_y, vol->stride_x, d_blocks, pack, plan.pack_stride);
+    // rows beyond one LDS panel of 512 columns anywhere in the batch: the panelled kernels for all of it
+    bool wide = false;
+    for (int i = 0; i < n_blocks; ++i) wide = wide || h_blocks[i].nx > 512;
+    auto launch = [&](auto kernel, auto* data) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, data, vol->stride_z, vol->stride_y, vol->stride_x, d_blocks, pack,
+                           plan.pack_stride);
+    };
+    if (vol->dtype == MMX_F32) {
+        if (wide) launch(zx6_pack_f32_kernel<true>, (const float*)vol->d_data);
+        else launch(zx6_pack_f32_kernel<false>, (const float*)vol->d_data);
+    } else if (vol->dtype == MMX_U16) {
+        if (wide) launch(zx6_pack_kernel<uint16_t, true>, (const uint16_t*)vol->d_data);
+        else launch(zx6_pack_kernel<uint16_t, false>, (const uint16_t*)vol->d_data);
+    } else {
+        if (wide) launch(zx6_pack_kernel<uint8_t, true>, (const uint8_t*)vol->d_data);
+        else launch(zx6_pack_kernel<uint8_t, false>, (const uint8_t*)vol->d_data);
+    }
     return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
 }
 

@@ -16,8 +16,8 @@
 #define MMX_COL_PREFETCH 4
 // widest row pitch (floats) zx2_kernel takes: 5 producer waves
 #define MMX_PACKED_MAX_PX 320
-// widest row pitch the fused kernels (zx2 / zx4) and the tiled path's plan take
-#define MMX_FUSED_MAX_PX 512
+// (the tiled kernels take any row pitch: their voxel copy is made in x panels of 512 columns, and what bounds a block is
+//  its plan -- 32-bit offsets inside a block's tiles and copy, the workspace, MMX_ZX4_MAXCLS width / depth classes)
 // largest radius of the matrix-core Y pass (ym_kernel)
 #define MMX_YM_MAX_RADIUS 24
 // xpass_kernel: outputs per thread; 16-byte loads and halo loads per thread, array and row group
@@ -107,7 +107,7 @@ inline bool mmx_xpass_accepts(const mmx_batch_geom& g, int radius)
 inline bool mmx_fused_accepts(const mmx_volume* vol, const mmx_batch_geom& g, int radius)
 {
     return mmx_ring_radius(radius) && mmx_lane_ok(vol, g) && g.min_ny >= radius + MMX_COL_PREFETCH && g.min_nz >= radius + 1 &&
-           g.min_nx >= radius && g.max_px <= MMX_FUSED_MAX_PX;
+           g.min_nx >= radius;
 }
 // zx2_kernel's own limits: the row pitch its producer waves cover, 32-bit scalar plane offsets
 inline bool mmx_zx2_launch_accepts(const mmx_volume* vol, int max_px, int radius)

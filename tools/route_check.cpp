@@ -145,8 +145,35 @@ int check_table()
          QUADS, true, true, {T16, T16}},
         {"row pitch 416 without: neither fused kernel, the separate passes", MMX_U16, 0, {40, 48, 400, 416, true, true, false},
          A, 0, kBandQ16, {8, 24}, MMX_OK, 1, 0, false, false, {S, S}},
-        {"rows 530 wide: the separate passes", MMX_U16, 0, {40, 48, 530, 544, true, true, false}, A, 0, kBandQ16, {8}, MMX_OK, 1, 0,
-         false, false, {S}},
+        {"rows 530 wide without a plan: the separate passes", MMX_U16, 0, {40, 48, 530, 544, true, true, false}, A, 0, kBandQ16,
+         {8}, MMX_OK, 1, 0, false, false, {S}},
+        // ---- rows beyond 512 floats with a plan: the tiled kernels at any pitch, one radius of each geometry class
+        {"row pitch 544, uint16: 16-bit tiles, quads", MMX_U16, 0, {40, 48, 530, 544, true, true, true}, A, 0, kBandQ16,
+         {8, 16, 24}, MMX_OK, 1, QUADS, true, true, {T16, T16, T16}},
+        {"row pitch 1024, uint16", MMX_U16, 0, {40, 48, 1024, 1024, true, true, true}, A, 0, kBandQ16, {8, 16, 24}, MMX_OK, 1,
+         QUADS, true, true, {T16, T16, T16}},
+        {"row pitch 1056, uint16", MMX_U16, 0, {40, 48, 1025, 1056, true, true, true}, A, 0, kBandQ16, {8, 16, 24}, MMX_OK, 1,
+         QUADS, true, true, {T16, T16, T16}},
+        {"row pitch 2048, uint16", MMX_U16, 0, {40, 48, 2048, 2048, true, true, true}, A, 0, kBandQ16, {8, 16, 24}, MMX_OK, 1,
+         QUADS, true, true, {T16, T16, T16}},
+        {"row pitch 544, float voxels in [0, 1]", MMX_F32, 1.f, {40, 48, 530, 544, true, true, true}, A, 0, kBandQ16,
+         {8, 16, 24}, MMX_OK, 1, QUADS, true, true, {T16, T16, T16}},
+        {"row pitch 1024, float voxels in [0, 1]", MMX_F32, 1.f, {40, 48, 1024, 1024, true, true, true}, A, 0, kBandQ16,
+         {8, 16, 24}, MMX_OK, 1, QUADS, true, true, {T16, T16, T16}},
+        {"row pitch 1056, float voxels in [0, 1]", MMX_F32, 1.f, {40, 48, 1025, 1056, true, true, true}, A, 0, kBandQ16,
+         {8, 16, 24}, MMX_OK, 1, QUADS, true, true, {T16, T16, T16}},
+        {"row pitch 2048, float voxels in [0, 1]", MMX_F32, 1.f, {40, 48, 2048, 2048, true, true, true}, A, 0, kBandQ16,
+         {8, 16, 24}, MMX_OK, 1, QUADS, true, true, {T16, T16, T16}},
+        {"row pitch 544, float voxels with no stated range: the separate passes", MMX_F32, 0, {40, 48, 530, 544, true, true, true},
+         A, 0, kBandQ16, {8, 16, 24}, MMX_OK, 1, 0, false, false, {S, S, S}},
+        {"row pitch 1024, float voxels with no stated range", MMX_F32, 0, {40, 48, 1024, 1024, true, true, true}, A, 0, kBandQ16,
+         {8, 16, 24}, MMX_OK, 1, 0, false, false, {S, S, S}},
+        {"row pitch 1056, float voxels with no stated range", MMX_F32, 0, {40, 48, 1025, 1056, true, true, true}, A, 0, kBandQ16,
+         {8, 16, 24}, MMX_OK, 1, 0, false, false, {S, S, S}},
+        {"row pitch 2048, float voxels with no stated range", MMX_F32, 0, {40, 48, 2048, 2048, true, true, true}, A, 0, kBandQ16,
+         {8, 16, 24}, MMX_OK, 1, 0, false, false, {S, S, S}},
+        {"rows 530 wide with a plan, radii 24, 25, 26: laid out as before -- wide, never tiled", MMX_U16, 0,
+         {40, 48, 530, 544, true, true, true}, A, 0, kBandQ16, {24, 25, 26}, MMX_OK, 1, ROWS, false, false, {W, W, W}},
         {"rows 2100 wide: the X pass generic", MMX_U16, 0, {40, 48, 2100, 2112, true, true, false}, A, 0, kBandQ16, {8}, MMX_OK, 1,
          0, false, false, {{SEP, 0, MMX_Y_NONE, MMX_ZX_SEPARATE, 0, 3}}},
         // (tests/test_gpu_routes.py, test A) radius 18 needs ny >= 22 for the fused path: quads and none -> no entries
@@ -222,7 +249,8 @@ int sweep()
     static double W0[kTab][kTab], W2[kTab][kTab], NORM[kTab];
     for (int r = 0; r <= MMX_MAX_RADIUS_GENERIC; ++r) gauss(r, W0[r], W2[r], &NORM[r]);
     // extents 1 .. 80 on a coarse grid -- every radius below meets each limit (r, r + 1, r + MMX_COL_PREFETCH) on them --
-    // and the rows around the pitch limits of the packed kernel (320), the fused path (512) and the X pass (2048)
+    // and the rows around the pitch limit of the packed kernel (320), the panel of the tiled path's voxel copy (512: no limit
+    // of any route) and the X pass's limit (2048)
     const int ext[] = {1, 12, 29, 80};
     const int wide[] = {1, 24, 28, 64, 320, 321, 512, 513, 2048, 2049};
     const int modes[] = {MMX_ZX_AUTO, MMX_ZX_SEPARATE, MMX_ZX_PACKED, MMX_ZX_TILED, MMX_ZX_TILED_Q16, MMX_ZX_WIDE,
@@ -269,7 +297,7 @@ int sweep()
                     if (r.family == WID) ok = mmx_wide_launch_accepts(&vol, radius) && mmx_wide_accepts(&vol, g, radius);
                     else if (r.family == TIL) {
                         ok = mmx_zx6_launch_accepts(&vol, g.min_nz, g.min_nx, radius) && g.plan_status == MMX_OK &&
-                             g.max_px <= MMX_FUSED_MAX_PX && r.makes_copy != r.trusts_copy;
+                             r.makes_copy != r.trusts_copy;       // (at any row pitch: the plan is what bounds a block)
                         float y0[MMX_MAX_RADIUS_FAST + 1], y2[MMX_MAX_RADIUS_FAST + 1];
                         for (int k = 0; k <= radius; ++k) { y0[k] = (float)(-norm * w0[k]); y2[k] = (float)(-norm * w2[k]); }
                         if (r.y_kernel == MMX_Y_YM)
