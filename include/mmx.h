@@ -139,6 +139,8 @@ int mmx_device_count(void);
  *                per 4 planes x 16 columns, entry y * ceil(nz/4) * ceil(nx/16) + (z >> 2) * ceil(nx/16) + (x >> 4),
  *                bit ((z & 3) << 4) | (x & 15), the unwritten segments of d_log being those 64 voxels.  Pass the
  *                value on to mmx_peaks_batch (every sigma of a batch must have produced the same layout).
+ *                The executable statement of both layouts and of the rule for word 0 is csrc/mmx_entries.h: every
+ *                kernel that writes or reads entries, and the host's "do they fit", take them from there.
  *   zx_mode    : how the Z and X passes run (a per-call argument: the library keeps no mode).
  *                MMX_ZX_AUTO (default): the fastest kernel that takes the geometry (MMX_ZX_TILED for integer
  *                voxels, else MMX_ZX_PACKED, else the separate passes); the others exist for cross-checks and

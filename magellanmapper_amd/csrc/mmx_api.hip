@@ -183,9 +183,8 @@ void mmx_batch_geom_make(const mmx_volume* vol, const mmx_block* h_blocks, int n
         if (b.nz * b.px > g->max_ycols) g->max_ycols = b.nz * b.px;
         if (b.nz * b.ny > g->max_rows) g->max_rows = b.nz * b.ny;
         if (b.nz * b.ny * b.px > g->max_vox) g->max_vox = b.nz * b.ny * b.px;
-        // the entries of a block (ny rows of ceil(nz * px / 64) words, or ny ceil(nz / 4) ceil(nx / 16) quads)
-        if ((int64_t)b.ny * (((int64_t)b.nz * b.px + 63) >> 6) > (slot_elems >> 5) - 1) g->rows_fit = false;
-        if ((int64_t)b.ny * ((b.nz + 3) >> 2) * ((b.nx + 15) >> 4) > (slot_elems >> 5) - 1) g->quads_fit = false;
+        if (!mmx_entries_fit(MMX_MASK_ROWS, b.nz, b.ny, b.nx, b.px, slot_elems)) g->rows_fit = false;
+        if (!mmx_entries_fit(MMX_MASK_QUADS, b.nz, b.ny, b.nx, b.px, slot_elems)) g->quads_fit = false;
         if (vol) {
             const int64_t lane = (int64_t)(b.ny - 1) * vol->stride_y + (int64_t)(b.nx - 1) * vol->stride_x;
             if (lane > g->max_lane_in) g->max_lane_in = lane;

@@ -26,7 +26,7 @@
 
 #include <type_traits>
 
-#include "mmx_common.h"
+#include "mmx_device.h"
 
 namespace {
 
@@ -34,41 +34,6 @@ namespace {
 #define MMX_PREFETCH 4
 #endif
 constexpr int kPrefetch = MMX_PREFETCH;  // D: loads kept in flight per thread beyond the live window
-
-// One reflection is enough when the extent is at least R + kPrefetch (the host routes
-// thinner blocks to the generic kernel): valid for -n <= i < 2n.
-__device__ __forceinline__ int reflect_once(int i, int n)
-{
-    i = i < 0 ? -1 - i : i;
-    return i >= n ? 2 * n - 1 - i : i;
-}
-
-// Buffer descriptors: wave-uniform 48-bit base in SGPRs + one constant 32-bit per-lane byte
-// offset in a VGPR.  The per-step address change is pure SALU work on the base.
-using rsrc_t = __amdgpu_buffer_rsrc_t;
-__device__ __forceinline__ rsrc_t make_rsrc(const void* p)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7fffffff, 0x00020000);
-}
-
-// raw voxel bits as they come from memory; converted ("activated") when first needed, D steps
-// after the load was issued, so the conversion does not pull the s_waitcnt forward.
-template <typename T> struct voxel_io;
-template <> struct voxel_io<uint16_t> {
-    static __device__ __forceinline__ float load(rsrc_t r, unsigned voff)
-    { return __uint_as_float((unsigned)__builtin_amdgcn_raw_buffer_load_b16(r, voff, 0, 0)); }
-    static __device__ __forceinline__ float activate(float raw) { return (float)__float_as_uint(raw); }
-};
-template <> struct voxel_io<uint8_t> {
-    static __device__ __forceinline__ float load(rsrc_t r, unsigned voff)
-    { return __uint_as_float((unsigned)__builtin_amdgcn_raw_buffer_load_b8(r, voff, 0, 0)); }
-    static __device__ __forceinline__ float activate(float raw) { return (float)__float_as_uint(raw); }
-};
-template <> struct voxel_io<float> {
-    static __device__ __forceinline__ float load(rsrc_t r, unsigned voff)
-    { return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff, 0, 0)); }
-    static __device__ __forceinline__ float activate(float raw) { return raw; }
-};
 
 __device__ __forceinline__ void store_f32(float v, rsrc_t r, unsigned voff)
 {
@@ -83,7 +48,7 @@ zpass_kernel(const InT* __restrict__ vol, int64_t stride_z, int stride_y, int st
              const mmx_block* __restrict__ blocks, int64_t slot_elems,
              float* __restrict__ gz, float* __restrict__ gzz, mmx_taps_f32 taps)
 {
-    using io = voxel_io<InT>;
+    using io = vox<InT>;
     constexpr int N = 2 * R + 1;
     constexpr int M = N + kPrefetch;
     const mmx_block bd = blocks[blockIdx.y];
@@ -104,7 +69,7 @@ zpass_kernel(const InT* __restrict__ vol, int64_t stride_z, int stride_y, int st
 #pragma unroll
     for (int j = -R; j < R + kPrefetch; ++j) {
         const float raw = io::load(make_rsrc(in + (int64_t)reflect_once(j, n) * stride_z), voff_in);
-        ring[(j + M) % M] = j < R ? io::activate(raw) : raw;
+        ring[(j + M) % M] = j < R ? io::act(raw) : raw;
     }
 
     const InT* pin = in + (int64_t)(R + kPrefetch) * stride_z;  // plane of the next prefetch
@@ -115,7 +80,7 @@ zpass_kernel(const InT* __restrict__ vol, int64_t stride_z, int stride_y, int st
         else
             nxt = io::load(make_rsrc(pin), voff_in);
         pin += stride_z;
-        ring[(s + R) % M] = io::activate(ring[(s + R) % M]);  // loaded kPrefetch steps ago
+        ring[(s + R) % M] = io::act(ring[(s + R) % M]);  // loaded kPrefetch steps ago
         const float c = ring[s];
         float a0 = c * taps.w0[0];
         float a2 = c * taps.w2[0];
@@ -159,7 +124,7 @@ ypass_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems,
              const float* __restrict__ gz, const float* __restrict__ gzz,
              float* __restrict__ oa, float* __restrict__ obc, mmx_taps_f32 taps)
 {
-    using io = voxel_io<float>;
+    using io = vox<float>;
     constexpr int N = 2 * R + 1;
     constexpr int M = N + kPrefetch;
     const mmx_block bd = blocks[blockIdx.y];

@@ -26,10 +26,6 @@ int launch_z(const mmx_volume* vol, const mmx_block* d_blocks, int n_blocks, int
 }
 }  // namespace
 
-#define MMX_FOR_EACH_RADIUS(X) \
-    X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) \
-    X(17) X(18) X(19) X(20) X(21) X(22) X(23) X(24)
-
 int mmx_launch_zpass(const mmx_volume* vol, const mmx_block* d_blocks, int n_blocks, int max_cols,
                      int64_t slot_elems, const mmx_taps_f32& taps, int radius,
                      float* d_gz, float* d_gzz, hipStream_t stream)

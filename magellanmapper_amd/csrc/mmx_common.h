@@ -97,6 +97,9 @@ struct mmx_batch_geom {
 // (vol: NULL for callers that read no voxels -- no plan, no input offsets)
 void mmx_batch_geom_make(const mmx_volume* vol, const mmx_block* h_blocks, int n_blocks, int64_t slot_elems, mmx_batch_geom* g);
 
+// The NMS entry layouts and the rule that decides an entry (host: the index arithmetic; device: the rule)
+#include "mmx_entries.h"
+
 // The kernel-path rules: the launchers' predicates, the route of a scale and of a ladder (host-only, no launch)
 #include "mmx_route.h"
 

@@ -11,47 +11,15 @@
 
 #include <type_traits>
 
-#include "mmx_common.h"
+#include "mmx_device.h"
 
 namespace {
-
-__device__ __forceinline__ int reflect_once(int i, int n)
-{
-    i = i < 0 ? -1 - i : i;
-    return i >= n ? 2 * n - 1 - i : i;
-}
-// reflect, then clamp: prefetches run up to 2G planes past the last needed one
-__device__ __forceinline__ int reflect_clamped(int i, int n)
-{
-    i = reflect_once(i, n);
-    return i < 0 ? 0 : (i >= n ? n - 1 : i);
-}
-
-using rsrc_t = __amdgpu_buffer_rsrc_t;
-__device__ __forceinline__ rsrc_t make_rsrc(const void* p)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7fffffff, 0x00020000);
-}
-template <typename T> struct vox;
-template <> struct vox<uint8_t> {
-    static __device__ __forceinline__ float load(rsrc_t r, unsigned o) { return __uint_as_float((unsigned)__builtin_amdgcn_raw_buffer_load_b8(r, o, 0, 0)); }
-    static __device__ __forceinline__ float act(float raw) { return (float)__float_as_uint(raw); }
-};
-template <> struct vox<uint16_t> {
-    static __device__ __forceinline__ float load(rsrc_t r, unsigned o) { return __uint_as_float((unsigned)__builtin_amdgcn_raw_buffer_load_b16(r, o, 0, 0)); }
-    static __device__ __forceinline__ float act(float raw) { return (float)__float_as_uint(raw); }
-};
-template <> struct vox<float> {
-    static __device__ __forceinline__ float load(rsrc_t r, unsigned o) { return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, o, 0, 0)); }
-    static __device__ __forceinline__ float act(float raw) { return raw; }
-};
 
 // ---------------------------------------------------------------- Y pass on (P, Q)
 #ifndef Y2_PF
 #define Y2_PF 4
 #endif
 constexpr int kPrefetch = Y2_PF;
-typedef float v2f __attribute__((ext_vector_type(2)));
 // (G''(y), G(y)) weights as pairs: the ring holds (P, Q) pairs, so one v_pk_add_f32 forms both pair sums of
 // a tap and one v_pk_fma_f32 accumulates (G''(y) P, G(y) Q); the two halves are added once per output.
 struct y2_taps {
@@ -82,22 +50,15 @@ y2_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems,
     const float* i2 = gq + sbase;
     const float* w1 = out + sbase;
 
-    // NMS pre-filter (optional): per 64 columns of a row one entry of two 64-bit words,
-    //   .x  one bit per voxel = "above thr - eps and not beaten by more than eps by its y and (same wave) x
-    //       neighbours" -- a superset of the local maxima, decided on the very float32 values computed here:
-    //       the NMS kernel only visits these bits (mmx_peaks.hip);
-    //   .y  one bit per voxel = "above thr - eps".  A 64-voxel segment without such a voxel (three quarters
-    //       of them on the benchmark volume) is NOT STORED: a value below the threshold can neither be a peak
-    //       nor out-vote a candidate, so the NMS kernel reads a neighbour only where .y != 0.
+    // NMS entries (optional; mmx_entries.h, MMX_MASK_ROWS): a wave's 64 columns are one entry per row.  A 64-voxel
+    // segment with nothing above the threshold (three quarters of them on the benchmark volume) is NOT STORED.
     const int lane = threadIdx.x & 63;
-    const int nwords = (ncol + 63) >> 6;
-    ulonglong2* mrow = MASK ? reinterpret_cast<ulonglong2*>(mask) + ((int64_t)bd.slot * slot_elems >> 5) + (col >> 6)
-                            : nullptr;      // entry of the row being decided (advanced by nwords per row)
-    unsigned long long ab_prev = 0;
+    const mmx_entry_geom eg = mmx_entry_geom_make(MMX_MASK_ROWS, bd.nz, bd.nx, bd.px);
+    ulonglong2* mrow = MASK ? reinterpret_cast<ulonglong2*>(mask) + mmx_entry_base(bd.slot, slot_elems) + mmx_entry_index(eg, z, x)
+                            : nullptr;
     const bool real = x < bd.nx;
     const bool has_l = lane > 0 && x > 0, has_r = lane < 63 && x + 1 < bd.nx && col + 1 < ncol;
-    float prev1 = -INFINITY, prev2 = -INFINITY, nbx_prev = -INFINITY;
-    int ydone = 0;       // outputs produced so far
+    mmx_pending_row<false> pend(mrow, eg.per_row, real, nms_lo, nms_eps);
 
     v2f r[M];     // (P, Q) window
 #pragma unroll
@@ -136,28 +97,12 @@ y2_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems,
         }
         a2 += b2;
         const float acc = a2.x + a2.y;
-        const unsigned long long ab = MASK ? __ballot(real & (acc > nms_lo)) : ~0ull;
+        const unsigned long long ab = MASK ? mmx_above_word(real, acc, nms_lo) : ~0ull;
         if (ab) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc), rsw, voff, woff, 0);
         woff += row_b;
         r[(s + R + kPrefetch) % M] = (v2f){n1, n2};
         if constexpr (MASK) {
-            // x neighbours by DPP wavefront shifts (no LDS crossbar traffic); lanes shifted in from
-            // outside the wave keep `acc`, which has_l / has_r discard
-            const float l = __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(
-                (int)__float_as_uint(acc), (int)__float_as_uint(acc), 0x138 /* wave_shr:1 */, 0xf, 0xf, false));
-            const float r = __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(
-                (int)__float_as_uint(acc), (int)__float_as_uint(acc), 0x130 /* wave_shl:1 */, 0xf, 0xf, false));
-            const float nbx = fmaxf(has_l ? l : -INFINITY, has_r ? r : -INFINITY);
-            if (ydone > 0) {      // decide row ydone - 1, now that its successor is known
-                const bool cand = real & (prev1 > nms_lo) &
-                                  !(fmaxf(fmaxf(prev2, acc), nbx_prev) > prev1 + nms_eps);
-                const unsigned long long m = __ballot(cand);
-                if (lane == 0) *mrow = make_ulonglong2(m, ab_prev);
-                mrow += nwords;
-            }
-            prev2 = prev1; prev1 = acc; nbx_prev = nbx;
-            ab_prev = ab;
-            ++ydone;
+            pend.push(acc, ab, mmx_x_neighbours<true>(acc, has_l, has_r));
         }
         __builtin_amdgcn_sched_barrier(0);
     };
@@ -175,11 +120,7 @@ y2_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems,
             step(s, std::true_type{}, y0 + s);
         }
     }
-    if constexpr (MASK) {     // the last row has no successor
-        const bool cand = real & (prev1 > nms_lo) & !(fmaxf(prev2, nbx_prev) > prev1 + nms_eps);
-        const unsigned long long m = __ballot(cand);
-        if (lane == 0) *mrow = make_ulonglong2(m, ab_prev);
-    }
+    if constexpr (MASK) pend.finish();
 }
 
 template <int R>
@@ -205,8 +146,8 @@ int launch_y2(const mmx_block* d_blocks, int n_blocks, int max_cols, int64_t slo
 // marches along y over 4 planes x 16 columns of it: one contiguous 256-byte piece per array and step, the next
 // one ntx ntz KiB further on -- at any time the workgroups of a block read inside the same few hundred KiB.  The LoG cube stays row-major (the NMS and re-scoring kernels
 // read single voxels from it): a wave stores four 64-byte row pieces, and only where something is above the
-// threshold.  NMS entries: per row y one entry per (4 planes, 16 columns) = this wave's footprint,
-// index y * (nzq * ntx) + (z >> 2) * ntx + (x >> 4), bit ((z & 3) << 4) | (x & 15)  (mmx_peaks.hip: layout 2).
+// threshold.  NMS entries: per row y one entry per (4 planes, 16 columns) = this wave's footprint
+// (mmx_entries.h, MMX_MASK_QUADS).
 // Q16: one dword per voxel in the tile, P = unorm16 (low half), Q = snorm16 (high half); their scales ride in the
 // weights.  Half the bytes and half the load instructions.
 template <int R, bool MASK, bool Q16>
@@ -237,9 +178,12 @@ y6_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile
     const unsigned voff = (unsigned)(zq * 64 + lane) * 4u;                          // inside a tile
     // (lanes past the block keep an in-range address: they never store)
     const unsigned ooff = (unsigned)((real ? z : 0) * bd.ny * bd.px + (real ? x : 0)) * 4u;   // row 0 of this voxel's column
-    const int nent = ((bd.nz + 3) >> 2) * ntx;
-    ulonglong2* mrow = MASK ? reinterpret_cast<ulonglong2*>(mask) + ((int64_t)bd.slot * slot_elems >> 5) +
-                              (4 * U + zq) * ntx + c
+    // (the pending row's state in locals, not in mmx_pending_row as in y2_kernel: in the struct some instantiations on
+    //  float32 tiles take two registers more)
+    const mmx_entry_geom eg = mmx_entry_geom_make(MMX_MASK_QUADS, bd.nz, bd.nx, bd.px);
+    const int nent = eg.per_row;
+    ulonglong2* mrow = MASK ? reinterpret_cast<ulonglong2*>(mask) + mmx_entry_base(bd.slot, slot_elems) +
+                              mmx_quads_entry(eg, 4 * U + zq, c)
                             : nullptr;
     unsigned long long ab_prev = 0;
     const bool has_l = xi > 0, has_r = xi < 15 && x + 1 < bd.nx;
@@ -287,7 +231,7 @@ y6_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile
         }
         a2 += b2;
         const float acc = a2.x + a2.y;
-        const unsigned long long ab = MASK ? __ballot(real & (acc > nms_lo)) : ~0ull;
+        const unsigned long long ab = MASK ? mmx_above_word(real, acc, nms_lo) : ~0ull;
         if (ab && real) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc), rsw, ooff, woff, 0);
         woff += row_b;
         if constexpr (Q16) r[(s + R + kPrefetch) % M] = unpack(__float_as_uint(n1));
@@ -299,17 +243,12 @@ y6_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile
             //  never looked at, and a row with nothing above it has no candidates -- wave-uniform branches)
             float nbx = -INFINITY;
             if (ab) {
-                const float l = __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(
-                    (int)__float_as_uint(acc), (int)__float_as_uint(acc), 0x111 /* row_shr:1 */, 0xf, 0xf, false));
-                const float rr = __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(
-                    (int)__float_as_uint(acc), (int)__float_as_uint(acc), 0x101 /* row_shl:1 */, 0xf, 0xf, false));
-                nbx = fmaxf(has_l ? l : -INFINITY, has_r ? rr : -INFINITY);
+                nbx = mmx_x_neighbours<false>(acc, has_l, has_r);
             }
             if (ydone > 0) {      // decide row ydone - 1, now that its successor is known
                 unsigned long long m = 0;
                 if (ab_prev) {
-                    const bool cand = real & (prev1 > nms_lo) &
-                                      !(fmaxf(fmaxf(prev2, acc), nbx_prev) > prev1 + nms_eps);
+                    const bool cand = mmx_candidate(real, prev1, nms_lo, nms_eps, prev2, acc, nbx_prev);
                     m = __ballot(cand);
                 }
                 if (lane == 0) *mrow = make_ulonglong2(m, ab_prev);
@@ -336,7 +275,7 @@ y6_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile
         }
     }
     if constexpr (MASK) {     // the last row has no successor
-        const bool cand = real & (prev1 > nms_lo) & !(fmaxf(prev2, nbx_prev) > prev1 + nms_eps);
+        const bool cand = mmx_candidate(real, prev1, nms_lo, nms_eps, prev2, nbx_prev);
         const unsigned long long m = __ballot(cand);
         if (lane == 0) *mrow = make_ulonglong2(m, ab_prev);
     }
@@ -361,10 +300,6 @@ int launch_y6(const mmx_block* d_blocks, int n_blocks, const mmx_zx6_plan& plan,
 }
 
 }  // namespace
-
-#define MMX_FOR_EACH_RADIUS(X) \
-    X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) \
-    X(17) X(18) X(19) X(20) X(21) X(22) X(23) X(24)
 
 int mmx_launch_y2(const mmx_block* d_blocks, int n_blocks, int max_cols, int64_t slot_elems,
                   const mmx_taps_f32& taps, int radius, const float* d_p, const float* d_q,

@@ -23,9 +23,7 @@
 
 #include <type_traits>
 
-#include "mmx_common.h"
-
-typedef float v2f __attribute__((ext_vector_type(2)));
+#include "mmx_device.h"
 
 struct mmx_taps_zx2 {
     v2f zw[MMX_MAX_RADIUS_FAST + 1];    // (w0z[k], w2z[k])
@@ -45,38 +43,9 @@ constexpr int kMaxPx = MMX_PACKED_MAX_PX;  // 5 producer waves
 #endif
 constexpr int kPF = ZX2_PF;  // groups of z planes in flight per producer lane
 
-__device__ __forceinline__ int reflect_once(int i, int n)
-{
-    i = i < 0 ? -1 - i : i;
-    return i >= n ? 2 * n - 1 - i : i;
-}
-__device__ __forceinline__ int reflect_clamped(int i, int n)
-{
-    i = reflect_once(i, n);
-    return i < 0 ? 0 : (i >= n ? n - 1 : i);
-}
 // LDS row layout in (Gz, Gzz) pairs: two pad pairs after every four, so that the consumers' 16-byte reads
 // at a 4-pair lane stride become a 48-byte stride = 8 lanes on 32 distinct banks (conflict free)
 __device__ __forceinline__ int pad2(int i) { return i + 2 * (i >> 2); }
-
-using rsrc_t = __amdgpu_buffer_rsrc_t;
-__device__ __forceinline__ rsrc_t make_rsrc(const void* p)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7fffffff, 0x00020000);
-}
-template <typename T> struct vox;
-template <> struct vox<uint8_t> {
-    static __device__ __forceinline__ float load(rsrc_t r, unsigned o, unsigned so = 0) { return __uint_as_float((unsigned)__builtin_amdgcn_raw_buffer_load_b8(r, o, so, 0)); }
-    static __device__ __forceinline__ float act(float raw) { return (float)__float_as_uint(raw); }
-};
-template <> struct vox<uint16_t> {
-    static __device__ __forceinline__ float load(rsrc_t r, unsigned o, unsigned so = 0) { return __uint_as_float((unsigned)__builtin_amdgcn_raw_buffer_load_b16(r, o, so, 0)); }
-    static __device__ __forceinline__ float act(float raw) { return (float)__float_as_uint(raw); }
-};
-template <> struct vox<float> {
-    static __device__ __forceinline__ float load(rsrc_t r, unsigned o, unsigned so = 0) { return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, o, so, 0)); }
-    static __device__ __forceinline__ float act(float raw) { return raw; }
-};
 
 template <int R> struct xgeom2 {
     static constexpr int LEAD = R & 1;                  // odd radius: window starts one pair early (16-B reads)
@@ -350,10 +319,6 @@ int launch_zx2(const mmx_volume* vol, const mmx_block* d_blocks, int n_blocks, i
 }
 
 }  // namespace
-
-#define MMX_FOR_EACH_RADIUS(X) \
-    X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) \
-    X(17) X(18) X(19) X(20) X(21) X(22) X(23) X(24)
 
 int mmx_launch_zx2(const mmx_volume* vol, const mmx_block* d_blocks, int n_blocks, int max_ny, int max_px,
                    int64_t slot_elems, const mmx_taps_f32& tz, const mmx_taps_f32& tx, int radius,

@@ -51,14 +51,7 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "mmx_common.h"
-
-typedef _Float16 h2_4 __attribute__((ext_vector_type(2)));
-typedef _Float16 h8_4 __attribute__((ext_vector_type(8)));
-typedef float f2_4 __attribute__((ext_vector_type(2)));
-typedef float f4_4 __attribute__((ext_vector_type(4)));
-typedef unsigned u4_4 __attribute__((ext_vector_type(4)));
-typedef unsigned u2_4 __attribute__((ext_vector_type(2)));
+#include "mmx_device.h"
 
 #define MMX_ZX4_MAXCLS 8
 // cache policy bits of the streaming accesses (gfx940+: 1 = sc0, 2 = nt, 16 = sc1)
@@ -95,12 +88,6 @@ constexpr int kPF4 = ZX4_PF;       // z tiles of voxels in flight per wave
 constexpr float kLoScale = 2048.f;
 constexpr float kLoInv = 1.f / 2048.f;
 
-using rsrc4_t = __amdgpu_buffer_rsrc_t;
-__device__ __forceinline__ rsrc4_t make_rsrc4(const void* p)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7fffffff, 0x00020000);
-}
-
 // geometry classes actually compiled: (NKX, LA) = (1, 1) for R <= 8, (2, 1) for R <= 16, (2, 2) for R <= 24
 template <int NKX, int LA> struct cls4 {
     static constexpr int R8 = NKX == 1 ? 8 : (LA == 1 ? 16 : 24);
@@ -131,12 +118,6 @@ template <int NKX, int LA> struct cls4 {
     static constexpr int NT = 4;
 };
 
-__device__ __forceinline__ unsigned pack_h2(float a, float b)
-{
-    const f2_4 v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, h2_4));
-}
-
 // ------------------------------------------------------------------------------------ setup: Toeplitz fragments
 // weight of input position p for output o on an axis of n voxels with SciPy "reflect" folded in
 __device__ __forceinline__ float folded_tap(const float* w, int R, int p, int o, int n)
@@ -155,7 +136,7 @@ __device__ __forceinline__ float folded_tap(const float* w, int R, int p, int o,
 //   X table [class][column][m][kernel][piece][lane], Z table [class][U][ks][kernel][piece][lane]
 template <int NKX, int LA>
 __global__ void __launch_bounds__(256)
-zx4_setup(mmx_zx4_cfg cfg, u4_4* __restrict__ xtab, u4_4* __restrict__ ztab)
+zx4_setup(mmx_zx4_cfg cfg, v4u* __restrict__ xtab, v4u* __restrict__ ztab)
 {
     using cg = cls4<NKX, LA>;
     const int R = cfg.radius;
@@ -165,7 +146,7 @@ zx4_setup(mmx_zx4_cfg cfg, u4_4* __restrict__ xtab, u4_4* __restrict__ ztab)
     const int nx_entries = cfg.ncw * cfg.maxcol * NKX * 2;
     const int nz_entries = cfg.ncz * cfg.maxu * cg::NKZ * 2;
     float wt[8];
-    u4_4* dst;
+    v4u* dst;
     if (e < nx_entries) {
         const int kern = e & 1;
         const int m = (e >> 1) % NKX;
@@ -215,14 +196,14 @@ zx4_setup(mmx_zx4_cfg cfg, u4_4* __restrict__ xtab, u4_4* __restrict__ ztab)
     unsigned hi[4], lo[4];
 #pragma unroll
     for (int j = 0; j < 8; j += 2) {
-        const f2_4 v = {wt[j], wt[j + 1]};
-        const h2_4 h = __builtin_convertvector(v, h2_4);
-        const f2_4 r = {(wt[j] - (float)h.x) * kLoScale, (wt[j + 1] - (float)h.y) * kLoScale};
+        const v2f v = {wt[j], wt[j + 1]};
+        const v2h h = __builtin_convertvector(v, v2h);
+        const v2f r = {(wt[j] - (float)h.x) * kLoScale, (wt[j + 1] - (float)h.y) * kLoScale};
         hi[j >> 1] = __builtin_bit_cast(unsigned, h);
-        lo[j >> 1] = __builtin_bit_cast(unsigned, __builtin_convertvector(r, h2_4));
+        lo[j >> 1] = __builtin_bit_cast(unsigned, __builtin_convertvector(r, v2h));
     }
-    dst[lane] = (u4_4){hi[0], hi[1], hi[2], hi[3]};
-    dst[64 + lane] = (u4_4){lo[0], lo[1], lo[2], lo[3]};
+    dst[lane] = (v4u){hi[0], hi[1], hi[2], hi[3]};
+    dst[64 + lane] = (v4u){lo[0], lo[1], lo[2], lo[3]};
 }
 
 // ------------------------------------------------------------------------------------------------ main kernel
@@ -231,29 +212,29 @@ template <typename InT> struct pieces4;
 //   0x4400 | b  =  4 + b / 256      (float16, exponent 2^2, ulp 2^-8)
 //   0x2400 | b  =  2^-6 + b / 65536 (exponent 2^-6, ulp 2^-16)
 template <> struct pieces4<uint16_t> {
-    using raw_t = u4_4;
-    static __device__ __forceinline__ raw_t load(rsrc4_t r, unsigned off, unsigned soff = 0)
+    using raw_t = v4u;
+    static __device__ __forceinline__ raw_t load(rsrc_t r, unsigned off, unsigned soff = 0)
     {
-        return __builtin_bit_cast(u4_4, __builtin_amdgcn_raw_buffer_load_b128(r, off, soff, ZX4_LD_AUX));
+        return __builtin_bit_cast(v4u, __builtin_amdgcn_raw_buffer_load_b128(r, off, soff, ZX4_LD_AUX));
     }
-    static __device__ __forceinline__ void split(const raw_t& d, u4_4& hi, u4_4& lo)
+    static __device__ __forceinline__ void split(const raw_t& d, v4u& hi, v4u& lo)
     {
-        const h2_4 four = {(_Float16)4.0f, (_Float16)4.0f};
-        const h2_4 sixty4th = {(_Float16)0.015625f, (_Float16)0.015625f};
+        const v2h four = {(_Float16)4.0f, (_Float16)4.0f};
+        const v2h sixty4th = {(_Float16)0.015625f, (_Float16)0.015625f};
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             // v_perm_b32: bytes of {S0 = constant, S1 = data}; selector bytes 0-3 pick from S1, 4-7 from S0
             const unsigned th = __builtin_amdgcn_perm(0x44004400u, d[i], 0x07030501u);   // [44 b3 44 b1]
             const unsigned tl = __builtin_amdgcn_perm(0x24002400u, d[i], 0x07020500u);   // [24 b2 24 b0]
-            hi[i] = __builtin_bit_cast(unsigned, __builtin_bit_cast(h2_4, th) - four);
-            lo[i] = __builtin_bit_cast(unsigned, __builtin_bit_cast(h2_4, tl) - sixty4th);
+            hi[i] = __builtin_bit_cast(unsigned, __builtin_bit_cast(v2h, th) - four);
+            lo[i] = __builtin_bit_cast(unsigned, __builtin_bit_cast(v2h, tl) - sixty4th);
         }
     }
     // The same pieces with their exponent offsets left in: hi = 4 + b / 256, lo = 2^-6 + b / 65536.  A constant added
     // to every element of an A operand adds (constant x column sum of B) to every row of the product: the kernel
     // starts its accumulators at minus that, computed once per wave -- half the split's instructions.
     static constexpr float kBiasHi = 4.0f, kBiasLo = 0.015625f;
-    static __device__ __forceinline__ void split_biased(const raw_t& d, u4_4& hi, u4_4& lo)
+    static __device__ __forceinline__ void split_biased(const raw_t& d, v4u& hi, v4u& lo)
     {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -266,29 +247,24 @@ template <> struct pieces4<uint16_t> {
 
 // float voxels: zx6_pack_f32_kernel has split them already -- per unit of 8 columns x 16 planes the high
 // float16 pieces (256 bytes) then the low ones, v = hi + lo / 2048 -- two 16-byte loads per k-step, no unpacking
-struct presplit_t { u4_4 h, l; };
+struct presplit_t { v4u h, l; };
 template <> struct pieces4<float> {
     using raw_t = presplit_t;
-    static __device__ __forceinline__ raw_t load(rsrc4_t r, unsigned off, unsigned soff = 0)
+    static __device__ __forceinline__ raw_t load(rsrc_t r, unsigned off, unsigned soff = 0)
     {
         raw_t v;
-        v.h = __builtin_bit_cast(u4_4, __builtin_amdgcn_raw_buffer_load_b128(r, off, soff, ZX4_LD_AUX));
-        v.l = __builtin_bit_cast(u4_4, __builtin_amdgcn_raw_buffer_load_b128(r, off + 256u, soff, ZX4_LD_AUX));
+        v.h = __builtin_bit_cast(v4u, __builtin_amdgcn_raw_buffer_load_b128(r, off, soff, ZX4_LD_AUX));
+        v.l = __builtin_bit_cast(v4u, __builtin_amdgcn_raw_buffer_load_b128(r, off + 256u, soff, ZX4_LD_AUX));
         return v;
     }
-    static __device__ __forceinline__ void split(const raw_t& d, u4_4& hi, u4_4& lo) { hi = d.h; lo = d.l; }
+    static __device__ __forceinline__ void split(const raw_t& d, v4u& hi, v4u& lo) { hi = d.h; lo = d.l; }
     [[maybe_unused]] static constexpr float kBiasHi = 0.f, kBiasLo = 0.f;      // (never biased: read in discarded branches only)
-    static __device__ __forceinline__ void split_biased(const raw_t& d, u4_4& hi, u4_4& lo) { hi = d.h; lo = d.l; }
+    static __device__ __forceinline__ void split_biased(const raw_t& d, v4u& hi, v4u& lo) { hi = d.h; lo = d.l; }
 };
 template <typename InT> struct is_f32_4 { static constexpr bool value = false; };
 template <> struct is_f32_4<float> { static constexpr bool value = true; };
 template <typename InT> struct lo_scaled4 { static constexpr bool value = false; };     // low piece carries x 2048?
 template <> struct lo_scaled4<float> { static constexpr bool value = true; };
-
-__device__ __forceinline__ f4_4 mfma16(const u4_4& a, const u4_4& b, const f4_4& c)
-{
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8_4, a), __builtin_bit_cast(h8_4, b), c, 0, 0, 0);
-}
 
 // The voxels come from the operand-ordered copy zx6_pack_kernel leaves (`vol` = that copy,
 // stride_z = its elements per block) and P / Q leave as 16 x 16 tiles of 1 KiB (slot_elems = tile elements per
@@ -310,7 +286,7 @@ __global__ void __launch_bounds__(256, (NTW == 1 && (LA == 1 || Q16) && !is_f32_
 zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
            const mmx_block* __restrict__ blocks, int64_t slot_elems,
            float* __restrict__ gp, float* __restrict__ gq,
-           const u4_4* __restrict__ xtab, const u4_4* __restrict__ ztab, mmx_zx4_cfg cfg)
+           const v4u* __restrict__ xtab, const v4u* __restrict__ ztab, mmx_zx4_cfg cfg)
 {
     using cg = cls4<NKX, LA>;
     using pc = pieces4<InT>;
@@ -348,7 +324,7 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
     const int R = cfg.radius;
     const int u_lo = (R + 15) >> 4;                             // first U with 16 U - R >= 0
     const int u_hi = (nz - 16 - R) >> 4;                        // last U with 16 U + 15 + R <= nz - 1 (may be < u_lo)
-    const u4_4* zt = ztab + ((size_t)cz * cfg.maxu * NKZ * 2) * 128 + lane;
+    const v4u* zt = ztab + ((size_t)cz * cfg.maxu * NKZ * 2) * 128 + lane;
     // (the steps at the ends of the block take their fragments straight from the table)
     // ROT: in the steady steps z tile t keeps the window slot t mod NT it was written to -- no shifting, the operand
     // quads (slots 2 q, 2 q + 1) never move -- and the fragments rotate instead: by whole k-steps when the window
@@ -364,17 +340,17 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
     // never move, and the shifted table is the cyclic one: F1[k] = [F0[k - 1 mod 2] upper half | F0[k] lower half].
     constexpr bool ROT = ZLDS && Q16 && NTW == 1 && !is_f32_4<InT>::value && (NKX == 1 || LA == 2);
     constexpr int ZL1 = NKZ * 4 * 64;                          // entries of one table
-    __shared__ u4_4 zl[ZLDS ? (ROT ? 2 : 1) * ZL1 : 1];
+    __shared__ v4u zl[ZLDS ? (ROT ? 2 : 1) * ZL1 : 1];
     if constexpr (ZLDS) {
-        const u4_4* zi = ztab + ((size_t)(cz * cfg.maxu + (u_lo < cfg.maxu ? u_lo : 0)) * NKZ * 2) * 128;
+        const v4u* zi = ztab + ((size_t)(cz * cfg.maxu + (u_lo < cfg.maxu ? u_lo : 0)) * NKZ * 2) * 128;
         for (int e = threadIdx.x; e < ZL1; e += 256) zl[e] = zi[e];
         __syncthreads();
         if constexpr (ROT) {
             for (int e = threadIdx.x; e < ZL1; e += 256) {
-                const u4_4 cur = zl[e];
+                const v4u cur = zl[e];
                 // (k-step before: 4 x 64 entries back; the split tile's window is a ring -- its first k-step follows its last)
-                const u4_4 prev = SPLIT ? zl[(e + ZL1 - 256) % ZL1] : (e >= 256 ? zl[e - 256] : (u4_4){0u, 0u, 0u, 0u});
-                zl[ZL1 + e] = (u4_4){prev.z, prev.w, cur.x, cur.y};
+                const v4u prev = SPLIT ? zl[(e + ZL1 - 256) % ZL1] : (e >= 256 ? zl[e - 256] : (v4u){0u, 0u, 0u, 0u});
+                zl[ZL1 + e] = (v4u){prev.z, prev.w, cur.x, cur.y};
             }
             __syncthreads();
         }
@@ -382,12 +358,12 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
     if (y >= bd.ny) return;                                   // whole wave (no barriers below)
 
     // X fragments of this wave's column tile(s): [tile][m][kernel][piece]
-    u4_4 xw[NTW][NKX][2][2];
+    v4u xw[NTW][NKX][2][2];
     const bool has2 = NTW == 2 && c + 1 < ntx;                 // (wave-uniform)
 #pragma unroll
     for (int i = 0; i < NTW; ++i) {
         // (a pair's missing second tile: any column's fragments -- its results are never stored)
-        const u4_4* xt = xtab + ((size_t)(cw * cfg.maxcol + (i && !has2 ? c : c + i)) * NKX * 2) * 128 + lane;
+        const v4u* xt = xtab + ((size_t)(cw * cfg.maxcol + (i && !has2 ? c : c + i)) * NKX * 2) * 128 + lane;
 #pragma unroll
         for (int m = 0; m < NKX; ++m)
 #pragma unroll
@@ -403,15 +379,15 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
     // (radius > 16: the eight start registers would push the kernel past three waves per SIMD)
     constexpr bool BIASED = Q16 && !is_f32_4<InT>::value && LA == 1;
     constexpr bool MIXSPLIT = Q16;
-    const f4_4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    f4_4 a_start[NTW], b_start[NTW];
+    const v4f zero4 = {0.f, 0.f, 0.f, 0.f};
+    v4f a_start[NTW], b_start[NTW];
 #pragma unroll
     for (int i = 0; i < NTW; ++i) { a_start[i] = zero4; b_start[i] = zero4; }
     if constexpr (BIASED) {
-        const u4_4 ones = {0x3C003C00u, 0x3C003C00u, 0x3C003C00u, 0x3C003C00u};
+        const v4u ones = {0x3C003C00u, 0x3C003C00u, 0x3C003C00u, 0x3C003C00u};
 #pragma unroll
         for (int i = 0; i < NTW; ++i) {
-            f4_4 sh[2] = {zero4, zero4}, sl[2] = {zero4, zero4};
+            v4f sh[2] = {zero4, zero4}, sl[2] = {zero4, zero4};
 #pragma unroll
             for (int m = 0; m < NKX; ++m)
 #pragma unroll
@@ -422,13 +398,13 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
             // a0 takes (hi + lo pieces) x high fragments, a1 hi pieces x low fragments (scaled by 2048), v = a0 + a1 / 2048
             const float ca = -((pc::kBiasHi + pc::kBiasLo) * sh[0][0] + pc::kBiasHi * sl[0][0] * kLoInv);
             const float cb = -((pc::kBiasHi + pc::kBiasLo) * sh[1][0] + pc::kBiasHi * sl[1][0] * kLoInv);
-            a_start[i] = (f4_4){ca, ca, ca, ca};
-            b_start[i] = (f4_4){cb, cb, cb, cb};
+            a_start[i] = (v4f){ca, ca, ca, ca};
+            b_start[i] = (v4f){cb, cb, cb, cb};
         }
     }
     // Z fragments: [ks][kernel][piece], of the z tile being produced (reloaded when its class changes);
     // interior z tiles share one set: the first tile whose taps all fall inside the block
-    u4_4 zw[ZLDS ? 1 : NKZ][2][2];
+    v4u zw[ZLDS ? 1 : NKZ][2][2];
     int zset = -1;
 
     // voxel rows: plane z0 + li, chunk of 8 x at xl[m] (clamped into the block; the fragments know)
@@ -441,7 +417,7 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
         j = j < 0 ? 0 : (j > nch8 - 1 ? nch8 - 1 : j);
         xoff[m] = (unsigned)(j * kUnit + li * 16);
     }
-    const rsrc4_t rin = make_rsrc4(in);
+    const rsrc_t rin = make_rsrc(in);
     auto load_tile = [&](int t, typename pc::raw_t (&raw)[NKX]) __attribute__((always_inline)) {
         const unsigned so = (unsigned)((y * ntz + t) * nch8) * (unsigned)kUnit;          // wave-uniform: the row tile
 #pragma unroll
@@ -465,9 +441,9 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
     const unsigned col_b = (unsigned)ntz * 1024u;                                        // bytes of one tile column
     const unsigned live_b = col_b - (unsigned)(16 * ntz - nz) * 64u;
     const int64_t wave_e = (int64_t)((y * ntx + c) * ntz) * 256;                          // elements before this wave's tiles
-    const rsrc4_t rp = __builtin_amdgcn_make_buffer_rsrc(gp + (int64_t)bd.slot * slot_elems + wave_e, 0, (int)live_b, 0x00020000);
-    const rsrc4_t rq = __builtin_amdgcn_make_buffer_rsrc(gq + (int64_t)bd.slot * slot_elems + wave_e, 0, (int)live_b, 0x00020000);
-    const rsrc4_t rp2 = __builtin_amdgcn_make_buffer_rsrc(gp + (int64_t)bd.slot * slot_elems + wave_e + (int64_t)ntz * 256, 0,
+    const rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(gp + (int64_t)bd.slot * slot_elems + wave_e, 0, (int)live_b, 0x00020000);
+    const rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(gq + (int64_t)bd.slot * slot_elems + wave_e, 0, (int)live_b, 0x00020000);
+    const rsrc_t rp2 = __builtin_amdgcn_make_buffer_rsrc(gp + (int64_t)bd.slot * slot_elems + wave_e + (int64_t)ntz * 256, 0,
                                                           has2 ? (int)live_b : 0, 0x00020000);
     // Tile (y, c, U) of 16 z x 16 x floats, row-major, at ((y ntx + c) ntz + U) KiB: what a wave writes
     // during its march is contiguous, the waves of a workgroup and the workgroups of a row follow each other --
@@ -493,7 +469,7 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
     // Results on their way to memory: a store reads its data registers asynchronously, so the compiler makes the
     // next writer of those registers wait (vmcnt) until the store has completed.  Each ring slot therefore has
     // its own result registers, kept allocated (an empty asm "use") until the slot comes round again.
-    f4_4 outP[PF][NTW], outQ[PF];
+    v4f outP[PF][NTW], outQ[PF];
 #pragma unroll
     for (int u = 0; u < PF; ++u) {
 #pragma unroll
@@ -502,7 +478,7 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
     }
     // (phase_tag: the window slot of z tile t in a steady step of the rotating form, -1 otherwise: the window is
     //  shifted and t takes slot 2 LA -- the arrangement the rotating steps start from and return to every NT steps)
-    auto step = [&](int t, auto steady_tag, auto phase_tag, typename pc::raw_t (&rw)[NKX], f4_4 (&P)[NTW], f4_4& Q) __attribute__((always_inline)) {
+    auto step = [&](int t, auto steady_tag, auto phase_tag, typename pc::raw_t (&rw)[NKX], v4f (&P)[NTW], v4f& Q) __attribute__((always_inline)) {
         constexpr bool STEADY = decltype(steady_tag)::value;
         constexpr int PH = decltype(phase_tag)::value;
         constexpr bool TURN = STEADY && ROT && PH >= 0;
@@ -526,7 +502,7 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
         }
         if (STEADY || t < ntz) {
             // ---- X pass of z tile t
-            u4_4 dh[NKX], dl[NKX];
+            v4u dh[NKX], dl[NKX];
 #pragma unroll
             for (int m = 0; m < NKX; ++m) {
                 if constexpr (BIASED) pc::split_biased(rw[m], dh[m], dl[m]);
@@ -541,7 +517,7 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int w = 0; w < NTW; ++w) {
-                f4_4 a0 = a_start[w], a1 = zero4, b0 = b_start[w], b1 = zero4;
+                v4f a0 = a_start[w], a1 = zero4, b0 = b_start[w], b1 = zero4;
 #pragma unroll
                 for (int m = 0; m < NKX; ++m) {
                     a0 = mfma16(dh[m], xw[w][m][0][0], a0);
@@ -568,8 +544,8 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
                 for (int r = 0; r < 4; r += 2) {
                     const float av0 = __builtin_fmaf(a1[r], kLoInv, a0[r]), av1 = __builtin_fmaf(a1[r + 1], kLoInv, a0[r + 1]);
                     const float bv0 = __builtin_fmaf(b1[r], kLoInv, b0[r]), bv1 = __builtin_fmaf(b1[r + 1], kLoInv, b0[r + 1]);
-                    const f2_4 av = {av0, av1}, bv = {bv0, bv1};
-                    const h2_4 ah = __builtin_convertvector(av, h2_4), bh = __builtin_convertvector(bv, h2_4);
+                    const v2f av = {av0, av1}, bv = {bv0, bv1};
+                    const v2h ah = __builtin_convertvector(av, v2h), bh = __builtin_convertvector(bv, v2h);
                     if constexpr (MIXSPLIT) {
                         // 16-bit tiles: the low piece is the plain residual v - half(v), not scaled by 2048 -- values are
                         // <= 1 here (the fragments carry 1 / bound), so the residual is below 2^-12 and float16 keeps it to
@@ -577,19 +553,19 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
                         // (v_fma_mix{lo,hi}_f16 would make it in one instruction per value, but only as inline assembly,
                         //  whose register writes the compiler's hazard recogniser does not see: one landed right behind an
                         //  MFMA that still read the register as its C operand -- wrong results for radius <= 8.)
-                        const f2_4 ar = {av0 - (float)ah.x, av1 - (float)ah.y}, br = {bv0 - (float)bh.x, bv1 - (float)bh.y};
+                        const v2f ar = {av0 - (float)ah.x, av1 - (float)ah.y}, br = {bv0 - (float)bh.x, bv1 - (float)bh.y};
                         put(w, 0, r >> 1, __builtin_bit_cast(unsigned, ah));
-                        put(w, 1, r >> 1, __builtin_bit_cast(unsigned, __builtin_convertvector(ar, h2_4)));
+                        put(w, 1, r >> 1, __builtin_bit_cast(unsigned, __builtin_convertvector(ar, v2h)));
                         put(w, 2, r >> 1, __builtin_bit_cast(unsigned, bh));
-                        put(w, 3, r >> 1, __builtin_bit_cast(unsigned, __builtin_convertvector(br, h2_4)));
+                        put(w, 3, r >> 1, __builtin_bit_cast(unsigned, __builtin_convertvector(br, v2h)));
                         continue;
                     }
-                    const f2_4 ar = {__builtin_fmaf((float)ah.x, -kLoScale, av0 * kLoScale), __builtin_fmaf((float)ah.y, -kLoScale, av1 * kLoScale)};
-                    const f2_4 br = {__builtin_fmaf((float)bh.x, -kLoScale, bv0 * kLoScale), __builtin_fmaf((float)bh.y, -kLoScale, bv1 * kLoScale)};
+                    const v2f ar = {__builtin_fmaf((float)ah.x, -kLoScale, av0 * kLoScale), __builtin_fmaf((float)ah.y, -kLoScale, av1 * kLoScale)};
+                    const v2f br = {__builtin_fmaf((float)bh.x, -kLoScale, bv0 * kLoScale), __builtin_fmaf((float)bh.y, -kLoScale, bv1 * kLoScale)};
                     put(w, 0, r >> 1, __builtin_bit_cast(unsigned, ah));
-                    put(w, 1, r >> 1, __builtin_bit_cast(unsigned, __builtin_convertvector(ar, h2_4)));
+                    put(w, 1, r >> 1, __builtin_bit_cast(unsigned, __builtin_convertvector(ar, v2h)));
                     put(w, 2, r >> 1, __builtin_bit_cast(unsigned, bh));
-                    put(w, 3, r >> 1, __builtin_bit_cast(unsigned, __builtin_convertvector(br, h2_4)));
+                    put(w, 3, r >> 1, __builtin_bit_cast(unsigned, __builtin_convertvector(br, v2h)));
                 }
             }
         } else {
@@ -625,12 +601,12 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
             auto wv = [&](int w, int a, int s, int d) __attribute__((always_inline)) {
                 return SPLIT && s == VS ? vsel[a][d] : win[w][a][s][d];
             };
-            f4_4 p0[NTW], p1[NTW], q0[NTW], q1[NTW];
+            v4f p0[NTW], p1[NTW], q0[NTW], q1[NTW];
 #pragma unroll
             for (int w = 0; w < NTW; ++w) { p0[w] = zero4; p1[w] = zero4; q0[w] = zero4; q1[w] = zero4; }
 #pragma unroll
             for (int ks = 0; ks < NKZ; ++ks) {
-                u4_4 z00, z01, z10, z11;          // [kernel][piece]
+                v4u z00, z01, z10, z11;          // [kernel][piece]
                 if constexpr (!ZLDS) {
                     z00 = zw[ks][0][0]; z01 = zw[ks][0][1]; z10 = zw[ks][1][0]; z11 = zw[ks][1][1];
                 } else if constexpr (STEADY) {
@@ -643,7 +619,7 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
                     z00 = zl[KF + 0 * 64 + lane]; z01 = zl[KF + 1 * 64 + lane];
                     z10 = zl[KF + 2 * 64 + lane]; z11 = zl[KF + 3 * 64 + lane];
                 } else {
-                    const u4_4* zp = zt + ((size_t)(want * NKZ + ks) * 2) * 128;
+                    const v4u* zp = zt + ((size_t)(want * NKZ + ks) * 2) * 128;
                     z00 = zp[0]; z01 = zp[64]; z10 = zp[128]; z11 = zp[192];
                 }
                 // (Radius <= 16: the window's last tile, U + 1, stands alone in its k-step -- the fragments' other half is
@@ -651,10 +627,10 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
                 //  mixed with it on one accumulator chain, gave run-dependent values: profiles/r05_experiments.txt, section 5.)
 #pragma unroll
                 for (int w = 0; w < NTW; ++w) {
-                    const u4_4 ah = {wv(w, 0, 2 * ks, 0), wv(w, 0, 2 * ks, 1), wv(w, 0, 2 * ks + 1, 0), wv(w, 0, 2 * ks + 1, 1)};
-                    const u4_4 al = {wv(w, 1, 2 * ks, 0), wv(w, 1, 2 * ks, 1), wv(w, 1, 2 * ks + 1, 0), wv(w, 1, 2 * ks + 1, 1)};
-                    const u4_4 bh = {wv(w, 2, 2 * ks, 0), wv(w, 2, 2 * ks, 1), wv(w, 2, 2 * ks + 1, 0), wv(w, 2, 2 * ks + 1, 1)};
-                    const u4_4 bl = {wv(w, 3, 2 * ks, 0), wv(w, 3, 2 * ks, 1), wv(w, 3, 2 * ks + 1, 0), wv(w, 3, 2 * ks + 1, 1)};
+                    const v4u ah = {wv(w, 0, 2 * ks, 0), wv(w, 0, 2 * ks, 1), wv(w, 0, 2 * ks + 1, 0), wv(w, 0, 2 * ks + 1, 1)};
+                    const v4u al = {wv(w, 1, 2 * ks, 0), wv(w, 1, 2 * ks, 1), wv(w, 1, 2 * ks + 1, 0), wv(w, 1, 2 * ks + 1, 1)};
+                    const v4u bh = {wv(w, 2, 2 * ks, 0), wv(w, 2, 2 * ks, 1), wv(w, 2, 2 * ks + 1, 0), wv(w, 2, 2 * ks + 1, 1)};
+                    const v4u bl = {wv(w, 3, 2 * ks, 0), wv(w, 3, 2 * ks, 1), wv(w, 3, 2 * ks + 1, 0), wv(w, 3, 2 * ks + 1, 1)};
                     p0[w] = mfma16(ah, z00, p0[w]);
                     q0[w] = mfma16(bh, z00, q0[w]);
                     p1[w] = mfma16(ah, z01, p1[w]);
@@ -699,8 +675,8 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
                             P[w][r + 1] = rb;
                         }
                         // (tile (y, c + w, U) lies ntz KiB after tile (y, c, U): rp2's base)
-                        if (w == 0) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4_4, P[w]), rp, obase, 0, ZX4_ST_AUX);
-                        else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4_4, P[w]), rp2, obase, 0, ZX4_ST_AUX);
+                        if (w == 0) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, P[w]), rp, obase, 0, ZX4_ST_AUX);
+                        else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, P[w]), rp2, obase, 0, ZX4_ST_AUX);
                     }
                 } else {
 #pragma unroll
@@ -713,8 +689,8 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
                     P[0][r] = pr;
                     Q[r] = qr;
                 }
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4_4, P[0]), rp, obase, 0, ZX4_ST_AUX);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4_4, Q), rq, obase, 0, ZX4_ST_AUX);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, P[0]), rp, obase, 0, ZX4_ST_AUX);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, Q), rq, obase, 0, ZX4_ST_AUX);
                 }
             }
             obase += 16u * plane_b;
@@ -836,7 +812,7 @@ zx6_pack_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
             // All of a wave's loads -- four planes x (up to) two 4-voxel groups per lane -- are issued before the first
             // LDS write: a workgroup moves 8 KiB in and 8 KiB out and nothing else hides its load latency (the loop form
             // had one or two loads in flight per wave: 2.8 TB/s).
-            u2_4 v[4][2];
+            v2u v[4][2];
             bool have[4][2];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -846,15 +822,15 @@ zx6_pack_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
                 for (int h = 0; h < 2; ++h) {
                     const int x = lane * 4 + 256 * h;
                     have[i][h] = x < 8 * nch8;
-                    v[i][h] = (u2_4){0u, 0u};
+                    v[i][h] = (v2u){0u, 0u};
                     if (have[i][h] && z < bd.nz) {
                         if (x + 3 < nx) {
-                            v[i][h] = *reinterpret_cast<const u2_4*>(row + x);
+                            v[i][h] = *reinterpret_cast<const v2u*>(row + x);
                         } else {
                             unsigned e[4];
 #pragma unroll
                             for (int j = 0; j < 4; ++j) e[j] = x + j < nx ? (unsigned)row[x + j] : 0u;
-                            v[i][h] = (u2_4){e[0] | (e[1] << 16), e[2] | (e[3] << 16)};
+                            v[i][h] = (v2u){e[0] | (e[1] << 16), e[2] | (e[3] << 16)};
                         }
                     }
                 }
@@ -863,13 +839,13 @@ zx6_pack_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int h = 0; h < 2; ++h)
-                    if (have[i][h]) *reinterpret_cast<u2_4*>(&tile[4 * wave + i][lane * 4 + 256 * h]) = v[i][h];
+                    if (have[i][h]) *reinterpret_cast<v2u*>(&tile[4 * wave + i][lane * 4 + 256 * h]) = v[i][h];
         } else
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int r = 4 * wave + i, z = 16 * t + r;
             if (z >= bd.nz) {
-                for (int x = lane * 4; x < 8 * nch8; x += 256) *reinterpret_cast<u2_4*>(&tile[r][x]) = (u2_4){0u, 0u};
+                for (int x = lane * 4; x < 8 * nch8; x += 256) *reinterpret_cast<v2u*>(&tile[r][x]) = (v2u){0u, 0u};
             } else {
                 for (int x = lane; x < 8 * nch8; x += 64)
                     tile[r][x] = x < nx ? (uint16_t)((unsigned)src[(int64_t)z * stride_z + (int64_t)x * stride_x] << (sizeof(InT) == 1 ? 8 : 0))
@@ -877,10 +853,10 @@ zx6_pack_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
             }
         }
         __syncthreads();
-        u4_4* dst = reinterpret_cast<u4_4*>(pack + (int64_t)bd.slot * pack_stride) + (int64_t)yt * nrow8 * 16 + (WIDE ? 1024 * p : 0);
+        v4u* dst = reinterpret_cast<v4u*>(pack + (int64_t)bd.slot * pack_stride) + (int64_t)yt * nrow8 * 16 + (WIDE ? 1024 * p : 0);
         for (int u = threadIdx.x; u < nch8 * 16; u += 256) {
             const int j = u >> 4, r = u & 15;
-            dst[u] = *reinterpret_cast<const u4_4*>(&tile[r][8 * j]);
+            dst[u] = *reinterpret_cast<const v4u*>(&tile[r][8 * j]);
         }
     };
     if constexpr (WIDE) {
@@ -930,11 +906,11 @@ zx6_pack_f32_kernel(const float* __restrict__ vol, int64_t stride_z, int64_t str
             if (quads && z < bd.nz) {
                 const float* row = src + (int64_t)z * stride_z;
                 for (int x = lane * 4; x < 8 * nch8; x += 256) {
-                    f4_4 v = {0.f, 0.f, 0.f, 0.f};
-                    if (x + 3 < nx) v = *reinterpret_cast<const f4_4*>(row + x);
+                    v4f v = {0.f, 0.f, 0.f, 0.f};
+                    if (x + 3 < nx) v = *reinterpret_cast<const v4f*>(row + x);
                     else
                         for (int j = 0; j < 4; ++j) v[j] = x + j < nx ? row[x + j] : 0.f;
-                    *reinterpret_cast<u4_4*>(&tile[r][x]) = (u4_4){pieces(v[0]), pieces(v[1]), pieces(v[2]), pieces(v[3])};
+                    *reinterpret_cast<v4u*>(&tile[r][x]) = (v4u){pieces(v[0]), pieces(v[1]), pieces(v[2]), pieces(v[3])};
                 }
             } else {
                 for (int x = lane; x < 8 * nch8; x += 64) {
@@ -945,15 +921,15 @@ zx6_pack_f32_kernel(const float* __restrict__ vol, int64_t stride_z, int64_t str
             }
         }
         __syncthreads();
-        u4_4* dst = reinterpret_cast<u4_4*>(pack + (int64_t)bd.slot * pack_stride) + (int64_t)yt * nrow8 * 32 + (WIDE ? 2048 * p : 0);
+        v4u* dst = reinterpret_cast<v4u*>(pack + (int64_t)bd.slot * pack_stride) + (int64_t)yt * nrow8 * 32 + (WIDE ? 2048 * p : 0);
         for (int u = threadIdx.x; u < nch8 * 16; u += 256) {
             const int j = u >> 4, r = u & 15;
-            const u4_4 a = *reinterpret_cast<const u4_4*>(&tile[r][8 * j]);
-            const u4_4 b = *reinterpret_cast<const u4_4*>(&tile[r][8 * j + 4]);
+            const v4u a = *reinterpret_cast<const v4u*>(&tile[r][8 * j]);
+            const v4u b = *reinterpret_cast<const v4u*>(&tile[r][8 * j + 4]);
             // dwords (hi | lo << 16) of 8 columns -> 4 dwords of packed high pieces, 4 of packed low pieces
-            const u4_4 hi = {__builtin_amdgcn_perm(a[1], a[0], 0x05040100u), __builtin_amdgcn_perm(a[3], a[2], 0x05040100u),
+            const v4u hi = {__builtin_amdgcn_perm(a[1], a[0], 0x05040100u), __builtin_amdgcn_perm(a[3], a[2], 0x05040100u),
                              __builtin_amdgcn_perm(b[1], b[0], 0x05040100u), __builtin_amdgcn_perm(b[3], b[2], 0x05040100u)};
-            const u4_4 lo = {__builtin_amdgcn_perm(a[1], a[0], 0x07060302u), __builtin_amdgcn_perm(a[3], a[2], 0x07060302u),
+            const v4u lo = {__builtin_amdgcn_perm(a[1], a[0], 0x07060302u), __builtin_amdgcn_perm(a[3], a[2], 0x07060302u),
                              __builtin_amdgcn_perm(b[1], b[0], 0x07060302u), __builtin_amdgcn_perm(b[3], b[2], 0x07060302u)};
             dst[j * 32 + r] = hi;
             dst[j * 32 + 16 + r] = lo;
@@ -1025,12 +1001,12 @@ int launch_zx6(const mmx_volume* vol, const mmx_block* d_blocks, const mmx_block
     }
     const int nx_entries = cfg.ncw * cfg.maxcol * NKX * 2;
     const int nz_entries = cfg.ncz * cfg.maxu * cg::NKZ * 2;
-    const size_t xbytes = (size_t)nx_entries * 2 * 64 * sizeof(u4_4);
-    const size_t zbytes = (size_t)nz_entries * 2 * 64 * sizeof(u4_4);
+    const size_t xbytes = (size_t)nx_entries * 2 * 64 * sizeof(v4u);
+    const size_t zbytes = (size_t)nz_entries * 2 * 64 * sizeof(v4u);
     if ((int64_t)(xbytes + zbytes) > plan.tab_bytes) return MMX_ERR_UNSUPPORTED;
     char* w = reinterpret_cast<char*>(d_work);
-    u4_4* xtab = reinterpret_cast<u4_4*>(w + plan.tab_off);
-    u4_4* ztab = reinterpret_cast<u4_4*>(w + plan.tab_off + xbytes);
+    v4u* xtab = reinterpret_cast<v4u*>(w + plan.tab_off);
+    v4u* ztab = reinterpret_cast<v4u*>(w + plan.tab_off + xbytes);
     hipLaunchKernelGGL((zx4_setup<NKX, LA>), dim3((nx_entries + nz_entries + 3) / 4), dim3(256), 0, s, cfg, xtab, ztab);
     dim3 grid((((max_waves + 3) / 4) + 7) & ~7, n_blocks);        // (a multiple of 8: the XCD-aware order in the kernel)
     if (vol->dtype == MMX_F32) {

@@ -153,10 +153,10 @@ peaks_kernel(const float* __restrict__ log, int ns, int64_t sigma_stride,
                     const float n2 = fmaxf(fmaxf(e1[k], e3[k]), fmaxf(e2[k - 1], e2[k + 1]));
                     const float n3 = fmaxf(fmaxf(e2[k], rgt), fmaxf(e3[k - 1], e3[k + 1]));
                     const unsigned sh = 4 * (k - 1);
-                    hits |= ((e0[k] > lo && !(n0 > e0[k] + eps)) ? 1u : 0u) << sh;
-                    hits |= ((e1[k] > lo && !(n1 > e1[k] + eps)) ? 2u : 0u) << sh;
-                    hits |= ((e2[k] > lo && !(n2 > e2[k] + eps)) ? 4u : 0u) << sh;
-                    hits |= ((e3[k] > lo && !(n3 > e3[k] + eps)) ? 8u : 0u) << sh;
+                    hits |= (mmx_candidate(true, e0[k], lo, eps, n0) ? 1u : 0u) << sh;
+                    hits |= (mmx_candidate(true, e1[k], lo, eps, n1) ? 2u : 0u) << sh;
+                    hits |= (mmx_candidate(true, e2[k], lo, eps, n2) ? 4u : 0u) << sh;
+                    hits |= (mmx_candidate(true, e3[k], lo, eps, n3) ? 8u : 0u) << sh;
                 }
             }
             while (hits) {              // rare: only inside blobs
@@ -172,23 +172,20 @@ peaks_kernel(const float* __restrict__ log, int ns, int64_t sigma_stride,
     }
 }
 
-// ---- sparse variant: works from the entries the Y pass of the fused path leaves per 64 columns of a row
-// (y2_kernel): .x = candidate bits (above thr - eps, not beaten by the y / x neighbours), .y = "above
-// thr - eps" bits.  Segments with .y == 0 were not stored: their voxels count as -inf (they can neither
-// be peaks nor out-vote a candidate, which is above thr - eps itself).
+// ---- sparse variant: works from the entries the Y pass of the fused and wide paths leaves (mmx_entries.h):
+// .x = candidate bits, .y = "above thr - eps" bits.  Segments with .y == 0 were not stored: their voxels count as
+// -inf (they can neither be peaks nor out-vote a candidate, which is above thr - eps itself).
 struct sparse_ctx {
     peak_ctx c;
     const ulonglong2* ent;      // entries of this block, sigma 0
     int64_t ent_sigma_stride;   // entries per sigma
-    int nwords;                 // entries per row y
-    int quads, ntx;             // entry layout 2 (y6_kernel): one entry per 4 planes x 16 columns, ntx per plane quad
+    mmx_entry_geom eg;          // the layout
 };
 
-// entry holding voxel (z, y, x).  Layout 1 (y2_kernel): 64 consecutive columns of the (z, x) plane of row y;
-// layout 2 (y6_kernel): planes 4 (z >> 2) .. + 3 x columns 16 (x >> 4) .. + 15, bit ((z & 3) << 4) | (x & 15)
+// entry holding voxel (z, y, x)
 __device__ __forceinline__ int64_t sparse_entry(const sparse_ctx& k, int z, int y, int x)
 {
-    return (int64_t)y * k.nwords + (k.quads ? (z >> 2) * k.ntx + (x >> 4) : (z * k.c.px + x) >> 6);
+    return (int64_t)y * k.eg.per_row + mmx_entry_index(k.eg, z, x);
 }
 
 __device__ __forceinline__ float sparse_at(const sparse_ctx& k, int s, int z, int y, int x)
@@ -280,13 +277,10 @@ peaks_sparse_kernel(const float* __restrict__ log, const ulonglong2* __restrict_
     c.ns = ns; c.nz = bd.nz; c.ny = bd.ny; c.nx = bd.nx; c.px = bd.px;
     c.plane = bd.ny * bd.px; c.slot = bd.slot;
     c.thr = thr; c.eps = eps; c.out = out; c.cap = cap; c.count = count;
-    const int ncol = bd.nz * bd.px;
-    k.quads = quads;
-    k.ntx = (bd.nx + 15) >> 4;
-    k.nwords = quads ? ((bd.nz + 3) >> 2) * k.ntx : (ncol + 63) >> 6;
-    k.ent = entries + ((int64_t)bd.slot * slot_elems >> 5);
+    k.eg = mmx_entry_geom_make(quads ? MMX_MASK_QUADS : MMX_MASK_ROWS, bd.nz, bd.nx, bd.px);
+    k.ent = entries + mmx_entry_base(bd.slot, slot_elems);
     k.ent_sigma_stride = sigma_stride >> 5;
-    const int64_t per_sigma = (int64_t)bd.ny * k.nwords;
+    const int64_t per_sigma = (int64_t)bd.ny * k.eg.per_row;
     const int64_t total = per_sigma * ns;
     // Set bits are rare (a few per cent of the words hold one) and each costs a chain of dependent loads:
     // a lane that walked the bits of its own word would leave the other 63 waiting.  So the workgroup first
@@ -297,18 +291,10 @@ peaks_sparse_kernel(const float* __restrict__ log, const ulonglong2* __restrict_
     auto test_bit = [&](int64_t i, int b) __attribute__((always_inline)) {
         const int s = (int)(i / per_sigma);
         const int64_t r = i - (int64_t)s * per_sigma;
-        const int y = (int)(r / k.nwords);
-        const int w = (int)(r - (int64_t)y * k.nwords);
+        const int y = (int)(r / k.eg.per_row);
+        const int w = (int)(r - (int64_t)y * k.eg.per_row);
         int z, x;
-        if (k.quads) {
-            const int zqi = w / k.ntx;
-            z = 4 * zqi + (b >> 4);
-            x = 16 * (w - zqi * k.ntx) + (b & 15);
-        } else {
-            const int col = (w << 6) + b;
-            z = col / bd.px;
-            x = col - z * bd.px;
-        }
+        mmx_entry_voxel(k.eg, w, b, &z, &x);
         if (x >= bd.nx || z >= bd.nz) return;
         const float v = c.base[(int64_t)s * sigma_stride + (int64_t)z * c.plane + y * bd.px + x];
         // (the y and x neighbours were tested when the bit was set: most set bits are the in-plane maxima of

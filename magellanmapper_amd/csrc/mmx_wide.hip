@@ -22,14 +22,12 @@
 //          wave at a lane stride of 8 pairs then fall on 32 distinct 8-byte bank slots.  A workgroup takes as many rows
 //          as give its 256 threads one run each (a row of 261 voxels: 7 rows of 33 runs), and x tiles of 512 outputs,
 //          so any row width goes;
-//   Y    : runs last and writes the MMX_MASK_ROWS entries exactly where y2_kernel (mmx_fused.hip) writes them -- a
+//   Y    : runs last and writes the MMX_MASK_ROWS entries (mmx_entries.h) -- a
 //          workgroup's 64 columns are one entry per row --, and leaves 64-voxel segments with nothing above the
 //          threshold unwritten.  The y neighbours of a run's first and last output come from the neighbouring waves
 //          through LDS; a tile's own first and last row are not tested against the next tile (word 0 stays a superset).
 
-#include "mmx_common.h"
-
-typedef float v2f __attribute__((ext_vector_type(2)));
+#include "mmx_device.h"
 
 namespace {
 
@@ -51,13 +49,6 @@ struct wide_taps {
 
 // inputs a run reads: J + 2 R rounded up to whole steps of J
 __host__ __device__ constexpr int run_inputs(int R) { return (kJ + 2 * R + kJ - 1) / kJ * kJ; }
-
-__device__ __forceinline__ int reflect_clamped(int i, int n)
-{
-    i = i < 0 ? -1 - i : i;
-    i = i >= n ? 2 * n - 1 - i : i;
-    return i < 0 ? 0 : (i >= n ? n - 1 : i);
-}
 
 template <typename T> __device__ __forceinline__ float to_f32(T v) { return (float)v; }
 
@@ -251,13 +242,15 @@ wide_y(const mmx_block* __restrict__ blocks, int64_t slot_elems, int R, int ntil
         const float below = has_below ? edge[((run - 1) * 2 + 1) * 64 + lane] : -INFINITY;
         const float above = has_above ? edge[((run + 1) * 2 + 0) * 64 + lane] : -INFINITY;
         const bool has_l = lane > 0 && x > 0, has_r = lane < 63 && x + 1 < bd.nx && col + 1 < ncol;
-        const int nwords = (ncol + 63) >> 6;
-        ulonglong2* mrow = reinterpret_cast<ulonglong2*>(mask) + (sbase >> 5) + (col >> 6) + (int64_t)yr * nwords;
+        const mmx_entry_geom eg = mmx_entry_geom_make(MMX_MASK_ROWS, bd.nz, bd.nx, bd.px);
+        const int nwords = eg.per_row;
+        ulonglong2* mrow = reinterpret_cast<ulonglong2*>(mask) + mmx_entry_base(bd.slot, slot_elems) +
+                           mmx_rows_entry(col) + (int64_t)yr * nwords;
 #pragma unroll
         for (int j = 0; j < kJ; ++j) {
             if (yr + j >= bd.ny) break;                     // (wave-uniform)
             const float v = val[j];
-            const unsigned long long ab = __ballot(real & (v > nms_lo));
+            const unsigned long long ab = mmx_above_word(real, v, nms_lo);
             unsigned long long m = 0;
             if (ab) {
                 if (col_on) out[cbase + (int64_t)(yr + j) * bd.px] = v;
@@ -266,7 +259,7 @@ wide_y(const mmx_block* __restrict__ blocks, int64_t slot_elems, int R, int ntil
                 nb = fmaxf(nb, j > 0 ? val[j > 0 ? j - 1 : 0] : below);
                 // (a neighbour past the block's last row is no neighbour: its value here is one of a row never stored)
                 nb = fmaxf(nb, yr + j + 1 >= bd.ny ? -INFINITY : (j + 1 < kJ ? val[j + 1 < kJ ? j + 1 : 0] : above));
-                m = __ballot(real & (v > nms_lo) & !(nb > v + nms_eps));
+                m = __ballot(mmx_candidate(real, v, nms_lo, nms_eps, nb));
             }
             if (lane == 0) mrow[(int64_t)j * nwords] = make_ulonglong2(m, ab);
         }

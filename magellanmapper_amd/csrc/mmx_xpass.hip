@@ -17,7 +17,7 @@
 //
 // Algorithmic HBM bytes per voxel: read 8 (A, BC) + write 4.
 
-#include "mmx_common.h"
+#include "mmx_device.h"
 
 namespace {
 
@@ -194,10 +194,6 @@ int launch_x(const mmx_block* d_blocks, int n_blocks, int max_rows, int max_nx, 
 }
 
 }  // namespace
-
-#define MMX_FOR_EACH_RADIUS(X) \
-    X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) \
-    X(17) X(18) X(19) X(20) X(21) X(22) X(23) X(24)
 
 int mmx_launch_xpass(const mmx_block* d_blocks, int n_blocks, int max_rows, int max_nx,
                      int64_t slot_elems, const mmx_taps_f32& taps, int radius,

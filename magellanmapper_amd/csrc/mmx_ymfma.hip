@@ -34,13 +34,7 @@
 
 #include <cstdlib>
 
-#include "mmx_common.h"
-
-typedef _Float16 h2_y __attribute__((ext_vector_type(2)));
-typedef _Float16 h8_y __attribute__((ext_vector_type(8)));
-typedef float f2_y __attribute__((ext_vector_type(2)));
-typedef float f4_y __attribute__((ext_vector_type(4)));
-typedef unsigned u4_y __attribute__((ext_vector_type(4)));
+#include "mmx_device.h"
 
 struct ym_cfg {
     float w2[MMX_MAX_RADIUS_FAST + 1];      // G''(y) x (-norm) x (bound(P) / 65535) x 2^e: what a P count weighs
@@ -53,21 +47,6 @@ struct ym_cfg {
 };
 
 namespace {
-
-using rsrc_y = __amdgpu_buffer_rsrc_t;
-__device__ __forceinline__ rsrc_y make_rsrc_y(const void* p)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7fffffff, 0x00020000);
-}
-__device__ __forceinline__ unsigned pack_h2y(float a, float b)
-{
-    const f2_y v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, h2_y));
-}
-__device__ __forceinline__ f4_y mfma_y(const u4_y& a, const u4_y& b, const f4_y& c)
-{
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8_y, a), __builtin_bit_cast(h8_y, b), c, 0, 0, 0);
-}
 
 // Workgroup = four waves = one tile column.  NB <= 4 (R <= 16): 164 registers and 44 / 48 KiB of LDS, three workgroups
 // per CU; NB == 5 (R <= 24): 180 registers and 52 KiB, two (held to 168 registers it spills 20 and is slower: 2.10
@@ -92,7 +71,7 @@ ym_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile
 {
     constexpr int RB = 8 * (NB - 2);            // rows a k-block starts before the first output tile it feeds
     constexpr int NF = NB <= 4 ? 4 : YM6_NF;    // fragments per tile: [kernel: G'' (P), G (Q)][piece: wh, wl(, 256 wh)]
-    __shared__ u4_y frag[NB * NF * 64];         // (NF == 4: 256 wh is made from wh -- 16 KiB instead of 24: the third workgroup)
+    __shared__ v4u frag[NB * NF * 64];         // (NF == 4: 256 wh is made from wh -- 16 KiB instead of 24: the third workgroup)
     constexpr int WAVES = NB <= 4 ? 4 : YM6_WAVES;     // per workgroup: WAVES / 4 tile columns
     constexpr int JH = NB <= 4 ? 4 : YM6_JH;           // column sets whose pieces are held at a time
     __shared__ float tr[WAVES * 2 * 1024];      // per wave: two finished tiles of 16 rows x 64 columns
@@ -120,9 +99,9 @@ ym_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile
                 const float h = (float)(_Float16)ws;
                 v[u] = piece == 0 ? h : (piece == 1 ? (ws - h) * 256.f : h * 256.f);
             }
-            pk[i >> 1] = pack_h2y(v[0], v[1]);
+            pk[i >> 1] = pack_h2(v[0], v[1]);
         }
-        frag[e] = (u4_y){pk[0], pk[1], pk[2], pk[3]};
+        frag[e] = (v4u){pk[0], pk[1], pk[2], pk[3]};
     }
     __syncthreads();
 
@@ -138,7 +117,7 @@ ym_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile
     // ---- as a loader / MFMA operand holder: k-group kq, column index n16 (plane n16 >> 2, x quad n16 & 3)
     const int kq = lane >> 4, n16 = lane & 15;
     const unsigned trow_b = (unsigned)(ntx * ntz) * 1024u;      // bytes from one y to the next
-    const rsrc_y rs = make_rsrc_y(gt + (int64_t)bd.slot * tile_stride + (int64_t)tile * 256);
+    const rsrc_t rs = make_rsrc(gt + (int64_t)bd.slot * tile_stride + (int64_t)tile * 256);
     const unsigned voff = (unsigned)(zq * 256 + n16 * 16);
     const unsigned voff_s = voff + (unsigned)(8 * kq) * trow_b;  // blocks wholly inside the column: rows by scalar offset
     // ---- as a row worker (y6_kernel's lane): plane lane >> 4 of the quarter, column lane & 15
@@ -146,12 +125,16 @@ ym_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile
     const int z = 16 * U + 4 * zq + (lane >> 4), x = 16 * c + xi;
     const bool real = z < bd.nz && x < bd.nx;
     float* w1 = out + (int64_t)bd.slot * slot_elems;
-    const rsrc_y rsw = make_rsrc_y(w1);
+    const rsrc_t rsw = make_rsrc(w1);
     const unsigned ooff = (unsigned)((real ? z : 0) * bd.ny * bd.px + (real ? x : 0)) * 4u;
     const unsigned row_b = (unsigned)bd.px * 4u;
-    const int nent = ((bd.nz + 3) >> 2) * ntx;
-    ulonglong2* mrow = MASK ? reinterpret_cast<ulonglong2*>(mask) + ((int64_t)bd.slot * slot_elems >> 5) +
-                              (4 * U + zq) * ntx + c
+    // the entries of this wave's footprint (mmx_entries.h, MMX_MASK_QUADS).  The pending row's state and the candidate
+    // tests stay written out in this kernel: through mmx_pending_row / mmx_candidate it compiles to other code
+    // (profiles/r11_kernel_isa.txt), and it is 30 % of the headline step.
+    const mmx_entry_geom eg = mmx_entry_geom_make(MMX_MASK_QUADS, bd.nz, bd.nx, bd.px);
+    const int nent = eg.per_row;
+    ulonglong2* mrow = MASK ? reinterpret_cast<ulonglong2*>(mask) + mmx_entry_base(bd.slot, slot_elems) +
+                              mmx_quads_entry(eg, 4 * U + zq, 0) + c      // (its plane quad's first entry, then the tile)
                             : nullptr;
     unsigned long long ab_prev = 0;
     const bool has_l = xi > 0, has_r = xi < 15 && x + 1 < bd.nx;
@@ -159,26 +142,30 @@ ym_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile
     int ydone = 0;
     float* trw = tr + wv * 2048;
 
+    // the pending row's entry when it has no successor (the block's last row), or one that cannot beat it
+    auto close_pending = [&]() __attribute__((always_inline)) {
+        unsigned long long m = 0;
+        if (ab_prev) {
+            const bool cand = real & (prev1 > nms_lo) & !(fmaxf(prev2, nbx_prev) > prev1 + nms_eps);
+            m = __ballot(cand);
+        }
+        if (lane == 0) *mrow = make_ulonglong2(m, ab_prev);
+    };
     // one output row (y6_kernel's step after its taps; values and thresholds in accumulator units)
     auto row = [&](float acc, int y) __attribute__((always_inline)) {
-        const unsigned long long ab = MASK ? __ballot(real & (acc > nms_lo)) : ~0ull;
+        const unsigned long long ab = MASK ? mmx_above_word(real, acc, nms_lo) : ~0ull;
 #ifndef YM_NOSTORE
         if (ab && real) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc * us), rsw, ooff, (unsigned)y * row_b, 0);
 #endif
         if constexpr (MASK) {
             float nbx = -INFINITY;
             if (ab) {
-                const float l = __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(
-                    (int)__float_as_uint(acc), (int)__float_as_uint(acc), 0x111 /* row_shr:1 */, 0xf, 0xf, false));
-                const float rr = __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(
-                    (int)__float_as_uint(acc), (int)__float_as_uint(acc), 0x101 /* row_shl:1 */, 0xf, 0xf, false));
-                nbx = fmaxf(has_l ? l : -INFINITY, has_r ? rr : -INFINITY);
+                nbx = mmx_x_neighbours<false>(acc, has_l, has_r);
             }
             if (ydone > 0) {      // decide row ydone - 1, now that its successor is known
                 unsigned long long m = 0;
                 if (ab_prev) {
-                    const bool cand = real & (prev1 > nms_lo) &
-                                      !(fmaxf(fmaxf(prev2, acc), nbx_prev) > prev1 + nms_eps);
+                    const bool cand = real & (prev1 > nms_lo) & !(fmaxf(fmaxf(prev2, acc), nbx_prev) > prev1 + nms_eps);
                     m = __ballot(cand);
                 }
                 if (lane == 0) *mrow = make_ulonglong2(m, ab_prev);
@@ -197,12 +184,7 @@ ym_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile
             // nothing above the threshold in 16 rows x 64 columns: a value below it neither is a candidate nor beats
             // one, so the pending row is decided as if its successor were -inf and the rest are zero entries
             if (ydone > 0) {
-                unsigned long long m = 0;
-                if (ab_prev) {
-                    const bool cand = real & (prev1 > nms_lo) & !(fmaxf(prev2, nbx_prev) > prev1 + nms_eps);
-                    m = __ballot(cand);
-                }
-                if (lane == 0) *mrow = make_ulonglong2(m, ab_prev);
+                close_pending();
                 mrow += nent;
             }
             if (lane < cnt - 1) mrow[(int64_t)lane * nent] = make_ulonglong2(0ull, 0ull);
@@ -227,7 +209,7 @@ ym_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile
         unsigned long long ab[16];
         unsigned long long some = 0;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { ab[r] = __ballot(real & (v[r] > nms_lo)); some |= ab[r]; }
+        for (int r = 0; r < 16; ++r) { ab[r] = mmx_above_word(real, v[r], nms_lo); some |= ab[r]; }
         unsigned e0 = 0, e1 = 0, e2 = 0, e3 = 0;                   // entry = (cand lo, cand hi, above lo, above hi)
         auto put = [&](int ln, unsigned long long m, unsigned long long a) __attribute__((always_inline)) {
             const bool me = lane == ln;
@@ -248,11 +230,7 @@ ym_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile
 #ifndef YM_NOSTORE
                     if (real) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[r] * us), rsw, ooff, (unsigned)(16 * T + r) * row_b, 0);
 #endif
-                    const float l = __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(
-                        (int)__float_as_uint(v[r]), (int)__float_as_uint(v[r]), 0x111 /* row_shr:1 */, 0xf, 0xf, false));
-                    const float rr = __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(
-                        (int)__float_as_uint(v[r]), (int)__float_as_uint(v[r]), 0x101 /* row_shl:1 */, 0xf, 0xf, false));
-                    const float nbx = fmaxf(has_l ? l : -INFINITY, has_r ? rr : -INFINITY);
+                    const float nbx = mmx_x_neighbours<false>(v[r], has_l, has_r);
                     if (r < 15) {
                         const float below = r > 0 ? v[r > 0 ? r - 1 : 0] : prev1;
                         const bool cand = real & (v[r] > nms_lo) & !(fmaxf(fmaxf(below, v[r < 15 ? r + 1 : 15]), nbx) > v[r] + nms_eps);
@@ -279,13 +257,13 @@ ym_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile
 #define YM_PFD 1
 #endif
     constexpr int PFD = YM_PFD;                     // k-blocks of loads in flight per wave
-    u4_y rawA[8], rawB[PFD == 2 ? 8 : 1];
-    auto load_block = [&](int b, u4_y (&raw)[8]) __attribute__((always_inline)) {
+    v4u rawA[8], rawB[PFD == 2 ? 8 : 1];
+    auto load_block = [&](int b, v4u (&raw)[8]) __attribute__((always_inline)) {
         const int r0 = -RB + 32 * b;
         if (r0 >= 0 && r0 + 32 <= n) {
 #pragma unroll
             for (int i = 0; i < 8; ++i)
-                raw[i] = __builtin_bit_cast(u4_y, __builtin_amdgcn_raw_buffer_load_b128(rs, voff_s, (unsigned)(r0 + i) * trow_b, 0));
+                raw[i] = __builtin_bit_cast(v4u, __builtin_amdgcn_raw_buffer_load_b128(rs, voff_s, (unsigned)(r0 + i) * trow_b, 0));
         } else {
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
@@ -293,14 +271,14 @@ ym_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile
                 v = v < 0 ? -1 - v : v;
                 v = v >= n ? 2 * n - 1 - v : v;
                 v = v < 0 ? 0 : (v > n - 1 ? n - 1 : v);       // beyond the taps' reach: any row, zero weights
-                raw[i] = __builtin_bit_cast(u4_y, __builtin_amdgcn_raw_buffer_load_b128(rs, voff + (unsigned)v * trow_b, 0, 0));
+                raw[i] = __builtin_bit_cast(v4u, __builtin_amdgcn_raw_buffer_load_b128(rs, voff + (unsigned)v * trow_b, 0, 0));
             }
         }
     };
     const int nT = (n + 15) >> 4;
     const int nKB = (nT + NB - 3) / 2 + 1;          // last block b with 2 b - NB + 2 <= nT - 1
-    const f4_y start = {cfg.start, cfg.start, cfg.start, cfg.start};
-    f4_y acc[NB][4];                                // output tiles t = 0 .. NB - 1 of the current block (the last two start in it)
+    const v4f start = {cfg.start, cfg.start, cfg.start, cfg.start};
+    v4f acc[NB][4];                                // output tiles t = 0 .. NB - 1 of the current block (the last two start in it)
 #pragma unroll
     for (int t = 0; t < NB; ++t)
 #pragma unroll
@@ -310,7 +288,7 @@ ym_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile
     const _Float16 k256 = (_Float16)256.f;
     // one k-block: rows of the tiles the previous block finished, then per group of JH column sets: this block's pieces,
     // (last group: the next block's loads,) the MFMAs, the hand-off of the two tiles that are complete
-    auto iter = [&](int b, u4_y (&raw)[8]) __attribute__((always_inline)) {
+    auto iter = [&](int b, v4u (&raw)[8]) __attribute__((always_inline)) {
         // -- rows first (before this block's operands take their registers; their stores are older than the loads
         //    issued below, so waiting for those does not wait for these)
 #ifndef YM_ROWS_LATE
@@ -326,7 +304,7 @@ ym_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile
         for (int j0 = 0; j0 < 4; j0 += JH) {
             __builtin_amdgcn_sched_barrier(0);
             // -- the four float16 pieces of every dword, one byte permute each: [j][Phi, Plo, Qhi, Qlo], k pairs (2p, 2p + 1)
-            u4_y pc[JH][4];
+            v4u pc[JH][4];
 #pragma unroll
             for (int j = 0; j < JH; ++j)
 #pragma unroll
@@ -349,31 +327,31 @@ ym_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile
             // -- output tile T = 2 b - NB + 2 + t.  Tiles t = 0, 1 get their last block here and leave for LDS at once
             //    (their registers are free for the two tiles that start with this block: t = NB - 2, NB - 1)
             auto tile_mfmas = [&](int t, bool fresh) __attribute__((always_inline)) {
-                f4_y* a = &acc[t][j0];
-                const u4_y* fr = frag + (t * NF) * 64 + lane;
-                const u4_y ah = fr[0], al = fr[64], bh = fr[(NF / 2) * 64], bl = fr[(NF / 2 + 1) * 64];
+                v4f* a = &acc[t][j0];
+                const v4u* fr = frag + (t * NF) * 64 + lane;
+                const v4u ah = fr[0], al = fr[64], bh = fr[(NF / 2) * 64], bl = fr[(NF / 2 + 1) * 64];
                 // (x 256: an exponent shift, exact)
-                const u4_y a256 = NF == 6 ? fr[128] : __builtin_bit_cast(u4_y, __builtin_bit_cast(h8_y, ah) * k256);
-                const u4_y b256 = NF == 6 ? fr[320] : __builtin_bit_cast(u4_y, __builtin_bit_cast(h8_y, bh) * k256);
+                const v4u a256 = NF == 6 ? fr[128] : __builtin_bit_cast(v4u, __builtin_bit_cast(v8h, ah) * k256);
+                const v4u b256 = NF == 6 ? fr[320] : __builtin_bit_cast(v4u, __builtin_bit_cast(v8h, bh) * k256);
 #pragma unroll
-                for (int j = 0; j < JH; ++j) a[j] = mfma_y(a256, pc[j][0], fresh ? start : a[j]);
+                for (int j = 0; j < JH; ++j) a[j] = mfma16(a256, pc[j][0], fresh ? start : a[j]);
 #pragma unroll
-                for (int j = 0; j < JH; ++j) a[j] = mfma_y(ah, pc[j][1], a[j]);
+                for (int j = 0; j < JH; ++j) a[j] = mfma16(ah, pc[j][1], a[j]);
 #pragma unroll
-                for (int j = 0; j < JH; ++j) a[j] = mfma_y(al, pc[j][0], a[j]);
+                for (int j = 0; j < JH; ++j) a[j] = mfma16(al, pc[j][0], a[j]);
 #pragma unroll
-                for (int j = 0; j < JH; ++j) a[j] = mfma_y(b256, pc[j][2], a[j]);
+                for (int j = 0; j < JH; ++j) a[j] = mfma16(b256, pc[j][2], a[j]);
 #pragma unroll
-                for (int j = 0; j < JH; ++j) a[j] = mfma_y(bh, pc[j][3], a[j]);
+                for (int j = 0; j < JH; ++j) a[j] = mfma16(bh, pc[j][3], a[j]);
 #pragma unroll
-                for (int j = 0; j < JH; ++j) a[j] = mfma_y(bl, pc[j][2], a[j]);
+                for (int j = 0; j < JH; ++j) a[j] = mfma16(bl, pc[j][2], a[j]);
             };
 #pragma unroll
             for (int t = 0; t < 2; ++t) tile_mfmas(t, t >= NB - 2);      // (NB == 3: tile 1 starts and ends in this block)
             // (accumulator register r of lane (g, n16) is row 4 g + r, column 4 n16 + j of the wave's 64)
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
-                const f4_y* a = &acc[t][j0];
+                const v4f* a = &acc[t][j0];
                 float mx = -INFINITY;
 #pragma unroll
                 for (int j = 0; j < JH; ++j)
@@ -383,15 +361,15 @@ ym_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile
                 if constexpr (JH == 4) {
                     if (t == 0) any0 = any; else any1 = any;
                     if (any) {
-                        f4_y* dst = reinterpret_cast<f4_y*>(trw + t * 1024) + (4 * kq) * 16 + n16;
+                        v4f* dst = reinterpret_cast<v4f*>(trw + t * 1024) + (4 * kq) * 16 + n16;
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) dst[r * 16] = (f4_y){a[0][r], a[1][r], a[2][r], a[3][r]};
+                        for (int r = 0; r < 4; ++r) dst[r * 16] = (v4f){a[0][r], a[1][r], a[2][r], a[3][r]};
                     }
                 } else {        // (half a tile: the other half may be what is above the threshold)
                     if (t == 0) any0 |= any; else any1 |= any;
-                    f2_y* dst = reinterpret_cast<f2_y*>(trw + t * 1024) + (4 * kq) * 32 + 2 * n16 + (j0 >> 1);
+                    v2f* dst = reinterpret_cast<v2f*>(trw + t * 1024) + (4 * kq) * 32 + 2 * n16 + (j0 >> 1);
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) dst[r * 32] = (f2_y){a[0][r], a[1][r]};
+                    for (int r = 0; r < 4; ++r) dst[r * 32] = (v2f){a[0][r], a[1][r]};
                 }
             }
             __builtin_amdgcn_sched_barrier(0);     // (the finished tiles' registers are free from here on)
@@ -412,24 +390,17 @@ ym_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile
     };
     load_block(0, rawA);
     if constexpr (PFD == 2) {
-        if (nKB > 1) load_block(1, reinterpret_cast<u4_y (&)[8]>(rawB));
+        if (nKB > 1) load_block(1, reinterpret_cast<v4u (&)[8]>(rawB));
 #pragma unroll 1
         for (int b = 0;; b += 2) {
             if (!iter(b, rawA)) break;
-            if (!iter(b + 1, reinterpret_cast<u4_y (&)[8]>(rawB))) break;
+            if (!iter(b + 1, reinterpret_cast<v4u (&)[8]>(rawB))) break;
         }
     } else {
 #pragma unroll 1
         for (int b = 0; iter(b, rawA); ++b) {}
     }
-    if constexpr (MASK) {     // the last row has no successor
-        unsigned long long m = 0;
-        if (ab_prev) {
-            const bool cand = real & (prev1 > nms_lo) & !(fmaxf(prev2, nbx_prev) > prev1 + nms_eps);
-            m = __ballot(cand);
-        }
-        if (lane == 0) *mrow = make_ulonglong2(m, ab_prev);
-    }
+    if constexpr (MASK) close_pending();     // the last row has no successor
 }
 
 template <int NB>

@@ -2,8 +2,9 @@
 // with the full route they must get --, the by-name rows shared with tests/test_gpu_routes.py (tests/golden/
 // route_by_name.txt, path in argv[1]), and a sweep over geometries, radii, voxel types and modes for two properties: no
 // route selects a launcher whose predicate refuses it, and the route of a call agrees with the route of a one-scale
-// ladder.  Meant to run under the host sanitizers (the command: DESIGN.md, "Wide radii").  No device code, no HIP call:
-// the batch geometry is filled in by hand.  Exit status 0 = every row and the sweep passed.
+// ladder.  Before that sweep, one over the NMS entry layouts (csrc/mmx_entries.h, host side).  Meant to run under the
+// host sanitizers (the command: DESIGN.md, "Wide radii").  No device code, no HIP call: the batch geometry is filled in
+// by hand.  Exit status 0 = every row and the sweeps passed.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -353,12 +354,60 @@ int sweep()
     return refused || disagree;
 }
 
+// ---- the NMS entry layouts (csrc/mmx_entries.h, host side): on ragged blocks -- planes no multiple of 4, columns no
+// multiple of 16 or 64, a row pitch above nx, one block 530 wide -- every voxel has an (entry, bit) below the per-row
+// count, no two voxels share one, both are what the prose of include/mmx.h says, the inverse returns the voxel, and
+// "fits" equals the two expressions mmx_batch_geom_make computed inline before the header existed (stated below).
+int sweep_entries()
+{
+    long voxels = 0, bad = 0;
+    for (int nz : {1, 3, 4, 5, 17, 30}) for (int nx : {1, 15, 16, 17, 63, 64, 65, 100, 261, 530}) for (int pad : {0, 1}) {
+        const int px = (nx + MMX_ROW_ALIGN - 1) / MMX_ROW_ALIGN * MMX_ROW_ALIGN + pad * MMX_ROW_ALIGN;
+        for (int layout : {MMX_MASK_ROWS, MMX_MASK_QUADS}) {
+            const mmx_entry_geom g = mmx_entry_geom_make(layout, nz, nx, px);
+            if (g.per_row != mmx_entries_per_row<int>(layout, nz, nx, px) || g.per_row < 1) ++bad;
+            // (mmx.h: ceil(nz * px / 64) entries per row y, or ceil(nz / 4) * ceil(nx / 16))
+            if (g.per_row != (layout == MMX_MASK_ROWS ? (nz * px + 63) / 64 : ((nz + 3) / 4) * ((nx + 15) / 16))) ++bad;
+            if (mmx_entry_base(3, 1000) != (3 * 1000) >> 5) ++bad;          // (the block in slot b starts at entry (b * slot_elems) >> 5)
+            std::vector<char> seen((size_t)g.per_row * 64, 0);
+            for (int z = 0; z < nz; ++z) for (int x = 0; x < nx; ++x, ++voxels) {
+                const int e = mmx_entry_index(g, z, x), b = mmx_entry_bit(g, z, x);
+                // the layouts as include/mmx.h states them (d_nms_mask), written out here independently of the header
+                const int c = z * px + x;
+                const int want_e = layout == MMX_MASK_ROWS ? c >> 6 : (z >> 2) * ((nx + 15) / 16) + (x >> 4);
+                const int want_b = layout == MMX_MASK_ROWS ? c & 63 : ((z & 3) << 4) | (x & 15);
+                if (e != want_e || b != want_b) ++bad;
+                if (e < 0 || e >= g.per_row || b < 0 || b > 63) { ++bad; continue; }
+                if (seen[(size_t)e * 64 + b]++) ++bad;
+                int zi = -1, xi = -1;
+                mmx_entry_voxel(g, e, b, &zi, &xi);
+                if (zi != z || xi != x) ++bad;
+            }
+            // slots from far too small to ample, every multiple of 32 around the limit included
+            for (int ny : {1, 7, 40}) {
+                const int64_t need = ((int64_t)ny * g.per_row + 1) * 32;
+                for (int64_t slot_elems : {int64_t(0), int64_t(31), need - 33, need - 32, need - 1, need, need + 31, need + 32,
+                                           (int64_t)nz * ny * px, int64_t(1) << 40}) {
+                    if (slot_elems < 0) continue;
+                    const bool old_fit = layout == MMX_MASK_ROWS
+                        ? !((int64_t)ny * (((int64_t)nz * px + 63) >> 6) > (slot_elems >> 5) - 1)
+                        : !((int64_t)ny * ((nz + 3) >> 2) * ((nx + 15) >> 4) > (slot_elems >> 5) - 1);
+                    if (mmx_entries_fit(layout, nz, ny, nx, px, slot_elems) != old_fit) ++bad;
+                }
+            }
+        }
+    }
+    printf("entries: %ld voxels in two layouts, %ld failures\n", voxels, bad);
+    return bad != 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv)
 {
     int bad = check_table();
     bad += check_by_name(argc > 1 ? argv[1] : "tests/golden/route_by_name.txt");
+    bad += sweep_entries();
     bad += sweep();
     return bad ? 1 : 0;
 }
