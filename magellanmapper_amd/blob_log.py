@@ -33,7 +33,7 @@ import ctypes
 import os
 import time
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -104,10 +104,7 @@ HOST_PATH = os.environ.get("MMX_HOST_PATH", "native")
 FLOAT_TILED_RANGE = (0.0, 2.0 ** 12)
 #: per-block preprocessing on a stream of its own (beside the previous batch's LoG kernels)
 PRE_STREAM = True
-#: ... with the NMS / re-score tail of a preprocessed batch on the second stream too.  Off:
-#: measured on the box it LOSES -- 283.6 against 278.9 ms (two-channel tile), 214.6 against 212.4 ms (--denoise 25): the
-#: preprocessing kernel already fills every CU it can, a third stream only adds to the time-sharing
-PRE_SIDE_TAIL = False
+#: (the NMS / re-score tail of a PREPROCESSED batch stays on the main stream: DESIGN.md, "Host side of a step")
 #: ... and this many batches ahead of the one the host is finishing (``preprocess.N_BUFFER_SETS`` - 1 buffer sets allow
 #: it): the first batch is then the only one whose LoG passes wait for their preprocessing
 PRE_AHEAD = 2
@@ -120,8 +117,10 @@ PRE_AHEAD_RETAINED = 2
 #: 4.5 ms and the Z+X kernel 59 instead of 53 when they run beside each other; the re-score alone on the side stream,
 #: one workspace: -2.8 ms)
 RESCORE_STREAM = True
-PACK_STREAM = False
 
+from . import batch_plan as _bp   # noqa: E402
+from .batch_plan import (LIB_MAX_SLOT_ELEMS, MAX_PARTS, BatchPlan, PartSplit, PlannedBatch, _isolate_parents,   # noqa: F401,E402
+                         _row_elems, _slot_elems, block_records, slot_limit, slot_refusal, split_oversized)
 from .volume import (DeviceVolume, _SlabUpload, _img_as_float_host, _require_gpu, _stream_ptr,   # noqa: F401,E402
                      _NP_TO_MMX, _TORCH_DTYPES)
 from .buffers import (_Buffers, _NativeEvent, _UploadRing, _buffers_for, _stream_wait, _to_device_bytes,   # noqa: F401,E402
@@ -230,27 +229,10 @@ TAPER = 4
 RAMP = 16
 #: experiments only: cut the block list into batches of exactly these sizes (when they add up to the number of blocks)
 FORCED_BATCH_SIZES: list = []
-
-
-def _row_elems(nx):
-    """Elements of a workspace row that holds ``nx`` voxels: rows are ``MMX_ROW_ALIGN`` elements (128 bytes) aligned."""
-    return -(-nx // nat.MMX_ROW_ALIGN) * nat.MMX_ROW_ALIGN
-
-
-def _slot_elems(shapes):
-    """Workspace elements a block of ``(nz, ny, nx)`` voxels takes, its rows padded (:func:`_row_elems`).  One shape
-    gives one number, an ``(n, 3)`` list of shapes an array of ``n``."""
-    shp = np.asarray(shapes, dtype=np.int64)
-    return shp[..., 0] * shp[..., 1] * _row_elems(shp[..., 2])
-
-
 #: a block whose workspace slot (:func:`_slot_elems`) reaches this many elements is detected as several overlapping parts
-#: (:func:`split_oversized`; DESIGN.md section 4f).  The library refuses such a slot itself (its kernels address a slot
-#: with 32-bit byte offsets), so a value above ``LIB_MAX_SLOT_ELEMS`` counts as that; tests lower it
+#: (:func:`split_oversized`).  The library refuses such a slot itself, so a value above
+#: ``LIB_MAX_SLOT_ELEMS`` counts as that; tests lower it
 MAX_SLOT_ELEMS = 1 << 29
-LIB_MAX_SLOT_ELEMS = 1 << 29
-#: most parts one block is cut into (the search for the smallest grid stops there)
-MAX_PARTS = 4096
 #: experiments and tests only: cut every oversized block into this ``(gz, gy, gx)`` grid instead of the smallest one (a
 #: grid the search would never pick -- a cut that saves no padded row -- or the cost of a split on blocks that need none,
 #: tools/partsbench.py); its boxes must still stay below the limit
@@ -258,125 +240,15 @@ FORCED_PART_GRID: Optional[Tuple[int, int, int]] = None
 
 
 def _slot_limit() -> int:
-    return max(1, min(int(MAX_SLOT_ELEMS), LIB_MAX_SLOT_ELEMS))
+    return slot_limit(MAX_SLOT_ELEMS)
 
 
-@dataclass
-class PartSplit:
-    """One block (the *parent*) cut into parts: ``grid`` parts per axis, ``cuts[axis]`` the ``grid[axis] + 1`` planes
-    between the cores (0 and the extent included), and per part, in C order of the grid, ``cores`` and ``boxes`` as
-    ``[lo, hi)`` corners in parent coordinates, shape ``(n, 2, 3)``.  The cores partition the parent; a box is its core
-    extended by the halo on every side, out to the next multiple of ``align`` where one is asked for, clipped to the
-    parent."""
-    shape: Tuple[int, int, int]
-    halo: int
-    grid: Tuple[int, int, int]
-    cuts: Tuple[np.ndarray, np.ndarray, np.ndarray]
-    cores: np.ndarray
-    boxes: np.ndarray
-
-    def __len__(self) -> int:
-        return len(self.cores)
-
-    @property
-    def box_shapes(self) -> np.ndarray:
-        return self.boxes[:, 1] - self.boxes[:, 0]
-
-    def records(self, parent: int = 0) -> np.ndarray:
-        """The ``mmx_part`` records (``mmx_fold_parts``): cores in part coordinates."""
-        rec = np.zeros(len(self), dtype=nat.PART_DTYPE)
-        rec["parent"] = parent
-        rec["off"] = self.boxes[:, 0]
-        rec["core_lo"] = self.cores[:, 0] - self.boxes[:, 0]
-        rec["core_hi"] = self.cores[:, 1] - self.boxes[:, 0]
-        return rec
-
-
-def _axis_pieces(n: int, g: int, halo: int, a: int):
-    """``g`` cores along an axis of ``n`` voxels and their boxes: ``(cuts, box_lo, box_hi)``, or None when ``n`` voxels
-    do not make ``g`` cores."""
-    if g > n:
-        return None
-    cuts = (np.arange(g + 1, dtype=np.int64) * n) // g
-    lo = np.maximum(cuts[:-1] - halo, 0) // a * a
-    hi = np.minimum(-(-(cuts[1:] + halo) // a) * a, n)
-    return cuts, lo, hi
-
-
-def split_oversized(shape: Sequence[int], max_slot_elems: int, halo: int, align: Sequence[int] = (1, 1, 1),
-                    grid: Optional[Sequence[int]] = None) -> PartSplit:
-    """Cut a block of ``shape`` whose workspace slot would reach ``max_slot_elems`` elements into the fewest parts whose
-    slots stay below it (:class:`PartSplit`).  A pure function of its arguments.
-
-    The cores are a grid of near-equal boxes that partition the block; every part's box is its core plus ``halo``
-    voxels on every side (``halo`` = largest kernel radius of the ladder + 1: a LoG value needs the voxels within the
-    radius, and the 3^4 NMS needs valid values one voxel around the core), clipped to the block.  With ``align`` (the
-    profile's ``denoise_max_shape`` when the blocks are preprocessed tile by tile) box faces that are not faces of the
-    block are moved outwards to the next multiple of ``align`` from the block's origin, so that a part's tile grid is
-    the block's.  Among the grids with the fewest parts the one whose largest box is smallest is taken -- the longest
-    axis is cut first, since that adds the least halo -- and of equals the one that cuts the later axes.  ``grid``
-    (experiments): that ``(gz, gy, gx)`` grid and no other.
-    ``MmxError`` when no such grid exists: the halo alone fills a slot."""
-    shape = tuple(int(v) for v in shape)
-    align = tuple(max(1, int(v)) for v in align)
-    halo, limit = int(halo), int(max_slot_elems)
-    if len(shape) != 3 or min(shape) < 1 or halo < 0 or len(align) != 3:
-        raise ValueError("split_oversized takes a (z, y, x) extent, a halo >= 0 and a per-axis alignment")
-    refuse = "block too large for one workspace slot (>= 2^29 voxels)" if limit >= LIB_MAX_SLOT_ELEMS else \
-        f"block too large for one workspace slot (>= {limit} elements)"
-    # the smallest box any grid can give: a core of one voxel and its halo, rounded out to the alignment
-    least = [min(n, -(-(1 + 2 * halo) // a) * a) for n, a in zip(shape, align)]
-    if int(_slot_elems(least)) >= limit:
-        raise nat.MmxError(f"{refuse} and it cannot be cut into parts: a part's halo of {halo} voxels on every side "
-                           f"(largest kernel radius + 1) alone takes {int(_slot_elems(least))} elements; detect with a "
-                           "smaller segment_size")
-    only = None if grid is None else tuple(int(v) for v in grid)
-    if only is not None and (len(only) != 3 or min(only) < 1):
-        raise ValueError("a grid of parts is (gz, gy, gx), each at least 1")
-    # per axis the piece counts worth trying -- those that make the largest box (along x: its padded row) smaller than
-    # every smaller count does -- and what they make it; the grids are their combinations
-    counts, sizes, pieces = [], [], {}
-    for ax in range(3):
-        tries = range(1, min(shape[ax], MAX_PARTS) + 1) if only is None else [only[ax]]
-        gs, es, least_e = [], [], None
-        for g in tries:
-            pc = _axis_pieces(shape[ax], g, halo, align[ax])
-            if pc is None:
-                continue
-            e = int((pc[2] - pc[1]).max())
-            e = int(_row_elems(e)) if ax == 2 else e
-            if least_e is None or e < least_e:
-                gs.append(g)
-                es.append(e)
-                pieces[(ax, g)] = pc
-                least_e = e
-            if e <= least[ax]:          # (it gets no smaller)
-                break
-        counts.append(np.asarray(gs, dtype=np.int64))
-        sizes.append(np.asarray(es, dtype=np.int64))
-    if all(len(c) for c in counts):
-        n_parts = counts[0][:, None, None] * counts[1][None, :, None] * counts[2][None, None, :]
-        worst = sizes[0][:, None, None] * sizes[1][None, :, None] * sizes[2][None, None, :]
-        ok = (worst < limit) & (n_parts <= MAX_PARTS)
-        if ok.any():
-            # fewest parts, then the smallest largest box, then the grid that cuts the later axes (C order of the grids)
-            key = np.where(ok, n_parts, np.iinfo(np.int64).max)
-            cand = np.argwhere(key == key.min())
-            cand = cand[np.argsort(worst[tuple(cand.T)], kind="stable")]
-            iz, iy, ix = (int(v) for v in cand[0])
-            grid3 = (int(counts[0][iz]), int(counts[1][iy]), int(counts[2][ix]))
-            axes = [pieces[(ax, g)] for ax, g in enumerate(grid3)]
-            idx = np.stack(np.meshgrid(*(np.arange(g) for g in grid3), indexing="ij"), axis=-1).reshape(-1, 3)
-            cores = np.empty((len(idx), 2, 3), dtype=np.int64)
-            boxes = np.empty_like(cores)
-            for ax in range(3):
-                cuts, lo, hi = axes[ax]
-                cores[:, 0, ax], cores[:, 1, ax] = cuts[idx[:, ax]], cuts[idx[:, ax] + 1]
-                boxes[:, 0, ax], boxes[:, 1, ax] = lo[idx[:, ax]], hi[idx[:, ax]]
-            return PartSplit(shape, halo, grid3, tuple(a_[0] for a_ in axes), cores, boxes)
-    how = f"{MAX_PARTS} parts or fewer" if only is None else f"a {only[0]} x {only[1]} x {only[2]} grid of parts"
-    raise nat.MmxError(f"{refuse} and it cannot be cut into {how} with a halo of {halo} voxels; detect with a smaller "
-                       "segment_size")
+def plan_batches(shapes: Sequence[Tuple[int, int, int]], num_sigma: int,
+                 budget_bytes: int, extra_bytes_per_voxel: int = 0) -> List[List[int]]:
+    """:func:`batch_plan.plan_batches` with this module's settings: block indices grouped into batches whose workspace
+    fits ``budget_bytes``."""
+    return _bp.plan_batches(shapes, num_sigma, budget_bytes, extra_bytes_per_voxel, taper=TAPER, ramp=RAMP,
+                            max_batch=_MAX_BATCH, forced_sizes=FORCED_BATCH_SIZES)
 
 
 def _split_blocks(lanes, shapes, limit: int) -> Dict[int, PartSplit]:
@@ -409,36 +281,6 @@ def _split_blocks(lanes, shapes, limit: int) -> Dict[int, PartSplit]:
     return {int(i): split_oversized(shapes[int(i)], limit, halo, align, FORCED_PART_GRID) for i in big}
 
 
-def _isolate_parents(batches: List[List[int]], splits: Dict[int, PartSplit]) -> List[List[int]]:
-    """``batches`` with every block that is detected in parts in a batch of its own (its parts are that batch's blocks)."""
-    out: List[List[int]] = []
-    for b in batches:
-        cur: List[int] = []
-        for i in b:
-            if i in splits:
-                if cur:
-                    out.append(cur)
-                out.append([i])
-                cur = []
-            else:
-                cur.append(i)
-        if cur:
-            out.append(cur)
-    return out
-
-
-def _part_blocks(parent, split: PartSplit, strides) -> Tuple[np.ndarray, int]:
-    """``mmx_block`` records of the parts of ``parent`` (one ``mmx_block`` record), which lies in a volume of element
-    ``strides`` (z, y, x): part i owns slot i.  Returns them and the slot size they need."""
-    lo, shp = split.boxes[:, 0], split.box_shapes
-    blocks = np.zeros(len(split), dtype=nat.BLOCK_DTYPE)
-    blocks["src_off"] = int(parent["src_off"]) + lo @ np.asarray(strides, dtype=np.int64)
-    blocks["nz"], blocks["ny"], blocks["nx"] = shp[:, 0], shp[:, 1], shp[:, 2]
-    blocks["slot"] = np.arange(len(split))
-    blocks["px"] = _row_elems(shp[:, 2])
-    return blocks, max(1, int(_slot_elems(shp).max()))
-
-
 def _workspace(bufs, n_floats: int, which: int, split: Optional[PartSplit]):
     """``bufs.workspace`` -- and for a block in parts, whose workspace holds all of them at once, an error that says what
     was needed and what to do about it."""
@@ -452,93 +294,9 @@ def _workspace(bufs, n_floats: int, which: int, split: Optional[PartSplit]):
                            "memory that could not be allocated; detect with a smaller segment_size") from exc
 
 
-def plan_batches(shapes: Sequence[Tuple[int, int, int]], num_sigma: int,
-                 budget_bytes: int, extra_bytes_per_voxel: int = 0) -> List[List[int]]:
-    """Group block indices into batches whose workspace fits ``budget_bytes``.
-
-    Workspace = (4 + num_sigma) float32 arrays of ``n_blocks * slot`` voxels, slot = the
-    largest block of the batch (+ ``extra_bytes_per_voxel`` for the preprocessed copies).
-    Blocks keep their order (z-major grid order).
-    """
-    per_vox = (4 + num_sigma) * 4 + (num_sigma + 1) // 2 + extra_bytes_per_voxel     # + the NMS bit masks
-    if not len(shapes):
-        return []
-    if FORCED_BATCH_SIZES and sum(FORCED_BATCH_SIZES) == len(shapes):       # (experiments: bench.py --batches)
-        cuts = np.concatenate(([0], np.cumsum(FORCED_BATCH_SIZES)))
-        return [list(range(int(a), int(b))) for a, b in zip(cuts[:-1], cuts[1:])]
-    slots = _slot_elems(np.asarray(shapes).reshape(-1, 3)).tolist()
-    batches: List[List[int]] = []
-    cur: List[int] = []
-    cur_slot = 0
-    for i, vox in enumerate(slots):
-        slot = max(cur_slot, vox)
-        if cur and ((len(cur) + 1) * slot * per_vox > budget_bytes or len(cur) >= _MAX_BATCH):
-            batches.append(cur)
-            cur, slot = [], vox
-        cur.append(i)
-        cur_slot = slot
-    if cur:
-        batches.append(cur)
-    # The host finishes batch k (candidates -> peaks -> per-block prune -> tables: ~0.45 ms per block of the
-    # benchmark volume) while the GPU runs batch k + 1 (~0.46 ms per block with the tiled kernels), so it trails the
-    # GPU by the host time of one batch, and nothing hides that of the LAST batches: the tail of the block list is
-    # re-split into batches that shrink geometrically towards the end (... 18 / 11 / 7 / 4 blocks) -- each still
-    # gives the GPU about as much work as the host has left from the batch before.  Measured (tools/steptrace.py):
-    # 89 / 89 / 59 / 19 blocks left the host 8 ms behind the GPU at the end and 18 ms of tail, 89 / 89 / 39 / 20 /
-    # 10 / 5 / 4 did not; with 22-block batches a tail of 22 / 7 / 7 against 18 / 18 / 11 / 7 / 4.
-    taper = TAPER
-    vox = [int(s_[0]) * int(s_[1]) * int(s_[2]) for s_ in shapes]
-
-    def fits(batch):
-        return len(batch) == 1 or (len(batch) * max(slots[i] for i in batch) * per_vox <= budget_bytes and len(batch) <= _MAX_BATCH)
-
-    full = max(len(b_) for b_ in batches)
-    tail = batches.pop()
-    while batches and len(tail) < 2 * full and _MAX_BATCH >= (1 << 30):      # (a capped batch size: no re-merging)
-        tail = batches.pop() + tail
-    # (only where there is real work: below ~64 Mvoxel a batch is a few hundred microseconds of kernels)
-    if taper > 0 and len(tail) > taper and sum(vox[i] for i in tail) > (64 << 20):
-        sizes, step = [], float(taper)
-        while sum(sizes) + int(step) <= len(tail) and int(step) < full:
-            sizes.append(int(step))
-            step *= 1.6
-        rest = len(tail) - sum(sizes)
-        n_front = -(-rest // full) if rest else 0
-        front = [rest // n_front + (1 if j < rest % n_front else 0) for j in range(n_front)] if n_front else []
-        at, pieces = 0, []
-        for n in front + sizes[::-1]:
-            pieces.append(tail[at:at + n])
-            at += n
-        tail_batches = []
-        for piece in pieces:                    # (blocks of different sizes: a piece may exceed the budget its count suggests)
-            while not fits(piece):
-                cut = len(piece) // 2
-                tail_batches.append(piece[:cut])
-                piece = piece[cut:]
-            tail_batches.append(piece)
-        batches.extend(tail_batches)
-    else:
-        stack = [tail]
-        while stack:                             # (the merged tail of small batches must still fit the budget)
-            piece = stack.pop(0)
-            if fits(piece):
-                batches.append(piece)
-            else:
-                stack[0:0] = [piece[:len(piece) // 2], piece[len(piece) // 2:]]
-    # ... and nothing hides the GPU time of the FIRST batch from the host, which has nothing to do until its
-    # candidates arrive: with the tiled kernels the host work per block (~0.5 ms) is as long as the kernels'
-    # (~0.55 ms), so a first batch of 89 blocks put the host 50 ms behind for the whole step (tail after the last
-    # kernel 24 - 38 ms).  The first batch is therefore split into a ramp of `MMX_RAMP`, 2 x, 4 x ... blocks.
-    ramp = RAMP
-    first = batches[0]
-    if ramp > 0 and len(batches) > 1 and len(first) > 2 * ramp and sum(vox[i] for i in first) > (64 << 20):
-        head = []
-        while len(first) > 2 * ramp:
-            head.append(first[:ramp])
-            first = first[ramp:]
-            ramp *= 2
-        batches[0:1] = head + [first]
-    return batches
+def _workspace_floats(nb: int, slot: int, ns: int) -> int:
+    """float32 elements of the workspace of a batch of ``nb`` blocks in slots of ``slot`` elements, ``ns`` scales."""
+    return -(-int(nat.lib().mmx_workspace_bytes(nb, slot, ns, 1)) // 4)
 
 
 _SELF_TESTED = set()
@@ -633,23 +391,20 @@ def log_cube_blocks(dvol: DeviceVolume, channel: int, origins, shapes, space: Sc
 
 def _make_blocks(dvol: DeviceVolume, channel: int, origins, shapes):
     """``mmx_block`` records of one batch (block i owns slot i) and the workspace slot size they need."""
-    t = dvol.tensor
-    strides = np.array([t.stride()[0], t.stride()[1], t.stride()[2]], dtype=np.int64)
-    blocks = np.zeros(len(shapes), dtype=nat.BLOCK_DTYPE)
-    if not len(shapes):
-        return blocks, 1
+    o = _held_origins(dvol, origins, shapes)
+    return block_records(o @ np.asarray(dvol.tensor.stride()[:3], dtype=np.int64), shapes)
+
+
+def _held_origins(dvol: DeviceVolume, origins, shapes) -> np.ndarray:
+    """``origins`` as an ``(n, 3)`` array, once the blocks are known to lie in what ``dvol`` holds."""
     o = np.asarray(origins, dtype=np.int64).reshape(-1, 3)
     shp = np.asarray(shapes, dtype=np.int64).reshape(-1, 3)
     if (o < 0).any() or (shp < 1).any() or (o + shp > np.asarray(dvol.shape[:3], dtype=np.int64)).any():
         raise ValueError("block outside the volume")
     held_lo = np.array([dvol.z_off, dvol.y_off, 0], dtype=np.int64)
-    if (o < held_lo).any() or (o[:, :2] + shp[:, :2] > held_lo[:2] + np.asarray(t.shape[:2], dtype=np.int64)).any():
+    if (o < held_lo).any() or (o[:, :2] + shp[:, :2] > held_lo[:2] + np.asarray(dvol.tensor.shape[:2], dtype=np.int64)).any():
         raise ValueError("block outside the planes and rows this volume holds")
-    blocks["src_off"] = o @ strides
-    blocks["nz"], blocks["ny"], blocks["nx"] = shp[:, 0], shp[:, 1], shp[:, 2]
-    blocks["slot"] = np.arange(len(shp))
-    blocks["px"] = _row_elems(shp[:, 2])
-    return blocks, max(1, int(_slot_elems(shp).max()))
+    return o
 
 
 def blob_log_blocks(dvol: DeviceVolume, channel: int, origins: Sequence[Sequence[int]],
@@ -743,6 +498,94 @@ BUDGET_BYTES = 24 << 30
 BATCH_MAJOR = "uploading"
 
 
+class _BlockLists(NamedTuple):
+    """The block lists of a call as given, their checked copies, content key and largest slot (``_Buffers.plan_lists``)."""
+    given: tuple                # (origins, shapes) as passed -- kept alive: their ids stay theirs
+    key: tuple
+    origins: list
+    shapes: list
+    slot_max: int
+
+
+def _block_lists(bufs: _Buffers, origins, shapes) -> _BlockLists:
+    """The very same tuple objects step after step (stack_detect hands over its cached block lists): their checked copies
+    and their content key are remembered -- converting and hashing 256 blocks is 0.3 ms before the first launch.
+    (tuples only: a list could have been edited in place since)"""
+    immutable = type(origins) is tuple and type(shapes) is tuple
+    seen = bufs.plan_lists.get((id(origins), id(shapes))) if immutable else None
+    if seen is not None and seen.given[0] is origins and seen.given[1] is shapes:
+        return seen
+    given = (origins, shapes)
+    shapes = [tuple(int(v) for v in s) for s in shapes]
+    origins = [tuple(int(v) for v in o) for o in origins]
+    slot_max = int(_slot_elems(np.asarray(shapes, dtype=np.int64).reshape(-1, 3)).max()) if shapes else 0
+    lists = _BlockLists(given, (tuple(origins), tuple(shapes)), origins, shapes, slot_max)
+    if immutable:
+        if len(bufs.plan_lists) >= 8:
+            bufs.plan_lists.clear()
+        bufs.plan_lists[(id(given[0]), id(given[1]))] = lists
+    return lists
+
+
+def _plan_for(dvol: DeviceVolume, lanes, lists: _BlockLists, bufs: _Buffers, ns: int, budget_bytes: int) -> BatchPlan:
+    """The batches of the call, planned for ``ns`` scales.  Raw lanes with no block in parts: remembered in
+    ``bufs.plans`` for the same block lists, volume layout and budget (a stack detected step after step) -- a
+    millisecond of planning, record building and upload per step otherwise, before the first kernel can start."""
+    pre = lanes[0].pre is not None
+    # blocks too large for one workspace slot go through as several overlapping parts, each in a batch of its own
+    # (DESIGN.md section 4f); without one -- nearly every call -- nothing takes another path
+    splits = _split_blocks(lanes, lists.shapes, _slot_limit()) if lists.slot_max >= _slot_limit() else {}
+    key = None
+    if not pre and not splits:
+        t_ = dvol.tensor
+        # (block records hold element offsets, not addresses: any volume of this layout can use them; the block lists
+        #  are compared by content -- `lists.key` -- so that a caller who builds them afresh finds the same device
+        #  tables, which is also what lets a small batch's captured graph be found again)
+        key = (lists.key, tuple(t_.stride()), tuple(t_.shape), str(t_.dtype), ns, int(budget_bytes), _MAX_BATCH, RAMP, TAPER)
+        hit = bufs.plans.get(key)
+        if hit is not None:
+            return hit
+    batches = plan_batches(lists.shapes, ns, budget_bytes,
+                           0 if not pre else max(lane.pre.bytes_per_voxel() for lane in lanes))
+    if splits:
+        batches = _isolate_parents(batches, splits)
+    # (raw lanes: the records of every batch but a block in parts are made here, for `_upload_records`)
+    if not pre:
+        _held_origins(dvol, lists.origins, lists.shapes)
+    plan = _bp.make_plan(lists.origins, lists.shapes, batches, splits, None if pre else dvol.tensor.stride()[:3])
+    if key is not None:
+        if len(bufs.plans) >= 8:
+            bufs.plans.clear()
+        bufs.plans[key] = plan
+    return plan
+
+
+def _upload_records(plan: BatchPlan, dev) -> None:
+    """The block tables of every batch that has one go to the device BEFORE the first kernel (a pageable host -> device
+    copy waits for everything queued on the stream before it), in ONE upload: fourteen small copies were 0.4 ms of idle
+    GPU at the start of a step.  A plan that comes from ``bufs.plans`` has them already."""
+    ready = [b for b in plan.batches if b.records is not None and b.d_records is None]
+    if not ready:
+        return
+    table = _to_device_bytes(np.concatenate([b.records.view(np.uint8).reshape(-1) for b in ready]), dev)
+    at = 0
+    for b in ready:
+        b.d_records = table[at:at + b.records.nbytes]
+        at += b.records.nbytes
+
+
+def _size_workspaces(bufs: _Buffers, plan: BatchPlan, ns: int, two: bool) -> None:
+    """Raw lanes: the shared workspace has its final size before anything is queued on it -- workspace 0 for every
+    batch, and with ``two`` workspace 1 for the batches that alternate (a block in parts works in workspace 0 alone)."""
+    if not plan.batches:
+        return
+    need = [_workspace_floats(b.n_blocks, b.slot, ns) for b in plan.batches]
+    _workspace(bufs, max(need), 0, max((b.split for b in plan.batches if b.split is not None), key=len, default=None))
+    if two and not all(b.split is not None for b in plan.batches):
+        bufs.workspace(max(n for n, b in zip(need, plan.batches) if b.split is None), 1)
+    bufs.ws_free = [None, None]
+
+
 def blob_log_lanes(dvol: DeviceVolume, lanes: Sequence[Lane], origins: Sequence[Sequence[int]],
                    shapes: Sequence[Sequence[int]], *, budget_bytes: Optional[int] = None, return_peaks: bool = False,
                    plan_num_sigma: Optional[int] = None):
@@ -763,63 +606,14 @@ def blob_log_lanes(dvol: DeviceVolume, lanes: Sequence[Lane], origins: Sequence[
         raise ValueError("lanes of one pipeline either all preprocess their blocks or none does")
     any_pre = lanes[0].pre is not None
     bufs = _buffers_for(dvol.tensor.device)
-    # The very same tuple objects step after step (stack_detect hands over its cached block lists): their checked copies
-    # and their content key are remembered -- converting and hashing 256 blocks is 0.3 ms before the first launch.
-    # (tuples only: a list could have been edited in place since)
-    immutable = type(origins) is tuple and type(shapes) is tuple
-    seen = bufs.plan_lists.get((id(origins), id(shapes))) if immutable else None
-    if seen is not None and seen[0] is origins and seen[1] is shapes:
-        _, _, lists_key, origins, shapes, slot_max = seen
-    else:
-        given = (origins, shapes)
-        shapes = [tuple(int(v) for v in s) for s in shapes]
-        origins = [tuple(int(v) for v in o) for o in origins]
-        lists_key = (tuple(origins), tuple(shapes))
-        slot_max = int(_slot_elems(np.asarray(shapes, dtype=np.int64).reshape(-1, 3)).max()) if shapes else 0
-        if immutable:
-            if len(bufs.plan_lists) >= 8:
-                bufs.plan_lists.clear()
-            bufs.plan_lists[(id(given[0]), id(given[1]))] = (given[0], given[1], lists_key, origins, shapes, slot_max)   # (kept alive: ids stay theirs)
+    lists = _block_lists(bufs, origins, shapes)
+    origins, shapes = lists.origins, lists.shapes
     for lane in lanes:
         lane.bind(dvol, len(shapes))
-    # blocks too large for one workspace slot go through as several overlapping parts, each in a batch of its own
-    # (DESIGN.md section 4f); without one -- every call so far -- nothing below takes another path
-    splits = _split_blocks(lanes, shapes, _slot_limit()) if slot_max >= _slot_limit() else {}
-    n_sig = [len(lane.space.sigmas) for lane in lanes]
-    ns_max = max(n_sig + [int(plan_num_sigma or 0)])
-    # the batches and their block tables on the device: remembered for the same block lists, volume layout and budget (a
-    # stack detected step after step) -- a millisecond of planning, record building and upload per step otherwise, before
-    # the first kernel can start
-    plan_key = None
-    planned = None
-    if not any_pre and not splits:
-        t_ = dvol.tensor
-        # (block records hold element offsets, not addresses: any volume of this layout can use them; the block lists
-        #  are compared by content -- `lists_key` above -- so that a caller who builds them afresh finds the same device
-        #  tables, which is also what lets a small batch's captured graph be found again)
-        plan_key = (lists_key, tuple(t_.stride()), tuple(t_.shape), str(t_.dtype), ns_max,
-                    int(budget_bytes), _MAX_BATCH, RAMP, TAPER)
-        planned = bufs.plans.get(plan_key)
-    if planned is not None:
-        batches = planned[0]
-    else:
-        batches = plan_batches(shapes, ns_max, budget_bytes,
-                               0 if not any_pre else max(lane.pre.bytes_per_voxel() for lane in lanes))
-        if splits:
-            batches = _isolate_parents(batches, splits)
-    split_of = [splits.get(b[0]) if len(b) == 1 else None for b in batches] if splits else [None] * len(batches)
-
-    def geometry(k):
-        """Blocks and slot size of batch ``k`` as the library will see it."""
-        if split_of[k] is not None:
-            return len(split_of[k]), int(_slot_elems(split_of[k].box_shapes).max())
-        if prepared is not None:
-            return len(prepared[k][0]), prepared[k][1]
-        return len(batches[k]), int(_slot_elems([shapes[i] for i in batches[k]]).max())
-
-    n_b = len(batches)
+    ns_max = max([len(lane.space.sigmas) for lane in lanes] + [int(plan_num_sigma or 0)])
+    plan = _plan_for(dvol, lanes, lists, bufs, ns_max, budget_bytes)
     n_l = len(lanes)
-    items = [(b, l) for b in range(n_b) for l in range(n_l)]       # batch-major
+    items = [(b, l) for b in plan.batches for l in range(n_l)]       # batch-major
     n_items = len(items)
     # How far the GPU queue runs ahead of the host.  Raw volumes: EVERY batch is enqueued before the host looks at
     # the first result, so the GPU runs the batches back to back whatever the host is doing (measured: enqueueing
@@ -833,72 +627,32 @@ def blob_log_lanes(dvol: DeviceVolume, lanes: Sequence[Lane], origins: Sequence[
         # batches
         ahead = max(ahead, min(n_items, PRE_AHEAD_RETAINED * n_l))
     bufs.slots(ahead + 1)
-    prepared = None
-    if planned is not None:
-        prepared = planned[1]
-    elif not any_pre:
-        # block tables of every batch go to the device BEFORE the first kernel: a pageable host -> device copy
-        # waits for everything queued on the stream before it
-        # (a block in parts: its tables are made when it is enqueued, `prepared` holds None in its place)
-        prepared = [None if split_of[k] is not None else
-                    _make_blocks(dvol, lanes[0].channel, [origins[i] for i in b], [shapes[i] for i in b])
-                    for k, b in enumerate(batches)]
-        ready = [k for k, p_ in enumerate(prepared) if p_ is not None]
-        if ready:           # (one upload for all of them: fourteen small copies were 0.4 ms of idle GPU at the start of a step)
-            sizes = [prepared[k][0].nbytes for k in ready]
-            allrec = _to_device_bytes(np.concatenate([prepared[k][0].view(np.uint8).reshape(-1) for k in ready]),
-                                      dvol.tensor.device)
-            offs = np.concatenate([[0], np.cumsum(sizes)])
-            for j, k in enumerate(ready):
-                prepared[k] = (prepared[k][0], prepared[k][1], allrec[int(offs[j]):int(offs[j + 1])])
-        if plan_key is not None:
-            if len(bufs.plans) >= 8:
-                bufs.plans.clear()
-            bufs.plans[plan_key] = (batches, prepared)
-    if any_pre and PRE_SIDE_TAIL and RESCORE_STREAM and all(lane.exact for lane in lanes) and n_items > 1:
-        # preprocessed batches alternate between two workspaces as well (the tail of a batch on the second stream beside
-        # the next batch's passes): both at their final size before anything is queued on them
-        need = 0
-        for k in range(n_b):
-            need = max(need, -(-int(nat.lib().mmx_workspace_bytes(*geometry(k), ns_max, 1)) // 4))
-        widest = max(splits.values(), key=len) if splits else None
-        _workspace(bufs, need, 0, widest)
-        _workspace(bufs, need, 1, widest)
-        bufs.ws_free = [None, None]
-    if not any_pre:        # ... and the shared workspace has its final size before anything is queued on it
-        if prepared:
-            need = max(-(-int(nat.lib().mmx_workspace_bytes(*geometry(k), ns_max, 1)) // 4) for k in range(n_b))
-            _workspace(bufs, need, 0, max(splits.values(), key=len) if splits else None)
-            if RESCORE_STREAM and n_items > 1:
-                # (a block in parts works in workspace 0 alone: the second one is as large as the other batches need)
-                need1 = max([-(-int(nat.lib().mmx_workspace_bytes(*geometry(k), ns_max, 1)) // 4)
-                             for k in range(n_b) if split_of[k] is None] or [0])
-                if need1:
-                    bufs.workspace(need1, 1)
-            bufs.ws_free = [None, None]
+    if not any_pre:
+        _upload_records(plan, dvol.tensor.device)
+        _size_workspaces(bufs, plan, ns_max, bool(RESCORE_STREAM and n_items > 1))
     jobs: List[Optional[_Batch]] = [None] * n_items
     done_events: List = []
     enq = 0
     uploading = dvol._upload is not None
-    for k, (b_k, l_k) in enumerate(items):
+    for k, (_, l_k) in enumerate(items):
         while enq < min(n_items, k + 1 + ahead):       # item k itself and `ahead` items behind it
-            b_e, l_e = items[enq]
-            batch, ln = batches[b_e], lanes[l_e]
+            planned, ln = items[enq][0], lanes[items[enq][1]]
+            batch = planned.indices
             if uploading and enq > k and not dvol.upload_ready(
                     [(origins[i][0], origins[i][0] + shapes[i][0], origins[i][1], origins[i][1] + shapes[i][1]) for i in batch]):
                 # a volume still on its way up: this batch's voxels have not been queued for copying yet.  Enqueueing it
                 # would block the host until they are -- with finished batches waiting for their host work (all of it
                 # then piled up behind the upload's last region: 30 ms at the end of a from-host step).  Item k first.
                 break
+            # (preprocessing: when the buffer set's previous holder is done; the first holders behind the main stream)
+            pipe = _Pipelined(planned, enq & 1, None if enq < ahead + 1 else done_events[enq - (ahead + 1)])
             jobs[enq] = _enqueue_detect(dvol, ln, [origins[i] for i in batch], [shapes[i] for i in batch], bufs,
-                                        enq % (ahead + 1), prepared=None if prepared is None else prepared[b_e],
-                                        buffer_free=(None if enq < ahead + 1 else done_events[enq - (ahead + 1)])
-                                        if ln.pre is not None else False, parity=enq, split=split_of[b_e])
+                                        enq % (ahead + 1), pipe=pipe, split=planned.split)
             done_events.append(jobs[enq].done)
             jobs[enq].indices = batch
             if enq == 0:
                 global FIRST_ENQUEUED_T, LAST_BATCH_SIZES
-                FIRST_ENQUEUED_T, LAST_BATCH_SIZES = time.perf_counter(), [len(b_) for b_ in batches]
+                FIRST_ENQUEUED_T, LAST_BATCH_SIZES = time.perf_counter(), [len(b_.indices) for b_ in plan.batches]
             enq += 1
         pending, jobs[k] = jobs[k], None
         ln = lanes[l_k]
@@ -967,90 +721,145 @@ class _Batch:
         return self.d_blocks if self.split is None else self.d_parents
 
 
+@dataclass
+class _Pipelined:
+    """What the pipeline of :func:`blob_log_lanes` tells :func:`_enqueue_detect` about a batch it enqueues ahead."""
+    planned: PlannedBatch
+    workspace: int              # which of the two workspaces a raw batch with a side tail works in
+    pre_after: object = None    # preprocessing lanes: the event its buffer set is free at; None: behind the main stream
+
+
+@dataclass
+class _Voxels:
+    """The voxels of a batch as the library reads them (:func:`_batch_voxels`)."""
+    blocks: np.ndarray
+    slot: int
+    d_blocks: object            # the uploaded ``blocks``, or None: not uploaded yet
+    parents: Optional[np.ndarray]       # a block in parts: its own record (``blocks`` are its parts)
+    vol32: object               # the ``mmx_volume`` records the passes / the exact re-score read
+    vol_exact: object
+    store_f32: int
+
+
+def _preprocess(dvol, lane: "Lane", origins, shapes, bufs: _Buffers, which: int, boxes, pipe: Optional[_Pipelined]):
+    """Enqueue P1-P3 of a batch -> ``(blocks, slot, vol32, vol_exact)``.  Pipelined with ``PRE_STREAM``: on a stream of
+    its own, where it may start as soon as the batch that last used this buffer set is done (``pipe.pre_after``: that
+    batch's completion event), i.e. while the batch before this one is still filtering.  (None: a buffer set no batch of
+    this call has used yet -- behind whatever is queued on the main stream.  Letting the first batches' preprocessing
+    start at once instead measured nothing on C3 --denoise 25 and +10 ms on C5, round 5.)"""
+    if not (PRE_STREAM and pipe is not None):
+        dvol.stream_wait(None, [torch.cuda.current_stream(), bufs.side], boxes)
+        return lane.pre.run(dvol, lane.channel, origins, shapes, which)
+    main = torch.cuda.current_stream()
+    bufs.pre_stream.wait_stream(main) if pipe.pre_after is None else _stream_wait(bufs.pre_stream, pipe.pre_after)
+    with torch.cuda.stream(bufs.pre_stream):
+        dvol.stream_wait(None, [torch.cuda.current_stream(), bufs.side], boxes)     # (side: co-localisation means)
+        out = lane.pre.run(dvol, lane.channel, origins, shapes, which)
+        ready = torch.cuda.Event()
+        ready.record()
+    timed = bool(nat.lib().mmx_timing_is_enabled())
+    if timed:       # how long the LoG stream waits for this batch's preprocessing (bench.py: pre_stream_wait_ms)
+        before = torch.cuda.Event(enable_timing=True)
+        before.record()
+    main.wait_event(ready)
+    if timed:
+        after = torch.cuda.Event(enable_timing=True)
+        after.record()
+        PRE_WAITS.append((before, after))
+    return out
+
+
+def _batch_voxels(dvol, lane: "Lane", origins, shapes, bufs: _Buffers, which: int, split: Optional[PartSplit],
+                  pipe: Optional[_Pipelined]) -> _Voxels:
+    """The voxels of the batch, raw or preprocessed (enqueued here), as the parts of ``split`` where there is one."""
+    channel, pre = lane.channel, lane.pre
+    # a volume still on its way up (`DeviceVolume.stream_wait`): this batch waits for the slabs its blocks touch, on
+    # every stream that reads voxels (the passes, the voxel copy of the tiled path, the exact re-score)
+    boxes = ([(int(o[0]), int(o[0]) + int(s_[0]), int(o[1]), int(o[1]) + int(s_[1])) for o, s_ in zip(origins, shapes)]
+             if dvol._upload is not None else None)
+    d_blocks = None
+    if pre is None:
+        if dvol._upload is not None:
+            dvol.stream_wait(None, [torch.cuda.current_stream(), bufs.pack_stream, bufs.rescore_stream, bufs.side], boxes)
+        if pipe is not None and pipe.planned.records is not None:
+            blocks, slot, d_blocks = pipe.planned.records, pipe.planned.slot, pipe.planned.d_records
+        else:
+            blocks, slot = _make_blocks(dvol, channel, origins, shapes)
+        vol32, vol_exact = dvol.view(channel, True), dvol.view(channel, False)
+        store_f32 = 1 if dvol.np_dtype == np.float32 else 0
+        strides = dvol.tensor.stride()[:3]
+    else:
+        blocks, slot, vol32, vol_exact = _preprocess(dvol, lane, origins, shapes, bufs, which, boxes, pipe)
+        store_f32 = int(getattr(pre, "store_f32", 0))
+        # (a block in parts was preprocessed whole, tile by tile as ever: its parts are boxes of that slot -- same
+        #  strides -- and the exact re-score reads the slot with the parent's extent)
+        strides = (vol32.stride_z, vol32.stride_y, vol32.stride_x)
+    parents = None
+    if split is not None:
+        parents = blocks
+        blocks, slot = split.block_records(parents["src_off"][0], strides)
+    return _Voxels(blocks, slot, d_blocks, parents, vol32, vol_exact, store_f32)
+
+
+def _detect_args(lane: "Lane", vox: _Voxels, bufs: _Buffers, which: int, ws, ws_i: int, cap: int, eps: float, exact: bool,
+                 native: bool, side_tail: bool) -> "nat.DetectArgs":
+    """The ``mmx_detect_args`` of a batch whose voxels, workspace and table slot are settled."""
+    space, stream = lane.space, _stream_ptr()
+    ev_read, ev_done = bufs.events(which)
+    a = nat.DetectArgs()
+    a.vol32, a.vol_exact = ctypes.pointer(vox.vol32), ctypes.pointer(vox.vol_exact)
+    a.d_blocks, a.h_blocks = vox.d_blocks.data_ptr(), vox.blocks.ctypes.data
+    a.n_blocks, a.n_sigma, a.slot_elems = len(vox.blocks), len(space.sigmas), vox.slot
+    a.h_w0, a.h_w2 = space.w0_tab.ctypes.data, space.w2_tab.ctypes.data
+    a.d_w0, a.d_w2 = lane.d_w0.data_ptr(), lane.d_w2.data_ptr()
+    a.h_radius, a.h_norm = space.radii.ctypes.data, space.norms.ctypes.data
+    a.d_work, a.work_bytes = ws.data_ptr(), ws.numel() * 4
+    a.thr, a.eps = lane.threshold, eps
+    a.d_cands, a.cap, a.d_count = bufs.cand_table(which, cap).data_ptr(), cap, bufs.counts[which].data_ptr()
+    a.h_count = bufs.host_counts[which].data_ptr()
+    if native:
+        a.h_cands, a.h_prefix = bufs.host_table(which).data_ptr(), min(cap, _PREFIX_ENTRIES)
+    a.zx_mode, a.zx_flags, a.store_f32, a.exact, a.expand = ZX_MODE, ZX_FLAGS, vox.store_f32, int(exact), int(native)
+    a.stream = a.pack_stream = stream
+    a.tail_stream = bufs.rescore_stream.cuda_stream if side_tail else stream      # (the library forks and joins it)
+    # (the last reader of this workspace; also a batch that is nominated again, on the main stream: same workspace)
+    a.ev_work_free = bufs.ws_free[ws_i].handle if bufs.ws_free[ws_i] is not None else None
+    a.ev_work_read = ev_read.handle if side_tail else None
+    a.ev_done = ev_done.handle
+    return a
+
+
 def _enqueue_detect(dvol, lane: "Lane", origins, shapes, bufs: _Buffers, which: int, *, cap: Optional[int] = None,
-                    eps: Optional[float] = None, exact: Optional[bool] = None, prepared=None, buffer_free=False,
-                    parity: Optional[int] = None, split: Optional[PartSplit] = None) -> _Batch:
+                    eps: Optional[float] = None, exact: Optional[bool] = None, split: Optional[PartSplit] = None,
+                    pipe: Optional[_Pipelined] = None) -> _Batch:
     """Enqueue (P1-P3,) A0-A4 of one batch of ``lane`` on the current stream: the preprocessing, then ONE
     ``mmx_detect_batch`` call (or the replay of its captured graph); nothing here waits for the GPU.
     ``eps`` / ``exact`` (default: the lane's): the nomination band, and whether every candidate is also re-scored in
     float64 (otherwise ``_resolve_peaks`` re-scores the few whose decision depends on it).
     ``split``: ``origins`` / ``shapes`` hold ONE block, which goes through the passes and the NMS as the parts of this
-    split; the library folds their candidates back into it (``mmx_fold_parts``) and everything behind sees that block."""
-    channel, space, pre, thr, vrange = lane.channel, lane.space, lane.pre, lane.threshold, lane.vrange
+    split; the library folds their candidates back into it (``mmx_fold_parts``) and everything behind sees that block.
+    ``pipe``: the batch's place in the pipeline of :func:`blob_log_lanes`.  Without it the block records are made here,
+    the batch works in workspace 0 with no side tail, and its preprocessing runs on the main stream."""
+    space, pre, vrange = lane.space, lane.pre, lane.vrange
     eps = lane.eps if eps is None else eps
     exact = lane.exact if exact is None else exact
     L = nat.lib()
     dev = dvol.tensor.device
-    d_blocks = None
-    parents = None
     if split is not None and (len(shapes) != 1 or tuple(int(v) for v in shapes[0]) != split.shape):
         raise ValueError("a split belongs to the one block of its batch")
-    # a volume still on its way up (`DeviceVolume.stream_wait`): this batch waits for the slabs its blocks touch, on
-    # every stream that reads voxels (the passes, the voxel copy of the tiled path, the exact re-score)
-    boxes = ([(int(o[0]), int(o[0]) + int(s_[0]), int(o[1]), int(o[1]) + int(s_[1])) for o, s_ in zip(origins, shapes)]
-             if dvol._upload is not None else None)
-    if pre is None:
-        if dvol._upload is not None:
-            dvol.stream_wait(None, [torch.cuda.current_stream(), bufs.pack_stream, bufs.rescore_stream, bufs.side], boxes)
-        if prepared is not None:
-            blocks, slot, d_blocks = prepared
-        else:
-            blocks, slot = _make_blocks(dvol, channel, origins, shapes)
-        if split is not None:
-            parents = blocks
-            blocks, slot = _part_blocks(parents[0], split, dvol.tensor.stride()[:3])
-        vol32 = dvol.view(channel, True)
-        vol_exact = dvol.view(channel, False)
-        store_f32 = 1 if dvol.np_dtype == np.float32 else 0
-    else:
-        if PRE_STREAM and buffer_free is not False:
-            # on its own stream: it may start as soon as the batch that last used this buffer set is done
-            # (`buffer_free`: that batch's completion event), i.e. while the batch before this one is still filtering.
-            # (None: a buffer set no batch of this call has used yet -- behind whatever is queued on the main stream.
-            #  Letting the first batches' preprocessing start at once instead measured nothing on C3 --denoise 25
-            #  and +10 ms on C5, round 5.)
-            main = torch.cuda.current_stream()
-            bufs.pre_stream.wait_stream(main) if buffer_free is None else _stream_wait(bufs.pre_stream, buffer_free)
-            with torch.cuda.stream(bufs.pre_stream):
-                dvol.stream_wait(None, [torch.cuda.current_stream(), bufs.side], boxes)     # (side: co-localisation means)
-                blocks, slot, vol32, vol_exact = pre.run(dvol, channel, origins, shapes, which)
-                ready = torch.cuda.Event()
-                ready.record()
-            timed = bool(L.mmx_timing_is_enabled())
-            if timed:       # how long the LoG stream waits for this batch's preprocessing (bench.py: pre_stream_wait_ms)
-                before = torch.cuda.Event(enable_timing=True)
-                before.record()
-            main.wait_event(ready)
-            if timed:
-                after = torch.cuda.Event(enable_timing=True)
-                after.record()
-                PRE_WAITS.append((before, after))
-        else:
-            dvol.stream_wait(None, [torch.cuda.current_stream(), bufs.side], boxes)
-            blocks, slot, vol32, vol_exact = pre.run(dvol, channel, origins, shapes, which)
-        store_f32 = int(getattr(pre, "store_f32", 0))
-        if split is not None:
-            # the parent was preprocessed whole, tile by tile as ever: its parts are boxes of that slot (same strides), and
-            # the exact re-score reads the slot with the parent's extent
-            parents = blocks
-            blocks, slot = _part_blocks(parents[0], split, (vol32.stride_z, vol32.stride_y, vol32.stride_x))
+    vox = _batch_voxels(dvol, lane, origins, shapes, bufs, which, split, pipe)
+    blocks, vol32 = vox.blocks, vox.vol32
     nb, ns = len(blocks), len(space.sigmas)
-    if slot >= _slot_limit():
-        raise nat.MmxError("block too large for one workspace slot (>= 2^29 voxels)" if _slot_limit() == LIB_MAX_SLOT_ELEMS
-                           else f"block too large for one workspace slot (>= {_slot_limit()} elements)")
-    # raw volumes: the batches alternate between two workspaces, and everything after a batch's last LoG kernel -- NMS,
-    # probe expansion, exact re-score, copies -- runs on a second stream beside the next batch's LoG kernels
-    # (preprocessed batches too with PRE_SIDE_TAIL -- measured and left off; their two workspaces are sized by
-    #  blob_log_blocks before anything is queued)
-    side_tail = bool(RESCORE_STREAM and exact and ((pre is None and prepared is not None) or
-                                                   (pre is not None and PRE_SIDE_TAIL and bufs.ws2 is not None)))
-    ws_i = ((which if parity is None else parity) & 1) if (side_tail and bufs.ws2 is not None) else 0
-    ws = _workspace(bufs, -(-int(L.mmx_workspace_bytes(nb, slot, ns, 1)) // 4), ws_i, split)
-    # ... and the voxel copy of the tiled path, the first kernel of a batch, on a third: it only needs the workspace
-    pack_side = side_tail and PACK_STREAM and bufs.ws2 is not None
-    if d_blocks is None:
-        d_blocks = _to_device_bytes(blocks, dev)
-    stream = _stream_ptr()
+    if vox.slot >= _slot_limit():
+        raise nat.MmxError(slot_refusal(_slot_limit()))
+    # raw volumes: the pipeline's batches alternate between two workspaces, and everything after a batch's last LoG
+    # kernel -- NMS, probe expansion, exact re-score, copies -- runs on a second stream beside the next batch's LoG
+    # kernels (never a block in parts, whose records the pipeline does not hold)
+    side_tail = bool(RESCORE_STREAM and exact and pre is None and pipe is not None and pipe.planned.records is not None)
+    ws_i = pipe.workspace if (side_tail and bufs.ws2 is not None) else 0
+    ws = _workspace(bufs, _workspace_floats(nb, vox.slot, ns), ws_i, split)
+    if vox.d_blocks is None:
+        vox.d_blocks = _to_device_bytes(blocks, dev)
     if vol32.dtype == nat.MMX_F32:
         # float voxels (float images, preprocessed blocks): the tiled path holds each as two float16 pieces, which
         # suits values of ordinary magnitude -- the range is known here, not in the library (mmx_volume.value_range)
@@ -1061,45 +870,23 @@ def _enqueue_detect(dvol, lane: "Lane", origins, shapes, bufs: _Buffers, which: 
     n_part_vox = n_vox if split is None else int(split.box_shapes.prod(axis=1).sum())       # (what the NMS nominates from)
     if cap is None:
         cap = max(4096, min(n_part_vox * ns, n_part_vox // 2000 * ns + 65536))
-    table = bufs.cand_table(which, cap)
-    count = bufs.counts[which]
-    ev_read, ev_done = bufs.events(which)
     native = bool(exact and HOST_PATH == "native")
-    a = nat.DetectArgs()
-    a.vol32, a.vol_exact = ctypes.pointer(vol32), ctypes.pointer(vol_exact)
-    a.d_blocks, a.h_blocks = d_blocks.data_ptr(), blocks.ctypes.data
-    a.n_blocks, a.n_sigma, a.slot_elems = nb, ns, slot
-    a.h_w0, a.h_w2 = space.w0_tab.ctypes.data, space.w2_tab.ctypes.data
-    a.d_w0, a.d_w2 = lane.d_w0.data_ptr(), lane.d_w2.data_ptr()
-    a.h_radius, a.h_norm = space.radii.ctypes.data, space.norms.ctypes.data
-    a.d_work, a.work_bytes = ws.data_ptr(), ws.numel() * 4
-    a.thr, a.eps = thr, eps
-    a.d_cands, a.cap, a.d_count = table.data_ptr(), cap, count.data_ptr()
-    a.h_count = bufs.host_counts[which].data_ptr()
-    if native:
-        a.h_cands, a.h_prefix = bufs.host_table(which).data_ptr(), min(cap, _PREFIX_ENTRIES)
-    a.zx_mode, a.zx_flags, a.store_f32, a.exact, a.expand = ZX_MODE, ZX_FLAGS, store_f32, int(exact), int(native)
-    a.stream = stream
-    a.tail_stream = bufs.rescore_stream.cuda_stream if side_tail else stream      # (the library forks and joins it)
-    a.pack_stream = bufs.pack_stream.cuda_stream if pack_side else stream
-    # (the last reader of this workspace; also a batch that is nominated again, on the main stream: same workspace)
-    a.ev_work_free = bufs.ws_free[ws_i].handle if bufs.ws_free[ws_i] is not None else None
-    a.ev_work_read = ev_read.handle if side_tail else None
-    a.ev_done = ev_done.handle
+    a = _detect_args(lane, vox, bufs, which, ws, ws_i, cap, eps, exact, native, side_tail)
+    ev_read, ev_done = bufs.events(which)
     d_parents = d_parts = None
     if split is not None:
         lo, hi = split.boxes[:, 0], split.boxes[:, 1]
         if (lo < 0).any() or (hi > np.asarray(split.shape)).any() or (split.cores[:, 0] < lo).any() or \
                 (split.cores[:, 1] > hi).any():
             raise ValueError("a part outside its block")           # (the re-score reads the parent at folded coordinates)
-        d_parents = _to_device_bytes(parents, dev)
+        d_parents = _to_device_bytes(vox.parents, dev)
         d_parts = _to_device_bytes(split.records(0), dev)
         a.d_parts, a.n_parts = d_parts.data_ptr(), len(split)
-        a.d_parents, a.h_parents, a.n_parents = d_parents.data_ptr(), parents.ctypes.data, 1
+        a.d_parents, a.h_parents, a.n_parents = d_parents.data_ptr(), vox.parents.ctypes.data, 1
     info = nat.DetectInfo()
     # a small raw batch that comes by again and again: captured once, then replayed (never a block in parts)
     if NATIVE_BATCH and pre is None and native and split is None:
-        rc = _launch_batch(L, a, info, bufs, nb, blocks, space, vol32, vol_exact, ev_read if side_tail else None)
+        rc = _launch_batch(L, a, info, bufs, nb, blocks, space, vol32, vox.vol_exact, ev_read if side_tail else None)
     else:
         rc = L.mmx_detect_batch(ctypes.byref(a), ctypes.byref(info))
     if rc != 0:
@@ -1112,9 +899,10 @@ def _enqueue_detect(dvol, lane: "Lane", origins, shapes, bufs: _Buffers, which: 
         LAST_Q16_BOUND, LAST_NMS_BAND = info.q16_bound, eps
     if side_tail:
         bufs.ws_free[ws_i] = ev_read
-    return _Batch(lane=lane, origins=origins, shapes=shapes, blocks=blocks, d_blocks=d_blocks, nb=nb, ns=ns, n_vox=n_vox,
-                  cap=cap, which=which, done=ev_done, store_f32=store_f32, vol_exact=vol_exact, eps=eps, exact=exact,
-                  native=native, split=split, parents=parents, d_parents=d_parents, d_parts=d_parts, n_part_vox=n_part_vox)
+    return _Batch(lane=lane, origins=origins, shapes=shapes, blocks=blocks, d_blocks=vox.d_blocks, nb=nb, ns=ns, n_vox=n_vox,
+                  cap=cap, which=which, done=ev_done, store_f32=vox.store_f32, vol_exact=vox.vol_exact, eps=eps, exact=exact,
+                  native=native, split=split, parents=vox.parents, d_parents=d_parents, d_parts=d_parts,
+                  n_part_vox=n_part_vox)
 
 
 def _launch_batch(L, a, info, bufs: _Buffers, nb: int, blocks, space, vol32, vol_exact, ev_read) -> int:
@@ -1183,11 +971,9 @@ _FINISHED = object()        # what `_finish_detect` returns when a finisher has 
 
 def _redo(batch: _Batch, dvol, bufs: _Buffers, *, cap: Optional[int], eps: float, exact: bool):
     """Nominate ``batch`` again -- its candidate table overflowed, or its band proved too narrow -- and finish it.  The
-    pipeline has reused the workspace, so the passes run again.  The main stream is synchronised first; the batch then
-    goes up without its prepared block table (``prepared=None``: no side tail, workspace 0, everything in stream order
-    on the main stream) and with ``buffer_free=False`` (preprocessing on the main stream too).  It keeps its slot
-    ``which``, its ``indices`` and its count of ``retries``, and is never offered to a ``finisher``.  A block in parts
-    is nominated again whole: all its parts, the same split."""
+    pipeline has reused the workspace, so the passes run again: the main stream is synchronised first, and the batch goes
+    up outside the pipeline (no ``pipe``).  It keeps its slot ``which``, its ``indices`` and its count of ``retries``,
+    and is never offered to a ``finisher``.  A block in parts is nominated again whole: all its parts, the same split."""
     torch.cuda.current_stream().synchronize()
     again = _enqueue_detect(dvol, batch.lane, batch.origins, batch.shapes, bufs, batch.which, cap=cap, eps=eps, exact=exact,
                             split=batch.split)

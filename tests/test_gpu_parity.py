@@ -432,6 +432,67 @@ def test_many_blocks_several_batches_identical_to_oracle(gpu, tmp_path, monkeypa
     np.testing.assert_array_equal(lexsorted(blobs.blobs), lexsorted(want))
 
 
+def test_batch_plan_found_again_and_tables_whatever_the_batches(gpu, monkeypatch):
+    """48 overlapping blocks of a stack's grid, 3 scales, in seven batches (the two workspaces alternate, the candidate
+    table slots wrap): the plan and its uploaded block tables are found again for the same tuples and for equal lists
+    built afresh, and the tables are the same in one batch (= the oracle's) and with blocks detected in parts -- the 24
+    blocks that share the largest slot; the grid has no single largest block -- for which nothing is remembered."""
+    from magellanmapper_amd import blob_log as bl
+    from magellanmapper_amd import config, stack_detect, synth
+    from oracle import blob_log_oracle as blo
+    shape = (120, 160, 160)
+    vol = synth.make_volume(61, shape, 330)
+    assert vol.dtype == np.uint16
+    config.setup_roi_profiles(None)
+    config.roi_profile.update(denoise_size=None, num_sigma=3, segment_size=40)
+    config.resolutions = np.array([[1.0, 1.0, 1.0]])
+    grid = stack_detect.setup_blocks(config.roi_profile, shape).sub_roi_slices
+    ext = [[s.indices(n)[:2] for s, n in zip(b, shape)] for b in grid.reshape(-1)]
+    origins = tuple(tuple(int(lo) for lo, _ in b) for b in ext)
+    shapes = tuple(tuple(int(hi - lo) for lo, hi in b) for b in ext)
+    assert len(shapes) == 48 and min(min(s) for s in shapes) == 40 and max(max(s) for s in shapes) > 40
+    dvol = bl.DeviceVolume(vol)
+    bufs = bl._buffers_for(gpu)
+    seen = []
+    real = bl._enqueue_detect
+    monkeypatch.setattr(bl, "_enqueue_detect", lambda *a, **k: seen.append((k["pipe"].planned, k.get("split"))) or real(*a, **k))
+
+    def run(o, s, budget=32 << 20):
+        del seen[:]
+        out = bl.blob_log_blocks(dvol, 0, o, s, 3, 5, 3, 0.1, 0.5, budget_bytes=budget)
+        assert sorted(i for p, _ in seen for i in p.indices) == list(range(48))
+        return out, [None if p.d_records is None else p.d_records.data_ptr() for p, _ in seen]
+
+    def same(got, want):
+        assert len(got) == len(want) == 48
+        for g, w in zip(got, want):
+            np.testing.assert_array_equal(g, w)
+
+    first, ptrs = run(origins, shapes)                           # (a) the same tuple objects, twice
+    assert len(bl.LAST_BATCH_SIZES) >= 4 and len(ptrs) == len(bl.LAST_BATCH_SIZES) and None not in ptrs
+    n_plans = len(bufs.plans)
+    again, ptrs_again = run(origins, shapes)
+    assert len(bufs.plans) == n_plans and ptrs_again == ptrs
+    same(again, first)
+    fresh, ptrs_fresh = run([list(o) for o in origins], [list(s) for s in shapes])       # (b) equal lists built afresh
+    assert len(bufs.plans) == n_plans and ptrs_fresh == ptrs
+    same(fresh, first)
+    one, _ = run(origins, shapes, 1 << 30)                       # (c) one batch
+    assert bl.LAST_BATCH_SIZES == [48]
+    same(one, first)
+    want = [blo.blob_log(vol[tuple(slice(a, a + n) for a, n in zip(o, s))], 3, 5, 3, 0.1, 0.5) for o, s in zip(origins, shapes)]
+    assert sum(len(w) for w in want) > 200
+    same(one, want)
+    n_plans = len(bufs.plans)
+    monkeypatch.setattr(bl, "MAX_SLOT_ELEMS", int(bl._slot_elems(np.asarray(shapes)).max()), raising=True)
+    parts, _ = run(origins, shapes)                     # (d) blocks in parts: nothing is remembered
+    n_split = sum(sp is not None for _, sp in seen)
+    assert n_split == 24 and all((sp is None) == (p.split is None) for p, sp in seen)
+    assert all(p.d_records is None for p, sp in seen if sp is not None)
+    assert len(bufs.plans) == n_plans
+    same(parts, first)
+
+
 def test_candidate_table_overflow_is_retried(gpu, monkeypatch, host_path):
     """A candidate table that is too small must be detected and the batch redone."""
     from magellanmapper_amd import blob_log as bl
