@@ -168,11 +168,18 @@ typedef enum {
                              handed to the Y pass (y6_kernel) as 16 x 16 tiles: every access one contiguous KiB */
     MMX_ZX_TILED_Q16 = 7, /* the same with the tiles as 16-bit fixed point (half the intermediate bytes): the LoG
                              values carry a rounding error of at most mmx_tiled_q16_error_bound()               */
-    MMX_ZX_WIDE = 8       /* the wide passes (wide_z / wide_x / wide_y): radius 1 .. MMX_MAX_RADIUS_WIDE, u8 / u16 / f32
+    MMX_ZX_WIDE = 8,      /* the wide passes (wide_z / wide_x / wide_y): radius 1 .. MMX_MAX_RADIUS_WIDE, u8 / u16 / f32
                              voxels, every extent of every block >= radius, any row width; float32 throughout, entries
                              in MMX_MASK_ROWS.  AUTO takes them for radii above MMX_MAX_RADIUS_FAST; by name they take
                              any radius from 1 (cross-checks).  A geometry they do not accept falls through to the
                              other paths as under AUTO */
+    MMX_ZX_THIN = 9       /* by name only (AUTO never takes it): a batch with a block shorter than radius +
+                             MMX_COL_PREFETCH along some axis -- the largest radius of a ladder -- runs the three separate
+                             passes, each on its register-ring kernel where that accepts and on the folded-reflection
+                             pass (mmx_thin.hip) where not: per block of extent n <= MMX_FOLD_MAX_N the 2 R + 1 reflected
+                             taps are folded onto the n voxels of the axis (the n x n matrix of mmx_fold_matrix), a
+                             longer extent runs the generic tap loop.  No entries.  A batch with no such block takes
+                             the path it would take under AUTO */
 } mmx_zx_mode;
 #define MMX_ZX_PREPACKED 0x100   /* or-ed into MMX_ZX_TILED / MMX_ZX_TILED_Q16: mmx_zx_pack ran on this d_work for these blocks */
 #define MMX_ZX_Y_VALU    0x200   /* or-ed into MMX_ZX_TILED_Q16 (any zx_mode >= 0 accepts it): the Y pass of the 16-bit tiles on the
@@ -196,6 +203,17 @@ int mmx_log_batch_f32(const mmx_volume* vol, const mmx_block* d_blocks, const mm
  * function of the weights alone (5.1e-5 for any sigma >= 1).  A true maximum is nominated as long as the NMS band is four
  * times this (mmx_rescore_f64 then decides on exact values as always).  < 0 on bad arguments. */
 double mmx_tiled_q16_error_bound(const double* h_w0, const double* h_w2, int radius, double norm);
+
+/* The folded operator of MMX_ZX_THIN on the host (tests, tools): SciPy's "reflect" folds the 2 radius + 1 taps of the
+ * symmetric kernel w[0 .. radius] onto the n voxels of an axis,
+ *   out[i * n + j] = sum of w[|p - i|] over the images p of j, p in {2 n m + j, 2 n m - 1 - j : m integer}, |p - i| <= radius,
+ * summed in double in ascending p and rounded once to float: the very function the kernels call (csrc/mmx_fold.h).
+ * Any n >= 1 (the kernels fold up to MMX_FOLD_MAX_N), radius 0 .. MMX_MAX_RADIUS_GENERIC; MMX_ERR_ARG otherwise. */
+#define MMX_COL_PREFETCH 4      /* the register-ring column kernels prefetch this many steps ahead and reflect once */
+#define MMX_FOLD_MAX_N 68       /* 64 + MMX_COL_PREFETCH: two n x n float matrices are 37 KB of LDS */
+int mmx_fold_matrix(const float* w, int radius, int n, float* out /* n * n */);
+/* MMX_COL_PREFETCH for callers that do not read this header: an extent below radius + this is thin */
+int mmx_col_prefetch(void);
 
 /* The sigma-independent part of MMX_ZX_TILED: the operand-ordered copy of the blocks' voxels, written into the
  * part of d_work (same pointer, blocks and slot_elems as the mmx_log_batch_f32 calls that follow) that the tiled
@@ -617,9 +635,13 @@ int mmx_order_stats(const mmx_volume* vol, int64_t nz, int64_t ny, int64_t nx,
  * MMX_K_*: 0 z pass, 1 y pass, 2 x pass, 3 generic passes, 4 peaks, 5 rescore,
  * 6 overlap pairs, 7 close pairs, 8 fused z+x pass, 9 y pass of the fused path, 10 preprocessing,
  * 11 co-localisation means, 12 operand-ordered voxel copy of the tiled path, 13 the wide passes) and starts a new window.
+ * Behind the MMX_K_COUNT families of ABI 21 comes MMX_K_THIN (14, the folded passes of MMX_ZX_THIN): a caller that
+ * passes n >= MMX_K_SLOTS gets it too, one that passes MMX_K_COUNT gets the families it knows.
  * mmx_timing_enable(m), m > 1: only the families whose bit (k + 1) is set in m record events (an event between two
  * kernels keeps the second from starting under the first one's tail: timing one family perturbs a step less). */
 #define MMX_K_COUNT 14
+#define MMX_K_THIN 14
+#define MMX_K_SLOTS 15
 int mmx_timing_enable(int on);
 int mmx_timing_read(double* ms, int64_t* launches, int n);
 

@@ -29,6 +29,10 @@ MMX_CAND_PROBE = 4
 MMX_ZX_AUTO, MMX_ZX_SEPARATE, MMX_ZX_PACKED, MMX_ZX_MFMA_F32, MMX_ZX_MFMA_F16, MMX_ZX_MFMA_F16_LDS = -1, 0, 2, 3, 4, 5
 MMX_ZX_TILED, MMX_ZX_TILED_Q16, MMX_ZX_PREPACKED, MMX_ZX_Y_VALU = 6, 7, 0x100, 0x200
 MMX_ZX_WIDE = 8
+#: by name only: the separate passes with the folded-reflection pass where a block is shorter than the kernel
+MMX_ZX_THIN = 9
+#: longest extent the folded passes fold (``MMX_FOLD_MAX_N``); a longer axis runs the generic tap loop
+MMX_FOLD_MAX_N = 68
 #: NMS entry layouts ``mmx_log_batch_f32`` reports and ``mmx_peaks_batch`` takes
 MMX_MASK_ROWS, MMX_MASK_QUADS = 1, 2
 MMX_MAX_BLOCKS = 65535
@@ -140,7 +144,7 @@ SYMBOLS = (
     "mmx_abi_version", "mmx_strerror", "mmx_last_hip_error", "mmx_device_count",
     "mmx_detect_batch", "mmx_log_scales_f32", "mmx_detect_batch_capture", "mmx_graph_launch", "mmx_graph_destroy", "mmx_detect_last_error",
     "mmx_event_synchronize", "mmx_stream_wait_event", "mmx_timing_is_enabled",
-    "mmx_log_batch_f32", "mmx_log_batch_f32_generic", "mmx_zx_pack", "mmx_tiled_q16_error_bound", "mmx_workspace_bytes", "mmx_peaks_batch", "mmx_rescore_f64",
+    "mmx_log_batch_f32", "mmx_log_batch_f32_generic", "mmx_zx_pack", "mmx_fold_matrix", "mmx_col_prefetch", "mmx_tiled_q16_error_bound", "mmx_workspace_bytes", "mmx_peaks_batch", "mmx_rescore_f64",
     "mmx_overlap_pairs", "mmx_close_pairs", "mmx_event_create", "mmx_event_destroy",
     "mmx_event_record", "mmx_event_elapsed_ms", "mmx_timing_enable", "mmx_timing_read",
     "mmx_calib_stream", "mmx_host_prune_axis",
@@ -152,6 +156,9 @@ SYMBOLS = (
 )
 KERNEL_KINDS = ("zpass", "ypass", "xpass", "generic", "peaks", "rescore", "overlap_pairs",
                 "close_pairs", "zxpass", "y2pass", "preproc", "coloc", "zxpack", "widepass")
+#: families behind the ``MMX_K_COUNT`` counted ones (``MMX_K_THIN``): timed and read with them
+MORE_KERNEL_KINDS = ("thinpass",)
+_ALL_KINDS = KERNEL_KINDS + MORE_KERNEL_KINDS
 
 
 def lib() -> ctypes.CDLL:
@@ -193,6 +200,10 @@ def lib() -> ctypes.CDLL:
     L.mmx_zx_pack.argtypes = [POINTER(Volume), vp, vp, c_int, c_int64, vp, vp]
     L.mmx_tiled_q16_error_bound.argtypes = [POINTER(c_double), POINTER(c_double), c_int, c_double]
     L.mmx_tiled_q16_error_bound.restype = c_double
+    L.mmx_fold_matrix.argtypes = [POINTER(c_float), c_int, c_int, POINTER(c_float)]
+    L.mmx_fold_matrix.restype = c_int
+    L.mmx_col_prefetch.argtypes = []
+    L.mmx_col_prefetch.restype = c_int
     L.mmx_peaks_batch.argtypes = [vp, vp, c_int, c_int, vp, vp, c_int, c_int64, c_float, c_float, vp,
                                   c_uint32, vp, vp]
     L.mmx_rescore_f64.argtypes = [POINTER(Volume), vp, c_int, vp, c_uint32, vp, vp, vp,
@@ -326,16 +337,31 @@ def timing_enable(on: bool = True, kinds=None) -> None:
     if on and kinds is not None:
         mask = 0
         for k in kinds:
-            mask |= 1 << (KERNEL_KINDS.index(k) + 1)
+            mask |= 1 << (_ALL_KINDS.index(k) + 1)
     check(lib().mmx_timing_enable(mask), "mmx_timing_enable")
 
 
 def timing_read() -> dict:
     """``{kind: (milliseconds, launches)}`` since the last read (synchronises the events)."""
-    ms = (c_double * len(KERNEL_KINDS))()
-    n = (c_int64 * len(KERNEL_KINDS))()
-    check(lib().mmx_timing_read(ms, n, len(KERNEL_KINDS)), "mmx_timing_read")
-    return {k: (ms[i], n[i]) for i, k in enumerate(KERNEL_KINDS)}
+    ms = (c_double * len(_ALL_KINDS))()
+    n = (c_int64 * len(_ALL_KINDS))()
+    check(lib().mmx_timing_read(ms, n, len(_ALL_KINDS)), "mmx_timing_read")
+    return {k: (ms[i], n[i]) for i, k in enumerate(_ALL_KINDS)}
+
+
+def col_prefetch() -> int:
+    """``MMX_COL_PREFETCH``, from the library: a block shorter than kernel radius + this along an axis is thin there."""
+    return int(lib().mmx_col_prefetch())
+
+
+def fold_matrix(w: np.ndarray, n: int) -> np.ndarray:
+    """``mmx_fold_matrix``: the ``(n, n)`` float32 operator SciPy's "reflect" folds the symmetric kernel of half
+    weights ``w[0 .. radius]`` (float32) into on an axis of ``n`` voxels."""
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    out = np.empty((int(n), int(n)), dtype=np.float32)
+    check(lib().mmx_fold_matrix(w.ctypes.data_as(POINTER(c_float)), len(w) - 1, int(n),
+                                out.ctypes.data_as(POINTER(c_float))), "mmx_fold_matrix")
+    return out
 
 
 def keep_host_heap(mmap_threshold: int = 1 << 30, trim_threshold: int = (1 << 31) - 1) -> bool:

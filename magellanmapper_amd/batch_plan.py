@@ -197,10 +197,42 @@ def _isolate_parents(batches: List[List[int]], splits: Dict[int, PartSplit]) -> 
     return out
 
 
+def thin_signature(shapes, thin_below: int) -> np.ndarray:
+    """Per block the set of axes it is *thin* along -- extent ``< thin_below`` -- as bits: 1 = z, 2 = y, 4 = x."""
+    shp = np.asarray(shapes, dtype=np.int64).reshape(-1, 3)
+    return ((shp < int(thin_below)) * np.array([1, 2, 4], dtype=np.int64)).sum(axis=1)
+
+
+def _fill_batches(order: Sequence[int], slots, per_vox: int, budget_bytes: int, max_batch: int) -> List[List[int]]:
+    """The blocks ``order`` in batches, in that order: a batch is closed when one more block -- every block in a slot of
+    the largest -- would exceed the budget or ``max_batch`` blocks."""
+    batches: List[List[int]] = []
+    cur: List[int] = []
+    cur_slot = 0
+    for i in order:
+        slot = max(cur_slot, slots[i])
+        if cur and ((len(cur) + 1) * slot * per_vox > budget_bytes or len(cur) >= max_batch):
+            batches.append(cur)
+            cur, slot = [], slots[i]
+        cur.append(i)
+        cur_slot = slot
+    if cur:
+        batches.append(cur)
+    return batches
+
+
 def plan_batches(shapes: Sequence[Tuple[int, int, int]], num_sigma: int, budget_bytes: int,
                  extra_bytes_per_voxel: int = 0, *, taper: int, ramp: int, max_batch: int = 1 << 30,
-                 forced_sizes: Sequence[int] = ()) -> List[List[int]]:
+                 forced_sizes: Sequence[int] = (), thin_below: int = 0, thin_min_voxels: int = 64 << 20,
+                 never_thin: Sequence[int] = ()) -> List[List[int]]:
     """Group block indices into batches whose workspace fits ``budget_bytes``.
+
+    ``thin_below`` > 0: blocks with an extent below it (:func:`thin_signature`; a ragged stack's remainders, shorter
+    than the kernels) leave the list -- one of them in a batch takes the whole batch off the fast kernels, whose path is
+    chosen from the batch's smallest extents.  The other blocks are planned as if they did not exist, and the thin ones
+    follow in batches of their own, one signature each, under the same budget rule.  Only when the regular blocks hold
+    real work (more than ``thin_min_voxels`` voxels, the taper's measure) and there are blocks of both kinds; the blocks
+    ``never_thin`` (detected in parts) count as regular whatever their extents.  0: no block leaves.
 
     Workspace = (4 + num_sigma) float32 arrays of ``n_blocks * slot`` voxels, slot = the
     largest block of the batch (+ ``extra_bytes_per_voxel`` for the preprocessed copies).
@@ -215,18 +247,19 @@ def plan_batches(shapes: Sequence[Tuple[int, int, int]], num_sigma: int, budget_
         cuts = np.concatenate(([0], np.cumsum(forced_sizes)))
         return [list(range(int(a), int(b))) for a, b in zip(cuts[:-1], cuts[1:])]
     slots = _slot_elems(np.asarray(shapes).reshape(-1, 3)).tolist()
-    batches: List[List[int]] = []
-    cur: List[int] = []
-    cur_slot = 0
-    for i, vox in enumerate(slots):
-        slot = max(cur_slot, vox)
-        if cur and ((len(cur) + 1) * slot * per_vox > budget_bytes or len(cur) >= max_batch):
-            batches.append(cur)
-            cur, slot = [], vox
-        cur.append(i)
-        cur_slot = slot
-    if cur:
-        batches.append(cur)
+    if thin_below > 0:
+        sig = thin_signature(shapes, thin_below)
+        sig[np.asarray(list(never_thin), dtype=np.int64)] = 0
+        regular = np.nonzero(sig == 0)[0].tolist()
+        if 0 < len(regular) < len(shapes) and \
+                sum(int(shapes[i][0]) * int(shapes[i][1]) * int(shapes[i][2]) for i in regular) > thin_min_voxels:
+            planned = plan_batches([shapes[i] for i in regular], num_sigma, budget_bytes, extra_bytes_per_voxel, taper=taper,
+                                   ramp=ramp, max_batch=max_batch)
+            batches = [[regular[k] for k in b] for b in planned]
+            for which in sorted(set(sig.tolist()) - {0}):
+                batches += _fill_batches(np.nonzero(sig == which)[0].tolist(), slots, per_vox, budget_bytes, max_batch)
+            return batches
+    batches = _fill_batches(range(len(slots)), slots, per_vox, budget_bytes, max_batch)
     # The host finishes batch k (candidates -> peaks -> per-block prune -> tables: ~0.45 ms per block of the
     # benchmark volume) while the GPU runs batch k + 1 (~0.46 ms per block with the tiled kernels), so it trails the
     # GPU by the host time of one batch, and nothing hides that of the LAST batches: the tail of the block list is
@@ -293,13 +326,15 @@ class PlannedBatch:
     will see of it -- ``n_blocks`` blocks in slots of ``slot`` elements: the parts of ``split`` when its one block is
     detected in parts, the blocks themselves otherwise.  ``records``: its host ``mmx_block`` array, or None where that
     is made when the batch is enqueued (a block in parts, a lane that preprocesses); ``d_records``: its slice of the
-    plan's one uploaded table, or None."""
+    plan's one uploaded table, or None.  ``zx_mode``: the ``mmx_zx_mode`` this batch asks for under ``MMX_ZX_AUTO`` --
+    ``MMX_ZX_THIN`` when every one of its blocks is thin along some axis -- or None: the lane's mode."""
     indices: List[int]
     split: Optional[PartSplit]
     n_blocks: int
     slot: int
     records: Optional[np.ndarray] = None
     d_records: object = None
+    zx_mode: Optional[int] = None
 
 
 @dataclass
@@ -310,9 +345,13 @@ class BatchPlan:
     shapes: List[Tuple[int, int, int]]
 
 
-def make_plan(origins, shapes, batches: List[List[int]], splits: Dict[int, PartSplit], strides=None) -> BatchPlan:
+def make_plan(origins, shapes, batches: List[List[int]], splits: Dict[int, PartSplit], strides=None,
+              thin_below: int = 0) -> BatchPlan:
     """The plan of ``batches`` (block indices; a block of ``splits`` alone in its batch).  ``strides``: the element
-    strides (z, y, x) of the volume the batches read raw -- they then carry their records; None: no batch does."""
+    strides (z, y, x) of the volume the batches read raw -- they then carry their records; None: no batch does.
+    ``thin_below`` > 0: a batch whose every block has an extent below it (never the parts of a block) asks for
+    ``MMX_ZX_THIN``."""
+    thin = thin_signature(shapes, thin_below) != 0 if thin_below > 0 and len(shapes) else None
     if strides is not None:
         src_offsets = np.asarray(origins, dtype=np.int64).reshape(-1, 3) @ np.asarray(strides, dtype=np.int64)
     planned = []
@@ -320,5 +359,6 @@ def make_plan(origins, shapes, batches: List[List[int]], splits: Dict[int, PartS
         split = splits.get(b[0]) if len(b) == 1 else None
         shp = split.box_shapes if split is not None else [shapes[i] for i in b]
         records = block_records(src_offsets[b], shp)[0] if split is None and strides is not None else None
-        planned.append(PlannedBatch(b, split, len(shp), batch_slot(shp), records))
+        zx_mode = nat.MMX_ZX_THIN if thin is not None and split is None and bool(thin[b].all()) else None
+        planned.append(PlannedBatch(b, split, len(shp), batch_slot(shp), records, zx_mode=zx_mode))
     return BatchPlan(planned, origins, shapes)

@@ -227,6 +227,11 @@ _MAX_BATCH = 1 << 30
 #: last batches), the first batch into a ramp that starts at this many blocks (nothing hides its GPU time from the host)
 TAPER = 4
 RAMP = 16
+#: blocks shorter than the largest kernel radius + ``MMX_COL_PREFETCH`` along an axis (a ragged stack's remainders) leave
+#: the batches of the others -- one of them takes its whole batch off the fast kernels -- when the others hold more than
+#: this many voxels (the taper's measure of real work); below it the plan is the one of all blocks together (a one-batch
+#: stack keeps its single native call and its captured graph).  Tests set it to 0
+THIN_SPLIT_MIN_VOXELS = 64 << 20
 #: experiments only: cut the block list into batches of exactly these sizes (when they add up to the number of blocks)
 FORCED_BATCH_SIZES: list = []
 #: a block whose workspace slot (:func:`_slot_elems`) reaches this many elements is detected as several overlapping parts
@@ -244,11 +249,22 @@ def _slot_limit() -> int:
 
 
 def plan_batches(shapes: Sequence[Tuple[int, int, int]], num_sigma: int,
-                 budget_bytes: int, extra_bytes_per_voxel: int = 0) -> List[List[int]]:
+                 budget_bytes: int, extra_bytes_per_voxel: int = 0, *, thin_below: int = 0,
+                 never_thin: Sequence[int] = ()) -> List[List[int]]:
     """:func:`batch_plan.plan_batches` with this module's settings: block indices grouped into batches whose workspace
-    fits ``budget_bytes``."""
+    fits ``budget_bytes``, the blocks with an extent below ``thin_below`` in batches of their own behind the others."""
     return _bp.plan_batches(shapes, num_sigma, budget_bytes, extra_bytes_per_voxel, taper=TAPER, ramp=RAMP,
-                            max_batch=_MAX_BATCH, forced_sizes=FORCED_BATCH_SIZES)
+                            max_batch=_MAX_BATCH, forced_sizes=FORCED_BATCH_SIZES, thin_below=thin_below,
+                            thin_min_voxels=THIN_SPLIT_MIN_VOXELS, never_thin=never_thin)
+
+
+def _thin_below(lanes) -> int:
+    """The extent below which a block is thin for this call: the largest kernel radius over the lanes +
+    ``MMX_COL_PREFETCH`` (what the register-ring column kernels need).  0 -- no block is -- unless the mode is
+    ``MMX_ZX_AUTO``: a mode asked for by name is passed as it is."""
+    if ZX_MODE != nat.MMX_ZX_AUTO:
+        return 0
+    return max(int(lane.space.radii.max(initial=0)) for lane in lanes) + nat.col_prefetch()
 
 
 def _split_blocks(lanes, shapes, limit: int) -> Dict[int, PartSplit]:
@@ -305,7 +321,8 @@ _SELF_TESTED = set()
 def self_test(dev) -> None:
     """Known-answer check of the matrix-core kernels, once per process and device (~30 ms): a small block tall
     enough for their steady-state loop through ``MMX_ZX_TILED`` and ``MMX_ZX_TILED_Q16`` (integer and float voxels,
-    one radius per kernel geometry class) against the library's generic one-thread-per-voxel kernels.
+    one radius per kernel geometry class) against the library's generic one-thread-per-voxel kernels -- and, at the
+    radius that is longer than its 12 rows, through ``MMX_ZX_THIN`` (the folded Y pass).
 
     Why it exists: the exactness machinery compares float32 with float64 values AT THE CANDIDATES a batch
     nominates -- a kernel that is wrong everywhere nominates nothing and the batch comes back empty without an
@@ -334,7 +351,7 @@ def self_test(dev) -> None:
             nat.check(L.mmx_log_batch_f32_generic(*args, ws.data_ptr() + 5 * slot * 4, ws.data_ptr(), _stream_ptr()),
                       "mmx_log_batch_f32_generic")
             want = ws[5 * slot:6 * slot].clone()
-            for mode, tol in ((nat.MMX_ZX_TILED, 2e-6), (nat.MMX_ZX_TILED_Q16, 6e-5)):
+            for mode, tol in ((nat.MMX_ZX_TILED, 2e-6), (nat.MMX_ZX_TILED_Q16, 6e-5), (nat.MMX_ZX_THIN, 2e-6)):
                 path = ctypes.c_int(0)
                 nat.check(L.mmx_log_batch_f32(*args, ws.data_ptr() + 4 * slot * 4, ws.data_ptr(), None, 0.0, 0.0, None,
                                               mode, ctypes.byref(path), _stream_ptr()), "mmx_log_batch_f32")
@@ -535,24 +552,28 @@ def _plan_for(dvol: DeviceVolume, lanes, lists: _BlockLists, bufs: _Buffers, ns:
     # blocks too large for one workspace slot go through as several overlapping parts, each in a batch of its own
     # (DESIGN.md section 4f); without one -- nearly every call -- nothing takes another path
     splits = _split_blocks(lanes, lists.shapes, _slot_limit()) if lists.slot_max >= _slot_limit() else {}
+    thin_below = _thin_below(lanes)
     key = None
     if not pre and not splits:
         t_ = dvol.tensor
         # (block records hold element offsets, not addresses: any volume of this layout can use them; the block lists
         #  are compared by content -- `lists.key` -- so that a caller who builds them afresh finds the same device
         #  tables, which is also what lets a small batch's captured graph be found again)
-        key = (lists.key, tuple(t_.stride()), tuple(t_.shape), str(t_.dtype), ns, int(budget_bytes), _MAX_BATCH, RAMP, TAPER)
+        key = (lists.key, tuple(t_.stride()), tuple(t_.shape), str(t_.dtype), ns, int(budget_bytes), _MAX_BATCH, RAMP, TAPER,
+               thin_below, THIN_SPLIT_MIN_VOXELS)
         hit = bufs.plans.get(key)
         if hit is not None:
             return hit
     batches = plan_batches(lists.shapes, ns, budget_bytes,
-                           0 if not pre else max(lane.pre.bytes_per_voxel() for lane in lanes))
+                           0 if not pre else max(lane.pre.bytes_per_voxel() for lane in lanes), thin_below=thin_below,
+                           never_thin=sorted(splits))
     if splits:
         batches = _isolate_parents(batches, splits)
     # (raw lanes: the records of every batch but a block in parts are made here, for `_upload_records`)
     if not pre:
         _held_origins(dvol, lists.origins, lists.shapes)
-    plan = _bp.make_plan(lists.origins, lists.shapes, batches, splits, None if pre else dvol.tensor.stride()[:3])
+    plan = _bp.make_plan(lists.origins, lists.shapes, batches, splits, None if pre else dvol.tensor.stride()[:3],
+                         thin_below)
     if key is not None:
         if len(bufs.plans) >= 8:
             bufs.plans.clear()
@@ -647,7 +668,7 @@ def blob_log_lanes(dvol: DeviceVolume, lanes: Sequence[Lane], origins: Sequence[
             # (preprocessing: when the buffer set's previous holder is done; the first holders behind the main stream)
             pipe = _Pipelined(planned, enq & 1, None if enq < ahead + 1 else done_events[enq - (ahead + 1)])
             jobs[enq] = _enqueue_detect(dvol, ln, [origins[i] for i in batch], [shapes[i] for i in batch], bufs,
-                                        enq % (ahead + 1), pipe=pipe, split=planned.split)
+                                        enq % (ahead + 1), pipe=pipe, split=planned.split, zx_mode=planned.zx_mode)
             done_events.append(jobs[enq].done)
             jobs[enq].indices = batch
             if enq == 0:
@@ -710,6 +731,7 @@ class _Batch:
     d_parents: Optional["torch.Tensor"] = None
     d_parts: Optional["torch.Tensor"] = None
     n_part_vox: int = 0
+    zx_mode: Optional[int] = None       # the mode its plan asks for (`PlannedBatch.zx_mode`)
 
     @property
     def table_blocks(self) -> np.ndarray:
@@ -802,8 +824,9 @@ def _batch_voxels(dvol, lane: "Lane", origins, shapes, bufs: _Buffers, which: in
 
 
 def _detect_args(lane: "Lane", vox: _Voxels, bufs: _Buffers, which: int, ws, ws_i: int, cap: int, eps: float, exact: bool,
-                 native: bool, side_tail: bool) -> "nat.DetectArgs":
-    """The ``mmx_detect_args`` of a batch whose voxels, workspace and table slot are settled."""
+                 native: bool, side_tail: bool, zx_mode: Optional[int] = None) -> "nat.DetectArgs":
+    """The ``mmx_detect_args`` of a batch whose voxels, workspace and table slot are settled.  ``zx_mode``: the mode
+    the batch's plan asks for, which holds under ``MMX_ZX_AUTO`` only."""
     space, stream = lane.space, _stream_ptr()
     ev_read, ev_done = bufs.events(which)
     a = nat.DetectArgs()
@@ -819,7 +842,8 @@ def _detect_args(lane: "Lane", vox: _Voxels, bufs: _Buffers, which: int, ws, ws_
     a.h_count = bufs.host_counts[which].data_ptr()
     if native:
         a.h_cands, a.h_prefix = bufs.host_table(which).data_ptr(), min(cap, _PREFIX_ENTRIES)
-    a.zx_mode, a.zx_flags, a.store_f32, a.exact, a.expand = ZX_MODE, ZX_FLAGS, vox.store_f32, int(exact), int(native)
+    a.zx_mode = ZX_MODE if (zx_mode is None or ZX_MODE != nat.MMX_ZX_AUTO) else zx_mode
+    a.zx_flags, a.store_f32, a.exact, a.expand = ZX_FLAGS, vox.store_f32, int(exact), int(native)
     a.stream = a.pack_stream = stream
     a.tail_stream = bufs.rescore_stream.cuda_stream if side_tail else stream      # (the library forks and joins it)
     # (the last reader of this workspace; also a batch that is nominated again, on the main stream: same workspace)
@@ -831,13 +855,14 @@ def _detect_args(lane: "Lane", vox: _Voxels, bufs: _Buffers, which: int, ws, ws_
 
 def _enqueue_detect(dvol, lane: "Lane", origins, shapes, bufs: _Buffers, which: int, *, cap: Optional[int] = None,
                     eps: Optional[float] = None, exact: Optional[bool] = None, split: Optional[PartSplit] = None,
-                    pipe: Optional[_Pipelined] = None) -> _Batch:
+                    pipe: Optional[_Pipelined] = None, zx_mode: Optional[int] = None) -> _Batch:
     """Enqueue (P1-P3,) A0-A4 of one batch of ``lane`` on the current stream: the preprocessing, then ONE
     ``mmx_detect_batch`` call (or the replay of its captured graph); nothing here waits for the GPU.
     ``eps`` / ``exact`` (default: the lane's): the nomination band, and whether every candidate is also re-scored in
     float64 (otherwise ``_resolve_peaks`` re-scores the few whose decision depends on it).
     ``split``: ``origins`` / ``shapes`` hold ONE block, which goes through the passes and the NMS as the parts of this
     split; the library folds their candidates back into it (``mmx_fold_parts``) and everything behind sees that block.
+    ``zx_mode``: the mode the batch's plan asks for (``PlannedBatch.zx_mode``; every path below passes it on).
     ``pipe``: the batch's place in the pipeline of :func:`blob_log_lanes`.  Without it the block records are made here,
     the batch works in workspace 0 with no side tail, and its preprocessing runs on the main stream."""
     space, pre, vrange = lane.space, lane.pre, lane.vrange
@@ -871,7 +896,7 @@ def _enqueue_detect(dvol, lane: "Lane", origins, shapes, bufs: _Buffers, which: 
     if cap is None:
         cap = max(4096, min(n_part_vox * ns, n_part_vox // 2000 * ns + 65536))
     native = bool(exact and HOST_PATH == "native")
-    a = _detect_args(lane, vox, bufs, which, ws, ws_i, cap, eps, exact, native, side_tail)
+    a = _detect_args(lane, vox, bufs, which, ws, ws_i, cap, eps, exact, native, side_tail, zx_mode)
     ev_read, ev_done = bufs.events(which)
     d_parents = d_parts = None
     if split is not None:
@@ -902,7 +927,7 @@ def _enqueue_detect(dvol, lane: "Lane", origins, shapes, bufs: _Buffers, which: 
     return _Batch(lane=lane, origins=origins, shapes=shapes, blocks=blocks, d_blocks=vox.d_blocks, nb=nb, ns=ns, n_vox=n_vox,
                   cap=cap, which=which, done=ev_done, store_f32=vox.store_f32, vol_exact=vox.vol_exact, eps=eps, exact=exact,
                   native=native, split=split, parents=vox.parents, d_parents=d_parents, d_parts=d_parts,
-                  n_part_vox=n_part_vox)
+                  n_part_vox=n_part_vox, zx_mode=zx_mode)
 
 
 def _launch_batch(L, a, info, bufs: _Buffers, nb: int, blocks, space, vol32, vol_exact, ev_read) -> int:
@@ -976,7 +1001,7 @@ def _redo(batch: _Batch, dvol, bufs: _Buffers, *, cap: Optional[int], eps: float
     and is never offered to a ``finisher``.  A block in parts is nominated again whole: all its parts, the same split."""
     torch.cuda.current_stream().synchronize()
     again = _enqueue_detect(dvol, batch.lane, batch.origins, batch.shapes, bufs, batch.which, cap=cap, eps=eps, exact=exact,
-                            split=batch.split)
+                            split=batch.split, zx_mode=batch.zx_mode)
     again.indices, again.retries = batch.indices, batch.retries
     return _finish_detect(again, dvol, bufs)
 

@@ -10,6 +10,9 @@
 int mmx_launch_generic_pass(int pass, const mmx_volume* vol, const mmx_block* d_blocks, int n_blocks,
                             int max_vox, int64_t slot_elems, const float* w0, const float* w2, int radius,
                             const float* in1, const float* in2, float* out1, float* out2, hipStream_t s);
+int mmx_launch_fold_pass(int pass, const mmx_volume* vol, const mmx_block* d_blocks, int n_blocks,
+                         int max_vox, int64_t slot_elems, const float* w0, const float* w2, int radius,
+                         const float* in1, const float* in2, float* out1, float* out2, hipStream_t s);
 int mmx_launch_peaks(const float* d_log, int n_sigma, int64_t sigma_stride, const mmx_block* d_blocks,
                      int n_blocks, int max_vox, int64_t slot_elems, float thr, float eps,
                      mmx_cand* d_cands, uint32_t cap, uint32_t* d_count, hipStream_t stream);
@@ -30,7 +33,7 @@ bool g_timing = false;
 uint32_t g_kinds = ~0u;              // kernel families that record events while g_timing is on
 std::vector<span> g_spans;          // recorded spans of the current window
 std::vector<hipEvent_t> g_pool;     // recycled events
-hipEvent_t g_open[MMX_K_COUNT];
+hipEvent_t g_open[MMX_K_SLOTS];
 
 hipEvent_t take_event()
 {
@@ -72,7 +75,7 @@ int mmx_timing_enable(int on)
     std::lock_guard<std::mutex> lk(g_tm);
     for (auto& sp : g_spans) { g_pool.push_back(sp.a); g_pool.push_back(sp.b); }
     g_spans.clear();
-    for (int k = 0; k < MMX_K_COUNT; ++k) g_open[k] = nullptr;
+    for (int k = 0; k < MMX_K_SLOTS; ++k) g_open[k] = nullptr;
     g_timing = on != 0;
     // 1: every family; any other non-zero value: bit (k + 1) selects family MMX_K_k
     g_kinds = on == 1 ? ~0u : ((uint32_t)on >> 1);
@@ -91,6 +94,11 @@ int mmx_timing_read(double* ms, int64_t* launches, int n)
     std::lock_guard<std::mutex> lk(g_tm);
     for (int k = 0; k < n; ++k) { ms[k] = 0.0; launches[k] = 0; }
     for (auto& sp : g_spans) {
+        if (sp.kind >= n) {             // (a family behind the ones this caller knows)
+            g_pool.push_back(sp.a);
+            g_pool.push_back(sp.b);
+            continue;
+        }
         hipError_t r = hipEventSynchronize(sp.b);
         if (r != hipSuccess) return hip_fail(r, "hipEventSynchronize");
         float t = 0.f;
@@ -316,29 +324,38 @@ int wide_passes(const mmx_log_call& c, const mmx_route& r, const pass_weights& w
     return launched(rc, "mmx_launch_wide_pass", "wide passes");
 }
 
-// The three separate passes, Z, Y, X: per pass the register-ring kernel (ring_*) or the generic one.  `timed`: under the
-// timing scopes of their families.
+// The three separate passes, Z, Y, X: per pass the register-ring kernel (ring bit), the folded-reflection pass (fold
+// bit) or the generic one; bit 0 = Z, 1 = Y, 2 = X.  `timed`: under the timing scopes of their families.
 int three_passes(const mmx_volume* vol, const mmx_block* d_blocks, int n_blocks, int64_t slot_elems, int radius,
-                 float* d_work, float* d_log, const mmx_batch_geom& g, const pass_weights& w, bool ring_z, bool ring_y,
-                 bool ring_x, bool timed, hipStream_t s)
+                 float* d_work, float* d_log, const mmx_batch_geom& g, const pass_weights& w, int rings, int folds,
+                 bool timed, hipStream_t s)
 {
     float* t0 = d_work;                                     // Gz
     float* t1 = t0 + (int64_t)n_blocks * slot_elems;        // Gzz
     float* t2 = t1 + (int64_t)n_blocks * slot_elems;        // A
     float* t3 = t2 + (int64_t)n_blocks * slot_elems;        // BC
-    int rc;
-    { pass_scope ts(!timed ? -1 : (ring_z ? MMX_K_ZPASS : MMX_K_GENERIC), s);
-    if (ring_z) rc = mmx_launch_zpass(vol, d_blocks, n_blocks, g.max_zcols, slot_elems, taps(w.z0, w.z2, radius), radius, t0, t1, s);
-    else rc = mmx_launch_generic_pass(0, vol, d_blocks, n_blocks, g.max_vox, slot_elems, w.z0, w.z2, radius, nullptr, nullptr, t0, t1, s); }
-    if (rc != MMX_OK) return launched(rc, ring_z ? "mmx_launch_zpass" : "mmx_launch_generic_pass", "z pass");
-    { pass_scope ts(!timed ? -1 : (ring_y ? MMX_K_YPASS : MMX_K_GENERIC), s);
-    if (ring_y) rc = mmx_launch_ypass(d_blocks, n_blocks, g.max_ycols, slot_elems, taps(w.y0, w.y2, radius), radius, t0, t1, t2, t3, s);
-    else rc = mmx_launch_generic_pass(1, vol, d_blocks, n_blocks, g.max_vox, slot_elems, w.y0, w.y2, radius, t0, t1, t2, t3, s); }
-    if (rc != MMX_OK) return launched(rc, ring_y ? "mmx_launch_ypass" : "mmx_launch_generic_pass", "y pass");
-    { pass_scope ts(!timed ? -1 : (ring_x ? MMX_K_XPASS : MMX_K_GENERIC), s);
-    if (ring_x) rc = mmx_launch_xpass(d_blocks, n_blocks, g.max_rows, g.max_nx, slot_elems, taps(w.x0, w.x2, radius), radius, t2, t3, d_log, s);
-    else rc = mmx_launch_generic_pass(2, vol, d_blocks, n_blocks, g.max_vox, slot_elems, w.x0, w.x2, radius, t2, t3, d_log, nullptr, s); }
-    return launched(rc, ring_x ? "mmx_launch_xpass" : "mmx_launch_generic_pass", "x pass");
+    const float* w0[3] = {w.z0, w.y0, w.x0};
+    const float* w2[3] = {w.z2, w.y2, w.x2};
+    const float* in1[3] = {nullptr, t0, t2};
+    const float* in2[3] = {nullptr, t1, t3};
+    float* out1[3] = {t0, t2, d_log};
+    float* out2[3] = {t1, t3, nullptr};
+    const int ring_kind[3] = {MMX_K_ZPASS, MMX_K_YPASS, MMX_K_XPASS};
+    const char* ring_name[3] = {"mmx_launch_zpass", "mmx_launch_ypass", "mmx_launch_xpass"};
+    const char* what[3] = {"z pass", "y pass", "x pass"};
+    for (int p = 0; p < 3; ++p) {
+        const bool ring = (rings >> p) & 1, fold = !ring && ((folds >> p) & 1);
+        int rc;
+        { pass_scope ts(!timed ? -1 : (ring ? ring_kind[p] : (fold ? MMX_K_THIN : MMX_K_GENERIC)), s);
+        if (ring && p == 0) rc = mmx_launch_zpass(vol, d_blocks, n_blocks, g.max_zcols, slot_elems, taps(w.z0, w.z2, radius), radius, t0, t1, s);
+        else if (ring && p == 1) rc = mmx_launch_ypass(d_blocks, n_blocks, g.max_ycols, slot_elems, taps(w.y0, w.y2, radius), radius, t0, t1, t2, t3, s);
+        else if (ring) rc = mmx_launch_xpass(d_blocks, n_blocks, g.max_rows, g.max_nx, slot_elems, taps(w.x0, w.x2, radius), radius, t2, t3, d_log, s);
+        else rc = (fold ? mmx_launch_fold_pass : mmx_launch_generic_pass)(p, vol, d_blocks, n_blocks, g.max_vox, slot_elems, w0[p], w2[p],
+                                                                          radius, in1[p], in2[p], out1[p], out2[p], s); }
+        if (rc != MMX_OK)
+            return launched(rc, ring ? ring_name[p] : (fold ? "mmx_launch_fold_pass" : "mmx_launch_generic_pass"), what[p]);
+    }
+    return MMX_OK;
 }
 
 }  // namespace
@@ -367,8 +384,8 @@ int mmx_log_scale_run(const mmx_log_call& c, const mmx_batch_geom& g, const mmx_
     int rc;
     if (r.family == MMX_ROUTE_WIDE) rc = wide_passes(c, r, w);
     else if (r.family == MMX_ROUTE_SEPARATE)
-        rc = three_passes(c.vol, c.d_blocks, c.n_blocks, c.slot_elems, c.radius, c.d_work, c.d_log, g, w, r.ring_z, r.ring_y,
-                          r.ring_x, true, c.stream);
+        rc = three_passes(c.vol, c.d_blocks, c.n_blocks, c.slot_elems, c.radius, c.d_work, c.d_log, g, w,
+                          r.ring_z | r.ring_y << 1 | r.ring_x << 2, r.fold_z | r.fold_y << 1 | r.fold_x << 2, true, c.stream);
     else rc = fused_passes(c, r, g, w);
     if (rc != MMX_OK) return rc;
     if (c.h_zx_path) *c.h_zx_path = r.path;
@@ -433,8 +450,7 @@ int mmx_log_batch_f32_generic(const mmx_volume* vol, const mmx_block* d_blocks, 
     if (g.status != MMX_OK) return g.status;
     pass_weights w;
     make_weights(vol, h_w0, h_w2, radius, norm, &w);
-    return three_passes(vol, d_blocks, n_blocks, slot_elems, radius, d_work, d_log, g, w, false, false, false, false,
-                        (hipStream_t)stream);
+    return three_passes(vol, d_blocks, n_blocks, slot_elems, radius, d_work, d_log, g, w, 0, 0, false, (hipStream_t)stream);
 }
 
 int mmx_zx_pack(const mmx_volume* vol, const mmx_block* d_blocks, const mmx_block* h_blocks, int n_blocks,

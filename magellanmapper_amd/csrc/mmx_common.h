@@ -125,6 +125,8 @@ enum mmx_kernel_kind {
 void mmx_time_begin(int kind, hipStream_t s);
 void mmx_time_end(int kind, hipStream_t s);
 static_assert(MMX_K_END == MMX_K_COUNT, "kernel kinds out of sync with mmx.h");
+// (MMX_K_THIN, the folded passes, is the slot behind them: mmx.h, MMX_K_SLOTS)
+static_assert(MMX_K_THIN == MMX_K_END && MMX_K_SLOTS == MMX_K_THIN + 1, "the thin family follows the counted ones");
 struct mmx_timed_scope {
     int kind; hipStream_t s;
     mmx_timed_scope(int k, hipStream_t st) : kind(k), s(st) { mmx_time_begin(k, st); }

@@ -5,64 +5,19 @@
 // extent >= radius; here SciPy's "reflect" may wrap several times), and the float64 cross-checks: it is the in-library
 // reference the tests and blob_log.self_test hold every other kernel to (mmx_log_batch_f32_generic).  Radii 25 .. 64 on
 // blocks at least that thick, which used to come here, take the wide passes.  Same math as mmx_colpass.hip /
-// mmx_xpass.hip (scipy/ndimage/_filters.py:644-707 in float32), one thread per output voxel, taps read through L1/L2,
-// weights from the kernarg segment (uniform index -> scalar loads).
+// mmx_xpass.hip (scipy/ndimage/_filters.py:644-707 in float32), one thread per output voxel: the tap loops of
+// mmx_taploop.h.
 
-#include "mmx_common.h"
-
-struct mmx_taps_generic {
-    float w0[MMX_MAX_RADIUS_GENERIC + 1];
-    float w2[MMX_MAX_RADIUS_GENERIC + 1];
-};
+#include "mmx_taploop.h"
 
 namespace {
-
-__device__ __forceinline__ float load_any(const void* base, int dtype, int64_t idx)
-{
-    switch (dtype) {
-        case MMX_U8:  return (float)((const uint8_t*)base)[idx];
-        case MMX_U16: return (float)((const uint16_t*)base)[idx];
-        case MMX_F32: return ((const float*)base)[idx];
-        default:      return (float)((const double*)base)[idx];
-    }
-}
-
-// idx runs over the pitched block [nz][ny][px]; returns 0 past the end, 1 for a voxel, 2 for a
-// pitch column (skipped)
-__device__ __forceinline__ int locate(const mmx_block& bd, int idx, int& z, int& y, int& x)
-{
-    const int plane = bd.ny * bd.px;
-    if (idx >= bd.nz * plane) return 0;
-    z = idx / plane;
-    const int rem = idx - z * plane;
-    y = rem / bd.px;
-    x = rem - y * bd.px;
-    return x < bd.nx ? 1 : 2;
-}
 
 __global__ void __launch_bounds__(MMX_WG)
 gen_z(mmx_volume vol, const mmx_block* __restrict__ blocks, int64_t slot_elems, int R,
       float* __restrict__ gz, float* __restrict__ gzz, mmx_taps_generic t)
 {
     const mmx_block bd = blocks[blockIdx.y];
-    for (int idx = blockIdx.x * MMX_WG + threadIdx.x;; idx += gridDim.x * MMX_WG) {
-        int z, y, x;
-        const int where = locate(bd, idx, z, y, x);
-        if (where == 0) return;
-        if (where == 2) continue;
-        const int64_t col = bd.src_off + (int64_t)y * vol.stride_y + (int64_t)x * vol.stride_x;
-        const float c = load_any(vol.d_data, vol.dtype, col + (int64_t)z * vol.stride_z);
-        float a0 = c * t.w0[0], a2 = c * t.w2[0];
-        for (int k = 1; k <= R; ++k) {
-            const float p = load_any(vol.d_data, vol.dtype, col + (int64_t)mmx_reflect(z - k, bd.nz) * vol.stride_z) +
-                            load_any(vol.d_data, vol.dtype, col + (int64_t)mmx_reflect(z + k, bd.nz) * vol.stride_z);
-            a0 = fmaf(p, t.w0[k], a0);
-            a2 = fmaf(p, t.w2[k], a2);
-        }
-        const int64_t o = (int64_t)bd.slot * slot_elems + idx;
-        gz[o] = a0;
-        gzz[o] = a2;
-    }
+    mmx_taploop_z(vol, bd, slot_elems, R, gz, gzz, t, blockIdx.x * MMX_WG + threadIdx.x, gridDim.x * MMX_WG);
 }
 
 __global__ void __launch_bounds__(MMX_WG)
@@ -71,28 +26,7 @@ gen_y(const mmx_block* __restrict__ blocks, int64_t slot_elems, int R,
       float* __restrict__ oa, float* __restrict__ obc, mmx_taps_generic t)
 {
     const mmx_block bd = blocks[blockIdx.y];
-    for (int idx = blockIdx.x * MMX_WG + threadIdx.x;; idx += gridDim.x * MMX_WG) {
-        int z, y, x;
-        const int where = locate(bd, idx, z, y, x);
-        if (where == 0) return;
-        if (where == 2) continue;
-        const int64_t col = (int64_t)bd.slot * slot_elems + (int64_t)z * bd.ny * bd.px + x;
-        const float c1 = gz[col + (int64_t)y * bd.px], c2 = gzz[col + (int64_t)y * bd.px];
-        float a = c1 * t.w0[0];
-        float bc = fmaf(c2, t.w0[0], c1 * t.w2[0]);
-        for (int k = 1; k <= R; ++k) {
-            const int64_t lo = col + (int64_t)mmx_reflect(y - k, bd.ny) * bd.px;
-            const int64_t hi = col + (int64_t)mmx_reflect(y + k, bd.ny) * bd.px;
-            const float p1 = gz[lo] + gz[hi];
-            const float p2 = gzz[lo] + gzz[hi];
-            a = fmaf(p1, t.w0[k], a);
-            bc = fmaf(p1, t.w2[k], bc);
-            bc = fmaf(p2, t.w0[k], bc);
-        }
-        const int64_t o = (int64_t)bd.slot * slot_elems + idx;
-        oa[o] = a;
-        obc[o] = bc;
-    }
+    mmx_taploop_y(bd, slot_elems, R, gz, gzz, oa, obc, t, blockIdx.x * MMX_WG + threadIdx.x, gridDim.x * MMX_WG);
 }
 
 __global__ void __launch_bounds__(MMX_WG)
@@ -101,20 +35,7 @@ gen_x(const mmx_block* __restrict__ blocks, int64_t slot_elems, int R,
       mmx_taps_generic t)
 {
     const mmx_block bd = blocks[blockIdx.y];
-    for (int idx = blockIdx.x * MMX_WG + threadIdx.x;; idx += gridDim.x * MMX_WG) {
-        int z, y, x;
-        const int where = locate(bd, idx, z, y, x);
-        if (where == 0) return;
-        if (where == 2) continue;
-        const int64_t row = (int64_t)bd.slot * slot_elems + ((int64_t)z * bd.ny + y) * bd.px;
-        float acc = ga[row + x] * t.w2[0];
-        for (int k = 1; k <= R; ++k)
-            acc = fmaf(ga[row + mmx_reflect(x - k, bd.nx)] + ga[row + mmx_reflect(x + k, bd.nx)], t.w2[k], acc);
-        acc = fmaf(gbc[row + x], t.w0[0], acc);
-        for (int k = 1; k <= R; ++k)
-            acc = fmaf(gbc[row + mmx_reflect(x - k, bd.nx)] + gbc[row + mmx_reflect(x + k, bd.nx)], t.w0[k], acc);
-        out[row + x] = acc;
-    }
+    mmx_taploop_x(bd, slot_elems, R, ga, gbc, out, t, blockIdx.x * MMX_WG + threadIdx.x, gridDim.x * MMX_WG);
 }
 
 }  // namespace

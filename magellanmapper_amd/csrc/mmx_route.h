@@ -12,8 +12,8 @@
 #include <cstddef>
 #include <vector>
 
-// the register-ring column kernels prefetch this many steps ahead and reflect once
-#define MMX_COL_PREFETCH 4
+// (MMX_COL_PREFETCH -- the register-ring column kernels prefetch this many steps ahead and reflect once -- and
+//  MMX_FOLD_MAX_N: include/mmx.h)
 // widest row pitch (floats) zx2_kernel takes: 5 producer waves
 #define MMX_PACKED_MAX_PX 320
 // (the tiled kernels take any row pitch: their voxel copy is made in x panels of 512 columns, and what bounds a block is
@@ -37,7 +37,7 @@ inline int mmx_zx_parse(int zx_mode, mmx_zx_request* q)
     q->prepacked = zx_mode == (MMX_ZX_TILED | MMX_ZX_PREPACKED) || zx_mode == (MMX_ZX_TILED_Q16 | MMX_ZX_PREPACKED);
     if (q->prepacked) zx_mode &= ~MMX_ZX_PREPACKED;
     q->mode = zx_mode;
-    if (zx_mode < MMX_ZX_AUTO || zx_mode > MMX_ZX_WIDE || zx_mode == 1 || (zx_mode >= 3 && zx_mode <= 5))
+    if (zx_mode < MMX_ZX_AUTO || zx_mode > MMX_ZX_THIN || zx_mode == 1 || (zx_mode >= 3 && zx_mode <= 5))
         return MMX_ERR_ARG;             // (3, 4, 5: retired experiment kernels)
     return MMX_OK;
 }
@@ -101,6 +101,17 @@ inline bool mmx_xpass_launch_accepts(int max_nx, int radius)
 inline bool mmx_xpass_accepts(const mmx_batch_geom& g, int radius)
 {
     return g.min_nx >= radius && mmx_xpass_launch_accepts(g.max_nx, radius);
+}
+
+// "this batch is thin at this radius": a block shorter than radius + MMX_COL_PREFETCH along some axis -- what sends a
+// pass of the separate passes off its register-ring kernel, and what MMX_ZX_THIN by name takes (a ladder: at its
+// largest radius).  The folded pass that then runs (mmx_launch_fold_pass) takes any radius up to
+// MMX_MAX_RADIUS_GENERIC and any extent: it folds the blocks of extent <= MMX_FOLD_MAX_N and runs the tap loop on the rest.
+inline bool mmx_thin_accepts(const mmx_batch_geom& g, int radius)
+{
+    const int thin_below = radius + MMX_COL_PREFETCH;
+    return radius >= 0 && radius <= MMX_MAX_RADIUS_GENERIC && g.status == MMX_OK &&
+           (g.min_nz < thin_below || g.min_ny < thin_below || g.min_nx < thin_below);
 }
 
 // "the fused path (Z+X in one kernel, then Y) takes this radius on this geometry"
@@ -214,7 +225,8 @@ struct mmx_route {
     bool makes_copy;            // tiled: this scale makes the voxel copy itself ...
     bool trusts_copy;           // ... or trusts the batch's (MMX_ZX_PREPACKED)
     int y_kernel;               // mmx_route_y (fused families)
-    bool ring_z, ring_y, ring_x;// separate: per pass, the register-ring kernel (else the generic one)
+    bool ring_z, ring_y, ring_x;// separate: per pass, the register-ring kernel (else the generic one, or the folded one:)
+    bool fold_z, fold_y, fold_x;// separate, MMX_ZX_THIN: per pass, the folded-reflection pass
     int layout;                 // NMS entry layout the scale writes: 0, MMX_MASK_ROWS, MMX_MASK_QUADS
     int path;                   // mmx_zx_mode reported through h_zx_path
     double bp, bq;              // q16: the bounds of P and Q in value units
@@ -225,10 +237,13 @@ struct mmx_route {
 // path where it accepts (unless MMX_ZX_SEPARATE) -- tiled when named or, under AUTO, for integer or ranged float voxels,
 // and the plan fits, on 16-bit tiles by mmx_tiles_q16's rule; else its packed kernel where that accepts; else the three
 // separate passes, each on its register-ring kernel where that accepts and on the generic one where not.
+// MMX_ZX_THIN by name: a batch that is thin at `thin_radius` (mmx_thin_accepts; < 0: at this scale's own radius -- a
+// ladder passes its largest) takes the separate passes with the folded pass in the generic one's place, path
+// MMX_ZX_THIN, no entries; any other batch goes on as under MMX_ZX_AUTO.
 // Returns MMX_OK or the status the call ends with (bad mode / radius: MMX_ERR_ARG; radius above MMX_MAX_RADIUS_GENERIC,
 // float64 voxels: MMX_ERR_UNSUPPORTED; else the geometry's).
 inline int mmx_route_scale(const mmx_volume* vol, const mmx_batch_geom& g, int radius, const double* w0, const double* w2,
-                           double norm, int zx_mode, double band, bool entries, mmx_route* r)
+                           double norm, int zx_mode, double band, bool entries, mmx_route* r, int thin_radius = -1)
 {
     *r = mmx_route{};
     r->path = MMX_ZX_SEPARATE;
@@ -236,6 +251,20 @@ inline int mmx_route_scale(const mmx_volume* vol, const mmx_batch_geom& g, int r
     if (mmx_zx_parse(zx_mode, &q) != MMX_OK || radius < 0) return MMX_ERR_ARG;
     if (radius > MMX_MAX_RADIUS_GENERIC || !mmx_voxels_ok(vol)) return MMX_ERR_UNSUPPORTED;
     if (g.status != MMX_OK) return g.status;
+    if (q.mode == MMX_ZX_THIN) {
+        if (mmx_thin_accepts(g, thin_radius < 0 ? radius : thin_radius)) {
+            r->family = MMX_ROUTE_SEPARATE;
+            r->path = MMX_ZX_THIN;
+            r->ring_z = mmx_zpass_accepts(vol, g, radius);
+            r->ring_y = mmx_ypass_accepts(g, radius);
+            r->ring_x = mmx_xpass_accepts(g, radius);
+            r->fold_z = !r->ring_z;
+            r->fold_y = !r->ring_y;
+            r->fold_x = !r->ring_x;
+            return MMX_OK;
+        }
+        q.mode = MMX_ZX_AUTO;
+    }
     if ((q.mode == MMX_ZX_WIDE || (q.mode == MMX_ZX_AUTO && radius > MMX_MAX_RADIUS_FAST)) && mmx_wide_accepts(vol, g, radius)) {
         r->family = MMX_ROUTE_WIDE;
         r->path = MMX_ZX_WIDE;
@@ -299,7 +328,8 @@ struct mmx_ladder_route {
 // bits (1 << layout), or a negative status.
 inline int mmx_route_config(const mmx_volume* vol, const mmx_batch_geom& g, const int32_t* radii, const double* w0_tab,
                             const double* w2_tab, const double* norms, int n_sigma, int mode, int zx_flags,
-                            const int32_t* modes, double band, bool entries, mmx_route* routes, mmx_ladder_route* out)
+                            const int32_t* modes, double band, bool entries, mmx_route* routes, mmx_ladder_route* out,
+                            int thin_radius = -1)
 {
     const size_t tab = MMX_MAX_RADIUS_GENERIC + 1;
     const bool is_float = vol->dtype == MMX_F32;
@@ -327,7 +357,8 @@ inline int mmx_route_config(const mmx_volume* vol, const mmx_batch_geom& g, cons
     int layouts = 0;
     for (int s = 0; s < n_sigma; ++s) {
         const int m = modes ? modes[s] : (trusted ? (tiled_mode | MMX_ZX_PREPACKED | zx_flags) : mode);
-        const int rc = mmx_route_scale(vol, g, radii[s], w0_tab + s * tab, w2_tab + s * tab, norms[s], m, band, entries, &routes[s]);
+        const int rc = mmx_route_scale(vol, g, radii[s], w0_tab + s * tab, w2_tab + s * tab, norms[s], m, band, entries, &routes[s],
+                                       thin_radius);
         if (rc != MMX_OK) return -rc;
         trusted = trusted && routes[s].path == tiled_mode;
         layouts |= 1 << routes[s].layout;
@@ -348,6 +379,8 @@ inline int mmx_route_config(const mmx_volume* vol, const mmx_batch_geom& g, cons
 //      type by name) while every scale so far ran the tiled path;
 //   3. MMX_ZX_PACKED with entries, when 2. mixed rows and quads;
 //   4. the requested mode without entries.
+// MMX_ZX_THIN by name: a batch that is thin at the ladder's largest radius gets that route for EVERY scale, in one
+// configuration without entries; any other batch is routed as under MMX_ZX_AUTO.
 // routes: [n_sigma].  Returns MMX_OK or the status of the first scale that has none.
 inline int mmx_route_ladder(const mmx_volume* vol, const mmx_batch_geom& g, const int32_t* radii, const double* w0_tab,
                             const double* w2_tab, const double* norms, int n_sigma, int zx_mode, int zx_flags, double band,
@@ -360,6 +393,18 @@ inline int mmx_route_ladder(const mmx_volume* vol, const mmx_batch_geom& g, cons
         layouts = mmx_route_config(vol, g, radii, w0_tab, w2_tab, norms, n_sigma, mode, zx_flags, modes, band, entries, routes, out);
         return layouts < 0 || !(layouts & (layouts - 1));      // (a status, or one layout: done)
     };
+    if (zx_mode == MMX_ZX_THIN) {
+        int r_max = 0;
+        for (int s = 0; s < n_sigma; ++s) if (radii[s] > r_max) r_max = radii[s];
+        if (!mmx_thin_accepts(g, r_max)) zx_mode = MMX_ZX_AUTO;
+        else {
+            out->n_configs = 1;
+            layouts = mmx_route_config(vol, g, radii, w0_tab, w2_tab, norms, n_sigma, zx_mode, zx_flags, nullptr, band, false,
+                                       routes, out, r_max);
+            if (layouts < 0) return -layouts;
+            return MMX_OK;              // (layout 0, no copy)
+        }
+    }
     bool any_wide = false;
     if (zx_mode == MMX_ZX_AUTO && g.status == MMX_OK)
         for (int s = 0; s < n_sigma; ++s)

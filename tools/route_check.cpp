@@ -1,6 +1,8 @@
 // Stand-alone host check of the kernel-path rules (csrc/mmx_route.h): the table of the rules -- ladders and single calls
 // with the full route they must get --, the by-name rows shared with tests/test_gpu_routes.py (tests/golden/
-// route_by_name.txt, path in argv[1]), and a sweep over geometries, radii, voxel types and modes for two properties: no
+// route_by_name.txt, path in argv[1]), the by-name rows of MMX_ZX_THIN on thin and thick blocks (tests/golden/
+// route_thin.txt, when argv[2] names it), the folded operator of that mode (csrc/mmx_fold.h) against a tap-by-tap
+// reflection for every extent and radius the kernels fold, and a sweep over geometries, radii, voxel types and modes for two properties: no
 // route selects a launcher whose predicate refuses it, and the route of a call agrees with the route of a one-scale
 // ladder.  Before that sweep, one over the NMS entry layouts (csrc/mmx_entries.h, host side).  Meant to run under the
 // host sanitizers (the command: DESIGN.md, "Wide radii").  No device code, no HIP call: the batch geometry is filled in
@@ -12,6 +14,7 @@
 #include <vector>
 
 #include "../magellanmapper_amd/csrc/mmx_common.h"
+#include "../magellanmapper_amd/csrc/mmx_fold.h"
 
 namespace {
 
@@ -49,17 +52,20 @@ mmx_volume volume(int dtype, float vrange, const geometry& r)
 }
 
 // the full route of a scale, as the table states it
-struct want { int family, q16, y, path, trusts, rings; };     // rings: 1 = z, 2 = y, 4 = x on the register-ring kernel
+struct want { int family, q16, y, path, trusts, rings, folds = 0; };  // rings: 1 = z, 2 = y, 4 = x on the register-ring kernel;
+                                                                      // folds: likewise, on the folded pass
 const int SEP = MMX_ROUTE_SEPARATE, WID = MMX_ROUTE_WIDE, TIL = MMX_ROUTE_TILED, PAC = MMX_ROUTE_PACKED;
 bool same(const mmx_route& r, const want& w)
 {
     return r.family == w.family && r.q16 == (w.q16 != 0) && r.y_kernel == w.y && r.path == w.path &&
-           r.trusts_copy == (w.trusts != 0) && (r.ring_z | r.ring_y << 1 | r.ring_x << 2) == w.rings;
+           r.trusts_copy == (w.trusts != 0) && (r.ring_z | r.ring_y << 1 | r.ring_x << 2) == w.rings &&
+           (r.fold_z | r.fold_y << 1 | r.fold_x << 2) == w.folds;
 }
 void show(const mmx_route& r)
 {
-    printf("    got family %d q16 %d copy %d trusts %d y %d rings %d layout %d path %d\n", r.family, r.q16, r.makes_copy,
-           r.trusts_copy, r.y_kernel, r.ring_z | r.ring_y << 1 | r.ring_x << 2, r.layout, r.path);
+    printf("    got family %d q16 %d copy %d trusts %d y %d rings %d folds %d layout %d path %d\n", r.family, r.q16, r.makes_copy,
+           r.trusts_copy, r.y_kernel, r.ring_z | r.ring_y << 1 | r.ring_x << 2, r.fold_z | r.fold_y << 1 | r.fold_x << 2,
+           r.layout, r.path);
 }
 
 struct row {
@@ -181,6 +187,22 @@ int check_table()
         {"the mixed ladder: 16-bit tiles, then the separate passes with a generic Y pass; two configurations", MMX_U16, 0,
          {40, 20, 40, 64, true, true, true}, A, 0, kBandQ16, {6, 18}, MMX_OK, 2, 0, true, false,
          {T16, {SEP, 0, MMX_Y_NONE, MMX_ZX_SEPARATE, 0, 5}}},
+        // ---- MMX_ZX_THIN by name: thin at the ladder's largest radius -> every scale the separate passes, folded where
+        // no ring kernel takes the pass, one configuration, no entries, no copy
+        {"thin by name, a shallow stack of 20 planes: Z folded from radius 17 on", MMX_U16, 0, {20, 261, 261, 288, true, true, true},
+         MMX_ZX_THIN, 0, kBandQ16, {8, 12, 20}, MMX_OK, 1, 0, false, false,
+         {{SEP, 0, MMX_Y_NONE, MMX_ZX_THIN, 0, 7, 0}, {SEP, 0, MMX_Y_NONE, MMX_ZX_THIN, 0, 7, 0}, {SEP, 0, MMX_Y_NONE, MMX_ZX_THIN, 0, 6, 1}}},
+        {"thin by name, a 2-D image", MMX_U8, 0, {1, 562, 562, 576, true, true, true}, MMX_ZX_THIN, 0, kBandQ16, {8, 24}, MMX_OK,
+         1, 0, false, false, {{SEP, 0, MMX_Y_NONE, MMX_ZX_THIN, 0, 6, 1}, {SEP, 0, MMX_Y_NONE, MMX_ZX_THIN, 0, 6, 1}}},
+        {"thin by name, a remainder 10 wide (x folded; it is shorter than the radius 12 the X ring kernel needs)", MMX_U16, 0,
+         {261, 261, 10, 32, true, true, true}, MMX_ZX_THIN, 0, kBandQ16, {8, 12}, MMX_OK, 1, 0, false, false,
+         {{SEP, 0, MMX_Y_NONE, MMX_ZX_THIN, 0, 7, 0}, {SEP, 0, MMX_Y_NONE, MMX_ZX_THIN, 0, 3, 4}}},
+        {"thin by name with wide radii: every pass folded above radius 24", MMX_F32, 0, {30, 40, 44, 64, true, true, true},
+         MMX_ZX_THIN, 0, kBandQ16, {31}, MMX_OK, 1, 0, false, false, {{SEP, 0, MMX_Y_NONE, MMX_ZX_THIN, 0, 0, 7}}},
+        {"thin by name on thick blocks: as MMX_ZX_AUTO", MMX_U16, 0, small, MMX_ZX_THIN, 0, kBandQ16, {4, 8, 12}, MMX_OK, 1,
+         QUADS, true, true, {T16, T16, T16}},
+        {"... and with wide radii the laid-out ladder of MMX_ZX_AUTO", MMX_U16, 0, {40, 48, 64, 64, true, true, false},
+         MMX_ZX_THIN, 0, kBandQ16, {24, 25, 26}, MMX_OK, 1, ROWS, false, false, {P, W, W}},
     };
     int bad = 0;
     for (size_t i = 0; i < table.size(); ++i) {
@@ -244,6 +266,80 @@ int check_by_name(const char* path)
     return bad + (n == 0);
 }
 
+// ---- single calls of MMX_ZX_THIN by name, on thin and on thick blocks: the rows tests/test_gpu_thin.py runs through
+// mmx_log_batch_f32.  A line: nz ny nx dtype radius entries | family rings folds layout path  (value_range 0, the wide
+// band, the plan and both entry layouts fit)
+int check_thin_table(const char* path)
+{
+    FILE* f = fopen(path, "r");
+    if (!f) { printf("cannot open %s\n", path); return 1; }
+    char line[256];
+    int bad = 0, n = 0;
+    while (fgets(line, sizeof line, f)) {
+        if (line[0] == '#' || line[0] == '\n') continue;
+        int nz, ny, nx, dtype, radius, entries, family, rings, folds, layout, zx;
+        if (sscanf(line, "%d %d %d %d %d %d | %d %d %d %d %d", &nz, &ny, &nx, &dtype, &radius, &entries, &family, &rings, &folds,
+                   &layout, &zx) != 11 || radius < 0 || radius > MMX_MAX_RADIUS_GENERIC) {
+            printf("bad line: %s", line); ++bad; continue;
+        }
+        const geometry geo = {nz, ny, nx, (nx + MMX_ROW_ALIGN - 1) / MMX_ROW_ALIGN * MMX_ROW_ALIGN, true, true, true};
+        const mmx_batch_geom g = geom(geo);
+        const mmx_volume vol = volume(dtype, 0.f, geo);
+        double w0[kTab], w2[kTab], norm;
+        gauss(radius, w0, w2, &norm);
+        mmx_route r;
+        const int rc = mmx_route_scale(&vol, g, radius, w0, w2, norm, MMX_ZX_THIN, kBandQ16, entries != 0, &r);
+        const bool ok = rc == MMX_OK && r.family == family && (r.ring_z | r.ring_y << 1 | r.ring_x << 2) == rings &&
+                        (r.fold_z | r.fold_y << 1 | r.fold_x << 2) == folds && r.layout == layout && r.path == zx;
+        if (!ok) { printf("thin by name, MISMATCH (status %d): %s", rc, line); show(r); }
+        bad += !ok; ++n;
+    }
+    fclose(f);
+    printf("%d of %d thin by-name rows mismatched\n", bad, n);
+    return bad + (n == 0);
+}
+
+// ---- the folded operator (csrc/mmx_fold.h) for every extent the kernels fold and radius 1 .. 64: each row against the
+// taps reflected one by one (mmx_reflect, summed in double) to one float32 ulp of the matrix's largest entry, its sum
+// against the sum of the taps, and the matrix against its transpose (the operator is symmetric; the two entries are
+// summed in opposite orders)
+int sweep_fold()
+{
+    long entries = 0, bad = 0;
+    std::vector<float> m((size_t)MMX_FOLD_MAX_N * MMX_FOLD_MAX_N);
+    std::vector<double> ref((size_t)MMX_FOLD_MAX_N * MMX_FOLD_MAX_N);
+    for (int radius = 1; radius <= MMX_MAX_RADIUS_WIDE; ++radius) {
+        double w0[kTab], w2[kTab], norm;
+        gauss(radius, w0, w2, &norm);
+        for (const double* wd : {w0, w2}) {
+            float w[kTab];
+            double sum = 0.0;
+            for (int k = 0; k <= radius; ++k) { w[k] = (float)wd[k]; sum += (k ? 2.0 : 1.0) * (double)w[k]; }
+            for (int n = 1; n <= MMX_FOLD_MAX_N; ++n) {
+                mmx_fold_matrix_host(w, radius, n, m.data());
+                double top = 0.0;
+                for (int i = 0; i < n; ++i) {
+                    for (int j = 0; j < n; ++j) ref[(size_t)i * n + j] = 0.0;
+                    for (int k = -radius; k <= radius; ++k) ref[(size_t)i * n + mmx_reflect(i + k, n)] += (double)w[k < 0 ? -k : k];
+                    for (int j = 0; j < n; ++j) top = fmax(top, fabs(ref[(size_t)i * n + j]));
+                }
+                const double ulp = (double)nextafterf((float)top, INFINITY) - (double)(float)top;
+                for (int i = 0; i < n; ++i) {
+                    double row = 0.0;
+                    for (int j = 0; j < n; ++j, ++entries) {
+                        row += (double)m[(size_t)i * n + j];
+                        if (fabs((double)m[(size_t)i * n + j] - ref[(size_t)i * n + j]) > ulp) ++bad;
+                        if (fabs((double)m[(size_t)i * n + j] - (double)m[(size_t)j * n + i]) > ulp) ++bad;
+                    }
+                    if (fabs(row - sum) > 1e-6 * fmax(1.0, fabs(sum)) + n * ulp) ++bad;
+                }
+            }
+        }
+    }
+    printf("fold: %ld matrix entries, %ld failures\n", entries, bad);
+    return bad != 0;
+}
+
 // ---- the sweep
 int sweep()
 {
@@ -255,7 +351,7 @@ int sweep()
     const int ext[] = {1, 12, 29, 80};
     const int wide[] = {1, 24, 28, 64, 320, 321, 512, 513, 2048, 2049};
     const int modes[] = {MMX_ZX_AUTO, MMX_ZX_SEPARATE, MMX_ZX_PACKED, MMX_ZX_TILED, MMX_ZX_TILED_Q16, MMX_ZX_WIDE,
-                         MMX_ZX_TILED | MMX_ZX_PREPACKED, MMX_ZX_TILED_Q16 | MMX_ZX_PREPACKED, -2, 1, 3, 4, 5, 9};
+                         MMX_ZX_TILED | MMX_ZX_PREPACKED, MMX_ZX_TILED_Q16 | MMX_ZX_PREPACKED, MMX_ZX_THIN, -2, 1, 3, 4, 5, 10};
     const int flags[] = {0, MMX_ZX_Y_VALU};
     struct vox { int dtype; float vrange; };
     const vox voxels[] = {{MMX_U8, 0}, {MMX_U16, 0}, {MMX_F32, 0}, {MMX_F32, 1.f}};         // (every other ranged one: [-3, 3])
@@ -277,6 +373,10 @@ int sweep()
                 if (mmx_packed_accepts(&vol, g, radius) && !mmx_fused_accepts(&vol, g, radius)) ++refused;
                 if (mmx_tiled_accepts(&vol, g, radius) && !mmx_fused_accepts(&vol, g, radius)) ++refused;
                 if (mmx_fused_accepts(&vol, g, radius) && (!mmx_ring_radius(radius) || !mmx_wide_accepts(&vol, g, radius))) ++refused;
+                // thin is what sends a column pass off its ring kernel; the fused path is not for thin batches
+                if (mmx_thin_accepts(g, radius) && mmx_fused_accepts(&vol, g, radius) && g.min_nz >= radius + MMX_COL_PREFETCH &&
+                    g.min_nx >= radius + MMX_COL_PREFETCH) ++refused;
+                if (valid && mmx_ring_radius(radius) && !mmx_thin_accepts(g, radius) && !mmx_ypass_accepts(g, radius)) ++refused;
                 // radii -1 .. 30 and the edges of the wide and generic ranges meet every mode, the others one mode each
                 const bool every = radius <= 30 || (radius >= 63 && radius <= 66) || radius >= MMX_MAX_RADIUS_GENERIC - 1;
                 const int n_modes = (int)(sizeof modes / sizeof *modes);
@@ -310,7 +410,12 @@ int sweep()
                     else
                         ok = (!r.ring_z || (mmx_ring_radius(radius) && mmx_voxels_ok(&vol) && mmx_zpass_accepts(&vol, g, radius))) &&
                              (!r.ring_y || mmx_ypass_accepts(g, radius)) &&
-                             (!r.ring_x || mmx_xpass_launch_accepts(g.max_nx, radius)) && r.layout == 0;
+                             (!r.ring_x || mmx_xpass_launch_accepts(g.max_nx, radius)) && r.layout == 0 &&
+                             // the folded passes: by name on a thin batch only, and then every pass no ring kernel takes
+                             (r.path == MMX_ZX_THIN ? mode == MMX_ZX_THIN && mmx_thin_accepts(g, radius) &&
+                                                      r.fold_z == !r.ring_z && r.fold_y == !r.ring_y && r.fold_x == !r.ring_x
+                                                    : !(r.fold_z || r.fold_y || r.fold_x));
+                    if (r.family != SEP && (r.fold_z || r.fold_y || r.fold_x || r.path == MMX_ZX_THIN)) ok = false;
                     ok = ok && (r.layout == 0 || entries) && (r.layout != MMX_MASK_ROWS || g.rows_fit) &&
                          (r.layout != MMX_MASK_QUADS || g.quads_fit);
                     if (!ok) { if (++refused < 10) { printf("refused: %d x %d x %d r %d mode %d\n", nz, ny, nx, radius, zx_mode); show(r); } }
@@ -325,6 +430,7 @@ int sweep()
                     const bool agree = lrc == MMX_OK && lad.n_configs == 1 && lr.family == r.family && lr.q16 == r.q16 &&
                                        lr.y_kernel == r.y_kernel && lr.layout == r.layout && lr.path == r.path &&
                                        lr.ring_z == r.ring_z && lr.ring_y == r.ring_y && lr.ring_x == r.ring_x &&
+                                       lr.fold_z == r.fold_z && lr.fold_y == r.fold_y && lr.fold_x == r.fold_x &&
                                        lad.layout == r.layout && lad.zx_path == r.path &&
                                        // (the copy: the batch's, trusted, where the ladder makes one; else as the call has it)
                                        lr.trusts_copy == (lr.family == TIL && (lad.copy || r.trusts_copy)) &&
@@ -334,7 +440,7 @@ int sweep()
             }
             // ladders of three radii around every limit: how often is the MMX_ZX_PACKED re-route (rows and quads mixed) taken?
             const int32_t trios[][3] = {{4, 8, 12}, {8, 24, 25}, {20, 24, 28}, {6, 18, 30}, {24, 64, 65}, {1, 2, 3}};
-            for (const auto& t : trios) for (int mode : {MMX_ZX_AUTO, MMX_ZX_TILED, MMX_ZX_TILED_Q16, MMX_ZX_PACKED, MMX_ZX_WIDE}) {
+            for (const auto& t : trios) for (int mode : {MMX_ZX_AUTO, MMX_ZX_TILED, MMX_ZX_TILED_Q16, MMX_ZX_PACKED, MMX_ZX_WIDE, MMX_ZX_THIN}) {
                 const ladder_in in(std::vector<int32_t>(t, t + 3));
                 mmx_route lr[3];
                 mmx_ladder_route lad;
@@ -407,6 +513,8 @@ int main(int argc, char** argv)
 {
     int bad = check_table();
     bad += check_by_name(argc > 1 ? argv[1] : "tests/golden/route_by_name.txt");
+    if (argc > 2) bad += check_thin_table(argv[2]);
+    bad += sweep_fold();
     bad += sweep_entries();
     bad += sweep();
     return bad ? 1 : 0;

@@ -1,0 +1,253 @@
+#!/usr/bin/env python
+"""What a thin remainder costs, and what the folded passes give: this tree against another checkout of the project
+(the parent commit's, built), in ONE run, the two alternating repeat by repeat (the scheme of tools/widerowbench.py).
+
+    python tools/thinbench.py --parent-tree /path/to/parent/checkout --repeats 5 --out profiles/r11_thin.json
+
+One GPU, the benchmark's default profile (bench.py, c3: sigma factors 3 .. 5 in 5 scales at 1 um / px -- radii 12 .. 20,
+so a block is thin below 24 voxels --, threshold 0.1, segment_size 256), resident uint16 volumes, a step = what
+``stack_detect.detect_blobs_blocks`` does between loading the image and writing its files (detection of all blocks, the
+stack's pruning, the final table):
+  a_exact   1024 x 2048 x 2048: divides exactly into blocks (this tree only: the yardstick and its run-to-run spread);
+  a_ragged  1024 x 2048 x 2058: a ninth column of blocks 10 voxels wide;
+  b_shallow   20 x  512 x 1024: 8 blocks of 20 x 261 x 261 (the last of a row or column: 256), every one thin in z;
+  b_2d         1 x 4456 x 4456 at segment_size 557: 64 blocks of 1 x 562 x 562 (the last: 557), a 2-D image.
+Per case and tree: wall milliseconds per step after warm-up (median, min, max), nanoseconds per voxel, the batches of a
+step (blocks, mode asked for, path reported), kernel milliseconds by family -- for a_ragged also those of the thin
+batches alone, from one extra step that waits after every batch -- and a digest of the final table, which must be equal
+between the trees.
+
+Required of a_ragged: its time per voxel in this tree lies within the exact volume's (its slowest repeat) plus the thin
+batches' own kernel time.  Of b_*: not slower than the parent beyond the parent's spread.  The ratios are recorded.
+
+Each tree runs in a worker process of its own (``--worker``, importing the package from its tree), both alive for the
+whole run; a worker that dies ends the run."""
+import argparse
+import hashlib
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+PROFILE = dict(min_sigma_factor=3, max_sigma_factor=5, num_sigma=5, detection_threshold=0.1, overlap=0.5,
+               exclude_border=None, segment_size=256, denoise_size=None, prune_tol_factor=(1, 1, 1), isotropic=None)
+#: name -> (volume shape, segment_size, trees that run it)
+CASES = {
+    "a_exact": ((1024, 2048, 2048), 256, ("new",)),
+    "a_ragged": ((1024, 2048, 2058), 256, ("parent", "new")),
+    "b_shallow": ((20, 512, 1024), 256, ("parent", "new")),
+    "b_2d": ((1, 4456, 4456), 557, ("parent", "new")),
+}
+
+
+# ---------------------------------------------------------------------------------------------------------- worker
+def worker(tree):
+    sys.path.insert(0, tree)
+    import numpy as np
+    import torch
+    from magellanmapper_amd import _native as nat
+    from magellanmapper_amd import blob_log as bl, config, detector, stack_detect, synth
+    assert os.path.abspath(os.path.dirname(os.path.dirname(bl.__file__))) == os.path.abspath(tree)
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    nat.keep_host_heap()
+    free = torch.cuda.mem_get_info()[0]
+    state = {}
+
+    def setup(name):
+        if state.get("name") == name:
+            return
+        state.clear()
+        bl.release_buffers()
+        torch.cuda.empty_cache()
+        shape, seg, _ = CASES[name]
+        config.setup_roi_profiles(None)
+        config.roi_profile.update(dict(PROFILE, segment_size=seg))
+        config.resolutions = np.array([[1.0, 1.0, 1.0]])
+        vol = synth.make_volume_device(shape, 3, dev)
+        state.update(name=name, dvol=bl.DeviceVolume(vol), blk=stack_detect.setup_blocks(config.roi_profile, shape))
+        bl.BUDGET_BYTES = min(24 << 30, max(1 << 30, (free - vol.numel() * 2) // 3))
+
+    def step():
+        dvol, blk = state["dvol"], state["blk"]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        stack_detect.StackDetector.plan_pruning(blk.overlap, blk.tol, blk.overlap_padding, [0])
+        seg = stack_detect.StackDetector.detect_blobs_sub_rois(None, dvol, blk.sub_roi_slices, blk.sub_rois_offsets,
+                                                               blk.denoise_max_shape, blk.exclude_border, False, [0])
+        pruned, _ = stack_detect.StackPruner.prune_blobs_mp(dvol, seg, blk.overlap, blk.tol, blk.sub_roi_slices,
+                                                            blk.sub_rois_offsets, [0], blk.overlap_padding, untouched=True,
+                                                            final_form=True, n_flag_cols=0)
+        torch.cuda.synchronize()
+        ms = (time.perf_counter() - t0) * 1e3
+        if pruned is None:
+            return ms, np.zeros((0, 0))
+        if isinstance(pruned, stack_detect._FinalTable):
+            return ms, np.array(pruned.view(np.ndarray))
+        bb = detector.Blobs(pruned)
+        bb.replace_rel_with_abs_blob_coords(pruned)
+        return ms, np.asarray(bb.remove_abs_blob_coords(True))
+
+    def describe():
+        """One step that waits after every batch: the batches, and the kernel time of the thin ones apart."""
+        batches, kinds, thin_kinds = [], {}, {}
+        enqueue = bl._enqueue_detect
+
+        def spy(dvol, lane, origins, shapes, *a, **k):
+            out = enqueue(dvol, lane, origins, shapes, *a, **k)
+            mode = k.get("zx_mode")
+            batches.append(dict(blocks=len(shapes), min_extent=[int(min(s[i] for s in shapes)) for i in range(3)],
+                                mode=mode, path=int(bl.LAST_ZX_PATH)))
+            out.done.synchronize()
+            torch.cuda.synchronize()
+            for fam, (ms, n) in nat.timing_read().items():
+                if n:
+                    for into in ([kinds, thin_kinds] if mode is not None else [kinds]):
+                        into[fam] = [into.get(fam, [0.0, 0])[0] + ms, into.get(fam, [0.0, 0])[1] + int(n)]
+            return out
+        bl._enqueue_detect = spy
+        nat.timing_enable(True)
+        try:
+            nat.timing_read()
+            _, table = step()
+        finally:
+            nat.timing_enable(False)
+            bl._enqueue_detect = enqueue
+        order = np.lexsort(tuple(table[:, i] for i in range(table.shape[1] - 1, -1, -1))) if table.size else []
+        digest = hashlib.sha1(np.ascontiguousarray(table[order]).tobytes()).hexdigest()
+        return dict(batches=batches, kinds=kinds, thin_kinds=thin_kinds, rows=int(len(table)), table_sha1=digest)
+
+    for line in sys.stdin:
+        req = json.loads(line)
+        if req["cmd"] == "quit":
+            break
+        setup(req["case"])
+        rep = describe() if req["cmd"] == "describe" else dict(ms=step()[0])
+        sys.stdout.write(json.dumps(rep) + "\n")
+        sys.stdout.flush()
+
+
+# ---------------------------------------------------------------------------------------------------------- driver
+class Worker:
+    def __init__(self, tree):
+        env = dict(os.environ)
+        env.pop("MMX_LIB_PATH", None)
+        self.p = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--worker", "--tree", os.path.abspath(tree)],
+                                  stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True, env=env, cwd=os.path.abspath(tree))
+
+    def ask(self, **req):
+        self.p.stdin.write(json.dumps(req) + "\n")
+        self.p.stdin.flush()
+        while True:
+            line = self.p.stdout.readline()
+            if not line:
+                raise RuntimeError("worker ended (exit status %s)" % self.p.wait())
+            if line.startswith("{"):
+                return json.loads(line)
+
+    def close(self):
+        try:
+            self.p.stdin.write('{"cmd": "quit"}\n')
+            self.p.stdin.close()
+            self.p.wait(timeout=60)
+        except Exception:
+            self.p.kill()
+
+
+def summarise(ms, voxels):
+    s = sorted(ms)
+    n = len(s)
+    med = s[n // 2] if n % 2 else 0.5 * (s[n // 2 - 1] + s[n // 2])
+    return dict(median_ms=med, min_ms=s[0], max_ms=s[-1], spread_ms=s[-1] - s[0], repeats=n, ms=ms,
+                ns_per_voxel=med * 1e6 / voxels, ns_per_voxel_max=s[-1] * 1e6 / voxels)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--tree", help=argparse.SUPPRESS)
+    ap.add_argument("--parent-tree", help="a checkout of the commit to compare against, its library built")
+    ap.add_argument("--parent-commit", default="", help="recorded in the output")
+    ap.add_argument("--commit", default="", help="recorded in the output (default: git rev-parse HEAD)")
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--cases", default=",".join(CASES))
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if args.worker:
+        return worker(args.tree)
+    if not args.parent_tree or not os.path.isdir(os.path.join(args.parent_tree, "magellanmapper_amd")):
+        ap.error("--parent-tree: the other checkout to measure against")
+    names = [c for c in args.cases.split(",") if c]
+    for c in names:
+        if c not in CASES:
+            ap.error("unknown case %s" % c)
+    commit = args.commit
+    if not commit:
+        try:
+            commit = subprocess.run(["git", "rev-parse", "HEAD"], cwd=ROOT, stdout=subprocess.PIPE, text=True).stdout.strip()
+        except OSError:
+            commit = ""
+    builds = {"parent": Worker(args.parent_tree), "new": Worker(ROOT)}
+    result = dict(command=" ".join([os.path.basename(sys.executable)] + sys.argv), commit=commit or "unknown",
+                  parent_commit=args.parent_commit or "unknown", profile={k: v for k, v in PROFILE.items()},
+                  warmup=args.warmup, cases={})
+    ok = True
+    try:
+        for c in names:
+            shape, seg, trees = CASES[c]
+            voxels = shape[0] * shape[1] * shape[2]
+            rec = dict(shape=shape, segment_size=seg, voxels=voxels)
+            for b in trees:
+                rec[b] = builds[b].ask(cmd="describe", case=c)              # (also the first warm-up step)
+            for _ in range(args.warmup):
+                for b in trees:
+                    builds[b].ask(cmd="run", case=c)
+            times = {b: [] for b in trees}
+            for _ in range(args.repeats):                                   # parent, new, parent, new, ...
+                for b in trees:
+                    times[b].append(builds[b].ask(cmd="run", case=c)["ms"])
+            for b in trees:
+                rec[b].update(summarise(times[b], voxels))
+            n = rec["new"]
+            line = "%-9s new %9.2f ms [%.2f .. %.2f] %.4f ns/voxel" % (c, n["median_ms"], n["min_ms"], n["max_ms"], n["ns_per_voxel"])
+            if "parent" in trees:
+                p = rec["parent"]
+                rec["same_table"] = p["table_sha1"] == n["table_sha1"] and p["rows"] == n["rows"]
+                rec["speedup"] = p["median_ms"] / n["median_ms"]
+                rec["not_slower_beyond_parent_spread"] = n["median_ms"] <= p["median_ms"] + p["spread_ms"]
+                ok = ok and rec["same_table"]
+                line += " | parent %9.2f ms [%.2f .. %.2f] | x%.2f | table %s (%d rows)" % (
+                    p["median_ms"], p["min_ms"], p["max_ms"], rec["speedup"], "equal" if rec["same_table"] else "DIFFERS", n["rows"])
+            print(line, flush=True)
+            print("          new kernels %s" % {k: round(v[0], 2) for k, v in n["kinds"].items()}, flush=True)
+            if "parent" in trees:
+                print("          parent kernels %s" % {k: round(v[0], 2) for k, v in rec["parent"]["kinds"].items()}, flush=True)
+            result["cases"][c] = rec
+        if "a_exact" in result["cases"] and "a_ragged" in result["cases"]:
+            e, r = result["cases"]["a_exact"]["new"], result["cases"]["a_ragged"]
+            thin_ms = sum(v[0] for v in r["new"]["thin_kinds"].values())
+            allowed = e["ns_per_voxel_max"] + thin_ms * 1e6 / r["voxels"]
+            result["ragged_vs_exact"] = dict(
+                exact_ns_per_voxel=e["ns_per_voxel"], exact_ns_per_voxel_max=e["ns_per_voxel_max"],
+                ragged_ns_per_voxel=r["new"]["ns_per_voxel"], parent_ragged_ns_per_voxel=r["parent"]["ns_per_voxel"],
+                thin_batches_kernel_ms=thin_ms, allowed_ns_per_voxel=allowed, within=r["new"]["ns_per_voxel"] <= allowed,
+                parent_cliff=r["parent"]["ns_per_voxel"] / e["ns_per_voxel"])
+            print("ragged: %.4f ns/voxel (allowed %.4f: exact max %.4f + %.2f ms of thin batches); parent %.4f ns/voxel, x%.2f of "
+                  "the exact volume's" % (r["new"]["ns_per_voxel"], allowed, e["ns_per_voxel_max"], thin_ms,
+                                          r["parent"]["ns_per_voxel"], result["ragged_vs_exact"]["parent_cliff"]), flush=True)
+    finally:
+        for w in builds.values():
+            w.close()
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(result, f, indent=1, sort_keys=True)
+            f.write("\n")
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
