@@ -881,6 +881,24 @@ int mmx_host_finish_stack(const mmx_finish_stack_args* a);
 int mmx_cdist_f64(const double* d_a, int64_t n, const double* d_b, int64_t m, int dim, double* d_out, void* stream);
 int mmx_host_lsap(const double* cost, int64_t nr, int64_t nc, int64_t* out_rows, int64_t* out_cols);
 
+/* ---- K1: the patches the blob classifier reads (added to ABI v21 without a version step, like mmx_fold_parts: a
+ * library without it lacks the symbol, which callers check for)
+ * replaces: the per-blob loop of classifier.extract_patches (magmap/cv/classifier.py:16-55): for every blob the 2-D patch
+ *     roi[z, y - size/2 : y + ceil(size/2), x - size/2 : x + size/2]   (size rows, 2 * (size / 2) columns: an odd size
+ *     gives one column less than rows, as the reference does)
+ * divided by its own maximum -- in float64 for uint8 / uint16 / float64 voxels and in float32 for float32 voxels, as
+ * NumPy's true divide does; the maximum propagates NaN like np.max, an all-zero patch gives NaN (0 / 0).  Bit-equal.
+ *   vol      : one channel, any mmx_dtype, any strides (a channel of a (z, y, x, c) image in place)
+ *   d_zyx    : [n][3] int32 blob coordinates in the volume
+ *   d_out    : NULL or out [n][size][2 * (size / 2)], float32 for float32 voxels and float64 otherwise
+ *   d_out32  : NULL or out, the same shape: float32(quotient), what a float32 model is fed
+ * PRECONDITION (the caller's: the launcher cannot see device coordinates): every patch lies inside the volume,
+ *     0 <= z < nz, size/2 <= y <= ny - ceil(size/2), size/2 <= x <= nx - size/2.
+ * MMX_ERR_ARG for a null volume, size < 2 or size > MMX_PATCH_MAX_SIZE; n = 0 or both outputs NULL: nothing to do. */
+#define MMX_PATCH_MAX_SIZE 4096
+int mmx_extract_patches(const mmx_volume* vol, const int32_t* d_zyx, int64_t n, int size, void* d_out, float* d_out32,
+                        void* stream);
+
 /* PMC calibration (tools/pmc_calib.py): one streaming launch over n_elems elements with a known
  * byte count.  kind 0: float copy, 4 B per lane; 1: float copy, 16 B per lane; 2: uint16 read. */
 int mmx_calib_stream(int kind, const void* d_in, void* d_out, int64_t n_elems, void* stream);

@@ -37,6 +37,8 @@ MMX_FOLD_MAX_N = 68
 MMX_MASK_ROWS, MMX_MASK_QUADS = 1, 2
 MMX_MAX_BLOCKS = 65535
 MMX_COLOC_BALL = 33
+#: largest patch size ``mmx_extract_patches`` takes
+MMX_PATCH_MAX_SIZE = 4096
 
 #: NumPy mirror of ``mmx_block`` (32 bytes).
 BLOCK_DTYPE = np.dtype([("src_off", "<i8"), ("nz", "<i4"), ("ny", "<i4"), ("nx", "<i4"),
@@ -152,7 +154,7 @@ SYMBOLS = (
     "mmx_coloc_means", "mmx_coloc_voxels", "mmx_host_take_rows", "mmx_host_map_columns", "mmx_resize_batch_as", "mmx_gauss_axis_batch", "mmx_unmix_batch", "mmx_minmax_batch", "mmx_resize_batch",
     "mmx_cdist_f64", "mmx_host_lsap", "mmx_expand_probes", "mmx_fold_parts", "mmx_host_resolve_peaks", "mmx_host_overlap_prune",
     "mmx_host_emit_tables", "mmx_host_prune_region", "mmx_host_prune_parts", "mmx_host_rows_in_boxes", "mmx_host_append_rows", "mmx_host_emit_parts", "mmx_host_merge_parts_by_key", "mmx_host_gather_parts_by_key", "mmx_host_emit_tables_multi", "mmx_host_coloc_flags", "mmx_host_finish_stack", "mmx_copy_rect_h2d", "mmx_host_stage_upload", "mmx_host_stage_upload_pitched", "mmx_event_query",
-    "mmx_order_stats_workspace", "mmx_order_stats",
+    "mmx_order_stats_workspace", "mmx_order_stats", "mmx_extract_patches",
 )
 KERNEL_KINDS = ("zpass", "ypass", "xpass", "generic", "peaks", "rescore", "overlap_pairs",
                 "close_pairs", "zxpass", "y2pass", "preproc", "coloc", "zxpack", "widepass")
@@ -296,6 +298,8 @@ def lib() -> ctypes.CDLL:
     L.mmx_order_stats_workspace.restype = ctypes.c_size_t
     L.mmx_order_stats.argtypes = [POINTER(Volume), c_int64, c_int64, c_int64, vp, vp, c_int, vp, vp, vp, ctypes.c_size_t, vp]
     L.mmx_order_stats.restype = c_int
+    L.mmx_extract_patches.argtypes = [POINTER(Volume), vp, c_int64, c_int, vp, vp, vp]
+    L.mmx_extract_patches.restype = c_int
     L.mmx_preprocess_batch.restype = c_int
     L.mmx_preprocess_batch_mode.restype = c_int
     L.mmx_preprocess_batch_generic.restype = c_int

@@ -36,6 +36,24 @@ save_subimg: bool = False
 truth_db_mode = None
 grid_search_profile = None
 
+
+class ClassifierData:
+    """Settings of the blob classifier (reference config.py ``ClassifierData``): ``model``, the path of the model
+    whose scores go into the ``confirmed`` column (a TorchScript archive here, see :mod:`.classifier`; ``None``: no
+    classification), and ``include``, the classes viewers show (kept for the reference's callers, not read here)."""
+
+    def __init__(self, model: Optional[str] = None, include=None):
+        self.model = model
+        self.include = include
+
+
+#: the classifier's settings; ``detect_blobs_stack`` classifies the detected blobs when ``classifier.model`` is set
+classifier = ClassifierData()
+#: the main image (``Image5d``) and blobs of the reference's CLI; nothing here sets them, and only the defaults of
+#: ``classifier.ClassifyImage.classify_whole_image`` read them
+img5d = None
+blobs = None
+
 #: default (channel 0) profile and the per-channel list
 roi_profile = None
 roi_profiles: List = []

@@ -956,10 +956,28 @@ def _combine_arrs(arrs):
     return arrs[0] if len(arrs) == 1 else np.concatenate(arrs)
 
 
+def _classify_detected(image5d, channels, blobs_all) -> None:
+    """The classifier hook of ``detect_blobs_stack`` (reference :599-605): with ``config.classifier.model`` set, the
+    patch classifier fills the ``confirmed`` column of the combined table before it is archived; without a model
+    ``classify_whole_image`` raises ``FileNotFoundError`` and the table stays as it is.  It reads the image of THIS call
+    (the reference reads ``config.img5d``, which its CLI has set to the same image).  ``channels`` is the first entry of
+    the list the detection looped over: the list of all channels when they share their block settings, else the int of
+    the first channel -- over which the reference's ``for chl in channels`` raises ``TypeError`` after a finished
+    detection; here the int is the one-element list (the one deliberate deviation)."""
+    from . import classifier
+    if not isinstance(channels, (list, tuple, range)):
+        channels = [channels]
+    try:
+        classifier.ClassifyImage.classify_whole_image(image5d=image5d, channels=channels, blobs=blobs_all)
+    except FileNotFoundError as e:
+        _logger.debug(e)
+
+
 def detect_blobs_stack(filename_base: str, img5d, subimg_offset=None, subimg_size=None,
                        coloc: bool = False):
     """Detect blobs in a whole image; channels whose profiles agree on
     ``ROIProfile.BLOCK_SIZES`` share one set of blocks, others get their own (:554-561).
+    With ``config.classifier.model`` set the detected blobs are classified (``_classify_detected``).
     Saves ``<base>_blobs.npz``."""
     if img5d is None or img5d.img is None:
         raise IOError("No image data available for blob detection")
@@ -982,6 +1000,8 @@ def detect_blobs_stack(filename_base: str, img5d, subimg_offset=None, subimg_siz
         blobs_all.colocalizations = _combine_arrs([o[2].colocalizations for o in outs])
         if blobs_all.blobs is not None:
             detector.Blobs.show_blobs_per_channel(blobs_all.blobs)
+        if channels and blobs_all.blobs is not None:
+            _classify_detected(img5d.img, channels[0], blobs_all)
         from . import dist
         if dist.rank() == 0:
             blobs_all.save_archive()

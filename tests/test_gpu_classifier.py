@@ -1,0 +1,252 @@
+"""The blob classifier on the device: ``mmx_extract_patches`` bit for bit against the real reference
+(``tests/golden/classifier.npz``) and the host statement of the formula, whole-image classification through a TorchScript
+model that involves no arithmetic (resident, in plane chunks, in small batches), and the hook of ``detect_blobs_stack``."""
+import numpy as np
+import pytest
+
+from conftest import load_golden
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+SIZES = (16, 5, 2)
+COLS = ["z", "y", "x", "radius", "confirmed", "truth", "channel", "region"]
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    if not torch.cuda.is_available():
+        pytest.fail("GPU tests need a GPU: torch.cuda.is_available() is False")
+    return torch.device("cuda", 0)
+
+
+@pytest.fixture(scope="module")
+def gold():
+    g = load_golden("classifier.npz")
+    return {k: g[k] for k in g.files}
+
+
+class CentreModule(torch.nn.Module):
+    """Score = the centre voxel of the patch, ``x[:, 0, H // 2, W // 2]``: no arithmetic, so comparisons are exact."""
+
+    def forward(self, x):
+        return x[:, 0, x.shape[2] // 2, x.shape[3] // 2]
+
+
+@pytest.fixture(scope="module")
+def model_path(tmp_path_factory):
+    path = str(tmp_path_factory.mktemp("model") / "centre.pt")
+    torch.jit.script(CentreModule()).save(path)
+    return path
+
+
+def crop_image(gold, name):
+    """``(image, channel)`` a ``patches_<name>_<size>`` array of the fixture was cut from."""
+    if name == "u16":
+        return gold["vol"][:12], None
+    if name == "u16c1":
+        return np.stack((gold["vol"][:12], gold["vol_ch1"][:12]), axis=-1), 1
+    return gold["crop_" + name], None
+
+
+def blobs_of(gold):
+    from magellanmapper_amd import detector
+    return detector.Blobs(gold["table"].copy(), cols=COLS)
+
+
+@pytest.mark.parametrize("size", SIZES)
+@pytest.mark.parametrize("name", ["u16", "u8", "f32", "f64", "u16c1"])
+def test_kernel_patches_equal_the_reference_bit_for_bit(gpu, gold, name, size):
+    """All four voxel types, a strided channel of an interleaved image, sizes 16, 5 (the odd-size x extent) and 2;
+    patches against the y / x limits of the image, all-zero patches (0 / 0) and NaN voxels; 43 patches = 10 workgroups of
+    4 waves and 3 more; the float32 model copy is ``float32(quotient)``."""
+    from magellanmapper_amd import blob_log as bl, classifier
+    img, channel = crop_image(gold, name)
+    table = gold["crop_table"]
+    want = gold["patches_%s_%d" % (name, size)]
+    host = classifier.extract_patches(img if channel is None else img[..., channel], table, size)
+    np.testing.assert_array_equal(host, want)
+    dvol = bl.DeviceVolume(img)
+    got = classifier.extract_patches(dvol, table, size, channel=channel)
+    assert got.device.type == "cuda" and tuple(got.shape) == want.shape and len(table) % 4 == 3
+    got = got.cpu().numpy()
+    assert got.dtype == want.dtype
+    np.testing.assert_array_equal(got, want)
+    np.testing.assert_array_equal(np.isnan(got), np.isnan(want))
+    assert np.isnan(want).any()
+    zyx = table[:, :3].astype(int)
+    ref, f32 = classifier._patches_device(dvol, channel or 0, zyx, size, ref=True, f32=True)
+    np.testing.assert_array_equal(ref.cpu().numpy(), want[..., 0])
+    np.testing.assert_array_equal(f32.cpu().numpy(), want[..., 0].astype(np.float32))
+    only32 = classifier._patches_device(dvol, channel or 0, zyx, size, ref=False, f32=True)
+    assert only32[0] is None
+    np.testing.assert_array_equal(only32[1].cpu().numpy(), want[..., 0].astype(np.float32))
+    # one patch; a device tensor in place of the volume
+    for r in (0, len(table) - 1):
+        one = classifier.extract_patches(dvol, table[r:r + 1], size, channel=channel).cpu().numpy()
+        np.testing.assert_array_equal(one, want[r:r + 1])
+    if channel is None:
+        t = classifier.extract_patches(dvol.tensor, table[:5], size)
+        np.testing.assert_array_equal(t.cpu().numpy(), want[:5])
+
+
+@pytest.mark.parametrize("size", SIZES)
+def test_kernel_patches_of_the_whole_volume_and_of_a_box_of_planes(gpu, gold, size):
+    """Every interior blob of the 230-plane volume, rim positions included; the same from a volume that holds planes
+    [90, 130) only and answers for the whole image (what a plane chunk is)."""
+    from magellanmapper_amd import blob_log as bl, classifier
+    vol, table = gold["vol"], gold["table"]
+    rows = table[gold["interior_%d" % size]]
+    want = gold["patches_vol_%d" % size]
+    got = classifier.extract_patches(bl.DeviceVolume(vol), rows, size).cpu().numpy()
+    np.testing.assert_array_equal(got, want)
+    box = bl.DeviceVolume(vol[90:130], z_off=90, full_shape=vol.shape)
+    inside = (rows[:, 0] >= 90) & (rows[:, 0] < 130)
+    assert inside.sum() >= 5
+    np.testing.assert_array_equal(classifier.extract_patches(box, rows[inside], size).cpu().numpy(), want[inside])
+    with pytest.raises(ValueError, match="leaves planes"):
+        classifier.extract_patches(box, rows, size)
+
+
+def test_a_patch_that_leaves_the_volume_is_refused_before_the_launch(gpu, gold):
+    from magellanmapper_amd import blob_log as bl, classifier
+    dvol = bl.DeviceVolume(gold["vol"][:12])
+    for row, size in (((0, 7, 8), 16), ((0, 8, 29), 16), ((12, 8, 8), 16), ((-1, 8, 8), 16), ((0, 38, 2), 5),
+                      ((0, 2, 35), 5), ((0, 40, 1), 2), ((0, 1, 0), 2)):
+        with pytest.raises(ValueError, match="leaves"):
+            classifier.extract_patches(dvol, np.array([[3, 20, 20], row], dtype=float), size)
+    two = bl.DeviceVolume(np.stack((gold["vol"][:12], gold["vol_ch1"][:12]), axis=-1))
+    with pytest.raises(ValueError, match="channel"):
+        classifier.extract_patches(two, np.array([[3, 20, 20]]), 16)
+    with pytest.raises(ValueError, match="channel"):
+        classifier.extract_patches(two, np.array([[3, 20, 20]]), 16, channel=2)
+
+
+CASES = [("confirmed_16", 16, False, [0]), ("confirmed_5", 5, False, [0]), ("confirmed_16_ch1", 16, True, [1])]
+
+
+def _whole(gold, model, key, size, two, channels, image=None):
+    from magellanmapper_amd import classifier
+    img = np.stack((gold["vol"], gold["vol_ch1"]), axis=-1) if two else gold["vol"]
+    blobs = blobs_of(gold)
+    classifier.ClassifyImage.classify_whole_image(model, img[None] if image is None else image(img), channels, blobs,
+                                                  patch_size=size)
+    np.testing.assert_array_equal(blobs.blobs[:, 4], gold[key])
+    rest = np.delete(np.arange(8), 4)
+    np.testing.assert_array_equal(blobs.blobs[:, rest], gold["table"][:, rest])
+
+
+@pytest.mark.parametrize("key, size, two, channels", CASES)
+def test_whole_image_gives_the_reference_column(gpu, gold, model_path, key, size, two, channels, monkeypatch):
+    from magellanmapper_amd import blob_log as bl, classifier
+    calls = []
+    real = classifier._patches_device
+    monkeypatch.setattr(classifier, "_patches_device", lambda *a, **k: calls.append(len(a[2])) or real(*a, **k))
+    _whole(gold, model_path, key, size, two, channels)
+    assert len(calls) == 1                                          # one launch per channel over all selected blobs
+    _whole(gold, model_path, key, size, two, channels, image=lambda img: bl.DeviceVolume(img))      # a resident image
+
+
+@pytest.mark.parametrize("key, size, two, channels", CASES)
+def test_whole_image_in_plane_chunks_and_small_batches(gpu, gold, model_path, key, size, two, channels, monkeypatch):
+    from magellanmapper_amd import classifier, stack_detect
+    img = np.stack((gold["vol"], gold["vol_ch1"]), axis=-1) if two else gold["vol"]
+    monkeypatch.setattr(stack_detect, "MAX_RESIDENT_BYTES", img.nbytes // 2)
+    chunks = classifier._plane_chunks(img, stack_detect._resident_limit())
+    assert len(chunks) >= 3 and chunks[0][0] == 0 and chunks[-1][1] == 230
+    assert all(a[1] == b[0] for a, b in zip(chunks, chunks[1:]))
+    seen = []
+    real = classifier._predict_device
+    monkeypatch.setattr(classifier, "_predict_device",
+                        lambda m, dvol, *a: seen.append((dvol.z_off, dvol.tensor.shape[0])) or real(m, dvol, *a))
+    _whole(gold, model_path, key, size, two, channels)
+    assert len(set(seen)) >= 3 and max(n for _, n in seen) < 230
+    monkeypatch.undo()
+    monkeypatch.setattr(classifier, "PATCH_BATCH", 7)
+    _whole(gold, model_path, key, size, two, channels)
+
+
+@pytest.fixture(scope="module")
+def stack():
+    from magellanmapper_amd import synth
+    return synth.make_volume(31, (64, 96, 96), 60)
+
+
+def _setup(config, monkeypatch, tmp_path, n_profiles=1):
+    monkeypatch.chdir(tmp_path)
+    config.setup_roi_profiles(["default"] * n_profiles)
+    for p in config.roi_profiles:
+        p.update(denoise_size=None, num_sigma=3, segment_size=40)
+    monkeypatch.setattr(config, "resolutions", np.array([[1.0, 1.0, 1.0]]))
+    monkeypatch.setattr(config, "filename", str(tmp_path / "stack.tif"))
+    monkeypatch.setattr(config, "channel", None)
+
+
+def _rim_rule(table, shape, size=16):
+    back = size // 2
+    return ((table[:, 0] >= 0) & (table[:, 0] < shape[0]) & (table[:, 1] >= back) & (table[:, 1] < shape[1] - back)
+            & (table[:, 2] >= back) & (table[:, 2] < shape[2] - back))
+
+
+def _host_confirmed(table, vol, rows, size=16):
+    """The ``confirmed`` column the centre model gives, from the host statement of the formula."""
+    from magellanmapper_amd import classifier
+    want = table[:, 4].copy()
+    x = classifier.extract_patches(vol, table[rows], size)
+    score = x[:, size // 2, size // 2, 0].astype(np.float32)
+    want[rows] = (score > 0.5).astype(int)
+    return want
+
+
+def test_the_hook_of_detect_blobs_stack(gpu, stack, model_path, tmp_path, monkeypatch):
+    """Without a model the table and the archive are what ``detect_blobs_blocks`` gives (the step before the hook);
+    with one the archive's ``confirmed`` column holds what the host path computes from that table: 0 / 1 inside the rim
+    rule, -1 outside."""
+    from magellanmapper_amd import config, detector, stack_detect
+    _setup(config, monkeypatch, tmp_path)
+    try:
+        img5d = stack_detect.Image5d(stack[None])
+        _, _, base = stack_detect.detect_blobs_blocks(config.filename, img5d, None, None, [0], False, False, False, False)
+        assert config.classifier.model is None
+        _, _, plain = stack_detect.detect_blobs_stack(config.filename, img5d)
+        np.testing.assert_array_equal(plain.blobs, base.blobs)
+        assert np.all(plain.blobs[:, 4] == -1) and len(plain.blobs) > 30
+        np.testing.assert_array_equal(detector.Blobs().load_blobs(plain.path).blobs, base.blobs)
+
+        monkeypatch.setattr(config.classifier, "model", model_path)
+        _, _, got = stack_detect.detect_blobs_stack(config.filename, img5d)
+        rows = _rim_rule(base.blobs, stack.shape)
+        assert 0 < rows.sum() < len(rows)
+        want = base.blobs.copy()
+        want[:, 4] = _host_confirmed(base.blobs, stack, rows)
+        np.testing.assert_array_equal(got.blobs, want)
+        arch = detector.Blobs().load_blobs(got.path)
+        np.testing.assert_array_equal(arch.blobs, want)
+        assert list(arch.cols) == COLS
+        assert set(np.unique(want[rows, 4])) <= {0.0, 1.0} and np.all(want[~rows, 4] == -1) and (want[:, 4] == 1).any()
+    finally:
+        config.setup_roi_profiles()
+
+
+def test_the_hook_with_channels_of_different_block_settings(gpu, stack, model_path, tmp_path, monkeypatch):
+    """Two channels with different ``segment_size`` are detected in separate groups, so the hook is handed the int 0:
+    channel 0 is classified, channel 1 keeps -1, nothing raises and the archive is written."""
+    from magellanmapper_amd import config, detector, stack_detect, synth
+    _setup(config, monkeypatch, tmp_path, n_profiles=2)
+    try:
+        config.roi_profiles[1].update(segment_size=30)
+        vol = np.stack((stack, synth.make_volume(32, stack.shape, 40)), axis=-1)
+        img5d = stack_detect.Image5d(vol[None])
+        _, _, plain = stack_detect.detect_blobs_stack(config.filename, img5d)
+        assert np.all(plain.blobs[:, 4] == -1) and set(np.unique(plain.blobs[:, 6])) == {0.0, 1.0}
+        monkeypatch.setattr(config.classifier, "model", model_path)
+        _, _, got = stack_detect.detect_blobs_stack(config.filename, img5d)
+        rows = _rim_rule(plain.blobs, stack.shape) & (plain.blobs[:, 6] == 0)
+        want = plain.blobs.copy()
+        want[:, 4] = _host_confirmed(plain.blobs, vol[..., 0], rows)
+        np.testing.assert_array_equal(got.blobs, want)
+        np.testing.assert_array_equal(detector.Blobs().load_blobs(got.path).blobs, want)
+        assert np.all(want[want[:, 6] == 1, 4] == -1) and (want[:, 4] >= 0).sum() == rows.sum() > 0
+    finally:
+        config.setup_roi_profiles()
