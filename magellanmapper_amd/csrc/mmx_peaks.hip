@@ -195,51 +195,60 @@ __device__ __forceinline__ float sparse_at(const sparse_ctx& k, int s, int z, in
     return k.c.base[(int64_t)s * k.c.sigma_stride + (int64_t)z * k.c.plane + y * k.c.px + x];
 }
 
-// check_voxel on the sparse cube (same decisions: a neighbour that is not stored is below thr - eps < v)
-__device__ __forceinline__ void check_voxel_sparse(const sparse_ctx& k, int s, int z, int y, int x, float v)
+// One group of 32 lanes tests one voxel that passed the pre-check against all 80 neighbours: lane l < 27 takes the row
+// (ds, dz, dy) = (l / 9 - 1, l / 3 % 3 - 1, l % 3 - 1), loads its (at most two) entries with the centre's value, then
+// its three values, all addresses clamped into the cube and every value load of a neighbour that is outside, the centre
+// or unstored pointed at the centre instead (a voxel that is certainly stored) -- two memory round trips per voxel.  The
+// group then reduces the maximum and the 80 band bits, and its first lane applies the rule and appends the row.
+// Same decisions as check_voxel on the stored cube: a neighbour that is not stored is below thr - eps < v.
+__device__ __forceinline__ void check_voxel_sparse_group(const sparse_ctx& k, int s, int z, int y, int x, int l)
 {
     const peak_ctx& c = k.c;
     const int nz = c.nz, ny = c.ny, nx = c.nx;
-    const float reject = v + c.eps;
-    const float band_lo = v - c.eps;       // a neighbour below this cannot out-vote the candidate whatever the exact values
-    float m = -INFINITY;
-    bool border = false;
+    const int ds = l / 9 - 1, dz = (l / 3) % 3 - 1, dy = l % 3 - 1;
+    const int ss = s + ds, zz = z + dz, yy = y + dy;
+    const bool row_ok = l < 27 && ss >= 0 && ss < c.ns && zz >= 0 && zz < nz && yy >= 0 && yy < ny;
+    const int sc = min(max(ss, 0), c.ns - 1), zc = min(max(zz, 0), nz - 1), yc = min(max(yy, 0), ny - 1);
+    const int xl = max(x - 1, 0), xr = min(x + 1, nx - 1);
+    const float* ctr = c.base + (int64_t)s * c.sigma_stride + (int64_t)z * c.plane + y * c.px + x;
+    const ulonglong2* er = k.ent + (int64_t)sc * k.ent_sigma_stride + (int64_t)yc * k.eg.per_row;
+    // the three x neighbours share at most two entries: the middle one lies in its left or its right neighbour's
+    const int el = mmx_entry_index(k.eg, zc, xl), em = mmx_entry_index(k.eg, zc, x), er_i = mmx_entry_index(k.eg, zc, xr);
+    const float v = *ctr;
+    const unsigned long long al = er[el].y;
+    const unsigned long long ar = er[er_i].y;
+    const unsigned long long am = em == el ? al : ar;
+    const float* row = c.base + (int64_t)sc * c.sigma_stride + (int64_t)zc * c.plane + yc * c.px;
+    const bool ok0 = row_ok && x > 0 && al != 0;
+    const bool ok1 = row_ok && l != 13 && am != 0;
+    const bool ok2 = row_ok && x + 1 < nx && ar != 0;
+    const float r0 = *(ok0 ? row + x - 1 : ctr);
+    const float r1 = *(ok1 ? row + x : ctr);
+    const float r2 = *(ok2 ? row + x + 1 : ctr);
+    const float u0 = ok0 ? r0 : -INFINITY, u1 = ok1 ? r1 : -INFINITY, u2 = ok2 ? r2 : -INFINITY;
+    float m = fmaxf(fmaxf(u0, u1), u2);
     // which of the 80 neighbours (C order of (ds, dz, dy, dx), the centre left out) lie in the band: the only ones
     // whose exact values the host needs when the candidate turns out contested
-    unsigned long long band = 0;
-    unsigned band_hi = 0;
-    for (int ds = -1; ds <= 1; ++ds) {
-        const int ss = s + ds;
-        if (ss < 0 || ss >= c.ns) { border = true; continue; }
-        for (int dz = -1; dz <= 1; ++dz) {
-            const int zz = z + dz;
-            if (zz < 0 || zz >= nz) { border = true; continue; }
-            for (int dy = -1; dy <= 1; ++dy) {
-                const int yy = y + dy;
-                if (yy < 0 || yy >= ny) { border = true; continue; }
-                // the three x neighbours share (at most two) entries and one row
-                const ulonglong2* er = k.ent + (int64_t)ss * k.ent_sigma_stride;
-                const float* row = c.base + (int64_t)ss * c.sigma_stride + (int64_t)zz * c.plane + yy * c.px;
+    const float band_lo = v - c.eps;       // a neighbour below this cannot out-vote the candidate whatever the exact values
+    unsigned b_lo = 0, b_mid = 0, b_hi = 0;     // bits 0..31, 32..63, 64..79
+    auto mark = [&](bool in, int j) __attribute__((always_inline)) {
+        j -= j > 40;
+        const unsigned bit = in ? 1u << (j & 31) : 0u;
+        if (j < 32) b_lo |= bit; else if (j < 64) b_mid |= bit; else b_hi |= bit;
+    };
+    mark(u0 >= band_lo, 3 * l);
+    mark(u1 >= band_lo, 3 * l + 1);
+    mark(u2 >= band_lo, 3 * l + 2);
 #pragma unroll
-                for (int dx = -1; dx <= 1; ++dx) {
-                    const int xx = x + dx;
-                    if (xx < 0 || xx >= nx) { border = true; continue; }
-                    if ((ds | dz | dy | dx) == 0) continue;
-                    if (er[sparse_entry(k, zz, yy, xx)].y) {
-                        const float u = row[xx];
-                        m = fmaxf(m, u);
-                        if (u >= band_lo) {
-                            int j = (((ds + 1) * 3 + (dz + 1)) * 3 + (dy + 1)) * 3 + (dx + 1);
-                            j -= j > 40;
-                            if (j < 64) band |= 1ull << j;
-                            else band_hi |= 1u << (j - 64);
-                        }
-                    }
-                }
-            }
-            if (m > reject) return;
-        }
+    for (int d = 16; d >= 1; d >>= 1) {
+        m = fmaxf(m, __shfl_xor(m, d, 32));
+        b_lo |= (unsigned)__shfl_xor((int)b_lo, d, 32);
+        b_mid |= (unsigned)__shfl_xor((int)b_mid, d, 32);
+        b_hi |= (unsigned)__shfl_xor((int)b_hi, d, 32);
     }
+    if (l != 0) return;
+    if (m > v + c.eps) return;              // a neighbour above this rules the voxel out
+    const bool border = s == 0 || s + 1 == c.ns || z == 0 || z + 1 == nz || y == 0 || y + 1 == ny || x == 0 || x + 1 == nx;
     if (border) m = fmaxf(m, 0.0f);  // mode='constant', cval = 0
     if (!(v >= m - c.eps)) return;
     const bool contested = !(v > m + c.eps) || !(v > c.thr + c.eps);
@@ -251,18 +260,22 @@ __device__ __forceinline__ void check_voxel_sparse(const sparse_ctx& k, int s, i
         r.z = z;
         r.y = y;
         r.x = x;
-        r.flags = (contested ? MMX_CAND_CONTESTED : 0u) | MMX_CAND_BAND | (band_hi << 16);
+        r.flags = (contested ? MMX_CAND_CONTESTED : 0u) | MMX_CAND_BAND | (b_hi << 16);
         r.v = v;
         r.nbr_max = m;
         r.v64 = __longlong_as_double(0x7ff8000000000000LL);
-        r.band = band;
+        r.band = ((unsigned long long)b_mid << 32) | b_lo;
         c.out[pos] = r;
     }
 }
 
-// One lane per entry and sigma: nearly all candidate words are zero; set bits are tested against z +- 1,
-// then sigma +- 1 (most of them are the in-plane maxima of the z-slices and scales of a blob and fall there),
-// survivors get the full 80-neighbour test.
+// One lane per entry and sigma: nearly all candidate words are zero.  The workgroup queues the set bits of its 2048
+// words in LDS and works the queue off in two stages, each with its loads in flight together instead of in a chain:
+//   1. one lane per queued bit: the voxel against z +- 1 and sigma +- 1 (the y and x neighbours were tested when the bit
+//      was set: most set bits are the in-plane maxima of the z-slices and scales of a blob and fall here) -- its value
+//      and the four entries in one round trip, the four values in a second;
+//   2. the few per cent that survive, queued again: a group of 32 lanes per voxel (check_voxel_sparse_group).
+// Either queue is worked off whenever it could not take what comes next, so a dense patch costs rounds, not correctness.
 __global__ void __launch_bounds__(MMX_WG)
 peaks_sparse_kernel(const float* __restrict__ log, const ulonglong2* __restrict__ entries,
                     int ns, int64_t sigma_stride, const mmx_block* __restrict__ blocks, int64_t slot_elems,
@@ -282,32 +295,59 @@ peaks_sparse_kernel(const float* __restrict__ log, const ulonglong2* __restrict_
     k.ent_sigma_stride = sigma_stride >> 5;
     const int64_t per_sigma = (int64_t)bd.ny * k.eg.per_row;
     const int64_t total = per_sigma * ns;
-    // Set bits are rare (a few per cent of the words hold one) and each costs a chain of dependent loads:
-    // a lane that walked the bits of its own word would leave the other 63 waiting.  So the workgroup first
-    // queues the set bits of 256 words in LDS, then every lane takes one queued bit.
-    constexpr int kQ = 1024;
+    constexpr int kQ = 1024;                // queued bits: (word index << 6) | bit
+    constexpr int kQ2 = 512;                // survivors of stage 1, the same items
     __shared__ unsigned long long q[kQ];
-    __shared__ int qn;
-    auto test_bit = [&](int64_t i, int b) __attribute__((always_inline)) {
-        const int s = (int)(i / per_sigma);
-        const int64_t r = i - (int64_t)s * per_sigma;
-        const int y = (int)(r / k.eg.per_row);
-        const int w = (int)(r - (int64_t)y * k.eg.per_row);
-        int z, x;
-        mmx_entry_voxel(k.eg, w, b, &z, &x);
-        if (x >= bd.nx || z >= bd.nz) return;
-        const float v = c.base[(int64_t)s * sigma_stride + (int64_t)z * c.plane + y * bd.px + x];
-        // (the y and x neighbours were tested when the bit was set: most set bits are the in-plane maxima of
-        // the z-slices and scales of a blob and fall to z +- 1 or sigma +- 1)
-        const float n0 = z > 0 ? sparse_at(k, s, z - 1, y, x) : -INFINITY;
-        const float n1 = z + 1 < bd.nz ? sparse_at(k, s, z + 1, y, x) : -INFINITY;
-        const float n2 = s > 0 ? sparse_at(k, s - 1, z, y, x) : -INFINITY;
-        const float n3 = s + 1 < ns ? sparse_at(k, s + 1, z, y, x) : -INFINITY;
-        if (fmaxf(fmaxf(n0, n1), fmaxf(n2, n3)) > v + eps) return;
-        check_voxel_sparse(k, s, z, y, x, v);
+    __shared__ unsigned long long q2[kQ2];
+    __shared__ int qn, q2n;
+    // word index and bit -> the voxel; false: a bit of a pitch column or of a plane past the block
+    auto voxel_of = [&](unsigned long long e, int* s, int* z, int* y, int* x) __attribute__((always_inline)) -> bool {
+        const int64_t i = (int64_t)(e >> 6);
+        *s = (int)(i / per_sigma);
+        const int64_t r = i - (int64_t)*s * per_sigma;
+        *y = (int)(r / k.eg.per_row);
+        const int w = (int)(r - (int64_t)*y * k.eg.per_row);
+        mmx_entry_voxel(k.eg, w, (int)(e & 63), z, x);
+        return *x < bd.nx && *z < bd.nz;
     };
-    if (threadIdx.x == 0) qn = 0;
-    for (int j = threadIdx.x; j < kQ; j += MMX_WG) q[j] = ~0ull;     // "no item"
+    // stage 1 on one queued item: true when the voxel goes on to stage 2
+    auto pre_check = [&](unsigned long long e) __attribute__((always_inline)) -> bool {
+        int s, z, y, x;
+        const bool real = voxel_of(e, &s, &z, &y, &x);
+        z = min(z, bd.nz - 1);              // (an item that is no voxel still loads inside the cube)
+        x = min(x, bd.nx - 1);
+        const float* ctr = c.base + (int64_t)s * sigma_stride + (int64_t)z * c.plane + y * bd.px + x;
+        const int zd = max(z - 1, 0), zu = min(z + 1, bd.nz - 1), sd = max(s - 1, 0), su = min(s + 1, ns - 1);
+        const ulonglong2* ey = k.ent + (int64_t)y * k.eg.per_row;
+        const int64_t es = (int64_t)s * k.ent_sigma_stride;
+        const int ec = mmx_entry_index(k.eg, z, x);
+        const float v = *ctr;
+        const unsigned long long a0 = ey[es + mmx_entry_index(k.eg, zd, x)].y;
+        const unsigned long long a1 = ey[es + mmx_entry_index(k.eg, zu, x)].y;
+        const unsigned long long a2 = ey[(int64_t)sd * k.ent_sigma_stride + ec].y;
+        const unsigned long long a3 = ey[(int64_t)su * k.ent_sigma_stride + ec].y;
+        const bool ok0 = z > 0 && a0 != 0, ok1 = z + 1 < bd.nz && a1 != 0, ok2 = s > 0 && a2 != 0, ok3 = s + 1 < ns && a3 != 0;
+        const float r0 = *(ok0 ? ctr - c.plane : ctr);
+        const float r1 = *(ok1 ? ctr + c.plane : ctr);
+        const float r2 = *(ok2 ? ctr - sigma_stride : ctr);
+        const float r3 = *(ok3 ? ctr + sigma_stride : ctr);
+        const float n0 = ok0 ? r0 : -INFINITY, n1 = ok1 ? r1 : -INFINITY, n2 = ok2 ? r2 : -INFINITY, n3 = ok3 ? r3 : -INFINITY;
+        return real && !(fmaxf(fmaxf(n0, n1), fmaxf(n2, n3)) > v + eps);
+    };
+    // stage 2 on the survivors queued so far (every lane of the workgroup calls it)
+    auto full_test = [&]() __attribute__((always_inline)) {
+        __syncthreads();
+        const int n2 = q2n;
+        const int l = threadIdx.x & 31;
+        for (int t = threadIdx.x >> 5; t < n2; t += MMX_WG / 32) {
+            int s, z, y, x;
+            voxel_of(q2[t], &s, &z, &y, &x);
+            check_voxel_sparse_group(k, s, z, y, x, l);
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) q2n = 0;
+    };
+    if (threadIdx.x == 0) { qn = 0; q2n = 0; }
     __syncthreads();
     constexpr int kW = 8;                          // words per lane and round
     const int64_t stride = (int64_t)gridDim.x * MMX_WG * kW;
@@ -324,39 +364,44 @@ peaks_sparse_kernel(const float* __restrict__ log, const ulonglong2* __restrict_
                 mw[u] = k.ent[(int64_t)s * k.ent_sigma_stride + (i - (int64_t)s * per_sigma)].x;
             }
         }
+        // Set bits are rare (a few per cent of the words hold one).  A dense patch holds more than the queue: a lane
+        // queues what fits, keeps the rest of its words, and the workgroup goes round again once the queue is empty.
+        for (;;) {
+            bool left = false;                    // this lane still holds bits
 #pragma unroll
-        for (int u = 0; u < kW; ++u) {
-            unsigned long long m = mw[u];
-            if (!m) continue;
-            const int64_t i = i0 + (int64_t)u * MMX_WG;
-            const int cnt = __popcll(m);
-            const int at = atomicAdd(&qn, cnt);
-            if (at + cnt <= kQ) {
-                int j = at;
-                while (m) {
+            for (int u = 0; u < kW; ++u) {
+                unsigned long long m = mw[u];
+                if (!m || left) { left = left || m != 0; continue; }
+                const int64_t i = i0 + (int64_t)u * MMX_WG;
+                const int cnt = __popcll(m);
+                const int at = atomicAdd(&qn, cnt);
+                int fit = kQ - at;                // (slots at .. kQ - 1 are this lane's, whatever else was asked for)
+                fit = fit < 0 ? 0 : fit < cnt ? fit : cnt;
+                for (int j = at; j < at + fit; ++j) {
                     const int b = __ffsll((long long)m) - 1;
                     m &= m - 1;
-                    q[j++] = ((unsigned long long)i << 6) | (unsigned long long)b;
+                    q[j] = ((unsigned long long)i << 6) | (unsigned long long)b;
                 }
-            } else {                              // queue full (a dense patch): this lane walks its own bits
-                while (m) {
-                    const int b = __ffsll((long long)m) - 1;
-                    m &= m - 1;
-                    test_bit(i, b);
+                mw[u] = m;
+                left = m != 0;
+            }
+            __syncthreads();
+            const int nq = qn < kQ ? qn : kQ;     // (the queue is dense: every slot below nq was written)
+            for (int j0 = 0; j0 < nq; j0 += MMX_WG) {
+                const int j = j0 + threadIdx.x;
+                const unsigned long long e = j < nq ? q[j] : 0;
+                if (j < nq && pre_check(e)) q2[atomicAdd(&q2n, 1)] = e;
+                // (at most 256 survivors a pass: stage 2 runs once the next pass might not fit, and at the end)
+                if (j0 + MMX_WG < nq) {
+                    __syncthreads();
+                    if (q2n > kQ2 - MMX_WG) full_test();
+                    __syncthreads();
                 }
             }
+            full_test();
+            if (threadIdx.x == 0) qn = 0;
+            if (!__syncthreads_or(left)) break;
         }
-        __syncthreads();
-        const int nq = qn < kQ ? qn : kQ;     // entries beyond kQ were never queued (handled inline above)
-        // (an `at` below kQ with at + cnt above it queued nothing either: its slots stay unused)
-        for (int j = threadIdx.x; j < nq; j += MMX_WG) {
-            const unsigned long long e = q[j];
-            if (e != ~0ull) test_bit((int64_t)(e >> 6), (int)(e & 63));
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) qn = 0;
-        for (int j = threadIdx.x; j < nq; j += MMX_WG) q[j] = ~0ull;
-        __syncthreads();
     }
 }
 

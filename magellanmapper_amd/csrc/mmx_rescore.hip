@@ -17,8 +17,11 @@
 // Design (gfx950): a 256-thread workgroup per point, a fixed number of workgroups walking the table.  The point needs a (2R+1)^2 window
 // of axis-0 sums (two kernels sharing their loads), staged in LDS in column strips, then
 // 3(2R+1) axis-1 sums, then 3 axis-2 sums.  Loads are L2/MALL hits (the block's voxels were
-// just streamed by the float32 passes); the work is ~1e5 float64 operations per point and
-// there are ~1e3 points per block, so this costs a few per cent of the float32 passes.
+// just streamed by the float32 passes).  At R = 20 a point is 1681 columns of 20 tap pairs, each pair 5 float64
+// operations and 4 of voxel conversion: ~3e5 per point, and the headline step re-scores 3-4 x 10^5 candidates and
+// probes.  That is ~1e11 float64-rate instructions per step, a floor of about 3 ms of the whole device, which the kernel shares
+// with the float32 passes of the next batch (DESIGN.md section 4b has the measured times).  What it must not do is
+// wait for memory tap by tap or column by column: see z_phase.
 
 #include <algorithm>
 #include <type_traits>
@@ -51,10 +54,126 @@ __device__ __forceinline__ double corr_at(const double* vals, int st, int R, con
     return (double)(StoreT)acc;
 }
 
-#ifndef MMX_RESCORE_BATCH
-#define MMX_RESCORE_BATCH 8
-#endif
-constexpr int kB = MMX_RESCORE_BATCH;    // taps whose loads are in flight together
+// ---- the z phase: every column a thread owns marches through the taps side by side.
+// A point's window has N sw columns for the 256 threads; a thread takes NC of them per pass (column e = pass base +
+// c 256 + thread), issues the loads of TB tap pairs of all NC columns, and only then does the arithmetic, column by
+// column in SciPy's order: the same 16 loads in flight per thread as one column at a time had, but a point at R = 20
+// (7 columns a thread) waits for memory 22 times in series where it was about 30, and no load address costs vector arithmetic.
+// NC is compiled in (the accumulators stay in registers); TB follows from a budget of kLoadRegs loaded voxels in flight
+// (registers, but for float64 voxels).  Measured on the headline step (profiles/r13_tail_kernels.txt): budgets of 16 / 32 / 64 registers with up to
+// 4 / 5 / 7 columns a pass all land within 0.3 ms of each other -- the kernel does not wait on the latency of its own
+// loads -- and the smallest, which keeps five workgroups on a CU at R = 20, is the fastest.
+constexpr int kLoadRegs = 16;
+constexpr int kMaxCols = 4;
+template <typename InT, int NC>
+struct z_cfg {
+    static constexpr int raw = kLoadRegs / (2 * NC);       // (float64 voxels too: half the loads in flight measured slower)
+    static constexpr int TB = raw >= 8 ? 8 : raw >= 4 ? 4 : raw >= 2 ? 2 : 1;
+};
+// columns per thread and pass for a window of `ncols` columns: passes of at most kMaxCols, as even as the classes allow
+__host__ __device__ __forceinline__ int rescore_col_class(int ncols)
+{
+    const int cols = (ncols + MMX_WG - 1) / MMX_WG;
+    const int passes = (cols + kMaxCols - 1) / kMaxCols;
+    const int per = (cols + passes - 1) / passes;
+    return per <= 1 ? 1 : per <= 2 ? 2 : 4;
+}
+
+template <typename T> struct off_type { using type = T; };
+
+// INTERIOR: the point's z window lies inside the block, plane k of it is (pt.z + k - R) sz -- scalar arithmetic on the
+// point; otherwise the reflected planes come from the table zr[] in LDS.  (The choice is the workgroup's: the point is.)
+// OffT: uint32_t where every (y, x) offset of the block fits 32 bits of BYTES (the loads then take a scalar plane base and
+// one offset register per column; 64-bit addresses cost a register pair per load in flight), else int64_t elements.
+template <typename InT, typename StoreT, int NC, bool INTERIOR, typename OffT>
+__device__ __forceinline__ void z_phase(const InT* __restrict__ in, int nyb, int nxb, int pz, int py, int px0, int R, int N,
+                                        int SW, int sw, int64_t sz, int64_t sy, int64_t sx,
+                                        const int64_t* __restrict__ zr, const double* __restrict__ w0,
+                                        const double* __restrict__ w2, double* __restrict__ zp0, double* __restrict__ zp2)
+{
+    constexpr int TB = z_cfg<InT, NC>::TB;
+    const int ncols = N * sw;
+    auto zoff = [&](int j) __attribute__((always_inline)) -> int64_t {
+        if constexpr (INTERIOR) return (int64_t)(pz + j - R) * sz;
+        else return zr[j];
+    };
+    constexpr bool kBytes = sizeof(OffT) == 4;
+    auto ld = [&](OffT o, int64_t z) __attribute__((always_inline)) -> InT {
+        if constexpr (kBytes) return *reinterpret_cast<const InT*>(reinterpret_cast<const char*>(in + z) + o);
+        else return in[o + z];
+    };
+    for (int base = 0; base < ncols; base += MMX_WG * NC) {          // (uniform trip count)
+        OffT off[NC];           // the column's (y, x) offset; columns past the window repeat its last one
+        int at[NC];             // where its sums go, -1: nowhere
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const int e = base + c * MMX_WG + (int)threadIdx.x;
+            const int ec = e < ncols ? e : ncols - 1;
+            const int dyi = ec / sw;
+            const int dxi = ec - dyi * sw;
+            const int yy = mmx_reflect(py + dyi - R, nyb);
+            const int xx = mmx_reflect(px0 + dxi - R, nxb);
+            off[c] = (OffT)(((int64_t)yy * sy + (int64_t)xx * sx) * (kBytes ? (int64_t)sizeof(InT) : 1));
+            at[c] = e < ncols ? dyi * SW + dxi : -1;
+        }
+        double a0[NC], a2[NC];
+        {
+            const int64_t zc = zoff(R);
+            InT ctr[NC];
+#pragma unroll
+            for (int c = 0; c < NC; ++c) ctr[c] = ld(off[c], zc);
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                const double cv = in_scale<InT>::get(ctr[c]);
+                a0[c] = cv * w0[0];
+                a2[c] = cv * w2[0];
+            }
+        }
+        // the taps in SciPy's order (k = R .. 1), TB at a time, then the remainder in halves: no tap-by-tap tail
+        int k = R;
+        auto batch = [&](auto nb) __attribute__((always_inline)) {
+            constexpr int B = decltype(nb)::value;
+            for (; k >= B; k -= B) {
+                InT lo[NC][B], hi[NC][B];
+                // (an empty statement the offsets pass through: hoisted out of this loop their 64-bit extensions would be
+                //  formed once, and the loads would take 64-bit vector addresses instead of the scalar base + 32-bit offset)
+                if constexpr (kBytes) {
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) asm volatile("" : "+v"(off[c]));
+                }
+#pragma unroll
+                for (int j = 0; j < B; ++j) {
+                    const int64_t zl = zoff(R - (k - j)), zh = zoff(R + (k - j));
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) {
+                        lo[c][j] = ld(off[c], zl);
+                        hi[c][j] = ld(off[c], zh);
+                    }
+                }
+#pragma unroll
+                for (int c = 0; c < NC; ++c) {
+#pragma unroll
+                    for (int j = 0; j < B; ++j) {
+                        const double p = in_scale<InT>::get(lo[c][j]) + in_scale<InT>::get(hi[c][j]);
+                        a0[c] += p * w0[k - j];
+                        a2[c] += p * w2[k - j];
+                    }
+                }
+            }
+        };
+        batch(std::integral_constant<int, TB>{});
+        if constexpr (TB > 4) batch(std::integral_constant<int, 4>{});
+        if constexpr (TB > 2) batch(std::integral_constant<int, 2>{});
+        if constexpr (TB > 1) batch(std::integral_constant<int, 1>{});
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            if (at[c] >= 0) {
+                zp0[at[c]] = (double)(StoreT)a0[c];
+                zp2[at[c]] = (double)(StoreT)a2[c];
+            }
+        }
+    }
+}
 
 template <typename InT, typename StoreT>
 __global__ void __launch_bounds__(MMX_WG)
@@ -96,48 +215,34 @@ rescore_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
     // multiply per load would cost as much issue time as the float64 arithmetic of the tap)
     int64_t* zr = (int64_t*)(yp + 3 * (size_t)N);
 
+    const bool interior = pt.z - R >= 0 && pt.z + R < bd.nz;
+    const int cls = rescore_col_class(N * SW);
+    // (strides are in elements and may be anything the caller's view has: decided on the block's largest offset)
+    const bool small = ((int64_t)(bd.ny - 1) * sy + (int64_t)(bd.nx - 1) * sx) * (int64_t)sizeof(InT) < (1ll << 31)
+                       && sy >= 0 && sx >= 0;
     __syncthreads();                    // (the previous point's last reads of this memory)
-    for (int k = threadIdx.x; k < N; k += MMX_WG) zr[k] = (int64_t)mmx_reflect(pt.z + k - R, bd.nz) * sz;
-    __syncthreads();
+    if (!interior) {
+        for (int k = threadIdx.x; k < N; k += MMX_WG) zr[k] = (int64_t)mmx_reflect(pt.z + k - R, bd.nz) * sz;
+        __syncthreads();
+    }
     for (int dx0 = 0; dx0 < N; dx0 += SW) {
         const int sw = (N - dx0) < SW ? (N - dx0) : SW;
         // ---- axis 0 (z): two kernels share every load
-        for (int e = threadIdx.x; e < N * sw; e += MMX_WG) {
-            const int dyi = e / sw;
-            const int dxi = e - dyi * sw;
-            const int yy = mmx_reflect(pt.y + dyi - R, bd.ny);
-            const int xx = mmx_reflect(pt.x + dx0 + dxi - R, bd.nx);
-            const InT* col = in + (int64_t)yy * sy + (int64_t)xx * sx;
-            const double c = in_scale<InT>::get(col[zr[R]]);
-            double a0 = c * w0[0];
-            double a2 = c * w2[0];
-            // the taps in SciPy's order (k = R .. 1); the loads of kB taps are issued before the first is
-            // used -- a tap-by-tap loop exposes the full memory latency 2R times per column, and that
-            // latency, not the arithmetic, was this kernel's time
-            int k = R;
-            auto batch = [&](auto nb) __attribute__((always_inline)) {
-                constexpr int B = decltype(nb)::value;
-                for (; k >= B; k -= B) {
-                    InT lo[B], hi[B];
-#pragma unroll
-                    for (int j = 0; j < B; ++j) {
-                        lo[j] = col[zr[R - (k - j)]];
-                        hi[j] = col[zr[R + (k - j)]];
-                    }
-#pragma unroll
-                    for (int j = 0; j < B; ++j) {
-                        const double p = in_scale<InT>::get(lo[j]) + in_scale<InT>::get(hi[j]);
-                        a0 += p * w0[k - j];
-                        a2 += p * w2[k - j];
-                    }
-                }
-            };
-            batch(std::integral_constant<int, kB>{});      // then the remainder in halves: no tap-by-tap tail
-            batch(std::integral_constant<int, 4>{});
-            batch(std::integral_constant<int, 2>{});
-            batch(std::integral_constant<int, 1>{});
-            zp0[dyi * SW + dxi] = (double)(StoreT)a0;
-            zp2[dyi * SW + dxi] = (double)(StoreT)a2;
+        auto zrun = [&](auto nc, auto ot) __attribute__((always_inline)) {
+            constexpr int NC = decltype(nc)::value;
+            using OffT = typename decltype(ot)::type;
+            if (interior)
+                z_phase<InT, StoreT, NC, true, OffT>(in, bd.ny, bd.nx, pt.z, pt.y, pt.x + dx0, R, N, SW, sw, sz, sy, sx,
+                                                     zr, w0, w2, zp0, zp2);
+            else
+                z_phase<InT, StoreT, NC, false, OffT>(in, bd.ny, bd.nx, pt.z, pt.y, pt.x + dx0, R, N, SW, sw, sz, sy, sx,
+                                                      zr, w0, w2, zp0, zp2);
+        };
+        if (!small) zrun(std::integral_constant<int, 2>{}, off_type<int64_t>{});   // (any NC walks any window)
+        else switch (cls) {                  // (the class of the point's full strip; a narrower last strip runs in it too)
+            case 1: zrun(std::integral_constant<int, 1>{}, off_type<uint32_t>{}); break;
+            case 2: zrun(std::integral_constant<int, 2>{}, off_type<uint32_t>{}); break;
+            default: zrun(std::integral_constant<int, 4>{}, off_type<uint32_t>{}); break;
         }
         __syncthreads();
         // ---- axis 1 (y): term 0 = G(y) on G''(z);  term 1 = G''(y) on G(z);  term 2 = G(y) on G(z)
