@@ -184,6 +184,9 @@ typedef enum {
 #define MMX_ZX_PREPACKED 0x100   /* or-ed into MMX_ZX_TILED / MMX_ZX_TILED_Q16: mmx_zx_pack ran on this d_work for these blocks */
 #define MMX_ZX_Y_VALU    0x200   /* or-ed into MMX_ZX_TILED_Q16 (any zx_mode >= 0 accepts it): the Y pass of the 16-bit tiles on the
                                     VALU (y6_kernel) instead of the matrix cores (ym_kernel, the default); for cross-checks */
+#define MMX_ZX_EDGE_GLOBAL 0x400 /* or-ed into MMX_ZX_TILED / MMX_ZX_TILED_Q16 (any zx_mode >= 0 accepts it): the Z+X kernel takes the Z
+                                    fragments of the z tiles at a block's faces from the table in global memory, step by step, instead
+                                    of from its LDS copy (the same arithmetic, bit for bit); for cross-checks */
 #define MMX_MASK_ROWS 1
 #define MMX_MASK_QUADS 2
 int mmx_log_batch_f32(const mmx_volume* vol, const mmx_block* d_blocks, const mmx_block* h_blocks,
@@ -312,7 +315,7 @@ int mmx_fold_parts(mmx_cand* d_cands, uint32_t cap, uint32_t* d_count, const mmx
  *   d_cands / cap / d_count : candidate table; d_count[0] = entries (keeps counting past cap: the caller retries with
  *                 a larger table), d_count[1] = candidates among them (the rest are probes)
  *   h_count, h_cands / h_prefix : pinned host copies of d_count[0..1] and of the first h_prefix entries (NULL: no copy)
- *   zx_mode / zx_flags : as for mmx_log_batch_f32 (flags: MMX_ZX_Y_VALU)
+ *   zx_mode / zx_flags : as for mmx_log_batch_f32 (flags: MMX_ZX_Y_VALU, MMX_ZX_EDGE_GLOBAL)
  *   exact       : re-score every candidate (and probe) in float64;  expand : append the probes (mmx_expand_probes)
  *   stream      : the LoG passes;  tail_stream (NULL = stream): NMS, probes, re-score, copies -- beside the next batch's
  *                 passes when it is another stream;  pack_stream (NULL = stream): the voxel copy

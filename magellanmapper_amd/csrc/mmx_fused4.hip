@@ -45,8 +45,21 @@
 // to the tap it mirrors), so no halo is ever materialised and no load leaves the block: chunks and planes that
 // would are clamped into it and get zero weights.  The fragments are built on the device by a small setup
 // kernel per launch (zx4_setup: one table per distinct block width / depth of the batch, in the part of the
-// workspace the fused path does not use) and live in registers in the main kernel, except the Z fragments of
-// the first and last z tiles, which are reloaded when the march reaches them.
+// workspace the fused path does not use).  The X fragments live in registers in the main kernel; the Z fragments
+// of the interior z tiles in registers or, for the classes with an LDS table (ZLDS), in LDS, shared by the workgroup.
+// The Z fragments of the z tiles at a block's two faces -- the edge output tiles, whose taps leave the block --
+// come from the global table when the march reaches them, except in the LDS form of the march (ELDS: 16-bit tiles
+// of integer voxels, radius 9 .. 24, the kernels of the headline configuration), where they stand in LDS beside the
+// interior table and no step of a wave waits for a load it has issued itself:
+//   - head (straight-line): LA steps of the X pass alone, whose stores leave through the descriptor's range, then the
+//     low edge tiles; steady loop as before, without the drain in front of it; tail: whole rings and an odd step, the
+//     table a run-time LDS address, the X pass of the tiles past the block on the clamped last tile (zero weights);
+//   - every step has the steady step's memory instructions, so every s_waitcnt vmcnt in the march is a counted one
+//     that leaves the younger voxel tile and the stores in flight.  The global-table form had, per edge step, the
+//     voxel tile waited for with vmcnt(0) and three drained fragment round trips in front of the MFMAs.
+// A batch with a depth whose edge tiles exceed the LDS budget (zx4_edges_fit), and any batch under
+// MMX_ZX_EDGE_GLOBAL, runs the global-table form: the same arithmetic, bit for bit.  Measurements:
+// profiles/r14_zx_edge_steps.txt, DESIGN.md section 4b.
 
 #include <algorithm>
 #include <type_traits>
@@ -116,7 +129,32 @@ template <int NKX, int LA> struct cls4 {
     static constexpr bool SPLIT = LA == 2;
     static constexpr int NKZ = 2;
     static constexpr int NT = 4;
+    // most edge output tiles whose tables a workgroup keeps in LDS beside the interior one (8 KiB each; three workgroups
+    // of the LA = 2 class still share a CU's 160 KiB at four)
+    static constexpr int kMaxEdge = LA == 1 ? 3 : 4;
 };
+
+// Edge output tiles of a block nz deep at radius R -- the z tiles whose taps leave the block: U < u_lo and U > u_hi --
+// and whether the LDS form of zx4_kernel takes the block: they fit, its straight-line head (LA steps of X alone, tiles
+// 0 .. LA - 1) is this block's head, and the block has that many steps.
+struct zx4_edges { int u_lo, u_hi, hi0, n; };
+__host__ __device__ inline zx4_edges zx4_edge_tiles(int nz, int R)
+{
+    zx4_edges e;
+    const int ntz = (nz + 15) >> 4;
+    e.u_lo = (R + 15) >> 4;                             // first U with 16 U - R >= 0
+    e.u_hi = (nz - 16 - R) >> 4;                        // last U with 16 U + 15 + R <= nz - 1 (may be < u_lo)
+    e.hi0 = e.u_hi + 1 > e.u_lo ? e.u_hi + 1 : e.u_lo;  // first high edge tile
+    e.n = e.u_lo + (ntz > e.hi0 ? ntz - e.hi0 : 0);
+    return e;
+}
+template <int NKX, int LA>
+bool zx4_edges_fit(int nz, int R)
+{
+    const zx4_edges e = zx4_edge_tiles(nz, R);
+    const int ntz = (nz + 15) >> 4;
+    return e.n <= cls4<NKX, LA>::kMaxEdge && e.u_lo == LA && ntz + LA >= 2 * LA && ntz >= e.u_lo;
+}
 
 // ------------------------------------------------------------------------------------ setup: Toeplitz fragments
 // weight of input position p for output o on an axis of n voxels with SciPy "reflect" folded in
@@ -281,7 +319,7 @@ template <> struct lo_scaled4<float> { static constexpr bool value = true; };
 // tile's X fragments and window are another 64 registers: two waves per SIMD instead of three, each with twice the
 // independent work per step.  An odd tile count leaves the last wave of a row one tile: it computes the second with
 // zero weights and its stores are dropped by a zero-length buffer descriptor (no branch in the march).
-template <int NKX, int LA, typename InT, bool Q16 = false, int NTW = 1>
+template <int NKX, int LA, typename InT, bool Q16 = false, int NTW = 1, bool ELDS = false>
 __global__ void __launch_bounds__(256, (NTW == 1 && (LA == 1 || Q16) && !is_f32_4<InT>::value) ? 3 : 2)   // (float32 tiles, LA == 2: 213 registers)
 zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
            const mmx_block* __restrict__ blocks, int64_t slot_elems,
@@ -340,10 +378,42 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
     // never move, and the shifted table is the cyclic one: F1[k] = [F0[k - 1 mod 2] upper half | F0[k] lower half].
     constexpr bool ROT = ZLDS && Q16 && NTW == 1 && !is_f32_4<InT>::value && (NKX == 1 || LA == 2);
     constexpr int ZL1 = NKZ * 4 * 64;                          // entries of one table
-    __shared__ v4u zl[ZLDS ? (ROT ? 2 : 1) * ZL1 : 1];
+    // EDGE: the tables of the block's edge output tiles (U < u_lo, U > u_hi) stand in LDS too, behind the interior one(s),
+    // in slots 0 .. nE - 1: the low tiles first, then the high ones from hi0 on.  A workgroup's four waves belong to one
+    // block, so one set serves them all, and no step of the march waits for a load it has issued itself: the steps
+    // outside the steady loop have the steady form's memory instructions -- one tile of voxels in, the results out -- and
+    // take their fragments from LDS at an address that is a run-time scalar.  kMaxEdge bounds nE for every depth of the
+    // class but those that leave radius 18 .. 24 a third high tile (nz mod 16 in [1, R - 16)) or no interior tile among
+    // five.  ELDS is a kernel of its own (one head and one tail per kernel: both forms in one spill): launch_zx6 takes it
+    // when every depth class of the batch fits (zx4_edge_tiles) and MMX_ZX_EDGE_GLOBAL is not set, and the kernel whose
+    // edge steps read the global table otherwise.
+    constexpr bool EDGE = ELDS;
+    static_assert(!ELDS || (ZLDS && Q16 && !is_f32_4<InT>::value), "LDS edge tables: 16-bit tiles of integer voxels");
+    constexpr int MAXE = EDGE ? cg::kMaxEdge : 0;
+    constexpr int ZE0 = (ROT ? 2 : 1) * ZL1;                   // first entry of the edge tables
+    const int hi0 = zx4_edge_tiles(nz, R).hi0;                 // first high edge tile
+    __shared__ v4u zl[ZLDS ? ZE0 + MAXE * ZL1 : 1];
     if constexpr (ZLDS) {
         const v4u* zi = ztab + ((size_t)(cz * cfg.maxu + (u_lo < cfg.maxu ? u_lo : 0)) * NKZ * 2) * 128;
-        for (int e = threadIdx.x; e < ZL1; e += 256) zl[e] = zi[e];
+        if constexpr (EDGE) {
+            // every load of the fill in flight before the first LDS write (slots past nE: the last z tile again)
+            const v4u* zc = ztab + ((size_t)(cz * cfg.maxu) * NKZ * 2) * 128;     // table of z tile 0 of this depth class
+            v4u f[MAXE + 1][ZL1 / 256];
+#pragma unroll
+            for (int sl = 0; sl <= MAXE; ++sl) {
+                int tile = sl - 1 < u_lo ? sl - 1 : hi0 + (sl - 1 - u_lo);
+                tile = tile < ntz - 1 ? tile : ntz - 1;
+                const v4u* src = sl ? zc + ((size_t)tile * NKZ * 2) * 128 : zi;
+#pragma unroll
+                for (int j = 0; j < ZL1 / 256; ++j) f[sl][j] = src[threadIdx.x + 256 * j];
+            }
+#pragma unroll
+            for (int sl = 0; sl <= MAXE; ++sl)
+#pragma unroll
+                for (int j = 0; j < ZL1 / 256; ++j) zl[(sl ? ZE0 + (sl - 1) * ZL1 : 0) + threadIdx.x + 256 * j] = f[sl][j];
+        } else {
+            for (int e = threadIdx.x; e < ZL1; e += 256) zl[e] = zi[e];
+        }
         __syncthreads();
         if constexpr (ROT) {
             for (int e = threadIdx.x; e < ZL1; e += 256) {
@@ -356,6 +426,24 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
         }
     }
     if (y >= bd.ny) return;                                   // whole wave (no barriers below)
+
+    // LDS form: the first PF voxel tiles go out here (load_tile's addresses, below), ahead of the X fragment loads
+    [[maybe_unused]] typename pc::raw_t raw_early[ELDS ? PF : 1][NKX];
+    if constexpr (ELDS) {
+        const rsrc_t rin0 = make_rsrc(vol + (int64_t)bd.slot * stride_z);
+        const int nch0 = (W + 7) >> 3;
+#pragma unroll
+        for (int u = 0; u < PF; ++u) {
+            const unsigned so = (unsigned)((y * ntz + (u < ntz ? u : ntz - 1)) * nch0) * (unsigned)kUnit;
+#pragma unroll
+            for (int m = 0; m < NKX; ++m) {
+                int j = 2 * c - cg::R8 / 8 + 4 * m + kq;
+                j = j < 0 ? 0 : (j > nch0 - 1 ? nch0 - 1 : j);
+                raw_early[u][m] = pc::load(rin0, (unsigned)(j * kUnit + li * 16), so);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
 
     // X fragments of this wave's column tile(s): [tile][m][kernel][piece]
     v4u xw[NTW][NKX][2][2];
@@ -458,9 +546,20 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
     // acknowledged by L2 -- measured, that wait and not the arithmetic set the step time (5.3 ms against 2.1 ms
     // without the stores).  With PF steps of distance the stores older than the tile being consumed have had
     // PF - 1 whole steps to complete.
+    // (LDS form: issued before the X fragments are loaded and waited for -- the BIASED start values need them at once
+    //  --, so that the two latencies overlap; the other kernels measured 0.4 .. 1.3 % slower with it and issue them here
+    //  as before: profiles/r14_zx_edge_steps.txt, section 4)
     typename pc::raw_t raw[PF][NKX];
+    constexpr bool EARLY = ELDS;
+    if constexpr (EARLY) {
 #pragma unroll
-    for (int u = 0; u < PF; ++u) load_tile(u < ntz ? u : ntz - 1, raw[u]);
+        for (int u = 0; u < PF; ++u)
+#pragma unroll
+            for (int m = 0; m < NKX; ++m) raw[u][m] = raw_early[u][m];
+    } else {
+#pragma unroll
+        for (int u = 0; u < PF; ++u) load_tile(u < ntz ? u : ntz - 1, raw[u]);
+    }
 
     // One march step: X pass of z tile t into the window, Z pass of z tile t - LA out of it.  STEADY = the
     // branch-free form for the tiles in the middle of the block (every tile real, interior Z fragments already
@@ -478,9 +577,16 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
     }
     // (phase_tag: the window slot of z tile t in a steady step of the rotating form, -1 otherwise: the window is
     //  shifted and t takes slot 2 LA -- the arrangement the rotating steps start from and return to every NT steps)
-    auto step = [&](int t, auto steady_tag, auto phase_tag, typename pc::raw_t (&rw)[NKX], v4f (&P)[NTW], v4f& Q) __attribute__((always_inline)) {
+    // (form_tag: 0 = as the other tags say; 1, 2 = a step outside the steady loop in the LDS form (EDGE): the voxel
+    //  loads and the X pass as in a steady step -- past the last z tile the clamped tile again, whose results meet zero
+    //  weights: the voxel pieces are finite numbers, 0 x finite = 0 --, 1: no Z pass (the first LA steps), 2: the Z pass
+    //  of z tile t - LA, a real one, with the fragments at entry zb of the LDS tables)
+    auto step = [&](int t, auto steady_tag, auto phase_tag, typename pc::raw_t (&rw)[NKX], v4f (&P)[NTW], v4f& Q,
+                    auto form_tag, int zb) __attribute__((always_inline)) {
         constexpr bool STEADY = decltype(steady_tag)::value;
         constexpr int PH = decltype(phase_tag)::value;
+        constexpr int FORM = decltype(form_tag)::value;
+        constexpr bool NOBR = STEADY || FORM != 0;               // no branch around a memory instruction
         constexpr bool TURN = STEADY && ROT && PH >= 0;
         constexpr int SLOT = TURN ? PH : 2 * LA;                 // where the X results of z tile t go
         // SPLIT: they go to xr, and into the window after the Z pass; VS = the slot of z tile t - 4, which the split
@@ -500,7 +606,7 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
 #pragma unroll
                     for (int i = 0; i < 2 * LA; ++i) { win[w][a][i][0] = win[w][a][i + 1][0]; win[w][a][i][1] = win[w][a][i + 1][1]; }
         }
-        if (STEADY || t < ntz) {
+        if (NOBR || t < ntz) {
             // ---- X pass of z tile t
             v4u dh[NKX], dl[NKX];
 #pragma unroll
@@ -512,7 +618,7 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
             // the scheduler must not sink these loads to the end of the unrolled ring (it does, given the chance:
             // all of a ring's loads then sit right in front of their first use)
             __builtin_amdgcn_sched_barrier(0);
-            if (STEADY) load_tile(t + PF < ntz ? t + PF : ntz - 1, rw);
+            if (NOBR) load_tile(t + PF < ntz ? t + PF : ntz - 1, rw);
             else if (t + PF < ntz) load_tile(t + PF, rw);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -575,7 +681,7 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
                 for (int a = 0; a < 4; ++a) { put(w, a, 0, 0u); put(w, a, 1, 0u); }
         }
         const int U = t - LA;
-        if (STEADY || U >= 0) {
+        if (FORM != 1 && (NOBR || U >= 0)) {
             // ---- Z pass of z tile U
             const int want = (U >= u_lo && U <= u_hi) ? u_lo : U;
             if constexpr (!STEADY && !ZLDS) {
@@ -618,6 +724,10 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
                     const int KF = ((TR & 1) ? ZL1 : 0) + ((ks - TR / 2 + NKZ) % NKZ) * 256;     // (a constant once unrolled)
                     z00 = zl[KF + 0 * 64 + lane]; z01 = zl[KF + 1 * 64 + lane];
                     z10 = zl[KF + 2 * 64 + lane]; z11 = zl[KF + 3 * 64 + lane];
+                } else if constexpr (FORM == 2) {
+                    const int KF = zb + ks * 256 + lane;
+                    z00 = zl[KF + 0 * 64]; z01 = zl[KF + 1 * 64];
+                    z10 = zl[KF + 2 * 64]; z11 = zl[KF + 3 * 64];
                 } else {
                     const v4u* zp = zt + ((size_t)(want * NKZ + ks) * 2) * 128;
                     z00 = zp[0]; z01 = zp[64]; z10 = zp[128]; z11 = zp[192];
@@ -647,7 +757,7 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
                     if constexpr (MIXSPLIT) q0[w] = mfma16(al, z10, q0[w]);
                     else q1[w] = mfma16(al, z10, q1[w]);
                 }
-                if constexpr (ZLDS && !STEADY) __builtin_amdgcn_sched_barrier(0);    // one k-step's fragments at a time
+                if constexpr (ZLDS && !STEADY && FORM == 0) __builtin_amdgcn_sched_barrier(0);    // one k-step's fragments at a time
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -695,6 +805,18 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
             }
             obase += 16u * plane_b;
         }
+        if constexpr (FORM == 1) {
+            // no output tile yet (U < 0): the step still issues its stores, at an offset past any tile column, where the
+            // descriptor's range drops them like the rows past the block -- every step of the march then has the same
+            // memory instructions, the compiler's vmcnt counts at the head of the steady loop are the steady state's own,
+            // and nothing has to be drained in front of it
+            constexpr unsigned kDropped = 0x80000000u;          // (a tile column is below 2^31 bytes: mmx_zx6_plan_make)
+#pragma unroll
+            for (int w = 0; w < NTW; ++w) {
+                if (w == 0) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, P[w]), rp, kDropped, 0, ZX4_ST_AUX);
+                else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, P[w]), rp2, kDropped, 0, ZX4_ST_AUX);
+            }
+        }
         if constexpr (SPLIT) {
             // z tile t takes its place in the window: the slot of z tile t - 4 where the slots stay, the last one where
             // they shift
@@ -719,11 +841,32 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
     nB = nB > 0 ? (nB / GROUP) * GROUP : 0;
     if (tA > t_end) tA = ((t_end + PF - 1) / PF) * PF;
     const int tB = tA + nB;
+    // LDS form: the head is straight-line code -- u_lo == LA in every class, so tA == 2 LA and the head is LA steps of X
+    // alone, then the low edge tiles U = 0 .. LA - 1 from slots 0 .. LA - 1 -- and every block has that many steps
+    // (zx4_edges_fit)
+    [[maybe_unused]] auto edge_step = [&](int t, auto u_tag, auto form_tag, int zb) __attribute__((always_inline)) {
+        constexpr int u = decltype(u_tag)::value;
+        step(t, std::false_type{}, std::integral_constant<int, -1>{}, raw[u], outP[u], outQ[u], form_tag, zb);
+    };
+    if constexpr (EDGE) {
+        using std::integral_constant;
+        static_assert(PF == 2, "the head and tail of the LDS form are written for a ring of two");
+        if constexpr (LA == 1) {
+            edge_step(0, integral_constant<int, 0>{}, integral_constant<int, 1>{}, 0);
+            edge_step(1, integral_constant<int, 1>{}, integral_constant<int, 2>{}, ZE0);
+        } else {
+            edge_step(0, integral_constant<int, 0>{}, integral_constant<int, 1>{}, 0);
+            edge_step(1, integral_constant<int, 1>{}, integral_constant<int, 1>{}, 0);
+            edge_step(2, integral_constant<int, 0>{}, integral_constant<int, 2>{}, ZE0);
+            edge_step(3, integral_constant<int, 1>{}, integral_constant<int, 2>{}, ZE0 + ZL1);
+        }
+    } else {
 #pragma unroll 1
-    for (int t0 = 0; t0 < tA; t0 += PF) {
+        for (int t0 = 0; t0 < tA; t0 += PF) {
 #pragma unroll
-        for (int u = 0; u < PF; ++u)
-            if (t0 + u < t_end) step(t0 + u, std::false_type{}, std::integral_constant<int, -1>{}, raw[u], outP[u], outQ[u]);
+            for (int u = 0; u < PF; ++u)
+                if (t0 + u < t_end) step(t0 + u, std::false_type{}, std::integral_constant<int, -1>{}, raw[u], outP[u], outQ[u], std::integral_constant<int, 0>{}, 0);
+        }
     }
     if (nB > 0) {
         // interior Z fragments (the generic steps may have left an edge set in the registers)
@@ -739,19 +882,21 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
         }
         // nothing may be pending at the loop head: a wait for the fragment loads above, placed inside the loop
         // at their first use, would be a static vmcnt(N) that in steady state waits for the previous step's stores
-        __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0)
+        // (LDS form: no fragment loads, and the head's steps have left what a turn of the loop leaves)
+        if constexpr (!EDGE) __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0)
         // (rotating form: step j of a turn writes slot NT - 1 + j (mod NT): the generic steps leave tile t in slot NT - 2;
         //  SPLIT: slot j, the generic steps leave z tiles t - 3 .. t in slots 0 .. 3)
         auto turn = [&](int t0, auto... J) __attribute__((always_inline)) {
             (step(t0 + decltype(J)::value, std::true_type{},
                   std::integral_constant<int, ROT ? ((SPLIT ? 0 : NT - 1) + decltype(J)::value) % NT : -1>{},
-                  raw[decltype(J)::value % PF], outP[decltype(J)::value % PF], outQ[decltype(J)::value % PF]), ...);
+                  raw[decltype(J)::value % PF], outP[decltype(J)::value % PF], outQ[decltype(J)::value % PF],
+                  std::integral_constant<int, 0>{}, 0), ...);
         };
         if constexpr (!ROT) {
 #pragma unroll 1
             for (int t0 = tA; t0 < tB; t0 += PF) {
 #pragma unroll
-                for (int u = 0; u < PF; ++u) step(t0 + u, std::true_type{}, std::integral_constant<int, -1>{}, raw[u], outP[u], outQ[u]);
+                for (int u = 0; u < PF; ++u) step(t0 + u, std::true_type{}, std::integral_constant<int, -1>{}, raw[u], outP[u], outQ[u], std::integral_constant<int, 0>{}, 0);
             }
         } else {
 #pragma unroll 1
@@ -762,11 +907,25 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
             }
         }
     }
+    if constexpr (EDGE) {
+        // tail: whole rings, then the odd step; output tile U = t - LA >= u_lo reads the interior table while
+        // U <= u_hi (the steps a whole turn or ring had no room for) and its own slot after that
+        using std::integral_constant;
+        auto zb_of = [&](int U) __attribute__((always_inline)) { return U <= u_hi ? 0 : ZE0 + (u_lo + U - hi0) * ZL1; };
+        int t0 = tB;
+#pragma unroll 1
+        for (; t0 + PF <= t_end; t0 += PF) {
+            edge_step(t0, integral_constant<int, 0>{}, integral_constant<int, 2>{}, zb_of(t0 - LA));
+            edge_step(t0 + 1, integral_constant<int, 1>{}, integral_constant<int, 2>{}, zb_of(t0 + 1 - LA));
+        }
+        if (t0 < t_end) edge_step(t0, integral_constant<int, 0>{}, integral_constant<int, 2>{}, zb_of(t0 - LA));
+        return;
+    }
 #pragma unroll 1
     for (int t0 = tB; t0 < t_end; t0 += PF) {
 #pragma unroll
         for (int u = 0; u < PF; ++u)
-            if (t0 + u < t_end) step(t0 + u, std::false_type{}, std::integral_constant<int, -1>{}, raw[u], outP[u], outQ[u]);
+            if (t0 + u < t_end) step(t0 + u, std::false_type{}, std::integral_constant<int, -1>{}, raw[u], outP[u], outQ[u], std::integral_constant<int, 0>{}, 0);
     }
 }
 
@@ -970,7 +1129,8 @@ bool collect_classes(const mmx_block* h_blocks, int n_blocks, zx_classes* c)
 
 template <int NKX, int LA>
 int launch_zx6(const mmx_volume* vol, const mmx_block* d_blocks, const mmx_block* h_blocks, int n_blocks,
-               const mmx_zx6_plan& plan, const mmx_taps_f32& tx, int radius, void* d_work, float qp, float qq, hipStream_t s)
+               const mmx_zx6_plan& plan, const mmx_taps_f32& tx, int radius, void* d_work, float qp, float qq, bool edge_global,
+               hipStream_t s)
 {
     using cg = cls4<NKX, LA>;
     mmx_zx4_cfg cfg{};          // (every field the setup kernel reads has a value: qp = qq = 0 means float32 tiles)
@@ -999,6 +1159,10 @@ int launch_zx6(const mmx_volume* vol, const mmx_block* d_blocks, const mmx_block
         const int ntx = (b.nx + 15) / 16;
         max_waves = std::max(max_waves, b.ny * (pair ? (ntx + 1) / 2 : ntx));
     }
+    // the LDS form of the edge steps (16-bit tiles of integer voxels, radius > 8: the class of radius <= 8 would pay for
+    // it with its fourth wave per SIMD -- 131 registers for 124): every depth class of the batch has to fit
+    bool elds = NKX == 2 && !edge_global && qp > 0.f && vol->dtype != MMX_F32;
+    for (int j = 0; j < cl.ncz; ++j) elds = elds && zx4_edges_fit<NKX, LA>(cl.zcls[j], radius);
     const int nx_entries = cfg.ncw * cfg.maxcol * NKX * 2;
     const int nz_entries = cfg.ncz * cfg.maxu * cg::NKZ * 2;
     const size_t xbytes = (size_t)nx_entries * 2 * 64 * sizeof(v4u);
@@ -1021,17 +1185,32 @@ int launch_zx6(const mmx_volume* vol, const mmx_block* d_blocks, const mmx_block
                                plan.tile_stride, reinterpret_cast<float*>(w), reinterpret_cast<float*>(w + plan.q_off),
                                xtab, ztab, cfg);
     } else if (pair) {
-        if constexpr (NKX == 2 && LA == 1)
-            hipLaunchKernelGGL((zx4_kernel<NKX, LA, uint16_t, true, 2>), grid, dim3(256), 0, s,
-                               reinterpret_cast<const uint16_t*>(w + plan.pack_off), plan.pack_stride, (int64_t)0, d_blocks,
-                               plan.tile_stride, reinterpret_cast<float*>(w), reinterpret_cast<float*>(w + plan.q_off),
-                               xtab, ztab, cfg);
-    } else if (qp > 0.f)
-        hipLaunchKernelGGL((zx4_kernel<NKX, LA, uint16_t, true>), grid, dim3(256), 0, s,
-                           reinterpret_cast<const uint16_t*>(w + plan.pack_off), plan.pack_stride, (int64_t)0, d_blocks,
-                           plan.tile_stride, reinterpret_cast<float*>(w), reinterpret_cast<float*>(w + plan.q_off),
-                           xtab, ztab, cfg);
-    else
+        if constexpr (NKX == 2 && LA == 1) {
+            if (elds)
+                hipLaunchKernelGGL((zx4_kernel<NKX, LA, uint16_t, true, 2, true>), grid, dim3(256), 0, s,
+                                   reinterpret_cast<const uint16_t*>(w + plan.pack_off), plan.pack_stride, (int64_t)0, d_blocks,
+                                   plan.tile_stride, reinterpret_cast<float*>(w), reinterpret_cast<float*>(w + plan.q_off),
+                                   xtab, ztab, cfg);
+            else
+                hipLaunchKernelGGL((zx4_kernel<NKX, LA, uint16_t, true, 2>), grid, dim3(256), 0, s,
+                                   reinterpret_cast<const uint16_t*>(w + plan.pack_off), plan.pack_stride, (int64_t)0, d_blocks,
+                                   plan.tile_stride, reinterpret_cast<float*>(w), reinterpret_cast<float*>(w + plan.q_off),
+                                   xtab, ztab, cfg);
+        }
+    } else if (qp > 0.f) {
+        if constexpr (!(NKX == 2 && LA == 1)) {      // (that class runs pairs)
+            if constexpr (NKX == 2) if (elds)
+                hipLaunchKernelGGL((zx4_kernel<NKX, LA, uint16_t, true, 1, true>), grid, dim3(256), 0, s,
+                                   reinterpret_cast<const uint16_t*>(w + plan.pack_off), plan.pack_stride, (int64_t)0, d_blocks,
+                                   plan.tile_stride, reinterpret_cast<float*>(w), reinterpret_cast<float*>(w + plan.q_off),
+                                   xtab, ztab, cfg);
+            if (!elds)
+                hipLaunchKernelGGL((zx4_kernel<NKX, LA, uint16_t, true>), grid, dim3(256), 0, s,
+                                   reinterpret_cast<const uint16_t*>(w + plan.pack_off), plan.pack_stride, (int64_t)0, d_blocks,
+                                   plan.tile_stride, reinterpret_cast<float*>(w), reinterpret_cast<float*>(w + plan.q_off),
+                                   xtab, ztab, cfg);
+        }
+    } else
         hipLaunchKernelGGL((zx4_kernel<NKX, LA, uint16_t, false>), grid, dim3(256), 0, s,
                            reinterpret_cast<const uint16_t*>(w + plan.pack_off), plan.pack_stride, (int64_t)0, d_blocks,
                            plan.tile_stride, reinterpret_cast<float*>(w), reinterpret_cast<float*>(w + plan.q_off),
@@ -1101,11 +1280,11 @@ int mmx_launch_zx6_pack(const mmx_volume* vol, const mmx_block* d_blocks, const 
 // qp, qq > 0: Q16 tiles (P qp in [0, 1], Q qq in [-1, 1]); 0: float32 tiles
 int mmx_launch_zx6(const mmx_volume* vol, const mmx_block* d_blocks, const mmx_block* h_blocks, int n_blocks,
                    const mmx_zx6_plan& plan, const mmx_taps_f32& tx, int radius, void* d_work, float qp, float qq,
-                   hipStream_t stream)
+                   bool edge_global, hipStream_t stream)
 {
     if (!mmx_ring_radius(radius) || !mmx_voxels_ok(vol)) return MMX_ERR_UNSUPPORTED;
-    if (radius <= 8) return launch_zx6<1, 1>(vol, d_blocks, h_blocks, n_blocks, plan, tx, radius, d_work, qp, qq, stream);
-    if (radius <= 16) return launch_zx6<2, 1>(vol, d_blocks, h_blocks, n_blocks, plan, tx, radius, d_work, qp, qq, stream);
-    return launch_zx6<2, 2>(vol, d_blocks, h_blocks, n_blocks, plan, tx, radius, d_work, qp, qq, stream);
+    if (radius <= 8) return launch_zx6<1, 1>(vol, d_blocks, h_blocks, n_blocks, plan, tx, radius, d_work, qp, qq, edge_global, stream);
+    if (radius <= 16) return launch_zx6<2, 1>(vol, d_blocks, h_blocks, n_blocks, plan, tx, radius, d_work, qp, qq, edge_global, stream);
+    return launch_zx6<2, 2>(vol, d_blocks, h_blocks, n_blocks, plan, tx, radius, d_work, qp, qq, edge_global, stream);
 }
 

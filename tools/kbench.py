@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Per-kernel micro-benchmark: HIP-event time of each kernel family on a batch of blocks.
 
-    python tools/kbench.py [--blocks 32] [--edge 261] [--sigmas 3 4 5] [--reps 3]
+    python tools/kbench.py [--blocks 32] [--edge 261 | --shape Z Y X] [--sigmas 3 4 5] [--reps 3]
+
+``--shape`` takes blocks that are not cubes through the same calls: a depth sweep at a constant voxel count (nz = 69,
+133, 261, 517 with 88, 44, 22, 11 blocks of ny = nx = 261) separates what a wave of the Z+X kernel pays once per march
+from what it pays per z tile (profiles/r14_zx_edge_steps.txt).
 """
 import argparse, ctypes, json, os, sys
 import numpy as np
@@ -12,21 +16,24 @@ from magellanmapper_amd import _native as nat, blob_log as bl, synth
 ap = argparse.ArgumentParser()
 ap.add_argument("--blocks", type=int, default=32)
 ap.add_argument("--edge", type=int, default=261)
+ap.add_argument("--shape", type=int, nargs=3, metavar=("Z", "Y", "X"), help="block extents (default: a cube of --edge)")
 ap.add_argument("--sigmas", type=float, nargs="+", default=[3.0, 4.0, 5.0])
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--generic", action="store_true")
 ap.add_argument("--mask", action="store_true", help="Y pass writes the NMS pre-filter masks; sparse NMS kernel")
 a = ap.parse_args()
 dev = torch.device("cuda", 0)
-e = a.edge
-# a volume holding `blocks` blocks of edge e, overlapping by 5 like the real grid
-g = int(np.ceil(a.blocks ** (1 / 3)))
-step = e - 5
-shape = (step * g + 5, step * g + 5, -(-(step * g + 5) // 64) * 64)   # rows of whole 128-byte lines
+ez, ey, ex = a.shape if a.shape else (a.edge,) * 3
+# a volume holding `blocks` blocks of that shape, overlapping by 5 like the real grid: a grid that is about a cube in
+# voxels (thin blocks stack deeper along z)
+gy = gx = max(1, int(round((a.blocks * ez / np.sqrt(ey * ex)) ** (1 / 3))))
+gz = -(-a.blocks // (gy * gx))
+sz, sy, sx = ez - 5, ey - 5, ex - 5
+shape = (sz * gz + 5, sy * gy + 5, -(-(sx * gx + 5) // 64) * 64)   # rows of whole 128-byte lines
 vol = synth.make_volume_device(shape, 3, dev)
 dvol = bl.DeviceVolume(vol)
-origins = [(z * step, y * step, x * step) for z in range(g) for y in range(g) for x in range(g)][:a.blocks]
-shapes = [(e, e, e)] * len(origins)
+origins = [(z * sz, y * sy, x * sx) for z in range(gz) for y in range(gy) for x in range(gx)][:a.blocks]
+shapes = [(ez, ey, ex)] * len(origins)
 L = nat.lib()
 blocks, slot = bl._make_blocks(dvol, 0, origins, shapes)
 nb = len(blocks)
@@ -36,7 +43,7 @@ d_blocks = bl._to_device_bytes(blocks, dev)
 v32 = dvol.view(0, True)
 stream = torch.cuda.current_stream().cuda_stream
 from magellanmapper_amd import kernels1d as k1
-nvox = nb * e ** 3   # algorithmic voxels (pitch columns not counted)
+nvox = nb * ez * ey * ex   # algorithmic voxels (pitch columns not counted)
 res = {}
 fn = L.mmx_log_batch_f32_generic if a.generic else L.mmx_log_batch_f32
 log_base = ws.data_ptr() + 4 * nb * slot * 4
@@ -76,7 +83,7 @@ for rep in range(a.reps + 1):
         res.setdefault(("peaks", ns), []).append(t["peaks"][0])
 torch.cuda.synchronize()
 alg = {"zpass": 10, "ypass": 16, "xpass": 12, "generic": 38 / 3, "zxpass": 10, "y2pass": 12, "zxpack": 4}
-print(f"blocks {nb} x {e}^3 = {nvox/1e6:.0f} Mvox; candidates {int(count.item())}; zx path {zxp.value}")
+print(f"blocks {nb} x {ez}x{ey}x{ex} = {nvox/1e6:.0f} Mvox; candidates {int(count.item())}; zx path {zxp.value}")
 for (k, R), v in sorted(res.items()):
     ms = float(np.median(v))
     if k == "peaks":
@@ -94,6 +101,7 @@ if os.environ.get("ZX2_PROFILE"):
     torch.cuda.synchronize()
     P = ws[:nb * slot].view(nb, slot).cpu().numpy()
     px = int(blocks["px"][0])
+    e = ey
     simd = P[:, :e * px].reshape(nb, e, px)[:, :, 8:24].reshape(-1, 16)
     import collections
     print("wave -> SIMD maps seen:", collections.Counter(tuple(int(v) for v in r[:14]) for r in simd).most_common(4))
