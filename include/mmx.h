@@ -526,8 +526,11 @@ int mmx_preprocess_batch_generic(const mmx_volume* vol, const mmx_subblock* d_su
  * channel over the voxels the blob owns
  * replaces: the label-volume dilation + per-blob np.mean of colocalizer.colocalize_blobs
  * (magmap/cv/colocalizer.py:372-421): ball(2) around every blob centre, contested voxels go to the
- * higher row index among blobs of the same channel of the same block; float64 mean in NumPy's
- * summation order (bit-equal), NaN when the blob owns no voxel.
+ * higher row index among blobs of the same channel of the same block; the mean in NumPy's
+ * summation order (bit-equal), NaN when the blob owns no voxel.  Arithmetic per voxel type, as np.mean of
+ * the selection in the image's dtype: MMX_U8 / MMX_U16 / MMX_F64 sum and divide in float64; MMX_F32 sums
+ * in float32 (same pairwise order, every step rounded to float) and divides in float32, and d_mean holds
+ * that float32 value widened -- comparing two such float64 values is the float32 comparison.
  *   vol      : the image channel to average (any mmx_dtype; raw voxels or a preprocessed slot buffer)
  *   d_blocks : block geometry (src_off into vol, extent); blob coordinates are block-relative
  *   d_blobs  : [n_blobs][5] int32 (block slot, z, y, x, channel of the blob), grouped by block in table
@@ -539,7 +542,9 @@ int mmx_coloc_means(const mmx_volume* vol, const mmx_block* d_blocks, int n_bloc
 /* The same, and the owned voxels themselves: d_voxels[n_blobs][MMX_COLOC_BALL] float64, the first d_count[b]
  * entries of row b in the C order of the reference's boolean-mask selection -- what its percentile thresholds
  * are taken over (`np.percentile(roi[mask >= 0, chl], thresh)`, magmap/cv/colocalizer.py:403-409).
- * d_voxels may be NULL (then this is mmx_coloc_means). */
+ * The copies are exact for every voxel type; the caller casts them back to the image's dtype before the
+ * percentile (np.percentile of float32 values interpolates in float32).  Entries behind d_count[b] are left
+ * as they were.  d_voxels may be NULL (then this is mmx_coloc_means). */
 int mmx_coloc_voxels(const mmx_volume* vol, const mmx_block* d_blocks, int n_blocks,
                      const int32_t* d_blobs, const int32_t* d_offsets, int n_blobs,
                      double* d_mean, int32_t* d_count, double* d_voxels, void* stream);
@@ -547,11 +552,19 @@ int mmx_coloc_voxels(const mmx_volume* vol, const mmx_block* d_blocks, int n_blo
 /* ---- U1: spectral unmixing ahead of detection
  * replaces: detector.detect_blobs' `roi_detect = np.subtract(roi_detect, fac * roi[..., k]);
  * roi_detect[roi_detect < 0] = 0` for every (k, fac) of the profile's spectral_unmixing entry
- * (magmap/cv/detector.py:910-921), float64, bit-equal.
- *   vol, h_subs[k] : the detected channel and the channels to subtract (same dtype, same block table)
+ * (magmap/cv/detector.py:910-921), bit-equal to NumPy's arithmetic for a Python-float factor, per voxel
+ * type: MMX_U8 / MMX_U16 / MMX_F64 -- product, difference and clip in float64, d_out64 the result and
+ * d_out32 that rounded to float; MMX_F32 -- the factor rounded to float, product, difference and clip in
+ * float32 (NumPy does not widen a float32 array for a Python float), d_out32 the result and d_out64 that
+ * widened.  The reference's blob_log then sees a float32 image: the caller re-scores d_out32 with
+ * store_f32 = 1.  No FMA anywhere; n_subs = 0 is a widening copy.
+ *   vol, h_subs[k] : the detected channel and the channels to subtract (same dtype -- MMX_ERR_ARG otherwise
+ *                    -- same block table); at most 8 subtractions, MMX_ERR_UNSUPPORTED beyond (nothing
+ *                    written in either case)
  *   d_blocks       : block geometry (src_off into every source, extent, slot)
  *   d_out32/64     : [n_blocks][dst_slot] with strides (dst_sz, dst_sy, 1): float32 for the LoG passes,
- *                    float64 for the exact re-score                                               */
+ *                    float64 for the exact re-score of integer and float64 images; only the blocks'
+ *                    voxels are written (not the pitch padding, not the rest of a smaller block's slot) */
 int mmx_unmix_batch(const mmx_volume* vol, const mmx_volume* h_subs, const double* h_facs, int n_subs,
                     const mmx_block* d_blocks, const mmx_block* h_blocks, int n_blocks,
                     int64_t dst_slot, int64_t dst_sy, int64_t dst_sz,

@@ -34,6 +34,8 @@ except ImportError:  # pragma: no cover
 
 from . import _native as nat
 
+_NP_DTYPES = {nat.MMX_U8: np.uint8, nat.MMX_U16: np.uint16, nat.MMX_F32: np.float32, nat.MMX_F64: np.float64}
+
 
 def _flags_from_means(table: np.ndarray, means: np.ndarray, shape3, n_channels: int,
                       thresholds: Optional[Dict[int, float]] = None) -> np.ndarray:
@@ -115,7 +117,9 @@ def colocalize_blocks_device(volumes: Dict[int, nat.Volume], blocks, d_blocks,
             nat.check(L.mmx_coloc_voxels(ctypes.byref(vol), d_blk.data_ptr(), len(blk), d_rows.data_ptr(),
                                          d_off.data_ptr(), n, d_mean[k].data_ptr(), d_cnt.data_ptr(),
                                          d_vox.data_ptr(), stream), "mmx_coloc_voxels")
-            owned[c] = (d_vox.cpu().numpy(), d_cnt.cpu().numpy())
+            # back in the image's own type (the float64 copies are exact): np.percentile of a float32 selection
+            # interpolates in float32 and returns a float32, as the reference's call does
+            owned[c] = (d_vox.cpu().numpy().astype(_NP_DTYPES[int(vol.dtype)]), d_cnt.cpu().numpy())
     h_mean = d_mean.cpu().numpy()           # (one wait for every channel's kernel)
     for k, c in enumerate(order):
         means[:, c] = h_mean[k]

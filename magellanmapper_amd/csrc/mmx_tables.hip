@@ -15,6 +15,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 
 #include "mmx_common.h"
 
@@ -164,8 +165,32 @@ extern "C" int mmx_close_pairs(const int32_t* d_master, int n_master, const int3
 // owns one blob: lanes 0..32 are the 33 offsets in C order (= the order boolean-mask indexing yields),
 // the block's later blobs of the same channel are scanned for takers, and lane 0 sums the owned
 // voxels in NumPy's pairwise order (n <= 33: eight accumulators over the first 8*floor(n/8), then the
-// tail) so the float64 mean is bit-equal.  A blob that owns nothing gets 0/0 = NaN, as NumPy gives.
+// tail) so the mean is bit-equal.  The sum and the quotient are float64 for uint8 / uint16 / float64
+// voxels (np.mean of an integer selection accumulates in float64) and float32 for float32 voxels (np.mean
+// of a float32 selection stays in float32: same order, every step rounded to float); the float32 mean is
+// widened into mean[], which loses nothing.  A blob that owns nothing gets 0/0 = NaN, as NumPy gives.
 namespace {
+// NumPy's pairwise sum of n <= 33 contiguous values (one block: n is below its 128-element split) behind the
+// reduction's initial 0, divided by the count, all in AccT
+template <typename AccT>
+__device__ __forceinline__ AccT coloc_mean_of(const double* vals, int n)
+{
+    AccT res;
+    if (n < 8) {
+        res = (AccT)0;
+        for (int i = 0; i < n; ++i) res += (AccT)vals[i];
+    } else {
+        AccT r[8];
+        for (int j = 0; j < 8; ++j) r[j] = (AccT)vals[j];
+        int i;
+        for (i = 8; i < n - (n % 8); i += 8)
+            for (int j = 0; j < 8; ++j) r[j] += (AccT)vals[i + j];
+        res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+        for (; i < n; ++i) res += (AccT)vals[i];
+    }
+    return ((AccT)0 + res) / (AccT)n;           // n == 0 -> NaN, like np.mean of an empty selection
+}
+
 template <typename InT>
 __global__ void __launch_bounds__(64)
 coloc_means_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
@@ -227,20 +252,8 @@ coloc_means_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t 
     // (optional) the owned voxels themselves, in the selection's C order: percentile thresholds
     if (voxels && lane < n) voxels[(int64_t)b * MMX_COLOC_BALL + lane] = vals[lane];
     if (lane == 0) {
-        double res;
-        if (n < 8) {
-            res = 0.;
-            for (int i = 0; i < n; ++i) res += vals[i];
-        } else {
-            double r[8];
-            for (int j = 0; j < 8; ++j) r[j] = vals[j];
-            int i;
-            for (i = 8; i < n - (n % 8); i += 8)
-                for (int j = 0; j < 8; ++j) r[j] += vals[i + j];
-            res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-            for (; i < n; ++i) res += vals[i];
-        }
-        mean[b] = (0. + res) / (double)n;       // n == 0 -> NaN, like np.mean of an empty selection
+        if constexpr (std::is_same<InT, float>::value) mean[b] = (double)coloc_mean_of<float>(vals, n);
+        else mean[b] = coloc_mean_of<double>(vals, n);
         count[b] = n;
     }
 }
@@ -280,10 +293,12 @@ extern "C" int mmx_coloc_means(const mmx_volume* vol, const mmx_block* d_blocks,
 }
 
 // ---- spectral unmixing ahead of detection (magmap/cv/detector.py:910-921): for the detected channel
-//     x = x - fac_k * roi[..., k]  ;  x[x < 0] = 0      for every (k, fac_k) in turn, in float64
-// (NumPy promotes `uint16 - float * uint16` to float64; one rounding for the product, one for the
-// difference: no FMA, this file is built with -ffp-contract=off).  Streaming kernel: 1 + K voxels in,
-// 8 + 4 bytes out per voxel, written in the uniform-stride slot layout the preprocessing uses.
+//     x = x - fac_k * roi[..., k]  ;  x[x < 0] = 0      for every (k, fac_k) in turn
+// in float64 for uint8 / uint16 / float64 voxels (NumPy promotes `uint16 - float * uint16` to float64) and in
+// float32 for float32 voxels (a Python-float factor does not widen a float32 array: the factor is rounded to
+// float32, product, difference and clip stay float32; out64 then holds the float32 values widened).  One rounding
+// for the product, one for the difference: no FMA, this file is built with -ffp-contract=off.  Streaming kernel:
+// 1 + K voxels in, 8 + 4 bytes out per voxel, written in the uniform-stride slot layout the preprocessing uses.
 #define MMX_UNMIX_MAX 8
 struct unmix_args {
     const void* sub[MMX_UNMIX_MAX];
@@ -302,15 +317,18 @@ unmix_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx, un
     const int64_t n = (int64_t)bd.nz * bd.ny * bd.nx;
     for (int64_t i = (int64_t)blockIdx.x * MMX_WG + threadIdx.x; i < n; i += (int64_t)gridDim.x * MMX_WG) {
         const int64_t t = i / bd.nx, x = i - t * bd.nx, z = t / bd.ny, y = t - z * bd.ny;
-        double v = (double)vol[bd.src_off + z * sz + y * sy + x * sx];
+        // float32 voxels: NumPy takes the Python-float factor as a float32 and keeps the product, the difference
+        // and the clip in float32; every other voxel type promotes to float64
+        using AccT = typename std::conditional<std::is_same<InT, float>::value, float, double>::type;
+        AccT v = (AccT)vol[bd.src_off + z * sz + y * sy + x * sx];
         for (int k = 0; k < U.n_subs; ++k) {
             const InT* sp = (const InT*)U.sub[k];
-            const double m = U.fac[k] * (double)sp[bd.src_off + z * U.sub_sz[k] + y * U.sub_sy[k] + x * U.sub_sx[k]];
+            const AccT m = (AccT)U.fac[k] * (AccT)sp[bd.src_off + z * U.sub_sz[k] + y * U.sub_sy[k] + x * U.sub_sx[k]];
             v = v - m;
-            if (v < 0.) v = 0.;
+            if (v < (AccT)0) v = (AccT)0;
         }
         const int64_t d = (int64_t)bd.slot * dst_slot + z * dst_sz + y * dst_sy + x;
-        out64[d] = v;
+        out64[d] = (double)v;
         out32[d] = (float)v;
     }
 }

@@ -475,6 +475,16 @@ def detect_blobs_blocks_device(dvol, channel, origins, shapes, stats=None,
                         for k, f in spec.items()]
             if subtract:
                 from . import preprocess
+                # `fac * roi[..., k]` with an int factor (YAML `1`) and integer voxels stays in the image's integer
+                # type in the reference: the subtraction wraps around instead of going negative and the clip never
+                # bites.  That is not what Unmixer computes (it takes the factor as a float): refuse it.  Preprocessed
+                # blocks are float64 and float images are floats, where an int factor is an ordinary number.
+                if denoise_max_shape is None and dvol.np_dtype.kind in "ui" and any(
+                        isinstance(f, (int, np.integer, np.bool_)) for _, f in subtract):
+                    raise NotImplementedError(
+                        f"spectral unmixing of a {dvol.np_dtype} image with an integer factor {dict(subtract)}: the "
+                        f"reference then subtracts in {dvol.np_dtype}, wrapping around below 0, which is not built; "
+                        "write the factor as a float (1.0) for the float64 arithmetic")
                 if isotropic is not None:       # resize every channel first, then unmix the resized ones
                     source = preprocess.Unmixer(subtract, denoise_max_shape, rescale=(iso_factor, channels))
                     source.set_blocks(origins, shapes, log_shapes)

@@ -491,10 +491,12 @@ class Preprocessor:
 class Unmixer:
     """Spectral unmixing of one detected channel for the blocks of a batch (reference
     magmap/cv/detector.py:910-921): ``x = x - fac * roi[..., k]; x[x < 0] = 0`` for every
-    ``(k, fac)`` in turn, in float64, on the block as detection sees it -- the raw voxels, or the
+    ``(k, fac)`` in turn, on the block as detection sees it -- the raw voxels, or the
     preprocessed channels when ``denoise_max_shape`` is set (the reference preprocesses the block in
-    ``detect_sub_roi`` before ``detect_blobs`` unmixes it).  Same ``run`` contract as
-    :class:`Preprocessor`, so ``blob_log_blocks`` takes either."""
+    ``detect_sub_roi`` before ``detect_blobs`` unmixes it).  In float64 for uint8 / uint16 / float64 sources; a
+    float32 source (raw or rescaled) is unmixed in float32 like NumPy's, and ``store_f32`` then tells the detection
+    that the exact volume is that float32 image.  Same ``run`` contract as :class:`Preprocessor`, so
+    ``blob_log_blocks`` takes either."""
 
     def __init__(self, subtract: Sequence[Tuple[int, float]], denoise_max_shape=None, near_max=None,
                  rescale=None):
@@ -506,6 +508,7 @@ class Unmixer:
         self.near_max = near_max
         self.rescale = rescale
         self._rs: Dict[int, "Rescaler"] = {}
+        self.store_f32 = 0                     # 1 after a run on a float32 source: the cube of such an image is float32
         self._blocks_args = None
         self._pres: Dict[int, Preprocessor] = {}
         self._out64 = [None] * N_BUFFER_SETS
@@ -592,8 +595,13 @@ class Unmixer:
         self._raw_scale = (float(np.iinfo(dvol.np_dtype).max) if dvol.np_dtype.kind in "ui"
                            else dvol.value_scale())
         self.last_geometry = (slot_pre, dst_sz, dst_sy, out64, out32)
-        return (blocks, slot, nat.Volume(out32.data_ptr(), nat.MMX_F32, 0, dst_sz, dst_sy, 1),
-                nat.Volume(out64.data_ptr(), nat.MMX_F64, 0, dst_sz, dst_sy, 1))
+        vol32 = nat.Volume(out32.data_ptr(), nat.MMX_F32, 0, dst_sz, dst_sy, 1)
+        # a float32 source (raw or rescaled) is unmixed in float32, as NumPy does it, and the reference's blob_log then
+        # runs on a float32 image: the float32 buffer IS the exact volume and the re-scored cube is a float32 cube
+        self.store_f32 = 1 if main.dtype == nat.MMX_F32 else 0
+        if self.store_f32:
+            return blocks, slot, vol32, vol32
+        return blocks, slot, vol32, nat.Volume(out64.data_ptr(), nat.MMX_F64, 0, dst_sz, dst_sy, 1)
 
     fetch = Preprocessor.fetch
 

@@ -1,0 +1,301 @@
+"""GPU tests of the two table-side kernels that read image voxels, at every voxel type: ``mmx_unmix_batch``
+(spectral unmixing, reference magmap/cv/detector.py:910-921) and ``mmx_coloc_means`` / ``mmx_coloc_voxels``
+(intensity co-localisation, magmap/cv/colocalizer.py:372-441), through the C ABI and through the callers that
+depend on their arithmetic (``preprocess.Unmixer`` -> the exact re-score, ``colocalizer.colocalize_blobs``).
+
+Every comparison is bit for bit.  The references are the NumPy expression of the reference's source line, evaluated
+on the CPU in the image's own dtype, and the CPU oracle -- not new golden files of the real reference, which needs
+scikit-image to run.  The cases, their references and the host tests showing that each case discriminates live in
+``test_table_kernels_host.py``."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import test_table_kernels_host as tk
+from test_oracle_golden import COLOC, coloc_roi
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+MMX_ERR_ARG, MMX_ERR_UNSUPPORTED = 1, 5
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    if not torch.cuda.is_available():
+        pytest.fail("GPU tests need a GPU: torch.cuda.is_available() is False")
+    from magellanmapper_amd import _native
+    assert _native.lib().mmx_device_count() >= 1
+    return torch.device("cuda", 0)
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+# ------------------------------------------------------------------------------------------ mmx_unmix_batch
+def _unmix_layout():
+    """The destination layout ``Unmixer.run`` uses: rows of the widest block rounded up to MMX_ROW_ALIGN."""
+    from magellanmapper_amd import _native as nat
+    shp = np.asarray(tk.UNMIX_EXTENTS, dtype=np.int64)
+    dst_sy = int(-(-shp[:, 2].max() // nat.MMX_ROW_ALIGN) * nat.MMX_ROW_ALIGN)
+    dst_sz = dst_sy * int(shp[:, 1].max())
+    return dst_sy, dst_sz, dst_sz * int(shp[:, 0].max())
+
+
+def _unmix_on_device(gpu, dtype, subtract, sub_dtype=None):
+    """One ``mmx_unmix_batch`` call over the four blocks into sentinel-filled buffers -> ``(status, out32, out64)``."""
+    from magellanmapper_amd import _native as nat, blob_log as bl
+    dvol = bl.DeviceVolume(tk.unmix_image(dtype).copy())
+    dvol.wait_all()
+    other = dvol if sub_dtype is None else bl.DeviceVolume(tk.unmix_image(sub_dtype).copy())
+    other.wait_all()
+    blocks, _ = bl._make_blocks(dvol, 0, tk.UNMIX_ORIGINS, tk.UNMIX_EXTENTS)
+    d_blocks = torch.from_numpy(blocks.view(np.uint8).reshape(-1)).to(gpu)
+    dst_sy, dst_sz, slot = _unmix_layout()
+    nb = len(blocks)
+    out32 = torch.full((nb * slot,), tk.SENTINEL, dtype=torch.float32, device=gpu)
+    out64 = torch.full((nb * slot,), tk.SENTINEL, dtype=torch.float64, device=gpu)
+    main = dvol.view(tk.UNMIX_CHANNEL, False)
+    subs = [other.view(k, False) for k, _ in subtract]
+    sub_arr = (nat.Volume * max(1, len(subs)))(*subs)
+    facs = np.array([f for _, f in subtract], dtype=np.float64)
+    rc = nat.lib().mmx_unmix_batch(ctypes.byref(main), sub_arr, nat.as_double_ptr(facs) if len(facs) else None,
+                                   len(subs), d_blocks.data_ptr(), blocks.ctypes.data, nb, slot, dst_sy, dst_sz,
+                                   out32.data_ptr(), out64.data_ptr(), _stream())
+    torch.cuda.synchronize()
+    return rc, out32.cpu().numpy(), out64.cpu().numpy()
+
+
+def _unmix_expected(dtype, subtract):
+    """The whole destination buffers: NumPy's result of every block in its slot, the sentinel everywhere else (the
+    pitch padding, the unused rows and planes of the smaller blocks)."""
+    dst_sy, dst_sz, slot = _unmix_layout()
+    nb = len(tk.UNMIX_EXTENTS)
+    want32 = np.full(nb * slot, tk.SENTINEL, dtype=np.float32)
+    want64 = np.full(nb * slot, tk.SENTINEL, dtype=np.float64)
+    for i, blk in enumerate(tk.unmix_blocks(tk.unmix_image(dtype))):
+        ref = tk.unmix_reference(blk, tk.UNMIX_CHANNEL, subtract)
+        if subtract:
+            assert ref.dtype == (np.float32 if dtype == "float32" else np.float64)
+        for want in (want32, want64):
+            it = want.itemsize
+            view = np.lib.stride_tricks.as_strided(want[i * slot:], ref.shape, (dst_sz * it, dst_sy * it, it))
+            view[...] = ref                # (exact: float32 -> float64 widens, float64 -> float32 rounds to nearest)
+    return want32, want64
+
+
+@pytest.mark.parametrize("case", list(tk.UNMIX_CASES))
+@pytest.mark.parametrize("dtype", tk.DTYPES)
+def test_unmix_batch_is_bit_equal_to_numpy(gpu, dtype, case):
+    """Four blocks of different extents at non-zero origins of an interleaved three-channel image, one call: both
+    outputs equal NumPy's result in the image's dtype bit for bit -- float32 images in float32 arithmetic -- and
+    nothing but the blocks' voxels is written."""
+    subtract = tk.UNMIX_CASES[case]
+    rc, out32, out64 = _unmix_on_device(gpu, dtype, subtract)
+    assert rc == 0
+    want32, want64 = _unmix_expected(dtype, subtract)
+    tk.assert_bits_equal(out32, want32, err_msg=f"out32 {dtype} {case}")
+    tk.assert_bits_equal(out64, want64, err_msg=f"out64 {dtype} {case}")
+
+
+@pytest.mark.parametrize("dtype", tk.DTYPES)
+def test_unmix_batch_refusals_write_nothing(gpu, dtype):
+    """One subtraction beyond MMX_UNMIX_MAX is unsupported, a subtracted channel of another voxel type a bad argument;
+    neither touches the outputs."""
+    assert len(tk.UNMIX_NINE) == tk.UNMIX_MAX + 1
+    other = "uint16" if dtype != "uint16" else "float32"
+    for subtract, sub_dtype, status in ((tk.UNMIX_NINE, None, MMX_ERR_UNSUPPORTED),
+                                        (tk.UNMIX_CASES["one"], other, MMX_ERR_ARG)):
+        rc, out32, out64 = _unmix_on_device(gpu, dtype, subtract, sub_dtype)
+        assert rc == status
+        assert (out32 == np.float32(tk.SENTINEL)).all() and (out64 == tk.SENTINEL).all()
+
+
+# ----------------------------------------------------------------------- the exact cube of an unmixed float32 image
+def _f32_two_channels(shape, seeds=(3, 4), n_blobs=12):
+    from magellanmapper_amd import synth
+    return np.stack([synth.make_volume(s, shape, n_blobs) / 65535 for s in seeds], axis=-1).astype(np.float32)
+
+
+@pytest.mark.parametrize("rescaled", [False, True])
+def test_exact_cube_of_an_unmixed_float32_image(gpu, rescaled):
+    """``Unmixer.run`` on a float32 two-channel volume (raw, and rescaled along z first): the volume it hands the
+    exact re-score holds NumPy's float32 unmixed image, and ``mmx_rescore_f64`` on it with the ``store_f32`` it
+    reports gives the float32 cube of the reference's ``blob_log`` on that image, bit for bit."""
+    from magellanmapper_amd import _native as nat, blob_log as bl, preprocess
+    from oracle import blob_log_oracle as blo, isotropic_oracle
+    shape = (20, 24, 40)
+    roi = _f32_two_channels(shape)
+    subtract = [(1, 0.4)]
+    dvol = bl.DeviceVolume(roi.copy())
+    if rescaled:
+        scale, res = (1, 1, 1), np.array([2.0, 1.0, 1.0])
+        factor = preprocess.calc_isotropic_factor(scale, res)
+        seen_shape = preprocess.isotropic_shape(shape, factor)
+        assert seen_shape == (40, 24, 40)
+        um = preprocess.Unmixer(subtract, None, rescale=(factor, [0, 1]))
+        um.set_blocks([(0, 0, 0)], [shape], [seen_shape])
+        seen = isotropic_oracle.make_isotropic(roi, scale, res)
+        assert seen.dtype == np.float32 and seen.shape == seen_shape + (2,)
+    else:
+        um, seen, seen_shape = preprocess.Unmixer(subtract), roi, shape
+    want_img = tk.unmix_reference(seen, 0, subtract)
+    assert want_img.dtype == np.float32
+    assert np.count_nonzero(want_img != tk.unmix_float64_formula(seen, 0, subtract).astype(np.float32)) > 100
+    blocks, _slot, _vol32, vol_exact = um.run(dvol, 0, [(0, 0, 0)], [seen_shape])
+    store_f32 = int(getattr(um, "store_f32", 0))          # (as blob_log._batch_voxels reads it)
+    # ---- the re-scored values at arbitrary points, borders included
+    min_sigma, max_sigma, num_sigma = 2.0, 3.0, 3
+    sigmas, _ = blo.sigma_list(min_sigma, max_sigma, num_sigma, 3)
+    cube = blo.log_cube(want_img, sigmas)
+    assert cube.dtype == np.float32
+    space = bl.ScaleSpace.make(min_sigma, max_sigma, num_sigma)
+    rng = np.random.default_rng(3)
+    n = 300
+    pts = np.zeros(n, dtype=nat.CAND_DTYPE)
+    pts["s"] = rng.integers(0, num_sigma, n)
+    for ax, name in enumerate("zyx"):
+        pts[name] = rng.integers(0, seen_shape[ax], n)
+    pts["z"][:20] = 0
+    pts["y"][10:30] = seen_shape[1] - 1
+    pts["x"][20:40] = 0
+    d_blocks = bl._to_device_bytes(blocks, gpu)
+    d_pts = bl._to_device_bytes(pts, gpu)
+    d_w0 = torch.from_numpy(space.w0_tab).to(gpu)
+    d_w2 = torch.from_numpy(space.w2_tab).to(gpu)
+    nat.check(nat.lib().mmx_rescore_f64(
+        ctypes.byref(vol_exact), d_blocks.data_ptr(), 1, d_pts.data_ptr(), n, None, d_w0.data_ptr(), d_w2.data_ptr(),
+        nat.as_int32_ptr(space.radii), nat.as_double_ptr(space.norms), num_sigma, store_f32, _stream()), "rescore")
+    got = d_pts.cpu().numpy().view(nat.CAND_DTYPE)["v64"]
+    want = cube[pts["z"], pts["y"], pts["x"], pts["s"]].astype(np.float64)
+    np.testing.assert_array_equal(got, want)
+    # ---- and the exact volume itself: a float32 image holding NumPy's values
+    assert store_f32 == 1 and vol_exact.dtype == nat.MMX_F32
+    _slot_pre, dst_sz, dst_sy, _out64, out32 = um.last_geometry
+    assert vol_exact.d_data == out32.data_ptr()            # the float32 buffer serves as both views
+    assert (vol_exact.stride_z, vol_exact.stride_y, vol_exact.stride_x) == (dst_sz, dst_sy, 1)
+    held = torch.as_strided(out32, seen_shape, (dst_sz, dst_sy, 1)).cpu().numpy()
+    tk.assert_bits_equal(np.ascontiguousarray(held), np.ascontiguousarray(want_img))
+
+
+def test_unmixing_of_preprocessed_float32_blocks_is_still_refused(gpu):
+    """With ``denoise_max_shape`` set the unmixing works on preprocessed blocks, and the preprocessing refuses float32
+    voxels (what the reference computes there depends on the NumPy release)."""
+    from magellanmapper_amd import blob_log as bl, preprocess
+    from magellanmapper_amd import config
+    config.setup_roi_profiles(None)
+    dvol = bl.DeviceVolume(tk.make_image("float32", (8, 12, 16, 2), 1))
+    with pytest.raises(NotImplementedError, match="not float32"):
+        preprocess.Unmixer([(1, 0.4)], (8, 8, 8)).run(dvol, 0, [(0, 0, 0)], [(8, 12, 16)])
+
+
+@pytest.mark.parametrize("isotropic", [None, (1, 1, 1)])
+def test_detect_blobs_of_an_unmixed_float32_image_matches_oracle(gpu, isotropic):
+    """``detect_blobs`` with ``spectral_unmixing`` on a float32 two-channel image, raw and rescaled along z."""
+    from magellanmapper_amd import config, detector
+    from oracle import magmap_oracle as mmo
+    roi = _f32_two_channels((30, 40, 44), seeds=(11, 12), n_blobs=25)
+    unmix = {0: {1: 0.4}}
+    config.setup_roi_profiles(None)
+    config.roi_profile.update(num_sigma=3, denoise_size=None, isotropic=isotropic)
+    config.roi_profile.spectral_unmixing = unmix
+    config.resolutions = np.array([[1.5, 1.0, 1.0]]) if isotropic else np.array([[1.0, 1.0, 1.0]])
+    try:
+        want = mmo.detect_blobs(roi, None, [dict(config.roi_profile, spectral_unmixing=unmix)], config.resolutions)
+        got = detector.detect_blobs(roi, None)
+    finally:
+        config.roi_profile.spectral_unmixing = None
+        config.setup_roi_profiles(None)
+    assert want is not None and len(want) > 10 and set(np.unique(want[:, 6])) == {0.0, 1.0}
+    np.testing.assert_array_equal(got, want)
+
+
+# --------------------------------------------------------------------------- mmx_coloc_means / mmx_coloc_voxels
+@pytest.mark.parametrize("dtype", tk.DTYPES)
+def test_coloc_means_and_voxels_are_bit_equal_to_numpy(gpu, dtype):
+    """Two blocks at non-zero origins of an interleaved two-channel image in one call, a table per block: counts,
+    means (``np.mean`` of the selection in the image's dtype: float32 sums and divides in float32), the owned voxels in
+    selection order, NaN for a blob that owns nothing, and nothing written behind a row's count."""
+    from magellanmapper_amd import _native as nat, blob_log as bl
+    img, refs = tk.coloc_case(dtype)
+    tables = tk.coloc_tables()
+    dvol = bl.DeviceVolume(img.copy())
+    dvol.wait_all()
+    blocks, _ = bl._make_blocks(dvol, 0, tk.COLOC_ORIGINS, tk.COLOC_EXTENTS)
+    d_blocks = torch.from_numpy(blocks.view(np.uint8).reshape(-1)).to(gpu)
+    offsets = np.concatenate([[0], np.cumsum([len(t) for t in tables])]).astype(np.int32)
+    assert len(offsets) == 3
+    n = int(offsets[-1])
+    rows = np.zeros((n, 5), np.int32)
+    for i, t in enumerate(tables):
+        rows[offsets[i]:offsets[i + 1], 0] = i
+        rows[offsets[i]:offsets[i + 1], 1:] = t
+    d_rows = torch.from_numpy(rows.reshape(-1)).to(gpu)
+    d_off = torch.from_numpy(offsets).to(gpu)
+    want_cnt = np.concatenate([r[0] for r in refs])
+    for c in range(2):
+        vol = dvol.view(c, False)
+        want_mean = np.concatenate([r[1][c] for r in refs])
+        want_vox = [v for r in refs for v in r[2][c]]
+        d_mean = torch.full((n,), tk.SENTINEL, dtype=torch.float64, device=gpu)
+        d_cnt = torch.full((n,), -1, dtype=torch.int32, device=gpu)
+        d_vox = torch.full((n, nat.MMX_COLOC_BALL), tk.SENTINEL, dtype=torch.float64, device=gpu)
+        nat.check(nat.lib().mmx_coloc_voxels(ctypes.byref(vol), d_blocks.data_ptr(), 2, d_rows.data_ptr(),
+                                             d_off.data_ptr(), n, d_mean.data_ptr(), d_cnt.data_ptr(),
+                                             d_vox.data_ptr(), _stream()), "mmx_coloc_voxels")
+        got_mean, got_cnt, got_vox = d_mean.cpu().numpy(), d_cnt.cpu().numpy(), d_vox.cpu().numpy()
+        np.testing.assert_array_equal(got_cnt, want_cnt)
+        np.testing.assert_array_equal(got_mean, want_mean, err_msg=f"{dtype} channel {c}")      # (NaN where NaN)
+        some = want_cnt > 0
+        assert np.isnan(got_mean[~some]).all() and (~some).sum() >= 4
+        tk.assert_bits_equal(got_mean[some], want_mean[some])
+        for b in range(n):
+            k = int(want_cnt[b])
+            tk.assert_bits_equal(got_vox[b, :k], want_vox[b].astype(np.float64), err_msg=f"row {b}")
+            assert (got_vox[b, k:] == tk.SENTINEL).all(), b
+        # the entry point without the voxels: the same means
+        d_mean2 = torch.full((n,), tk.SENTINEL, dtype=torch.float64, device=gpu)
+        nat.check(nat.lib().mmx_coloc_means(ctypes.byref(vol), d_blocks.data_ptr(), 2, d_rows.data_ptr(),
+                                            d_off.data_ptr(), n, d_mean2.data_ptr(), d_cnt.data_ptr(), _stream()),
+                  "mmx_coloc_means")
+        np.testing.assert_array_equal(d_mean2.cpu().numpy(), want_mean)
+    for row, k in tk.COLOC_KNOWN_COUNTS.items():
+        assert got_cnt[row] == k
+
+
+# ------------------------------------------------------------------------------- colocalize_blobs end to end
+def test_colocalize_blobs_float32_tie(gpu):
+    """Two means that are distinct reals and one float32 (see the host test): flagged, as the reference flags them."""
+    from magellanmapper_amd import colocalizer
+    got = colocalizer.colocalize_blobs(tk.tie_roi(), tk.tie_blobs())
+    assert got.dtype == np.uint8
+    np.testing.assert_array_equal(got, [[1, 1], [1, 1]])
+    np.testing.assert_array_equal(colocalizer.colocalize_blobs(tk.tie_roi().astype(np.float64), tk.tie_blobs()),
+                                  [[1, 0], [1, 1]])
+
+
+@pytest.mark.parametrize("percentile", [5, 50, 99])
+@pytest.mark.parametrize("dtype", ["float32", "uint8"])
+def test_colocalize_blobs_percentile_thresholds_match_oracle(gpu, dtype, percentile):
+    """Percentile thresholds over the owned voxels in the image's dtype (a float32 percentile is a float32)."""
+    from magellanmapper_amd import colocalizer
+    roi, blobs = tk.percentile_case(dtype)
+    want = tk.oracle_flags(roi, blobs, percentile)
+    got = colocalizer.colocalize_blobs(roi, blobs, percentile)
+    assert 0 < want.sum() < want.size
+    np.testing.assert_array_equal(got, want)
+
+
+@pytest.mark.parametrize("dtype", ["uint8", "float32"])
+def test_colocalize_blobs_of_the_cast_golden_case_matches_oracle(gpu, dtype):
+    """``coloc.npz``'s ``two`` case with its uint16 ROI cast to uint8 / float32, minimum-mean thresholds."""
+    from magellanmapper_amd import colocalizer
+    roi16 = coloc_roi(COLOC, "two")
+    roi = (roi16 // 137).astype(np.uint8) if dtype == "uint8" else (roi16 / 65535).astype(np.float32)
+    blobs = COLOC["two_blobs"]
+    want = tk.oracle_flags(roi, blobs)
+    assert 0 < want.sum() < want.size
+    np.testing.assert_array_equal(colocalizer.colocalize_blobs(roi, blobs), want)
