@@ -47,7 +47,20 @@ typedef enum {
 
 /* input voxel types (reference accepts any dtype through skimage.img_as_float,
  * skimage/util/dtype.py:310-328) */
-typedef enum { MMX_U8 = 0, MMX_U16 = 1, MMX_F32 = 2, MMX_F64 = 3 } mmx_dtype;
+typedef enum { MMX_U8 = 0, MMX_U16 = 1, MMX_F32 = 2, MMX_F64 = 3, MMX_I16 = 4 } mmx_dtype;
+/* MMX_I16 (signed 16-bit voxels) was added without a version step: older libraries answer MMX_ERR_UNSUPPORTED.
+ * img_as_float of a signed type is (x + 0.5) * (2 / 65535): the image lies in [-1, 1], value span 2.  Every entry point
+ * that takes an mmx_volume takes MMX_I16 wherever it takes MMX_U16 and treats it the same way with signed values:
+ *   - the float32 LoG passes (mmx_log_batch_f32, mmx_log_batch_f32_generic, mmx_log_scales_f32, mmx_detect_batch,
+ *     mmx_zx_pack): every kernel path of uint16; the tiled path copies x ^ 0x8000 and adds each scale's constant
+ *     (-norm x the LoG of the constant image -1) before thresholds and NMS entries; its 16-bit tiles state their bound
+ *     for the value span 2 (twice mmx_tiled_q16_error_bound);
+ *   - mmx_rescore_f64: (x + 0.5) * (2 / 65535.0) in float64, the two roundings of img_as_float;
+ *   - mmx_order_stats: the signed values at the ranks;
+ *   - mmx_preprocess_*: the uint16 arithmetic on signed values; the percentile's lerp takes its difference in int16
+ *     and wraps, as NumPy's does;
+ *   - mmx_coloc_means, mmx_unmix, the min / max, resize and anti-aliasing kernels, mmx_extract_patches: float64
+ *     arithmetic on the signed values, as for uint16; a resize back to the input type truncates toward zero. */
 
 /* largest kernel radius with a register-resident (fully unrolled) column pass;
  * larger radii take the generic path.  radius = int(4*sigma + 0.5)

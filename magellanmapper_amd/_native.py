@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MMX_LIB_PATH") or os.path.join(_HERE, "libmmx_hip.so")
 
 MMX_ABI_VERSION = 21
-MMX_U8, MMX_U16, MMX_F32, MMX_F64 = 0, 1, 2, 3
+MMX_U8, MMX_U16, MMX_F32, MMX_F64, MMX_I16 = 0, 1, 2, 3, 4
 MMX_MAX_RADIUS_FAST = 24
 MMX_MAX_RADIUS_WIDE = 64
 MMX_MAX_RADIUS_GENERIC = 255

@@ -490,15 +490,21 @@ class Lane:
         # what is known about the voxels the passes will read: raw integer images [0, 1]; float images their measured
         # range; preprocessed / unmixed / rescaled blocks the bounds their arithmetic implies
         self.vrange = vrange = dvol.value_range(channel) if pre is None else pre.value_range([channel])
-        integer_voxels = pre is None and dvol.np_dtype in (np.dtype(np.uint8), np.dtype(np.uint16))
+        integer_voxels = pre is None and dvol.np_dtype in (np.dtype(np.uint8), np.dtype(np.uint16), np.dtype(np.int16))
+        # (raw int16: [-1, 1], which the tiled kernels carry as [0, 2] less a constant per scale -- a value SPAN of 2,
+        #  twice the rounding error of the 16-bit intermediates; the wide band is taken only where it still covers that
+        #  fourfold, as the library's own rule asks, else the batch keeps float32 tiles and the narrow band)
+        signed_raw = integer_voxels and dvol.np_dtype.kind == "i"
+        span = 2.0 if signed_raw else 1.0
         # volumes whose voxels are known to be non-negative and of ordinary magnitude take 16-bit intermediates: the
         # band must cover their rounding error fourfold
         # -- and their error in value units must stay inside the LoG contract (a profile whose unsharp / clip settings
         # stretch the preprocessed range past ~3.4 keeps float32 intermediates and the narrow band)
-        if (vrange is not None and vrange[0] >= 0.0 and vrange[1] <= FLOAT_TILED_RANGE[1] and EPS_REL_Q16 > EPS_REL
-                and ZX_MODE in (nat.MMX_ZX_AUTO, nat.MMX_ZX_TILED_Q16)
-                and (ZX_MODE == nat.MMX_ZX_TILED_Q16 or space.q16_bound() * (vrange[1] if not integer_voxels else 1.0)
-                     <= LOG_ABS_TOL)):
+        if (vrange is not None and (vrange[0] >= 0.0 or signed_raw) and vrange[1] <= FLOAT_TILED_RANGE[1]
+                and EPS_REL_Q16 > EPS_REL and ZX_MODE in (nat.MMX_ZX_AUTO, nat.MMX_ZX_TILED_Q16)
+                and (ZX_MODE == nat.MMX_ZX_TILED_Q16 or space.q16_bound() * (vrange[1] if not integer_voxels else span)
+                     <= LOG_ABS_TOL)
+                and (not signed_raw or 4.0 * space.q16_bound() * span <= EPS_REL_Q16 * self.vscale)):
             eps = EPS_REL_Q16 * self.vscale
         self.eps = eps
         self.d_w0, self.d_w2 = space.device_tables(dvol.tensor.device)

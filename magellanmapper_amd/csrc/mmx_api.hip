@@ -214,6 +214,7 @@ void make_weights(const mmx_volume* vol, const double* h_w0, const double* h_w2,
     double in_scale = 1.0;
     if (vol->dtype == MMX_U8) in_scale = 1.0 / 255.0;        // skimage img_as_float: x * (1/imax)
     else if (vol->dtype == MMX_U16) in_scale = 1.0 / 65535.0;
+    else if (vol->dtype == MMX_I16) in_scale = 2.0 / 65535.0;    // signed: (x + 0.5) * (2 / (imax - imin)); the 0.5 is the load's
     for (int k = 0; k <= radius; ++k) {
         w->z0[k] = (float)(h_w0[k] * in_scale);
         w->z2[k] = (float)(h_w2[k] * in_scale);
@@ -281,12 +282,21 @@ int fused_passes(const mmx_log_call& c, const mmx_route& r, const mmx_batch_geom
     { mmx_timed_scope ts(MMX_K_Y2, s);
       unsigned long long* d_mask = r.layout ? (unsigned long long*)c.d_nms_mask : nullptr;
       const float cp = r.q16 ? (float)(r.bp / 65535.0) : 0.f, cq = r.q16 ? (float)(r.bq / 32767.0) : 0.f;
+      // int16 voxels on the tiled path: the copy holds u = x ^ 0x8000 and the kernels filter 2 u / 65535 in [0, 2], the image
+      // plus one.  "reflect" keeps every tap's weight, so the LoG of that one is the same everywhere, 3 S0^2 S2 of the
+      // float64 weight sums, and -norm times it is what the Y pass takes off again before anything looks at a value.
+      float bias = 0.f;
+      if (tiled && vol->dtype == MMX_I16) {
+          double s0 = c.h_w0[0], s2 = c.h_w2[0];
+          for (int k = 1; k <= radius; ++k) { s0 += 2.0 * c.h_w0[k]; s2 += 2.0 * c.h_w2[k]; }
+          bias = (float)(c.norm * 3.0 * s0 * s0 * s2);
+      }
       if (r.y_kernel == MMX_Y_YM)
-          rc = mmx_launch_ym(c.d_blocks, n_blocks, plan, slot_elems, tyy, radius, c.d_work, cp, cq, c.d_log, d_mask,
+          rc = mmx_launch_ym(c.d_blocks, n_blocks, plan, slot_elems, tyy, radius, c.d_work, cp, cq, bias, c.d_log, d_mask,
                              c.nms_lo, c.nms_eps, s);
       else if (r.y_kernel == MMX_Y_Y6)
           rc = mmx_launch_y6(c.d_blocks, n_blocks, plan, slot_elems, tyy, radius, c.d_work,
-                             reinterpret_cast<const float*>(reinterpret_cast<const char*>(c.d_work) + plan.q_off), cp, cq,
+                             reinterpret_cast<const float*>(reinterpret_cast<const char*>(c.d_work) + plan.q_off), cp, cq, bias,
                              c.d_log, d_mask, c.nms_lo, c.nms_eps, s);
       else
           rc = mmx_launch_y2(c.d_blocks, n_blocks, g.max_ycols, slot_elems, tyy, radius, t0, t1, c.d_log, d_mask, c.nms_lo,
@@ -412,7 +422,7 @@ int mmx_zx_pack_geom(const mmx_volume* vol, const mmx_block* d_blocks, const mmx
 {
     if (!vol || !vol->d_data || !d_blocks || !h_blocks || !d_work || n_blocks < 1 || slot_elems < 1) return MMX_ERR_ARG;
     if (n_blocks > MMX_MAX_BLOCKS) return MMX_ERR_UNSUPPORTED;
-    if (vol->dtype != MMX_U8 && vol->dtype != MMX_U16 && vol->dtype != MMX_F32) return MMX_ERR_UNSUPPORTED;
+    if (!mmx_voxels_ok(vol)) return MMX_ERR_UNSUPPORTED;
     if (g.bad_block) return MMX_ERR_ARG;
     if (g.plan_status != MMX_OK) return g.plan_status;
     mmx_timed_scope ts(MMX_K_ZXPACK, stream);

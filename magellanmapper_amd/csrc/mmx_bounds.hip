@@ -12,7 +12,7 @@
 //           bins go to the group's 64-bit histogram in global memory;
 //   select: one workgroup per group, one wave per rank: scan the 256 bins, pick the bin, update prefix and remaining
 //           rank, clear the histograms, work out which ranks still share a prefix (they share a histogram).
-// Traffic: levels x bytes of the channel (1 level for uint8, 2 for uint16, 4 for float32, 8 for float64).
+// Traffic: levels x bytes of the channel (1 level for uint8, 2 for uint16 / int16, 4 for float32, 8 for float64).
 // Everything is queued on the caller's stream; nothing waits for the device.
 #include <algorithm>
 
@@ -50,6 +50,11 @@ template <> struct os_key<uint16_t> {
     using type = uint32_t; static constexpr int levels = 2;
     static __device__ __forceinline__ type make(uint16_t v, bool& nan) { return v; }
     static __device__ __forceinline__ double value(unsigned long long k) { return (double)k; }
+};
+template <> struct os_key<int16_t> {       // offset binary: x ^ 0x8000 sorts as x does
+    using type = uint32_t; static constexpr int levels = 2;
+    static __device__ __forceinline__ type make(int16_t v, bool& nan) { return (uint32_t)(uint16_t)v ^ 0x8000u; }
+    static __device__ __forceinline__ double value(unsigned long long k) { return (double)(int16_t)((uint32_t)k ^ 0x8000u); }
 };
 template <> struct os_key<float> {
     using type = uint32_t; static constexpr int levels = 4;
@@ -91,6 +96,10 @@ template <> __device__ __forceinline__ uint16_t os_elem<uint16_t>(const uint4& q
 {
     const uint32_t w = j < 2 ? q.x : j < 4 ? q.y : j < 6 ? q.z : q.w;
     return (uint16_t)(w >> (16 * (j & 1)));
+}
+template <> __device__ __forceinline__ int16_t os_elem<int16_t>(const uint4& q, int j)
+{
+    return (int16_t)os_elem<uint16_t>(q, j);
 }
 template <> __device__ __forceinline__ float os_elem<float>(const uint4& q, int j)
 {
@@ -387,7 +396,7 @@ extern "C" int mmx_order_stats(const mmx_volume* vol, int64_t nz, int64_t ny, in
     if (!vol || !vol->d_data || !d_groups || !h_groups || n_groups < 1 || !d_stats || !d_nan || !d_work)
         return MMX_ERR_ARG;
     if (nz < 1 || ny < 1 || nx < 1 || nz > 0x7fffffff || ny > 0x7fffffff || nx > 0x7fffffff) return MMX_ERR_ARG;
-    if (vol->dtype < MMX_U8 || vol->dtype > MMX_F64) return MMX_ERR_ARG;
+    if (vol->dtype < MMX_U8 || vol->dtype > MMX_I16) return MMX_ERR_ARG;
     if (((uintptr_t)d_work & 15) != 0) return MMX_ERR_ARG;
     int64_t max_voxels = 0;
     for (int g = 0; g < n_groups; ++g) {
@@ -409,6 +418,7 @@ extern "C" int mmx_order_stats(const mmx_volume* vol, int64_t nz, int64_t ny, in
         case MMX_U8: return os_run<uint8_t>(vol, ny, nx, d_groups, n_groups, max_voxels, d_stats, d_nan, hist, state, s);
         case MMX_U16: return os_run<uint16_t>(vol, ny, nx, d_groups, n_groups, max_voxels, d_stats, d_nan, hist, state, s);
         case MMX_F32: return os_run<float>(vol, ny, nx, d_groups, n_groups, max_voxels, d_stats, d_nan, hist, state, s);
+        case MMX_I16: return os_run<int16_t>(vol, ny, nx, d_groups, n_groups, max_voxels, d_stats, d_nan, hist, state, s);
         default: return os_run<double>(vol, ny, nx, d_groups, n_groups, max_voxels, d_stats, d_nan, hist, state, s);
     }
 }

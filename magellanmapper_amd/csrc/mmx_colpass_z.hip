@@ -20,6 +20,10 @@ int launch_z(const mmx_volume* vol, const mmx_block* d_blocks, int n_blocks, int
         hipLaunchKernelGGL((zpass_kernel<R, uint8_t>), grid, dim3(MMX_WG), 0, s,
                            (const uint8_t*)vol->d_data, vol->stride_z, sy, sx, d_blocks, slot_elems,
                            d_gz, d_gzz, taps);
+    else if (vol->dtype == MMX_I16)
+        hipLaunchKernelGGL((zpass_kernel<R, int16_t>), grid, dim3(MMX_WG), 0, s,
+                           (const int16_t*)vol->d_data, vol->stride_z, sy, sx, d_blocks, slot_elems,
+                           d_gz, d_gzz, taps);
     else
         return MMX_ERR_UNSUPPORTED;
     return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;

@@ -150,12 +150,15 @@ int launch_y2(const mmx_block* d_blocks, int n_blocks, int max_cols, int64_t slo
 // (mmx_entries.h, MMX_MASK_QUADS).
 // Q16: one dword per voxel in the tile, P = unorm16 (low half), Q = snorm16 (high half); their scales ride in the
 // weights.  Half the bytes and half the load instructions.
-template <int R, bool MASK, bool Q16>
+// BIAS: int16 voxels, whose copy holds x ^ 0x8000 -- the image as [0, 2] -- owe every output the scale's constant
+// (-norm x the LoG of the constant image -1: SciPy's truncated kernels do not sum to zero), added before the threshold
+// and the entries see the value.
+template <int R, bool MASK, bool Q16, bool BIAS = false>
 __global__ void __launch_bounds__(MMX_WG)
 y6_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile_stride,
           const float* __restrict__ gp, const float* __restrict__ gq,
           float* __restrict__ out, y2_taps taps,
-          unsigned long long* __restrict__ mask, float nms_lo, float nms_eps)
+          unsigned long long* __restrict__ mask, float nms_lo, float nms_eps, float bias)
 {
     constexpr int N = 2 * R + 1;
     constexpr int M = N + kPrefetch;
@@ -230,7 +233,7 @@ y6_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile
             }
         }
         a2 += b2;
-        const float acc = a2.x + a2.y;
+        const float acc = BIAS ? (a2.x + a2.y) + bias : a2.x + a2.y;
         const unsigned long long ab = MASK ? mmx_above_word(real, acc, nms_lo) : ~0ull;
         if (ab && real) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc), rsw, ooff, woff, 0);
         woff += row_b;
@@ -283,7 +286,7 @@ y6_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile
 
 template <int R>
 int launch_y6(const mmx_block* d_blocks, int n_blocks, const mmx_zx6_plan& plan, int64_t slot_elems,
-              const mmx_taps_f32& taps, const float* d_p, const float* d_q, float cp, float cq, float* d_log,
+              const mmx_taps_f32& taps, const float* d_p, const float* d_q, float cp, float cq, float bias, float* d_log,
               unsigned long long* d_mask, float nms_lo, float nms_eps, hipStream_t s)
 {
     dim3 grid(plan.max_tiles, n_blocks);
@@ -291,8 +294,14 @@ int launch_y6(const mmx_block* d_blocks, int n_blocks, const mmx_zx6_plan& plan,
     const bool q16 = cp > 0.f;
     for (int k = 0; k <= R; ++k) pk.w[k] = q16 ? (v2f){taps.w2[k] * cp, taps.w0[k] * cq} : (v2f){taps.w2[k], taps.w0[k]};
 #define MMX_Y6_LAUNCH(MK, QQ) \
-    hipLaunchKernelGGL((y6_kernel<R, MK, QQ>), grid, dim3(MMX_WG), 0, s, d_blocks, slot_elems, plan.tile_stride, d_p, d_q, \
-                       d_log, pk, d_mask, nms_lo, nms_eps)
+    do { \
+        if (bias != 0.f) \
+            hipLaunchKernelGGL((y6_kernel<R, MK, QQ, true>), grid, dim3(MMX_WG), 0, s, d_blocks, slot_elems, plan.tile_stride, \
+                               d_p, d_q, d_log, pk, d_mask, nms_lo, nms_eps, bias); \
+        else \
+            hipLaunchKernelGGL((y6_kernel<R, MK, QQ>), grid, dim3(MMX_WG), 0, s, d_blocks, slot_elems, plan.tile_stride, \
+                               d_p, d_q, d_log, pk, d_mask, nms_lo, nms_eps, bias); \
+    } while (0)
     if (d_mask) { if (q16) MMX_Y6_LAUNCH(true, true); else MMX_Y6_LAUNCH(true, false); }
     else        { if (q16) MMX_Y6_LAUNCH(false, true); else MMX_Y6_LAUNCH(false, false); }
 #undef MMX_Y6_LAUNCH
@@ -315,12 +324,12 @@ int mmx_launch_y2(const mmx_block* d_blocks, int n_blocks, int max_cols, int64_t
 }
 
 int mmx_launch_y6(const mmx_block* d_blocks, int n_blocks, const mmx_zx6_plan& plan, int64_t slot_elems,
-                  const mmx_taps_f32& taps, int radius, const float* d_p, const float* d_q, float cp, float cq,
+                  const mmx_taps_f32& taps, int radius, const float* d_p, const float* d_q, float cp, float cq, float bias,
                   float* d_log, unsigned long long* d_mask, float nms_lo, float nms_eps, hipStream_t stream)
 {
     if (!mmx_ring_radius(radius)) return MMX_ERR_UNSUPPORTED;
     switch (radius) {
-#define X(R) case R: return launch_y6<R>(d_blocks, n_blocks, plan, slot_elems, taps, d_p, d_q, cp, cq, d_log, d_mask, nms_lo, nms_eps, stream);
+#define X(R) case R: return launch_y6<R>(d_blocks, n_blocks, plan, slot_elems, taps, d_p, d_q, cp, cq, bias, d_log, d_mask, nms_lo, nms_eps, stream);
         MMX_FOR_EACH_RADIUS(X)
 #undef X
         default: return MMX_ERR_UNSUPPORTED;

@@ -313,6 +313,7 @@ int launch_zx2(const mmx_volume* vol, const mmx_block* d_blocks, int n_blocks, i
     if (vol->dtype == MMX_U16) MMX_ZX2_LAUNCH(uint16_t);
     else if (vol->dtype == MMX_F32) MMX_ZX2_LAUNCH(float);
     else if (vol->dtype == MMX_U8) MMX_ZX2_LAUNCH(uint8_t);
+    else if (vol->dtype == MMX_I16) MMX_ZX2_LAUNCH(int16_t);
     else return MMX_ERR_UNSUPPORTED;
 #undef MMX_ZX2_LAUNCH
     return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;

@@ -942,6 +942,10 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
 // fills units 64 p .. 64 p + 63 of the row tile, the unit order of the copy is the same.  Rows up to 512 voxels run the
 // one-panel form (WIDE = false): the same statements with x0 = 0 and the row's own unit count, no loop and no second
 // barrier (C3's rows are 261 voxels: profiles/r10_c3_ab.txt has its zxpack times against the kernel without panels).
+// (int16 voxels leave as u = x ^ 0x8000, the order-preserving uint16 -- the uint16 pieces and kernels serve them too:
+//  zx4's weights carry 2 x 65536 / 65535 for them and the Y pass takes the constant off that the offset adds)
+template <typename InT> struct pack_flip { static constexpr unsigned one = 0u, two = 0u; };
+template <> struct pack_flip<int16_t> { static constexpr unsigned one = 0x8000u, two = 0x80008000u; };
 template <typename InT, bool WIDE>
 __global__ void __launch_bounds__(256)
 zx6_pack_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y, int64_t stride_x,
@@ -985,10 +989,11 @@ zx6_pack_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
                     if (have[i][h] && z < bd.nz) {
                         if (x + 3 < nx) {
                             v[i][h] = *reinterpret_cast<const v2u*>(row + x);
+                            if constexpr (pack_flip<InT>::two != 0u) v[i][h] ^= (v2u){pack_flip<InT>::two, pack_flip<InT>::two};
                         } else {
                             unsigned e[4];
 #pragma unroll
-                            for (int j = 0; j < 4; ++j) e[j] = x + j < nx ? (unsigned)row[x + j] : 0u;
+                            for (int j = 0; j < 4; ++j) e[j] = x + j < nx ? ((unsigned)row[x + j] & 0xffffu) ^ pack_flip<InT>::one : 0u;
                             v[i][h] = (v2u){e[0] | (e[1] << 16), e[2] | (e[3] << 16)};
                         }
                     }
@@ -1007,7 +1012,8 @@ zx6_pack_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
                 for (int x = lane * 4; x < 8 * nch8; x += 256) *reinterpret_cast<v2u*>(&tile[r][x]) = (v2u){0u, 0u};
             } else {
                 for (int x = lane; x < 8 * nch8; x += 64)
-                    tile[r][x] = x < nx ? (uint16_t)((unsigned)src[(int64_t)z * stride_z + (int64_t)x * stride_x] << (sizeof(InT) == 1 ? 8 : 0))
+                    tile[r][x] = x < nx ? (uint16_t)(((unsigned)src[(int64_t)z * stride_z + (int64_t)x * stride_x] << (sizeof(InT) == 1 ? 8 : 0)) ^
+                                                     pack_flip<InT>::one)
                                            : (uint16_t)0;     // (uint8 voxels go to the HIGH byte: the exact high float16 piece carries them)
             }
         }
@@ -1138,7 +1144,8 @@ int launch_zx6(const mmx_volume* vol, const mmx_block* d_blocks, const mmx_block
     cfg.radius = radius;
     // the pieces carry v / 2^16 of the widened voxel: skimage's img_as_float scale on top
     cfg.xscale = vol->dtype == MMX_U16 ? (float)(65536.0 / 65535.0) :
-                 (vol->dtype == MMX_U8 ? (float)(65536.0 / (255.0 * 256.0)) : 1.f);      // (float voxels: as they are)
+                 (vol->dtype == MMX_U8 ? (float)(65536.0 / (255.0 * 256.0)) :
+                 (vol->dtype == MMX_I16 ? (float)(2.0 * 65536.0 / 65535.0) : 1.f));     // (float voxels: as they are)
     cfg.staged = 2;
     cfg.qp = qp; cfg.qq = qq;
     // two column tiles per wave (zx4_kernel's NTW): 16-bit tiles of integer voxels, 8 < radius <= 16; tile rows past
@@ -1270,6 +1277,9 @@ int mmx_launch_zx6_pack(const mmx_volume* vol, const mmx_block* d_blocks, const 
     } else if (vol->dtype == MMX_U16) {
         if (wide) launch(zx6_pack_kernel<uint16_t, true>, (const uint16_t*)vol->d_data);
         else launch(zx6_pack_kernel<uint16_t, false>, (const uint16_t*)vol->d_data);
+    } else if (vol->dtype == MMX_I16) {
+        if (wide) launch(zx6_pack_kernel<int16_t, true>, (const int16_t*)vol->d_data);
+        else launch(zx6_pack_kernel<int16_t, false>, (const int16_t*)vol->d_data);
     } else {
         if (wide) launch(zx6_pack_kernel<uint8_t, true>, (const uint8_t*)vol->d_data);
         else launch(zx6_pack_kernel<uint8_t, false>, (const uint8_t*)vol->d_data);

@@ -80,6 +80,7 @@ extern "C" int mmx_extract_patches(const mmx_volume* vol, const int32_t* d_zyx, 
     switch (vol->dtype) {
         case MMX_U8:  return patches_launch<uint8_t, double>(vol, d_zyx, n, size, d_out, d_out32, s);
         case MMX_U16: return patches_launch<uint16_t, double>(vol, d_zyx, n, size, d_out, d_out32, s);
+        case MMX_I16: return patches_launch<int16_t, double>(vol, d_zyx, n, size, d_out, d_out32, s);
         case MMX_F32: return patches_launch<float, float>(vol, d_zyx, n, size, d_out, d_out32, s);
         case MMX_F64: return patches_launch<double, double>(vol, d_zyx, n, size, d_out, d_out32, s);
         default:      return MMX_ERR_ARG;

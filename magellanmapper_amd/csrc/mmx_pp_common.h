@@ -55,12 +55,17 @@ __device__ __forceinline__ double pp_lerp(int a, int b, double t)
 // integer and an interpolated one).  Otherwise the plain `/` is used.
 // An *identity* tile (vmin == vmax: the reference leaves the voxels alone) runs the same formula with
 // vmin = 0, vmax = +inf, span = 1, which returns x exactly.
-struct pp_sat {
-    double vmin, vmax, span, rcp;
+// SIGNED (int16 voxels): the identity form must not clip negative voxels at its stand-in vmin = 0, so the clip's lower
+// bound is a member of its own (-inf on an identity tile, vmin otherwise); the unsigned form is as it always was.
+template <bool SIGNED>
+struct pp_sat_t {
+    double vmin, vmax, span, rcp, clo;
     int identity, fast;
+    __device__ __forceinline__ double lower() const { return SIGNED ? clo : vmin; }
     __device__ __forceinline__ void finish()
     {
-        if (identity) { vmin = 0.; vmax = __builtin_inf(); span = 1.; }
+        clo = vmin;
+        if (identity) { vmin = 0.; vmax = __builtin_inf(); span = 1.; clo = -__builtin_inf(); }
         fast = span > 0x1p-200 && span < 0x1p200;
         double r = __builtin_amdgcn_rcp(span);
         r = __builtin_fma(__builtin_fma(-span, r, 1.0), r, r);
@@ -69,14 +74,37 @@ struct pp_sat {
     }
     __device__ __forceinline__ double operator()(double raw) const      // requires `fast`
     {
-        const double num = pp_clip(raw, vmin, vmax) - vmin;
+        const double num = pp_clip(raw, lower(), vmax) - vmin;
         const double q = num * rcp;
         const double e = __builtin_fma(-span, q, num);
         return __builtin_fma(e, rcp, q);
     }
     __device__ __forceinline__ double plain(double raw) const            // any magnitude
     {
-        return (pp_clip(raw, vmin, vmax) - vmin) / span;
+        return (pp_clip(raw, lower(), vmax) - vmin) / span;
+    }
+};
+using pp_sat = pp_sat_t<false>;
+
+// The voxel types of the integer kernels.  Histograms, the radix select and every "no voxel" sentinel work on a
+// non-negative, order-preserving KEY: the value itself for the unsigned types, value + 32768 (= x ^ 0x8000 as uint16) for
+// int16; value() takes a key back.  lerp: NumPy's _lerp on the two order statistics, whose difference NumPy takes IN
+// THE VOXEL TYPE -- for int16 it wraps, and np.percentile returns what follows from the wrapped difference.
+template <typename InT> struct pp_vox {
+    static constexpr int bias = 0;
+    static constexpr bool is_signed = false;
+    static __device__ __forceinline__ double lerp(int ka, int kb, double t) { return pp_lerp(ka, kb, t); }
+};
+template <> struct pp_vox<int16_t> {
+    static constexpr int bias = 32768;
+    static constexpr bool is_signed = true;
+    static __device__ __forceinline__ double lerp(int ka, int kb, double t)
+    {
+        const int a = ka - bias, b = kb - bias;
+        const double d = (double)(int16_t)(b - a);
+        double r = (double)a + d * t;
+        if (t >= 0.5) r = (double)b - d * (1.0 - t);
+        return r;
     }
 };
 

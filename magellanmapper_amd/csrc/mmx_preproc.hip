@@ -94,7 +94,7 @@ pp_fast_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
             const int row = rb + j * rpi < nrows ? rb + j * rpi : 0;
             const int z = (int)(((float)row + 0.5f) * inv_ny);
             const int y = row - z * ny;
-            v[j] = (int)src[z * sz + y * sy + (r0 < nrows ? x : 0) * sx];
+            v[j] = (int)src[z * sz + y * sy + (r0 < nrows ? x : 0) * sx] + pp_vox<InT>::bias;      // (keys)
         }
 #pragma unroll
         for (int j = 0; j < PP_NB_LOAD; ++j) {
@@ -139,11 +139,11 @@ pp_fast_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
     __syncthreads();
     PP_STAMP();
 
-    pp_sat S;
+    pp_sat_t<pp_vox<InT>::is_signed> S;
     double info_vmin, info_vmax;
     {
-        const double vmin = pp_lerp(s_val[0], s_val[1], qc.lo_gamma);
-        double vmax = pp_lerp(s_val[2], s_val[3], qc.hi_gamma);
+        const double vmin = pp_vox<InT>::lerp(s_val[0], s_val[1], qc.lo_gamma);
+        double vmax = pp_vox<InT>::lerp(s_val[2], s_val[3], qc.hi_gamma);
         S.identity = vmin == vmax;
         if (vmax < A.max_thresh) vmax = A.max_thresh;
         S.vmin = vmin; S.vmax = vmax; S.span = vmax - vmin;
@@ -158,7 +158,7 @@ pp_fast_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
 #pragma unroll
         for (int j = 0; j < PP_NB; ++j) {
             const int row = rb + j * rpi < nrows ? rb + j * rpi : rb;
-            s[j] = S((double)(int)raw[row * nx + x]);
+            s[j] = S((double)((int)raw[row * nx + x] - pp_vox<InT>::bias));
         }
 #pragma unroll
         for (int j = 0; j < PP_NB; ++j) {
@@ -172,7 +172,7 @@ pp_fast_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
     if (!S.fast) {                 // extreme span (never with integer voxels): plain division, same stores
         part = 0.;
         for (int row = r0; row < nrows; row += rpi) {
-            const double sv = S.plain((double)(int)raw[row * nx + x]);
+            const double sv = S.plain((double)((int)raw[row * nx + x] - pp_vox<InT>::bias));
             part += sv;
             tile[row * px + x] = pp_clip(sv, A.clip_min, A.clip_max);
         }
@@ -189,7 +189,7 @@ pp_fast_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
             const double tol = 1e-9 * (fabs(A.ero_thr) > 1. ? fabs(A.ero_thr) : 1.);
             if (!S.identity && fabs(mean - A.ero_thr) <= tol) {
                 // knife edge: NumPy's own summation order decides
-                auto val = [&](int i) { return S.plain((double)(int)raw[i]); };
+                auto val = [&](int i) { return S.plain((double)((int)raw[i] - pp_vox<InT>::bias)); };
                 mean = pp_pairwise(val, n, &s_stack) / (double)n;
                 flags |= MMX_PP_EXACT_MEAN;
             }
@@ -242,7 +242,7 @@ pp_fast_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
             const int row = rb + j * rpi < nrows ? rb + j * rpi : rb;
             const double blur = tile[row * px + x];
             if (A.do_unsharp) {
-                const double den = pp_clip(S((double)(int)raw[row * nx + x]), A.clip_min, A.clip_max);
+                const double den = pp_clip(S((double)((int)raw[row * nx + x] - pp_vox<InT>::bias)), A.clip_min, A.clip_max);
                 const double m = A.strength * blur;
                 const double hp = den - m;
                 o[j] = den + hp;
@@ -253,7 +253,7 @@ pp_fast_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
         if (A.do_unsharp && !S.fast) {
             for (int j = 0; j < PP_NB; ++j) {
                 const int row = rb + j * rpi < nrows ? rb + j * rpi : rb;
-                const double den = pp_clip(S.plain((double)(int)raw[row * nx + x]), A.clip_min, A.clip_max);
+                const double den = pp_clip(S.plain((double)((int)raw[row * nx + x] - pp_vox<InT>::bias)), A.clip_min, A.clip_max);
                 const double m = A.strength * tile[row * px + x];
                 const double hp = den - m;
                 o[j] = den + hp;
@@ -328,7 +328,7 @@ pp_mid_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
     double* buf = scratch + sb.scratch_off;
     auto raw = [&](int i) {                 // (rare paths only: two integer divisions)
         const int t = i / nx, x = i - t * nx, z = t / ny, y = t - z * ny;
-        return (int)src[z * sz + y * sy + x * sx];
+        return (int)src[z * sz + y * sy + x * sx] + pp_vox<InT>::bias;         // (keys, as raw_at)
     };
     // element-wise stages: a lane keeps its x and walks rows (z*ny + y) in steps of rpi, no per-voxel
     // index arithmetic; rows < 4096, so the float reciprocal gives row / ny exactly
@@ -340,7 +340,7 @@ pp_mid_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
     auto raw_at = [&](int row) {
         const int z = (int)(((float)row + 0.5f) * inv_ny);
         const int y = row - z * ny;
-        return (int)src[z * sz + y * sy + x * sx];
+        return (int)src[z * sz + y * sy + x * sx] + pp_vox<InT>::bias;
     };
 
     for (int i = tid; i < PP_HIST; i += PP_WG_MID) hist[i] = 0;
@@ -396,11 +396,11 @@ pp_mid_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
     }
     __syncthreads();
 
-    pp_sat S;
+    pp_sat_t<pp_vox<InT>::is_signed> S;
     double info_vmin, info_vmax;
     {
-        const double vmin = pp_lerp(s_val[0], s_val[1], qc.lo_gamma);
-        double vmax = pp_lerp(s_val[2], s_val[3], qc.hi_gamma);
+        const double vmin = pp_vox<InT>::lerp(s_val[0], s_val[1], qc.lo_gamma);
+        double vmax = pp_vox<InT>::lerp(s_val[2], s_val[3], qc.hi_gamma);
         S.identity = vmin == vmax;
         if (vmax < A.max_thresh) vmax = A.max_thresh;
         S.vmin = vmin; S.vmax = vmax; S.span = vmax - vmin;
@@ -416,7 +416,7 @@ pp_mid_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             if (vv[j] < 0) continue;
-            const double rv = (double)vv[j];
+            const double rv = (double)(vv[j] - pp_vox<InT>::bias);
             const double s = S.fast ? S(rv) : S.plain(rv);
             part += s;
             buf[(rb + j * rpi) * nx + x] = pp_clip(s, A.clip_min, A.clip_max);
@@ -433,7 +433,7 @@ pp_mid_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
         if (A.do_erosion) {
             const double tol = 1e-9 * (fabs(A.ero_thr) > 1. ? fabs(A.ero_thr) : 1.);
             if (!S.identity && fabs(mean - A.ero_thr) <= tol) {
-                auto val = [&](int i) { return S.plain((double)raw(i)); };
+                auto val = [&](int i) { return S.plain((double)(raw(i) - pp_vox<InT>::bias)); };
                 mean = pp_pairwise(val, n, &s_stack) / (double)n;
                 flags |= MMX_PP_EXACT_MEAN;
             }
@@ -507,7 +507,7 @@ pp_mid_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
         const int i = row * nx + x;
         double o;
         if (A.do_unsharp) {
-            const double rv = (double)vv[j];
+            const double rv = (double)(vv[j] - pp_vox<InT>::bias);
             const double sv = S.fast ? S(rv) : S.plain(rv);
             const double den = pp_clip(sv, A.clip_min, A.clip_max);
             const double m = A.strength * bl8[j];
@@ -625,7 +625,7 @@ pp_generic_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t s
         for (int64_t i = tid; i < n; i += PP_WG_GENERIC) {
             const int v = raw(i);
             bufA[i] = (double)v;
-            atomicAdd(&hist[v >> 8], 1u);
+            atomicAdd(&hist[(v + pp_vox<InT>::bias) >> 8], 1u);
         }
         __syncthreads();
         if (wave < 4) {
@@ -638,7 +638,7 @@ pp_generic_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t s
         {
             const int b0 = s_bin[0], b1 = s_bin[1], b2 = s_bin[2], b3 = s_bin[3];
             for (int64_t i = tid; i < n; i += PP_WG_GENERIC) {
-                const int v = (int)bufA[i];
+                const int v = (int)bufA[i] + pp_vox<InT>::bias;
                 const int hi = v >> 8, lo = v & 255;
                 if (hi == b0) atomicAdd(&hist[256 + lo], 1u);
                 if (hi == b1) atomicAdd(&hist[512 + lo], 1u);
@@ -654,14 +654,18 @@ pp_generic_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t s
         }
         __syncthreads();
 #pragma unroll
-        for (int w = 0; w < 4; ++w) q_val[w] = (double)s_val[w];
+        for (int w = 0; w < 4; ++w) q_val[w] = (double)(s_val[w] - pp_vox<InT>::bias);
     }
 
-    pp_sat S;
+    pp_sat_t<pp_vox<InT>::is_signed> S;
     double info_vmin, info_vmax;
     {
-        const double vmin = pp_lerp(q_val[0], q_val[1], qc.lo_gamma);
+        double vmin = pp_lerp(q_val[0], q_val[1], qc.lo_gamma);
         double vmax = pp_lerp(q_val[2], q_val[3], qc.hi_gamma);
+        if constexpr (pp_vox<InT>::is_signed) {       // (the difference in the voxel type: pp_vox)
+            vmin = pp_vox<InT>::lerp(s_val[0], s_val[1], qc.lo_gamma);
+            vmax = pp_vox<InT>::lerp(s_val[2], s_val[3], qc.hi_gamma);
+        }
         S.identity = vmin == vmax;
         if (vmax < A.max_thresh) vmax = A.max_thresh;
         S.vmin = vmin; S.vmax = vmax; S.span = vmax - vmin;
@@ -883,7 +887,7 @@ static int pp_check(const mmx_volume* vol, const mmx_subblock* d_subs, const mmx
     if (p->radius != PP_R) return MMX_ERR_UNSUPPORTED;
     // (float64 images: the one-output-per-lane kernel of the generic entry only; float32 images compute in float32 in
     //  the reference -- another arithmetic, not built)
-    if (vol->dtype != MMX_U8 && vol->dtype != MMX_U16 && vol->dtype != MMX_F64) return MMX_ERR_UNSUPPORTED;
+    if (vol->dtype != MMX_U8 && vol->dtype != MMX_U16 && vol->dtype != MMX_I16 && vol->dtype != MMX_F64) return MMX_ERR_UNSUPPORTED;
     for (int i = 0; i < n_subs; ++i) {
         const mmx_subblock& b = h_subs[i];
         if (b.nz < 1 || b.ny < 1 || b.nx < 1 || b.qclass < 0 || b.qclass >= n_qc || b.src_off < 0 || b.dst_off < 0)
@@ -958,6 +962,7 @@ int mmx_preprocess_batch_mode(const mmx_volume* vol, const mmx_subblock* d_subs,
                            d_out32, d_out64, d_info);                                                     \
     } while (0)
     if (vol->dtype == MMX_U16) { if (small) PP_FAST_LAUNCH(uint16_t, 256); else PP_FAST_LAUNCH(uint16_t, PP_WG); }
+    else if (vol->dtype == MMX_I16) { if (small) PP_FAST_LAUNCH(int16_t, 256); else PP_FAST_LAUNCH(int16_t, PP_WG); }
     else { if (small) PP_FAST_LAUNCH(uint8_t, 256); else PP_FAST_LAUNCH(uint8_t, PP_WG); }
 #undef PP_FAST_LAUNCH
     return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
@@ -1012,6 +1017,13 @@ int mmx_preprocess_batch_generic(const mmx_volume* vol, const mmx_subblock* d_su
             hipLaunchKernelGGL(k, dim3(n_subs), dim3(PP_WG_MID), lds, s, (const uint16_t*)vol->d_data,
                                vol->stride_z, vol->stride_y, vol->stride_x, d_subs, d_qclasses, d_weights, A,
                                d_out32, d_out64, d_info, d_scratch);
+        } else if (vol->dtype == MMX_I16) {
+            auto k = pp_mid_kernel<int16_t>;
+            if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+                return MMX_ERR_HIP;
+            hipLaunchKernelGGL(k, dim3(n_subs), dim3(PP_WG_MID), lds, s, (const int16_t*)vol->d_data,
+                               vol->stride_z, vol->stride_y, vol->stride_x, d_subs, d_qclasses, d_weights, A,
+                               d_out32, d_out64, d_info, d_scratch);
         } else {
             auto k = pp_mid_kernel<uint8_t>;
             if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
@@ -1029,6 +1041,10 @@ int mmx_preprocess_batch_generic(const mmx_volume* vol, const mmx_subblock* d_su
     else if (vol->dtype == MMX_U16)
         hipLaunchKernelGGL(pp_generic_kernel<uint16_t>, dim3(n_subs), dim3(PP_WG_GENERIC), 0, s,
                            (const uint16_t*)vol->d_data, vol->stride_z, vol->stride_y, vol->stride_x, d_subs,
+                           d_qclasses, d_weights, A, d_out32, d_out64, d_info, d_scratch);
+    else if (vol->dtype == MMX_I16)
+        hipLaunchKernelGGL(pp_generic_kernel<int16_t>, dim3(n_subs), dim3(PP_WG_GENERIC), 0, s,
+                           (const int16_t*)vol->d_data, vol->stride_z, vol->stride_y, vol->stride_x, d_subs,
                            d_qclasses, d_weights, A, d_out32, d_out64, d_info, d_scratch);
     else
         hipLaunchKernelGGL(pp_generic_kernel<uint8_t>, dim3(n_subs), dim3(PP_WG_GENERIC), 0, s,

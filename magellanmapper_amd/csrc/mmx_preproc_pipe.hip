@@ -200,7 +200,7 @@ pp_retile_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx
 #pragma unroll
             for (int k = 0; k < PPR_NK; ++k) {
                 if constexpr (sizeof(InT) == 1) v[k] = (int)(unsigned)__builtin_amdgcn_raw_buffer_load_b8(src, scol[k], soff, 0);
-                else v[k] = (int)(unsigned)__builtin_amdgcn_raw_buffer_load_b16(src, scol[k], soff, 0);
+                else v[k] = (int)(unsigned)__builtin_amdgcn_raw_buffer_load_b16(src, scol[k], soff, 0) ^ pp_vox<InT>::bias;   // (the copy holds keys)
             }
 #pragma unroll
             for (int k = 0; k < PPR_NK; ++k)
@@ -253,6 +253,9 @@ struct pp_hist2 {
     }
 };
 
+// SIGNED: the copy holds the keys of int16 voxels (pp_vox<int16_t>): the order statistics come back as keys, the lerp
+// wraps as NumPy's, and the integer sums run on keys against vmin / vmax moved by the same 32768.
+template <bool SIGNED>
 __global__ void __launch_bounds__(PPS_WG)
 pp_stats_kernel(const uint16_t* __restrict__ copy, const int64_t* __restrict__ copy_off,
                 const mmx_subblock* __restrict__ subs, int n_subs,
@@ -341,13 +344,16 @@ pp_stats_kernel(const uint16_t* __restrict__ copy, const int64_t* __restrict__ c
     // (sum over vmin <= v <= vmax of (v - floor(vmin)) - n_mid frac(vmin) + n_hi span) / span up to roundings of
     // 1e-16 of itself: integer sums.  Within 1e-9 of the threshold the blur kernel, which
     // holds the voxels in LDS, re-sums in NumPy's pairwise order (MMX_PP_KNIFE: internal, cleared there).
-    const double vmin = pp_lerp(s_val[0], s_val[1], qc.lo_gamma);
-    double vmax = pp_lerp(s_val[2], s_val[3], qc.hi_gamma);
+    using vx = pp_vox<typename std::conditional<SIGNED, int16_t, uint16_t>::type>;
+    const double vmin = vx::lerp(s_val[0], s_val[1], qc.lo_gamma);
+    double vmax = vx::lerp(s_val[2], s_val[3], qc.hi_gamma);
     const bool identity = vmin == vmax;
     if (vmax < A.max_thresh) vmax = A.max_thresh;
-    const int v0 = (int)floor(vmin);
+    // (the sums below only gate the erosion, to 1e-9: the moved bounds may round in their last bit)
+    const double kmin = SIGNED ? vmin + (double)vx::bias : vmin, kmax = SIGNED ? vmax + (double)vx::bias : vmax;
+    const int v0 = (int)floor(kmin);
     // (integer voxels: v >= vmin <=> v >= ceil(vmin), v <= vmax <=> v <= floor(vmax); vmax may exceed every voxel)
-    const int ic_lo = (int)ceil(vmin), ic_hi = vmax >= 65535.0 ? 65535 : (int)floor(vmax);
+    const int ic_lo = (int)ceil(kmin), ic_hi = kmax >= 65535.0 ? 65535 : (int)floor(kmax);
     uint32_t i_mid = 0, n_mid = 0, n_hi = 0, i_all = 0;
     auto tally = [&](int vv) {
         const bool mid = vv >= ic_lo && vv <= ic_hi;
@@ -375,8 +381,8 @@ pp_stats_kernel(const uint16_t* __restrict__ copy, const int64_t* __restrict__ c
         for (int w = 0; w < PPS_WG / 64; ++w) for (int q = 0; q < 4; ++q) t[q] += s_sum[w][q];
         const double nd = (double)n, span = vmax - vmin;
         double mean;
-        if (identity) mean = (double)t[3] / nd;
-        else mean = (((double)t[0] - (double)t[1] * (vmin - (double)v0)) + (double)t[2] * span) / span / nd;
+        if (identity) mean = SIGNED ? ((double)t[3] - (double)vx::bias * nd) / nd : (double)t[3] / nd;
+        else mean = (((double)t[0] - (double)t[1] * (kmin - (double)v0)) + (double)t[2] * span) / span / nd;
         int fl = identity ? MMX_PP_IDENTITY : 0;
         if (A.do_erosion) {
             const double tol = 1e-9 * (fabs(A.ero_thr) > 1. ? fabs(A.ero_thr) : 1.);
@@ -445,6 +451,7 @@ __device__ __forceinline__ void pp_line_addr(const pp_geom& g, int axis, int l, 
     else { tbase = t * g.ny * g.px + x; tstride = g.px; rbase = t * g.ny * g.nx + x; rstride = g.nx; }
 }
 
+template <bool SIGNED>
 __global__ void __launch_bounds__(PPB_WG)
 pp_blur_kernel(const uint16_t* __restrict__ copy, const int64_t* __restrict__ copy_off,
                const mmx_subblock* __restrict__ subs, int n_subs, int tiles_per_wg,
@@ -495,7 +502,8 @@ pp_blur_kernel(const uint16_t* __restrict__ copy, const int64_t* __restrict__ co
         pp_geom g;
         g.nz = sb.nz; g.ny = sb.ny; g.nx = sb.nx; g.px = sb.nx | 1; g.n = sb.nz * sb.ny * sb.nx; g.nrows = sb.nz * sb.ny;
         const float inv_nx = 1.0f / (float)g.nx, inv_ny = 1.0f / (float)g.ny;
-        pp_sat S;
+        constexpr int kBias = SIGNED ? 32768 : 0;          // (raw holds keys: pp_vox)
+        pp_sat_t<SIGNED> S;
         S.identity = inf.flags & MMX_PP_IDENTITY;
         S.vmin = inf.vmin; S.vmax = inf.vmax; S.span = inf.vmax - inf.vmin;
         S.finish();
@@ -503,11 +511,12 @@ pp_blur_kernel(const uint16_t* __restrict__ copy, const int64_t* __restrict__ co
         if (tid == 0) {                 // (read after the passes' barriers; rewritten after this tile's last barrier)
             s_par[0] = A.clip_min; s_par[1] = A.clip_max; s_par[2] = A.strength;
             s_par[3] = S.vmin; s_par[4] = S.vmax; s_par[5] = S.span; s_par[6] = S.rcp;
+            if constexpr (SIGNED) s_par[7] = S.clo;
         }
         const double cmin = A.clip_min, cmax = A.clip_max;
         // (S.fast holds for every tile of integer voxels: 2^-200 < span <= 65535; the plain division is kept for form)
-        auto sat_fast = [&](int rv) { return S((double)rv); };
-        auto sat_plain = [&](int rv) { return S.plain((double)rv); };
+        auto sat_fast = [&](int rv) { return S((double)(rv - kBias)); };
+        auto sat_plain = [&](int rv) { return S.plain((double)(rv - kBias)); };
         PP_TICK(1, 1);
 
         // ---- Gaussian blur, axis 0, 1, 2 (scipy gaussian_filter order); the first pass reads the voxels
@@ -612,7 +621,7 @@ pp_blur_kernel(const uint16_t* __restrict__ copy, const int64_t* __restrict__ co
         int flags = inf.flags;
         if (flags & MMX_PP_KNIFE) {
             if (tid == 0) {
-                auto val = [&](int i) { return S.plain((double)(int)raw[i]); };
+                auto val = [&](int i) { return S.plain((double)((int)raw[i] - kBias)); };
                 const double mean = pp_pairwise(val, g.n, &s_stack) / (double)g.n;
                 int fl = (flags & ~MMX_PP_KNIFE) | MMX_PP_EXACT_MEAN;
                 if (mean > A.ero_thr) fl |= MMX_PP_ERODED;
@@ -664,8 +673,9 @@ pp_blur_kernel(const uint16_t* __restrict__ copy, const int64_t* __restrict__ co
             pp_store_f64(o64, off << 3, o);
             pp_store_f32(o32, off << 2, (float)o);
         };
-        pp_sat Sv;                                        // the same numbers as S, in vector registers
+        pp_sat_t<SIGNED> Sv;                              // the same numbers as S, in vector registers
         Sv.vmin = s_par[3]; Sv.vmax = s_par[4]; Sv.span = s_par[5]; Sv.rcp = s_par[6]; Sv.identity = 0; Sv.fast = 1;
+        if constexpr (SIGNED) Sv.clo = s_par[7];
         const double v_cmin = s_par[0], v_cmax = s_par[1], v_str = s_par[2];
         // PPB_NB voxels: all LDS reads first, then the arithmetic, then LDS writes or stores
         auto batch = [&](walk& w, auto unsharp, auto totile) {
@@ -681,7 +691,7 @@ pp_blur_kernel(const uint16_t* __restrict__ copy, const int64_t* __restrict__ co
             }
 #pragma unroll
             for (int j = 0; j < PPB_NB; ++j) {
-                const double den = pp_clip(Sv((double)rv[j]), v_cmin, v_cmax);
+                const double den = pp_clip(Sv((double)(rv[j] - kBias)), v_cmin, v_cmax);
                 if (unsharp.value) {
                     const double m = v_str * bl[j];
                     const double hp = den - m;
@@ -800,7 +810,7 @@ int mmx_launch_pp_pipe(const mmx_volume* vol, const mmx_subblock* d_subs, const 
         if ((int64_t)b.nz * A.dst_sz >= (1ll << 28)) return MMX_ERR_UNSUPPORTED;
     }
     if (tile_b + raw_b > MMX_PP_MAX_LDS - 1024) return MMX_ERR_UNSUPPORTED;
-    if (vol->dtype != MMX_U16 && vol->dtype != MMX_U8) return MMX_ERR_UNSUPPORTED;
+    if (vol->dtype != MMX_U16 && vol->dtype != MMX_U8 && vol->dtype != MMX_I16) return MMX_ERR_UNSUPPORTED;
     if (tiles_per_wg < 1) tiles_per_wg = 1;
     uint16_t* copy = (uint16_t*)d_work;
     int64_t* copy_off = (int64_t*)((char*)d_work + ((vox * 2 + 255) & ~255ll));
@@ -810,7 +820,7 @@ int mmx_launch_pp_pipe(const mmx_volume* vol, const mmx_subblock* d_subs, const 
     if (n_owg > PPO_WG) return MMX_ERR_UNSUPPORTED;
     // (32-bit byte offsets inside a strip's extent in the volume and in the copy)
     {
-        const int64_t esz = vol->dtype == MMX_U16 ? 2 : 1;
+        const int64_t esz = vol->dtype == MMX_U8 ? 1 : 2;
         int64_t zmax = 0, ymax = 0;
         for (int i = 0; i < n_subs; ++i) { zmax = std::max<int64_t>(zmax, h_subs[i].nz); ymax = std::max<int64_t>(ymax, h_subs[i].ny); }
         const int64_t ext = (zmax * std::abs(vol->stride_z) + ymax * std::abs(vol->stride_y)) * esz;
@@ -828,12 +838,16 @@ int mmx_launch_pp_pipe(const mmx_volume* vol, const mmx_subblock* d_subs, const 
     if (vol->dtype == MMX_U16)
         hipLaunchKernelGGL(pp_retile_kernel<uint16_t>, dim3(n_subs), dim3(PPR_WG), 0, s, (const uint16_t*)vol->d_data,
                            vol->stride_z, vol->stride_y, vol->stride_x, d_subs, n_subs, copy_off, is_head, copy);
+    else if (vol->dtype == MMX_I16)
+        hipLaunchKernelGGL(pp_retile_kernel<int16_t>, dim3(n_subs), dim3(PPR_WG), 0, s, (const int16_t*)vol->d_data,
+                           vol->stride_z, vol->stride_y, vol->stride_x, d_subs, n_subs, copy_off, is_head, copy);
     else
         hipLaunchKernelGGL(pp_retile_kernel<uint8_t>, dim3(n_subs), dim3(PPR_WG), 0, s, (const uint8_t*)vol->d_data,
                            vol->stride_z, vol->stride_y, vol->stride_x, d_subs, n_subs, copy_off, is_head, copy);
-    hipLaunchKernelGGL(pp_stats_kernel, dim3(grid_a), dim3(PPS_WG), 0, s, (const uint16_t*)copy,
-                       (const int64_t*)copy_off, d_subs, n_subs, d_qclasses, A, d_info);
-    auto kb = pp_blur_kernel;
+    const bool sgn = vol->dtype == MMX_I16;
+    hipLaunchKernelGGL(sgn ? pp_stats_kernel<true> : pp_stats_kernel<false>, dim3(grid_a), dim3(PPS_WG), 0, s,
+                       (const uint16_t*)copy, (const int64_t*)copy_off, d_subs, n_subs, d_qclasses, A, d_info);
+    auto kb = sgn ? pp_blur_kernel<true> : pp_blur_kernel<false>;
     if (hipFuncSetAttribute((const void*)kb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(tile_b + raw_b)) != hipSuccess)
         return MMX_ERR_HIP;
     hipLaunchKernelGGL(kb, dim3(grid_b), dim3(PPB_WG), (size_t)(tile_b + raw_b), s, (const uint16_t*)copy,

@@ -42,6 +42,8 @@ namespace {
 template <typename InT> struct in_scale;
 template <> struct in_scale<uint8_t>  { static __device__ double get(uint8_t v)  { return (double)v * (1.0 / 255.0); } };
 template <> struct in_scale<uint16_t> { static __device__ double get(uint16_t v) { return (double)v * (1.0 / 65535.0); } };
+// signed: img_as_float's two steps and their two roundings -- out = x + 0.5 (exact), out *= 2 / (imax - imin)
+template <> struct in_scale<int16_t>  { static __device__ double get(int16_t v)  { return ((double)v + 0.5) * (2.0 / 65535.0); } };
 template <> struct in_scale<float>    { static __device__ double get(float v)    { return (double)v; } };
 template <> struct in_scale<double>   { static __device__ double get(double v)   { return v; } };
 
@@ -373,6 +375,7 @@ extern "C" int mmx_rescore_f64(const mmx_volume* vol, const mmx_block* d_blocks,
     switch (vol->dtype) {
         case MMX_U8:  return launch<uint8_t, double>(vol, d_blocks, d_pts, cap, d_count, d_w0, d_w2, prm, lds, s);
         case MMX_U16: return launch<uint16_t, double>(vol, d_blocks, d_pts, cap, d_count, d_w0, d_w2, prm, lds, s);
+        case MMX_I16: return launch<int16_t, double>(vol, d_blocks, d_pts, cap, d_count, d_w0, d_w2, prm, lds, s);
         case MMX_F32: return f32s ? launch<float, float>(vol, d_blocks, d_pts, cap, d_count, d_w0, d_w2, prm, lds, s)
                                   : launch<float, double>(vol, d_blocks, d_pts, cap, d_count, d_w0, d_w2, prm, lds, s);
         case MMX_F64: return launch<double, double>(vol, d_blocks, d_pts, cap, d_count, d_w0, d_w2, prm, lds, s);

@@ -45,7 +45,14 @@ inline int mmx_zx_parse(int zx_mode, mmx_zx_request* q)
 }
 
 // ---------------------------------------------------------------------------------------------------- the launchers
-inline bool mmx_voxels_ok(const mmx_volume* vol) { return vol->dtype == MMX_U8 || vol->dtype == MMX_U16 || vol->dtype == MMX_F32; }
+inline bool mmx_voxels_ok(const mmx_volume* vol)
+{
+    return vol->dtype == MMX_U8 || vol->dtype == MMX_U16 || vol->dtype == MMX_F32 || vol->dtype == MMX_I16;
+}
+// integer voxels: their value range is the type's (img_as_float), and its span -- 1 for the unsigned types' [0, 1],
+// 2 for int16's [-1, 1], which the tiled path carries as [0, 2] (the copy holds x ^ 0x8000) less each scale's constant
+inline bool mmx_voxels_integer(const mmx_volume* vol) { return vol->dtype == MMX_U8 || vol->dtype == MMX_U16 || vol->dtype == MMX_I16; }
+inline double mmx_integer_span(const mmx_volume* vol) { return vol->dtype == MMX_I16 ? 2.0 : 1.0; }
 inline bool mmx_ring_radius(int radius) { return radius >= 1 && radius <= MMX_MAX_RADIUS_FAST; }
 // 32-bit lane offsets into the input plane of a block
 inline bool mmx_lane_ok(const mmx_volume* vol, const mmx_batch_geom& g)
@@ -204,12 +211,12 @@ inline double mmx_q16_error_bound(const double* w0, const double* w2, int radius
 
 // The tile choice of the tiled path, float32 or 16-bit: unit_bound = mmx_q16_error_bound of the scale(s) the answer is
 // for, band = the nomination band.  *value_scale: value units per unit of the [0, 1] range that bound is stated for -- 1
-// for integer voxels (img_as_float), m for float voxels that state a range [0, m], 0 when 16-bit tiles cannot hold the
-// voxels.
+// for unsigned integer voxels (img_as_float), 2 for int16 (mmx_integer_span), m for float voxels that state a range
+// [0, m], 0 when 16-bit tiles cannot hold the voxels.
 inline bool mmx_tiles_q16(int zx_mode, const mmx_volume* vol, double unit_bound, double band, bool entries, double* value_scale)
 {
     const bool ranged = vol->dtype == MMX_F32 && vol->value_range > 0.f && vol->value_range < 60000.f;
-    *value_scale = vol->dtype == MMX_U8 || vol->dtype == MMX_U16 ? 1.0 : (ranged ? (double)vol->value_range : 0.0);
+    *value_scale = mmx_voxels_integer(vol) ? mmx_integer_span(vol) : (ranged ? (double)vol->value_range : 0.0);
     if (!(*value_scale > 0.0)) return false;
     // (by name: taken whatever the band; the caller's run-time check of |float32 - float64| against eps / 4 on the
     //  re-scored candidates is what then widens it)
@@ -277,7 +284,7 @@ inline int mmx_route_scale(const mmx_volume* vol, const mmx_batch_geom& g, int r
     if (q.mode != MMX_ZX_SEPARATE && mmx_fused_accepts(vol, g, radius)) {
         // float voxels: the tiled path when the volume states its value range (or when asked for by name: the float16
         // pieces of its copy cover |v| < 65504), 16-bit tiles when that range is [0, m]: their bounds scale with m
-        const bool integer = vol->dtype == MMX_U8 || vol->dtype == MMX_U16;
+        const bool integer = mmx_voxels_integer(vol);
         const bool ranged = vol->dtype == MMX_F32 && vol->value_range != 0.f && fabsf(vol->value_range) < 60000.f;
         double bp, bq, err, vscale;
         mmx_q16_bounds(w0, w2, radius, norm, &bp, &bq, &err);

@@ -277,6 +277,7 @@ extern "C" int mmx_coloc_voxels(const mmx_volume* vol, const mmx_block* d_blocks
     switch (vol->dtype) {
         case MMX_U8: MMX_COLOC_LAUNCH(uint8_t); break;
         case MMX_U16: MMX_COLOC_LAUNCH(uint16_t); break;
+        case MMX_I16: MMX_COLOC_LAUNCH(int16_t); break;
         case MMX_F32: MMX_COLOC_LAUNCH(float); break;
         case MMX_F64: MMX_COLOC_LAUNCH(double); break;
         default: return MMX_ERR_UNSUPPORTED;
@@ -366,6 +367,7 @@ extern "C" int mmx_unmix_batch(const mmx_volume* vol, const mmx_volume* h_subs, 
     switch (vol->dtype) {
         case MMX_U8: MMX_UNMIX_LAUNCH(uint8_t); break;
         case MMX_U16: MMX_UNMIX_LAUNCH(uint16_t); break;
+        case MMX_I16: MMX_UNMIX_LAUNCH(int16_t); break;
         case MMX_F32: MMX_UNMIX_LAUNCH(float); break;
         case MMX_F64: MMX_UNMIX_LAUNCH(double); break;
         default: return MMX_ERR_UNSUPPORTED;
@@ -567,6 +569,7 @@ extern "C" int mmx_minmax_batch(const mmx_volume* vol, const mmx_block* d_blocks
     switch (vol->dtype) {
         case MMX_U8: MMX_MM_LAUNCH(uint8_t); break;
         case MMX_U16: MMX_MM_LAUNCH(uint16_t); break;
+        case MMX_I16: MMX_MM_LAUNCH(int16_t); break;
         case MMX_F32: MMX_MM_LAUNCH(float); break;
         case MMX_F64: MMX_MM_LAUNCH(double); break;
         default: return MMX_ERR_UNSUPPORTED;
@@ -642,6 +645,7 @@ extern "C" int mmx_gauss_axis_batch(const mmx_volume* vol, const mmx_block* d_bl
     switch (vol->dtype) {
         case MMX_U8: MMX_GA_LAUNCH(uint8_t, double); break;
         case MMX_U16: MMX_GA_LAUNCH(uint16_t, double); break;
+        case MMX_I16: MMX_GA_LAUNCH(int16_t, double); break;
         case MMX_F64: MMX_GA_LAUNCH(double, double); break;
         case MMX_F32: MMX_GA_LAUNCH(float, float); break;    // SciPy filters a float32 image into float32 arrays
         default: return MMX_ERR_UNSUPPORTED;
@@ -696,10 +700,12 @@ extern "C" int mmx_resize_batch_as(const mmx_volume* vol, const mmx_resize_block
                        dst_sy, dst_sz, (O*)d_out, O32)
     if (vol->dtype == MMX_F64 && out_dtype == MMX_U8) { MMX_RS_LAUNCH(double, uint8_t, (float*)nullptr); }
     else if (vol->dtype == MMX_F64 && out_dtype == MMX_U16) { MMX_RS_LAUNCH(double, uint16_t, (float*)nullptr); }
+    else if (vol->dtype == MMX_F64 && out_dtype == MMX_I16) { MMX_RS_LAUNCH(double, int16_t, (float*)nullptr); }
     else if (out_dtype != vol->dtype) return MMX_ERR_UNSUPPORTED;
     else switch (vol->dtype) {
         case MMX_U8: MMX_RS_LAUNCH(uint8_t, uint8_t, (float*)nullptr); break;
         case MMX_U16: MMX_RS_LAUNCH(uint16_t, uint16_t, (float*)nullptr); break;
+        case MMX_I16: MMX_RS_LAUNCH(int16_t, int16_t, (float*)nullptr); break;    // (truncation toward zero)
         case MMX_F64:
             if (!d_out32) return MMX_ERR_ARG;
             MMX_RS_LAUNCH(double, double, d_out32);

@@ -17,6 +17,7 @@ __device__ __forceinline__ float mmx_load_any(const void* base, int dtype, int64
         case MMX_U8:  return (float)((const uint8_t*)base)[idx];
         case MMX_U16: return (float)((const uint16_t*)base)[idx];
         case MMX_F32: return ((const float*)base)[idx];
+        case MMX_I16: return (float)((const int16_t*)base)[idx] + 0.5f;     // (vox<int16_t>::act)
         default:      return (float)((const double*)base)[idx];
     }
 }

@@ -51,6 +51,7 @@ struct wide_taps {
 __host__ __device__ constexpr int run_inputs(int R) { return (kJ + 2 * R + kJ - 1) / kJ * kJ; }
 
 template <typename T> __device__ __forceinline__ float to_f32(T v) { return (float)v; }
+template <> __device__ __forceinline__ float to_f32<int16_t>(int16_t v) { return (float)v + 0.5f; }     // (vox<int16_t>::act)
 
 // ---------------------------------------------------------------- Z
 template <typename InT>
@@ -331,6 +332,7 @@ int mmx_launch_wide_pass(int pass, const mmx_volume* vol, const mmx_block* d_blo
         if (vol->dtype == MMX_U16) MMX_WIDE_Z(uint16_t);
         else if (vol->dtype == MMX_F32) MMX_WIDE_Z(float);
         else if (vol->dtype == MMX_U8) MMX_WIDE_Z(uint8_t);
+        else if (vol->dtype == MMX_I16) MMX_WIDE_Z(int16_t);
         else return MMX_ERR_UNSUPPORTED;
 #undef MMX_WIDE_Z
     } else {

@@ -420,9 +420,10 @@ int launch_ym(const mmx_block* d_blocks, int n_blocks, const mmx_zx6_plan& plan,
 
 }  // namespace
 
-// cp, cq: what one count of P (unorm16) and of Q (snorm16) is worth (mmx_launch_y6's)
+// cp, cq: what one count of P (unorm16) and of Q (snorm16) is worth (mmx_launch_y6's); bias: the constant every output
+// is owed (y6_kernel's BIAS: int16 voxels; else 0) -- it leaves through the accumulators' start value
 int mmx_launch_ym(const mmx_block* d_blocks, int n_blocks, const mmx_zx6_plan& plan, int64_t slot_elems,
-                  const mmx_taps_f32& taps, int radius, const float* d_p, float cp, float cq,
+                  const mmx_taps_f32& taps, int radius, const float* d_p, float cp, float cq, float bias,
                   float* d_log, unsigned long long* d_mask, float nms_lo, float nms_eps, hipStream_t stream)
 {
     if (!mmx_ym_accepts(taps.w0, taps.w2, radius, cp, cq)) return MMX_ERR_UNSUPPORTED;      // (radius, weights in float16's reach)
@@ -445,8 +446,8 @@ int mmx_launch_ym(const mmx_block* d_blocks, int n_blocks, const mmx_zx6_plan& p
         q128 += (k ? 2.0 : 1.0) * ((double)h * 256.0 + (double)l);
     }
     // the pieces are bytes x 2^-24 (float16 subnormals); Q's high byte arrives as offset binary, 128 too large
-    cfg.start = (float)(-128.0 * 0x1p-24 * q128);
     cfg.unscale = ldexpf(1.f, e + 1 + 24);
+    cfg.start = (float)(-128.0 * 0x1p-24 * q128 + (double)bias / (double)cfg.unscale);
     cfg.lo = nms_lo / cfg.unscale;
     cfg.eps = nms_eps / cfg.unscale;
     cfg.radius = radius;

@@ -490,8 +490,7 @@ def detect_blobs_blocks_device(dvol, channel, origins, shapes, stats=None,
                     source.set_blocks(origins, shapes, log_shapes)
                 else:
                     source = preprocess.Unmixer(subtract, denoise_max_shape)
-                source._raw_scale = (float(np.iinfo(dvol.np_dtype).max) if dvol.np_dtype.kind in "ui"
-                                     else dvol.value_scale())
+                source._raw_scale = preprocess.raw_unmix_scale(dvol, subtract)
         scaling_factor = calc_scaling_factor()[2]          # x scaling alone, as the reference
         root3 = math.sqrt(3)
 

@@ -177,17 +177,19 @@ def read_file(filename: str, series: Optional[int] = None, offset=None, size=Non
 #: memory free at the call, and no chunking at all for an image below that
 BOUNDS_CHUNK_BYTES = None
 
-_BOUNDS_DTYPES = (np.dtype(np.uint8), np.dtype(np.uint16), np.dtype(np.float64))
+_BOUNDS_DTYPES = (np.dtype(np.uint8), np.dtype(np.uint16), np.dtype(np.int16), np.dtype(np.float64))
+_BOUNDS_NAMES = "uint8, uint16, int16 and float64 are supported"
 
 
 def percentile_from_order_stats(a_prev, a_next, gamma, dtype):
     """``np.percentile(a, pct)`` (method "linear") from ``sorted(a)[prev]``, ``sorted(a)[next]`` and ``gamma`` of
     :func:`preprocess.quantile_ranks`, in float64, as NumPy's ``_lerp`` assembles it
     (numpy/lib/_function_base_impl.py): ``a + (b - a) * g``, replaced by ``b - (b - a) * (1 - g)`` where
-    ``g >= 0.5``, with ``b - a`` taken in the input type.  Scalars or arrays; returns float64."""
+    ``g >= 0.5``, with ``b - a`` taken in the input type -- for int16 the difference of two order statistics more than
+    32767 apart WRAPS, in NumPy and here.  Scalars or arrays; returns float64."""
     dtype = np.dtype(dtype)
     if dtype not in _BOUNDS_DTYPES:
-        raise NotImplementedError(f"percentiles of {dtype} images (uint8, uint16 and float64 are supported)")
+        raise NotImplementedError(f"percentiles of {dtype} images ({_BOUNDS_NAMES})")
     a = np.asarray(a_prev).astype(dtype)
     b = np.asarray(a_next).astype(dtype)
     g = np.asarray(gamma, dtype=np.float64)
@@ -209,7 +211,7 @@ def _bounds_ranks(n: int, lower, upper):
 def _percentiles_of_groups(dv, channel: int, groups, lower, upper):
     """``np.percentile(group, (lower, upper))`` of z-ranges of one channel of a device volume: ``(lows, highs)``."""
     if dv.np_dtype not in _BOUNDS_DTYPES:
-        raise NotImplementedError(f"percentiles of {dv.np_dtype} images (uint8, uint16 and float64 are supported)")
+        raise NotImplementedError(f"percentiles of {dv.np_dtype} images ({_BOUNDS_NAMES})")
     plane = int(dv.shape[1]) * int(dv.shape[2])
     ranks, gammas = [], []
     for z0, z1 in groups:
@@ -254,7 +256,7 @@ def calc_intensity_bounds(image5d, lower=0.5, upper=99.5, dim_channel=4):
         arr = image5d if isinstance(image5d, np.ndarray) else np.asarray(image5d)
         multichannel = arr.ndim > dim_channel
         if arr.dtype not in _BOUNDS_DTYPES:
-            raise NotImplementedError(f"percentiles of {arr.dtype} images (uint8, uint16 and float64 are supported)")
+            raise NotImplementedError(f"percentiles of {arr.dtype} images ({_BOUNDS_NAMES})")
         if arr.size == 0:
             raise ValueError("empty image")
         if arr.nbytes > 0.9 * _free_device_bytes():
@@ -331,7 +333,7 @@ def measure_near_bounds(img, lower=0.5, upper=99.5, assign=False):
         measure(arr)
     else:
         if arr.dtype not in _BOUNDS_DTYPES:
-            raise NotImplementedError(f"percentiles of {arr.dtype} images (uint8, uint16 and float64 are supported)")
+            raise NotImplementedError(f"percentiles of {arr.dtype} images ({_BOUNDS_NAMES})")
         if arr.size == 0:
             raise ValueError("empty image")
         n_chl = arr.shape[3] if arr.ndim == 4 else 1

@@ -15,7 +15,7 @@ device, all O(number of distinct tile sizes)):
 * the sigma-8 Gaussian weights, built like ``scipy.ndimage._filters._gaussian_kernel1d``
   (:mod:`kernels1d`).
 
-Scope: uint8 / uint16 voxels (what microscopes write) and float64 images (the same float64 arithmetic once the
+Scope: uint8 / uint16 / int16 voxels (what microscopes write) and float64 images (the same float64 arithmetic once the
 order statistics are found); float32 images, whose result in the reference depends on the NumPy release, raise
 ``NotImplementedError``.  scikit-image < 0.19 treats a 3-D array whose last axis has length 3
 as RGB inside ``filters.gaussian``; the reference pins 0.25 (no such guess), :data:`RGB_GUESS`
@@ -318,9 +318,9 @@ class Preprocessor:
         # reference computes depends on the NumPy release (float32 throughout under 1.26, float64 after the clip under
         # 2.2: DESIGN.md section 6) -- not built.
         f64_voxels = dvol.np_dtype == np.dtype(np.float64)
-        if dvol.np_dtype not in (np.dtype(np.uint8), np.dtype(np.uint16), np.dtype(np.float64)):
+        if dvol.np_dtype not in (np.dtype(np.uint8), np.dtype(np.uint16), np.dtype(np.int16), np.dtype(np.float64)):
             raise NotImplementedError(
-                f"device preprocessing reads uint8 / uint16 / float64 voxels, not {dvol.np_dtype}")
+                f"device preprocessing reads uint8 / uint16 / int16 / float64 voxels, not {dvol.np_dtype}")
         params, pct_lo, pct_hi = channel_params(int(channel), self.near_max)
         nb = len(shapes)
         shp = np.asarray(shapes, dtype=np.int64).reshape(nb, 3)
@@ -488,12 +488,22 @@ class Preprocessor:
         return res
 
 
+def raw_unmix_scale(dvol, subtract) -> float:
+    """Largest voxel an unmixed RAW block can hold: the type's maximum for unsigned images (the difference is clipped at
+    0 and positive factors only take away); signed voxels may be negative, where a positive factor adds: max +
+    sum |f| * |min|; float images their own value scale."""
+    if dvol.np_dtype.kind == "i":
+        info = np.iinfo(dvol.np_dtype)
+        return float(info.max) - float(info.min) * sum(abs(float(f)) for _, f in subtract)
+    return float(np.iinfo(dvol.np_dtype).max) if dvol.np_dtype.kind == "u" else dvol.value_scale()
+
+
 class Unmixer:
     """Spectral unmixing of one detected channel for the blocks of a batch (reference
     magmap/cv/detector.py:910-921): ``x = x - fac * roi[..., k]; x[x < 0] = 0`` for every
     ``(k, fac)`` in turn, on the block as detection sees it -- the raw voxels, or the
     preprocessed channels when ``denoise_max_shape`` is set (the reference preprocesses the block in
-    ``detect_sub_roi`` before ``detect_blobs`` unmixes it).  In float64 for uint8 / uint16 / float64 sources; a
+    ``detect_sub_roi`` before ``detect_blobs`` unmixes it).  In float64 for uint8 / uint16 / int16 / float64 sources; a
     float32 source (raw or rescaled) is unmixed in float32 like NumPy's, and ``store_f32`` then tells the detection
     that the exact volume is that float32 image.  Same ``run`` contract as :class:`Preprocessor`, so
     ``blob_log_blocks`` takes either."""
@@ -592,8 +602,7 @@ class Unmixer:
             px = -(-int(shp[i, 2]) // nat.MMX_ROW_ALIGN) * nat.MMX_ROW_ALIGN
             blocks[i] = (i * slot_pre, shp[i, 0], shp[i, 1], shp[i, 2], i, px, 0)
             slot = max(slot, int(shp[i, 0]) * int(shp[i, 1]) * px)
-        self._raw_scale = (float(np.iinfo(dvol.np_dtype).max) if dvol.np_dtype.kind in "ui"
-                           else dvol.value_scale())
+        self._raw_scale = raw_unmix_scale(dvol, self.subtract)
         self.last_geometry = (slot_pre, dst_sz, dst_sy, out64, out32)
         vol32 = nat.Volume(out32.data_ptr(), nat.MMX_F32, 0, dst_sz, dst_sy, 1)
         # a float32 source (raw or rescaled) is unmixed in float32, as NumPy does it, and the reference's blob_log then
@@ -743,7 +752,7 @@ class Rescaler:
                 for o, n in zip(origins, new_shp)]
         # ---- sources: the block as detect_blobs receives it, every channel (for the clip range)
         if self.dms is None:
-            if dvol.np_dtype not in (np.dtype(np.uint8), np.dtype(np.uint16), np.dtype(np.float32),
+            if dvol.np_dtype not in (np.dtype(np.uint8), np.dtype(np.uint16), np.dtype(np.int16), np.dtype(np.float32),
                                      np.dtype(np.float64)):
                 raise NotImplementedError(f"isotropic rescale of {dvol.np_dtype} images is not built")
             blocks_src, _ = bl._make_blocks(dvol, 0, origins, orig)
@@ -851,7 +860,8 @@ class Rescaler:
         else:
             # integer images come back in their own type; float32 images as float32 (SciPy interpolates in
             # double and stores into a float32 array; detection then runs in float32 like the reference's)
-            tdt = {nat.MMX_U8: torch.uint8, nat.MMX_U16: torch.uint16, nat.MMX_F32: torch.float32}[out_code]
+            tdt = {nat.MMX_U8: torch.uint8, nat.MMX_U16: torch.uint16, nat.MMX_I16: torch.int16,
+                   nat.MMX_F32: torch.float32}[out_code]
             out = self._buffer("_out", which, nb * slot_pre, tdt, dev)
             if out.dtype != tdt:
                 self._out[which] = out = torch.empty(nb * slot_pre, dtype=tdt, device=dev)

@@ -805,7 +805,7 @@ def _save_subimage(path: str, volume, roi) -> None:
         return
     if not isinstance(roi, np.ndarray):
         # an image already resident in HBM (a DeviceVolume / a tensor): its voxels as they are there -- the
-        # caller's own for the voxel types the kernels read in place (uint8 / uint16 / float32 / float64)
+        # caller's own for the voxel types the kernels read in place (uint8 / uint16 / int16 / float32 / float64)
         tensor = getattr(roi, "tensor", roi)
         if not hasattr(tensor, "cpu"):
             raise TypeError(f"config.save_subimg: cannot save a ROI of type {type(roi).__name__}")

@@ -23,9 +23,11 @@ except Exception as exc:  # pragma: no cover
 
 
 _NP_TO_MMX = {np.dtype(np.uint8): nat.MMX_U8, np.dtype(np.uint16): nat.MMX_U16,
-              np.dtype(np.float32): nat.MMX_F32, np.dtype(np.float64): nat.MMX_F64}
+              np.dtype(np.float32): nat.MMX_F32, np.dtype(np.float64): nat.MMX_F64,
+              np.dtype(np.int16): nat.MMX_I16}
 _TORCH_DTYPES = {np.dtype(np.uint8): torch.uint8, np.dtype(np.uint16): torch.uint16,
-                 np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}
+                 np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64,
+                 np.dtype(np.int16): torch.int16}
 
 
 def _require_gpu() -> "torch.device":
@@ -41,8 +43,10 @@ def _stream_ptr() -> int:
 class DeviceVolume:
     """A ``(z, y, x[, c])`` image resident in HBM.
 
-    Integer images other than uint8/uint16 and float16 are converted like
-    ``skimage.img_as_float`` would (to float64) on the host first.  For a float64 image a
+    uint8, uint16, int16, float32 and float64 images are held as they are (int16: 2 bytes per voxel, streamed and
+    chunked like uint16; the kernels apply ``img_as_float``'s signed conversion, range [-1, 1]).  Other integer
+    images and float16 are converted like ``skimage.img_as_float`` would (to float64) on the host first -- a
+    preprocessing stage then sees converted values, not the raw ones the reference preprocesses.  For a float64 image a
     float32 copy feeds the float32 passes; the exact re-score reads the float64 original.
 
     ``streamed``: how a large host image gets there.  ``False``: one synchronous copy -- the constructor returns with
@@ -192,7 +196,8 @@ class DeviceVolume:
             pass
 
     def value_scale(self) -> float:
-        """Magnitude of the image values after ``img_as_float`` (1 for integer images)."""
+        """Magnitude of the image values after ``img_as_float`` (1 for integer images: [0, 1], or [-1, 1] for int16,
+        whose SPAN is 2 -- :meth:`value_range`)."""
         if self._scale is None:
             if self.np_dtype.kind == "f":
                 self.wait_all()
@@ -203,9 +208,10 @@ class DeviceVolume:
         return self._scale
 
     def value_range(self, channel: int = 0) -> Tuple[float, float]:
-        """``(min, max)`` of one channel's voxels after ``img_as_float`` (``(0, 1)`` for integer images)."""
+        """``(min, max)`` of one channel's voxels after ``img_as_float`` (the type's range for integer images: ``(0, 1)``,
+        ``(-1, 1)`` for int16)."""
         if self.np_dtype.kind != "f":
-            return 0.0, 1.0
+            return (-1.0, 1.0) if self.np_dtype.kind == "i" else (0.0, 1.0)
         key = int(channel) if self.multichannel else 0
         if key not in self._ranges:
             self.wait_all()
