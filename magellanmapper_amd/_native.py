@@ -19,6 +19,26 @@ LIB_PATH = os.environ.get("MMX_LIB_PATH") or os.path.join(_HERE, "libmmx_hip.so"
 
 MMX_ABI_VERSION = 21
 MMX_U8, MMX_U16, MMX_F32, MMX_F64, MMX_I16 = 0, 1, 2, 3, 4
+#: THE voxel-type table (``mmx_voxel_table`` of csrc/mmx_voxel.h states the same for the kernels), in code order:
+#: (mmx_dtype code, NumPy dtype, name of the torch dtype -- this module does not import torch --, integer, signed).
+#: Every dtype map and every tuple of accepted dtypes in the package is a view of it.
+VOXEL_TYPES = (
+    (MMX_U8, np.dtype(np.uint8), "uint8", True, False),
+    (MMX_U16, np.dtype(np.uint16), "uint16", True, False),
+    (MMX_F32, np.dtype(np.float32), "float32", False, True),
+    (MMX_F64, np.dtype(np.float64), "float64", False, True),
+    (MMX_I16, np.dtype(np.int16), "int16", True, True),
+)
+NP_TO_MMX = {v[1]: v[0] for v in VOXEL_TYPES}
+MMX_TO_NP = {v[0]: v[1] for v in VOXEL_TYPES}
+MMX_TO_TORCH_NAME = {v[0]: v[2] for v in VOXEL_TYPES}
+
+
+def voxel_dtypes(integer):
+    """The NumPy dtypes of the integer (``True``) or the float (``False``) voxel types, in code order."""
+    return tuple(v[1] for v in VOXEL_TYPES if v[3] == integer)
+
+
 MMX_MAX_RADIUS_FAST = 24
 MMX_MAX_RADIUS_WIDE = 64
 MMX_MAX_RADIUS_GENERIC = 255

@@ -223,6 +223,7 @@ class BatchStats:
 
 #: debugging aid: cap on the blocks of one batch (``MMX_MAX_BATCH``; bisecting a batch-size dependent failure)
 _MAX_BATCH = 1 << 30
+_INTEGER_DTYPES = nat.voxel_dtypes(integer=True)      # raw voxels whose value range is the type's
 #: the tail of the block list is re-split into batches that shrink by this factor (nothing hides the host work of the
 #: last batches), the first batch into a ramp that starts at this many blocks (nothing hides its GPU time from the host)
 TAPER = 4
@@ -490,7 +491,7 @@ class Lane:
         # what is known about the voxels the passes will read: raw integer images [0, 1]; float images their measured
         # range; preprocessed / unmixed / rescaled blocks the bounds their arithmetic implies
         self.vrange = vrange = dvol.value_range(channel) if pre is None else pre.value_range([channel])
-        integer_voxels = pre is None and dvol.np_dtype in (np.dtype(np.uint8), np.dtype(np.uint16), np.dtype(np.int16))
+        integer_voxels = pre is None and dvol.np_dtype in _INTEGER_DTYPES
         # (raw int16: [-1, 1], which the tiled kernels carry as [0, 2] less a constant per scale -- a value SPAN of 2,
         #  twice the rounding error of the 16-bit intermediates; the wide band is taken only where it still covers that
         #  fourfold, as the library's own rule asks, else the batch keeps float32 tiles and the narrow band)

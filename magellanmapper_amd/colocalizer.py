@@ -34,8 +34,7 @@ except ImportError:  # pragma: no cover
 
 from . import _native as nat
 
-_NP_DTYPES = {nat.MMX_U8: np.uint8, nat.MMX_U16: np.uint16, nat.MMX_F32: np.float32, nat.MMX_F64: np.float64,
-              nat.MMX_I16: np.int16}
+_NP_DTYPES = nat.MMX_TO_NP
 
 
 def _flags_from_means(table: np.ndarray, means: np.ndarray, shape3, n_channels: int,

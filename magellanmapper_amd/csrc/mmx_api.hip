@@ -211,10 +211,7 @@ struct pass_weights {
 };
 void make_weights(const mmx_volume* vol, const double* h_w0, const double* h_w2, int radius, double norm, pass_weights* w)
 {
-    double in_scale = 1.0;
-    if (vol->dtype == MMX_U8) in_scale = 1.0 / 255.0;        // skimage img_as_float: x * (1/imax)
-    else if (vol->dtype == MMX_U16) in_scale = 1.0 / 65535.0;
-    else if (vol->dtype == MMX_I16) in_scale = 2.0 / 65535.0;    // signed: (x + 0.5) * (2 / (imax - imin)); the 0.5 is the load's
+    const double in_scale = mmx_voxel(vol->dtype)->in_scale;     // img_as_float's multiplier; the signed form's 0.5 is the load's
     for (int k = 0; k <= radius; ++k) {
         w->z0[k] = (float)(h_w0[k] * in_scale);
         w->z2[k] = (float)(h_w2[k] * in_scale);
@@ -455,6 +452,7 @@ int mmx_log_batch_f32_generic(const mmx_volume* vol, const mmx_block* d_blocks, 
         return MMX_ERR_ARG;
     if (n_blocks < 1 || radius < 0 || radius > MMX_MAX_RADIUS_GENERIC || slot_elems < 1) return MMX_ERR_ARG;
     if (n_blocks > MMX_MAX_BLOCKS) return MMX_ERR_UNSUPPORTED;
+    if (!mmx_voxel_in(vol->dtype, MMX_VOX_ALL)) return MMX_ERR_UNSUPPORTED;    // (float64 voxels too: mmx_load_any)
     mmx_batch_geom g;
     mmx_batch_geom_make(vol, h_blocks, n_blocks, slot_elems, &g);
     if (g.status != MMX_OK) return g.status;

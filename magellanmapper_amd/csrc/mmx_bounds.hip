@@ -38,52 +38,6 @@ struct os_state {
 };
 static_assert(sizeof(os_state) == 128, "os_state layout");
 
-// order-preserving keys: the value itself for unsigned integers; for floats the sign-flip key, every NaN last
-// (np.sort's place for it)
-template <typename T> struct os_key;
-template <> struct os_key<uint8_t> {
-    using type = uint32_t; static constexpr int levels = 1;
-    static __device__ __forceinline__ type make(uint8_t v, bool& nan) { return v; }
-    static __device__ __forceinline__ double value(unsigned long long k) { return (double)k; }
-};
-template <> struct os_key<uint16_t> {
-    using type = uint32_t; static constexpr int levels = 2;
-    static __device__ __forceinline__ type make(uint16_t v, bool& nan) { return v; }
-    static __device__ __forceinline__ double value(unsigned long long k) { return (double)k; }
-};
-template <> struct os_key<int16_t> {       // offset binary: x ^ 0x8000 sorts as x does
-    using type = uint32_t; static constexpr int levels = 2;
-    static __device__ __forceinline__ type make(int16_t v, bool& nan) { return (uint32_t)(uint16_t)v ^ 0x8000u; }
-    static __device__ __forceinline__ double value(unsigned long long k) { return (double)(int16_t)((uint32_t)k ^ 0x8000u); }
-};
-template <> struct os_key<float> {
-    using type = uint32_t; static constexpr int levels = 4;
-    static __device__ __forceinline__ type make(float v, bool& nan)
-    {
-        const uint32_t b = __float_as_uint(v);
-        if ((b & 0x7fffffffu) > 0x7f800000u) { nan = true; return 0xffffffffu; }
-        return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    }
-    static __device__ __forceinline__ double value(unsigned long long k)
-    {
-        const uint32_t key = (uint32_t)k;
-        return (double)__uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
-    }
-};
-template <> struct os_key<double> {
-    using type = unsigned long long; static constexpr int levels = 8;
-    static __device__ __forceinline__ type make(double v, bool& nan)
-    {
-        const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-        if ((b & 0x7fffffffffffffffull) > 0x7ff0000000000000ull) { nan = true; return ~0ull; }
-        return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-    }
-    static __device__ __forceinline__ double value(unsigned long long k)
-    {
-        return __longlong_as_double((long long)((k >> 63) ? (k ^ 0x8000000000000000ull) : ~k));
-    }
-};
-
 // the elements of one 16-byte load
 template <typename T> struct os_vec { static constexpr int n = 16 / (int)sizeof(T); };
 template <typename T> __device__ __forceinline__ T os_elem(const uint4& q, int j);
@@ -153,7 +107,7 @@ os_count_kernel(const T* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx, i
                 const mmx_rank_group* __restrict__ groups, int group0, int level, int64_t chunk,
                 unsigned long long* __restrict__ hist, const os_state* __restrict__ state, int32_t* __restrict__ d_nan)
 {
-    using K = os_key<T>;
+    using K = mmx_key<T>;
     using key_t = typename K::type;
     constexpr int VE = os_vec<T>::n;
     constexpr int WB = os_wbits<VE>::n;
@@ -334,7 +288,7 @@ os_select_kernel(unsigned long long* __restrict__ hist, os_state* __restrict__ s
     __syncthreads();                                           // (every read of the state and the bins is behind us)
     for (int i = tid; i < n_uniq_now * kBins; i += MMX_WG) gh[i] = 0;
     if (last) {
-        if (tid < kRanks) d_stats[(int64_t)g * kRanks + tid] = os_key<T>::value(s_prefix[tid]);
+        if (tid < kRanks) d_stats[(int64_t)g * kRanks + tid] = mmx_key<T>::value(s_prefix[tid]);
     } else if (tid == 0) {
         int n_uniq = 0;
         for (int k = 0; k < kRanks; ++k) {
@@ -366,7 +320,7 @@ int os_run(const mmx_volume* vol, int64_t ny, int64_t nx, const mmx_rank_group* 
     if (chunks > MMX_MAX_GRID_X) return MMX_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(os_init_kernel, dim3((unsigned)((n_groups + MMX_WG - 1) / MMX_WG)), dim3(MMX_WG), 0, s,
                        d_groups, n_groups, state);
-    for (int level = 0; level < os_key<T>::levels; ++level) {
+    for (int level = 0; level < mmx_key<T>::levels; ++level) {
         for (int g0 = 0; g0 < n_groups; g0 += MMX_MAX_BLOCKS) {
             const int ng = std::min(MMX_MAX_BLOCKS, n_groups - g0);
             auto count = level == 0 ? os_count_kernel<T, true> : os_count_kernel<T, false>;
@@ -375,7 +329,7 @@ int os_run(const mmx_volume* vol, int64_t ny, int64_t nx, const mmx_rank_group* 
                                d_groups, g0, level, chunk, hist, (const os_state*)state, d_nan);
         }
         hipLaunchKernelGGL(os_select_kernel<T>, dim3((unsigned)n_groups), dim3(MMX_WG), 0, s, hist, state,
-                           level == os_key<T>::levels - 1 ? 1 : 0, d_stats);
+                           level == mmx_key<T>::levels - 1 ? 1 : 0, d_stats);
     }
     return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
 }
@@ -396,7 +350,7 @@ extern "C" int mmx_order_stats(const mmx_volume* vol, int64_t nz, int64_t ny, in
     if (!vol || !vol->d_data || !d_groups || !h_groups || n_groups < 1 || !d_stats || !d_nan || !d_work)
         return MMX_ERR_ARG;
     if (nz < 1 || ny < 1 || nx < 1 || nz > 0x7fffffff || ny > 0x7fffffff || nx > 0x7fffffff) return MMX_ERR_ARG;
-    if (vol->dtype < MMX_U8 || vol->dtype > MMX_I16) return MMX_ERR_ARG;
+    if (!mmx_voxel_in(vol->dtype, MMX_VOX_ALL)) return MMX_ERR_ARG;      // (ahead of the memsets: a refusal writes nothing)
     if (((uintptr_t)d_work & 15) != 0) return MMX_ERR_ARG;
     int64_t max_voxels = 0;
     for (int g = 0; g < n_groups; ++g) {
@@ -414,11 +368,7 @@ extern "C" int mmx_order_stats(const mmx_volume* vol, int64_t nz, int64_t ny, in
     os_state* state = (os_state*)((char*)d_work + hist_bytes);
     if (hipMemsetAsync(hist, 0, (size_t)hist_bytes, s) != hipSuccess) return MMX_ERR_HIP;
     if (hipMemsetAsync(d_nan, 0, (size_t)n_groups * sizeof(int32_t), s) != hipSuccess) return MMX_ERR_HIP;
-    switch (vol->dtype) {
-        case MMX_U8: return os_run<uint8_t>(vol, ny, nx, d_groups, n_groups, max_voxels, d_stats, d_nan, hist, state, s);
-        case MMX_U16: return os_run<uint16_t>(vol, ny, nx, d_groups, n_groups, max_voxels, d_stats, d_nan, hist, state, s);
-        case MMX_F32: return os_run<float>(vol, ny, nx, d_groups, n_groups, max_voxels, d_stats, d_nan, hist, state, s);
-        case MMX_I16: return os_run<int16_t>(vol, ny, nx, d_groups, n_groups, max_voxels, d_stats, d_nan, hist, state, s);
-        default: return os_run<double>(vol, ny, nx, d_groups, n_groups, max_voxels, d_stats, d_nan, hist, state, s);
-    }
+    return mmx_for_voxel<MMX_VOX_ALL>(vol->dtype, MMX_ERR_ARG, [&](auto t) {
+        return os_run<MMX_TAG_T(t)>(vol, ny, nx, d_groups, n_groups, max_voxels, d_stats, d_nan, hist, state, s);
+    });
 }

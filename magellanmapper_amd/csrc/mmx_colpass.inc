@@ -48,7 +48,7 @@ zpass_kernel(const InT* __restrict__ vol, int64_t stride_z, int stride_y, int st
              const mmx_block* __restrict__ blocks, int64_t slot_elems,
              float* __restrict__ gz, float* __restrict__ gzz, mmx_taps_f32 taps)
 {
-    using io = vox<InT>;
+    using io = mmx_vox<InT>;
     constexpr int N = 2 * R + 1;
     constexpr int M = N + kPrefetch;
     const mmx_block bd = blocks[blockIdx.y];
@@ -124,7 +124,7 @@ ypass_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems,
              const float* __restrict__ gz, const float* __restrict__ gzz,
              float* __restrict__ oa, float* __restrict__ obc, mmx_taps_f32 taps)
 {
-    using io = vox<float>;
+    using io = mmx_vox<float>;
     constexpr int N = 2 * R + 1;
     constexpr int M = N + kPrefetch;
     const mmx_block bd = blocks[blockIdx.y];

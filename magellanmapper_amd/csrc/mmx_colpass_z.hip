@@ -8,25 +8,12 @@ int launch_z(const mmx_volume* vol, const mmx_block* d_blocks, int n_blocks, int
 {
     dim3 grid((max_cols + MMX_WG - 1) / MMX_WG, n_blocks);
     const int sy = (int)vol->stride_y, sx = (int)vol->stride_x;
-    if (vol->dtype == MMX_U16)
-        hipLaunchKernelGGL((zpass_kernel<R, uint16_t>), grid, dim3(MMX_WG), 0, s,
-                           (const uint16_t*)vol->d_data, vol->stride_z, sy, sx, d_blocks, slot_elems,
-                           d_gz, d_gzz, taps);
-    else if (vol->dtype == MMX_F32)
-        hipLaunchKernelGGL((zpass_kernel<R, float>), grid, dim3(MMX_WG), 0, s,
-                           (const float*)vol->d_data, vol->stride_z, sy, sx, d_blocks, slot_elems,
-                           d_gz, d_gzz, taps);
-    else if (vol->dtype == MMX_U8)
-        hipLaunchKernelGGL((zpass_kernel<R, uint8_t>), grid, dim3(MMX_WG), 0, s,
-                           (const uint8_t*)vol->d_data, vol->stride_z, sy, sx, d_blocks, slot_elems,
-                           d_gz, d_gzz, taps);
-    else if (vol->dtype == MMX_I16)
-        hipLaunchKernelGGL((zpass_kernel<R, int16_t>), grid, dim3(MMX_WG), 0, s,
-                           (const int16_t*)vol->d_data, vol->stride_z, sy, sx, d_blocks, slot_elems,
-                           d_gz, d_gzz, taps);
-    else
-        return MMX_ERR_UNSUPPORTED;
-    return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
+    return mmx_for_voxel<MMX_VOX_LOG>(vol->dtype, MMX_ERR_UNSUPPORTED, [&](auto t) {
+        using T = MMX_TAG_T(t);
+        hipLaunchKernelGGL((zpass_kernel<R, T>), grid, dim3(MMX_WG), 0, s, (const T*)vol->d_data, vol->stride_z, sy, sx,
+                           d_blocks, slot_elems, d_gz, d_gzz, taps);
+        return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
+    });
 }
 }  // namespace
 

@@ -6,6 +6,9 @@
 
 #include "../../include/mmx.h"
 
+// What a voxel type is: its record, the accepted sets, the dispatcher and the device traits
+#include "mmx_voxel.h"
+
 #define MMX_WG 256  // workgroup size used by the streaming kernels (4 waves of 64)
 #define MMX_MAX_GRID_X 2147483647  // workgroups along x of one launch
 

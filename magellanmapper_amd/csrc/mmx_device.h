@@ -39,29 +39,6 @@ __device__ __forceinline__ rsrc_t make_rsrc(const void* p)
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7fffffff, 0x00020000);
 }
 
-// raw voxel bits as they come from memory (o: per-lane byte offset, so: scalar byte offset); converted
-// ("activated") when first needed, some steps after the load was issued, so the conversion does not pull
-// the s_waitcnt forward.
-template <typename T> struct vox;
-template <> struct vox<uint8_t> {
-    static __device__ __forceinline__ float load(rsrc_t r, unsigned o, unsigned so = 0) { return __uint_as_float((unsigned)__builtin_amdgcn_raw_buffer_load_b8(r, o, so, 0)); }
-    static __device__ __forceinline__ float act(float raw) { return (float)__float_as_uint(raw); }
-};
-template <> struct vox<uint16_t> {
-    static __device__ __forceinline__ float load(rsrc_t r, unsigned o, unsigned so = 0) { return __uint_as_float((unsigned)__builtin_amdgcn_raw_buffer_load_b16(r, o, so, 0)); }
-    static __device__ __forceinline__ float act(float raw) { return (float)__float_as_uint(raw); }
-};
-// int16: the signed value plus the 0.5 of img_as_float's signed conversion, exact in float32 (17 significant bits); the
-// 2 / 65535 rides in the weights
-template <> struct vox<int16_t> {
-    static __device__ __forceinline__ float load(rsrc_t r, unsigned o, unsigned so = 0) { return __uint_as_float((unsigned)__builtin_amdgcn_raw_buffer_load_b16(r, o, so, 0)); }
-    static __device__ __forceinline__ float act(float raw) { return (float)(int)(int16_t)__float_as_uint(raw) + 0.5f; }
-};
-template <> struct vox<float> {
-    static __device__ __forceinline__ float load(rsrc_t r, unsigned o, unsigned so = 0) { return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, o, so, 0)); }
-    static __device__ __forceinline__ float act(float raw) { return raw; }
-};
-
 // two floats as one dword of float16 (round to nearest even)
 __device__ __forceinline__ unsigned pack_h2(float a, float b)
 {

@@ -33,7 +33,7 @@ y2_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems,
           float* __restrict__ out, y2_taps taps,
           unsigned long long* __restrict__ mask, float nms_lo, float nms_eps)
 {
-    using io = vox<float>;
+    using io = mmx_vox<float>;
     constexpr int N = 2 * R + 1;
     constexpr int M = N + kPrefetch;
     const mmx_block bd = blocks[blockIdx.y];

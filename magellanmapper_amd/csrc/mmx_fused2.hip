@@ -65,7 +65,7 @@ __device__ __forceinline__ void zx2_producer(const InT* __restrict__ vol, int64_
                                              const mmx_block& bd, int y, int xlane, v2f* tile, const mmx_taps_zx2& T,
                                              float* __restrict__ gp, int64_t sbase)
 {
-    using io = vox<InT>;
+    using io = mmx_vox<InT>;
     using xg = xgeom2<R>;
     constexpr int NA = 2 * R + kG;       // register window: inputs z0-R .. z0+R+G-1 (+ zs)
     constexpr int PW = xg::PITCH;
@@ -302,21 +302,15 @@ int launch_zx2(const mmx_volume* vol, const mmx_block* d_blocks, int n_blocks, i
     const size_t lds = (size_t)2 * kG * xgeom2<R>::PITCH * sizeof(v2f);
     dim3 grid(max_ny, n_blocks);
     const int sy = (int)vol->stride_y, sx = (int)vol->stride_x;
-#define MMX_ZX2_LAUNCH(TT)                                                                                 \
-    do {                                                                                                   \
-        auto k = zx2_kernel<R, TT>;                                                                        \
-        if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-            return MMX_ERR_HIP;                                                                            \
-        hipLaunchKernelGGL(k, grid, dim3(threads), lds, s, (const TT*)vol->d_data, vol->stride_z, sy, sx,   \
-                           d_blocks, slot_elems, d_p, d_q, T);                                             \
-    } while (0)
-    if (vol->dtype == MMX_U16) MMX_ZX2_LAUNCH(uint16_t);
-    else if (vol->dtype == MMX_F32) MMX_ZX2_LAUNCH(float);
-    else if (vol->dtype == MMX_U8) MMX_ZX2_LAUNCH(uint8_t);
-    else if (vol->dtype == MMX_I16) MMX_ZX2_LAUNCH(int16_t);
-    else return MMX_ERR_UNSUPPORTED;
-#undef MMX_ZX2_LAUNCH
-    return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
+    return mmx_for_voxel<MMX_VOX_LOG>(vol->dtype, MMX_ERR_UNSUPPORTED, [&](auto t) {
+        using V = MMX_TAG_T(t);
+        auto k = zx2_kernel<R, V>;
+        if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return MMX_ERR_HIP;
+        hipLaunchKernelGGL(k, grid, dim3(threads), lds, s, (const V*)vol->d_data, vol->stride_z, sy, sx,
+                           d_blocks, slot_elems, d_p, d_q, T);
+        return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
+    });
 }
 
 }  // namespace

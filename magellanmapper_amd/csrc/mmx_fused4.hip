@@ -944,8 +944,7 @@ zx4_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y,
 // barrier (C3's rows are 261 voxels: profiles/r10_c3_ab.txt has its zxpack times against the kernel without panels).
 // (int16 voxels leave as u = x ^ 0x8000, the order-preserving uint16 -- the uint16 pieces and kernels serve them too:
 //  zx4's weights carry 2 x 65536 / 65535 for them and the Y pass takes the constant off that the offset adds)
-template <typename InT> struct pack_flip { static constexpr unsigned one = 0u, two = 0u; };
-template <> struct pack_flip<int16_t> { static constexpr unsigned one = 0x8000u, two = 0x80008000u; };
+template <typename InT> struct pack_flip { static constexpr unsigned one = mmx_key<InT>::bias, two = one * 0x10001u; };
 template <typename InT, bool WIDE>
 __global__ void __launch_bounds__(256)
 zx6_pack_kernel(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y, int64_t stride_x,
@@ -1143,9 +1142,7 @@ int launch_zx6(const mmx_volume* vol, const mmx_block* d_blocks, const mmx_block
     for (int k = 0; k <= MMX_MAX_RADIUS_FAST; ++k) { cfg.w0[k] = tx.w0[k]; cfg.w2[k] = tx.w2[k]; }
     cfg.radius = radius;
     // the pieces carry v / 2^16 of the widened voxel: skimage's img_as_float scale on top
-    cfg.xscale = vol->dtype == MMX_U16 ? (float)(65536.0 / 65535.0) :
-                 (vol->dtype == MMX_U8 ? (float)(65536.0 / (255.0 * 256.0)) :
-                 (vol->dtype == MMX_I16 ? (float)(2.0 * 65536.0 / 65535.0) : 1.f));     // (float voxels: as they are)
+    cfg.xscale = (float)mmx_voxel_xscale(vol->dtype);
     cfg.staged = 2;
     cfg.qp = qp; cfg.qq = qq;
     // two column tiles per wave (zx4_kernel's NTW): 16-bit tiles of integer voxels, 8 < radius <= 16; tile rows past
@@ -1229,7 +1226,8 @@ int launch_zx6(const mmx_volume* vol, const mmx_block* d_blocks, const mmx_block
 
 int mmx_zx6_plan_make(const mmx_block* h_blocks, int n_blocks, int64_t slot_elems, int voxel_dtype, mmx_zx6_plan* plan)
 {
-    const int pieces = voxel_dtype == MMX_F32 ? 2 : 1;        // float voxels: two float16 pieces per voxel in the copy
+    if (!mmx_voxel(voxel_dtype)) return MMX_ERR_UNSUPPORTED;
+    const int pieces = mmx_voxel(voxel_dtype)->pieces;        // float voxels: two float16 pieces per voxel in the copy
     int64_t tile = 0, pk = 0;
     int max_tiles = 0, max_rowtiles = 0;
     zx_classes cl;
@@ -1261,7 +1259,6 @@ int mmx_zx6_plan_make(const mmx_block* h_blocks, int n_blocks, int64_t slot_elem
 int mmx_launch_zx6_pack(const mmx_volume* vol, const mmx_block* d_blocks, const mmx_block* h_blocks, int n_blocks,
                         const mmx_zx6_plan& plan, void* d_work, hipStream_t stream)
 {
-    if (!mmx_voxels_ok(vol)) return MMX_ERR_UNSUPPORTED;
     uint16_t* pack = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(d_work) + plan.pack_off);
     dim3 grid(plan.max_rowtiles, n_blocks);
     // rows beyond one LDS panel of 512 columns anywhere in the batch: the panelled kernels for all of it
@@ -1270,21 +1267,15 @@ int mmx_launch_zx6_pack(const mmx_volume* vol, const mmx_block* d_blocks, const 
     auto launch = [&](auto kernel, auto* data) {
         hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, data, vol->stride_z, vol->stride_y, vol->stride_x, d_blocks, pack,
                            plan.pack_stride);
+        return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
     };
-    if (vol->dtype == MMX_F32) {
-        if (wide) launch(zx6_pack_f32_kernel<true>, (const float*)vol->d_data);
-        else launch(zx6_pack_f32_kernel<false>, (const float*)vol->d_data);
-    } else if (vol->dtype == MMX_U16) {
-        if (wide) launch(zx6_pack_kernel<uint16_t, true>, (const uint16_t*)vol->d_data);
-        else launch(zx6_pack_kernel<uint16_t, false>, (const uint16_t*)vol->d_data);
-    } else if (vol->dtype == MMX_I16) {
-        if (wide) launch(zx6_pack_kernel<int16_t, true>, (const int16_t*)vol->d_data);
-        else launch(zx6_pack_kernel<int16_t, false>, (const int16_t*)vol->d_data);
-    } else {
-        if (wide) launch(zx6_pack_kernel<uint8_t, true>, (const uint8_t*)vol->d_data);
-        else launch(zx6_pack_kernel<uint8_t, false>, (const uint8_t*)vol->d_data);
-    }
-    return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
+    return mmx_for_voxel<MMX_VOX_LOG>(vol->dtype, MMX_ERR_UNSUPPORTED, [&](auto t) {
+        using T = MMX_TAG_T(t);
+        if constexpr (std::is_same<T, float>::value)       // (two float16 pieces per voxel: a kernel of its own)
+            return wide ? launch(zx6_pack_f32_kernel<true>, (const T*)vol->d_data) : launch(zx6_pack_f32_kernel<false>, (const T*)vol->d_data);
+        else
+            return wide ? launch(zx6_pack_kernel<T, true>, (const T*)vol->d_data) : launch(zx6_pack_kernel<T, false>, (const T*)vol->d_data);
+    });
 }
 
 // qp, qq > 0: Q16 tiles (P qp in [0, 1], Q qq in [-1, 1]); 0: float32 tiles

@@ -77,12 +77,9 @@ extern "C" int mmx_extract_patches(const mmx_volume* vol, const int32_t* d_zyx, 
     if (n == 0 || (!d_out && !d_out32)) return MMX_OK;
     if (!vol->d_data || !d_zyx) return MMX_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    switch (vol->dtype) {
-        case MMX_U8:  return patches_launch<uint8_t, double>(vol, d_zyx, n, size, d_out, d_out32, s);
-        case MMX_U16: return patches_launch<uint16_t, double>(vol, d_zyx, n, size, d_out, d_out32, s);
-        case MMX_I16: return patches_launch<int16_t, double>(vol, d_zyx, n, size, d_out, d_out32, s);
-        case MMX_F32: return patches_launch<float, float>(vol, d_zyx, n, size, d_out, d_out32, s);
-        case MMX_F64: return patches_launch<double, double>(vol, d_zyx, n, size, d_out, d_out32, s);
-        default:      return MMX_ERR_ARG;
-    }
+    return mmx_for_voxel<MMX_VOX_ALL>(vol->dtype, MMX_ERR_ARG, [&](auto t) {
+        using V = MMX_TAG_T(t);
+        using T = typename std::conditional<std::is_same<V, float>::value, float, double>::type;    // (true divide keeps float32)
+        return patches_launch<V, T>(vol, d_zyx, n, size, d_out, d_out32, s);
+    });
 }

@@ -86,17 +86,17 @@ struct pp_sat_t {
 };
 using pp_sat = pp_sat_t<false>;
 
-// The voxel types of the integer kernels.  Histograms, the radix select and every "no voxel" sentinel work on a
-// non-negative, order-preserving KEY: the value itself for the unsigned types, value + 32768 (= x ^ 0x8000 as uint16) for
-// int16; value() takes a key back.  lerp: NumPy's _lerp on the two order statistics, whose difference NumPy takes IN
-// THE VOXEL TYPE -- for int16 it wraps, and np.percentile returns what follows from the wrapped difference.
+// The voxel types of the integer kernels.  Histograms, the radix select and every "no voxel" sentinel work on the
+// order-preserving KEY of the type, value + bias (mmx_key).  lerp: NumPy's _lerp on the two order statistics, whose
+// difference NumPy takes IN THE VOXEL TYPE -- for int16 it wraps, and np.percentile returns what follows from the
+// wrapped difference.
 template <typename InT> struct pp_vox {
-    static constexpr int bias = 0;
+    static constexpr int bias = mmx_key<InT>::bias;
     static constexpr bool is_signed = false;
     static __device__ __forceinline__ double lerp(int ka, int kb, double t) { return pp_lerp(ka, kb, t); }
 };
 template <> struct pp_vox<int16_t> {
-    static constexpr int bias = 32768;
+    static constexpr int bias = mmx_key<int16_t>::bias;
     static constexpr bool is_signed = true;
     static __device__ __forceinline__ double lerp(int ka, int kb, double t)
     {

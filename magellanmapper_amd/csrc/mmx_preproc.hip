@@ -576,13 +576,12 @@ pp_generic_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t s
     const mmx_quantile_class qc = qcs[sb.qclass];
     double q_val[4];                        // the four order statistics np.percentile interpolates between
     if constexpr (F64) {
-        // float64 voxels: an eight-level radix select on the order-preserving bit pattern of the doubles (sign bit
-        // flipped for positives, all bits for negatives), the four ranks side by side -- one 256-bin histogram each
-        // per level, counted over the voxels that share the rank's prefix so far
+        // float64 voxels: an eight-level radix select on the order-preserving key of the doubles (mmx_key; no NaNs on
+        // this path), the four ranks side by side -- one 256-bin histogram each per level, counted over the voxels
+        // that share the rank's prefix so far
         __shared__ unsigned long long s_pre[4];
         auto key = [](double v) {
-            const unsigned long long u = (unsigned long long)__double_as_longlong(v + 0.0);     // (-0.0 sorts as +0.0)
-            return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+            return mmx_key<double>::flip((unsigned long long)__double_as_longlong(v + 0.0));     // (-0.0 sorts as +0.0)
         };
         for (int64_t i = tid; i < n; i += PP_WG_GENERIC) bufA[i] = raw(i);
         if (tid < 4) {
@@ -613,11 +612,7 @@ pp_generic_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t s
             __syncthreads();
         }
 #pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const unsigned long long k = s_pre[w];
-            const unsigned long long u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-            q_val[w] = __longlong_as_double((long long)u);
-        }
+        for (int w = 0; w < 4; ++w) q_val[w] = mmx_key<double>::value(s_pre[w]);
     } else {
 
         for (int i = tid; i < PP_HIST; i += PP_WG_GENERIC) hist[i] = 0;
@@ -887,7 +882,7 @@ static int pp_check(const mmx_volume* vol, const mmx_subblock* d_subs, const mmx
     if (p->radius != PP_R) return MMX_ERR_UNSUPPORTED;
     // (float64 images: the one-output-per-lane kernel of the generic entry only; float32 images compute in float32 in
     //  the reference -- another arithmetic, not built)
-    if (vol->dtype != MMX_U8 && vol->dtype != MMX_U16 && vol->dtype != MMX_I16 && vol->dtype != MMX_F64) return MMX_ERR_UNSUPPORTED;
+    if (!mmx_voxel_in(vol->dtype, MMX_VOX_PREPROC)) return MMX_ERR_UNSUPPORTED;
     for (int i = 0; i < n_subs; ++i) {
         const mmx_subblock& b = h_subs[i];
         if (b.nz < 1 || b.ny < 1 || b.nx < 1 || b.qclass < 0 || b.qclass >= n_qc || b.src_off < 0 || b.dst_off < 0)
@@ -913,7 +908,7 @@ int mmx_preprocess_batch_mode(const mmx_volume* vol, const mmx_subblock* d_subs,
     if (st != MMX_OK) return st;
     if (mode != MMX_PP_AUTO && mode != MMX_PP_SINGLE && mode != MMX_PP_PIPELINED) return MMX_ERR_ARG;
     if (params->tv_weight != 0.0) return MMX_ERR_UNSUPPORTED;      // total-variation denoising: the generic entry
-    if (vol->dtype == MMX_F64) return MMX_ERR_UNSUPPORTED;         // float64 voxels: the generic entry
+    if (!mmx_voxel_in(vol->dtype, MMX_VOX_INTEGER)) return MMX_ERR_UNSUPPORTED;    // float64 voxels: the generic entry
     if (n_subs == 0) return MMX_OK;
     int64_t lds = 0;
     for (int i = 0; i < n_subs; ++i) {
@@ -952,20 +947,18 @@ int mmx_preprocess_batch_mode(const mmx_volume* vol, const mmx_subblock* d_subs,
         if (!freed_inf || !freed_work) return MMX_ERR_HIP;
         if (rc != MMX_ERR_UNSUPPORTED || mode == MMX_PP_PIPELINED) return rc;
     }
-#define PP_FAST_LAUNCH(T, W)                                                                              \
-    do {                                                                                                  \
-        auto k = pp_fast_kernel<T, W>;                                                                    \
-        if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-            return MMX_ERR_HIP;                                                                           \
-        hipLaunchKernelGGL(k, dim3(grid), dim3(W), (size_t)lds, s, (const T*)vol->d_data, vol->stride_z,  \
-                           vol->stride_y, vol->stride_x, d_subs, n_subs, d_qclasses, d_weights, A,        \
-                           d_out32, d_out64, d_info);                                                     \
-    } while (0)
-    if (vol->dtype == MMX_U16) { if (small) PP_FAST_LAUNCH(uint16_t, 256); else PP_FAST_LAUNCH(uint16_t, PP_WG); }
-    else if (vol->dtype == MMX_I16) { if (small) PP_FAST_LAUNCH(int16_t, 256); else PP_FAST_LAUNCH(int16_t, PP_WG); }
-    else { if (small) PP_FAST_LAUNCH(uint8_t, 256); else PP_FAST_LAUNCH(uint8_t, PP_WG); }
-#undef PP_FAST_LAUNCH
-    return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
+    return mmx_for_voxel<MMX_VOX_INTEGER>(vol->dtype, MMX_ERR_UNSUPPORTED, [&](auto t) {
+        using T = MMX_TAG_T(t);
+        auto launch = [&](auto k, int wg) {
+            if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+                return MMX_ERR_HIP;
+            hipLaunchKernelGGL(k, dim3(grid), dim3(wg), (size_t)lds, s, (const T*)vol->d_data, vol->stride_z,
+                               vol->stride_y, vol->stride_x, d_subs, n_subs, d_qclasses, d_weights, A,
+                               d_out32, d_out64, d_info);
+            return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
+        };
+        return small ? launch(pp_fast_kernel<T, 256>, 256) : launch(pp_fast_kernel<T, PP_WG>, PP_WG);
+    });
 }
 
 int mmx_preprocess_batch(const mmx_volume* vol, const mmx_subblock* d_subs, const mmx_subblock* h_subs,
@@ -1001,7 +994,7 @@ int mmx_preprocess_batch_generic(const mmx_volume* vol, const mmx_subblock* d_su
     hipStream_t s = (hipStream_t)stream;
     mmx_timed_scope ts(MMX_K_PREPROC, s);
     // every side <= 64: register-resident lines over the scratch (pp_mid_kernel); else one output per lane
-    bool mid = params->tv_weight == 0.0 && vol->dtype != MMX_F64;   // (the iteration, and float64 voxels, live in the one-output-per-lane kernel only)
+    bool mid = params->tv_weight == 0.0 && mmx_voxel_in(vol->dtype, MMX_VOX_INTEGER);   // (the iteration, and float64 voxels, live in the one-output-per-lane kernel only)
     int max_nx = 1;
     for (int i = 0; i < n_subs; ++i) {
         const mmx_subblock& b = h_subs[i];
@@ -1010,47 +1003,24 @@ int mmx_preprocess_batch_generic(const mmx_volume* vol, const mmx_subblock* d_su
     }
     if (mid) {
         const size_t lds = (size_t)PP_MID_ROWS * (max_nx | 1) * sizeof(double);
-        if (vol->dtype == MMX_U16) {
-            auto k = pp_mid_kernel<uint16_t>;
+        return mmx_for_voxel<MMX_VOX_INTEGER>(vol->dtype, MMX_ERR_UNSUPPORTED, [&](auto t) {
+            using T = MMX_TAG_T(t);
+            auto k = pp_mid_kernel<T>;
             if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
                 return MMX_ERR_HIP;
-            hipLaunchKernelGGL(k, dim3(n_subs), dim3(PP_WG_MID), lds, s, (const uint16_t*)vol->d_data,
+            hipLaunchKernelGGL(k, dim3(n_subs), dim3(PP_WG_MID), lds, s, (const T*)vol->d_data,
                                vol->stride_z, vol->stride_y, vol->stride_x, d_subs, d_qclasses, d_weights, A,
                                d_out32, d_out64, d_info, d_scratch);
-        } else if (vol->dtype == MMX_I16) {
-            auto k = pp_mid_kernel<int16_t>;
-            if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-                return MMX_ERR_HIP;
-            hipLaunchKernelGGL(k, dim3(n_subs), dim3(PP_WG_MID), lds, s, (const int16_t*)vol->d_data,
-                               vol->stride_z, vol->stride_y, vol->stride_x, d_subs, d_qclasses, d_weights, A,
-                               d_out32, d_out64, d_info, d_scratch);
-        } else {
-            auto k = pp_mid_kernel<uint8_t>;
-            if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-                return MMX_ERR_HIP;
-            hipLaunchKernelGGL(k, dim3(n_subs), dim3(PP_WG_MID), lds, s, (const uint8_t*)vol->d_data,
-                               vol->stride_z, vol->stride_y, vol->stride_x, d_subs, d_qclasses, d_weights, A,
-                               d_out32, d_out64, d_info, d_scratch);
-        }
-        return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
+            return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
+        });
     }
-    if (vol->dtype == MMX_F64)
-        hipLaunchKernelGGL(pp_generic_kernel<double>, dim3(n_subs), dim3(PP_WG_GENERIC), 0, s,
-                           (const double*)vol->d_data, vol->stride_z, vol->stride_y, vol->stride_x, d_subs,
+    return mmx_for_voxel<MMX_VOX_PREPROC>(vol->dtype, MMX_ERR_UNSUPPORTED, [&](auto t) {
+        using T = MMX_TAG_T(t);
+        hipLaunchKernelGGL(pp_generic_kernel<T>, dim3(n_subs), dim3(PP_WG_GENERIC), 0, s,
+                           (const T*)vol->d_data, vol->stride_z, vol->stride_y, vol->stride_x, d_subs,
                            d_qclasses, d_weights, A, d_out32, d_out64, d_info, d_scratch);
-    else if (vol->dtype == MMX_U16)
-        hipLaunchKernelGGL(pp_generic_kernel<uint16_t>, dim3(n_subs), dim3(PP_WG_GENERIC), 0, s,
-                           (const uint16_t*)vol->d_data, vol->stride_z, vol->stride_y, vol->stride_x, d_subs,
-                           d_qclasses, d_weights, A, d_out32, d_out64, d_info, d_scratch);
-    else if (vol->dtype == MMX_I16)
-        hipLaunchKernelGGL(pp_generic_kernel<int16_t>, dim3(n_subs), dim3(PP_WG_GENERIC), 0, s,
-                           (const int16_t*)vol->d_data, vol->stride_z, vol->stride_y, vol->stride_x, d_subs,
-                           d_qclasses, d_weights, A, d_out32, d_out64, d_info, d_scratch);
-    else
-        hipLaunchKernelGGL(pp_generic_kernel<uint8_t>, dim3(n_subs), dim3(PP_WG_GENERIC), 0, s,
-                           (const uint8_t*)vol->d_data, vol->stride_z, vol->stride_y, vol->stride_x, d_subs,
-                           d_qclasses, d_weights, A, d_out32, d_out64, d_info, d_scratch);
-    return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
+        return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
+    });
 }
 
 }  // extern "C"

@@ -502,7 +502,7 @@ pp_blur_kernel(const uint16_t* __restrict__ copy, const int64_t* __restrict__ co
         pp_geom g;
         g.nz = sb.nz; g.ny = sb.ny; g.nx = sb.nx; g.px = sb.nx | 1; g.n = sb.nz * sb.ny * sb.nx; g.nrows = sb.nz * sb.ny;
         const float inv_nx = 1.0f / (float)g.nx, inv_ny = 1.0f / (float)g.ny;
-        constexpr int kBias = SIGNED ? 32768 : 0;          // (raw holds keys: pp_vox)
+        constexpr int kBias = SIGNED ? mmx_key<int16_t>::bias : 0;          // (raw holds keys)
         pp_sat_t<SIGNED> S;
         S.identity = inf.flags & MMX_PP_IDENTITY;
         S.vmin = inf.vmin; S.vmax = inf.vmax; S.span = inf.vmax - inf.vmin;
@@ -810,7 +810,7 @@ int mmx_launch_pp_pipe(const mmx_volume* vol, const mmx_subblock* d_subs, const 
         if ((int64_t)b.nz * A.dst_sz >= (1ll << 28)) return MMX_ERR_UNSUPPORTED;
     }
     if (tile_b + raw_b > MMX_PP_MAX_LDS - 1024) return MMX_ERR_UNSUPPORTED;
-    if (vol->dtype != MMX_U16 && vol->dtype != MMX_U8 && vol->dtype != MMX_I16) return MMX_ERR_UNSUPPORTED;
+    if (!mmx_voxel_in(vol->dtype, MMX_VOX_INTEGER)) return MMX_ERR_UNSUPPORTED;
     if (tiles_per_wg < 1) tiles_per_wg = 1;
     uint16_t* copy = (uint16_t*)d_work;
     int64_t* copy_off = (int64_t*)((char*)d_work + ((vox * 2 + 255) & ~255ll));
@@ -820,7 +820,7 @@ int mmx_launch_pp_pipe(const mmx_volume* vol, const mmx_subblock* d_subs, const 
     if (n_owg > PPO_WG) return MMX_ERR_UNSUPPORTED;
     // (32-bit byte offsets inside a strip's extent in the volume and in the copy)
     {
-        const int64_t esz = vol->dtype == MMX_U8 ? 1 : 2;
+        const int64_t esz = mmx_voxel(vol->dtype)->bytes;
         int64_t zmax = 0, ymax = 0;
         for (int i = 0; i < n_subs; ++i) { zmax = std::max<int64_t>(zmax, h_subs[i].nz); ymax = std::max<int64_t>(ymax, h_subs[i].ny); }
         const int64_t ext = (zmax * std::abs(vol->stride_z) + ymax * std::abs(vol->stride_y)) * esz;
@@ -832,26 +832,23 @@ int mmx_launch_pp_pipe(const mmx_volume* vol, const mmx_subblock* d_subs, const 
     const int runs = (n_subs + tiles_per_wg - 1) / tiles_per_wg;
     const int grid_b = ((runs + 7) / 8) * 8;
     const int raw_off = (int)(tile_b / (int64_t)sizeof(double));
-    hipLaunchKernelGGL(pp_offsets1_kernel, dim3(n_owg), dim3(PPO_WG), 0, s, d_subs, n_subs, copy_off, wg_sum);
-    hipLaunchKernelGGL(pp_offsets2_kernel, dim3(n_owg), dim3(PPO_WG), 0, s, d_subs, n_subs, vol->stride_x, copy_off,
-                       (const int64_t*)wg_sum, is_head);
-    if (vol->dtype == MMX_U16)
-        hipLaunchKernelGGL(pp_retile_kernel<uint16_t>, dim3(n_subs), dim3(PPR_WG), 0, s, (const uint16_t*)vol->d_data,
+    // (every launch behind the dispatcher: a type it refuses launches nothing)
+    return mmx_for_voxel<MMX_VOX_INTEGER>(vol->dtype, MMX_ERR_UNSUPPORTED, [&](auto t) {
+        using T = MMX_TAG_T(t);
+        constexpr bool sgn = std::is_signed<T>::value;
+        hipLaunchKernelGGL(pp_offsets1_kernel, dim3(n_owg), dim3(PPO_WG), 0, s, d_subs, n_subs, copy_off, wg_sum);
+        hipLaunchKernelGGL(pp_offsets2_kernel, dim3(n_owg), dim3(PPO_WG), 0, s, d_subs, n_subs, vol->stride_x, copy_off,
+                           (const int64_t*)wg_sum, is_head);
+        hipLaunchKernelGGL(pp_retile_kernel<T>, dim3(n_subs), dim3(PPR_WG), 0, s, (const T*)vol->d_data,
                            vol->stride_z, vol->stride_y, vol->stride_x, d_subs, n_subs, copy_off, is_head, copy);
-    else if (vol->dtype == MMX_I16)
-        hipLaunchKernelGGL(pp_retile_kernel<int16_t>, dim3(n_subs), dim3(PPR_WG), 0, s, (const int16_t*)vol->d_data,
-                           vol->stride_z, vol->stride_y, vol->stride_x, d_subs, n_subs, copy_off, is_head, copy);
-    else
-        hipLaunchKernelGGL(pp_retile_kernel<uint8_t>, dim3(n_subs), dim3(PPR_WG), 0, s, (const uint8_t*)vol->d_data,
-                           vol->stride_z, vol->stride_y, vol->stride_x, d_subs, n_subs, copy_off, is_head, copy);
-    const bool sgn = vol->dtype == MMX_I16;
-    hipLaunchKernelGGL(sgn ? pp_stats_kernel<true> : pp_stats_kernel<false>, dim3(grid_a), dim3(PPS_WG), 0, s,
-                       (const uint16_t*)copy, (const int64_t*)copy_off, d_subs, n_subs, d_qclasses, A, d_info);
-    auto kb = sgn ? pp_blur_kernel<true> : pp_blur_kernel<false>;
-    if (hipFuncSetAttribute((const void*)kb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(tile_b + raw_b)) != hipSuccess)
-        return MMX_ERR_HIP;
-    hipLaunchKernelGGL(kb, dim3(grid_b), dim3(PPB_WG), (size_t)(tile_b + raw_b), s, (const uint16_t*)copy,
-                       (const int64_t*)copy_off, d_subs, n_subs, tiles_per_wg, d_weights, A, d_out32, d_out64, d_info,
-                       raw_off);
-    return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
+        hipLaunchKernelGGL(pp_stats_kernel<sgn>, dim3(grid_a), dim3(PPS_WG), 0, s,
+                           (const uint16_t*)copy, (const int64_t*)copy_off, d_subs, n_subs, d_qclasses, A, d_info);
+        auto kb = pp_blur_kernel<sgn>;
+        if (hipFuncSetAttribute((const void*)kb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(tile_b + raw_b)) != hipSuccess)
+            return MMX_ERR_HIP;
+        hipLaunchKernelGGL(kb, dim3(grid_b), dim3(PPB_WG), (size_t)(tile_b + raw_b), s, (const uint16_t*)copy,
+                           (const int64_t*)copy_off, d_subs, n_subs, tiles_per_wg, d_weights, A, d_out32, d_out64, d_info,
+                           raw_off);
+        return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
+    });
 }

@@ -39,14 +39,6 @@ struct mmx_rescore_params {
 
 namespace {
 
-template <typename InT> struct in_scale;
-template <> struct in_scale<uint8_t>  { static __device__ double get(uint8_t v)  { return (double)v * (1.0 / 255.0); } };
-template <> struct in_scale<uint16_t> { static __device__ double get(uint16_t v) { return (double)v * (1.0 / 65535.0); } };
-// signed: img_as_float's two steps and their two roundings -- out = x + 0.5 (exact), out *= 2 / (imax - imin)
-template <> struct in_scale<int16_t>  { static __device__ double get(int16_t v)  { return ((double)v + 0.5) * (2.0 / 65535.0); } };
-template <> struct in_scale<float>    { static __device__ double get(float v)    { return (double)v; } };
-template <> struct in_scale<double>   { static __device__ double get(double v)   { return v; } };
-
 // one symmetric 1-D correlation at the centre of `vals` (length 2R+1, stride `st`), SciPy order
 template <typename StoreT>
 __device__ __forceinline__ double corr_at(const double* vals, int st, int R, const double* w)
@@ -126,7 +118,7 @@ __device__ __forceinline__ void z_phase(const InT* __restrict__ in, int nyb, int
             for (int c = 0; c < NC; ++c) ctr[c] = ld(off[c], zc);
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
-                const double cv = in_scale<InT>::get(ctr[c]);
+                const double cv = mmx_vox<InT>::exact(ctr[c]);
                 a0[c] = cv * w0[0];
                 a2[c] = cv * w2[0];
             }
@@ -156,7 +148,7 @@ __device__ __forceinline__ void z_phase(const InT* __restrict__ in, int nyb, int
                 for (int c = 0; c < NC; ++c) {
 #pragma unroll
                     for (int j = 0; j < B; ++j) {
-                        const double p = in_scale<InT>::get(lo[c][j]) + in_scale<InT>::get(hi[c][j]);
+                        const double p = mmx_vox<InT>::exact(lo[c][j]) + mmx_vox<InT>::exact(hi[c][j]);
                         a0[c] += p * w0[k - j];
                         a2[c] += p * w2[k - j];
                     }
@@ -372,13 +364,10 @@ extern "C" int mmx_rescore_f64(const mmx_volume* vol, const mmx_block* d_blocks,
     hipStream_t s = (hipStream_t)stream;
     const bool f32s = store_f32 != 0;
     mmx_timed_scope ts(MMX_K_RESCORE, s);
-    switch (vol->dtype) {
-        case MMX_U8:  return launch<uint8_t, double>(vol, d_blocks, d_pts, cap, d_count, d_w0, d_w2, prm, lds, s);
-        case MMX_U16: return launch<uint16_t, double>(vol, d_blocks, d_pts, cap, d_count, d_w0, d_w2, prm, lds, s);
-        case MMX_I16: return launch<int16_t, double>(vol, d_blocks, d_pts, cap, d_count, d_w0, d_w2, prm, lds, s);
-        case MMX_F32: return f32s ? launch<float, float>(vol, d_blocks, d_pts, cap, d_count, d_w0, d_w2, prm, lds, s)
-                                  : launch<float, double>(vol, d_blocks, d_pts, cap, d_count, d_w0, d_w2, prm, lds, s);
-        case MMX_F64: return launch<double, double>(vol, d_blocks, d_pts, cap, d_count, d_w0, d_w2, prm, lds, s);
-        default: return MMX_ERR_ARG;
-    }
+    return mmx_for_voxel<MMX_VOX_ALL>(vol->dtype, MMX_ERR_ARG, [&](auto t) {
+        using T = MMX_TAG_T(t);
+        if constexpr (std::is_same<T, float>::value)
+            if (f32s) return launch<T, float>(vol, d_blocks, d_pts, cap, d_count, d_w0, d_w2, prm, lds, s);
+        return launch<T, double>(vol, d_blocks, d_pts, cap, d_count, d_w0, d_w2, prm, lds, s);
+    });
 }

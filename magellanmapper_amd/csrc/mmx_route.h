@@ -45,14 +45,11 @@ inline int mmx_zx_parse(int zx_mode, mmx_zx_request* q)
 }
 
 // ---------------------------------------------------------------------------------------------------- the launchers
-inline bool mmx_voxels_ok(const mmx_volume* vol)
-{
-    return vol->dtype == MMX_U8 || vol->dtype == MMX_U16 || vol->dtype == MMX_F32 || vol->dtype == MMX_I16;
-}
+inline bool mmx_voxels_ok(const mmx_volume* vol) { return mmx_voxel_in(vol->dtype, MMX_VOX_LOG); }
 // integer voxels: their value range is the type's (img_as_float), and its span -- 1 for the unsigned types' [0, 1],
 // 2 for int16's [-1, 1], which the tiled path carries as [0, 2] (the copy holds x ^ 0x8000) less each scale's constant
-inline bool mmx_voxels_integer(const mmx_volume* vol) { return vol->dtype == MMX_U8 || vol->dtype == MMX_U16 || vol->dtype == MMX_I16; }
-inline double mmx_integer_span(const mmx_volume* vol) { return vol->dtype == MMX_I16 ? 2.0 : 1.0; }
+inline bool mmx_voxels_integer(const mmx_volume* vol) { return mmx_voxel_in(vol->dtype, MMX_VOX_INTEGER); }
+inline double mmx_integer_span(const mmx_volume* vol) { return mmx_voxel(vol->dtype)->span; }
 inline bool mmx_ring_radius(int radius) { return radius >= 1 && radius <= MMX_MAX_RADIUS_FAST; }
 // 32-bit lane offsets into the input plane of a block
 inline bool mmx_lane_ok(const mmx_volume* vol, const mmx_batch_geom& g)

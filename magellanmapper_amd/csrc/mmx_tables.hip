@@ -270,20 +270,13 @@ extern "C" int mmx_coloc_voxels(const mmx_volume* vol, const mmx_block* d_blocks
     if (n_blobs > MMX_MAX_GRID_X) return MMX_ERR_UNSUPPORTED;      // one workgroup per blob, one-dimensional grid
     hipStream_t s = (hipStream_t)stream;
     mmx_timed_scope ts(MMX_K_COLOC, s);
-#define MMX_COLOC_LAUNCH(T)                                                                              \
-    hipLaunchKernelGGL(coloc_means_kernel<T>, dim3(n_blobs), dim3(64), 0, s, (const T*)vol->d_data,        \
-                       vol->stride_z, vol->stride_y, vol->stride_x, d_blocks, d_blobs, d_offsets, n_blobs, \
-                       d_mean, d_count, d_voxels)
-    switch (vol->dtype) {
-        case MMX_U8: MMX_COLOC_LAUNCH(uint8_t); break;
-        case MMX_U16: MMX_COLOC_LAUNCH(uint16_t); break;
-        case MMX_I16: MMX_COLOC_LAUNCH(int16_t); break;
-        case MMX_F32: MMX_COLOC_LAUNCH(float); break;
-        case MMX_F64: MMX_COLOC_LAUNCH(double); break;
-        default: return MMX_ERR_UNSUPPORTED;
-    }
-#undef MMX_COLOC_LAUNCH
-    return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
+    return mmx_for_voxel<MMX_VOX_ALL>(vol->dtype, MMX_ERR_UNSUPPORTED, [&](auto t) {
+        using T = MMX_TAG_T(t);
+        hipLaunchKernelGGL(coloc_means_kernel<T>, dim3(n_blobs), dim3(64), 0, s, (const T*)vol->d_data,
+                           vol->stride_z, vol->stride_y, vol->stride_x, d_blocks, d_blobs, d_offsets, n_blobs,
+                           d_mean, d_count, d_voxels);
+        return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
+    });
 }
 
 extern "C" int mmx_coloc_means(const mmx_volume* vol, const mmx_block* d_blocks, int n_blocks,
@@ -361,19 +354,12 @@ extern "C" int mmx_unmix_batch(const mmx_volume* vol, const mmx_volume* h_subs, 
     hipStream_t s = (hipStream_t)stream;
     dim3 grid((unsigned)std::min<int64_t>((max_vox + MMX_WG * 4 - 1) / (MMX_WG * 4), 65535), (unsigned)n_blocks);
     mmx_timed_scope ts(MMX_K_GENERIC, s);
-#define MMX_UNMIX_LAUNCH(T)                                                                                 \
-    hipLaunchKernelGGL(unmix_kernel<T>, grid, dim3(MMX_WG), 0, s, (const T*)vol->d_data, vol->stride_z,      \
-                       vol->stride_y, vol->stride_x, U, d_blocks, dst_slot, dst_sy, dst_sz, d_out32, d_out64)
-    switch (vol->dtype) {
-        case MMX_U8: MMX_UNMIX_LAUNCH(uint8_t); break;
-        case MMX_U16: MMX_UNMIX_LAUNCH(uint16_t); break;
-        case MMX_I16: MMX_UNMIX_LAUNCH(int16_t); break;
-        case MMX_F32: MMX_UNMIX_LAUNCH(float); break;
-        case MMX_F64: MMX_UNMIX_LAUNCH(double); break;
-        default: return MMX_ERR_UNSUPPORTED;
-    }
-#undef MMX_UNMIX_LAUNCH
-    return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
+    return mmx_for_voxel<MMX_VOX_ALL>(vol->dtype, MMX_ERR_UNSUPPORTED, [&](auto t) {
+        using T = MMX_TAG_T(t);
+        hipLaunchKernelGGL(unmix_kernel<T>, grid, dim3(MMX_WG), 0, s, (const T*)vol->d_data, vol->stride_z,
+                           vol->stride_y, vol->stride_x, U, d_blocks, dst_slot, dst_sy, dst_sz, d_out32, d_out64);
+        return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
+    });
 }
 
 // ---- isotropic rescale ahead of detection (magmap/cv/cv_nd.py:1070-1164 -> skimage.transform.resize ->
@@ -563,19 +549,12 @@ extern "C" int mmx_minmax_batch(const mmx_volume* vol, const mmx_block* d_blocks
     // 16 rows per wave: few enough atomics, enough workgroups (4 waves each) to fill the chip
     dim3 grid((unsigned)std::min<int64_t>((max_rows + 63) / 64, 4096), (unsigned)n_blocks);
     mmx_timed_scope ts(MMX_K_GENERIC, s);
-#define MMX_MM_LAUNCH(T)                                                                                  \
-    hipLaunchKernelGGL(minmax_kernel<T>, grid, dim3(MMX_WG), 0, s, (const T*)vol->d_data, vol->stride_z,   \
-                       vol->stride_y, vol->stride_x, d_blocks, d_minmax)
-    switch (vol->dtype) {
-        case MMX_U8: MMX_MM_LAUNCH(uint8_t); break;
-        case MMX_U16: MMX_MM_LAUNCH(uint16_t); break;
-        case MMX_I16: MMX_MM_LAUNCH(int16_t); break;
-        case MMX_F32: MMX_MM_LAUNCH(float); break;
-        case MMX_F64: MMX_MM_LAUNCH(double); break;
-        default: return MMX_ERR_UNSUPPORTED;
-    }
-#undef MMX_MM_LAUNCH
-    return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
+    return mmx_for_voxel<MMX_VOX_ALL>(vol->dtype, MMX_ERR_UNSUPPORTED, [&](auto t) {
+        using T = MMX_TAG_T(t);
+        hipLaunchKernelGGL(minmax_kernel<T>, grid, dim3(MMX_WG), 0, s, (const T*)vol->d_data, vol->stride_z,
+                           vol->stride_y, vol->stride_x, d_blocks, d_minmax);
+        return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
+    });
 }
 
 // ---- anti-aliasing ahead of a down-sampling resize: one exact float64 correlate1d pass along one axis,
@@ -638,20 +617,14 @@ extern "C" int mmx_gauss_axis_batch(const mmx_volume* vol, const mmx_block* d_bl
     hipStream_t s = (hipStream_t)stream;
     dim3 grid((unsigned)std::min<int64_t>((max_rows + 15) / 16, 65535), (unsigned)n_blocks);
     mmx_timed_scope ts(MMX_K_GENERIC, s);
-#define MMX_GA_LAUNCH(T, O)                                                                                  \
-    hipLaunchKernelGGL((gauss_axis_kernel<T, O>), grid, dim3(MMX_WG), 0, s, (const T*)vol->d_data, vol->stride_z, \
-                       vol->stride_y, vol->stride_x, d_blocks, axis, d_weights, d_radius, w_pitch, nearest, \
-                       dst_slot, dst_sy, dst_sz, (O*)d_out)
-    switch (vol->dtype) {
-        case MMX_U8: MMX_GA_LAUNCH(uint8_t, double); break;
-        case MMX_U16: MMX_GA_LAUNCH(uint16_t, double); break;
-        case MMX_I16: MMX_GA_LAUNCH(int16_t, double); break;
-        case MMX_F64: MMX_GA_LAUNCH(double, double); break;
-        case MMX_F32: MMX_GA_LAUNCH(float, float); break;    // SciPy filters a float32 image into float32 arrays
-        default: return MMX_ERR_UNSUPPORTED;
-    }
-#undef MMX_GA_LAUNCH
-    return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
+    return mmx_for_voxel<MMX_VOX_ALL>(vol->dtype, MMX_ERR_UNSUPPORTED, [&](auto t) {
+        using T = MMX_TAG_T(t);
+        using O = typename std::conditional<std::is_same<T, float>::value, float, double>::type;    // SciPy filters a float32 image into float32 arrays
+        hipLaunchKernelGGL((gauss_axis_kernel<T, O>), grid, dim3(MMX_WG), 0, s, (const T*)vol->d_data, vol->stride_z,
+                           vol->stride_y, vol->stride_x, d_blocks, axis, d_weights, d_radius, w_pitch, nearest,
+                           dst_slot, dst_sy, dst_sz, (O*)d_out);
+        return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
+    });
 }
 
 extern "C" int mmx_resize_batch_as(const mmx_volume* vol, const mmx_resize_block* d_blocks,
@@ -694,27 +667,23 @@ extern "C" int mmx_resize_batch_as(const mmx_volume* vol, const mmx_resize_block
     // 16 rows per wave: the per-wave set-up (block record, x tables) is three dependent memory round trips
     dim3 grid((unsigned)std::min<int64_t>((max_rows + 16 * (MMX_WG / 64) - 1) / (16 * (MMX_WG / 64)), 65535), (unsigned)n_blocks);
     mmx_timed_scope ts(MMX_K_GENERIC, s);
-#define MMX_RS_LAUNCH(T, O, O32)                                                                            \
-    hipLaunchKernelGGL((resize_kernel<T, O>), grid, dim3(MMX_WG), 0, s, (const T*)vol->d_data, vol->stride_z, \
-                       vol->stride_y, vol->stride_x, d_blocks, d_index, d_weight, d_minmax, dst_slot,        \
-                       dst_sy, dst_sz, (O*)d_out, O32)
-    if (vol->dtype == MMX_F64 && out_dtype == MMX_U8) { MMX_RS_LAUNCH(double, uint8_t, (float*)nullptr); }
-    else if (vol->dtype == MMX_F64 && out_dtype == MMX_U16) { MMX_RS_LAUNCH(double, uint16_t, (float*)nullptr); }
-    else if (vol->dtype == MMX_F64 && out_dtype == MMX_I16) { MMX_RS_LAUNCH(double, int16_t, (float*)nullptr); }
-    else if (out_dtype != vol->dtype) return MMX_ERR_UNSUPPORTED;
-    else switch (vol->dtype) {
-        case MMX_U8: MMX_RS_LAUNCH(uint8_t, uint8_t, (float*)nullptr); break;
-        case MMX_U16: MMX_RS_LAUNCH(uint16_t, uint16_t, (float*)nullptr); break;
-        case MMX_I16: MMX_RS_LAUNCH(int16_t, int16_t, (float*)nullptr); break;    // (truncation toward zero)
-        case MMX_F64:
-            if (!d_out32) return MMX_ERR_ARG;
-            MMX_RS_LAUNCH(double, double, d_out32);
-            break;
-        case MMX_F32: MMX_RS_LAUNCH(float, float, (float*)nullptr); break;    // SciPy's float32 output array
-        default: return MMX_ERR_UNSUPPORTED;
-    }
-#undef MMX_RS_LAUNCH
-    return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
+    auto launch = [&](auto in, auto out, float* o32) {
+        using T = MMX_TAG_T(in);
+        using O = MMX_TAG_T(out);
+        hipLaunchKernelGGL((resize_kernel<T, O>), grid, dim3(MMX_WG), 0, s, (const T*)vol->d_data, vol->stride_z,
+                           vol->stride_y, vol->stride_x, d_blocks, d_index, d_weight, d_minmax, dst_slot,
+                           dst_sy, dst_sz, (O*)d_out, o32);
+        return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
+    };
+    // the anti-aliasing filter's float64 output standing in for an integer image (truncation toward zero)
+    if (vol->dtype == MMX_F64 && out_dtype != MMX_F64)
+        return mmx_for_voxel<MMX_VOX_INTEGER>(out_dtype, MMX_ERR_UNSUPPORTED, [&](auto o) { return launch(mmx_tag<double>{}, o, nullptr); });
+    if (out_dtype != vol->dtype) return MMX_ERR_UNSUPPORTED;
+    if (vol->dtype == MMX_F64 && !d_out32) return MMX_ERR_ARG;
+    // (float32: SciPy's float32 output array; float64: its float32 copy beside it)
+    return mmx_for_voxel<MMX_VOX_ALL>(vol->dtype, MMX_ERR_UNSUPPORTED, [&](auto t) {
+        return launch(t, t, std::is_same<MMX_TAG_T(t), double>::value ? d_out32 : nullptr);
+    });
 }
 
 // ---- PMC calibration kernels (tools/pmc_calib.py): streams of a known byte count with the

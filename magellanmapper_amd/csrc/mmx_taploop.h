@@ -13,13 +13,7 @@ struct mmx_taps_generic {
 
 __device__ __forceinline__ float mmx_load_any(const void* base, int dtype, int64_t idx)
 {
-    switch (dtype) {
-        case MMX_U8:  return (float)((const uint8_t*)base)[idx];
-        case MMX_U16: return (float)((const uint16_t*)base)[idx];
-        case MMX_F32: return ((const float*)base)[idx];
-        case MMX_I16: return (float)((const int16_t*)base)[idx] + 0.5f;     // (vox<int16_t>::act)
-        default:      return (float)((const double*)base)[idx];
-    }
+    return mmx_for_voxel<MMX_VOX_ALL, float>(dtype, 0.f, [&](auto t) { return mmx_vox<MMX_TAG_T(t)>::of(((const MMX_TAG_T(t)*)base)[idx]); });
 }
 
 // idx runs over the pitched block [nz][ny][px]; returns 0 past the end, 1 for a voxel, 2 for a

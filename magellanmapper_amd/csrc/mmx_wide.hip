@@ -50,9 +50,6 @@ struct wide_taps {
 // inputs a run reads: J + 2 R rounded up to whole steps of J
 __host__ __device__ constexpr int run_inputs(int R) { return (kJ + 2 * R + kJ - 1) / kJ * kJ; }
 
-template <typename T> __device__ __forceinline__ float to_f32(T v) { return (float)v; }
-template <> __device__ __forceinline__ float to_f32<int16_t>(int16_t v) { return (float)v + 0.5f; }     // (vox<int16_t>::act)
-
 // ---------------------------------------------------------------- Z
 template <typename InT>
 __global__ void __launch_bounds__(kColThreads)
@@ -77,7 +74,7 @@ wide_z(const InT* __restrict__ vol, int64_t stride_z, int64_t stride_y, int64_t 
     const int NI = run_inputs(R);
     const int nstage = kTile - kJ + NI;
     for (int r = run; r < nstage; r += kRuns)
-        stage[r * 64 + lane] = to_f32(in[(int64_t)reflect_clamped(z0 - R + r, bd.nz) * stride_z]);
+        stage[r * 64 + lane] = mmx_vox<InT>::of(in[(int64_t)reflect_clamped(z0 - R + r, bd.nz) * stride_z]);
     __syncthreads();
     const int zr = z0 + run * kJ;                           // first output of this wave's run
     if (zr >= bd.nz) return;                                // (no barrier below)
@@ -326,15 +323,12 @@ int mmx_launch_wide_pass(int pass, const mmx_volume* vol, const mmx_block* d_blo
     if (pass == 0) {
         fill_taps(&T, R, w0, w2, nullptr);
         const size_t lds = (size_t)nstage * 64 * sizeof(float);
-#define MMX_WIDE_Z(TT) \
-        hipLaunchKernelGGL((wide_z<TT>), grid, dim3(kColThreads), lds, s, (const TT*)vol->d_data, vol->stride_z, \
-                           vol->stride_y, vol->stride_x, d_blocks, slot_elems, R, ntile, out1, out2, T)
-        if (vol->dtype == MMX_U16) MMX_WIDE_Z(uint16_t);
-        else if (vol->dtype == MMX_F32) MMX_WIDE_Z(float);
-        else if (vol->dtype == MMX_U8) MMX_WIDE_Z(uint8_t);
-        else if (vol->dtype == MMX_I16) MMX_WIDE_Z(int16_t);
-        else return MMX_ERR_UNSUPPORTED;
-#undef MMX_WIDE_Z
+        return mmx_for_voxel<MMX_VOX_LOG>(vol->dtype, MMX_ERR_UNSUPPORTED, [&](auto t) {
+            using V = MMX_TAG_T(t);
+            hipLaunchKernelGGL((wide_z<V>), grid, dim3(kColThreads), lds, s, (const V*)vol->d_data, vol->stride_z,
+                               vol->stride_y, vol->stride_x, d_blocks, slot_elems, R, ntile, out1, out2, T);
+            return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
+        });
     } else {
         fill_taps(&T, R, w2, w0, nullptr);
         const size_t lds = (size_t)nstage * 64 * sizeof(v2f) + (size_t)kRuns * 2 * 64 * sizeof(float);

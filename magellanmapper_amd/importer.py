@@ -29,6 +29,7 @@ from typing import Any, Dict, Optional, Sequence, Tuple
 import numpy as np
 import yaml
 
+from . import _native as nat
 from . import config
 from .stack_detect import Image5d
 
@@ -177,7 +178,7 @@ def read_file(filename: str, series: Optional[int] = None, offset=None, size=Non
 #: memory free at the call, and no chunking at all for an image below that
 BOUNDS_CHUNK_BYTES = None
 
-_BOUNDS_DTYPES = (np.dtype(np.uint8), np.dtype(np.uint16), np.dtype(np.int16), np.dtype(np.float64))
+_BOUNDS_DTYPES = nat.voxel_dtypes(integer=True) + (nat.MMX_TO_NP[nat.MMX_F64],)
 _BOUNDS_NAMES = "uint8, uint16, int16 and float64 are supported"
 
 

@@ -119,6 +119,9 @@ def channel_params(chl: int, near_max: Optional[Sequence[float]] = None) -> Tupl
 N_BUFFER_SETS = 3
 #: bytes per block voxel of one stage's output slots: a float32 and a float64 copy in every buffer set
 _SLOT_BYTES = (4 + 8) * N_BUFFER_SETS
+#: voxel types the device preprocessing reads (the integer types and float64), and those the isotropic rescale reads (all)
+_PREPROC_DTYPES = nat.voxel_dtypes(integer=True) + (nat.MMX_TO_NP[nat.MMX_F64],)
+_RESCALE_DTYPES = nat.voxel_dtypes(integer=True) + nat.voxel_dtypes(integer=False)
 #: device -> {"f64_<channel>" / "f32": tensor}: the resident preprocessed blocks of `Preprocessor.retain`
 _RETAINED: Dict[str, Dict[str, "torch.Tensor"]] = {}
 
@@ -318,7 +321,7 @@ class Preprocessor:
         # reference computes depends on the NumPy release (float32 throughout under 1.26, float64 after the clip under
         # 2.2: DESIGN.md section 6) -- not built.
         f64_voxels = dvol.np_dtype == np.dtype(np.float64)
-        if dvol.np_dtype not in (np.dtype(np.uint8), np.dtype(np.uint16), np.dtype(np.int16), np.dtype(np.float64)):
+        if dvol.np_dtype not in _PREPROC_DTYPES:
             raise NotImplementedError(
                 f"device preprocessing reads uint8 / uint16 / int16 / float64 voxels, not {dvol.np_dtype}")
         params, pct_lo, pct_hi = channel_params(int(channel), self.near_max)
@@ -752,8 +755,7 @@ class Rescaler:
                 for o, n in zip(origins, new_shp)]
         # ---- sources: the block as detect_blobs receives it, every channel (for the clip range)
         if self.dms is None:
-            if dvol.np_dtype not in (np.dtype(np.uint8), np.dtype(np.uint16), np.dtype(np.int16), np.dtype(np.float32),
-                                     np.dtype(np.float64)):
+            if dvol.np_dtype not in _RESCALE_DTYPES:
                 raise NotImplementedError(f"isotropic rescale of {dvol.np_dtype} images is not built")
             blocks_src, _ = bl._make_blocks(dvol, 0, origins, orig)
             views = {c: dvol.view(c, False) for c in range(dvol.n_channels)}
@@ -860,8 +862,7 @@ class Rescaler:
         else:
             # integer images come back in their own type; float32 images as float32 (SciPy interpolates in
             # double and stores into a float32 array; detection then runs in float32 like the reference's)
-            tdt = {nat.MMX_U8: torch.uint8, nat.MMX_U16: torch.uint16, nat.MMX_I16: torch.int16,
-                   nat.MMX_F32: torch.float32}[out_code]
+            tdt = getattr(torch, nat.MMX_TO_TORCH_NAME[out_code])
             out = self._buffer("_out", which, nb * slot_pre, tdt, dev)
             if out.dtype != tdt:
                 self._out[which] = out = torch.empty(nb * slot_pre, dtype=tdt, device=dev)

@@ -22,12 +22,8 @@ except Exception as exc:  # pragma: no cover
     raise ImportError("magellanmapper_amd needs PyTorch-ROCm for device memory and streams") from exc
 
 
-_NP_TO_MMX = {np.dtype(np.uint8): nat.MMX_U8, np.dtype(np.uint16): nat.MMX_U16,
-              np.dtype(np.float32): nat.MMX_F32, np.dtype(np.float64): nat.MMX_F64,
-              np.dtype(np.int16): nat.MMX_I16}
-_TORCH_DTYPES = {np.dtype(np.uint8): torch.uint8, np.dtype(np.uint16): torch.uint16,
-                 np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64,
-                 np.dtype(np.int16): torch.int16}
+_NP_TO_MMX = nat.NP_TO_MMX
+_TORCH_DTYPES = {nat.MMX_TO_NP[code]: getattr(torch, name) for code, name in nat.MMX_TO_TORCH_NAME.items()}
 
 
 def _require_gpu() -> "torch.device":

@@ -48,7 +48,9 @@ def kernels(asm):
         if not code or code.startswith(".") or code.endswith(":"):
             continue
         ops[code.split()[0]] += 1
-        norm.update(re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r"\b_Z\w+", "SYM", code)).encode() + b"\n")
+        # (.LBB<function>_ and .Lpost_getpc<n> count through the file: they move with the order the kernels are emitted in)
+        code = re.sub(r"\.Lpost_getpc\d+", ".Lpost_getpc", re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r"\b_Z\w+", "SYM", code)))
+        norm.update(code.encode() + b"\n")
     return out
 
 
