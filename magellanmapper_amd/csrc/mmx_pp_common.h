@@ -1,5 +1,14 @@
-// Device helpers shared by the preprocessing kernels (mmx_preproc.hip: one workgroup per tile with the whole
-// life of the tile in one kernel; mmx_preproc_pipe.hip: statistics kernel + pipelined blur kernel).
+// The per-tile statistics and element-wise rules of the preprocessing, stated once for every kernel form
+// (mmx_preproc.hip: one workgroup per tile with the whole life of the tile in one kernel -- pp_fast_kernel,
+// pp_mid_kernel, pp_generic_kernel; mmx_preproc_pipe.hip: pp_stats_kernel + the pipelined pp_blur_kernel).
+// A kernel keeps its own voxel walk (loads in flight, LDS / scratch / buffer loads) and its own high-byte histogram;
+// the stages between and after them are the helpers below, in the order a tile meets them:
+//   pp_select_high -> pp_bins::add -> pp_select_low      the four order statistics np.percentile interpolates between
+//   pp_key_bounds / pp_make_bounds -> pp_sat_t::make     vmin, vmax, identity -> the stretch
+//   pp_mean_verdict, pp_exact_verdict                    the mean's tolerance, knife edge and erosion flag
+//   pp_write_info                                        the tile's mmx_subblock_info record
+//   pp_unsharp, pp_erode7, pp_put                        the unsharp mask, the 7-point minimum, both output copies
+// plus the leaves they are built from (pp_select, pp_pairwise, pp_line_pass, ...).
 #pragma once
 
 #include <algorithm>
@@ -22,6 +31,7 @@ struct pp_args {
 };
 #define PP_TV_SCRATCH 7      // doubles of scratch per voxel with total-variation denoising on (2 without)
 #define PP_MAXLEAF 2048      // leaves of NumPy's pairwise summation tree kept in LDS (n <= ~130 000 voxels)
+#define MMX_PP_KNIFE 0x100   // internal flag: the statistics kernel asks the blur kernel for np.mean's own summation order
 
 namespace {
 
@@ -61,6 +71,15 @@ template <bool SIGNED>
 struct pp_sat_t {
     double vmin, vmax, span, rcp, clo;
     int identity, fast;
+    // from the bounds of a tile (pp_key_bounds / pp_make_bounds, or the tile's info record)
+    static __device__ __forceinline__ pp_sat_t make(double vmin, double vmax, int identity)
+    {
+        pp_sat_t S;
+        S.identity = identity;
+        S.vmin = vmin; S.vmax = vmax; S.span = vmax - vmin;
+        S.finish();
+        return S;
+    }
     __device__ __forceinline__ double lower() const { return SIGNED ? clo : vmin; }
     __device__ __forceinline__ void finish()
     {
@@ -84,7 +103,6 @@ struct pp_sat_t {
         return (pp_clip(raw, lower(), vmax) - vmin) / span;
     }
 };
-using pp_sat = pp_sat_t<false>;
 
 // The voxel types of the integer kernels.  Histograms, the radix select and every "no voxel" sentinel work on the
 // order-preserving KEY of the type, value + bias (mmx_key).  lerp: NumPy's _lerp on the two order statistics, whose
@@ -143,6 +161,131 @@ __device__ __forceinline__ void pp_select(const uint32_t* h, uint32_t rank, int&
     if (r >= c0) { r -= c0; ++b; if (r >= c1) { r -= c1; ++b; if (r >= c2) { r -= c2; ++b; } } }
     bin = __shfl(b, src);
     res = __shfl(r, src);
+}
+
+// ---- the four order statistics of a tile of 16-bit keys: a two-level radix select.  hist[0..255] is the kernel's own
+// histogram of the high bytes; hist[256 (1 + s) ..] the low-byte histogram of the s-th DISTINCT high-byte bin the
+// ranks fall in (prev / next ranks usually share theirs).  Barriers between the steps are the caller's.
+struct pp_ranks { int bin[4]; uint32_t res[4]; int val[4]; };        // (LDS) high-byte bin, rank inside it, the key
+
+// waves 0..3: the high-byte bin of rank lo_prev / lo_next / hi_prev / hi_next
+// (qc by value: through a reference the class's loads sink into the guarded region and every kernel gains four
+//  exec-mask regions; pp_stats_kernel, which takes one more VGPR from this helper, keeps the step pasted)
+__device__ __forceinline__ void pp_select_high(const uint32_t* hist, mmx_quantile_class qc, pp_ranks* R)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (wave < 4) {
+        const uint32_t rank = wave == 0 ? qc.lo_prev : wave == 1 ? qc.lo_next : wave == 2 ? qc.hi_prev : qc.hi_next;
+        int b; uint32_t r;
+        pp_select(hist, rank, b, r);
+        if (lane == 0) { R->bin[wave] = b; R->res[wave] = r; }
+    }
+}
+
+// the distinct bins among the four, in registers; add(): one voxel into the low-byte histogram of its bin
+struct pp_bins {
+    int b0, b1, b2, b3;
+    bool u1, u2, u3;
+    __device__ __forceinline__ explicit pp_bins(const pp_ranks* R)
+        : b0(R->bin[0]), b1(R->bin[1]), b2(R->bin[2]), b3(R->bin[3]),
+          u1(b1 != b0), u2(b2 != b0 && b2 != b1), u3(b3 != b0 && b3 != b1 && b3 != b2) {}
+    __device__ __forceinline__ void add(uint32_t* hist, int key) const
+    {
+        const int hi = key >> 8, lo = key & 255;
+        if (hi == b0) atomicAdd(&hist[256 + lo], 1u);
+        if (u1 && hi == b1) atomicAdd(&hist[512 + lo], 1u);
+        if (u2 && hi == b2) atomicAdd(&hist[768 + lo], 1u);
+        if (u3 && hi == b3) atomicAdd(&hist[1024 + lo], 1u);
+    }
+};
+
+// waves 0..3: the key of the wave's rank, from the low-byte histogram of the first slot that holds its bin
+__device__ __forceinline__ void pp_select_low(const uint32_t* hist, pp_ranks* R)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (wave < 4) {
+        int slot = wave;
+        for (int w = wave - 1; w >= 0; --w) if (R->bin[w] == R->bin[wave]) slot = w;
+        int b; uint32_t r;
+        pp_select(hist + 256 * (1 + slot), R->res[wave], b, r);
+        if (lane == 0) R->val[wave] = (R->bin[wave] << 8) | b;
+    }
+}
+
+// ---- saturate_roi's bounds: the two percentiles, `identity` (vmin == vmax, tested BEFORE max_thresh raises vmax)
+struct pp_bounds { double vmin, vmax; int identity; };
+__device__ __forceinline__ pp_bounds pp_make_bounds(double vmin, double vmax, double max_thresh)
+{
+    pp_bounds B;
+    B.identity = vmin == vmax;
+    if (vmax < max_thresh) vmax = max_thresh;
+    B.vmin = vmin; B.vmax = vmax;
+    return B;
+}
+template <typename InT>
+__device__ __forceinline__ pp_bounds pp_key_bounds(const pp_ranks* R, mmx_quantile_class qc, double max_thresh)
+{
+    return pp_make_bounds(pp_vox<InT>::lerp(R->val[0], R->val[1], qc.lo_gamma),
+                          pp_vox<InT>::lerp(R->val[2], R->val[3], qc.hi_gamma), max_thresh);
+}
+
+// ---- np.mean(saturated) gates the erosion: the tile's flags from a mean summed in any order.  Where that mean lands
+// within 1e-9 (relative to max(1, |threshold|)) of the threshold, NumPy's own summation order decides: at_knife(mean)
+// either replaces the mean by the pairwise sum and returns pp_exact_verdict of it, or returns MMX_PP_KNIFE to leave
+// both to a later kernel.
+__device__ __forceinline__ int pp_exact_verdict(double mean, const pp_args& A)      // of a mean summed in NumPy's order
+{
+    return MMX_PP_EXACT_MEAN | (mean > A.ero_thr ? MMX_PP_ERODED : 0);
+}
+template <typename Knife>
+__device__ __forceinline__ int pp_mean_verdict(double& mean, bool identity, const pp_args& A, Knife at_knife)
+{
+    int flags = identity ? MMX_PP_IDENTITY : 0;
+    if (A.do_erosion) {
+        const double tol = 1e-9 * (fabs(A.ero_thr) > 1. ? fabs(A.ero_thr) : 1.);
+        if (!identity && fabs(mean - A.ero_thr) <= tol) flags |= at_knife(mean);
+        else if (mean > A.ero_thr) flags |= MMX_PP_ERODED;
+    }
+    return flags;
+}
+
+__device__ __forceinline__ void pp_write_info(mmx_subblock_info* info, int id, double vmin, double vmax, double mean,
+                                              int flags)
+{
+    mmx_subblock_info o;
+    o.vmin = vmin; o.vmax = vmax; o.mean = mean; o.flags = flags; o._pad = 0;
+    info[id] = o;
+}
+
+// ---- den + (den - strength * blur): three roundings, in this order (the kernels are built with -ffp-contract=off)
+__device__ __forceinline__ double pp_unsharp(double den, double blur, double strength)
+{
+    const double m = strength * blur;
+    const double hp = den - m;
+    return den + hp;
+}
+
+// ---- grey_erosion with octahedron(1): the minimum over a voxel and the neighbours it has ('reflect' == skip outside).
+// t[pos] is the voxel, py / pz the row and plane pitches (x pitch 1).
+template <typename I>
+__device__ __forceinline__ double pp_erode7(const double* t, I pos, I py, I pz, bool xm, bool xp, bool ym, bool yp,
+                                            bool zm, bool zp)
+{
+    double o = t[pos];
+    if (xm) o = fmin(o, t[pos - 1]);
+    if (xp) o = fmin(o, t[pos + 1]);
+    if (ym) o = fmin(o, t[pos - py]);
+    if (yp) o = fmin(o, t[pos + py]);
+    if (zm) o = fmin(o, t[pos - pz]);
+    if (zp) o = fmin(o, t[pos + pz]);
+    return o;
+}
+
+// both output copies of one voxel (the float32 copy feeds the LoG passes)
+__device__ __forceinline__ void pp_put(double* __restrict__ out64, float* __restrict__ out32, int64_t d, double o)
+{
+    out64[d] = o;
+    out32[d] = (float)o;
 }
 
 __device__ __forceinline__ double pp_wave_sum(double v)
@@ -263,19 +406,6 @@ __device__ __forceinline__ void pp_line_pass(double* __restrict__ tile, int64_t 
             tile[base + i * stride] = acc;
         }
     }
-}
-
-// (z, y, x) of the dense index i of an n-voxel tile: exact for i < 2^15 (float has 24 bits and
-// (i + 0.5) / nx is at least 0.5 / 32 away from an integer)
-struct pp_coord { int t, x, y, z; };
-__device__ __forceinline__ pp_coord pp_decode(int i, int nx, int ny, float inv_nx, float inv_ny)
-{
-    pp_coord c;
-    c.t = (int)(((float)i + 0.5f) * inv_nx);
-    c.x = i - c.t * nx;
-    c.z = (int)(((float)c.t + 0.5f) * inv_ny);
-    c.y = c.t - c.z * ny;
-    return c;
 }
 
 inline pp_args pp_make_args(const mmx_preproc_params* p, int64_t dst_sy, int64_t dst_sz)

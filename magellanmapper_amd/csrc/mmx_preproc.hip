@@ -48,9 +48,7 @@ pp_fast_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
                mmx_subblock_info* __restrict__ info)
 {
     extern __shared__ double tile[];
-    __shared__ int s_bin[4];
-    __shared__ uint32_t s_res[4];
-    __shared__ int s_val[4];
+    __shared__ pp_ranks s_ranks;
     __shared__ double s_red[WG / 64];
     __shared__ double s_mean;
     __shared__ int s_flags;
@@ -70,8 +68,6 @@ pp_fast_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
     uint16_t* raw = (uint16_t*)(hist + PP_HIST);  // the voxels themselves, dense index
     const InT* src = vol + sb.src_off;
     const float inv_nx = 1.0f / (float)nx, inv_ny = 1.0f / (float)ny;
-#define PP_STAMP() do {} while (0)
-    PP_STAMP();
 
     for (int i = tid; i < PP_HIST; i += WG) hist[i] = 0;
     __syncthreads();
@@ -104,52 +100,21 @@ pp_fast_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
         }
     }
     __syncthreads();
-    PP_STAMP();
 
     // 2. order statistics: ranks lo_prev, lo_next, hi_prev, hi_next
     const mmx_quantile_class qc = qcs[sb.qclass];
-    if (wave < 4) {
-        const uint32_t rank = wave == 0 ? qc.lo_prev : wave == 1 ? qc.lo_next : wave == 2 ? qc.hi_prev : qc.hi_next;
-        int b; uint32_t r;
-        pp_select(hist, rank, b, r);
-        if (lane == 0) { s_bin[wave] = b; s_res[wave] = r; }
-    }
+    pp_select_high(hist, qc, &s_ranks);
     __syncthreads();
     {
-        // one low-byte histogram per DISTINCT high-byte bin (prev / next ranks usually share theirs)
-        const int b0 = s_bin[0], b1 = s_bin[1], b2 = s_bin[2], b3 = s_bin[3];
-        const bool u1 = b1 != b0, u2 = b2 != b0 && b2 != b1, u3 = b3 != b0 && b3 != b1 && b3 != b2;
-        for (int i = tid; i < n; i += WG) {
-            const int v = raw[i];
-            const int hi = v >> 8, lo = v & 255;
-            if (hi == b0) atomicAdd(&hist[256 + lo], 1u);
-            if (u1 && hi == b1) atomicAdd(&hist[512 + lo], 1u);
-            if (u2 && hi == b2) atomicAdd(&hist[768 + lo], 1u);
-            if (u3 && hi == b3) atomicAdd(&hist[1024 + lo], 1u);
-        }
+        const pp_bins bins(&s_ranks);
+        for (int i = tid; i < n; i += WG) bins.add(hist, raw[i]);
     }
     __syncthreads();
-    if (wave < 4) {
-        int slot = wave;
-        for (int w = wave - 1; w >= 0; --w) if (s_bin[w] == s_bin[wave]) slot = w;
-        int b; uint32_t r;
-        pp_select(hist + 256 * (1 + slot), s_res[wave], b, r);
-        if (lane == 0) s_val[wave] = (s_bin[wave] << 8) | b;
-    }
+    pp_select_low(hist, &s_ranks);
     __syncthreads();
-    PP_STAMP();
 
-    pp_sat_t<pp_vox<InT>::is_signed> S;
-    double info_vmin, info_vmax;
-    {
-        const double vmin = pp_vox<InT>::lerp(s_val[0], s_val[1], qc.lo_gamma);
-        double vmax = pp_vox<InT>::lerp(s_val[2], s_val[3], qc.hi_gamma);
-        S.identity = vmin == vmax;
-        if (vmax < A.max_thresh) vmax = A.max_thresh;
-        S.vmin = vmin; S.vmax = vmax; S.span = vmax - vmin;
-        info_vmin = vmin; info_vmax = vmax;
-        S.finish();
-    }
+    const pp_bounds B = pp_key_bounds<InT>(&s_ranks, qc, A.max_thresh);
+    const auto S = pp_sat_t<pp_vox<InT>::is_signed>::make(B.vmin, B.vmax, B.identity);
 
     // 3. saturate, sum, clip -> the float64 tile (PP_NB independent divisions in flight per lane)
     double part = 0.;
@@ -184,28 +149,16 @@ pp_fast_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
         double tot = 0.;
         for (int w = 0; w < WG / 64; ++w) tot += s_red[w];
         double mean = tot / (double)n;
-        int flags = S.identity ? MMX_PP_IDENTITY : 0;
-        if (A.do_erosion) {
-            const double tol = 1e-9 * (fabs(A.ero_thr) > 1. ? fabs(A.ero_thr) : 1.);
-            if (!S.identity && fabs(mean - A.ero_thr) <= tol) {
-                // knife edge: NumPy's own summation order decides
-                auto val = [&](int i) { return S.plain((double)((int)raw[i] - pp_vox<InT>::bias)); };
-                mean = pp_pairwise(val, n, &s_stack) / (double)n;
-                flags |= MMX_PP_EXACT_MEAN;
-            }
-            if (mean > A.ero_thr) flags |= MMX_PP_ERODED;
-        }
+        s_flags = pp_mean_verdict(mean, S.identity, A, [&](double& m) {
+            auto val = [&](int i) { return S.plain((double)((int)raw[i] - pp_vox<InT>::bias)); };
+            m = pp_pairwise(val, n, &s_stack) / (double)n;
+            return pp_exact_verdict(m, A);
+        });
         s_mean = mean;
-        s_flags = flags;
     }
     __syncthreads();
     const int flags = s_flags;
-    if (info && tid == 0) {
-        mmx_subblock_info o;
-        o.vmin = info_vmin; o.vmax = info_vmax; o.mean = s_mean; o.flags = flags; o._pad = 0;
-        info[sub_id] = o;
-    }
-    PP_STAMP();
+    if (info && tid == 0) pp_write_info(info, sub_id, B.vmin, B.vmax, s_mean, flags);
 
     // 4. Gaussian blur, axis 0, 1, 2 in place (scipy gaussian_filter order)
     if (A.do_unsharp) {
@@ -231,7 +184,6 @@ pp_fast_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
             __syncthreads();
         }
     }
-    PP_STAMP();
 
     // 5. unsharp mask (+ erosion), write out
     const bool erode = flags & MMX_PP_ERODED;
@@ -243,9 +195,7 @@ pp_fast_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
             const double blur = tile[row * px + x];
             if (A.do_unsharp) {
                 const double den = pp_clip(S((double)((int)raw[row * nx + x] - pp_vox<InT>::bias)), A.clip_min, A.clip_max);
-                const double m = A.strength * blur;
-                const double hp = den - m;
-                o[j] = den + hp;
+                o[j] = pp_unsharp(den, blur, A.strength);
             } else {
                 o[j] = blur;
             }
@@ -254,9 +204,7 @@ pp_fast_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
             for (int j = 0; j < PP_NB; ++j) {
                 const int row = rb + j * rpi < nrows ? rb + j * rpi : rb;
                 const double den = pp_clip(S.plain((double)((int)raw[row * nx + x] - pp_vox<InT>::bias)), A.clip_min, A.clip_max);
-                const double m = A.strength * tile[row * px + x];
-                const double hp = den - m;
-                o[j] = den + hp;
+                o[j] = pp_unsharp(den, tile[row * px + x], A.strength);
             }
         }
 #pragma unroll
@@ -267,9 +215,7 @@ pp_fast_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
             else {
                 const int z = (int)(((float)row + 0.5f) * inv_ny);
                 const int y = row - z * ny;
-                const int64_t d = sb.dst_off + z * A.dst_sz + y * A.dst_sy + x;
-                out64[d] = o[j];
-                out32[d] = (float)o[j];
+                pp_put(out64, out32, sb.dst_off + z * A.dst_sz + y * A.dst_sy + x, o[j]);
             }
         }
     }
@@ -278,17 +224,8 @@ pp_fast_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
     for (int row = r0; row < nrows; row += rpi) {
         const int z = (int)(((float)row + 0.5f) * inv_ny);
         const int y = row - z * ny;
-        const int pos = row * px + x;
-        double o = tile[pos];
-        if (x > 0) o = fmin(o, tile[pos - 1]);
-        if (x < nx - 1) o = fmin(o, tile[pos + 1]);
-        if (y > 0) o = fmin(o, tile[pos - px]);
-        if (y < ny - 1) o = fmin(o, tile[pos + px]);
-        if (z > 0) o = fmin(o, tile[pos - ny * px]);
-        if (z < nz - 1) o = fmin(o, tile[pos + ny * px]);
-        const int64_t d = sb.dst_off + z * A.dst_sz + y * A.dst_sy + x;
-        out64[d] = o;
-        out32[d] = (float)o;
+        const double o = pp_erode7(tile, row * px + x, px, ny * px, x > 0, x < nx - 1, y > 0, y < ny - 1, z > 0, z < nz - 1);
+        pp_put(out64, out32, sb.dst_off + z * A.dst_sz + y * A.dst_sy + x, o);
     }
 }
 
@@ -311,9 +248,7 @@ pp_mid_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
 {
     extern __shared__ double xrows[];              // [PP_MID_ROWS][nx | 1] for the x pass
     __shared__ uint32_t hist[PP_HIST];
-    __shared__ int s_bin[4];
-    __shared__ uint32_t s_res[4];
-    __shared__ int s_val[4];
+    __shared__ pp_ranks s_ranks;
     __shared__ double s_red[PP_WG_MID / 64];
     __shared__ double s_mean;
     __shared__ int s_flags;
@@ -361,52 +296,26 @@ pp_mid_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
     }
     __syncthreads();
     const mmx_quantile_class qc = qcs[sb.qclass];
-    {
-        const uint32_t rank = wave == 0 ? qc.lo_prev : wave == 1 ? qc.lo_next : wave == 2 ? qc.hi_prev : qc.hi_next;
-        int b; uint32_t r;
-        pp_select(hist, rank, b, r);
-        if (lane == 0) { s_bin[wave] = b; s_res[wave] = r; }
-    }
+    pp_select_high(hist, qc, &s_ranks);
     __syncthreads();
     {
-        const int b0 = s_bin[0], b1 = s_bin[1], b2 = s_bin[2], b3 = s_bin[3];
-        const bool u1 = b1 != b0, u2 = b2 != b0 && b2 != b1, u3 = b3 != b0 && b3 != b1 && b3 != b2;
+        const pp_bins bins(&s_ranks);
         for (int rb = lane_on ? r_first : nrows; rb < nrows; rb += 8 * rpi) {
             int vv[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) vv[j] = rb + j * rpi < nrows ? raw_at(rb + j * rpi) : -1;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                if (vv[j] < 0) continue;
-                const int hi = vv[j] >> 8, lo = vv[j] & 255;
-                if (hi == b0) atomicAdd(&hist[256 + lo], 1u);
-                if (u1 && hi == b1) atomicAdd(&hist[512 + lo], 1u);
-                if (u2 && hi == b2) atomicAdd(&hist[768 + lo], 1u);
-                if (u3 && hi == b3) atomicAdd(&hist[1024 + lo], 1u);
+                if (vv[j] >= 0) bins.add(hist, vv[j]);
             }
         }
     }
     __syncthreads();
-    {
-        int slot = wave;
-        for (int w = wave - 1; w >= 0; --w) if (s_bin[w] == s_bin[wave]) slot = w;
-        int b; uint32_t r;
-        pp_select(hist + 256 * (1 + slot), s_res[wave], b, r);
-        if (lane == 0) s_val[wave] = (s_bin[wave] << 8) | b;
-    }
+    pp_select_low(hist, &s_ranks);
     __syncthreads();
 
-    pp_sat_t<pp_vox<InT>::is_signed> S;
-    double info_vmin, info_vmax;
-    {
-        const double vmin = pp_vox<InT>::lerp(s_val[0], s_val[1], qc.lo_gamma);
-        double vmax = pp_vox<InT>::lerp(s_val[2], s_val[3], qc.hi_gamma);
-        S.identity = vmin == vmax;
-        if (vmax < A.max_thresh) vmax = A.max_thresh;
-        S.vmin = vmin; S.vmax = vmax; S.span = vmax - vmin;
-        info_vmin = vmin; info_vmax = vmax;
-        S.finish();
-    }
+    const pp_bounds B = pp_key_bounds<InT>(&s_ranks, qc, A.max_thresh);
+    const auto S = pp_sat_t<pp_vox<InT>::is_signed>::make(B.vmin, B.vmax, B.identity);
 
     double part = 0.;
     for (int rb = lane_on ? r_first : nrows; rb < nrows; rb += 8 * rpi) {
@@ -429,26 +338,16 @@ pp_mid_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
         double tot = 0.;
         for (int w = 0; w < PP_WG_MID / 64; ++w) tot += s_red[w];
         double mean = tot / (double)n;
-        int flags = S.identity ? MMX_PP_IDENTITY : 0;
-        if (A.do_erosion) {
-            const double tol = 1e-9 * (fabs(A.ero_thr) > 1. ? fabs(A.ero_thr) : 1.);
-            if (!S.identity && fabs(mean - A.ero_thr) <= tol) {
-                auto val = [&](int i) { return S.plain((double)(raw(i) - pp_vox<InT>::bias)); };
-                mean = pp_pairwise(val, n, &s_stack) / (double)n;
-                flags |= MMX_PP_EXACT_MEAN;
-            }
-            if (mean > A.ero_thr) flags |= MMX_PP_ERODED;
-        }
+        s_flags = pp_mean_verdict(mean, S.identity, A, [&](double& m) {
+            auto val = [&](int i) { return S.plain((double)(raw(i) - pp_vox<InT>::bias)); };
+            m = pp_pairwise(val, n, &s_stack) / (double)n;
+            return pp_exact_verdict(m, A);
+        });
         s_mean = mean;
-        s_flags = flags;
     }
     __syncthreads();          // also orders the scratch writes above before the passes below
     const int flags = s_flags;
-    if (info && tid == 0) {
-        mmx_subblock_info o;
-        o.vmin = info_vmin; o.vmax = info_vmax; o.mean = s_mean; o.flags = flags; o._pad = 0;
-        info[blockIdx.x] = o;
-    }
+    if (info && tid == 0) pp_write_info(info, blockIdx.x, B.vmin, B.vmax, s_mean, flags);
 
     if (A.do_unsharp) {
         double wl[PP_R + 1];
@@ -509,19 +408,12 @@ pp_mid_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
         if (A.do_unsharp) {
             const double rv = (double)(vv[j] - pp_vox<InT>::bias);
             const double sv = S.fast ? S(rv) : S.plain(rv);
-            const double den = pp_clip(sv, A.clip_min, A.clip_max);
-            const double m = A.strength * bl8[j];
-            const double hp = den - m;
-            o = den + hp;
+            o = pp_unsharp(pp_clip(sv, A.clip_min, A.clip_max), bl8[j], A.strength);
         } else {
             o = bl8[j];
         }
         if (erode) buf[i] = o;
-        else {
-            const int64_t d = sb.dst_off + z * A.dst_sz + y * A.dst_sy + x;
-            out64[d] = o;
-            out32[d] = (float)o;
-        }
+        else pp_put(out64, out32, sb.dst_off + z * A.dst_sz + y * A.dst_sy + x, o);
       }
     }
     if (!erode) return;
@@ -529,17 +421,8 @@ pp_mid_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
     for (int row = lane_on ? r_first : nrows; row < nrows; row += rpi) {
         const int z = (int)(((float)row + 0.5f) * inv_ny);
         const int y = row - z * ny;
-        const int i = row * nx + x;
-        double o = buf[i];
-        if (x > 0) o = fmin(o, buf[i - 1]);
-        if (x < nx - 1) o = fmin(o, buf[i + 1]);
-        if (y > 0) o = fmin(o, buf[i - nx]);
-        if (y < ny - 1) o = fmin(o, buf[i + nx]);
-        if (z > 0) o = fmin(o, buf[i - ny * nx]);
-        if (z < nz - 1) o = fmin(o, buf[i + ny * nx]);
-        const int64_t d = sb.dst_off + z * A.dst_sz + y * A.dst_sy + x;
-        out64[d] = o;
-        out32[d] = (float)o;
+        const double o = pp_erode7(buf, row * nx + x, nx, ny * nx, x > 0, x < nx - 1, y > 0, y < ny - 1, z > 0, z < nz - 1);
+        pp_put(out64, out32, sb.dst_off + z * A.dst_sz + y * A.dst_sy + x, o);
     }
 }
 
@@ -553,9 +436,7 @@ pp_generic_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t s
                   mmx_subblock_info* __restrict__ info, double* __restrict__ scratch)
 {
     __shared__ uint32_t hist[PP_HIST];
-    __shared__ int s_bin[4];
-    __shared__ uint32_t s_res[4];
-    __shared__ int s_val[4];
+    __shared__ pp_ranks s_ranks;
     __shared__ double s_red[PP_WG_GENERIC / 64];
     __shared__ double s_mean;
     __shared__ int s_flags;
@@ -574,7 +455,7 @@ pp_generic_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t s
         else return (int)src[z * sz + y * sy + x * sx];
     };
     const mmx_quantile_class qc = qcs[sb.qclass];
-    double q_val[4];                        // the four order statistics np.percentile interpolates between
+    pp_bounds B;
     if constexpr (F64) {
         // float64 voxels: an eight-level radix select on the order-preserving key of the doubles (mmx_key; no NaNs on
         // this path), the four ranks side by side -- one 256-bin histogram each per level, counted over the voxels
@@ -586,7 +467,7 @@ pp_generic_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t s
         for (int64_t i = tid; i < n; i += PP_WG_GENERIC) bufA[i] = raw(i);
         if (tid < 4) {
             s_pre[tid] = 0ull;
-            s_res[tid] = tid == 0 ? qc.lo_prev : tid == 1 ? qc.lo_next : tid == 2 ? qc.hi_prev : qc.hi_next;
+            s_ranks.res[tid] = tid == 0 ? qc.lo_prev : tid == 1 ? qc.lo_next : tid == 2 ? qc.hi_prev : qc.hi_next;
         }
         __syncthreads();
         for (int level = 7; level >= 0; --level) {
@@ -606,15 +487,14 @@ pp_generic_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t s
             __syncthreads();
             if (wave < 4) {
                 int b; uint32_t r;
-                pp_select(hist + 256 * (1 + wave), s_res[wave], b, r);
-                if (lane == 0) { s_pre[wave] = (s_pre[wave] << 8) | (unsigned long long)b; s_res[wave] = r; }
+                pp_select(hist + 256 * (1 + wave), s_ranks.res[wave], b, r);
+                if (lane == 0) { s_pre[wave] = (s_pre[wave] << 8) | (unsigned long long)b; s_ranks.res[wave] = r; }
             }
             __syncthreads();
         }
-#pragma unroll
-        for (int w = 0; w < 4; ++w) q_val[w] = mmx_key<double>::value(s_pre[w]);
+        auto q = [&](int w) { return mmx_key<double>::value(s_pre[w]); };
+        B = pp_make_bounds(pp_lerp(q(0), q(1), qc.lo_gamma), pp_lerp(q(2), q(3), qc.hi_gamma), A.max_thresh);
     } else {
-
         for (int i = tid; i < PP_HIST; i += PP_WG_GENERIC) hist[i] = 0;
         __syncthreads();
         for (int64_t i = tid; i < n; i += PP_WG_GENERIC) {
@@ -623,53 +503,21 @@ pp_generic_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t s
             atomicAdd(&hist[(v + pp_vox<InT>::bias) >> 8], 1u);
         }
         __syncthreads();
-        if (wave < 4) {
-            const uint32_t rank = wave == 0 ? qc.lo_prev : wave == 1 ? qc.lo_next : wave == 2 ? qc.hi_prev : qc.hi_next;
-            int b; uint32_t r;
-            pp_select(hist, rank, b, r);
-            if (lane == 0) { s_bin[wave] = b; s_res[wave] = r; }
-        }
+        pp_select_high(hist, qc, &s_ranks);
         __syncthreads();
         {
-            const int b0 = s_bin[0], b1 = s_bin[1], b2 = s_bin[2], b3 = s_bin[3];
-            for (int64_t i = tid; i < n; i += PP_WG_GENERIC) {
-                const int v = (int)bufA[i] + pp_vox<InT>::bias;
-                const int hi = v >> 8, lo = v & 255;
-                if (hi == b0) atomicAdd(&hist[256 + lo], 1u);
-                if (hi == b1) atomicAdd(&hist[512 + lo], 1u);
-                if (hi == b2) atomicAdd(&hist[768 + lo], 1u);
-                if (hi == b3) atomicAdd(&hist[1024 + lo], 1u);
-            }
+            const pp_bins bins(&s_ranks);
+            for (int64_t i = tid; i < n; i += PP_WG_GENERIC) bins.add(hist, (int)bufA[i] + pp_vox<InT>::bias);
         }
         __syncthreads();
-        if (wave < 4) {
-            int b; uint32_t r;
-            pp_select(hist + 256 * (1 + wave), s_res[wave], b, r);
-            if (lane == 0) s_val[wave] = (s_bin[wave] << 8) | b;
-        }
+        pp_select_low(hist, &s_ranks);
         __syncthreads();
-#pragma unroll
-        for (int w = 0; w < 4; ++w) q_val[w] = (double)(s_val[w] - pp_vox<InT>::bias);
+        B = pp_key_bounds<InT>(&s_ranks, qc, A.max_thresh);
     }
-
-    pp_sat_t<pp_vox<InT>::is_signed> S;
-    double info_vmin, info_vmax;
-    {
-        double vmin = pp_lerp(q_val[0], q_val[1], qc.lo_gamma);
-        double vmax = pp_lerp(q_val[2], q_val[3], qc.hi_gamma);
-        if constexpr (pp_vox<InT>::is_signed) {       // (the difference in the voxel type: pp_vox)
-            vmin = pp_vox<InT>::lerp(s_val[0], s_val[1], qc.lo_gamma);
-            vmax = pp_vox<InT>::lerp(s_val[2], s_val[3], qc.hi_gamma);
-        }
-        S.identity = vmin == vmax;
-        if (vmax < A.max_thresh) vmax = A.max_thresh;
-        S.vmin = vmin; S.vmax = vmax; S.span = vmax - vmin;
-        info_vmin = vmin; info_vmax = vmax;
-        S.finish();
-    }
+    const auto S = pp_sat_t<pp_vox<InT>::is_signed>::make(B.vmin, B.vmax, B.identity);
 
     // (an identity tile -- vmin == vmax: the reference leaves the voxels alone -- of a float64 image may hold negative
-    //  values, which the vmin = 0 stand-in of pp_sat would clip)
+    //  values, which the vmin = 0 stand-in of pp_sat_t would clip)
     auto sat = [&](double v) { return (F64 && S.identity) ? v : S.plain(v); };
     double part = 0.;
     for (int64_t i = tid; i < n; i += PP_WG_GENERIC) {
@@ -684,26 +532,17 @@ pp_generic_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t s
         double tot = 0.;
         for (int w = 0; w < PP_WG_GENERIC / 64; ++w) tot += s_red[w];
         double mean = tot / (double)n;
-        int flags = S.identity ? MMX_PP_IDENTITY : 0;
-        if (A.do_erosion) {
-            const double tol = 1e-9 * (fabs(A.ero_thr) > 1. ? fabs(A.ero_thr) : 1.);
-            if (!S.identity && fabs(mean - A.ero_thr) <= tol && n < (1ll << 31)) {
-                auto val = [&](int i) { return sat((double)raw(i)); };
-                mean = pp_pairwise(val, (int)n, &s_stack) / (double)n;
-                flags |= MMX_PP_EXACT_MEAN;
-            }
-            if (mean > A.ero_thr) flags |= MMX_PP_ERODED;
-        }
+        s_flags = pp_mean_verdict(mean, S.identity, A, [&](double& m) {
+            if (n >= (1ll << 31)) return m > A.ero_thr ? MMX_PP_ERODED : 0;      // (pp_pairwise indexes with int: the parallel sum stands)
+            auto val = [&](int i) { return sat((double)raw(i)); };
+            m = pp_pairwise(val, (int)n, &s_stack) / (double)n;
+            return pp_exact_verdict(m, A);
+        });
         s_mean = mean;
-        s_flags = flags;
     }
     __syncthreads();
     const int flags = s_flags;
-    if (info && tid == 0) {
-        mmx_subblock_info o;
-        o.vmin = info_vmin; o.vmax = info_vmax; o.mean = s_mean; o.flags = flags; o._pad = 0;
-        info[blockIdx.x] = o;
-    }
+    if (info && tid == 0) pp_write_info(info, blockIdx.x, B.vmin, B.vmax, s_mean, flags);
 
     // ---- total-variation denoising of the clipped tile (reference plot_3d.py:147-149 ->
     // skimage.restoration.denoise_tv_chambolle, restoration/_denoise.py:315-393): Chambolle's projection
@@ -828,33 +667,19 @@ pp_generic_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t s
         if (A.do_unsharp) {
             const double den = tv ? den_buf[i]
                                   : pp_clip(sat((double)raw(i)), A.clip_min, A.clip_max);
-            const double m = A.strength * cur[i];
-            const double hp = den - m;
-            o = den + hp;
+            o = pp_unsharp(den, cur[i], A.strength);
         } else {
             o = cur[i];
         }
         if (erode) oth[i] = o;
-        else {
-            const int64_t d = sb.dst_off + z * A.dst_sz + y * A.dst_sy + x;
-            out64[d] = o;
-            out32[d] = (float)o;
-        }
+        else pp_put(out64, out32, sb.dst_off + z * A.dst_sz + y * A.dst_sy + x, o);
     }
     if (!erode) return;
     __syncthreads();
     for (int64_t i = tid; i < n; i += PP_WG_GENERIC) {
         const int64_t t = i / nx, x = i - t * nx, z = t / ny, y = t - z * ny;
-        double o = oth[i];
-        if (x > 0) o = fmin(o, oth[i - 1]);
-        if (x < nx - 1) o = fmin(o, oth[i + 1]);
-        if (y > 0) o = fmin(o, oth[i - nx]);
-        if (y < ny - 1) o = fmin(o, oth[i + nx]);
-        if (z > 0) o = fmin(o, oth[i - ny * nx]);
-        if (z < nz - 1) o = fmin(o, oth[i + ny * nx]);
-        const int64_t d = sb.dst_off + z * A.dst_sz + y * A.dst_sy + x;
-        out64[d] = o;
-        out32[d] = (float)o;
+        const double o = pp_erode7(oth, i, nx, ny * nx, x > 0, x < nx - 1, y > 0, y < ny - 1, z > 0, z < nz - 1);
+        pp_put(out64, out32, sb.dst_off + z * A.dst_sz + y * A.dst_sy + x, o);
     }
 }
 

@@ -33,7 +33,6 @@
 #define PPS_NB_LOAD 16       // global loads in flight per lane
 #define PPB_WG 768           // blur kernel: twelve waves, three per SIMD (<= 168 VGPRs)
 #define PPB_L 25             // the line length the pass is specialised for
-#define MMX_PP_KNIFE 0x100   // internal: the statistics kernel asks the blur kernel for np.mean's own summation order
 #define PPB_NB 7             // voxels per lane and step in the element-wise stages (25^3: 21 rows per lane = 3 x 7)
 
 // -DPP_PROFILE (an experiment build: make EXTRA=-DPP_PROFILE OBJDIR=_obj_prof OUT=../libmmx_prof.so): lane 0 of every
@@ -262,9 +261,7 @@ pp_stats_kernel(const uint16_t* __restrict__ copy, const int64_t* __restrict__ c
                 const mmx_quantile_class* __restrict__ qcs, pp_args A, mmx_subblock_info* __restrict__ info)
 {
     __shared__ uint32_t hist[PP_HIST];
-    __shared__ int s_bin[4];
-    __shared__ uint32_t s_res[4];
-    __shared__ int s_val[4];
+    __shared__ pp_ranks s_ranks;
     __shared__ uint32_t s_sum[PPS_WG / 64][4];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -301,54 +298,38 @@ pp_stats_kernel(const uint16_t* __restrict__ copy, const int64_t* __restrict__ c
     PP_TICK(0, 0);
 
     const mmx_quantile_class qc = qcs[sb.qclass];
-    {
+    {   // pp_select_high, pasted: the helper costs this kernel a VGPR (exactly four waves here: no guard)
+        static_assert(PPS_WG == 256, "one wave per rank");
         const uint32_t rank = wave == 0 ? qc.lo_prev : wave == 1 ? qc.lo_next : wave == 2 ? qc.hi_prev : qc.hi_next;
         int b; uint32_t r;
         pp_select(hist, rank, b, r);
-        if (lane == 0) { s_bin[wave] = b; s_res[wave] = r; }
+        if (lane == 0) { s_ranks.bin[wave] = b; s_ranks.res[wave] = r; }
     }
     __syncthreads();
     PP_TICK(0, 1);
     {
-        // one low-byte histogram per DISTINCT high-byte bin (prev / next ranks usually share theirs)
-        const int b0 = s_bin[0], b1 = s_bin[1], b2 = s_bin[2], b3 = s_bin[3];
-        const bool u1 = b1 != b0, u2 = b2 != b0 && b2 != b1, u3 = b3 != b0 && b3 != b1 && b3 != b2;
-        auto add2 = [&](int vv) {
-            if (vv < 0) return;
-            const int hi = vv >> 8, lo = vv & 255;
-            if (hi == b0) atomicAdd(&hist[256 + lo], 1u);
-            if (u1 && hi == b1) atomicAdd(&hist[512 + lo], 1u);
-            if (u2 && hi == b2) atomicAdd(&hist[768 + lo], 1u);
-            if (u3 && hi == b3) atomicAdd(&hist[1024 + lo], 1u);
-        };
+        const pp_bins bins(&s_ranks);
         for (int i0 = 0; i0 < n; i0 += 8 * PPS_WG) {
             int w8[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) w8[j] = vox(i0 + j * PPS_WG + tid);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) add2(w8[j]);
+            for (int j = 0; j < 8; ++j) if (w8[j] >= 0) bins.add(hist, w8[j]);
         }
     }
     __syncthreads();
     PP_TICK(0, 2);
-    {
-        int slot = wave;
-        for (int w = wave - 1; w >= 0; --w) if (s_bin[w] == s_bin[wave]) slot = w;
-        int b; uint32_t r;
-        pp_select(hist + 256 * (1 + slot), s_res[wave], b, r);
-        if (lane == 0) s_val[wave] = (s_bin[wave] << 8) | b;
-    }
+    pp_select_low(hist, &s_ranks);
     __syncthreads();
     PP_TICK(0, 3);
     // np.mean(saturated) gates the erosion.  saturated = (clip(v, vmin, vmax) - vmin) / span, so its sum is
     // (sum over vmin <= v <= vmax of (v - floor(vmin)) - n_mid frac(vmin) + n_hi span) / span up to roundings of
     // 1e-16 of itself: integer sums.  Within 1e-9 of the threshold the blur kernel, which
     // holds the voxels in LDS, re-sums in NumPy's pairwise order (MMX_PP_KNIFE: internal, cleared there).
-    using vx = pp_vox<typename std::conditional<SIGNED, int16_t, uint16_t>::type>;
-    const double vmin = vx::lerp(s_val[0], s_val[1], qc.lo_gamma);
-    double vmax = vx::lerp(s_val[2], s_val[3], qc.hi_gamma);
-    const bool identity = vmin == vmax;
-    if (vmax < A.max_thresh) vmax = A.max_thresh;
+    using vox_t = typename std::conditional<SIGNED, int16_t, uint16_t>::type;
+    using vx = pp_vox<vox_t>;
+    const pp_bounds B = pp_key_bounds<vox_t>(&s_ranks, qc, A.max_thresh);
+    const double vmin = B.vmin, vmax = B.vmax;
     // (the sums below only gate the erosion, to 1e-9: the moved bounds may round in their last bit)
     const double kmin = SIGNED ? vmin + (double)vx::bias : vmin, kmax = SIGNED ? vmax + (double)vx::bias : vmax;
     const int v0 = (int)floor(kmin);
@@ -381,17 +362,10 @@ pp_stats_kernel(const uint16_t* __restrict__ copy, const int64_t* __restrict__ c
         for (int w = 0; w < PPS_WG / 64; ++w) for (int q = 0; q < 4; ++q) t[q] += s_sum[w][q];
         const double nd = (double)n, span = vmax - vmin;
         double mean;
-        if (identity) mean = SIGNED ? ((double)t[3] - (double)vx::bias * nd) / nd : (double)t[3] / nd;
+        if (B.identity) mean = SIGNED ? ((double)t[3] - (double)vx::bias * nd) / nd : (double)t[3] / nd;
         else mean = (((double)t[0] - (double)t[1] * (kmin - (double)v0)) + (double)t[2] * span) / span / nd;
-        int fl = identity ? MMX_PP_IDENTITY : 0;
-        if (A.do_erosion) {
-            const double tol = 1e-9 * (fabs(A.ero_thr) > 1. ? fabs(A.ero_thr) : 1.);
-            if (!identity && fabs(mean - A.ero_thr) <= tol) fl |= MMX_PP_KNIFE;
-            else if (mean > A.ero_thr) fl |= MMX_PP_ERODED;
-        }
-        mmx_subblock_info o;
-        o.vmin = vmin; o.vmax = vmax; o.mean = mean; o.flags = fl; o._pad = 0;
-        info[sub_id] = o;
+        const int fl = pp_mean_verdict(mean, B.identity, A, [](double&) { return MMX_PP_KNIFE; });
+        pp_write_info(info, sub_id, vmin, vmax, mean, fl);
     }
     PP_TICK(0, 4);
 }
@@ -503,10 +477,7 @@ pp_blur_kernel(const uint16_t* __restrict__ copy, const int64_t* __restrict__ co
         g.nz = sb.nz; g.ny = sb.ny; g.nx = sb.nx; g.px = sb.nx | 1; g.n = sb.nz * sb.ny * sb.nx; g.nrows = sb.nz * sb.ny;
         const float inv_nx = 1.0f / (float)g.nx, inv_ny = 1.0f / (float)g.ny;
         constexpr int kBias = SIGNED ? mmx_key<int16_t>::bias : 0;          // (raw holds keys)
-        pp_sat_t<SIGNED> S;
-        S.identity = inf.flags & MMX_PP_IDENTITY;
-        S.vmin = inf.vmin; S.vmax = inf.vmax; S.span = inf.vmax - inf.vmin;
-        S.finish();
+        pp_sat_t<SIGNED> S = pp_sat_t<SIGNED>::make(inf.vmin, inf.vmax, inf.flags & MMX_PP_IDENTITY);
         S.vmin = pp_uniform(S.vmin); S.vmax = pp_uniform(S.vmax); S.span = pp_uniform(S.span); S.rcp = pp_uniform(S.rcp);
         if (tid == 0) {                 // (read after the passes' barriers; rewritten after this tile's last barrier)
             s_par[0] = A.clip_min; s_par[1] = A.clip_max; s_par[2] = A.strength;
@@ -534,6 +505,26 @@ pp_blur_kernel(const uint16_t* __restrict__ copy, const int64_t* __restrict__ co
                 const bool from_raw = axis == 0;
                 const bool flush = from_raw && flush_prev;
                 auto no_pre = [](int) {};
+                // a line's registers: clip(stretch(voxel)) on the first pass, the tile afterwards
+                auto ld = [&](auto& ln, int tbase, int tstride, int rbase, int rstride) {
+                    auto vox = [&](auto sat) {
+                        ln.load([&](int i, bool) { return pp_clip(sat((int)raw[rbase + i * rstride]), cmin, cmax); }, L);
+                    };
+                    if (!from_raw) ln.load([&](int i, bool) { return tile[tbase + i * tstride]; }, L);
+                    else if (S.fast) vox(sat_fast);
+                    else vox(sat_plain);
+                };
+                // the previous tile's result goes out from where output i is about to land
+                // (z lines: line l = y * nx + x, output i is plane z = i -- the previous tile's voxel (i, y, x))
+                auto pre_flush = [&](int tbase, int tstride, int rbase) {
+                    const int f_off = rbase / g.nx * f_dsy + rbase % g.nx;
+                    return [=](int i) {
+                        const double o = tile[tbase + i * tstride];
+                        const unsigned off = (unsigned)(f_off + i * f_dsz);
+                        pp_store_f64(p64, off << 3, o);
+                        pp_store_f32(p32, off << 2, (float)o);
+                    };
+                };
                 if (L == PPB_L && nlines > 512 && nlines <= 640) {
                     // twelve waves, 2.5 wave-lines per SIMD: whole lines on waves 0..7, half passes on 8..11
                     const int l = wave < 8 ? tid : (8 + ((wave - 8) >> 1)) * 64 + lane;
@@ -542,29 +533,15 @@ pp_blur_kernel(const uint16_t* __restrict__ copy, const int64_t* __restrict__ co
                     int tbase, tstride, rbase, rstride;
                     pp_line_addr(g, axis, on ? l : 0, inv_nx, tbase, tstride, rbase, rstride);
                     pp_line<PPB_L, true> ln;
-                    if (from_raw) {
-                        auto ld = [&](auto sat) {
-                            ln.load([&](int i, bool) { return pp_clip(sat((int)raw[rbase + i * rstride]), cmin, cmax); }, L);
-                        };
-                        if (S.fast) ld(sat_fast); else ld(sat_plain);
-                    } else {
-                        ln.load([&](int i, bool) { return tile[tbase + i * tstride]; }, L);
-                        // (two waves share the lines of the half passes: every read of an in-place pass before any write)
-                        pp_lds_barrier();
-                    }
-                    // (z lines: line l = y * nx + x, output i is plane z = i -- the previous tile's voxel (i, y, x))
-                    const int f_off = rbase / g.nx * f_dsy + rbase % g.nx;
-                    auto pre_flush = [&](int i) {
-                        const double o = tile[tbase + i * tstride];
-                        const unsigned off = (unsigned)(f_off + i * f_dsz);
-                        pp_store_f64(p64, off << 3, o);
-                        pp_store_f32(p32, off << 2, (float)o);
-                    };
+                    ld(ln, tbase, tstride, rbase, rstride);
+                    // (two waves share the lines of the half passes: every read of an in-place pass before any write)
+                    if (!from_raw) pp_lds_barrier();
+                    const auto pf = pre_flush(tbase, tstride, rbase);
                     if (on) {
                         if (flush) {
-                            if (half == 0) ln.template run<0, PPB_L>(tile, tbase, tstride, L, wl, pre_flush);
-                            else if (half == 1) ln.template run<0, (PPB_L + 1) / 2>(tile, tbase, tstride, L, wl, pre_flush);
-                            else ln.template run<(PPB_L + 1) / 2, PPB_L>(tile, tbase, tstride, L, wl, pre_flush);
+                            if (half == 0) ln.template run<0, PPB_L>(tile, tbase, tstride, L, wl, pf);
+                            else if (half == 1) ln.template run<0, (PPB_L + 1) / 2>(tile, tbase, tstride, L, wl, pf);
+                            else ln.template run<(PPB_L + 1) / 2, PPB_L>(tile, tbase, tstride, L, wl, pf);
                         } else {
                             if (half == 0) ln.template run<0, PPB_L>(tile, tbase, tstride, L, wl, no_pre);
                             else if (half == 1) ln.template run<0, (PPB_L + 1) / 2>(tile, tbase, tstride, L, wl, no_pre);
@@ -576,40 +553,18 @@ pp_blur_kernel(const uint16_t* __restrict__ copy, const int64_t* __restrict__ co
                         int tbase, tstride, rbase, rstride;
                         pp_line_addr(g, axis, l, inv_nx, tbase, tstride, rbase, rstride);
                         pp_line<PPB_L, true> ln;
-                        auto ld = [&](auto sat) {
-                            ln.load([&](int i, bool) { return pp_clip(sat((int)raw[rbase + i * rstride]), cmin, cmax); }, L);
-                        };
-                        if (from_raw) { if (S.fast) ld(sat_fast); else ld(sat_plain); }
-                        else ln.load([&](int i, bool) { return tile[tbase + i * tstride]; }, L);
-                        const int f_off = rbase / g.nx * f_dsy + rbase % g.nx;
-                        auto pre_flush = [&](int i) {
-                            if (!flush) return;
-                            const double o = tile[tbase + i * tstride];
-                            const unsigned off = (unsigned)(f_off + i * f_dsz);
-                            pp_store_f64(p64, off << 3, o);
-                            pp_store_f32(p32, off << 2, (float)o);
-                        };
-                        ln.template run<0, PPB_L>(tile, tbase, tstride, L, wl, pre_flush);
+                        ld(ln, tbase, tstride, rbase, rstride);
+                        const auto pf = pre_flush(tbase, tstride, rbase);
+                        ln.template run<0, PPB_L>(tile, tbase, tstride, L, wl, [&](int i) { if (flush) pf(i); });
                     }
                 } else {
                     for (int l = tid; l < nlines; l += PPB_WG) {
                         int tbase, tstride, rbase, rstride;
                         pp_line_addr(g, axis, l, inv_nx, tbase, tstride, rbase, rstride);
                         pp_line<PP_MAXL, false> ln;
-                        auto ld = [&](auto sat) {
-                            ln.load([&](int i, bool) { return pp_clip(sat((int)raw[rbase + i * rstride]), cmin, cmax); }, L);
-                        };
-                        if (from_raw) { if (S.fast) ld(sat_fast); else ld(sat_plain); }
-                        else ln.load([&](int i, bool) { return tile[tbase + i * tstride]; }, L);
-                        const int f_off = rbase / g.nx * f_dsy + rbase % g.nx;
-                        auto pre_flush = [&](int i) {
-                            if (!flush) return;
-                            const double o = tile[tbase + i * tstride];
-                            const unsigned off = (unsigned)(f_off + i * f_dsz);
-                            pp_store_f64(p64, off << 3, o);
-                            pp_store_f32(p32, off << 2, (float)o);
-                        };
-                        ln.template run<0, PP_MAXL>(tile, tbase, tstride, L, wl, pre_flush);
+                        ld(ln, tbase, tstride, rbase, rstride);
+                        const auto pf = pre_flush(tbase, tstride, rbase);
+                        ln.template run<0, PP_MAXL>(tile, tbase, tstride, L, wl, [&](int i) { if (flush) pf(i); });
                     }
                 }
                 pp_lds_barrier();
@@ -623,11 +578,10 @@ pp_blur_kernel(const uint16_t* __restrict__ copy, const int64_t* __restrict__ co
             if (tid == 0) {
                 auto val = [&](int i) { return S.plain((double)((int)raw[i] - kBias)); };
                 const double mean = pp_pairwise(val, g.n, &s_stack) / (double)g.n;
-                int fl = (flags & ~MMX_PP_KNIFE) | MMX_PP_EXACT_MEAN;
-                if (mean > A.ero_thr) fl |= MMX_PP_ERODED;
+                const int fl = (flags & ~MMX_PP_KNIFE) | pp_exact_verdict(mean, A);
                 s_flags = fl;
-                mmx_subblock_info o = inf;
-                o.mean = mean; o.flags = fl;
+                mmx_subblock_info o = inf;       // (the statistics kernel's record with two fields replaced; pp_write_info
+                o.mean = mean; o.flags = fl;     //  of the five fields costs this kernel a VGPR)
                 info[k] = o;
             }
             pp_lds_barrier();
@@ -692,13 +646,7 @@ pp_blur_kernel(const uint16_t* __restrict__ copy, const int64_t* __restrict__ co
 #pragma unroll
             for (int j = 0; j < PPB_NB; ++j) {
                 const double den = pp_clip(Sv((double)(rv[j] - kBias)), v_cmin, v_cmax);
-                if (unsharp.value) {
-                    const double m = v_str * bl[j];
-                    const double hp = den - m;
-                    o[j] = den + hp;
-                } else {
-                    o[j] = den;
-                }
+                o[j] = unsharp.value ? pp_unsharp(den, bl[j], v_str) : den;
             }
 #pragma unroll
             for (int j = 0; j < PPB_NB; ++j) {
@@ -717,12 +665,7 @@ pp_blur_kernel(const uint16_t* __restrict__ copy, const int64_t* __restrict__ co
         if (!S.fast) {                       // (never with integer voxels) the plain division, one voxel at a time
             for (walk w = w0; w.row < nrows; advance(w)) {
                 const double den = pp_clip(sat_plain((int)raw[w.ri]), cmin, cmax);
-                double o = den;
-                if (A.do_unsharp) {
-                    const double m = A.strength * tile[w.ti];
-                    const double hp = den - m;
-                    o = den + hp;
-                }
+                const double o = A.do_unsharp ? pp_unsharp(den, tile[w.ti], A.strength) : den;
                 if (erode) tile[w.ti] = o;
                 else put(w, o);
             }
@@ -757,15 +700,8 @@ pp_blur_kernel(const uint16_t* __restrict__ copy, const int64_t* __restrict__ co
         if (erode) {
             pp_lds_barrier();
             for (walk w = w0; w.row < nrows; advance(w)) {
-                const int pos = w.ti;
-                double o = tile[pos];
-                if (x > 0) o = fmin(o, tile[pos - 1]);
-                if (x < nx - 1) o = fmin(o, tile[pos + 1]);
-                if (w.y > 0) o = fmin(o, tile[pos - px]);
-                if (w.y < ny - 1) o = fmin(o, tile[pos + px]);
-                if (w.row >= ny) o = fmin(o, tile[pos - ny * px]);
-                if (w.row < nrows - ny) o = fmin(o, tile[pos + ny * px]);
-                put(w, o);
+                put(w, pp_erode7(tile, w.ti, px, ny * px, x > 0, x < nx - 1, w.y > 0, w.y < ny - 1, w.row >= ny,
+                                 w.row < nrows - ny));
             }
         }
         pp_lds_barrier();                 // the tile and the voxel copy are free / complete

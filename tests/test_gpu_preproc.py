@@ -134,6 +134,61 @@ def test_generic_kernel_equals_fast_kernel(gpu, env, monkeypatch):
         np.testing.assert_array_equal(fast, slow)
 
 
+def _select_tile(kind, dtype):
+    """One small tile whose four percentile ranks land in a known number of DISTINCT high-byte bins of the two-level
+    radix select: ``(tile, distinct bins)``.  16-bit ramps step by 300, more than a high byte, so every voxel has a bin
+    of its own; uint8 keys ("ramp") all share high byte 0."""
+    wide = np.dtype(dtype).itemsize == 2
+    shift = -20000 if dtype == np.int16 else 0
+    if kind == "const":                                   # all four ranks in one bin, vmin == vmax: identity
+        return np.full((3, 5, 9), {np.uint8: 77, np.uint16: 777, np.int16: -777}[dtype], dtype), 1
+    shape = (1, 3, 7) if kind == "gamma0" else (3, 5, 9)  # gamma0: clip_vmin * (n - 1) is an integer, the lerp's weight is 0
+    v = np.arange(int(np.prod(shape)), dtype=np.int64) * (300 if wide else 1) + shift
+    if kind == "three":
+        v[-1] = v[-2] + 10                                # the two top ranks share a high byte
+    bins = {"four": 4, "three": 3, "gamma0": 4, "ramp": 1}[kind]
+    return np.random.default_rng(4).permutation(v).reshape(shape).astype(dtype), bins
+
+
+@pytest.mark.parametrize("kind,dtype", [(k, d) for d in (np.uint16, np.int16) for k in ("four", "three", "gamma0", "const")]
+                         + [("ramp", np.uint8), ("const", np.uint8)], ids=lambda v: getattr(v, "__name__", v))
+def test_every_kernel_form_selects_the_same_order_statistics(gpu, env, monkeypatch, kind, dtype):
+    """The branches of the two-level select through every kernel form.
+
+    Tiles: four / three / one distinct high-byte bins among the ranks, and a lower percentile that is an order
+    statistic itself (gamma 0).  Forms: one-tile blocks through ``MMX_PP_SINGLE``, ``MMX_PP_PIPELINED``, the
+    register-line kernel over a scratch (``FORCE_GENERIC = True``) and one output per lane (``"big"``).  Compared with
+    the oracle bit for bit and with ``np.percentile``; where the ranks land is asserted on the host first."""
+    from magellanmapper_amd import _native as nat, preprocess
+    from oracle import preprocess_oracle as ppo
+    roi, bins = _select_tile(kind, dtype)
+    profs = _set_profiles({})
+    lo, hi = profs[0]["clip_vmin"], profs[0]["clip_vmax"]
+    (lo_prev, lo_next, lo_g), (hi_prev, hi_next, _) = (preprocess.quantile_ranks(roi.size, q) for q in (lo, hi))
+    ranks = (lo_prev, lo_next, hi_prev, hi_next)
+    keys = np.sort(roi.ravel().astype(np.int64)) - np.iinfo(dtype).min          # the order-preserving keys
+    high = [int(keys[r]) >> 8 for r in ranks]
+    assert len(set(high)) == bins, (ranks, high)
+    vmin, vmax = np.percentile(roi, (lo, hi))
+    assert (vmin == vmax) == (kind == "const")
+    if kind == "gamma0":                                  # 5 % of 20 intervals: rank 1 exactly
+        assert lo == 5 and lo_prev == 1 and lo_g == 0.0 and vmin == np.sort(roi.ravel())[1]
+    elif kind != "const":
+        assert 0.0 < lo_g < 1.0
+
+    want = ppo.preprocess_block(roi, roi.shape, profs, [-1.0])
+    for label, mode, force in (("single", nat.MMX_PP_SINGLE, False), ("pipelined", nat.MMX_PP_PIPELINED, False),
+                               ("generic", nat.MMX_PP_AUTO, True), ("one output per lane", nat.MMX_PP_AUTO, "big")):
+        monkeypatch.setattr(preprocess, "KERNEL_MODE", mode)
+        monkeypatch.setattr(preprocess, "FORCE_GENERIC", force)
+        got, infos = preprocess.preprocess_roi(roi, roi.shape, near_max=[-1.0], return_info=True)
+        np.testing.assert_array_equal(got, want, err_msg=label)
+        (_, info), = infos
+        assert len(info) == 1 and info["vmin"][0] == vmin, label
+        assert bool(info["flags"][0] & nat.MMX_PP_IDENTITY) == (kind == "const"), label
+        assert info["vmax"][0] == max(vmax, -1.0 * profs[0]["max_thresh_factor"]), label
+
+
 def _synthetic_block(shape, seed, dtype=np.uint16, flat=()):
     """Background + blobs like the benchmark volume (tiles with and without erosion); ``flat`` = (z0, y0, x0, n)
     cubes of one value (vmin == vmax tiles: the reference leaves those voxels alone)."""
