@@ -8,21 +8,13 @@ import pytest
 
 from conftest import load_golden
 from test_bounds_host import BOUNDS, NAMES, fixture_volume
+from gpu_support import gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
 PCTS = [tuple(float(v) for v in p) for p in BOUNDS["pcts"]]
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a GPU: torch.cuda.is_available() is False")
-    from magellanmapper_amd import _native
-    assert _native.lib().mmx_device_count() >= 1
-    return torch.device("cuda", 0)
 
 
 @pytest.fixture

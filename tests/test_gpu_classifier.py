@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from gpu_support import gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -12,13 +13,6 @@ torch = pytest.importorskip("torch")
 
 SIZES = (16, 5, 2)
 COLS = ["z", "y", "x", "radius", "confirmed", "truth", "channel", "region"]
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a GPU: torch.cuda.is_available() is False")
-    return torch.device("cuda", 0)
 
 
 @pytest.fixture(scope="module")

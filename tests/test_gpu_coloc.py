@@ -6,19 +6,11 @@ import pytest
 
 from conftest import load_golden
 from test_oracle_golden import COLOC, coloc_roi, coloc_thresh
+from gpu_support import gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a GPU: torch.cuda.is_available() is False")
-    from magellanmapper_amd import _native
-    assert _native.lib().mmx_device_count() >= 1
-    return torch.device("cuda", 0)
 
 
 @pytest.mark.parametrize("case", [str(n) for n in COLOC["names"]])

@@ -17,17 +17,10 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from gpu_support import gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 RES = np.array([[1.0, 1.0, 1.0]])
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    torch = pytest.importorskip("torch")
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a GPU: torch.cuda.is_available() is False")
-    return torch.device("cuda", 0)
 
 
 def _host_volume(shape, seed, channels=1):

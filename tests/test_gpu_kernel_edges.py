@@ -8,22 +8,13 @@ import math
 import numpy as np
 import pytest
 
+from gpu_support import as_dtype, gpu, rescore_strip, stream_ptr  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
 LOG_TOL = 1e-4
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import os
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a GPU: torch.cuda.is_available() is False")
-    from magellanmapper_amd import _native
-    assert os.path.exists(_native.LIB_PATH), "libmmx_hip.so must be built in-tree"
-    assert _native.lib().mmx_device_count() >= 1, "no gfx950 device visible to libmmx_hip.so"
-    return torch.device("cuda", 0)
 
 
 @pytest.fixture(params=["native", "numpy"])
@@ -32,19 +23,6 @@ def host_path(request, monkeypatch):
     from magellanmapper_amd import blob_log as bl
     monkeypatch.setattr(bl, "HOST_PATH", request.param)
     return request.param
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _as_dtype(vol16, dtype):
-    """One uint16 volume in each of the four voxel types the ABI takes."""
-    if dtype == np.uint16:
-        return vol16
-    if dtype == np.uint8:
-        return (vol16 >> 8).astype(np.uint8)
-    return (vol16 / 65535.0).astype(dtype)
 
 
 DTYPES = [np.uint8, np.uint16, np.float32, np.float64]
@@ -71,7 +49,7 @@ def test_log_cube_at_large_radii_on_blocks_thinner_than_the_radius(gpu, thin_vol
     radius along each axis -- SciPy's ``reflect`` extension wraps there several times -- beside a thick one."""
     from magellanmapper_amd import _native as nat, blob_log as bl
     from oracle import blob_log_oracle as blo
-    vol = _as_dtype(thin_volume, dtype)
+    vol = as_dtype(thin_volume, dtype)
     dvol = bl.DeviceVolume(vol)
     subs = [blo.img_as_float(vol[o[0]:o[0] + s[0], o[1]:o[1] + s[1], o[2]:o[2] + s[2]])
             for o, s in zip(THIN_ORIGINS, THIN_SHAPES)]
@@ -103,15 +81,6 @@ def test_log_cube_at_large_radii_on_blocks_thinner_than_the_radius(gpu, thin_vol
 
 
 # ---------------------------------------------------------------- 2. exact re-score: the strip loop
-LDS_BUDGET = 60 * 1024
-
-
-def _strip(rmax):
-    """Columns the re-score stages at once for a batch whose largest radius is ``rmax`` (mmx_rescore.hip)."""
-    n = 2 * rmax + 1
-    return min(n, (LDS_BUDGET - 32 * n - 16) // (16 * n))
-
-
 def _n_strips(r, strip):
     n = 2 * r + 1
     return -(-n // min(strip, n))
@@ -144,7 +113,7 @@ def _rescore(dvol, origins, shapes, ladder, pts, store_f32, dev):
     vol = dvol.view(0, False)
     nat.check(nat.lib().mmx_rescore_f64(
         ctypes.byref(vol), d_blocks.data_ptr(), len(blocks), d_pts.data_ptr(), len(pts), None, d_w0.data_ptr(),
-        d_w2.data_ptr(), nat.as_int32_ptr(radii), nat.as_double_ptr(norms), len(radii), store_f32, _stream()),
+        d_w2.data_ptr(), nat.as_int32_ptr(radii), nat.as_double_ptr(norms), len(radii), store_f32, stream_ptr()),
         "mmx_rescore_f64")
     return d_pts.cpu().numpy().view(nat.CAND_DTYPE)["v64"]
 
@@ -165,7 +134,7 @@ def test_rescore_strip_loop_bit_exact(gpu, dtype):
     and corner voxel (fewer at R >= 200) and random inner points of three small blocks: bit for bit the oracle cube."""
     from magellanmapper_amd import _native as nat, blob_log as bl, synth
     from oracle import blob_log_oracle as blo
-    vol = _as_dtype(synth.make_volume(5, (24, 40, 36), 10, blob_sigma=2.5), dtype)
+    vol = as_dtype(synth.make_volume(5, (24, 40, 36), 10, blob_sigma=2.5), dtype)
     dvol = bl.DeviceVolume(vol)
     store_f32 = 1 if dtype == np.float32 else 0
     rng = np.random.default_rng(17)
@@ -173,7 +142,7 @@ def test_rescore_strip_loop_bit_exact(gpu, dtype):
         lad = _ladder(sigmas)
         radii = lad[2]
         assert sorted(strips) == sorted(int(r) for r in radii)
-        strip = _strip(int(radii.max()))
+        strip = rescore_strip(int(radii.max()))
         for r, n in strips.items():
             assert _n_strips(r, strip) == n, (r, strip)
         rows, want = [], []
@@ -216,7 +185,7 @@ def test_blob_log_at_large_sigma_matches_oracle(gpu, case, host_path):
     shape, n_blobs, blob_sigma, (lo, hi, ns) = LARGE_SIGMA_CASES[case]
     vol = synth.make_volume(7, shape, n_blobs, blob_sigma=blob_sigma, margin=10)
     space = bl.ScaleSpace.make(lo, hi, ns)
-    assert space.radii.min() > 30 and _n_strips(int(space.radii.max()), _strip(int(space.radii.max()))) > 2
+    assert space.radii.min() > 30 and _n_strips(int(space.radii.max()), rescore_strip(int(space.radii.max()))) > 2
     if case not in _LARGE_SIGMA_ORACLE:
         _LARGE_SIGMA_ORACLE[case] = blo.blob_log(vol, lo, hi, ns, 0.05, 0.5)
     want = _LARGE_SIGMA_ORACLE[case]
@@ -315,7 +284,7 @@ def _overlap_call(allb, offsets, overlap, band, max_sigma, cap, guard, dev):
     d_count = torch.zeros(1, dtype=torch.int32, device=dev)
     nat.check(nat.lib().mmx_overlap_pairs(d_blobs.data_ptr(), d_off.data_ptr(), len(offsets) - 1, overlap, band,
                                           max_sigma, d_pairs.data_ptr(), d_frac.data_ptr(), cap, d_count.data_ptr(),
-                                          _stream()), "mmx_overlap_pairs")
+                                          stream_ptr()), "mmx_overlap_pairs")
     n = int(d_count.item()) & 0xFFFFFFFF
     return n, d_pairs.cpu().numpy().reshape(-1, 2).astype(np.int64), d_frac.cpu().numpy()
 
@@ -432,7 +401,7 @@ def test_resize_wide_rows_bit_exact(gpu, dtype):
     from scipy import ndimage as ndi
     from magellanmapper_amd import _native as nat, blob_log as bl, preprocess
     rng = np.random.default_rng(19)
-    vol = _as_dtype(rng.integers(0, 65536, (6, 8, 900)).astype(np.uint16), dtype)
+    vol = as_dtype(rng.integers(0, 65536, (6, 8, 900)).astype(np.uint16), dtype)
     dvol = bl.DeviceVolume(vol)
     src = dvol.view(0, False)
     strides = (src.stride_z, src.stride_y, src.stride_x)
@@ -448,7 +417,7 @@ def test_resize_wide_rows_bit_exact(gpu, dtype):
     d_mm = torch.from_numpy(mm).to(gpu)
     d_src = bl._to_device_bytes(src_blocks, gpu)
     nat.check(nat.lib().mmx_minmax_batch(ctypes.byref(src), d_src.data_ptr(), src_blocks.ctypes.data, nb,
-                                         d_mm.data_ptr(), _stream()), "mmx_minmax_batch")
+                                         d_mm.data_ptr(), stream_ptr()), "mmx_minmax_batch")
     tabs_i, tabs_w, rb, at = [], [], np.zeros(nb, dtype=nat.RESIZE_DTYPE), 0
     for i, (o, si, so) in enumerate(zip(origins, ins, outs)):
         t3 = []
@@ -471,7 +440,7 @@ def test_resize_wide_rows_bit_exact(gpu, dtype):
     out32 = torch.zeros(nb * slot, dtype=torch.float32, device=gpu) if dtype == np.float64 else None
     nat.check(nat.lib().mmx_resize_batch_as(ctypes.byref(src), d_rb.data_ptr(), rb.ctypes.data, nb, d_idx.data_ptr(),
                                             d_wts.data_ptr(), d_mm.data_ptr(), slot, sy, sz, int(src.dtype),
-                                            out.data_ptr(), None if out32 is None else out32.data_ptr(), _stream()),
+                                            out.data_ptr(), None if out32 is None else out32.data_ptr(), stream_ptr()),
               "mmx_resize_batch_as")
     mm_got = d_mm.cpu().numpy()
     res = out.cpu().numpy().view(dtype).reshape(nb, -1)
@@ -499,7 +468,7 @@ def test_gauss_axis_short_lines_mirror_and_nearest(gpu, dtype):
     from scipy import ndimage as ndi
     from magellanmapper_amd import _native as nat, blob_log as bl, kernels1d as k1
     rng = np.random.default_rng(23)
-    vol = _as_dtype(rng.integers(0, 65536, (12, 14, 140)).astype(np.uint16), dtype)
+    vol = as_dtype(rng.integers(0, 65536, (12, 14, 140)).astype(np.uint16), dtype)
     dvol = bl.DeviceVolume(vol)
     src = dvol.view(0, False)
     strides = (src.stride_z, src.stride_y, src.stride_x)
@@ -532,7 +501,7 @@ def test_gauss_axis_short_lines_mirror_and_nearest(gpu, dtype):
             out = torch.zeros(len(shapes) * slot, dtype=out_t, device=gpu)
             nat.check(nat.lib().mmx_gauss_axis_batch(ctypes.byref(src), d_blocks.data_ptr(), blocks.ctypes.data,
                                                      len(shapes), axis, d_w.data_ptr(), d_r.data_ptr(), pitch, nearest,
-                                                     slot, sy, sz, out.data_ptr(), _stream()), "mmx_gauss_axis_batch")
+                                                     slot, sy, sz, out.data_ptr(), stream_ptr()), "mmx_gauss_axis_batch")
             res = out.cpu().numpy().reshape(len(shapes), -1)
             for i, (o, s) in enumerate(zip(origins, shapes)):
                 assert s[axis] == lengths[i]
@@ -570,7 +539,7 @@ def test_minmax_extremes_at_the_last_row_and_column_of_channel_views(gpu):
         d_mm = torch.from_numpy(mm).to(gpu)
         d_blocks = bl._to_device_bytes(blocks, gpu)
         nat.check(nat.lib().mmx_minmax_batch(ctypes.byref(v), d_blocks.data_ptr(), blocks.ctypes.data, len(shapes),
-                                             d_mm.data_ptr(), _stream()), "mmx_minmax_batch")
+                                             d_mm.data_ptr(), stream_ptr()), "mmx_minmax_batch")
         got = d_mm.cpu().numpy()
         for b, (o, s) in enumerate(zip(origins, shapes)):
             sub = img[o[0]:o[0] + s[0], o[1]:o[1] + s[1], o[2]:o[2] + s[2], c]
@@ -591,11 +560,11 @@ def test_cdist_row_limit_and_chunked_rows(gpu, monkeypatch):
     b = rng.random((5, 3)) * 300
     d_a, d_b = torch.from_numpy(a).to(gpu), torch.from_numpy(b).to(gpu)
     d_out = torch.full((65536 * 5,), -1.0, dtype=torch.float64, device=gpu)
-    nat.check(L.mmx_cdist_f64(d_a.data_ptr(), 65535, d_b.data_ptr(), 5, 3, d_out.data_ptr(), _stream()), "mmx_cdist_f64")
+    nat.check(L.mmx_cdist_f64(d_a.data_ptr(), 65535, d_b.data_ptr(), 5, 3, d_out.data_ptr(), stream_ptr()), "mmx_cdist_f64")
     got = d_out.cpu().numpy().reshape(-1, 5)
     np.testing.assert_array_equal(got[:65535], distance.cdist(a[:65535], b))
     assert (got[65535] == -1.0).all()
-    assert L.mmx_cdist_f64(d_a.data_ptr(), 65536, d_b.data_ptr(), 5, 3, d_out.data_ptr(), _stream()) == 5
+    assert L.mmx_cdist_f64(d_a.data_ptr(), 65536, d_b.data_ptr(), 5, 3, d_out.data_ptr(), stream_ptr()) == 5
     torch.cuda.synchronize()
     real = L.mmx_cdist_f64
     rows = []
@@ -635,7 +604,7 @@ def _close_call(master, check, tol, dev):
     d_hit = torch.full((max(1, len(check)),), 9, dtype=torch.uint8, device=dev)
     t = np.ascontiguousarray(tol, dtype=np.int32)
     nat.check(nat.lib().mmx_close_pairs(d_m.data_ptr(), len(master), d_c.data_ptr(), len(check), nat.as_int32_ptr(t),
-                                        d_last.data_ptr(), d_hit.data_ptr(), _stream()), "mmx_close_pairs")
+                                        d_last.data_ptr(), d_hit.data_ptr(), stream_ptr()), "mmx_close_pairs")
     return d_last.cpu().numpy()[:len(master)], d_hit.cpu().numpy()
 
 

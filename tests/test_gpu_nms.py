@@ -16,13 +16,13 @@ unstored segments.  (ii) ``rounds > 1`` in ``peaks_sparse_kernel``: the grid cov
 until a batch holds more than 8192 x 2048 = 2^24 of them per block, which no test-sized batch does; that loop-carried
 path is left uncovered."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
 
 import test_nms_host as H
 from test_nms_host import DENSE, MAX_DELTA, QUADS, ROWS, SPARSE, case
+from gpu_support import cand_key, gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -34,16 +34,6 @@ _LAYOUTS = {None: "dense", ROWS: "rows", QUADS: "quads"}
 #: every (case, entry layout) of parts 1-4: the dense kernel on the dense cases, the sparse one on both layouts
 RUNS = [(n, None) for n in DENSE] + [(n, lay) for n in SPARSE for lay in (ROWS, QUADS)]
 RUN_IDS = ["%s-%s" % (n, _LAYOUTS[lay]) for n, lay in RUNS]
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a GPU: torch.cuda.is_available() is False")
-    from magellanmapper_amd import _native
-    assert os.path.exists(_native.LIB_PATH), "libmmx_hip.so must be built in-tree"
-    assert _native.lib().mmx_device_count() >= 1, "no gfx950 device visible to libmmx_hip.so"
-    return torch.device("cuda", 0)
 
 
 def _blocks(shapes, slots=None):
@@ -99,12 +89,8 @@ def _run(dev, name, layout=None, word0="same", cap=CAP):
     return r
 
 
-def _key(rows):
-    return np.stack([rows[f].astype(np.int64) for f in ("slot", "s", "z", "y", "x")], axis=1)
-
-
 def _order(rows):
-    return np.lexsort(_key(rows).T[::-1])
+    return np.lexsort(cand_key(rows).T[::-1])
 
 
 def _guard_is_intact(table, cap):
@@ -113,7 +99,7 @@ def _guard_is_intact(table, cap):
 
 def _assert_rows_equal(got, want, banded):
     """Candidate rows in the same order: place, value, nbr_max and flags bit for bit, the band, v64 still NaN."""
-    np.testing.assert_array_equal(_key(got), _key(want))
+    np.testing.assert_array_equal(cand_key(got), cand_key(want))
     np.testing.assert_array_equal(got["v"].view(np.uint32), want["v"].view(np.uint32))
     np.testing.assert_array_equal(got["nbr_max"].view(np.uint32), want["nbr_max"].view(np.uint32))
     np.testing.assert_array_equal(got["flags"], want["flags"])
@@ -149,9 +135,9 @@ def test_dense_table_overflow_keeps_counting_and_stays_inside(gpu):
     assert cap >= 50 and r.count == len(want)
     got = r.nominated[:cap]
     got = got[_order(got)]
-    assert len(np.unique(_key(got), axis=0)) == cap
-    pos = {tuple(k): i for i, k in enumerate(_key(want))}
-    idx = [pos.get(tuple(k), -1) for k in _key(got)]
+    assert len(np.unique(cand_key(got), axis=0)) == cap
+    pos = {tuple(k): i for i, k in enumerate(cand_key(want))}
+    idx = [pos.get(tuple(k), -1) for k in cand_key(got)]
     assert min(idx) >= 0
     _assert_rows_equal(got, want[idx], banded=False)
     assert _guard_is_intact(r.nominated, cap)
@@ -214,9 +200,9 @@ def test_sparse_table_overflow_keeps_counting_and_stays_inside(gpu, layout):
     assert cap >= 50 and r.count == len(want)
     got = r.nominated[:cap]
     got = got[_order(got)]
-    assert len(np.unique(_key(got), axis=0)) == cap
-    pos = {tuple(k): i for i, k in enumerate(_key(want))}
-    idx = [pos.get(tuple(k), -1) for k in _key(got)]
+    assert len(np.unique(cand_key(got), axis=0)) == cap
+    pos = {tuple(k): i for i, k in enumerate(cand_key(want))}
+    idx = [pos.get(tuple(k), -1) for k in cand_key(got)]
     assert min(idx) >= 0
     _assert_rows_equal(got, want[idx], banded=True)
     assert _guard_is_intact(r.nominated, cap)
@@ -242,7 +228,7 @@ def test_expand_probes_appends_exactly_the_reference(gpu, name, layout):
     # the index of a candidate in the device's table -> its index in the reference's (sorted) table
     rank = np.empty(r.n_cands, dtype=np.int64)
     rank[_order(r.nominated[:r.n_cands])] = np.arange(r.n_cands)
-    got = np.concatenate([_key(probes), rank[probes["band"].astype(np.int64)][:, None]], axis=1)
+    got = np.concatenate([cand_key(probes), rank[probes["band"].astype(np.int64)][:, None]], axis=1)
     np.testing.assert_array_equal(H.sort_rows(got), want_p)
     dims = np.asarray(c.shapes)[probes["slot"]]
     for f, hi in (("s", c.ns), ("z", dims[:, 0]), ("y", dims[:, 1]), ("x", dims[:, 2])):
@@ -269,7 +255,7 @@ def test_expand_probes_overflow_keeps_counting_and_stays_inside(gpu, name, layou
     assert (probes["flags"] == H.PROBE).all()
     rank = np.empty(r.n_cands, dtype=np.int64)
     rank[_order(r.nominated[:r.n_cands])] = np.arange(r.n_cands)
-    got = np.concatenate([_key(probes), rank[probes["band"].astype(np.int64)][:, None]], axis=1)
+    got = np.concatenate([cand_key(probes), rank[probes["band"].astype(np.int64)][:, None]], axis=1)
     assert len(np.unique(got, axis=0)) == len(got)
     assert {tuple(g) for g in got} <= {tuple(w) for w in want_p}
     assert _guard_is_intact(r.expanded, cap)

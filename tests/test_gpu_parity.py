@@ -13,22 +13,13 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, lexsorted, load_golden
+from gpu_support import gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
 LOG_TOL = 1e-4
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a GPU: torch.cuda.is_available() is False")
-    from magellanmapper_amd import _native
-    assert os.path.exists(_native.LIB_PATH), "libmmx_hip.so must be built in-tree"
-    assert _native.lib().mmx_device_count() >= 1, "no gfx950 device visible to libmmx_hip.so"
-    return torch.device("cuda", 0)
 
 
 @pytest.fixture(params=["native", "numpy"])
@@ -1228,85 +1219,64 @@ _TAIL_FIELDS = ("slot", "s", "z", "y", "x", "v", "flags", "band", "v64")
 
 def _tail_both_ways(bl, nat, g, exact):
     """One batch (the golden volume as one block) enqueued twice on the same ``mmx_detect_args``: piece by piece through
-    the public entries -- ``mmx_log_scales_f32``, a zeroed counter, ``mmx_peaks_batch`` on the workspace layout worked out
-    HERE, ``mmx_expand_probes``, ``mmx_rescore_f64`` -- and by ``mmx_detect_batch`` into a second table.
+    the public entries -- ``mmx_log_scales_f32``, a zeroed counter, ``mmx_peaks_batch`` on the workspace layout as
+    ``rawbatch`` states it, ``mmx_expand_probes``, ``mmx_rescore_f64`` -- and by ``mmx_detect_batch`` into a second table.
+    Buffers and ``mmx_detect_args`` come from a ``RawBatch``; the sequence of calls is this function's.
     ``exact``: the value of both ``exact`` and ``expand``.  Returns ``(words, table)`` of each form, as the device holds
     them, the cap, and what ``mmx_detect_batch`` copied to the host."""
     import ctypes
     import torch
+    from magellanmapper_amd.rawbatch import RawBatch
     L = nat.lib()
     dvol = bl.DeviceVolume(g["volume"])
-    dev = dvol.tensor.device
     lane = bl.Lane(0, float(g["min_sigma"]), float(g["max_sigma"]), int(g["num_sigma"]), float(g["threshold"]),
                    float(g["overlap"]))
     lane.bind(dvol, 1)
-    space = lane.space
     shape = tuple(int(v) for v in g["volume"].shape)
-    blocks, slot = bl._make_blocks(dvol, 0, [(0, 0, 0)], [shape])
-    d_blocks = bl._to_device_bytes(blocks, dev)
-    nb, ns = 1, len(space.sigmas)
-    vol32, vol_exact = dvol.view(0, True), dvol.view(0, False)
-    if vol32.dtype == nat.MMX_F32:          # (float voxels of ordinary magnitude, all >= 0 or not: mmx_volume.value_range)
+    value_range = None
+    if dvol.view(0, True).dtype == nat.MMX_F32:  # (float voxels of ordinary magnitude, all >= 0 or not: mmx_volume.value_range)
         lo, hi = lane.vrange
         assert max(abs(lo), abs(hi)) <= bl.FLOAT_TILED_RANGE[1]
-        vol32.value_range = max(hi, 1e-30) if lo >= 0.0 else -max(abs(lo), abs(hi))
+        value_range = max(hi, 1e-30) if lo >= 0.0 else -max(abs(lo), abs(hi))
     store_f32 = 1 if dvol.np_dtype == np.float32 else 0
-    ws = torch.empty(-(-int(L.mmx_workspace_bytes(nb, slot, ns, 1)) // 4), dtype=torch.float32, device=dev)
     n_vox = int(np.prod(shape))
+    ns = len(lane.space.sigmas)
     cap = max(4096, min(n_vox * ns, n_vox // 2000 * ns + 65536))
-    item = nat.CAND_DTYPE.itemsize
-    tables = [torch.zeros(cap * item, dtype=torch.uint8, device=dev) for _ in range(2)]
-    counts = [torch.full((2,), 12345, dtype=torch.int32, device=dev) for _ in range(2)]     # (garbage: the reset is the tail's)
-    h_count = torch.full((2,), 12345, dtype=torch.int32).pin_memory()
     n_prefix = min(cap, bl._PREFIX_ENTRIES)
-    h_cands = torch.zeros(n_prefix * item, dtype=torch.uint8).pin_memory()
-    ev_done = bl._NativeEvent()
-    stream = bl._stream_ptr()
-    a = nat.DetectArgs()
-    a.vol32, a.vol_exact = ctypes.pointer(vol32), ctypes.pointer(vol_exact)
-    a.d_blocks, a.h_blocks = d_blocks.data_ptr(), blocks.ctypes.data
-    a.n_blocks, a.n_sigma, a.slot_elems = nb, ns, slot
-    a.h_w0, a.h_w2 = space.w0_tab.ctypes.data, space.w2_tab.ctypes.data
-    a.d_w0, a.d_w2 = lane.d_w0.data_ptr(), lane.d_w2.data_ptr()
-    a.h_radius, a.h_norm = space.radii.ctypes.data, space.norms.ctypes.data
-    a.d_work, a.work_bytes = ws.data_ptr(), ws.numel() * 4
-    a.thr, a.eps = lane.threshold, lane.eps
-    a.d_cands, a.cap, a.d_count = tables[0].data_ptr(), cap, counts[0].data_ptr()
-    a.zx_mode, a.zx_flags, a.store_f32, a.exact, a.expand = bl.ZX_MODE, bl.ZX_FLAGS, store_f32, int(exact), int(exact)
-    a.stream = a.tail_stream = a.pack_stream = stream
-    info = nat.DetectInfo()
+    # (counters of garbage: the reset is the tail's)
+    b = RawBatch(dvol, [(0, 0, 0)], [shape], lane.space, lane.threshold, lane.eps, cap, value_range=value_range,
+                 store_f32=store_f32, zx_mode=bl.ZX_MODE, zx_flags=bl.ZX_FLAGS, exact=exact, expand=exact,
+                 host_entries=n_prefix, event=True, count_fill=12345, n_tables=2)
+    nb, slot, stream, d_blocks = b.nb, b.slot, b.stream, b.d_blocks.data_ptr()
+    tables, counts = [t.data_ptr() for t in b.tables], [c.data_ptr() for c in b.counts_dev]
+    a = b.args(h_count=None, h_cands=None, h_prefix=0, ev_done=None)
     # ---- piece by piece
-    nat.check(L.mmx_log_scales_f32(ctypes.byref(a), ctypes.byref(info)), "mmx_log_scales_f32")
-    # the workspace (mmx_workspace_bytes): four intermediate arrays, the LoG arrays [ns][nb * slot], then -- 16-byte
-    # aligned -- the NMS entries the Y pass wrote, in the layout the scales report
-    log_base = ws.data_ptr() + 4 * nb * slot * 4
-    mask_base = (log_base + ns * nb * slot * 4 + 15) & ~15
-    counts[0].zero_()
-    nat.check(L.mmx_peaks_batch(log_base, mask_base if info.mask_layout else None, info.mask_layout, ns,
-                                d_blocks.data_ptr(), blocks.ctypes.data, nb, slot, lane.threshold, lane.eps,
-                                tables[0].data_ptr(), cap, counts[0].data_ptr(), stream), "mmx_peaks_batch")
+    info = b.log_scales(a)
+    # (the LoG arrays and, behind them, the NMS entries the Y pass wrote in the layout the scales report)
+    b.counts_dev[0].zero_()
+    nat.check(L.mmx_peaks_batch(b.log_base, b.entries_base if info.mask_layout else None, info.mask_layout, ns,
+                                d_blocks, b.blocks.ctypes.data, nb, slot, lane.threshold, lane.eps,
+                                tables[0], cap, counts[0], stream), "mmx_peaks_batch")
     if exact:
-        nat.check(L.mmx_expand_probes(tables[0].data_ptr(), cap, counts[0].data_ptr(), counts[0].data_ptr() + 4,
-                                      d_blocks.data_ptr(), nb, ns, stream), "mmx_expand_probes")
-        nat.check(L.mmx_rescore_f64(ctypes.byref(vol_exact), d_blocks.data_ptr(), nb, tables[0].data_ptr(), cap,
-                                    counts[0].data_ptr(), lane.d_w0.data_ptr(), lane.d_w2.data_ptr(),
-                                    nat.as_int32_ptr(space.radii), nat.as_double_ptr(space.norms), ns, store_f32, stream),
-                  "mmx_rescore_f64")
+        nat.check(L.mmx_expand_probes(tables[0], cap, counts[0], counts[0] + 4, d_blocks, nb, ns, stream),
+                  "mmx_expand_probes")
+        nat.check(L.mmx_rescore_f64(ctypes.byref(b.vex), d_blocks, nb, tables[0], cap, counts[0], b.d_w0.data_ptr(),
+                                    b.d_w2.data_ptr(), nat.as_int32_ptr(b.space.radii), nat.as_double_ptr(b.space.norms),
+                                    ns, store_f32, stream), "mmx_rescore_f64")
     torch.cuda.synchronize()
     path_a, layout_a = info.zx_path, info.mask_layout
     # ---- the one call, same arguments, second table
-    a.d_cands, a.d_count = tables[1].data_ptr(), counts[1].data_ptr()
-    a.h_count = h_count.data_ptr()
+    a.d_cands, a.d_count = tables[1], counts[1]
+    a.h_count = b.h_count.data_ptr()
     if exact:
-        a.h_cands, a.h_prefix = h_cands.data_ptr(), n_prefix
-    a.ev_done = ev_done.handle
-    rc = L.mmx_detect_batch(ctypes.byref(a), ctypes.byref(info))
-    nat.check(rc, "mmx_detect_batch [%s]" % L.mmx_detect_last_error().decode())
-    ev_done.synchronize()
-    host = (h_count.numpy().view(np.uint32).copy(), h_cands.numpy().view(nat.CAND_DTYPE).copy())
+        a.h_cands, a.h_prefix = b.h_table.data_ptr(), n_prefix
+    a.ev_done = b.event.handle
+    info = b.detect(a)
+    b.event.synchronize()
+    host = (np.array(b.counts(host=True), dtype=np.uint32), b.table(host=True).copy())
     torch.cuda.synchronize()
     assert (info.zx_path, info.mask_layout) == (path_a, layout_a)
-    out = [(c.cpu().numpy().view(np.uint32), t.cpu().numpy().view(nat.CAND_DTYPE)) for c, t in zip(counts, tables)]
+    out = [(np.array(b.counts(i), dtype=np.uint32), b.table(i)) for i in range(2)]
     return out[0], out[1], cap, host
 
 
@@ -1341,9 +1311,10 @@ def _assert_same_entries(nat, got, want, n, fields):
 def test_one_native_call_per_batch_equals_the_call_by_call_form(gpu, case, monkeypatch):
     """``mmx_detect_batch`` (SURVEY.md 8b's fused A0-A4 entry: voxel copy, every scale, NMS, probes, exact re-score and
     the copies enqueued by native code) -- the form EVERY batch of the product takes -- against the tail enqueued piece
-    by piece through the public entries by this test (``_tail_both_ways``: its own statement of the workspace layout,
-    of the counter reset and of the order of the calls): the two counter words and every entry of the table equal, the
-    pinned copies equal to the device's.  Then the product against the real scikit-image: ordered peaks, pruned blobs,
+    by piece through the public entries by this test (``_tail_both_ways``: ``rawbatch``'s statement of the workspace
+    layout, its own of the counter reset and of the order of the calls): the two counter words and every entry of the
+    table equal, the pinned copies equal to the device's.  Then the product against the real scikit-image: ordered peaks,
+    pruned blobs,
     the peak values bit-equal to the float64 values of the piece-by-piece table."""
     from magellanmapper_amd import _native as nat, blob_log as bl
     g = load_golden("bloblog_%s.npz" % case)
@@ -1443,7 +1414,7 @@ def test_detect_batch_through_the_abi(gpu):
     stream = torch.cuda.current_stream().cuda_stream
 
     def args(cap_now):
-        a = nat.DetectArgs()
+        a = nat.DetectArgs()            # (filled by hand on purpose: a binding written from the header alone)
         a.vol32, a.vol_exact = ctypes.pointer(v32), ctypes.pointer(vex)
         a.d_blocks, a.h_blocks, a.n_blocks, a.n_sigma, a.slot_elems = d_blocks.data_ptr(), blocks.ctypes.data, nb, ns, slot
         a.h_w0, a.h_w2, a.d_w0, a.d_w2 = space.w0_tab.ctypes.data, space.w2_tab.ctypes.data, d_w0.data_ptr(), d_w2.data_ptr()

@@ -11,18 +11,9 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, load_golden
+from gpu_support import gpu  # noqa: F401
 
 torch = pytest.importorskip("torch")
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a GPU: torch.cuda.is_available() is False")
-    from magellanmapper_amd import _native
-    assert os.path.exists(_native.LIB_PATH), "libmmx_hip.so must be built in-tree"
-    assert _native.lib().mmx_device_count() >= 1, "no gfx950 device visible to libmmx_hip.so"
-    return torch.device("cuda", 0)
 
 
 # ---------------------------------------------------------------- 1. mmx_fold_parts alone

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from gpu_support import gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -15,15 +16,6 @@ torch = pytest.importorskip("torch")
 
 PREPROC = load_golden("preproc.npz")
 CASES = [str(n) for n in PREPROC["names"]]
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a GPU: torch.cuda.is_available() is False")
-    from magellanmapper_amd import _native
-    assert _native.lib().mmx_device_count() >= 1
-    return torch.device("cuda", 0)
 
 
 @pytest.fixture

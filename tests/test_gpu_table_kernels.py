@@ -14,25 +14,13 @@ import pytest
 
 import test_table_kernels_host as tk
 from test_oracle_golden import COLOC, coloc_roi
+from gpu_support import gpu, stream_ptr  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
 MMX_ERR_ARG, MMX_ERR_UNSUPPORTED = 1, 5
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a GPU: torch.cuda.is_available() is False")
-    from magellanmapper_amd import _native
-    assert _native.lib().mmx_device_count() >= 1
-    return torch.device("cuda", 0)
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 # ------------------------------------------------------------------------------------------ mmx_unmix_batch
@@ -64,7 +52,7 @@ def _unmix_on_device(gpu, dtype, subtract, sub_dtype=None):
     facs = np.array([f for _, f in subtract], dtype=np.float64)
     rc = nat.lib().mmx_unmix_batch(ctypes.byref(main), sub_arr, nat.as_double_ptr(facs) if len(facs) else None,
                                    len(subs), d_blocks.data_ptr(), blocks.ctypes.data, nb, slot, dst_sy, dst_sz,
-                                   out32.data_ptr(), out64.data_ptr(), _stream())
+                                   out32.data_ptr(), out64.data_ptr(), stream_ptr())
     torch.cuda.synchronize()
     return rc, out32.cpu().numpy(), out64.cpu().numpy()
 
@@ -168,7 +156,7 @@ def test_exact_cube_of_an_unmixed_float32_image(gpu, rescaled):
     d_w2 = torch.from_numpy(space.w2_tab).to(gpu)
     nat.check(nat.lib().mmx_rescore_f64(
         ctypes.byref(vol_exact), d_blocks.data_ptr(), 1, d_pts.data_ptr(), n, None, d_w0.data_ptr(), d_w2.data_ptr(),
-        nat.as_int32_ptr(space.radii), nat.as_double_ptr(space.norms), num_sigma, store_f32, _stream()), "rescore")
+        nat.as_int32_ptr(space.radii), nat.as_double_ptr(space.norms), num_sigma, store_f32, stream_ptr()), "rescore")
     got = d_pts.cpu().numpy().view(nat.CAND_DTYPE)["v64"]
     want = cube[pts["z"], pts["y"], pts["x"], pts["s"]].astype(np.float64)
     np.testing.assert_array_equal(got, want)
@@ -245,7 +233,7 @@ def test_coloc_means_and_voxels_are_bit_equal_to_numpy(gpu, dtype):
         d_vox = torch.full((n, nat.MMX_COLOC_BALL), tk.SENTINEL, dtype=torch.float64, device=gpu)
         nat.check(nat.lib().mmx_coloc_voxels(ctypes.byref(vol), d_blocks.data_ptr(), 2, d_rows.data_ptr(),
                                              d_off.data_ptr(), n, d_mean.data_ptr(), d_cnt.data_ptr(),
-                                             d_vox.data_ptr(), _stream()), "mmx_coloc_voxels")
+                                             d_vox.data_ptr(), stream_ptr()), "mmx_coloc_voxels")
         got_mean, got_cnt, got_vox = d_mean.cpu().numpy(), d_cnt.cpu().numpy(), d_vox.cpu().numpy()
         np.testing.assert_array_equal(got_cnt, want_cnt)
         np.testing.assert_array_equal(got_mean, want_mean, err_msg=f"{dtype} channel {c}")      # (NaN where NaN)
@@ -259,7 +247,7 @@ def test_coloc_means_and_voxels_are_bit_equal_to_numpy(gpu, dtype):
         # the entry point without the voxels: the same means
         d_mean2 = torch.full((n,), tk.SENTINEL, dtype=torch.float64, device=gpu)
         nat.check(nat.lib().mmx_coloc_means(ctypes.byref(vol), d_blocks.data_ptr(), 2, d_rows.data_ptr(),
-                                            d_off.data_ptr(), n, d_mean2.data_ptr(), d_cnt.data_ptr(), _stream()),
+                                            d_off.data_ptr(), n, d_mean2.data_ptr(), d_cnt.data_ptr(), stream_ptr()),
                   "mmx_coloc_means")
         np.testing.assert_array_equal(d_mean2.cpu().numpy(), want_mean)
     for row, k in tk.COLOC_KNOWN_COUNTS.items():

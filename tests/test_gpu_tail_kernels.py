@@ -12,29 +12,14 @@ import pytest
 
 import test_nms_host as H
 from test_nms_host import QUADS, ROWS
+from gpu_support import cand_key, gpu, rescore_strip, stream_ptr  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
 WG = 256                                # MMX_WG
-LDS_BUDGET = 60 * 1024                  # mmx_rescore_f64
 RESCORE_GRID = 8192                     # workgroups of one re-score launch
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import os
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a GPU: torch.cuda.is_available() is False")
-    from magellanmapper_amd import _native
-    assert os.path.exists(_native.LIB_PATH), "libmmx_hip.so must be built in-tree"
-    assert _native.lib().mmx_device_count() >= 1, "no gfx950 device visible to libmmx_hip.so"
-    return torch.device("cuda", 0)
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 # ---------------------------------------------------------------- 1. the exact re-score
@@ -54,15 +39,10 @@ RS_VARIANTS = [("u8", np.uint8, 0), ("u16", np.uint16, 0), ("f32", np.float32, 1
                ("f64", np.float64, 0)]
 
 
-def _strip(rmax):
-    n = 2 * rmax + 1
-    return min(n, (LDS_BUDGET - 32 * n - 16) // (16 * n))
-
-
 def _col_class(radius, rmax):
     """Columns per thread and pass of a point of this radius (rescore_col_class of csrc/mmx_rescore.hip), and the passes."""
     n = 2 * radius + 1
-    cols = -(-(n * min(_strip(rmax), n)) // WG)
+    cols = -(-(n * min(rescore_strip(rmax), n)) // WG)
     passes = -(-cols // 4)
     per = -(-cols // passes)
     return (1 if per <= 1 else 2 if per <= 2 else 4), passes
@@ -163,7 +143,7 @@ def test_the_rescore_table_holds_what_its_test_relies_on():
     has workgroups -- from the table alone (no GPU is used; the mark is the module's)."""
     rmax = max(RADII)
     assert [_col_class(r, rmax) for r in RADII] == [(1, 1), (2, 1), (4, 1), (4, 2), (4, 3), (4, 4)]
-    assert _strip(rmax) < 2 * rmax + 1 and _strip(24) == 49
+    assert rescore_strip(rmax) < 2 * rmax + 1 and rescore_strip(24) == 49
     rows = _rs_table()
     assert len(rows) > RESCORE_GRID
     for b, (si, _, shp) in enumerate(RS_BLOCKS):
@@ -196,7 +176,7 @@ def test_rescore_interleaved_columns_bit_exact(gpu, name):
     vol = dvol.view(0, False)
     nat.check(nat.lib().mmx_rescore_f64(
         ctypes.byref(vol), d_blocks.data_ptr(), len(blocks), d_pts.data_ptr(), len(pts), None, d_w0.data_ptr(),
-        d_w2.data_ptr(), nat.as_int32_ptr(radii), nat.as_double_ptr(norms), len(radii), store_f32, _stream()),
+        d_w2.data_ptr(), nat.as_int32_ptr(radii), nat.as_double_ptr(norms), len(radii), store_f32, stream_ptr()),
         "mmx_rescore_f64")
     got = d_pts.cpu().numpy().view(nat.CAND_DTYPE)
     want = _rs_expected(name)
@@ -230,7 +210,7 @@ def test_rescore_rows_two_gibibytes_apart(gpu):
     d_w0, d_w2 = torch.from_numpy(w0).to(gpu), torch.from_numpy(w2).to(gpu)
     nat.check(nat.lib().mmx_rescore_f64(
         ctypes.byref(vol), d_blocks.data_ptr(), 1, d_pts.data_ptr(), len(pts), None, d_w0.data_ptr(), d_w2.data_ptr(),
-        nat.as_int32_ptr(radii), nat.as_double_ptr(norms), len(radii), 0, _stream()), "mmx_rescore_f64")
+        nat.as_int32_ptr(radii), nat.as_double_ptr(norms), len(radii), 0, stream_ptr()), "mmx_rescore_f64")
     got = d_pts.cpu().numpy().view(nat.CAND_DTYPE)["v64"]
     cube = blo.log_cube(blo.img_as_float(sub), np.array([[SIGMAS[0]] * 3, [SIGMAS[1]] * 3]))
     want = cube[rows[:, 2], rows[:, 3], rows[:, 4], rows[:, 1]].astype(np.float64)
@@ -341,21 +321,17 @@ def _nms_run(dev, ns, layout, cap):
     count = torch.zeros(1, dtype=torch.int32, device=dev)
     nat.check(nat.lib().mmx_peaks_batch(log.data_ptr(), masks.data_ptr(), layout, ns, d_blocks.data_ptr(),
                                         blocks.ctypes.data, 1, slot, NMS_THR, NMS_EPS, table.data_ptr(), cap,
-                                        count.data_ptr(), _stream()), "mmx_peaks_batch")
+                                        count.data_ptr(), stream_ptr()), "mmx_peaks_batch")
     torch.cuda.synchronize()
     return int(count.item()), table.cpu().numpy().view(nat.CAND_DTYPE)
 
 
-def _key(rows):
-    return np.stack([rows[f].astype(np.int64) for f in ("slot", "s", "z", "y", "x")], axis=1)
-
-
 def _sorted(rows):
-    return rows[np.lexsort(_key(rows).T[::-1])]
+    return rows[np.lexsort(cand_key(rows).T[::-1])]
 
 
 def _assert_same_rows(got, want):
-    np.testing.assert_array_equal(_key(got), _key(want))
+    np.testing.assert_array_equal(cand_key(got), cand_key(want))
     for f in ("v", "nbr_max"):
         np.testing.assert_array_equal(got[f].view(np.uint32), want[f].view(np.uint32))
     np.testing.assert_array_equal(got["flags"], want["flags"])
@@ -384,7 +360,7 @@ def test_the_nms_cube_holds_what_its_test_relies_on(ns, layout):
     assert mask[0, slice(*FLAT[0]), slice(*FLAT[1]), slice(*FLAT[2])].all()
     kinds = H.face_kind(cube.shape)[mask]
     assert set(range(16)) <= set(kinds.tolist()) if ns >= 3 else set(kinds.tolist()) >= {1, 3, 5, 7, 9, 11, 13, 15}
-    row = {tuple(k[1:]): i for i, k in enumerate(_key(table))}
+    row = {tuple(k[1:]): i for i, k in enumerate(cand_key(table))}
     assert sites["beaten_by_last"] not in row and sites["beaten_by_first"] not in row
     first, last = _site_offsets(ns)
     where = {tuple(o): j for j, o in enumerate(H.OFFSETS)}
@@ -423,9 +399,9 @@ def test_sparse_kernel_counts_past_a_table_that_is_too_small(gpu, layout):
     count, table = _nms_run(gpu, ns, layout, cap)
     assert count == len(want)
     got = _sorted(table[:cap])
-    assert len(np.unique(_key(got), axis=0)) == cap
-    pos = {tuple(k): i for i, k in enumerate(_key(want))}
-    idx = [pos.get(tuple(k), -1) for k in _key(got)]
+    assert len(np.unique(cand_key(got), axis=0)) == cap
+    pos = {tuple(k): i for i, k in enumerate(cand_key(want))}
+    idx = [pos.get(tuple(k), -1) for k in cand_key(got)]
     assert min(idx) >= 0
     _assert_same_rows(got, want[idx])
     assert (table[cap:].view(np.uint8) == 0xA5).all()

@@ -3,12 +3,11 @@ kernel) and of the batch plan that gives a ragged stack's thin remainders batche
 the generic passes and the float64 oracle, the mode by name on thick blocks, the golden image of 5 planes through
 ``blob_log``, and a ragged stack end to end -- the tables of the split plan against the oracle and against the unsplit
 plan, raw, streamed, preprocessed, with two co-localised channels and pruned ahead.  Needs a real MI355X (``-m gpu``)."""
-import os
-
 import numpy as np
 import pytest
 
 from conftest import load_golden
+from gpu_support import as_dtype, gpu, timed_cubes  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -20,24 +19,6 @@ LOG_TOL = 1e-4
 F32_TOL, CUBE_TOL = 5e-6, LOG_TOL * 1e-2
 FAMILIES = ("zpass", "ypass", "xpass", "generic", "zxpass", "y2pass", "zxpack", "widepass", "thinpass")
 DTYPES = [np.uint8, np.uint16, np.float32]
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a GPU: torch.cuda.is_available() is False")
-    from magellanmapper_amd import _native
-    assert os.path.exists(_native.LIB_PATH), "libmmx_hip.so must be built in-tree"
-    assert _native.lib().mmx_device_count() >= 1, "no gfx950 device visible to libmmx_hip.so"
-    return torch.device("cuda", 0)
-
-
-def _as_dtype(vol16, dtype):
-    if dtype == np.uint16:
-        return vol16
-    if dtype == np.uint8:
-        return (vol16 >> 8).astype(np.uint8)
-    return (vol16 / 65535.0).astype(dtype)
 
 
 def _thin_blocks(R):
@@ -71,7 +52,7 @@ def _reference(name, dtype, R, origins, shapes):
     from oracle import blob_log_oracle as blo
     key = (name, np.dtype(dtype).name, R)
     if key not in _REFERENCE:
-        vol = _as_dtype(_volume(name), dtype)
+        vol = as_dtype(_volume(name), dtype)
         sigma = (R + 0.2) / 4.0
         _REFERENCE[key] = [blo.log_cube(blo.img_as_float(vol[o[0]:o[0] + s[0], o[1]:o[1] + s[1], o[2]:o[2] + s[2]]),
                                         np.array([[sigma] * 3]))[..., 0] for o, s in zip(origins, shapes)]
@@ -79,18 +60,8 @@ def _reference(name, dtype, R, origins, shapes):
 
 
 def _families(kinds):
-    return {k: int(kinds[k][1]) for k in FAMILIES if kinds[k][1]}
-
-
-def _timed_cubes(bl, nat, dvol, origins, shapes, space):
-    nat.timing_enable(True)
-    try:
-        nat.timing_read()
-        cubes = bl.log_cube_blocks(dvol, 0, origins, shapes, space)
-        kinds = nat.timing_read()
-    finally:
-        nat.timing_enable(False)
-    return cubes, kinds
+    from magellanmapper_amd.rawbatch import families
+    return families(kinds, FAMILIES)
 
 
 def _ring_passes(shapes, R):
@@ -103,14 +74,14 @@ def _ring_passes(shapes, R):
 
 
 def _check_cubes(bl, nat, monkeypatch, name, dtype, R, origins, shapes, tol):
-    vol = _as_dtype(_volume(name), dtype)
+    vol = as_dtype(_volume(name), dtype)
     dvol = bl.DeviceVolume(vol)
     sigma = (R + 0.2) / 4.0
     space = bl.ScaleSpace.make(sigma, sigma, 1)
     assert space.radii[0] == R
     want = _reference(name, dtype, R, origins, shapes)
     monkeypatch.setattr(bl, "ZX_MODE", nat.MMX_ZX_THIN)
-    got, kinds = _timed_cubes(bl, nat, dvol, origins, shapes, space)
+    got, kinds = timed_cubes(dvol, origins, shapes, space)
     fams = _families(kinds)
     print("R %d %s families %s" % (R, np.dtype(dtype).name, fams))
     assert bl.LAST_ZX_PATH == nat.MMX_ZX_THIN
@@ -171,7 +142,7 @@ def test_thin_by_name_on_thick_blocks_is_auto(gpu, monkeypatch):
     seen = {}
     for mode in (nat.MMX_ZX_AUTO, nat.MMX_ZX_THIN):
         monkeypatch.setattr(bl, "ZX_MODE", mode)
-        cubes, kinds = _timed_cubes(bl, nat, dvol, origins, shapes, space)
+        cubes, kinds = timed_cubes(dvol, origins, shapes, space)
         seen[mode] = (bl.LAST_ZX_PATH, _families(kinds), cubes[0])
     print(seen[nat.MMX_ZX_THIN][:2])
     assert seen[nat.MMX_ZX_THIN][0] == seen[nat.MMX_ZX_AUTO][0] != nat.MMX_ZX_THIN

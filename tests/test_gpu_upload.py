@@ -3,16 +3,11 @@ callers hand a memory-mapped ``image5d.npy``, magmap/io/importer.py:794, magmap/
 import numpy as np
 import pytest
 
+from gpu_support import gpu  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a GPU: torch.cuda.is_available() is False")
-    return torch.device("cuda", 0)
 
 
 def _stack(vol, denoise):

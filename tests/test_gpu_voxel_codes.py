@@ -87,7 +87,7 @@ def _detect_args(c):
     w0, w2 = np.zeros(TAB), np.zeros(TAB)
     w0[:2], w2[:2] = (0.5, 0.25), (-0.5, 0.25)
     radius, norm = np.array([1], dtype=np.int32), np.array([1.0])
-    a = nat.DetectArgs()
+    a = nat.DetectArgs()                # (filled by hand on purpose: every output is a sentinel-tracked buffer of `c`)
     c.keep.append(c.vol)
     a.vol32 = a.vol_exact = ctypes.pointer(c.vol)
     a.d_blocks, a.h_blocks, a.n_blocks, a.n_sigma, a.slot_elems = c.d_blocks, c.h_blocks, 1, 1, SLOT

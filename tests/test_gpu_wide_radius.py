@@ -3,10 +3,10 @@ extent is at least the radius -- the cube at the edges of that geometry, the fal
 by name at small radii, the row entries of the Y pass, the one-round ladder rule of ``mmx_log_scales_f32`` and the tables
 of ``blob_log`` / ``detect_blobs_blocks`` at a fine resolution.  Float64 references come from ``oracle/`` and are computed
 once per input.  Needs a real MI355X (``-m gpu``)."""
-import ctypes
-
 import numpy as np
 import pytest
+
+from gpu_support import as_dtype, gpu, ladder_run, timed_cubes  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -15,26 +15,6 @@ torch = pytest.importorskip("torch")
 LOG_TOL = 1e-4
 #: the bound the large-radius test of test_gpu_kernel_edges.py holds the generic float32 passes to
 CUBE_TOL = LOG_TOL * 1e-2
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import os
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a GPU: torch.cuda.is_available() is False")
-    from magellanmapper_amd import _native
-    assert os.path.exists(_native.LIB_PATH), "libmmx_hip.so must be built in-tree"
-    assert _native.lib().mmx_device_count() >= 1, "no gfx950 device visible to libmmx_hip.so"
-    return torch.device("cuda", 0)
-
-
-def _as_dtype(vol16, dtype):
-    """One uint16 volume in each of the four voxel types the ABI takes (as in test_gpu_kernel_edges.py)."""
-    if dtype == np.uint16:
-        return vol16
-    if dtype == np.uint8:
-        return (vol16 >> 8).astype(np.uint8)
-    return (vol16 / 65535.0).astype(dtype)
 
 
 DTYPES = [np.uint8, np.uint16, np.float32, np.float64]
@@ -82,17 +62,6 @@ def _reference(vol, kind, R, origins, shapes, tag=""):
     return _REFERENCE[key]
 
 
-def _timed_cubes(bl, nat, dvol, origins, shapes, space, generic=False):
-    nat.timing_enable(True)
-    try:
-        nat.timing_read()
-        cubes = bl.log_cube_blocks(dvol, 0, origins, shapes, space, generic=generic)
-        kinds = nat.timing_read()
-    finally:
-        nat.timing_enable(False)
-    return cubes, kinds
-
-
 def _kind_of(dtype):
     return "u16" if dtype in (np.uint16, np.float64) else np.dtype(dtype).name
 
@@ -105,7 +74,7 @@ def test_cube_at_the_edges_of_the_wide_geometry(gpu, edge_volume, dtype, R):
     non-zero origin: three wide passes, no generic one, the cube within the generic float32 passes' bound of the float64
     oracle and within the float32 paths' agreement of the generic passes."""
     from magellanmapper_amd import _native as nat, blob_log as bl
-    vol = _as_dtype(edge_volume, dtype)
+    vol = as_dtype(edge_volume, dtype)
     origins, shapes = _edge_blocks(R)
     for a in range(3):
         assert shapes[a][a] == R and all(s[i] % 2 == 1 for i, s in enumerate([shapes[a]] * 3) if i != a)
@@ -115,7 +84,7 @@ def test_cube_at_the_edges_of_the_wide_geometry(gpu, edge_volume, dtype, R):
     space = bl.ScaleSpace.make(sigma, sigma, 1)
     assert space.radii[0] == R
     want = _reference(vol, _kind_of(dtype), R, origins, shapes)
-    got, kinds = _timed_cubes(bl, nat, dvol, origins, shapes, space)
+    got, kinds = timed_cubes(dvol, origins, shapes, space)
     assert kinds["widepass"][1] == 3 and kinds["generic"][1] == 0, kinds
     assert all(kinds[k][1] == 0 for k in ("zpass", "ypass", "xpass", "zxpass", "y2pass", "zxpack"))
     assert bl.LAST_ZX_PATH == nat.MMX_ZX_WIDE
@@ -140,7 +109,7 @@ def test_one_voxel_short_of_the_radius_takes_the_generic_passes(gpu, edge_volume
     sigma = (R + 0.2) / 4.0
     space = bl.ScaleSpace.make(sigma, sigma, 1)
     want = _reference(edge_volume, "u16", R, origins, shapes, tag="short%d" % axis)
-    got, kinds = _timed_cubes(bl, nat, dvol, origins, shapes, space)
+    got, kinds = timed_cubes(dvol, origins, shapes, space)
     assert kinds["generic"][1] == 3 and kinds["widepass"][1] == 0, kinds
     assert bl.LAST_ZX_PATH == nat.MMX_ZX_SEPARATE
     for shp, g, ref in zip(shapes, got, want):
@@ -163,7 +132,7 @@ def test_wide_passes_by_name_at_small_radii(gpu, monkeypatch, R, shape):
     space = bl.ScaleSpace.make(sigma, sigma, 1)
     assert space.radii[0] == R
     monkeypatch.setattr(bl, "ZX_MODE", nat.MMX_ZX_WIDE)
-    wide, kinds = _timed_cubes(bl, nat, dvol, origins, shapes, space)
+    wide, kinds = timed_cubes(dvol, origins, shapes, space)
     path = bl.LAST_ZX_PATH
     monkeypatch.setattr(bl, "ZX_MODE", nat.MMX_ZX_SEPARATE)
     sep = bl.log_cube_blocks(dvol, 0, origins, shapes, space)
@@ -212,33 +181,23 @@ def test_row_entries_and_unwritten_segments_of_the_wide_y_pass(gpu):
     ``cube > nms_lo`` (voxels within the float32 bound of the threshold aside), every local maximum of the oracle above
     the threshold has its word-0 bit, written segments hold the values and the others still hold NaN."""
     from scipy import ndimage
-    from magellanmapper_amd import _native as nat, blob_log as bl
+    from magellanmapper_amd import _native as nat
+    from magellanmapper_amd.rawbatch import RawBatch
     vol, cube, lo = _entry_case()
     nz, ny, nx = ENTRY_SHAPE
-    L = nat.lib()
-    dvol = bl.DeviceVolume(vol)
-    dev = dvol.tensor.device
     sigma = (ENTRY_R + 0.2) / 4.0
-    space = bl.ScaleSpace.make(sigma, sigma, 1)
-    assert space.radii[0] == ENTRY_R
-    blocks, slot = bl._make_blocks(dvol, 0, [(0, 0, 0)], [ENTRY_SHAPE])
-    px = int(blocks["px"][0])
-    d_blocks = bl._to_device_bytes(blocks, dev)
-    ws = torch.empty(-(-int(L.mmx_workspace_bytes(1, slot, 1, 1)) // 4), dtype=torch.float32, device=dev)
-    d_log = ws[4 * slot:5 * slot]
-    d_log.fill_(float("nan"))
-    mask_base = (ws.data_ptr() + 5 * slot * 4 + 15) & ~15
-    n_entries = slot >> 5
-    v32 = dvol.view(0, True)
-    written, path = ctypes.c_int(-1), ctypes.c_int(-1)
     eps = 2e-5
-    nat.check(L.mmx_log_batch_f32(ctypes.byref(v32), d_blocks.data_ptr(), blocks.ctypes.data, 1, slot,
-                                  nat.as_double_ptr(space.w0[0]), nat.as_double_ptr(space.w2[0]), ENTRY_R,
-                                  float(space.norms[0]), d_log.data_ptr(), ws.data_ptr(), mask_base, lo, eps,
-                                  ctypes.byref(written), nat.MMX_ZX_WIDE, ctypes.byref(path),
-                                  torch.cuda.current_stream().cuda_stream), "mmx_log_batch_f32")
+    b = RawBatch(vol, [(0, 0, 0)], [ENTRY_SHAPE], (sigma, sigma, 1), lo, eps, 0)
+    assert b.space.radii[0] == ENTRY_R
+    px, slot, ws = int(b.blocks["px"][0]), b.slot, b.ws
+    off = (b.log_base - ws.data_ptr()) // 4
+    d_log = ws[off:off + slot]
+    d_log.fill_(float("nan"))
+    mask_base = b.entries_base
+    n_entries = slot >> 5
+    path, written = b.log_batch(0, nat.MMX_ZX_WIDE, lo, eps, entries=True)
     torch.cuda.synchronize()
-    assert written.value == nat.MMX_MASK_ROWS and path.value == nat.MMX_ZX_WIDE
+    assert written == nat.MMX_MASK_ROWS and path == nat.MMX_ZX_WIDE
     off = (mask_base - ws.data_ptr()) // 4
     words = ws[off:off + n_entries * 4].cpu().numpy().view(np.uint64).reshape(-1, 2)
     log = d_log.cpu().numpy()[:nz * ny * px].reshape(nz, ny, px)
@@ -273,73 +232,6 @@ def test_row_entries_and_unwritten_segments_of_the_wide_y_pass(gpu):
 
 
 # ---------------------------------------------------------------- 5. the ladder rule
-def _candidates(table, n):
-    t = table[:n]
-    t = t[(t["flags"] & 4) == 0]                             # MMX_CAND_PROBE
-    order = np.lexsort(tuple(t[k] for k in ("x", "y", "z", "s", "slot")))
-    return t[order]
-
-
-def _ladder_run(bl, nat, vol, origin, shape, lo_sigma, hi_sigma, ns, entries_off_modes=None):
-    """One block through ``mmx_log_scales_f32`` (the report) and ``mmx_detect_batch`` (the table); with
-    ``entries_off_modes`` instead every scale by ``mmx_log_batch_f32`` in the given mode WITHOUT entries, then the dense
-    NMS, the probes and the re-score: the same float32 cube, nominated from every voxel."""
-    L = nat.lib()
-    dvol = bl.DeviceVolume(vol)
-    dev = dvol.tensor.device
-    lane = bl.Lane(0, lo_sigma, hi_sigma, ns, 0.05, 0.5)
-    lane.bind(dvol, 1)
-    space = lane.space
-    blocks, slot = bl._make_blocks(dvol, 0, [origin], [shape])
-    d_blocks = bl._to_device_bytes(blocks, dev)
-    v32, vex = dvol.view(0, True), dvol.view(0, False)
-    ws = torch.empty(-(-int(L.mmx_workspace_bytes(1, slot, ns, 1)) // 4), dtype=torch.float32, device=dev)
-    cap = 65536
-    item = nat.CAND_DTYPE.itemsize
-    table = torch.zeros(cap * item, dtype=torch.uint8, device=dev)
-    count = torch.zeros(2, dtype=torch.int32, device=dev)
-    stream = torch.cuda.current_stream().cuda_stream
-    a = nat.DetectArgs()
-    a.vol32, a.vol_exact = ctypes.pointer(v32), ctypes.pointer(vex)
-    a.d_blocks, a.h_blocks, a.n_blocks, a.n_sigma, a.slot_elems = d_blocks.data_ptr(), blocks.ctypes.data, 1, ns, slot
-    a.h_w0, a.h_w2 = space.w0_tab.ctypes.data, space.w2_tab.ctypes.data
-    a.d_w0, a.d_w2 = lane.d_w0.data_ptr(), lane.d_w2.data_ptr()
-    a.h_radius, a.h_norm = space.radii.ctypes.data, space.norms.ctypes.data
-    a.d_work, a.work_bytes, a.thr, a.eps = ws.data_ptr(), ws.numel() * 4, lane.threshold, lane.eps
-    a.d_cands, a.cap, a.d_count = table.data_ptr(), cap, count.data_ptr()
-    a.zx_mode, a.zx_flags, a.store_f32, a.exact, a.expand = nat.MMX_ZX_AUTO, 0, 0, 1, 1
-    a.stream = a.tail_stream = a.pack_stream = stream
-    info = nat.DetectInfo()
-    if entries_off_modes is None:
-        half = nat.DetectInfo()
-        nat.check(L.mmx_log_scales_f32(ctypes.byref(a), ctypes.byref(half)), "mmx_log_scales_f32")
-        nat.check(L.mmx_detect_batch(ctypes.byref(a), ctypes.byref(info)), "mmx_detect_batch")
-        torch.cuda.synchronize()
-        assert (half.zx_path, half.mask_layout, half.n_pass_rounds) == (info.zx_path, info.mask_layout, info.n_pass_rounds)
-    else:
-        log_base = ws.data_ptr() + 4 * slot * 4
-        for s in range(ns):
-            path = ctypes.c_int(-1)
-            nat.check(L.mmx_log_batch_f32(ctypes.byref(v32), d_blocks.data_ptr(), blocks.ctypes.data, 1, slot,
-                                          nat.as_double_ptr(space.w0[s]), nat.as_double_ptr(space.w2[s]),
-                                          int(space.radii[s]), float(space.norms[s]), log_base + s * slot * 4,
-                                          ws.data_ptr(), None, 0.0, 0.0, None, entries_off_modes[s], ctypes.byref(path),
-                                          stream), "mmx_log_batch_f32")
-            assert path.value == entries_off_modes[s]
-        nat.check(L.mmx_peaks_batch(log_base, None, 0, ns, d_blocks.data_ptr(), blocks.ctypes.data, 1, slot,
-                                    lane.threshold, lane.eps, table.data_ptr(), cap, count.data_ptr(), stream),
-                  "mmx_peaks_batch")
-        nat.check(L.mmx_expand_probes(table.data_ptr(), cap, count.data_ptr(), count.data_ptr() + 4,
-                                      d_blocks.data_ptr(), 1, ns, stream), "mmx_expand_probes")
-        nat.check(L.mmx_rescore_f64(ctypes.byref(vex), d_blocks.data_ptr(), 1, table.data_ptr(), cap, count.data_ptr(),
-                                    lane.d_w0.data_ptr(), lane.d_w2.data_ptr(), nat.as_int32_ptr(space.radii),
-                                    nat.as_double_ptr(space.norms), ns, 0, stream), "mmx_rescore_f64")
-        torch.cuda.synchronize()
-    n_all = int(count.cpu().numpy().view(np.uint32)[0])
-    assert 0 < n_all <= cap
-    return info, _candidates(table.cpu().numpy().view(nat.CAND_DTYPE), n_all), [int(r) for r in space.radii]
-
-
 @pytest.fixture(scope="module")
 def ladder_volume():
     from magellanmapper_amd import synth
@@ -351,24 +243,19 @@ def test_a_ladder_with_wide_radii_is_one_round_with_row_entries(gpu, ladder_volu
     """Radii {24, 25, 26} on a uint16 block of 40 x 48 x 64: laid out before the first launch -- one round, row entries,
     the last scale wide -- and the re-scored candidates are those nominated from the full cube of the same kernels.
     On rows 530 wide the radius-24 scale goes wide too."""
-    from magellanmapper_amd import _native as nat, blob_log as bl
+    from magellanmapper_amd import _native as nat
+    from magellanmapper_amd.rawbatch import timed
     origin, shape = (0, 0, 5), (40, 48, width)
-    info, cands, radii = _ladder_run(bl, nat, ladder_volume, origin, shape, 6.05, 6.55, 3)
-    assert radii == [24, 25, 26]
+    info, cands, space = ladder_run(ladder_volume, origin, shape, 6.05, 6.55, 3)
+    assert [int(r) for r in space.radii] == [24, 25, 26]
     assert (info.n_pass_rounds, info.mask_layout, info.zx_path) == (1, nat.MMX_MASK_ROWS, nat.MMX_ZX_WIDE)
     modes = [nat.MMX_ZX_PACKED if width <= 320 else nat.MMX_ZX_WIDE, nat.MMX_ZX_WIDE, nat.MMX_ZX_WIDE]
-    _, dense, _ = _ladder_run(bl, nat, ladder_volume, origin, shape, 6.05, 6.55, 3, entries_off_modes=modes)
+    _, dense, _ = ladder_run(ladder_volume, origin, shape, 6.05, 6.55, 3, by_name=modes)
     assert len(dense) > 0 and len(cands) == len(dense)
     for f in ("slot", "s", "z", "y", "x", "v", "v64"):
         np.testing.assert_array_equal(cands[f], dense[f], err_msg=f)
     # the kinds that ran: three wide passes per wide scale, the packed Z+X and Y kernels for the other
-    nat.timing_enable(True)
-    try:
-        nat.timing_read()
-        _ladder_run(bl, nat, ladder_volume, origin, shape, 6.05, 6.55, 3)
-        kinds = nat.timing_read()
-    finally:
-        nat.timing_enable(False)
+    _, kinds = timed(lambda: ladder_run(ladder_volume, origin, shape, 6.05, 6.55, 3))
     n_wide = modes.count(nat.MMX_ZX_WIDE)
     # (mmx_log_scales_f32 and mmx_detect_batch each ran the ladder once)
     assert kinds["widepass"][1] == 2 * 3 * n_wide and kinds["generic"][1] == 0, kinds
@@ -377,9 +264,9 @@ def test_a_ladder_with_wide_radii_is_one_round_with_row_entries(gpu, ladder_volu
 
 def test_a_ladder_without_wide_radii_runs_what_it_ran(gpu, ladder_volume):
     """Radii {20, 24} only: the report is the one of the register-resident paths -- 16-bit tiles, quads, one round."""
-    from magellanmapper_amd import _native as nat, blob_log as bl
-    info, cands, radii = _ladder_run(bl, nat, ladder_volume, (0, 0, 5), (40, 48, 64), 5.0, 6.0, 2)
-    assert radii == [20, 24]
+    from magellanmapper_amd import _native as nat
+    info, cands, space = ladder_run(ladder_volume, (0, 0, 5), (40, 48, 64), 5.0, 6.0, 2)
+    assert [int(r) for r in space.radii] == [20, 24]
     assert (info.n_pass_rounds, info.mask_layout, info.zx_path) == (1, nat.MMX_MASK_QUADS, nat.MMX_ZX_TILED_Q16)
     assert len(cands) > 0
 

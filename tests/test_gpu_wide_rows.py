@@ -13,12 +13,10 @@ batch gets the larger of that slot and the one its plan needs (``_tiled_slot``: 
 ``mmx_zx6_plan_make``), which is what puts these widths on the tiled kernels at all; through ``blob_log_blocks`` the path
 of each case is the one that arithmetic predicts (the 513 voxels wide block of 26 planes is there for the tiled path to
 meet an odd number of column tiles through ``blob_log_blocks`` as well)."""
-import ctypes
-import os
-
 import numpy as np
 import pytest
 
+from gpu_support import gpu  # noqa: F401
 from test_wide_rows_host import (CASES, OVERLAP, SIGMAS, STACK_BLOCKS, STACK_SEGMENT, STACK_SIGMAS, THRESHOLD, block_image,
                                  oracle_peaks, stack_volume, volume)
 
@@ -33,16 +31,6 @@ FAMILIES = ("zpass", "ypass", "xpass", "generic", "zxpass", "y2pass", "zxpack", 
 #: column tiles per wave on an odd (513 -> 33) and an even (530 -> 34) number of column tiles
 RADII = (8, 12, 16, 17, 24)
 KINDS = ("u8", "u16", "f32")
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a GPU: torch.cuda.is_available() is False")
-    from magellanmapper_amd import _native
-    assert os.path.exists(_native.LIB_PATH), "libmmx_hip.so must be built in-tree"
-    assert _native.lib().mmx_device_count() >= 1, "no gfx950 device visible to libmmx_hip.so"
-    return torch.device("cuda", 0)
 
 
 def _voxels(vol16, kind):
@@ -101,91 +89,45 @@ def _reference(name, i, kind, R):
 class _Batch:
     """One batch of a case on the device, driven through the ABI with a slot of this test's choosing."""
 
-    def __init__(self, bl, nat, name, kind):
-        self.bl, self.nat, self.L = bl, nat, nat.lib()
-        self.dvol = bl.DeviceVolume(_voxels(volume(name), kind))
-        self.dev = self.dvol.tensor.device
-        self.origins = [o for o, _ in CASES[name][2]]
-        self.shapes = [s for _, s in CASES[name][2]]
-        self.blocks, slot = bl._make_blocks(self.dvol, 0, self.origins, self.shapes)
-        assert slot == _blob_log_slot(self.shapes)
-        self.slot = _tiled_slot(self.shapes, 2 if kind == "f32" else 1)
-        self.nb = len(self.blocks)
-        self.d_blocks = bl._to_device_bytes(self.blocks, self.dev)
-        self.v32, self.vex = self.dvol.view(0, True), self.dvol.view(0, False)
-        if kind == "f32":
-            self.v32.value_range = 1.0
-        self.ws = torch.empty(-(-int(self.L.mmx_workspace_bytes(self.nb, self.slot, 1, 1)) // 4), dtype=torch.float32,
-                              device=self.dev)
-        self.stream = torch.cuda.current_stream().cuda_stream
+    def __init__(self, bl, name, kind):
+        from magellanmapper_amd.rawbatch import RawBatch
+        self.bl = bl
+        shapes = [s for _, s in CASES[name][2]]
+        self.raw = RawBatch(_voxels(volume(name), kind), [o for o, _ in CASES[name][2]], shapes, self.space(RADII[0]), 0.0,
+                            0.0, 0, slot=_tiled_slot(shapes, 2 if kind == "f32" else 1),
+                            value_range=1.0 if kind == "f32" else None, exact=0, expand=0)
+        assert self.raw.blocks_slot == _blob_log_slot(shapes)
+        self.shapes = shapes
 
-    def cubes(self, flat):
-        out = []
-        for i, s in enumerate(self.shapes):
-            px = int(self.blocks["px"][i])
-            out.append(flat[i * self.slot:i * self.slot + s[0] * s[1] * px].reshape(s[0], s[1], px))
-        return out
+    def space(self, R):
+        sigma = (R + 0.2) / 4.0
+        space = self.bl.ScaleSpace.make(sigma, sigma, 1)
+        assert space.radii[0] == R
+        return space
 
     def ladder_of_one(self, R, thr, eps):
         """``mmx_log_scales_f32`` of the one scale under MMX_ZX_AUTO (entries wanted) on a NaN-filled workspace: the
         report, the kernel families, the LoG arrays and, per block, which voxels the entries say were written."""
-        bl, nat, L = self.bl, self.nat, self.L
-        sigma = (R + 0.2) / 4.0
-        space = bl.ScaleSpace.make(sigma, sigma, 1)
-        assert space.radii[0] == R
-        d_w0, d_w2 = space.device_tables(self.dev)
-        a = nat.DetectArgs()
-        a.vol32, a.vol_exact = ctypes.pointer(self.v32), ctypes.pointer(self.vex)
-        a.d_blocks, a.h_blocks, a.n_blocks, a.n_sigma, a.slot_elems = (self.d_blocks.data_ptr(), self.blocks.ctypes.data,
-                                                                      self.nb, 1, self.slot)
-        a.h_w0, a.h_w2, a.d_w0, a.d_w2 = space.w0_tab.ctypes.data, space.w2_tab.ctypes.data, d_w0.data_ptr(), d_w2.data_ptr()
-        a.h_radius, a.h_norm = space.radii.ctypes.data, space.norms.ctypes.data
-        a.d_work, a.work_bytes, a.thr, a.eps = self.ws.data_ptr(), self.ws.numel() * 4, thr, eps
-        a.zx_mode, a.zx_flags, a.store_f32, a.exact, a.expand = nat.MMX_ZX_AUTO, 0, 0, 0, 0
-        a.stream = a.tail_stream = a.pack_stream = self.stream
-        info = nat.DetectInfo()
-        self.ws.fill_(float("nan"))
-        nat.timing_enable(True)
-        try:
-            nat.timing_read()
-            nat.check(L.mmx_log_scales_f32(ctypes.byref(a), ctypes.byref(info)), "mmx_log_scales_f32")
-            kinds = nat.timing_read()
-        finally:
-            nat.timing_enable(False)
+        from magellanmapper_amd import _native as nat
+        from magellanmapper_amd.rawbatch import families, timed
+        b = self.raw
+        b.set_scales(self.space(R))
+        a = b.args(thr=thr, eps=eps, d_cands=None, d_count=None)     # (no table, no counters: this entry has no tail)
+        b.ws.fill_(float("nan"))
+        info, kinds = timed(lambda: b.log_scales(a))
         torch.cuda.synchronize()
-        n = self.nb * self.slot
-        logs = self.cubes(self.ws[4 * n:5 * n].cpu().numpy())
-        written = None
-        if info.mask_layout == nat.MMX_MASK_QUADS:
-            # entries: 16 bytes each (word 0: candidates, word 1: above the threshold), 16-byte aligned behind the LoG
-            # arrays; block b's start (b slot_elems) >> 5 entries in; entry y nwords + (z >> 2) ntx + (x >> 4) holds 4
-            # planes x 16 columns of row y, and the Y pass writes those 64 values when any of them is above
-            off = ((self.ws.data_ptr() + 5 * n * 4 + 15) & ~15) - self.ws.data_ptr()
-            assert off % 4 == 0
-            words = self.ws[off // 4:off // 4 + (n >> 5) * 4].cpu().numpy().view(np.uint64).reshape(-1, 2)
-            written = []
-            for i, (nz, ny, nx) in enumerate(self.shapes):
-                ntx, nzq = -(-nx // 16), -(-nz // 4)
-                ent = words[(i * self.slot) >> 5:][:ny * nzq * ntx].reshape(ny, nzq, ntx, 2)
-                on = ent[..., 1] != 0                                            # [y][z quad][column tile]
-                vox = np.repeat(np.repeat(on, 4, axis=1), 16, axis=2)[:, :nz, :nx]
-                written.append(np.moveaxis(vox, 0, 1))                           # [z][y][x]
-        return info, {k: int(kinds[k][1]) for k in FAMILIES if kinds[k][1]}, logs, written, space
+        logs = b.cubes(b.log_arrays()[0])
+        written = b.quads_written() if info.mask_layout == nat.MMX_MASK_QUADS else None
+        return info, families(kinds, FAMILIES), logs, written, b.space
 
     def by_name(self, R, mode):
         """``mmx_log_batch_f32`` in ``mode`` without entries: the whole cube."""
-        bl, nat, L = self.bl, self.nat, self.L
-        sigma = (R + 0.2) / 4.0
-        space = bl.ScaleSpace.make(sigma, sigma, 1)
-        n = self.nb * self.slot
-        self.ws.fill_(float("nan"))
-        path = ctypes.c_int(-1)
-        nat.check(L.mmx_log_batch_f32(ctypes.byref(self.v32), self.d_blocks.data_ptr(), self.blocks.ctypes.data, self.nb,
-                                      self.slot, nat.as_double_ptr(space.w0[0]), nat.as_double_ptr(space.w2[0]), R,
-                                      float(space.norms[0]), self.ws.data_ptr() + 4 * n * 4, self.ws.data_ptr(), None, 0.0,
-                                      0.0, None, mode, ctypes.byref(path), self.stream), "mmx_log_batch_f32")
+        b = self.raw
+        b.set_scales(self.space(R))
+        b.ws.fill_(float("nan"))
+        path = b.log_batch(0, mode)
         torch.cuda.synchronize()
-        return path.value, self.cubes(self.ws[4 * n:5 * n].cpu().numpy())
+        return path, b.cubes(b.log_arrays()[0])
 
 
 # ---------------------------------------------------------------- 1. the cube
@@ -198,7 +140,7 @@ def test_cube_on_rows_wider_than_one_panel(gpu, name, kind):
     and nothing above the threshold left unwritten.  MMX_ZX_TILED by name: the whole cube within the float32 tiles'
     tolerance."""
     from magellanmapper_amd import _native as nat, blob_log as bl
-    b = _Batch(bl, nat, name, kind)
+    b = _Batch(bl, name, kind)
     eps = bl.EPS_REL_Q16
     both_kinds = False              # at the detection threshold, some radius leaves written and unwritten segments
     for R in _radii_of(min(b.shapes)):

@@ -6,16 +6,11 @@ import threading
 import numpy as np
 import pytest
 
+from gpu_support import gpu  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a GPU: torch.cuda.is_available() is False")
-    return torch.device("cuda", 0)
 
 
 def _two_channels(c0, seed, n_blobs):

@@ -11,10 +11,11 @@ the same kernels (the copy widens uint8): the pair kernel at radius 9..16, the s
 run the one-tile kernels, which keep the global-table form.
 """
 import ctypes
-import os
 
 import numpy as np
 import pytest
+
+from gpu_support import gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -26,15 +27,6 @@ NX = 40
 NY_MAX = 24 + 4
 FLOAT_RANGE = 2.0
 PATTERN = 0x5A5AC3C3
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a GPU: torch.cuda.is_available() is False")
-    from magellanmapper_amd import _native
-    assert os.path.exists(_native.LIB_PATH), "libmmx_hip.so must be built in-tree"
-    return torch.device("cuda", 0)
 
 
 # ---------------------------------------------------------------------------------------------- the march's geometry

@@ -13,10 +13,10 @@ The tiled path takes a batch whose blocks have ny >= R + 4, nz >= R + 1 and nx >
 blocks here are R + 4 rows high -- the least it admits -- and the depth nz = R of every sweep runs in a batch of its own,
 which the library sends through the separate passes: compared all the same, but not asserted to be the tiled path.
 """
-import os
-
 import numpy as np
 import pytest
+
+from gpu_support import gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -29,15 +29,6 @@ FLOAT_RANGE = 2.0
 F32_TILE_TOL = 1e-6
 # (the float32 separate passes, which take the blocks of depth R: test_block_shape_and_dtype_sweep_matches_oracle)
 SEPARATE_TOL = 5e-6
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a GPU: torch.cuda.is_available() is False")
-    from magellanmapper_amd import _native
-    assert os.path.exists(_native.LIB_PATH), "libmmx_hip.so must be built in-tree"
-    return torch.device("cuda", 0)
 
 
 class _Volumes:

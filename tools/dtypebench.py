@@ -19,13 +19,13 @@
    and their digests are recorded.
 """
 import argparse
-import hashlib
-import json
 import os
 import subprocess
 import sys
 import tempfile
 import time
+
+import abbench
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -33,13 +33,6 @@ SIGMA = (3.0, 5.0)
 NUM_SIGMA = 5
 THRESHOLD, OVERLAP = 0.1, 0.5
 SEGMENT, HALO = 256, 25
-
-
-def summarise(ms):
-    s = sorted(ms)
-    n = len(s)
-    med = s[n // 2] if n % 2 else 0.5 * (s[n // 2 - 1] + s[n // 2])
-    return dict(median_ms=med, min_ms=s[0], max_ms=s[-1], spread_ms=s[-1] - s[0], repeats=n, ms=list(ms))
 
 
 def block_grid(shape):
@@ -52,17 +45,6 @@ def block_grid(shape):
                 origins.append((z0, y0, x0))
                 shapes.append((z1 - z0, y1 - y0, x1 - x0))
     return origins, shapes
-
-
-def table_digest(tables):
-    import numpy as np
-    h = hashlib.sha1()
-    n = 0
-    for t in tables:
-        t = np.ascontiguousarray(t, dtype=np.float64)
-        h.update(t.tobytes())
-        n += len(t)
-    return n, h.hexdigest()
 
 
 # ------------------------------------------------------------------------------------------------ 1. resident step
@@ -102,14 +84,14 @@ def resident(args):
         for k in vols:
             for _ in range(args.warmup):
                 _, res, stats = step(k)
-            n, sha = table_digest(res)
+            n, sha = abbench.table_digest(res)
             rec[k] = dict(blobs=n, table_sha1=sha, zx_path=bl.LAST_ZX_PATH, q16_bound=bl.LAST_Q16_BOUND,
                           nms_band=bl.LAST_NMS_BAND, candidates=int(stats.n_candidates))
         for _ in range(args.repeats):                  # uint16, int16, uint16, int16, ...
             for k in vols:
                 times[k].append(step(k)[0])
         for k in vols:
-            rec[k].update(summarise(times[k]))
+            rec[k].update(abbench.summarise(times[k]), ms=times[k])
         u, i = rec["uint16"], rec["int16"]
         rec["int16_over_uint16"] = i["median_ms"] / u["median_ms"]
         rec["uint16_relative_spread"] = u["spread_ms"] / u["median_ms"]
@@ -139,9 +121,8 @@ def worker(root, path):
     config.resolutions = np.array([[1.0, 1.0, 1.0]])
     config.filename = "dtypebench"
     config.near_max = [-1.0]
-    for line in sys.stdin:
-        if line.strip() == "quit":
-            break
+
+    def run(req):
         img = np.load(path, mmap_mode="r")
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -149,35 +130,9 @@ def worker(root, path):
                                                        False, False, True, False)
         torch.cuda.synchronize()
         ms = (time.perf_counter() - t0) * 1e3
-        n, sha = table_digest([blobs.blobs] if blobs.blobs is not None else [])
-        sys.stdout.write(json.dumps(dict(ms=ms, blobs=n, table_sha1=sha)) + "\n")
-        sys.stdout.flush()
-
-
-class Worker:
-    def __init__(self, root, path):
-        env = dict(os.environ)
-        env.pop("MMX_LIB_PATH", None)
-        self.p = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--worker", root, path],
-                                  stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True, env=env, cwd=root)
-
-    def run(self):
-        self.p.stdin.write("run\n")
-        self.p.stdin.flush()
-        while True:
-            line = self.p.stdout.readline()
-            if not line:
-                raise RuntimeError("worker ended (exit status %s)" % self.p.wait())
-            if line.startswith("{"):
-                return json.loads(line)
-
-    def close(self):
-        try:
-            self.p.stdin.write("quit\n")
-            self.p.stdin.close()
-            self.p.wait(timeout=60)
-        except Exception:
-            self.p.kill()
+        n, sha = abbench.table_digest([blobs.blobs] if blobs.blobs is not None else [])
+        return dict(ms=ms, blobs=n, table_sha1=sha)
+    abbench.serve(dict(describe=run, run=run))
 
 
 def make_map(path, shape, seed):
@@ -199,24 +154,22 @@ def against_parent(args):
     # (the seeded generator runs on the device, in a child that is gone before the workers start)
     subprocess.check_call([sys.executable, os.path.abspath(__file__), "--make-map", path, "--map-shape",
                            *[str(v) for v in shape], "--seed", str(args.seed)], cwd=ROOT)
-    builds = {"parent": Worker(os.path.abspath(args.parent_root), path), "tree": Worker(ROOT, path)}
+    env = dict(os.environ)
+    env.pop("MMX_LIB_PATH", None)
+    builds = {b: abbench.Worker(os.path.abspath(__file__), ["--worker", root, path], env=env, cwd=root)
+              for b, root in (("parent", os.path.abspath(args.parent_root)), ("tree", ROOT))}
     out = dict(shape=list(shape), bytes_int16=int(np.prod(shape)) * 2, bytes_float64=int(np.prod(shape)) * 8,
                workload="read-only int16 memory map -> stack_detect.detect_blobs_blocks (raw voxels) -> final table")
+    last = {}
+
+    def keep_last(b, reply, _):
+        last[b] = reply
     try:
-        first = {b: w.run() for b, w in builds.items()}          # (also the warm-up)
-        for _ in range(max(0, args.warmup - 1)):
-            for w in builds.values():
-                w.run()
-        times = {b: [] for b in builds}
-        last = {}
-        for _ in range(args.repeats):                            # parent, tree, parent, tree, ...
-            for b, w in builds.items():
-                r = w.run()
-                times[b].append(r["ms"])
-                last[b] = r
+        # (the first run of each is also a warm-up)
+        first, times = abbench.alternate(builds, list(builds), None, max(0, args.warmup - 1), args.repeats, check=keep_last)
         for b in builds:
-            out[b] = dict(summarise(times[b]), blobs=last[b]["blobs"], table_sha1=last[b]["table_sha1"],
-                          first_ms=first[b]["ms"])
+            out[b] = dict(abbench.summarise(times[b]), ms=times[b], blobs=last[b]["blobs"],
+                          table_sha1=last[b]["table_sha1"], first_ms=first[b]["ms"])
     finally:
         for w in builds.values():
             w.close()
@@ -260,10 +213,7 @@ def main():
         # (before this process opens the GPU itself: three processes on the device at the most)
         result["against_parent"] = against_parent(args)
     result["resident"] = resident(args)
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(result, f, indent=1, sort_keys=True)
-            f.write("\n")
+    abbench.write_json(args.out, result)
     return 0
 
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """What a thin remainder costs, and what the folded passes give: this tree against another checkout of the project
-(the parent commit's, built), in ONE run, the two alternating repeat by repeat (the scheme of tools/widerowbench.py).
+(the parent commit's, built), in ONE run, the two alternating repeat by repeat (the scheme of tools/abbench.py).
 
     python tools/thinbench.py --parent-tree /path/to/parent/checkout --repeats 5 --out profiles/r11_thin.json
 
@@ -23,12 +23,12 @@ batches' own kernel time.  Of b_*: not slower than the parent beyond the parent'
 Each tree runs in a worker process of its own (``--worker``, importing the package from its tree), both alive for the
 whole run; a worker that dies ends the run."""
 import argparse
-import hashlib
-import json
 import os
 import subprocess
 import sys
 import time
+
+import abbench
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -117,54 +117,16 @@ def worker(tree):
             nat.timing_enable(False)
             bl._enqueue_detect = enqueue
         order = np.lexsort(tuple(table[:, i] for i in range(table.shape[1] - 1, -1, -1))) if table.size else []
-        digest = hashlib.sha1(np.ascontiguousarray(table[order]).tobytes()).hexdigest()
-        return dict(batches=batches, kinds=kinds, thin_kinds=thin_kinds, rows=int(len(table)), table_sha1=digest)
+        rows, digest = abbench.table_digest([table[order]])
+        return dict(batches=batches, kinds=kinds, thin_kinds=thin_kinds, rows=rows, table_sha1=digest)
 
-    for line in sys.stdin:
-        req = json.loads(line)
-        if req["cmd"] == "quit":
-            break
+    def answer(req):
         setup(req["case"])
-        rep = describe() if req["cmd"] == "describe" else dict(ms=step()[0])
-        sys.stdout.write(json.dumps(rep) + "\n")
-        sys.stdout.flush()
+        return describe() if req["cmd"] == "describe" else dict(ms=step()[0])
+    abbench.serve(dict(describe=answer, run=answer))
 
 
 # ---------------------------------------------------------------------------------------------------------- driver
-class Worker:
-    def __init__(self, tree):
-        env = dict(os.environ)
-        env.pop("MMX_LIB_PATH", None)
-        self.p = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--worker", "--tree", os.path.abspath(tree)],
-                                  stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True, env=env, cwd=os.path.abspath(tree))
-
-    def ask(self, **req):
-        self.p.stdin.write(json.dumps(req) + "\n")
-        self.p.stdin.flush()
-        while True:
-            line = self.p.stdout.readline()
-            if not line:
-                raise RuntimeError("worker ended (exit status %s)" % self.p.wait())
-            if line.startswith("{"):
-                return json.loads(line)
-
-    def close(self):
-        try:
-            self.p.stdin.write('{"cmd": "quit"}\n')
-            self.p.stdin.close()
-            self.p.wait(timeout=60)
-        except Exception:
-            self.p.kill()
-
-
-def summarise(ms, voxels):
-    s = sorted(ms)
-    n = len(s)
-    med = s[n // 2] if n % 2 else 0.5 * (s[n // 2 - 1] + s[n // 2])
-    return dict(median_ms=med, min_ms=s[0], max_ms=s[-1], spread_ms=s[-1] - s[0], repeats=n, ms=ms,
-                ns_per_voxel=med * 1e6 / voxels, ns_per_voxel_max=s[-1] * 1e6 / voxels)
-
-
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
@@ -191,7 +153,10 @@ def main():
             commit = subprocess.run(["git", "rev-parse", "HEAD"], cwd=ROOT, stdout=subprocess.PIPE, text=True).stdout.strip()
         except OSError:
             commit = ""
-    builds = {"parent": Worker(args.parent_tree), "new": Worker(ROOT)}
+    env = dict(os.environ)
+    env.pop("MMX_LIB_PATH", None)
+    builds = {b: abbench.Worker(os.path.abspath(__file__), ["--worker", "--tree", os.path.abspath(tree)], env=env,
+                                cwd=os.path.abspath(tree)) for b, tree in (("parent", args.parent_tree), ("new", ROOT))}
     result = dict(command=" ".join([os.path.basename(sys.executable)] + sys.argv), commit=commit or "unknown",
                   parent_commit=args.parent_commit or "unknown", profile={k: v for k, v in PROFILE.items()},
                   warmup=args.warmup, cases={})
@@ -201,17 +166,9 @@ def main():
             shape, seg, trees = CASES[c]
             voxels = shape[0] * shape[1] * shape[2]
             rec = dict(shape=shape, segment_size=seg, voxels=voxels)
+            described, times = abbench.alternate(builds, trees, c, args.warmup, args.repeats)
             for b in trees:
-                rec[b] = builds[b].ask(cmd="describe", case=c)              # (also the first warm-up step)
-            for _ in range(args.warmup):
-                for b in trees:
-                    builds[b].ask(cmd="run", case=c)
-            times = {b: [] for b in trees}
-            for _ in range(args.repeats):                                   # parent, new, parent, new, ...
-                for b in trees:
-                    times[b].append(builds[b].ask(cmd="run", case=c)["ms"])
-            for b in trees:
-                rec[b].update(summarise(times[b], voxels))
+                rec[b] = dict(described[b], ms=times[b], **abbench.summarise(times[b], voxels))
             n = rec["new"]
             line = "%-9s new %9.2f ms [%.2f .. %.2f] %.4f ns/voxel" % (c, n["median_ms"], n["min_ms"], n["max_ms"], n["ns_per_voxel"])
             if "parent" in trees:
@@ -242,10 +199,7 @@ def main():
     finally:
         for w in builds.values():
             w.close()
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(result, f, indent=1, sort_keys=True)
-            f.write("\n")
+    abbench.write_json(args.out, result)
     return 0 if ok else 1
 
 

@@ -17,11 +17,10 @@ achieved FMA rate of the three wide passes against the float32 vector peak, from
 Each build runs in a worker process of its own (``--worker``; the library is chosen by ``MMX_LIB_PATH``), both alive for
 the whole run; the driver hands out one repeat at a time, parent and new in turn.  A worker that dies ends the run."""
 import argparse
-import hashlib
-import json
 import os
-import subprocess
 import sys
+
+import abbench
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
@@ -57,13 +56,12 @@ def wide_fma_per_voxel(radius):
 # ---------------------------------------------------------------------------------------------------------- worker
 def worker():
     import ctypes
-    import numpy as np
     import torch
     from magellanmapper_amd import _native as nat
     # (the other build may be of the ABI before this one: same entry points, one timing family fewer)
     nat.MMX_ABI_VERSION = ctypes.CDLL(nat.LIB_PATH).mmx_abi_version()
     from magellanmapper_amd import blob_log as bl, synth
-    L = nat.lib()
+    from magellanmapper_amd.rawbatch import RawBatch, timed
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     side = STEP + BLOCK
@@ -71,113 +69,45 @@ def worker():
     dvol = bl.DeviceVolume(vol)
     origins = [(z, y, x) for z in (0, STEP) for y in (0, STEP) for x in (0, STEP)]
     shapes = [(BLOCK,) * 3] * 8
-    blocks, slot = bl._make_blocks(dvol, 0, origins, shapes)
-    d_blocks = bl._to_device_bytes(blocks, dev)
-    nb = len(blocks)
-    v32, vex = dvol.view(0, True), dvol.view(0, False)
-    ws = torch.empty(-(-int(L.mmx_workspace_bytes(nb, slot, NUM_SIGMA, 1)) // 4), dtype=torch.float32, device=dev)
-    cap = 1 << 22
-    table = torch.zeros(cap * nat.CAND_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-    count = torch.zeros(2, dtype=torch.int32, device=dev)
-    stream = torch.cuda.current_stream().cuda_stream
     keep = {}
 
-    def args_of(name):
+    def batch_of(name):
         if name not in keep:
             lo, hi, ns = cases()[name]
             lane = bl.Lane(0, lo, hi, ns, THRESHOLD, OVERLAP)
-            lane.bind(dvol, nb)
-            space = lane.space
-            a = nat.DetectArgs()
-            a.vol32, a.vol_exact = ctypes.pointer(v32), ctypes.pointer(vex)
-            a.d_blocks, a.h_blocks, a.n_blocks, a.n_sigma, a.slot_elems = d_blocks.data_ptr(), blocks.ctypes.data, nb, ns, slot
-            a.h_w0, a.h_w2 = space.w0_tab.ctypes.data, space.w2_tab.ctypes.data
-            a.d_w0, a.d_w2 = lane.d_w0.data_ptr(), lane.d_w2.data_ptr()
-            a.h_radius, a.h_norm = space.radii.ctypes.data, space.norms.ctypes.data
-            a.d_work, a.work_bytes, a.thr, a.eps = ws.data_ptr(), ws.numel() * 4, lane.threshold, lane.eps
-            a.d_cands, a.cap, a.d_count = table.data_ptr(), cap, count.data_ptr()
-            a.zx_mode, a.zx_flags, a.store_f32, a.exact, a.expand = nat.MMX_ZX_AUTO, 0, 0, 1, 1
-            a.stream = a.tail_stream = a.pack_stream = stream
-            keep[name] = (a, lane)
+            lane.bind(dvol, len(shapes))
+            keep.clear()                # (one case's workspace and table at a time)
+            batch = RawBatch(dvol, origins, shapes, lane.space, lane.threshold, lane.eps, 1 << 22)
+            keep[name] = (batch, batch.args())
         return keep[name]
 
     def one_call(name):
-        a, lane = args_of(name)
+        batch, a = batch_of(name)
         info = nat.DetectInfo()
         t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0.record()
-        rc = L.mmx_detect_batch(ctypes.byref(a), ctypes.byref(info))
+        rc = batch.L.mmx_detect_batch(ctypes.byref(a), ctypes.byref(info))
         t1.record()
         nat.check(rc, "mmx_detect_batch")
         torch.cuda.synchronize()
-        n_all, n_cands = (int(v) for v in count.cpu().numpy().view(np.uint32))
+        n_all, n_cands = batch.counts()
         return dict(ms=t0.elapsed_time(t1), n_pass_rounds=info.n_pass_rounds, mask_layout=info.mask_layout,
-                    zx_path=info.zx_path, entries=n_all, candidates=n_cands, radii=[int(r) for r in lane.space.radii])
+                    zx_path=info.zx_path, entries=n_all, candidates=n_cands, radii=[int(r) for r in batch.space.radii])
 
-    for line in sys.stdin:
-        req = json.loads(line)
-        if req["cmd"] == "quit":
-            break
-        name = req["case"]
-        if req["cmd"] == "run":
-            rep = one_call(name)
-        else:       # "describe": the kernel families of one call, and the resolved peaks
-            nat.timing_enable(True)
-            try:
-                nat.timing_read()
-                rep = one_call(name)
-                rep["kinds"] = {k: [ms, int(n)] for k, (ms, n) in nat.timing_read().items() if n}
-            finally:
-                nat.timing_enable(False)
-            lo, hi, ns = cases()[name]
-            _, peaks = bl.blob_log_blocks(dvol, 0, origins, shapes, lo, hi, ns, THRESHOLD, OVERLAP, return_peaks=True)
-            h = hashlib.sha1()
-            n_peaks = 0
-            for coords, vals in peaks:
-                h.update(np.ascontiguousarray(coords).tobytes())
-                h.update(np.ascontiguousarray(vals).tobytes())
-                n_peaks += len(coords)
-            rep["peaks"], rep["peaks_sha1"] = n_peaks, h.hexdigest()
-            bl.release_buffers()
-        sys.stdout.write(json.dumps(rep) + "\n")
-        sys.stdout.flush()
+    def describe(name):
+        """The kernel families of one call, and the resolved peaks."""
+        rep, kinds = timed(lambda: one_call(name))
+        rep["kinds"] = {k: [ms, int(n)] for k, (ms, n) in kinds.items() if n}
+        lo, hi, ns = cases()[name]
+        _, peaks = bl.blob_log_blocks(dvol, 0, origins, shapes, lo, hi, ns, THRESHOLD, OVERLAP, return_peaks=True)
+        rep["peaks"], rep["peaks_sha1"] = abbench.peaks_digest(peaks)
+        bl.release_buffers()
+        return rep
+
+    abbench.serve(dict(run=lambda req: one_call(req["case"]), describe=lambda req: describe(req["case"])))
 
 
 # ---------------------------------------------------------------------------------------------------------- driver
-class Worker:
-    def __init__(self, lib):
-        env = dict(os.environ)
-        if lib:
-            env["MMX_LIB_PATH"] = os.path.abspath(lib)
-        self.p = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--worker"], stdin=subprocess.PIPE,
-                                  stdout=subprocess.PIPE, text=True, env=env, cwd=ROOT)
-
-    def ask(self, **req):
-        self.p.stdin.write(json.dumps(req) + "\n")
-        self.p.stdin.flush()
-        while True:
-            line = self.p.stdout.readline()
-            if not line:
-                raise RuntimeError("worker ended (exit status %s)" % self.p.wait())
-            if line.startswith("{"):
-                return json.loads(line)
-
-    def close(self):
-        try:
-            self.p.stdin.write('{"cmd": "quit"}\n')
-            self.p.stdin.close()
-            self.p.wait(timeout=60)
-        except Exception:
-            self.p.kill()
-
-
-def summarise(ms):
-    s = sorted(ms)
-    n = len(s)
-    med = s[n // 2] if n % 2 else 0.5 * (s[n // 2 - 1] + s[n // 2])
-    return dict(median_ms=med, min_ms=s[0], max_ms=s[-1], spread_ms=s[-1] - s[0], repeats=n)
-
-
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
@@ -197,29 +127,21 @@ def main():
     for c in names:
         if c not in cases():
             ap.error("unknown case %s" % c)
-    builds = {"parent": Worker(args.parent_lib), "new": Worker(None)}
+    me = os.path.abspath(__file__)
+    builds = {"parent": abbench.Worker(me, ["--worker"], cwd=ROOT,
+                                       env=dict(os.environ, MMX_LIB_PATH=os.path.abspath(args.parent_lib))),
+              "new": abbench.Worker(me, ["--worker"], cwd=ROOT)}
     result = dict(volume="uint16 %d^3, 8 blocks of %d^3" % (STEP + BLOCK, BLOCK), resolution_um=RES_UM,
                   threshold=THRESHOLD, peak_f32_vector_tflops=PEAK_F32_VECTOR_TFLOPS, cases={})
     voxels = 8 * BLOCK ** 3
     ok = True
     try:
         for c in names:
-            rec = {}
-            for b, w in builds.items():
-                rec[b] = w.ask(cmd="describe", case=c)          # (also the first warm-up call)
-                rec[b]["ms_first"] = rec[b].pop("ms")
-            for _ in range(args.warmup):
-                for w in builds.values():
-                    w.ask(cmd="run", case=c)
-            times = {b: [] for b in builds}
-            for _ in range(args.repeats):                       # parent, new, parent, new, ...
-                for b, w in builds.items():
-                    r = w.ask(cmd="run", case=c)
-                    times[b].append(r["ms"])
-                    for k in ("n_pass_rounds", "mask_layout", "zx_path", "candidates"):
-                        assert r[k] == rec[b][k], (c, b, k, r[k], rec[b][k])
+            rec, times = abbench.alternate(builds, list(builds), c, args.warmup, args.repeats,
+                                           check=abbench.same_fields("n_pass_rounds", "mask_layout", "zx_path", "candidates"))
             for b in builds:
-                rec[b].update(summarise(times[b]), ms=times[b])
+                rec[b]["ms_first"] = rec[b].pop("ms")
+                rec[b].update(abbench.summarise(times[b]), ms=times[b])
             p, n = rec["parent"], rec["new"]
             rec["same_peaks"] = p["peaks_sha1"] == n["peaks_sha1"] and p["peaks"] == n["peaks"]
             rec["same_candidate_count"] = p["candidates"] == n["candidates"]
@@ -244,10 +166,7 @@ def main():
     finally:
         for w in builds.values():
             w.close()
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(result, f, indent=1, sort_keys=True)
-            f.write("\n")
+    abbench.write_json(args.out, result)
     return 0 if ok else 1
 
 
