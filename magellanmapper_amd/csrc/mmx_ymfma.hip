@@ -29,6 +29,16 @@
 // (4 KiB per wave and tile) to come back as one row of 64 columns per step, lane = column as in y6_kernel, whose
 // ballot / sparse store / entry code then runs unchanged -- except that a tile with nothing above the threshold (a
 // ballot over the accumulators) skips all of it and writes its sixteen zero entries with one store.
+//
+// The k-block loop, as the listing has it (profiles/r19_y_kblock_loop.txt): the block's 32 registers of rows become 64
+// of pieces, the next block's rows are loaded into the 32 just freed -- always, also behind the last block, so that no
+// path merges loaded and kept registers --, then the rows of the two tiles the previous block finished (their stores a
+// whole MFMA phase ahead of the wait for those loads: one counter counts both), the MFMAs, the hand-off.  Nothing is
+// copied: not the rows, not the accumulators on their way to LDS (each leaves as it is, the reader takes four rows of
+// its column with one read), not the window.  What a wave keeps per lane across the loop is counted in registers it
+// does not have (166 of 168 at NB = 4), so lane-dependent offsets that only rare paths want are made where they are
+// used.  The entry of a decided row is written into its lane from the scalar side (four v_writelane_b32), the tests
+// behind it are compares whose results are the wave's words already.
 
 #include <type_traits>
 
@@ -48,8 +58,20 @@ struct ym_cfg {
 
 namespace {
 
-// Workgroup = four waves = one tile column.  NB <= 4 (R <= 16): 164 registers and 44 / 48 KiB of LDS, three workgroups
-// per CU; NB == 5 (R <= 24): 180 registers and 52 KiB, two (held to 168 registers it spills 20 and is slower: 2.10
+// v with lane LN replaced by the wave-uniform s (v_writelane_b32 has no builtin in this compiler; the lane is an immediate)
+template <int LN>
+__device__ __forceinline__ unsigned ym_writelane(unsigned v, unsigned s)
+{
+    asm("v_writelane_b32 %0, %1, %2" : "+v"(v) : "s"(s), "n"(LN));
+    return v;
+}
+
+// where lane (kq = lane >> 4, n16 = lane & 15) puts its accumulator 0 in a hand-off slot, in units of 16 bytes:
+// 64 kq + 4 n16 + (n16 >> 2) (see trw in the kernel)
+__device__ __forceinline__ int ym_hput(int lane) { return (lane << 2) | ((lane >> 2) & 3); }
+
+// Workgroup = four waves = one tile column.  NB <= 4 (R <= 16): 154 / 166 registers and 44 / 48 KiB of LDS, three workgroups
+// per CU; NB == 5 (R <= 24): 182 registers and 52 KiB, two (held to 168 registers it spilled 20 and was slower: 2.10
 // against 1.72 ms per 64 blocks).  Measured with six offsets (RB = 32, what R <= 24 took before the five-offset
 // alignment was found: 1.99 ms) and kept as the YM6_* switches: pieces built for two column sets at a time -- 32
 // registers less, the fragments read twice -- with TWELVE waves = three tile columns sharing one fragment table, i.e.
@@ -81,6 +103,46 @@ ym_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile
     const mmx_block bd = blocks[cfg.reverse ? gridDim.y - 1 - blockIdx.y : blockIdx.y];
     const int ntx = (bd.nx + 15) >> 4, ntz = (bd.nz + 15) >> 4;
     if ((int)blockIdx.x * (WAVES / 4) >= ntx * ntz) return;     // (the whole workgroup)
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int tile = (int)blockIdx.x * (WAVES / 4) + (wv >> 2);
+    const int c = tile / ntz, U = tile - c * ntz;
+    const int zq = wv & 3;
+    const bool live = tile < ntx * ntz && 16 * U + 4 * zq < bd.nz;     // (whole waves; the others leave behind the barrier)
+    const int lane = threadIdx.x & 63;
+    const int n = bd.ny;
+    // ---- as a loader / MFMA operand holder: k-group kq, column index n16 (plane n16 >> 2, x quad n16 & 3)
+    const int kq = lane >> 4, n16 = lane & 15;
+    const unsigned trow_b = (unsigned)(ntx * ntz) * 1024u;      // bytes from one y to the next
+    const rsrc_t rs = make_rsrc(gt + (int64_t)bd.slot * tile_stride + (int64_t)tile * 256);
+    const unsigned voff = (unsigned)(zq * 256 + n16 * 16);
+    const unsigned voff_s = voff + (unsigned)(8 * kq) * trow_b;  // blocks wholly inside the column: rows by scalar offset
+    // k-blocks of 32 input rows: block b holds rows -RB + 32 b + [0, 32), lane row 8 kq + i.  A block past the column's
+    // last takes the second form too: rows clamped into the column, whatever they hold
+    v4u raw[8];
+    auto load_block = [&](int b) __attribute__((always_inline)) {
+        const int r0 = -RB + 32 * b;
+        if (r0 >= 0 && r0 + 32 <= n) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+                raw[i] = __builtin_bit_cast(v4u, __builtin_amdgcn_raw_buffer_load_b128(rs, voff_s, (unsigned)(r0 + i) * trow_b, 0));
+        } else {
+            // (the lane's first row, 8 kq, made from the lane number here: the blocks at the column's ends are the
+            //  only ones to want it, and kept for them across the loop it is a register too many -- scratch)
+            int ln;
+            asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
+            const int k8 = (ln >> 1) & 24;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                int v = r0 + k8 + i;
+                v = v < 0 ? -1 - v : v;
+                v = v >= n ? 2 * n - 1 - v : v;
+                v = v < 0 ? 0 : (v > n - 1 ? n - 1 : v);       // beyond the taps' reach: any row, zero weights
+                raw[i] = __builtin_bit_cast(v4u, __builtin_amdgcn_raw_buffer_load_b128(rs, voff + (unsigned)v * trow_b, 0, 0));
+            }
+        }
+    };
+    // the first block's rows are on their way while the fragment table is built
+    if (live) load_block(0);
     // ---- Toeplitz fragments: A[m][k] = w[|k - m + delta_t|], lane = (m = l & 15, k = 8 (l >> 4) + i)
     for (int e = threadIdx.x; e < NB * NF * 64; e += WAVES * 64) {
         const int ln = e & 63, f = e >> 6;
@@ -105,21 +167,8 @@ ym_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile
     }
     __syncthreads();
 
-    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int tile = (int)blockIdx.x * (WAVES / 4) + (wv >> 2);
-    if (tile >= ntx * ntz) return;                              // (whole waves; no barriers below)
-    const int c = tile / ntz, U = tile - c * ntz;
-    const int zq = wv & 3;
-    if (16 * U + 4 * zq >= bd.nz) return;                       // whole wave past the block
-    const int lane = threadIdx.x & 63;
-    const int n = bd.ny;
+    if (!live) return;                                          // (no barriers below)
     const float nms_lo = cfg.lo, nms_eps = cfg.eps, us = cfg.unscale;
-    // ---- as a loader / MFMA operand holder: k-group kq, column index n16 (plane n16 >> 2, x quad n16 & 3)
-    const int kq = lane >> 4, n16 = lane & 15;
-    const unsigned trow_b = (unsigned)(ntx * ntz) * 1024u;      // bytes from one y to the next
-    const rsrc_t rs = make_rsrc(gt + (int64_t)bd.slot * tile_stride + (int64_t)tile * 256);
-    const unsigned voff = (unsigned)(zq * 256 + n16 * 16);
-    const unsigned voff_s = voff + (unsigned)(8 * kq) * trow_b;  // blocks wholly inside the column: rows by scalar offset
     // ---- as a row worker (y6_kernel's lane): plane lane >> 4 of the quarter, column lane & 15
     const int xi = lane & 15;
     const int z = 16 * U + 4 * zq + (lane >> 4), x = 16 * c + xi;
@@ -138,9 +187,17 @@ ym_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile
                             : nullptr;
     unsigned long long ab_prev = 0;
     const bool has_l = xi > 0, has_r = xi < 15 && x + 1 < bd.nx;
+    // (the same three as words of the wave, for tests taken as ballots)
+    const unsigned long long realw = __builtin_amdgcn_ballot_w64(real), has_lw = __builtin_amdgcn_ballot_w64(has_l),
+                             has_rw = __builtin_amdgcn_ballot_w64(has_r);
     float prev1 = -INFINITY, prev2 = -INFINITY, nbx_prev = -INFINITY;
     int ydone = 0;
-    float* trw = tr + wv * 2048;
+    // the wave's two hand-off slots, in units of 16 bytes: four consecutive rows of one column -- an accumulator as the
+    // MFMA leaves it -- at unit 64 g + (col ^ (col >> 4)), col = the row worker's lane, g = row >> 2.  The swizzle spreads
+    // the sixteen lanes of a k-group (columns 4 n16 + j) over all banks; a row worker's sixteen columns stay a permutation
+    v4f* trw = reinterpret_cast<v4f*>(tr + wv * 2048);
+    // (accumulator j of lane (kq, n16) goes to unit ym_hput(lane) ^ j)
+    const int hget = lane ^ (lane >> 4);                        // rows 4 g .. 4 g + 3 of this lane's column: unit 64 g + hget
 
     // the pending row's entry when it has no successor (the block's last row), or one that cannot beat it
     auto close_pending = [&]() __attribute__((always_inline)) {
@@ -187,17 +244,30 @@ ym_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile
                 close_pending();
                 mrow += nent;
             }
-            if (lane < cnt - 1) mrow[(int64_t)lane * nent] = make_ulonglong2(0ull, 0ull);
+            int ln = lane;                  // (the lane's entry offset is made here: kept for this path it spills)
+            asm volatile("" : "+v"(ln));
+            if (ln < cnt - 1) mrow[(int64_t)ln * nent] = make_ulonglong2(0ull, 0ull);
             mrow += (int64_t)(cnt - 1) * nent;
             prev1 = prev2 = nbx_prev = -INFINITY;
             ab_prev = 0;
             ydone += cnt;
             return;
         }
-        const float* src = trw + s * 1024 + lane;
-        if (!MASK || cnt < 16) {                   // (every row stored, or the column's last, partial tile: row by row)
+        const v4f* src = trw + s * 256 + hget;
+        if constexpr (!MASK) {                     // every row stored: four at a time
 #pragma unroll 1
-            for (int r = 0; r < cnt; ++r) row(src[r * 64], 16 * T + r);
+            for (int g = 0; 4 * g < cnt; ++g) {
+                const v4f q = src[g * 64];
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (4 * g + r < cnt) row(q[r], 16 * T + 4 * g + r);
+            }
+            return;
+        }
+        if (cnt < 16) {                            // (the column's last, partial tile: row by row)
+            const float* src1 = reinterpret_cast<const float*>(src);
+#pragma unroll 1
+            for (int r = 0; r < cnt; ++r) row(src1[(r >> 2) * 256 + (r & 3)], 16 * T + r);
             return;
         }
         // A whole tile at once: all sixteen rows in registers, one ballot each; only rows with something above the
@@ -205,42 +275,59 @@ ym_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile
         // -- the pending row and rows 0 .. 14 -- leave in one store, lane i holding the entry of row 16 T - 1 + i.
         float v[16];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) v[r] = src[r * 64];
-        unsigned long long ab[16];
-        unsigned long long some = 0;
+        for (int g = 0; g < 4; ++g) {
+            const v4f q = src[g * 64];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { ab[r] = mmx_above_word(real, v[r], nms_lo); some |= ab[r]; }
-        unsigned e0 = 0, e1 = 0, e2 = 0, e3 = 0;                   // entry = (cand lo, cand hi, above lo, above hi)
-        auto put = [&](int ln, unsigned long long m, unsigned long long a) __attribute__((always_inline)) {
-            const bool me = lane == ln;
-            e0 = me ? (unsigned)m : e0;
-            e1 = me ? (unsigned)(m >> 32) : e1;
-            e2 = me ? (unsigned)a : e2;
-            e3 = me ? (unsigned)(a >> 32) : e3;
-        };
-        if (ab_prev) {                                              // the pending row: its successor is v[0]
-            const bool cand = real & (prev1 > nms_lo) & !(fmaxf(fmaxf(prev2, v[0]), nbx_prev) > prev1 + nms_eps);
-            put(0, __ballot(cand), ab_prev);
+            for (int r = 0; r < 4; ++r) v[4 * g + r] = q[r];
         }
+        // entry = (cand lo, cand hi, above lo, above hi), written into its lane from the scalar side.  A row's
+        // candidates are its lanes above the threshold -- its word `a` -- that no neighbour beats
+        unsigned e0 = 0, e1 = 0, e2 = 0, e3 = 0;
+        auto put = [&](auto LN, unsigned long long beaten, unsigned long long a) __attribute__((always_inline)) {
+            constexpr int ln = decltype(LN)::value;
+            const unsigned long long m = a & ~beaten;
+            e0 = ym_writelane<ln>(e0, (unsigned)m);
+            e1 = ym_writelane<ln>(e1, (unsigned)(m >> 32));
+            e2 = ym_writelane<ln>(e2, (unsigned)a);
+            e3 = ym_writelane<ln>(e3, (unsigned)(a >> 32));
+        };
+        if (ab_prev)                                                // the pending row: its successor is v[0]
+            put(std::integral_constant<int, 0>{},
+                __builtin_amdgcn_ballot_w64(fmaxf(fmaxf(prev2, v[0]), nbx_prev) > prev1 + nms_eps), ab_prev);
         float nbx15 = -INFINITY;
-        if (some) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                if (ab[r]) {
+        unsigned long long ab15 = 0;
+        // (a row's word is taken when its turn comes: sixteen words taken first are thirty-two scalar registers held
+        //  across the tile, which this kernel does not have)
+        auto one = [&](auto R) __attribute__((always_inline)) {
+            constexpr int r = decltype(R)::value;
+            const unsigned long long ab_r = __builtin_amdgcn_ballot_w64(v[r] > nms_lo) & realw;
+            if constexpr (r == 15) ab15 = ab_r;
+            if (ab_r) {
 #ifndef YM_NOSTORE
-                    if (real) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[r] * us), rsw, ooff, (unsigned)(16 * T + r) * row_b, 0);
+                if (real) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[r] * us), rsw, ooff, (unsigned)(16 * T + r) * row_b, 0);
 #endif
-                    const float nbx = mmx_x_neighbours<false>(v[r], has_l, has_r);
-                    if (r < 15) {
-                        const float below = r > 0 ? v[r > 0 ? r - 1 : 0] : prev1;
-                        const bool cand = real & (v[r] > nms_lo) & !(fmaxf(fmaxf(below, v[r < 15 ? r + 1 : 15]), nbx) > v[r] + nms_eps);
-                        put(r + 1, __ballot(cand), ab[r]);
-                    } else {
-                        nbx15 = nbx;
-                    }
+                if constexpr (r < 15) {
+                    // beaten by the row below or above, or by an x neighbour: the neighbours compared where they
+                    // arrive (lanes without one get 0 and are masked out), not gathered into a maximum first
+                    const float below = r > 0 ? v[r > 0 ? r - 1 : 0] : prev1;
+                    const float t = v[r] + nms_eps;
+                    const int b = (int)__float_as_uint(v[r]);
+                    const float l = __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, b, 0x111 /* row_shr:1 */, 0xf, 0xf, true));
+                    const float rr = __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, b, 0x101 /* row_shl:1 */, 0xf, 0xf, true));
+                    put(std::integral_constant<int, r + 1>{},
+                        __builtin_amdgcn_ballot_w64(below > t) | __builtin_amdgcn_ballot_w64(v[r < 15 ? r + 1 : 15] > t) |
+                            (__builtin_amdgcn_ballot_w64(l > t) & has_lw) | (__builtin_amdgcn_ballot_w64(rr > t) & has_rw),
+                        ab_r);
+                } else {
+                    nbx15 = mmx_x_neighbours<false>(v[r], has_l, has_r);      // (a value: the next tile, or row(), tests it)
                 }
             }
-        }
+        };
+        auto each = [&](auto... R) __attribute__((always_inline)) { (one(R), ...); };
+#define YM_R(i) std::integral_constant<int, i>{}
+        each(YM_R(0), YM_R(1), YM_R(2), YM_R(3), YM_R(4), YM_R(5), YM_R(6), YM_R(7), YM_R(8), YM_R(9), YM_R(10), YM_R(11),
+             YM_R(12), YM_R(13), YM_R(14), YM_R(15));
+#undef YM_R
         if (lane < 16 && (lane > 0 || ydone > 0)) {
             ulonglong2* dst = mrow + (int64_t)(ydone > 0 ? lane : lane - 1) * nent;
             *dst = make_ulonglong2((unsigned long long)e0 | ((unsigned long long)e1 << 32),
@@ -248,33 +335,10 @@ ym_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile
         }
         mrow += (int64_t)(ydone > 0 ? 16 : 15) * nent;
         prev2 = v[14]; prev1 = v[15]; nbx_prev = nbx15;
-        ab_prev = ab[15];
+        ab_prev = ab15;
         ydone += 16;
     };
 
-    // ---- k-blocks of 32 input rows: block b holds rows -RB + 32 b + [0, 32), lane row 8 kq + i
-#ifndef YM_PFD
-#define YM_PFD 1
-#endif
-    constexpr int PFD = YM_PFD;                     // k-blocks of loads in flight per wave
-    v4u rawA[8], rawB[PFD == 2 ? 8 : 1];
-    auto load_block = [&](int b, v4u (&raw)[8]) __attribute__((always_inline)) {
-        const int r0 = -RB + 32 * b;
-        if (r0 >= 0 && r0 + 32 <= n) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-                raw[i] = __builtin_bit_cast(v4u, __builtin_amdgcn_raw_buffer_load_b128(rs, voff_s, (unsigned)(r0 + i) * trow_b, 0));
-        } else {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                int v = r0 + 8 * kq + i;
-                v = v < 0 ? -1 - v : v;
-                v = v >= n ? 2 * n - 1 - v : v;
-                v = v < 0 ? 0 : (v > n - 1 ? n - 1 : v);       // beyond the taps' reach: any row, zero weights
-                raw[i] = __builtin_bit_cast(v4u, __builtin_amdgcn_raw_buffer_load_b128(rs, voff + (unsigned)v * trow_b, 0, 0));
-            }
-        }
-    };
     const int nT = (n + 15) >> 4;
     const int nKB = (nT + NB - 3) / 2 + 1;          // last block b with 2 b - NB + 2 <= nT - 1
     const v4f start = {cfg.start, cfg.start, cfg.start, cfg.start};
@@ -288,17 +352,16 @@ ym_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile
     const _Float16 k256 = (_Float16)256.f;
     // one k-block: rows of the tiles the previous block finished, then per group of JH column sets: this block's pieces,
     // (last group: the next block's loads,) the MFMAs, the hand-off of the two tiles that are complete
-    auto iter = [&](int b, v4u (&raw)[8]) __attribute__((always_inline)) {
+    auto iter = [&](int b) __attribute__((always_inline)) {
         // -- rows first (before this block's operands take their registers; their stores are older than the loads
         //    issued below, so waiting for those does not wait for these)
 #ifndef YM_ROWS_LATE
 #define YM_ROWS_LATE 1
 #endif
-        if (!YM_ROWS_LATE || b == nKB) {
+        if (!YM_ROWS_LATE) {
 #pragma unroll 1
             for (int h = 0; h < 2; ++h) rows_of(2 * (b - 1) - NB + 2 + h, h, h ? any1 : any0);
         }
-        if (b == nKB) return false;
         if constexpr (JH < 4) { any0 = !MASK; any1 = !MASK; }
 #pragma unroll
         for (int j0 = 0; j0 < 4; j0 += JH) {
@@ -316,8 +379,18 @@ ym_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile
                     pc[j][2][p] = __builtin_amdgcn_perm(d1, d0, 0x0c070c03u) ^ 0x00800080u;
                     pc[j][3][p] = __builtin_amdgcn_perm(d1, d0, 0x0c060c02u);
                 }
+            // (the pieces exist from here on: left to itself the compiler sinks the permutes below the row code, the
+            //  block's rows stay alive across it, and the next block's rows go to a second set of registers and are
+            //  copied back at the loop's end)
+#pragma unroll
+            for (int j = 0; j < JH; ++j)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) asm volatile("" : "+v"(pc[j][k]));
             __builtin_amdgcn_sched_barrier(0);
-            if (j0 + JH == 4 && b + PFD < nKB) load_block(b + PFD, raw);
+            // -- the next block's rows, into the registers this block's rows have just left.  Always issued: a
+            //    conditional load would merge loaded and old registers -- a copy of all of them per turn -- and the
+            //    block past the last one is one more read of the column's last rows, which nobody uses
+            if (j0 + JH == 4) load_block(b + 1);
             __builtin_amdgcn_sched_barrier(0);
             if (YM_ROWS_LATE && JH == 4) {
 #pragma unroll 1
@@ -358,18 +431,22 @@ ym_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile
 #pragma unroll
                     for (int r = 0; r < 4; ++r) mx = fmaxf(mx, a[j][r]);
                 const bool any = MASK ? __ballot(mx > nms_lo) != 0ull : true;
+                // (each accumulator as it is: four rows of one column, one 16-byte store, nothing to assemble)
                 if constexpr (JH == 4) {
                     if (t == 0) any0 = any; else any1 = any;
                     if (any) {
-                        v4f* dst = reinterpret_cast<v4f*>(trw + t * 1024) + (4 * kq) * 16 + n16;
+                        // (the units are made here from the lane number, a few instructions: kept across the loop
+                        //  they are four registers this kernel does not have)
+                        int ln = lane;
+                        asm volatile("" : "+v"(ln));
+                        const int hp = ym_hput(ln);
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) dst[r * 16] = (v4f){a[0][r], a[1][r], a[2][r], a[3][r]};
+                        for (int j = 0; j < 4; ++j) trw[t * 256 + (hp ^ j)] = a[j];
                     }
                 } else {        // (half a tile: the other half may be what is above the threshold)
                     if (t == 0) any0 |= any; else any1 |= any;
-                    v2f* dst = reinterpret_cast<v2f*>(trw + t * 1024) + (4 * kq) * 32 + 2 * n16 + (j0 >> 1);
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) dst[r * 32] = (v2f){a[0][r], a[1][r]};
+                    for (int j = 0; j < JH; ++j) trw[t * 256 + (ym_hput(lane) ^ (j0 + j))] = a[j];
                 }
             }
             __builtin_amdgcn_sched_barrier(0);     // (the finished tiles' registers are free from here on)
@@ -379,27 +456,19 @@ ym_kernel(const mmx_block* __restrict__ blocks, int64_t slot_elems, int64_t tile
                 if constexpr (NB > 4) __builtin_amdgcn_sched_barrier(0);       // one tile's fragments at a time
             }
         }
-        // the window moves on by two tiles (a rotation by renaming needs the loop unrolled NB / 2 times with the row code in
-        // every copy -- 70 KiB of instructions --, or a switch, after which the compiler keeps every set alive: 251 registers)
+        // the window moves on by two tiles.  No instruction in the listing: the compiler shifts it through the C operand
+        // of the tiles' first MFMAs, which read one set of registers and write the other
 #pragma unroll
         for (int t = 0; t + 2 < NB; ++t)
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[t][j] = acc[t + 2][j];
         __builtin_amdgcn_wave_barrier();
-        return true;
     };
-    load_block(0, rawA);
-    if constexpr (PFD == 2) {
-        if (nKB > 1) load_block(1, reinterpret_cast<v4u (&)[8]>(rawB));
 #pragma unroll 1
-        for (int b = 0;; b += 2) {
-            if (!iter(b, rawA)) break;
-            if (!iter(b + 1, reinterpret_cast<v4u (&)[8]>(rawB))) break;
-        }
-    } else {
+    for (int b = 0; b < nKB; ++b) iter(b);
+    // the rows of the last block's two tiles
 #pragma unroll 1
-        for (int b = 0; iter(b, rawA); ++b) {}
-    }
+    for (int h = 0; h < 2; ++h) rows_of(2 * (nKB - 1) - NB + 2 + h, h, h ? any1 : any0);
     if constexpr (MASK) close_pending();     // the last row has no successor
 }
 
