@@ -200,6 +200,12 @@ typedef enum {
 #define MMX_ZX_EDGE_GLOBAL 0x400 /* or-ed into MMX_ZX_TILED / MMX_ZX_TILED_Q16 (any zx_mode >= 0 accepts it): the Z+X kernel takes the Z
                                     fragments of the z tiles at a block's faces from the table in global memory, step by step, instead
                                     of from its LDS copy (the same arithmetic, bit for bit); for cross-checks */
+#define MMX_ZX_ROWS_SHIFT 12
+#define MMX_ZX_ROWS_MASK 0xF000
+#define MMX_ZX_ROWS(n) ((n) << MMX_ZX_ROWS_SHIFT) /* or-ed in like the flags above, n = 1 .. 15: the Z+X kernel whose waves march through
+                                    several rows of their column (16-bit tiles of integer voxels, radius 9 .. 16, LDS edge form)
+                                    gives every wave n rows in every block; 0, the default, chooses per block of the launch.  The
+                                    same arithmetic, bit for bit; n = 1 is the one-row march; for cross-checks and sweeps */
 #define MMX_MASK_ROWS 1
 #define MMX_MASK_QUADS 2
 int mmx_log_batch_f32(const mmx_volume* vol, const mmx_block* d_blocks, const mmx_block* h_blocks,

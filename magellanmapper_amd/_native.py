@@ -49,6 +49,15 @@ MMX_CAND_PROBE = 4
 MMX_ZX_AUTO, MMX_ZX_SEPARATE, MMX_ZX_PACKED, MMX_ZX_MFMA_F32, MMX_ZX_MFMA_F16, MMX_ZX_MFMA_F16_LDS = -1, 0, 2, 3, 4, 5
 MMX_ZX_TILED, MMX_ZX_TILED_Q16, MMX_ZX_PREPACKED, MMX_ZX_Y_VALU = 6, 7, 0x100, 0x200
 MMX_ZX_EDGE_GLOBAL = 0x400
+MMX_ZX_ROWS_SHIFT = 12
+MMX_ZX_ROWS_MASK = 0xF000
+
+
+def MMX_ZX_ROWS(n):
+    """zx flag field: n rows per wave of the Z+X row march in every block (0: chosen per block of the launch)."""
+    return int(n) << MMX_ZX_ROWS_SHIFT
+
+
 MMX_ZX_WIDE = 8
 #: by name only: the separate passes with the folded-reflection pass where a block is shorter than the kernel
 MMX_ZX_THIN = 9

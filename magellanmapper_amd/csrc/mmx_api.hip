@@ -272,7 +272,7 @@ int fused_passes(const mmx_log_call& c, const mmx_route& r, const mmx_batch_geom
     { mmx_timed_scope ts(MMX_K_ZX, s);
       if (tiled)
           rc = mmx_launch_zx6(vol, c.d_blocks, c.h_blocks, n_blocks, plan, txx, radius, c.d_work,
-                              r.q16 ? (float)(1.0 / r.bp) : 0.f, r.q16 ? (float)(1.0 / r.bq) : 0.f, r.edge_global, s);
+                              r.q16 ? (float)(1.0 / r.bp) : 0.f, r.q16 ? (float)(1.0 / r.bq) : 0.f, r.edge_global, r.zx_rows, s);
       else
           rc = mmx_launch_zx2(vol, c.d_blocks, n_blocks, g.max_ny, g.max_px, slot_elems, tzz, txx, radius, t0, t1, s); }
     if (rc != MMX_OK) return launched(rc, tiled ? "mmx_launch_zx6" : "mmx_launch_zx2", "fused passes");

@@ -62,7 +62,16 @@ int mmx_launch_zx6_pack(const mmx_volume* vol, const mmx_block* d_blocks, const 
                         const mmx_zx6_plan& plan, void* d_work, hipStream_t stream);
 int mmx_launch_zx6(const mmx_volume* vol, const mmx_block* d_blocks, const mmx_block* h_blocks, int n_blocks,
                    const mmx_zx6_plan& plan, const mmx_taps_f32& tx, int radius, void* d_work, float qp, float qq,
-                   bool edge_global, hipStream_t stream);
+                   bool edge_global, int rows, hipStream_t stream);
+// The row march's schedule on the host, exported for tests and tools (not part of include/mmx.h): for a launch of n_blocks
+// blocks with rows[b] rows and waves_per_row[b] waves per row on a device with `slots` resident waves of the row kernel
+// (< 0: the current device's, asked of the runtime), nr[b] = the rows per wave of block b -- never growing from block to
+// block, 1 on the last blocks and everywhere in small launches; forced > 0: that value everywhere.  cover (may be NULL):
+// one counter per (block, row, wave of the row), blocks one after the other, raised by every wave of the flat grid that
+// owns it, found as the kernel finds its rows -- all 1 when every row is marched once.  Returns the workgroups of the flat
+// grid, or minus a status.
+extern "C" int mmx_zx_rows_schedule(int n_blocks, const int32_t* rows, const int32_t* waves_per_row, int slots, int forced,
+                                    int32_t* nr, int32_t* cover);
 // cp, cq > 0: d_p holds Q16 tiles, P = unorm16 * cp, Q = snorm16 * cq (d_q unused); 0: float32 tiles
 // bias: added to every output before the threshold and the entries (int16 voxels: the scale's constant; else 0)
 int mmx_launch_y6(const mmx_block* d_blocks, int n_blocks, const mmx_zx6_plan& plan, int64_t slot_elems,

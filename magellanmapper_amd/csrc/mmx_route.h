@@ -28,7 +28,7 @@
 #define MMX_LDS_BYTES (64 * 1024)
 
 // ---------------------------------------------------------------------------------------------------- the request
-struct mmx_zx_request { int mode; bool y_valu, prepacked, edge_global; };
+struct mmx_zx_request { int mode; bool y_valu, prepacked, edge_global; int rows; };
 // zx_mode with its flags -> the mode and the flags; MMX_ERR_ARG for a value that names no kernel path
 inline int mmx_zx_parse(int zx_mode, mmx_zx_request* q)
 {
@@ -36,6 +36,8 @@ inline int mmx_zx_parse(int zx_mode, mmx_zx_request* q)
     if (q->y_valu) zx_mode &= ~MMX_ZX_Y_VALU;
     q->edge_global = zx_mode >= 0 && (zx_mode & MMX_ZX_EDGE_GLOBAL);
     if (q->edge_global) zx_mode &= ~MMX_ZX_EDGE_GLOBAL;
+    q->rows = zx_mode >= 0 ? (zx_mode & MMX_ZX_ROWS_MASK) >> MMX_ZX_ROWS_SHIFT : 0;
+    if (q->rows) zx_mode &= ~MMX_ZX_ROWS_MASK;
     q->prepacked = zx_mode == (MMX_ZX_TILED | MMX_ZX_PREPACKED) || zx_mode == (MMX_ZX_TILED_Q16 | MMX_ZX_PREPACKED);
     if (q->prepacked) zx_mode &= ~MMX_ZX_PREPACKED;
     q->mode = zx_mode;
@@ -231,6 +233,7 @@ struct mmx_route {
     bool makes_copy;            // tiled: this scale makes the voxel copy itself ...
     bool trusts_copy;           // ... or trusts the batch's (MMX_ZX_PREPACKED)
     bool edge_global;           // tiled: edge z tiles take their Z fragments from global memory (MMX_ZX_EDGE_GLOBAL)
+    int zx_rows;                // tiled: rows per wave of the Z+X row march (MMX_ZX_ROWS), 0 = chosen per block of the launch
     int y_kernel;               // mmx_route_y (fused families)
     bool ring_z, ring_y, ring_x;// separate: per pass, the register-ring kernel (else the generic one, or the folded one:)
     bool fold_z, fold_y, fold_x;// separate, MMX_ZX_THIN: per pass, the folded-reflection pass
@@ -293,6 +296,7 @@ inline int mmx_route_scale(const mmx_volume* vol, const mmx_batch_geom& g, int r
             r->trusts_copy = q.prepacked;
             r->makes_copy = !q.prepacked;
             r->edge_global = q.edge_global;
+            r->zx_rows = q.rows;
             r->path = q16 ? MMX_ZX_TILED_Q16 : MMX_ZX_TILED;
             r->layout = entries && g.quads_fit ? MMX_MASK_QUADS : 0;
             r->y_kernel = MMX_Y_Y6;

@@ -5,7 +5,8 @@
 
 ``--shape`` takes blocks that are not cubes through the same calls: a depth sweep at a constant voxel count (nz = 69,
 133, 261, 517 with 88, 44, 22, 11 blocks of ny = nx = 261) separates what a wave of the Z+X kernel pays once per march
-from what it pays per z tile (profiles/r14_zx_edge_steps.txt).
+from what it pays per z tile (profiles/r14_zx_edge_steps.txt).  ``MMX_FUSE=7`` runs the 16-bit tiles; ``MMX_ZX_ROWS=n`` forces n
+rows per wave of the Z+X row march (profiles/r20_zx_row_march.txt).
 """
 import argparse, ctypes, json, os, sys
 import numpy as np
@@ -65,7 +66,7 @@ for rep in range(a.reps + 1):
         nat.check(fn(ctypes.byref(v32), d_blocks.data_ptr(), blocks.ctypes.data, nb, slot,
                      nat.as_double_ptr(w0), nat.as_double_ptr(w2), R, s * s,
                      log_base + i * nb * slot * 4, ws.data_ptr(), *(() if a.generic else ((masks.data_ptr() + i * mask_words * 16) if a.mask else None, 0.1 - 2e-5, 2e-5,
-                                                    ctypes.byref(written), ((ZX if ZX in (6, 7) else 6) | 0x100 | (0x200 if os.environ.get('MMX_Y_VALU') == '1' else 0)) if packed else ZX, ctypes.byref(zxp))), stream), "log")
+                                                    ctypes.byref(written), ((ZX if ZX in (6, 7) else 6) | 0x100 | (0x200 if os.environ.get('MMX_Y_VALU') == '1' else 0) | nat.MMX_ZX_ROWS(os.environ.get('MMX_ZX_ROWS', 0))) if packed else ZX, ctypes.byref(zxp))), stream), "log")
         assert not a.mask or written.value in (1, 2)
         layout = written.value
         if rep >= 1:
