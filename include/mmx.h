@@ -345,7 +345,13 @@ int mmx_fold_parts(mmx_cand* d_cands, uint32_t cap, uint32_t* d_count, const mmx
  *                 mmx_fold_parts then rewrites the table into parent coordinates, and the probe expansion, the exact
  *                 re-score (vol_exact read with the parents' src_off and extents) and the host see the n_parents blocks
  *                 of d_parents / h_parents only.  Such a batch is not captured (mmx_detect_batch_capture:
- *                 MMX_ERR_UNSUPPORTED). */
+ *                 MMX_ERR_UNSUPPORTED).
+ *   d_block_f32 (appended likewise; NULL: store_f32 holds for the batch): a device flag per block, as
+ *                 mmx_preprocess_block_dtypes writes them -- preprocessed blocks of a float32 image are float32 or
+ *                 float64 block by block.  vol_exact must be the float64 copy (a float32 block holds its float32 values
+ *                 widened there); the exact re-score then keeps float32 intermediates for the flagged blocks and float64
+ *                 ones for the others (both instantiations are launched, each skips the other's blocks).  Not with
+ *                 parts (MMX_ERR_UNSUPPORTED). */
 typedef struct {
     const mmx_volume* vol32;
     const mmx_volume* vol_exact;
@@ -372,6 +378,7 @@ typedef struct {
     const mmx_block* d_parents;
     const mmx_block* h_parents;
     int32_t n_parts, n_parents;
+    const int32_t* d_block_f32;
 } mmx_detect_args;
 typedef struct {
     int32_t zx_path;        /* mmx_zx_mode the last scale ran */
@@ -540,6 +547,21 @@ int mmx_preprocess_batch_generic(const mmx_volume* vol, const mmx_subblock* d_su
                                  int64_t dst_sy, int64_t dst_sz, float* d_out32, double* d_out64,
                                  mmx_subblock_info* d_info, double* d_scratch, int64_t scratch_doubles,
                                  void* stream);
+
+/* float32 images (MMX_F32: mmx_preprocess_batch / _mode run one LDS kernel for it whatever the mode and need no d_work;
+ * mmx_preprocess_batch_generic its scratch-line kernel for sides up to 64, the one-output-per-lane kernel beyond) follow NumPy 2: np.percentile takes the difference of
+ * its two order statistics in float32 and returns float64, so a stretched tile is float64 from the clip on (each voxel
+ * widened, then the float64 stages); an identity tile (MMX_PP_IDENTITY) stays float32 through denoise_roi (float32 clip
+ * and unsharp mask, the blur's double accumulator stored as float32 after every axis pass).  The reference's merged
+ * block takes the dtype of its FIRST tile; this entry, queued behind the tiles of a batch, states it per block:
+ *   d_blocks / h_blocks : the blocks over d_out64 (src_off = the block's origin in d_out64)
+ *   d/h_first_tile      : per block the index of its first tile (origin 0, 0, 0) in the d_info the tiles wrote
+ *   d_flags             : [n_blocks] out: 1 = the reference's block is float32 (first tile an identity tile); d_out64 of
+ *                         such a block is rounded in place, (double)(float)v, and equals d_out32 widened; 0 = float64 */
+int mmx_preprocess_block_dtypes(const mmx_block* d_blocks, const mmx_block* h_blocks, int n_blocks,
+                                const int32_t* d_first_tile, const int32_t* h_first_tile, int n_subs,
+                                const mmx_subblock_info* d_info, int64_t dst_sy, int64_t dst_sz,
+                                double* d_out64, int64_t out64_elems, int32_t* d_flags, void* stream);
 
 /* ---- C1: intensity co-localisation: for every blob the mean of ONE image
  * channel over the voxels the blob owns

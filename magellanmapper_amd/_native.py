@@ -122,7 +122,7 @@ class DetectArgs(Structure):
                 ("stream", c_void_p), ("tail_stream", c_void_p), ("pack_stream", c_void_p),
                 ("ev_work_free", c_void_p), ("ev_work_read", c_void_p), ("ev_done", c_void_p),
                 ("d_parts", c_void_p), ("d_parents", c_void_p), ("h_parents", c_void_p),
-                ("n_parts", c_int32), ("n_parents", c_int32)]
+                ("n_parts", c_int32), ("n_parents", c_int32), ("d_block_f32", c_void_p)]
 
 
 class FinishStackArgs(Structure):
@@ -180,7 +180,7 @@ SYMBOLS = (
     "mmx_overlap_pairs", "mmx_close_pairs", "mmx_event_create", "mmx_event_destroy",
     "mmx_event_record", "mmx_event_elapsed_ms", "mmx_timing_enable", "mmx_timing_read",
     "mmx_calib_stream", "mmx_host_prune_axis",
-    "mmx_preprocess_fast_lds", "mmx_preprocess_batch", "mmx_preprocess_batch_mode", "mmx_preprocess_work_bytes", "mmx_preprocess_batch_generic",
+    "mmx_preprocess_fast_lds", "mmx_preprocess_batch", "mmx_preprocess_batch_mode", "mmx_preprocess_work_bytes", "mmx_preprocess_batch_generic", "mmx_preprocess_block_dtypes",
     "mmx_coloc_means", "mmx_coloc_voxels", "mmx_host_take_rows", "mmx_host_map_columns", "mmx_resize_batch_as", "mmx_gauss_axis_batch", "mmx_unmix_batch", "mmx_minmax_batch", "mmx_resize_batch",
     "mmx_cdist_f64", "mmx_host_lsap", "mmx_expand_probes", "mmx_fold_parts", "mmx_host_resolve_peaks", "mmx_host_overlap_prune",
     "mmx_host_emit_tables", "mmx_host_prune_region", "mmx_host_prune_parts", "mmx_host_rows_in_boxes", "mmx_host_append_rows", "mmx_host_emit_parts", "mmx_host_merge_parts_by_key", "mmx_host_gather_parts_by_key", "mmx_host_emit_tables_multi", "mmx_host_coloc_flags", "mmx_host_finish_stack", "mmx_copy_rect_h2d", "mmx_host_stage_upload", "mmx_host_stage_upload_pitched", "mmx_event_query",
@@ -268,6 +268,7 @@ def lib() -> ctypes.CDLL:
     L.mmx_preprocess_work_bytes.argtypes = [vp, c_int]
     L.mmx_preprocess_work_bytes.restype = c_int64
     L.mmx_preprocess_batch_generic.argtypes = pre_args + [vp, c_int64, vp]
+    L.mmx_preprocess_block_dtypes.argtypes = [vp, vp, c_int, vp, vp, c_int, vp, c_int64, c_int64, vp, c_int64, vp, vp]
     L.mmx_minmax_batch.argtypes = [POINTER(Volume), vp, vp, c_int, vp, vp]
     L.mmx_minmax_batch.restype = c_int
     L.mmx_resize_batch.argtypes = [POINTER(Volume), vp, vp, c_int, vp, vp, vp, c_int64, c_int64, c_int64,
@@ -333,6 +334,7 @@ def lib() -> ctypes.CDLL:
     L.mmx_preprocess_batch.restype = c_int
     L.mmx_preprocess_batch_mode.restype = c_int
     L.mmx_preprocess_batch_generic.restype = c_int
+    L.mmx_preprocess_block_dtypes.restype = c_int
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name in ("mmx_preprocess_fast_lds", "mmx_workspace_bytes", "mmx_preprocess_work_bytes",

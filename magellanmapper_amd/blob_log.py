@@ -739,6 +739,7 @@ class _Batch:
     d_parts: Optional["torch.Tensor"] = None
     n_part_vox: int = 0
     zx_mode: Optional[int] = None       # the mode its plan asks for (`PlannedBatch.zx_mode`)
+    block_f32: object = None            # `_Voxels.block_f32`, alive until the batch is finished
 
     @property
     def table_blocks(self) -> np.ndarray:
@@ -768,6 +769,7 @@ class _Voxels:
     vol32: object               # the ``mmx_volume`` records the passes / the exact re-score read
     vol_exact: object
     store_f32: int
+    block_f32: object = None    # preprocessed blocks of a float32 image: the device flag per block (1 = a float32 block)
 
 
 def _preprocess(dvol, lane: "Lane", origins, shapes, bufs: _Buffers, which: int, boxes, pipe: Optional[_Pipelined]):
@@ -807,6 +809,7 @@ def _batch_voxels(dvol, lane: "Lane", origins, shapes, bufs: _Buffers, which: in
     boxes = ([(int(o[0]), int(o[0]) + int(s_[0]), int(o[1]), int(o[1]) + int(s_[1])) for o, s_ in zip(origins, shapes)]
              if dvol._upload is not None else None)
     d_blocks = None
+    block_f32 = None
     if pre is None:
         if dvol._upload is not None:
             dvol.stream_wait(None, [torch.cuda.current_stream(), bufs.pack_stream, bufs.rescore_stream, bufs.side], boxes)
@@ -820,6 +823,8 @@ def _batch_voxels(dvol, lane: "Lane", origins, shapes, bufs: _Buffers, which: in
     else:
         blocks, slot, vol32, vol_exact = _preprocess(dvol, lane, origins, shapes, bufs, which, boxes, pipe)
         store_f32 = int(getattr(pre, "store_f32", 0))
+        # a float32 image (preprocess.FLOAT32_RULES): float32 and float64 blocks in one batch, told apart on the device
+        block_f32 = getattr(pre, "block_flags", None)
         # (a block in parts was preprocessed whole, tile by tile as ever: its parts are boxes of that slot -- same
         #  strides -- and the exact re-score reads the slot with the parent's extent)
         strides = (vol32.stride_z, vol32.stride_y, vol32.stride_x)
@@ -827,7 +832,7 @@ def _batch_voxels(dvol, lane: "Lane", origins, shapes, bufs: _Buffers, which: in
     if split is not None:
         parents = blocks
         blocks, slot = split.block_records(parents["src_off"][0], strides)
-    return _Voxels(blocks, slot, d_blocks, parents, vol32, vol_exact, store_f32)
+    return _Voxels(blocks, slot, d_blocks, parents, vol32, vol_exact, store_f32, block_f32)
 
 
 def _detect_args(lane: "Lane", vox: _Voxels, bufs: _Buffers, which: int, ws, ws_i: int, cap: int, eps: float, exact: bool,
@@ -851,6 +856,8 @@ def _detect_args(lane: "Lane", vox: _Voxels, bufs: _Buffers, which: int, ws, ws_
         a.h_cands, a.h_prefix = bufs.host_table(which).data_ptr(), min(cap, _PREFIX_ENTRIES)
     a.zx_mode = ZX_MODE if (zx_mode is None or ZX_MODE != nat.MMX_ZX_AUTO) else zx_mode
     a.zx_flags, a.store_f32, a.exact, a.expand = ZX_FLAGS, vox.store_f32, int(exact), int(native)
+    if vox.block_f32 is not None:
+        a.d_block_f32 = vox.block_f32.data_ptr()
     a.stream = a.pack_stream = stream
     a.tail_stream = bufs.rescore_stream.cuda_stream if side_tail else stream      # (the library forks and joins it)
     # (the last reader of this workspace; also a batch that is nominated again, on the main stream: same workspace)
@@ -903,6 +910,10 @@ def _enqueue_detect(dvol, lane: "Lane", origins, shapes, bufs: _Buffers, which: 
     if cap is None:
         cap = max(4096, min(n_part_vox * ns, n_part_vox // 2000 * ns + 65536))
     native = bool(exact and HOST_PATH == "native")
+    if vox.block_f32 is not None and (not native or split is not None):
+        # (the store type per block exists in mmx_detect_batch's exact re-score of every candidate alone)
+        raise NotImplementedError("preprocessed blocks of a float32 image are detected with exact values and the native "
+                                  "host path only (blob_log.HOST_PATH = \"native\"), and never in parts")
     a = _detect_args(lane, vox, bufs, which, ws, ws_i, cap, eps, exact, native, side_tail, zx_mode)
     ev_read, ev_done = bufs.events(which)
     d_parents = d_parts = None
@@ -934,7 +945,7 @@ def _enqueue_detect(dvol, lane: "Lane", origins, shapes, bufs: _Buffers, which: 
     return _Batch(lane=lane, origins=origins, shapes=shapes, blocks=blocks, d_blocks=vox.d_blocks, nb=nb, ns=ns, n_vox=n_vox,
                   cap=cap, which=which, done=ev_done, store_f32=vox.store_f32, vol_exact=vox.vol_exact, eps=eps, exact=exact,
                   native=native, split=split, parents=vox.parents, d_parents=d_parents, d_parts=d_parts,
-                  n_part_vox=n_part_vox, zx_mode=zx_mode)
+                  n_part_vox=n_part_vox, zx_mode=zx_mode, block_f32=vox.block_f32)
 
 
 def _launch_batch(L, a, info, bufs: _Buffers, nb: int, blocks, space, vol32, vol_exact, ev_read) -> int:

@@ -113,6 +113,13 @@ void mmx_batch_geom_make(const mmx_volume* vol, const mmx_block* h_blocks, int n
 // The NMS entry layouts and the rule that decides an entry (host: the index arithmetic; device: the rule)
 #include "mmx_entries.h"
 
+// mmx_rescore.hip (internal; mmx_detect_batch calls it): mmx_rescore_f64 with the store type chosen per block.
+//   d_block_f32 == NULL : every block alike, float32 intermediates where store_f32 is set and the voxels are float32
+//   d_block_f32 != NULL : a device flag per block over a float64 volume (store_f32 is not read)
+int mmx_rescore_per_block(const mmx_volume* vol, const mmx_block* d_blocks, int n_blocks, mmx_cand* d_pts, uint32_t cap,
+                          const uint32_t* d_count, const double* d_w0, const double* d_w2, const int32_t* h_radius,
+                          const double* h_norm, int n_sigma, int store_f32, const int32_t* d_block_f32, void* stream);
+
 // The kernel-path rules: the launchers' predicates, the route of a scale and of a ladder (host-only, no launch)
 #include "mmx_route.h"
 

@@ -190,6 +190,11 @@ int mmx_detect_batch(const mmx_detect_args* a, mmx_detect_info* info)
         if (rc != MMX_OK) return rc;
     }
     if (a->exact) {
+        if (a->d_block_f32) {            // preprocessed blocks of a float32 image: the store type block by block
+            if (parts) return MMX_ERR_UNSUPPORTED;
+            rc = mmx_rescore_per_block(a->vol_exact, d_tail_blocks, n_tail_blocks, a->d_cands, a->cap, a->d_count, a->d_w0,
+                                       a->d_w2, a->h_radius, a->h_norm, ns, 0, a->d_block_f32, (void*)tail);
+        } else
         rc = mmx_rescore_f64(a->vol_exact, d_tail_blocks, n_tail_blocks, a->d_cands, a->cap, a->d_count, a->d_w0, a->d_w2,
                              a->h_radius, a->h_norm, ns, a->store_f32, (void*)tail);
         if (rc != MMX_OK) return rc;

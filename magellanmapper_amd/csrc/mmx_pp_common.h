@@ -56,6 +56,31 @@ __device__ __forceinline__ double pp_lerp(int a, int b, double t)
     if (t >= 0.5) r = (double)b - d * (1.0 - t);
     return r;
 }
+// float32 images under NumPy 2: subtract(b, a) of the two float32 order statistics is a float32 difference (one
+// rounding); gamma is float64, so the product and the sum are float64 operations on the widened values
+__device__ __forceinline__ double pp_lerp(float a, float b, double t)
+{
+    const double d = (double)(b - a);
+    double r = (double)a + d * t;
+    if (t >= 0.5) r = (double)b - d * (1.0 - t);
+    return r;
+}
+
+// ---- identity tiles of a float32 image (vmin == vmax: saturate_roi hands the float32 view on and denoise_roi stays in
+// float32).  The working copy holds the float32 values widened to double; every stage rounds to float32 where NumPy /
+// SciPy store one: np.clip against the float32 casts of the Python bounds, correlate1d's double accumulator stored
+// into a float32 array after each axis pass (pp_round32), the unsharp mask's three float32 operations.
+__device__ __forceinline__ double pp_round32(double v) { return (double)(float)v; }
+__device__ __forceinline__ double pp_clip32(double x, double lo, double hi)
+{
+    return (double)fminf(fmaxf((float)x, (float)lo), (float)hi);
+}
+__device__ __forceinline__ double pp_unsharp32(double den, double blur, double strength)
+{
+    const float m = (float)strength * (float)blur;
+    const float hp = (float)den - m;
+    return (double)((float)den + hp);
+}
 
 // saturate_roi's stretch (clip(x, vmin, vmax) - vmin) / span.  The division is IEEE-exact: it is the
 // compiler's own float64 expansion (v_div_scale / v_rcp + 2 Newton steps / q = n*r; e = fma(-d, q, n);

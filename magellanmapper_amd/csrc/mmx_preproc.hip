@@ -448,21 +448,25 @@ pp_generic_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t s
     const InT* src = vol + sb.src_off;
     double* bufA = scratch + sb.scratch_off;
     double* bufB = bufA + n;
-    constexpr bool F64 = std::is_same<InT, double>::value;
+    constexpr bool F32 = std::is_same<InT, float>::value;
+    constexpr bool FLT = std::is_same<InT, double>::value || F32;      // float voxels: the select on the values' keys
     auto raw = [&](int64_t i) {
         const int64_t t = i / nx, x = i - t * nx, z = t / ny, y = t - z * ny;
-        if constexpr (F64) return (double)src[z * sz + y * sy + x * sx];
+        if constexpr (FLT) return (double)src[z * sz + y * sy + x * sx];
         else return (int)src[z * sz + y * sy + x * sx];
     };
     const mmx_quantile_class qc = qcs[sb.qclass];
     pp_bounds B;
-    if constexpr (F64) {
+    if constexpr (FLT) {
         // float64 voxels: an eight-level radix select on the order-preserving key of the doubles (mmx_key; no NaNs on
         // this path), the four ranks side by side -- one 256-bin histogram each per level, counted over the voxels
-        // that share the rank's prefix so far
+        // that share the rank's prefix so far.  float32 voxels: the same over the four bytes of the float's key (the
+        // working copy holds the floats widened, so the narrowing is exact)
         __shared__ unsigned long long s_pre[4];
+        constexpr int top = mmx_key<InT>::levels - 1;
         auto key = [](double v) {
-            return mmx_key<double>::flip((unsigned long long)__double_as_longlong(v + 0.0));     // (-0.0 sorts as +0.0)
+            if constexpr (F32) return (unsigned long long)mmx_key<float>::flip(__float_as_uint((float)v + 0.0f));
+            else return mmx_key<double>::flip((unsigned long long)__double_as_longlong(v + 0.0));     // (-0.0 sorts as +0.0)
         };
         for (int64_t i = tid; i < n; i += PP_WG_GENERIC) bufA[i] = raw(i);
         if (tid < 4) {
@@ -470,14 +474,14 @@ pp_generic_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t s
             s_ranks.res[tid] = tid == 0 ? qc.lo_prev : tid == 1 ? qc.lo_next : tid == 2 ? qc.hi_prev : qc.hi_next;
         }
         __syncthreads();
-        for (int level = 7; level >= 0; --level) {
+        for (int level = top; level >= 0; --level) {
             for (int i = tid; i < PP_HIST; i += PP_WG_GENERIC) hist[i] = 0;
             __syncthreads();
             const unsigned long long p0 = s_pre[0], p1 = s_pre[1], p2 = s_pre[2], p3 = s_pre[3];
             const int sh = 8 * level;
             for (int64_t i = tid; i < n; i += PP_WG_GENERIC) {
                 const unsigned long long k = key(bufA[i]);
-                const unsigned long long up = level == 7 ? 0ull : k >> (sh + 8);
+                const unsigned long long up = level == top ? 0ull : k >> (sh + 8);
                 const unsigned b8 = (unsigned)(k >> sh) & 255u;
                 if (up == p0) atomicAdd(&hist[256 + b8], 1u);
                 if (up == p1) atomicAdd(&hist[512 + b8], 1u);
@@ -492,7 +496,8 @@ pp_generic_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t s
             }
             __syncthreads();
         }
-        auto q = [&](int w) { return mmx_key<double>::value(s_pre[w]); };
+        // (the lerp of the type: float32 order statistics take their difference in float32)
+        auto q = [&](int w) { return (InT)mmx_key<InT>::value(s_pre[w]); };
         B = pp_make_bounds(pp_lerp(q(0), q(1), qc.lo_gamma), pp_lerp(q(2), q(3), qc.hi_gamma), A.max_thresh);
     } else {
         for (int i = tid; i < PP_HIST; i += PP_WG_GENERIC) hist[i] = 0;
@@ -518,12 +523,15 @@ pp_generic_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t s
 
     // (an identity tile -- vmin == vmax: the reference leaves the voxels alone -- of a float64 image may hold negative
     //  values, which the vmin = 0 stand-in of pp_sat_t would clip)
-    auto sat = [&](double v) { return (F64 && S.identity) ? v : S.plain(v); };
+    auto sat = [&](double v) { return (FLT && S.identity) ? v : S.plain(v); };
+    // an identity tile of a float32 image stays float32 through denoise_roi (pp_clip32, pp_round32, pp_unsharp32)
+    const bool id32 = F32 && S.identity;
+    auto clip = [&](double s) { return id32 ? pp_clip32(s, A.clip_min, A.clip_max) : pp_clip(s, A.clip_min, A.clip_max); };
     double part = 0.;
     for (int64_t i = tid; i < n; i += PP_WG_GENERIC) {
         const double s = sat(bufA[i]);
         part += s;
-        bufA[i] = pp_clip(s, A.clip_min, A.clip_max);
+        bufA[i] = clip(s);
     }
     part = pp_wave_sum(part);
     if (lane == 0) s_red[wave] = part;
@@ -651,7 +659,7 @@ pp_generic_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t s
                     const int64_t b = c + k > L - 1 ? L - 1 : c + k;
                     acc += (line[a * stride] + line[b * stride]) * wts[k];
                 }
-                dstb[i] = acc;
+                dstb[i] = id32 ? pp_round32(acc) : acc;
             }
             __syncthreads();
             cur = dstb;
@@ -665,9 +673,8 @@ pp_generic_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t s
         const int64_t t = i / nx, x = i - t * nx, z = t / ny, y = t - z * ny;
         double o;
         if (A.do_unsharp) {
-            const double den = tv ? den_buf[i]
-                                  : pp_clip(sat((double)raw(i)), A.clip_min, A.clip_max);
-            o = pp_unsharp(den, cur[i], A.strength);
+            const double den = tv ? den_buf[i] : clip(sat((double)raw(i)));
+            o = id32 ? pp_unsharp32(den, cur[i], A.strength) : pp_unsharp(den, cur[i], A.strength);
         } else {
             o = cur[i];
         }
@@ -683,6 +690,202 @@ pp_generic_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t s
     }
 }
 
+// ---- float32 voxels (NumPy 2's rules, pp_generic_kernel), tiles with every side <= MAXL: the register-line forms.
+//   LDS = true   the working copy is the float64 tile in LDS, as in pp_fast_kernel: the stock 25^3 tile's 122 KiB.  A
+//                32-bit copy of the voxels does not fit beside it (pp_fast_kernel keeps a 16-bit one), so it is organised
+//                differently: the raw values sit in the tile itself through the four-level select, and the unsharp stage
+//                (and a knife-edge mean) read the voxels from the image again -- the second read of a tile a workgroup
+//                has just streamed, an L2 hit.  Every mode of mmx_preprocess_batch_mode runs this one kernel for float32.
+//   LDS = false  the working copy is the tile's global scratch (pp_mid_kernel's tiles: sides up to 64), lines straight
+//                from the scratch.
+// Arithmetic: pp_generic_kernel<float>'s, statement by statement (plain division, pp_clip32 / pp_round32 / pp_unsharp32
+// on an identity tile), with the blur as pp_line_pass; the sum behind the mean is taken in another order, which the
+// knife-edge replay in NumPy's order makes immaterial (an identity tile has none, as everywhere).
+template <int WG, int MAXL, bool LDS>
+__global__ void __launch_bounds__(WG)
+pp_f32_kernel(const float* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
+              const mmx_subblock* __restrict__ subs, int n_subs,
+              const mmx_quantile_class* __restrict__ qcs, const double* __restrict__ wts,
+              pp_args A, float* __restrict__ out32, double* __restrict__ out64,
+              mmx_subblock_info* __restrict__ info, double* __restrict__ scratch)
+{
+    extern __shared__ double tile_lds[];
+    __shared__ uint32_t hist[PP_HIST];
+    __shared__ unsigned long long s_pre[4];
+    __shared__ pp_ranks s_ranks;
+    __shared__ double s_red[WG / 64];
+    __shared__ double s_mean;
+    __shared__ int s_flags;
+    __shared__ pp_stack s_stack;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int sub_id = blockIdx.x;
+    if (LDS) {                                    // (8 XCD-contiguous runs of tiles, as pp_fast_kernel)
+        const int per = (n_subs + 7) >> 3;
+        sub_id = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
+    }
+    if (sub_id >= n_subs) return;
+    const mmx_subblock sb = subs[sub_id];
+    const int nz = sb.nz, ny = sb.ny, nx = sb.nx, n = nz * ny * nx, nrows = nz * ny;
+    const int px = LDS ? (nx | 1) : nx;
+    double* __restrict__ t = LDS ? tile_lds : scratch + sb.scratch_off;
+    const float* src = vol + sb.src_off;
+    const float inv_nx = 1.0f / (float)nx, inv_ny = 1.0f / (float)ny;
+    // a lane keeps its x and walks rows (z * ny + y) in steps of rpi (rows < 4096: the float reciprocals are exact)
+    const int rpi = WG / nx;
+    const int r_first = (int)(((float)tid + 0.5f) * inv_nx);
+    const int x = tid - r_first * nx;
+    const int r0 = r_first < rpi ? r_first : nrows;
+    auto raw_at = [&](int row) {
+        const int z = (int)(((float)row + 0.5f) * inv_ny);
+        const int y = row - z * ny;
+        return (double)src[z * sz + y * sy + x * sx];
+    };
+
+    // 1. voxels -> the working copy, widened
+    for (int row = r0; row < nrows; row += rpi) t[row * px + x] = raw_at(row);
+    if (tid < 4) {
+        const mmx_quantile_class q0 = qcs[sb.qclass];
+        s_pre[tid] = 0ull;
+        s_ranks.res[tid] = tid == 0 ? q0.lo_prev : tid == 1 ? q0.lo_next : tid == 2 ? q0.hi_prev : q0.hi_next;
+    }
+    __syncthreads();
+
+    // 2. the four order statistics: a four-level radix select on the floats' keys (-0.0 sorts as +0.0), the four ranks
+    //    side by side
+    const mmx_quantile_class qc = qcs[sb.qclass];
+    for (int level = 3; level >= 0; --level) {
+        for (int i = tid; i < PP_HIST; i += WG) hist[i] = 0;
+        __syncthreads();
+        const uint32_t p0 = (uint32_t)s_pre[0], p1 = (uint32_t)s_pre[1], p2 = (uint32_t)s_pre[2], p3 = (uint32_t)s_pre[3];
+        const int sh = 8 * level;
+        for (int row = r0; row < nrows; row += rpi) {
+            const uint32_t k = mmx_key<float>::flip(__float_as_uint((float)t[row * px + x] + 0.0f));
+            const uint32_t up = level == 3 ? 0u : k >> (sh + 8);
+            const unsigned b8 = (k >> sh) & 255u;
+            if (up == p0) atomicAdd(&hist[256 + b8], 1u);
+            if (up == p1) atomicAdd(&hist[512 + b8], 1u);
+            if (up == p2) atomicAdd(&hist[768 + b8], 1u);
+            if (up == p3) atomicAdd(&hist[1024 + b8], 1u);
+        }
+        __syncthreads();
+        if (wave < 4) {
+            int b; uint32_t r;
+            pp_select(hist + 256 * (1 + wave), s_ranks.res[wave], b, r);
+            if (lane == 0) { s_pre[wave] = (s_pre[wave] << 8) | (unsigned long long)b; s_ranks.res[wave] = r; }
+        }
+        __syncthreads();
+    }
+    auto q = [&](int w) { return (float)mmx_key<float>::value(s_pre[w]); };
+    const pp_bounds B = pp_make_bounds(pp_lerp(q(0), q(1), qc.lo_gamma), pp_lerp(q(2), q(3), qc.hi_gamma), A.max_thresh);
+    const auto S = pp_sat_t<false>::make(B.vmin, B.vmax, B.identity);
+    const bool id32 = S.identity;                       // the tile stays float32 through denoise_roi
+    auto sat = [&](double v) { return id32 ? v : S.plain(v); };
+    auto clip = [&](double s) { return id32 ? pp_clip32(s, A.clip_min, A.clip_max) : pp_clip(s, A.clip_min, A.clip_max); };
+
+    // 3. saturate, sum, clip in place
+    double part = 0.;
+    for (int row = r0; row < nrows; row += rpi) {
+        const double s = sat(t[row * px + x]);
+        part += s;
+        t[row * px + x] = clip(s);
+    }
+    part = pp_wave_sum(part);
+    if (lane == 0) s_red[wave] = part;
+    __syncthreads();
+    if (tid == 0) {
+        double tot = 0.;
+        for (int w = 0; w < WG / 64; ++w) tot += s_red[w];
+        double mean = tot / (double)n;
+        s_flags = pp_mean_verdict(mean, S.identity, A, [&](double& m) {
+            auto val = [&](int i) {
+                const int tt = i / nx, xx = i - tt * nx, z = tt / ny, y = tt - z * ny;
+                return sat((double)src[z * sz + y * sy + xx * sx]);
+            };
+            m = pp_pairwise(val, n, &s_stack) / (double)n;
+            return pp_exact_verdict(m, A);
+        });
+        s_mean = mean;
+    }
+    __syncthreads();
+    const int flags = s_flags;
+    if (info && tid == 0) pp_write_info(info, sub_id, B.vmin, B.vmax, s_mean, flags);
+
+    // 4. Gaussian blur, axis 0, 1, 2 in place; an identity tile stores float32 after every axis pass
+    if (A.do_unsharp) {
+        double wl[PP_R + 1];
+#pragma unroll
+        for (int k = 0; k <= PP_R; ++k) wl[k] = wts[k];
+#pragma unroll 1
+        for (int axis = 0; axis < 3; ++axis) {
+            const int L = axis == 0 ? nz : axis == 1 ? ny : nx;
+            if (axis == 2 && A.rgb_guess && nx == 3) break;
+            const int nlines = n / L;
+            for (int l = tid; l < nlines; l += WG) {
+                int base, stride;
+                if (axis == 2) { base = l * px; stride = 1; }
+                else {
+                    const int tt = (int)(((float)l + 0.5f) * inv_nx);
+                    const int xx = l - tt * nx;
+                    if (axis == 0) { base = tt * px + xx; stride = ny * px; }
+                    else { base = tt * ny * px + xx; stride = px; }
+                }
+                pp_line_pass<MAXL>(t, base, stride, L, wl);
+            }
+            __syncthreads();
+            if (id32) {
+                for (int row = r0; row < nrows; row += rpi) t[row * px + x] = pp_round32(t[row * px + x]);
+                __syncthreads();
+            }
+        }
+    }
+
+    // 5. unsharp mask on the voxels read again (+ erosion), write out
+    const bool erode = flags & MMX_PP_ERODED;
+    for (int row = r0; row < nrows; row += rpi) {
+        double o = t[row * px + x];
+        if (A.do_unsharp) {
+            const double den = clip(sat(raw_at(row)));
+            o = id32 ? pp_unsharp32(den, o, A.strength) : pp_unsharp(den, o, A.strength);
+        }
+        if (erode) t[row * px + x] = o;
+        else {
+            const int z = (int)(((float)row + 0.5f) * inv_ny);
+            const int y = row - z * ny;
+            pp_put(out64, out32, sb.dst_off + z * A.dst_sz + y * A.dst_sy + x, o);
+        }
+    }
+    if (!erode) return;
+    __syncthreads();
+    for (int row = r0; row < nrows; row += rpi) {
+        const int z = (int)(((float)row + 0.5f) * inv_ny);
+        const int y = row - z * ny;
+        const double o = pp_erode7(t, row * px + x, px, ny * px, x > 0, x < nx - 1, y > 0, y < ny - 1, z > 0, z < nz - 1);
+        pp_put(out64, out32, sb.dst_off + z * A.dst_sz + y * A.dst_sy + x, o);
+    }
+}
+
+// ---- float32 images: the dtype of the reference's merged block.  Its tile loop allocates the block from the FIRST
+// tile's dtype (stack_detect.py: merged = np.zeros(shape, dtype=piece.dtype)): an identity first tile makes a float32
+// block, into which every float64 piece is rounded.  Tiles run in different workgroups, so this pass follows them: it
+// reads the first tile's record, states the block's flag and rounds out64 of a flagged block in place (out32 already
+// is that rounding; a float32 piece of a float64 block widened exactly when it was stored).
+__global__ void __launch_bounds__(256)
+pp_block_dtype_kernel(const mmx_block* __restrict__ blocks, const int32_t* __restrict__ first_tile,
+                      const mmx_subblock_info* __restrict__ info, int64_t dst_sy, int64_t dst_sz,
+                      double* __restrict__ out64, int32_t* __restrict__ flags)
+{
+    const mmx_block b = blocks[blockIdx.y];
+    const int f32 = (info[first_tile[blockIdx.y]].flags & MMX_PP_IDENTITY) ? 1 : 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) flags[blockIdx.y] = f32;
+    if (!f32) return;
+    const int64_t rows = (int64_t)b.nz * b.ny;
+    for (int64_t r = blockIdx.x; r < rows; r += gridDim.x) {
+        const int64_t z = r / b.ny, y = r - z * b.ny;
+        double* row = out64 + b.src_off + z * dst_sz + y * dst_sy;
+        for (int x = threadIdx.x; x < b.nx; x += 256) row[x] = pp_round32(row[x]);
+    }
+}
 
 }  // namespace
 
@@ -705,8 +908,8 @@ static int pp_check(const mmx_volume* vol, const mmx_subblock* d_subs, const mmx
         !d_out32 || !d_out64)
         return MMX_ERR_ARG;
     if (p->radius != PP_R) return MMX_ERR_UNSUPPORTED;
-    // (float64 images: the one-output-per-lane kernel of the generic entry only; float32 images compute in float32 in
-    //  the reference -- another arithmetic, not built)
+    // (float64 and float32 images: the one-output-per-lane kernel of the generic entry only; float32 images under the
+    //  casting rules of NumPy 2, which the caller opts into -- mmx_voxel.h)
     if (!mmx_voxel_in(vol->dtype, MMX_VOX_PREPROC)) return MMX_ERR_UNSUPPORTED;
     for (int i = 0; i < n_subs; ++i) {
         const mmx_subblock& b = h_subs[i];
@@ -733,7 +936,8 @@ int mmx_preprocess_batch_mode(const mmx_volume* vol, const mmx_subblock* d_subs,
     if (st != MMX_OK) return st;
     if (mode != MMX_PP_AUTO && mode != MMX_PP_SINGLE && mode != MMX_PP_PIPELINED) return MMX_ERR_ARG;
     if (params->tv_weight != 0.0) return MMX_ERR_UNSUPPORTED;      // total-variation denoising: the generic entry
-    if (!mmx_voxel_in(vol->dtype, MMX_VOX_INTEGER)) return MMX_ERR_UNSUPPORTED;    // float64 voxels: the generic entry
+    // (float64 voxels: the generic entry; float32 voxels: one LDS kernel of their own, whatever the mode)
+    if (!mmx_voxel_in(vol->dtype, MMX_VOX_INTEGER) && vol->dtype != MMX_F32) return MMX_ERR_UNSUPPORTED;
     if (n_subs == 0) return MMX_OK;
     int64_t lds = 0;
     for (int i = 0; i < n_subs; ++i) {
@@ -751,6 +955,20 @@ int mmx_preprocess_batch_mode(const mmx_volume* vol, const mmx_subblock* d_subs,
         max_vox = std::max<int64_t>(max_vox, (int64_t)h_subs[i].nz * h_subs[i].ny * h_subs[i].nx);
     const bool small = max_vox <= 4096;
     mmx_timed_scope ts(MMX_K_PREPROC, s);
+    if (vol->dtype == MMX_F32) {
+        int64_t tile_bytes = 0;
+        for (int i = 0; i < n_subs; ++i)
+            tile_bytes = std::max<int64_t>(tile_bytes, (int64_t)h_subs[i].nz * h_subs[i].ny * (h_subs[i].nx | 1) * (int64_t)sizeof(double));
+        auto launch = [&](auto k, int wg) {
+            if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_bytes) != hipSuccess)
+                return MMX_ERR_HIP;
+            hipLaunchKernelGGL(k, dim3(grid), dim3(wg), (size_t)tile_bytes, s, (const float*)vol->d_data, vol->stride_z,
+                               vol->stride_y, vol->stride_x, d_subs, n_subs, d_qclasses, d_weights, A,
+                               d_out32, d_out64, d_info, (double*)nullptr);
+            return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
+        };
+        return small ? launch(pp_f32_kernel<256, PP_MAXL, true>, 256) : launch(pp_f32_kernel<PP_WG, PP_MAXL, true>, PP_WG);
+    }
     // tiles that fill a CU's LDS one at a time: statistics kernel + pipelined blur kernel (mmx_preproc_pipe.hip)
     if (mode == MMX_PP_PIPELINED || (mode == MMX_PP_AUTO && !small)) {
         const int64_t need = mmx_pp_pipe_work_bytes(h_subs, n_subs);
@@ -808,6 +1026,8 @@ int mmx_preprocess_batch_generic(const mmx_volume* vol, const mmx_subblock* d_su
     if (st != MMX_OK) return st;
     if (n_subs == 0) return MMX_OK;
     if (!d_scratch) return MMX_ERR_ARG;
+    // (total-variation denoising of a float32 identity tile would iterate in float32: not built)
+    if (params->tv_weight != 0.0 && vol->dtype == MMX_F32) return MMX_ERR_UNSUPPORTED;
     for (int i = 0; i < n_subs; ++i) {
         const mmx_subblock& b = h_subs[i];
         const int64_t n = (int64_t)b.nz * b.ny * b.nx;
@@ -819,12 +1039,19 @@ int mmx_preprocess_batch_generic(const mmx_volume* vol, const mmx_subblock* d_su
     hipStream_t s = (hipStream_t)stream;
     mmx_timed_scope ts(MMX_K_PREPROC, s);
     // every side <= 64: register-resident lines over the scratch (pp_mid_kernel); else one output per lane
-    bool mid = params->tv_weight == 0.0 && mmx_voxel_in(vol->dtype, MMX_VOX_INTEGER);   // (the iteration, and float64 voxels, live in the one-output-per-lane kernel only)
+    // (the iteration, and float64 voxels, live in the one-output-per-lane kernel only)
+    bool mid = params->tv_weight == 0.0 && (mmx_voxel_in(vol->dtype, MMX_VOX_INTEGER) || vol->dtype == MMX_F32);
     int max_nx = 1;
     for (int i = 0; i < n_subs; ++i) {
         const mmx_subblock& b = h_subs[i];
         if (b.nz > PP_MIDL || b.ny > PP_MIDL || b.nx > PP_MIDL || (int64_t)b.nz * b.ny * b.nx >= (1ll << 30)) mid = false;
         max_nx = b.nx > max_nx ? b.nx : max_nx;
+    }
+    if (mid && vol->dtype == MMX_F32) {
+        hipLaunchKernelGGL((pp_f32_kernel<PP_WG_MID, PP_MIDL, false>), dim3(n_subs), dim3(PP_WG_MID), 0, s,
+                           (const float*)vol->d_data, vol->stride_z, vol->stride_y, vol->stride_x, d_subs, n_subs,
+                           d_qclasses, d_weights, A, d_out32, d_out64, d_info, d_scratch);
+        return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
     }
     if (mid) {
         const size_t lds = (size_t)PP_MID_ROWS * (max_nx | 1) * sizeof(double);
@@ -846,6 +1073,34 @@ int mmx_preprocess_batch_generic(const mmx_volume* vol, const mmx_subblock* d_su
                            d_qclasses, d_weights, A, d_out32, d_out64, d_info, d_scratch);
         return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
     });
+}
+
+int mmx_preprocess_block_dtypes(const mmx_block* d_blocks, const mmx_block* h_blocks, int n_blocks,
+                                const int32_t* d_first_tile, const int32_t* h_first_tile, int n_subs,
+                                const mmx_subblock_info* d_info, int64_t dst_sy, int64_t dst_sz,
+                                double* d_out64, int64_t out64_elems, int32_t* d_flags, void* stream)
+{
+    if (!d_blocks || !h_blocks || n_blocks < 0 || !d_first_tile || !h_first_tile || !d_info || !d_out64 || !d_flags ||
+        dst_sy < 1 || dst_sz < dst_sy)
+        return MMX_ERR_ARG;
+    if (n_blocks > MMX_MAX_BLOCKS) return MMX_ERR_UNSUPPORTED;
+    int64_t max_rows = 1;
+    for (int i = 0; i < n_blocks; ++i) {
+        const mmx_block& b = h_blocks[i];
+        if (b.nz < 1 || b.ny < 1 || b.nx < 1 || b.src_off < 0 || b.nx > dst_sy || (int64_t)b.ny * dst_sy > dst_sz ||
+            h_first_tile[i] < 0 || h_first_tile[i] >= n_subs)
+            return MMX_ERR_ARG;
+        if (b.src_off + (b.nz - 1) * dst_sz + (b.ny - 1) * dst_sy + b.nx > out64_elems) return MMX_ERR_WORKSPACE;
+        max_rows = std::max<int64_t>(max_rows, (int64_t)b.nz * b.ny);
+    }
+    if (n_blocks == 0) return MMX_OK;
+    hipStream_t s = (hipStream_t)stream;
+    mmx_timed_scope ts(MMX_K_PREPROC, s);
+    // (a wave stores half a row of a stock block: rows over grid.x, up to 1 024 workgroups a block)
+    const int gx = (int)std::min<int64_t>(max_rows, 1024);
+    hipLaunchKernelGGL(pp_block_dtype_kernel, dim3(gx, n_blocks), dim3(256), 0, s, d_blocks, d_first_tile, d_info,
+                       dst_sy, dst_sz, d_out64, d_flags);
+    return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
 }
 
 }  // extern "C"

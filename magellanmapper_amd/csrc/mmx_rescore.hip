@@ -169,12 +169,16 @@ __device__ __forceinline__ void z_phase(const InT* __restrict__ in, int nyb, int
     }
 }
 
-template <typename InT, typename StoreT>
+// PER_BLOCK (preprocessed blocks of a float32 image: float32 or float64 block by block): `block_f32` holds a flag per
+// block and this launch takes the points of the blocks whose flag equals `want` alone; the other instantiation, launched
+// beside it, takes the rest.
+template <typename InT, typename StoreT, bool PER_BLOCK = false>
 __global__ void __launch_bounds__(MMX_WG)
 rescore_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
                const mmx_block* __restrict__ blocks, mmx_cand* __restrict__ pts, uint32_t cap,
                const uint32_t* __restrict__ count, const double* __restrict__ w0_tab,
-               const double* __restrict__ w2_tab, mmx_rescore_params prm)
+               const double* __restrict__ w2_tab, mmx_rescore_params prm,
+               const int32_t* __restrict__ block_f32 = nullptr, int want = 0)
 {
     extern __shared__ double smem[];
     uint32_t n = cap;
@@ -194,6 +198,9 @@ rescore_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
     pt.y = __builtin_amdgcn_readfirstlane(ptv.y);
     pt.x = __builtin_amdgcn_readfirstlane(ptv.x);
     if (pt.slot < 0 || pt.slot >= prm.n_blocks || pt.s < 0 || pt.s >= MMX_MAX_SIGMAS) continue;     // (whole workgroup)
+    if constexpr (PER_BLOCK) {
+        if ((block_f32[pt.slot] != 0) != (want != 0)) continue;                                      // (whole workgroup)
+    }
     const mmx_block bd = blocks[pt.slot];
     const int R = prm.radius[pt.s];
     const int N = 2 * R + 1;
@@ -263,6 +270,18 @@ rescore_kernel(const InT* __restrict__ vol, int64_t sz, int64_t sy, int64_t sx,
         pts[idx].v64 = (double)cube;
     }
     }       // next point
+}
+
+template <typename InT, typename StoreT>
+int launch_per_block(const mmx_volume* vol, const mmx_block* d_blocks, mmx_cand* d_pts, uint32_t cap,
+                     const uint32_t* d_count, const double* d_w0, const double* d_w2,
+                     const mmx_rescore_params& prm, size_t lds, hipStream_t s, const int32_t* d_block_f32, int want)
+{
+    const uint32_t gx = cap < 8192u ? cap : 8192u;
+    hipLaunchKernelGGL((rescore_kernel<InT, StoreT, true>), dim3(gx), dim3(MMX_WG), lds, s,
+                       (const InT*)vol->d_data, vol->stride_z, vol->stride_y, vol->stride_x, d_blocks,
+                       d_pts, cap, d_count, d_w0, d_w2, prm, d_block_f32, want);
+    return hipGetLastError() == hipSuccess ? MMX_OK : MMX_ERR_HIP;
 }
 
 template <typename InT, typename StoreT>
@@ -339,6 +358,19 @@ extern "C" int mmx_rescore_f64(const mmx_volume* vol, const mmx_block* d_blocks,
                                const double* d_w0, const double* d_w2, const int32_t* h_radius,
                                const double* h_norm, int n_sigma, int store_f32, void* stream)
 {
+    return mmx_rescore_per_block(vol, d_blocks, n_blocks, d_pts, cap, d_count, d_w0, d_w2, h_radius, h_norm, n_sigma,
+                                 store_f32, nullptr, stream);
+}
+
+// mmx_rescore_f64 with the store type chosen PER BLOCK (mmx_detect_args.d_block_f32; called by mmx_detect_batch): `vol`
+// is the float64 copy of preprocessed blocks, in which a float32 block already holds float32 values widened -- reading
+// it as doubles is reading the float32 image -- so one volume serves both instantiations; each skips the other's blocks.
+int mmx_rescore_per_block(const mmx_volume* vol, const mmx_block* d_blocks, int n_blocks,
+                          mmx_cand* d_pts, uint32_t cap, const uint32_t* d_count,
+                          const double* d_w0, const double* d_w2, const int32_t* h_radius,
+                          const double* h_norm, int n_sigma, int store_f32, const int32_t* d_block_f32, void* stream)
+{
+    const bool per_block = d_block_f32 != nullptr;
     if (!vol || !vol->d_data || !d_blocks || !d_pts || !d_w0 || !d_w2 || !h_radius || !h_norm)
         return MMX_ERR_ARG;
     if (n_sigma < 1 || n_sigma > MMX_MAX_SIGMAS || n_blocks < 1) return MMX_ERR_ARG;
@@ -364,6 +396,14 @@ extern "C" int mmx_rescore_f64(const mmx_volume* vol, const mmx_block* d_blocks,
     hipStream_t s = (hipStream_t)stream;
     const bool f32s = store_f32 != 0;
     mmx_timed_scope ts(MMX_K_RESCORE, s);
+    if (per_block) {
+        if (vol->dtype != MMX_F64) return MMX_ERR_UNSUPPORTED;
+        const int rc = launch_per_block<double, double>(vol, d_blocks, d_pts, cap, d_count, d_w0, d_w2, prm, lds, s,
+                                                        d_block_f32, 0);
+        if (rc != MMX_OK) return rc;
+        return launch_per_block<double, float>(vol, d_blocks, d_pts, cap, d_count, d_w0, d_w2, prm, lds, s,
+                                               d_block_f32, 1);
+    }
     return mmx_for_voxel<MMX_VOX_ALL>(vol->dtype, MMX_ERR_ARG, [&](auto t) {
         using T = MMX_TAG_T(t);
         if constexpr (std::is_same<T, float>::value)

@@ -49,7 +49,11 @@ constexpr unsigned mmx_vox_bit(int dtype) { return 1u << dtype; }
 constexpr unsigned MMX_VOX_ALL = mmx_vox_bit(MMX_U8) | mmx_vox_bit(MMX_U16) | mmx_vox_bit(MMX_F32) | mmx_vox_bit(MMX_F64) | mmx_vox_bit(MMX_I16);
 constexpr unsigned MMX_VOX_LOG = MMX_VOX_ALL & ~mmx_vox_bit(MMX_F64);                         // the float32 LoG passes
 constexpr unsigned MMX_VOX_INTEGER = mmx_vox_bit(MMX_U8) | mmx_vox_bit(MMX_U16) | mmx_vox_bit(MMX_I16);
-constexpr unsigned MMX_VOX_PREPROC = MMX_VOX_INTEGER | mmx_vox_bit(MMX_F64);                  // (float32 images: another arithmetic, not built)
+// the preprocessing: every type.  float64 voxels take the one-output-per-lane kernel only, float32 voxels the register-
+// line forms of their own as well (pp_f32_kernel); a float32 image is computed
+// under the casting rules of NumPy 2 (non-identity tiles in float64, identity tiles in float32), which the host layer
+// makes its caller opt into (preprocess.FLOAT32_RULES): the library itself has one arithmetic per type
+constexpr unsigned MMX_VOX_PREPROC = MMX_VOX_INTEGER | mmx_vox_bit(MMX_F64) | mmx_vox_bit(MMX_F32);
 constexpr bool mmx_voxel_in(int dtype, unsigned mask) { return mmx_voxel(dtype) && ((mask >> dtype) & 1u); }
 
 // ------------------------------------------------------------------------------------------------ the dispatcher

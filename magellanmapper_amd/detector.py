@@ -392,6 +392,35 @@ def detect_blobs(roi, channel: Optional[Sequence[int]],
     return blobs_all
 
 
+def _refuse_float32_detection(dvol, channels, shapes, coloc, isotropic):
+    """A float32 image with the per-block preprocessing on, under ``preprocess.FLOAT32_RULES = "numpy2"``: its
+    preprocessed blocks are float32 or float64 block by block (``Preprocessor.block_flags``), which the plain
+    detection takes (``mmx_detect_args.d_block_f32``) and the steps around it do not.  Each of those is refused here by name -- from the arguments and the profiles alone, never
+    from the data, ahead of any buffer, upload wait or launch."""
+    from . import blob_log as bl
+    what = 'of a float32 image with the per-block preprocessing on (denoise_size; FLOAT32_RULES = "numpy2")'
+    if coloc:
+        raise NotImplementedError(f"intensity co-localisation (coloc=True) {what} is not built")
+    if isotropic is not None:
+        raise NotImplementedError(f"the isotropic rescale {what} is not built")
+    if any(getattr(config.get_roi_profile(c), "spectral_unmixing", None) for c in channels):
+        raise NotImplementedError(f"spectral unmixing of preprocessed blocks takes float64 blocks, not float32 ones: "
+                                  f"unmixing {what} is not built")
+    if any(config.get_roi_profile(c)["tot_var_denoise"] for c in channels):
+        raise NotImplementedError(f"tot_var_denoise {what} is not built (its identity tiles would iterate in float32)")
+    if len(shapes) and int(bl._slot_elems(np.asarray(shapes, dtype=np.int64).reshape(-1, 3)).max()) >= bl._slot_limit():
+        raise NotImplementedError(f"a block detected in parts -- too large for one workspace slot -- {what} is not "
+                                  "built; detect with a smaller segment_size")
+    if len(channels) > 1:
+        # (saturate_roi / denoise_roi allocate a multichannel tile from its first channel's dtype: an identity tile in
+        #  that channel rounds every other channel of the tile between the stages)
+        raise NotImplementedError(f"several channels in one detection {what} are not built (a tile's channels share "
+                                  "the dtype of the first in the reference): detect one channel per call")
+    if bl.HOST_PATH != "native":
+        raise NotImplementedError(f"blob detection {what} on the host path {bl.HOST_PATH!r} is not built: the store "
+                                  "type per block exists in the native path's exact re-score alone")
+
+
 def detect_blobs_blocks_device(dvol, channel, origins, shapes, stats=None,
                                on_block=None, denoise_max_shape=None, exclude=None,
                                coloc: bool = False, sink=None, stack_finisher=None) -> List[Optional[np.ndarray]]:
@@ -420,6 +449,10 @@ def detect_blobs_blocks_device(dvol, channel, origins, shapes, stats=None,
     iso_factor = None
     pre = None
     keeper = None
+    if denoise_max_shape is not None and dvol.np_dtype == np.dtype(np.float32):
+        from . import preprocess
+        if preprocess.float32_rules() == "numpy2":
+            _refuse_float32_detection(dvol, channels, shapes, coloc, isotropic)
     # a block too large for one workspace slot is detected as several overlapping parts (blob_log.split_oversized),
     # which these steps around the detection do not take
     if len(shapes) and int(bl._slot_elems(np.asarray(shapes, dtype=np.int64).reshape(-1, 3)).max()) >= bl._slot_limit():
@@ -435,7 +468,8 @@ def detect_blobs_blocks_device(dvol, channel, origins, shapes, stats=None,
                                       f"workspace slot -- is not supported; {way_out}")
     if denoise_max_shape is not None:
         from . import preprocess
-        pre = preprocess.Preprocessor(denoise_max_shape)
+        # (a float32 image: its blocks' dtypes go to the exact re-score with the batch, blob_log._batch_voxels)
+        pre = preprocess.Preprocessor(denoise_max_shape, block_dtypes=dvol.np_dtype == np.dtype(np.float32))
         if coloc and isotropic is None and dvol.multichannel and \
                 not any(getattr(config.get_roi_profile(c), "spectral_unmixing", None) for c in channels):
             # the co-localisation reads every channel's preprocessed blocks: keep them instead of making them twice

@@ -182,14 +182,24 @@ _BOUNDS_DTYPES = nat.voxel_dtypes(integer=True) + (nat.MMX_TO_NP[nat.MMX_F64],)
 _BOUNDS_NAMES = "uint8, uint16, int16 and float64 are supported"
 
 
+def _bounds_dtype_ok(dtype) -> bool:
+    """The types above, and float32 once ``preprocess.FLOAT32_RULES`` names NumPy 2's rules (a float32 difference of
+    the two order statistics, the rest of ``_lerp`` in float64): the switch the preprocessing reads, at call time."""
+    if dtype in _BOUNDS_DTYPES:
+        return True
+    from . import preprocess
+    return np.dtype(dtype) == np.dtype(np.float32) and preprocess.float32_rules() == "numpy2"
+
+
 def percentile_from_order_stats(a_prev, a_next, gamma, dtype):
     """``np.percentile(a, pct)`` (method "linear") from ``sorted(a)[prev]``, ``sorted(a)[next]`` and ``gamma`` of
     :func:`preprocess.quantile_ranks`, in float64, as NumPy's ``_lerp`` assembles it
     (numpy/lib/_function_base_impl.py): ``a + (b - a) * g``, replaced by ``b - (b - a) * (1 - g)`` where
     ``g >= 0.5``, with ``b - a`` taken in the input type -- for int16 the difference of two order statistics more than
-    32767 apart WRAPS, in NumPy and here.  Scalars or arrays; returns float64."""
+    32767 apart WRAPS, in NumPy and here; for float32 (``preprocess.FLOAT32_RULES = "numpy2"``) it is a float32
+    difference, rounded once, while the products and sums are float64.  Scalars or arrays; returns float64."""
     dtype = np.dtype(dtype)
-    if dtype not in _BOUNDS_DTYPES:
+    if not _bounds_dtype_ok(dtype):
         raise NotImplementedError(f"percentiles of {dtype} images ({_BOUNDS_NAMES})")
     a = np.asarray(a_prev).astype(dtype)
     b = np.asarray(a_next).astype(dtype)
@@ -211,7 +221,7 @@ def _bounds_ranks(n: int, lower, upper):
 
 def _percentiles_of_groups(dv, channel: int, groups, lower, upper):
     """``np.percentile(group, (lower, upper))`` of z-ranges of one channel of a device volume: ``(lows, highs)``."""
-    if dv.np_dtype not in _BOUNDS_DTYPES:
+    if not _bounds_dtype_ok(dv.np_dtype):
         raise NotImplementedError(f"percentiles of {dv.np_dtype} images ({_BOUNDS_NAMES})")
     plane = int(dv.shape[1]) * int(dv.shape[2])
     ranks, gammas = [], []
@@ -256,7 +266,7 @@ def calc_intensity_bounds(image5d, lower=0.5, upper=99.5, dim_channel=4):
     else:
         arr = image5d if isinstance(image5d, np.ndarray) else np.asarray(image5d)
         multichannel = arr.ndim > dim_channel
-        if arr.dtype not in _BOUNDS_DTYPES:
+        if not _bounds_dtype_ok(arr.dtype):
             raise NotImplementedError(f"percentiles of {arr.dtype} images ({_BOUNDS_NAMES})")
         if arr.size == 0:
             raise ValueError("empty image")
@@ -333,7 +343,7 @@ def measure_near_bounds(img, lower=0.5, upper=99.5, assign=False):
         lows, highs = [[] for _ in range(arr.n_channels)], [[] for _ in range(arr.n_channels)]
         measure(arr)
     else:
-        if arr.dtype not in _BOUNDS_DTYPES:
+        if not _bounds_dtype_ok(arr.dtype):
             raise NotImplementedError(f"percentiles of {arr.dtype} images ({_BOUNDS_NAMES})")
         if arr.size == 0:
             raise ValueError("empty image")

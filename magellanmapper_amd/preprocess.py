@@ -16,8 +16,13 @@ device, all O(number of distinct tile sizes)):
   (:mod:`kernels1d`).
 
 Scope: uint8 / uint16 / int16 voxels (what microscopes write) and float64 images (the same float64 arithmetic once the
-order statistics are found); float32 images, whose result in the reference depends on the NumPy release, raise
-``NotImplementedError``.  scikit-image < 0.19 treats a 3-D array whose last axis has length 3
+order statistics are found).  float32 images: what the reference computes depends on the NumPy release, so they raise
+``NotImplementedError`` until the caller names the release whose rules it wants: :data:`FLOAT32_RULES` ``= "numpy2"``
+(the reference pins NumPy 2.2).  Under those rules ``np.percentile`` of a float32 tile takes the difference of its two
+order statistics in float32 and returns float64 scalars, so a stretched tile is float64 from the clip on, while an
+identity tile (``vmin == vmax``) stays float32 through ``denoise_roi``; the merged block has the dtype of its FIRST tile
+(``Preprocessor.block_flags``, :func:`preprocess_roi`; the detection hands the flags to the exact re-score).
+scikit-image < 0.19 treats a 3-D array whose last axis has length 3
 as RGB inside ``filters.gaussian``; the reference pins 0.25 (no such guess), :data:`RGB_GUESS`
 switches the old behaviour on for the golden fixtures made with 0.18.3.
 """
@@ -39,6 +44,10 @@ from . import config, kernels1d
 GAUSS_SIGMA = 8.0                    # hard-coded in the reference (plot_3d.py:151)
 #: scikit-image < 0.19 ``filters.gaussian`` RGB guess for ``(M, N, 3)`` arrays
 RGB_GUESS = False
+#: casting rules a float32 image is preprocessed (and its intensity bounds measured) under: ``None`` -- refused, as the
+#: result depends on the NumPy release the reference runs on -- or ``"numpy2"`` (NEP 50; what the reference pins).
+#: Read at call time, like the profiles; :mod:`importer` reads it too.
+FLOAT32_RULES = None
 #: test hook: half kernel ``w[0..32]`` to use instead of this NumPy's (``np.exp`` is not bit-stable
 #: across NumPy releases and the golden fixtures were made under NumPy 1.26)
 GAUSS_WEIGHTS_OVERRIDE: Optional[np.ndarray] = None
@@ -49,6 +58,14 @@ FORCE_GENERIC = False
 #: workgroup of the pipelined blur kernel walks (0 = the library's default): what tests and tools switch
 KERNEL_MODE = nat.MMX_PP_AUTO
 TILES_PER_WG = 0
+
+
+def float32_rules():
+    """The validated :data:`FLOAT32_RULES`: ``None`` or ``"numpy2"``; anything else is a ``ValueError``."""
+    rules = FLOAT32_RULES
+    if rules is not None and rules != "numpy2":
+        raise ValueError(f'preprocess.FLOAT32_RULES must be None or "numpy2", not {rules!r}')
+    return rules
 
 
 def _wait_upload(dvol, origins, shapes) -> None:
@@ -135,7 +152,11 @@ class Preprocessor:
     """Preprocesses the blocks of a batch into uniform-stride float32 / float64 slots."""
 
     def __init__(self, denoise_max_shape: Sequence[int], near_max: Optional[Sequence[float]] = None,
-                 want_info: bool = False):
+                 want_info: bool = False, block_dtypes: bool = False):
+        """``block_dtypes``: the caller reads :attr:`block_flags` -- which blocks of a float32 image the reference
+        merges as float32 -- and treats the blocks accordingly; without it a float32 image is refused."""
+        self.block_dtypes = block_dtypes
+        self.block_flags = None         # device int32 per block of the last run on a float32 image: 1 = float32 block
         dms = [int(v) for v in denoise_max_shape]
         if len(dms) != 3 or min(dms) < 1:
             raise ValueError("denoise_max_shape must be three positive sizes")
@@ -319,12 +340,25 @@ class Preprocessor:
         # float64 images: the reference's arithmetic is the same float64 arithmetic once np.percentile has found its
         # order statistics (a radix select on the doubles, in the one-output-per-lane kernel).  float32 images: what the
         # reference computes depends on the NumPy release (float32 throughout under 1.26, float64 after the clip under
-        # 2.2: DESIGN.md section 6) -- not built.
+        # 2.2): refused unless FLOAT32_RULES names NumPy 2's rules, then the same kernel with a select on the floats'
+        # keys and float32 identity tiles.
         f64_voxels = dvol.np_dtype == np.dtype(np.float64)
-        if dvol.np_dtype not in _PREPROC_DTYPES:
+        f32_voxels = dvol.np_dtype == np.dtype(np.float32) and float32_rules() == "numpy2"
+        if dvol.np_dtype not in _PREPROC_DTYPES and not f32_voxels:
             raise NotImplementedError(
                 f"device preprocessing reads uint8 / uint16 / int16 / float64 voxels, not {dvol.np_dtype}")
         params, pct_lo, pct_hi = channel_params(int(channel), self.near_max)
+        if f32_voxels:
+            # static refusals (never data-dependent, ahead of every launch)
+            if params.tv_weight != 0.0:
+                raise NotImplementedError("tot_var_denoise on a float32 image (its identity tiles would iterate in "
+                                          "float32) is not built")
+            if self._retain is not None and int(channel) in self._retain["out64"]:
+                raise NotImplementedError("Preprocessor.retain of a float32 image (blocks of two dtypes) is not built")
+            if not self.block_dtypes:
+                raise NotImplementedError(
+                    "preprocessed blocks of a float32 image are float32 or float64 block by block "
+                    "(Preprocessor.block_flags): this caller handles one dtype per batch, not float32 images")
         nb = len(shapes)
         shp = np.asarray(shapes, dtype=np.int64).reshape(nb, 3)
         org = np.asarray(origins, dtype=np.int64).reshape(nb, 3)
@@ -387,11 +421,15 @@ class Preprocessor:
         subs = stage.numpy()[:total * item].view(nat.SUBBLOCK_DTYPE)
         at = [0, n_fast, n_fast + n_mid]
         base_src_all = org[:, 0] * vsz + org[:, 1] * vsy + org[:, 2] * vsx
+        first_tile = np.full(nb, -1, dtype=np.int32)         # per block the table row of the tile at its origin
         for cls, tmpl, members in plan:
             m, nt = len(members), len(tmpl)
             view = subs[at[cls]:at[cls] + m * nt].reshape(m, nt)
             view[...] = tmpl[None, :]
             idx = np.asarray(members, dtype=np.int64)
+            at_origin = np.nonzero(tmpl["dst_off"] == 0)[0]      # (offsets relative to the block: 0 is its origin)
+            if len(at_origin):
+                first_tile[idx] = at[cls] + nt * np.arange(m) + int(at_origin[0])
             view["src_off"] += base_src_all[idx][:, None]
             view["dst_off"] += (slots_of[idx] * slot_pre)[:, None]
             at[cls] += m * nt
@@ -453,13 +491,6 @@ class Preprocessor:
                     dst_sy, dst_sz, out32.data_ptr(), out64.data_ptr(),
                     (info_ptr + first * nat.SUBINFO_DTYPE.itemsize) if info_ptr else None,
                     scratch.data_ptr(), int(scratch.numel()), stream), "mmx_preprocess_batch_generic")
-        used = torch.cuda.Event()
-        used.record()
-        self._last_use = (stream, used)
-        self.last_subs = subs.copy() if self.want_info else None
-        self._keep = (d_subs, d_qc, d_info)
-        if self.want_info:
-            self.last_info = d_info[:len(subs) * nat.SUBINFO_DTYPE.itemsize]        # device bytes; see info()
         # block table over the preprocessed slots
         blocks = np.zeros(nb, dtype=nat.BLOCK_DTYPE)
         slot = 1
@@ -467,6 +498,26 @@ class Preprocessor:
             px = -(-int(shp[i, 2]) // nat.MMX_ROW_ALIGN) * nat.MMX_ROW_ALIGN
             blocks[i] = (int(slots_of[i]) * slot_pre, shp[i, 0], shp[i, 1], shp[i, 2], i, px, 0)
             slot = max(slot, int(shp[i, 0]) * int(shp[i, 1]) * px)
+        self.block_flags = None
+        d_blk = None
+        if f32_voxels and nb:
+            if (first_tile < 0).any():
+                raise nat.MmxError("a block without a tile at its origin")
+            # the reference's merged block has its first tile's dtype: the pass behind the tiles states it per block and
+            # rounds the float64 copy of a float32 block in place
+            d_blk = (_bl._to_device_bytes(blocks, dev), _bl._to_device_bytes(first_tile, dev))
+            self.block_flags = torch.zeros(nb, dtype=torch.int32, device=dev)
+            nat.check(L.mmx_preprocess_block_dtypes(
+                d_blk[0].data_ptr(), blocks.ctypes.data, nb, d_blk[1].data_ptr(), first_tile.ctypes.data, total,
+                info_ptr, dst_sy, dst_sz, out64.data_ptr(), int(out64.numel()), self.block_flags.data_ptr(), stream),
+                "mmx_preprocess_block_dtypes")
+        used = torch.cuda.Event()
+        used.record()
+        self._last_use = (stream, used)
+        self.last_subs = subs.copy() if self.want_info else None
+        self._keep = (d_subs, d_qc, d_info, d_blk)
+        if self.want_info:
+            self.last_info = d_info[:len(subs) * nat.SUBINFO_DTYPE.itemsize]        # device bytes; see info()
         vol32 = nat.Volume(out32.data_ptr(), nat.MMX_F32, 0, dst_sz, dst_sy, 1)
         vol64 = nat.Volume(out64.data_ptr(), nat.MMX_F64, 0, dst_sz, dst_sy, 1)
         self.last_geometry = (slot_pre, dst_sz, dst_sy, out64, out32) if kept is None else None
@@ -906,21 +957,34 @@ def preprocess_roi(roi, denoise_max_shape, channel: Optional[Sequence[int]] = No
                    near_max: Optional[Sequence[float]] = None, return_info: bool = False):
     """Saturate + denoise a ``(z, y, x[, c])`` block tile by tile -> float64 array of the same
     shape: what ``detect_sub_roi`` hands to ``detect_blobs`` (stack_detect.py:122-150).
-    Channels not selected stay zero, as in the reference."""
+    Channels not selected stay zero, as in the reference.  A float32 image (:data:`FLOAT32_RULES`) comes back in the
+    reference's dtype for the block: float32 when the first tile is an identity tile, float64 otherwise (one channel per
+    call: the channels of a multichannel tile share the dtype of the first in the reference, which is not built)."""
     from . import blob_log as bl
     from .detector import _channels_of
     dvol = roi if isinstance(roi, bl.DeviceVolume) else bl.DeviceVolume(roi)
     multichannel, channels = _channels_of(dvol.tensor.ndim, dvol.n_channels, channel)
-    out = np.zeros(dvol.shape, dtype=np.float64)
+    if dvol.np_dtype == np.dtype(np.float32) and float32_rules() == "numpy2" and len(list(channels)) > 1:
+        # (saturate_roi / denoise_roi allocate a multichannel tile from its first channel's dtype: an identity tile in
+        #  channel 0 rounds every other channel of that tile between the stages)
+        raise NotImplementedError("several channels of a float32 image in one call (a tile's channels share the dtype "
+                                  "of the first) are not built: preprocess them one channel at a time")
+    out = None
     infos = []
     for chl in channels:
-        pre = Preprocessor(denoise_max_shape, near_max, want_info=return_info)
+        pre = Preprocessor(denoise_max_shape, near_max, want_info=return_info, block_dtypes=True)
         pre.run(dvol, chl if multichannel else 0, [(0, 0, 0)], [dvol.shape[:3]])
         block = pre.fetch([dvol.shape[:3]])[0]
+        if pre.block_flags is not None and int(pre.block_flags.cpu()[0]):
+            block = block.astype(np.float32)        # (exact: the device rounded the float64 copy of a float32 block)
+        if out is None:
+            out = np.zeros(dvol.shape, dtype=block.dtype)
         if multichannel:
             out[..., chl] = block
         else:
             out = block
         if return_info:
             infos.append((pre.last_subs, pre.info()))
+    if out is None:
+        out = np.zeros(dvol.shape, dtype=np.float64)
     return (out, infos) if return_info else out

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Preprocessing micro-benchmark: HIP-event time of mmx_preprocess_batch on a batch of blocks.
 
-    python tools/ppbench.py [--blocks 27] [--edge 266] [--dms 25] [--reps 3] [--generic]
+    python tools/ppbench.py [--blocks 27] [--edge 266] [--dms 25] [--reps 3] [--generic] [--dtype float32]
+
+--dtype float32 / float64: the same voxels as v / 65535 (float32, and that float32 widened), float32 under
+preprocess.FLOAT32_RULES = "numpy2".  The JSON line carries the mean, the median and the spread of the repetitions.
 """
 import argparse, json, os, sys
 import numpy as np
@@ -21,6 +24,7 @@ ap.add_argument("--mode", choices=("auto", "single", "pipelined"), default="auto
 ap.add_argument("--tpw", type=int, default=0, help="tiles per workgroup of the pipelined blur kernel")
 ap.add_argument("--profile", action="store_true", help="phase ticks of a -DPP_PROFILE build (MMX_LIB_PATH)")
 ap.add_argument("--check", action="store_true", help="compare the float64 output with the single-kernel form")
+ap.add_argument("--dtype", choices=("uint16", "float32", "float64"), default="uint16")
 a = ap.parse_args()
 dev = torch.device("cuda", 0)
 e = a.edge
@@ -28,6 +32,12 @@ g = int(np.ceil(a.blocks ** (1 / 3)))
 step = e - 10
 shape = (step * g + 10,) * 3
 vol = synth.make_volume_device(shape, 3, dev)
+if a.dtype != "uint16":
+    vol = (vol.view(torch.int16).to(torch.int32) & 0xFFFF).to(torch.float32) / 65535.0
+    if a.dtype == "float64":
+        vol = vol.to(torch.float64)
+    else:
+        preprocess.FLOAT32_RULES = "numpy2"
 dvol = bl.DeviceVolume(vol)
 origins = [(z * step, y * step, x * step) for z in range(g) for y in range(g) for x in range(g)][:a.blocks]
 shapes = [(e, e, e)] * len(origins)
@@ -40,7 +50,7 @@ dms = a.dms * 3 if len(a.dms) == 1 else a.dms
 preprocess.FORCE_GENERIC = a.generic
 preprocess.KERNEL_MODE = dict(auto=nat.MMX_PP_AUTO, single=nat.MMX_PP_SINGLE, pipelined=nat.MMX_PP_PIPELINED)[a.mode]
 preprocess.TILES_PER_WG = a.tpw
-pre = preprocess.Preprocessor(dms, want_info=True)
+pre = preprocess.Preprocessor(dms, want_info=True, block_dtypes=a.dtype == "float32")
 nvox = len(origins) * e ** 3
 times = []
 for rep in range(a.reps + 1):
@@ -80,7 +90,9 @@ if os.environ.get("PP_PROFILE"):
     print("stage ticks (100 MHz) load %.0f select %.0f saturate %.0f blur %.0f write %.0f" % (
         a1.mean(), a2.mean(), b1.mean(), b2.mean(), info["mean"].mean()))
 k = float(np.mean([t[0] for t in times])); w = float(np.mean([t[1] for t in times]))
-print(json.dumps(dict(blocks=len(origins), edge=e, dms=dms, tiles=len(info), kernel_ms=round(k, 3),
-                      wall_ms=round(w, 3), gvox_per_s=round(nvox / k / 1e6, 2),
+walls = [t[1] for t in times]
+print(json.dumps(dict(blocks=len(origins), edge=e, dms=dms, dtype=a.dtype, tiles=len(info), kernel_ms=round(k, 3),
+                      wall_ms=round(w, 3), wall_median_ms=round(float(np.median(walls)), 3),
+                      wall_min_ms=round(min(walls), 3), wall_max_ms=round(max(walls), 3), gvox_per_s=round(nvox / k / 1e6, 2),
                       us_per_tile_per_cu=round(k * 1e3 / (len(info) / 256), 2),
                       eroded=int((info["flags"] & 2 != 0).sum()), identity=int((info["flags"] & 1 != 0).sum()))))
