@@ -956,6 +956,62 @@ int mmx_host_lsap(const double* cost, int64_t nr, int64_t nc, int64_t* out_rows,
 int mmx_extract_patches(const mmx_volume* vol, const int32_t* d_zyx, int64_t n, int size, void* d_out, float* d_out32,
                         void* stream);
 
+/* ---- T1: whole-image down-sampling (added to ABI v21 without a version step: a library without it lacks the symbols)
+ * replaces: cv_nd.rescale_resize as transformer.transpose_img calls it for every chunk of its plan
+ * (magmap/atlas/transformer.py:41-73, 220-285) = skimage.transform.rescale / resize (>= 0.19) with
+ * preserve_range=False: img_as_float, the anti-aliasing Gaussian along shrinking axes (resize only),
+ * scipy.ndimage.zoom(order=1, mode='mirror', grid_mode=True), the clip to the converted chunk's range.  Bit-equal.
+ * Every sample is converted as it is loaded -- x * (1 / imax) for the unsigned types, (x + 0.5) * (2 / 65535) for
+ * int16, float voxels as they are -- and every result is float64, or float32 for a float32 image.
+ *
+ * One chunk of a batch.  Zoom: in_* the source extent as the tables address it, out_* the resized extent, tz / ty / tx
+ * the offsets (in output indices) of its axis tables.  Pick pass: in_* the source extent as it stands, out_* the same
+ * with the extent along the pass's axis replaced by the number of picked positions, and the t? of that axis the offset
+ * of its pick list. */
+typedef struct {
+    int64_t src_off;                  /* element offset of the chunk origin in the source                         */
+    int64_t dst_off;                  /* element offset of the chunk's first output voxel in the destination      */
+    int32_t in_nz, in_ny, in_nx;
+    int32_t out_nz, out_ny, out_nx;
+    int32_t slot;                     /* row of d_minmax (zoom); row of d_weights / d_radius (pick pass)          */
+    int32_t tz, ty, tx;
+    int32_t _pad[2];
+} mmx_ds_chunk;                       /* 64 bytes */
+/* One channel of the source, or of the destination, of a down-sampling batch: any strides (a plane swap is a
+ * permutation of them, a (z, y, x, c) image passes stride_x = n_channels).  An unknown dtype code is
+ * MMX_ERR_UNSUPPORTED and nothing is launched. */
+typedef struct {
+    void* d_data;
+    int32_t dtype;                    /* mmx_dtype */
+    int32_t _pad;
+    int64_t stride_z, stride_y, stride_x; /* in elements */
+} mmx_ds_view;
+/* mmx_ds_zoom_batch: the order-1 zoom of every chunk, clipped, written straight to the chunk's place in `dst` (a
+ * view of the output volume at its strides: no staging slot, no second copy).
+ *   src          : the raw image (any mmx_dtype, any strides), or the compacted output of the pick passes (float64;
+ *                  float32 for a float32 image)
+ *   dst          : MMX_F64, or MMX_F32 when raw_dtype is MMX_F32; dst_elems: elements behind dst->d_data (no chunk
+ *                  may write at or beyond it: MMX_ERR_ARG)
+ *   d_index / h_index / d_weight : [n_index][2] tables as for mmx_resize_batch; the host copy is checked against
+ *                  every chunk's source extent before the launch (MMX_ERR_ARG, nothing launched)
+ *   d_minmax     : [n][2] RAW min / max of each chunk over all channels (mmx_minmax_batch); raw_dtype: the image's
+ *                  voxel type -- the conversion is monotonic, so the converted range is the conversion of these two
+ * mmx_ds_gauss_pick_batch: one anti-aliasing correlate1d pass along `axis` (as mmx_gauss_axis_batch: SciPy's symmetric
+ * sum, mirror extension for any radius, weights d_weights[slot * w_pitch + 0..d_radius[slot]]; radius 0 copies)
+ * evaluated ONLY at the positions d_pick[t .. t + out_n) along that axis and written compacted: float64 (float32 for a
+ * float32 source) at d_out + dst_off with strides (dst_sz, dst_sy, 1).  h_pick is checked like h_index.
+ * PRECONDITION (the caller's: neither launcher is told the size of the source allocation): every chunk's source box,
+ *     src_off + [0, in_nz) stride_z + [0, in_ny) stride_y + [0, in_nx) stride_x, lies inside the source.  What IS checked
+ *     before a launch: the tables and pick lists against in_*, and every chunk's last output element against dst_elems. */
+int mmx_ds_zoom_batch(const mmx_ds_view* src, const mmx_ds_view* dst, int64_t dst_elems, const mmx_ds_chunk* d_chunks,
+                      const mmx_ds_chunk* h_chunks, int n_chunks, const int32_t* d_index, const int32_t* h_index,
+                      int64_t n_index, const double* d_weight, const double* d_minmax, int raw_dtype, void* stream);
+int mmx_ds_gauss_pick_batch(const mmx_ds_view* src, const mmx_ds_chunk* d_chunks, const mmx_ds_chunk* h_chunks,
+                            int n_chunks, int axis, const double* d_weights, const int32_t* d_radius,
+                            const int32_t* h_radius, int w_pitch, const int32_t* d_pick, const int32_t* h_pick,
+                            int64_t n_pick, int64_t dst_sy, int64_t dst_sz, int64_t dst_elems, void* d_out,
+                            void* stream);
+
 /* PMC calibration (tools/pmc_calib.py): one streaming launch over n_elems elements with a known
  * byte count.  kind 0: float copy, 4 B per lane; 1: float copy, 16 B per lane; 2: uint16 read. */
 int mmx_calib_stream(int kind, const void* d_in, void* d_out, int64_t n_elems, void* stream);

@@ -101,11 +101,22 @@ assert RESIZE_DTYPE.itemsize == 48
 #: NumPy mirror of ``mmx_rank_group`` (40 bytes): planes ``[z0, z1)`` and four 0-based ranks into their sorted voxels
 RANK_GROUP_DTYPE = np.dtype([("z0", "<i4"), ("z1", "<i4"), ("rank", "<i8", (4,))], align=True)
 assert RANK_GROUP_DTYPE.itemsize == 40
+#: NumPy mirror of ``mmx_ds_chunk`` (64 bytes): one chunk of a down-sampling batch
+DS_CHUNK_DTYPE = np.dtype([("src_off", "<i8"), ("dst_off", "<i8"), ("in_nz", "<i4"), ("in_ny", "<i4"), ("in_nx", "<i4"),
+                           ("out_nz", "<i4"), ("out_ny", "<i4"), ("out_nx", "<i4"), ("slot", "<i4"),
+                           ("tz", "<i4"), ("ty", "<i4"), ("tx", "<i4"), ("_pad", "<i4", (2,))], align=True)
+assert DS_CHUNK_DTYPE.itemsize == 64
 
 
 class Volume(Structure):
     """``mmx_volume``."""
     _fields_ = [("d_data", c_void_p), ("dtype", c_int32), ("value_range", c_float),
+                ("stride_z", c_int64), ("stride_y", c_int64), ("stride_x", c_int64)]
+
+
+class DsView(Structure):
+    """``mmx_ds_view``: one channel of the source or the destination of a down-sampling batch."""
+    _fields_ = [("d_data", c_void_p), ("dtype", c_int32), ("_pad", c_int32),
                 ("stride_z", c_int64), ("stride_y", c_int64), ("stride_x", c_int64)]
 
 
@@ -185,6 +196,7 @@ SYMBOLS = (
     "mmx_cdist_f64", "mmx_host_lsap", "mmx_expand_probes", "mmx_fold_parts", "mmx_host_resolve_peaks", "mmx_host_overlap_prune",
     "mmx_host_emit_tables", "mmx_host_prune_region", "mmx_host_prune_parts", "mmx_host_rows_in_boxes", "mmx_host_append_rows", "mmx_host_emit_parts", "mmx_host_merge_parts_by_key", "mmx_host_gather_parts_by_key", "mmx_host_emit_tables_multi", "mmx_host_coloc_flags", "mmx_host_finish_stack", "mmx_copy_rect_h2d", "mmx_host_stage_upload", "mmx_host_stage_upload_pitched", "mmx_event_query",
     "mmx_order_stats_workspace", "mmx_order_stats", "mmx_extract_patches",
+    "mmx_ds_zoom_batch", "mmx_ds_gauss_pick_batch",
 )
 KERNEL_KINDS = ("zpass", "ypass", "xpass", "generic", "peaks", "rescore", "overlap_pairs",
                 "close_pairs", "zxpass", "y2pass", "preproc", "coloc", "zxpack", "widepass")
@@ -331,6 +343,12 @@ def lib() -> ctypes.CDLL:
     L.mmx_order_stats.restype = c_int
     L.mmx_extract_patches.argtypes = [POINTER(Volume), vp, c_int64, c_int, vp, vp, vp]
     L.mmx_extract_patches.restype = c_int
+    L.mmx_ds_zoom_batch.argtypes = [POINTER(DsView), POINTER(DsView), c_int64, vp, vp, c_int, vp, vp, c_int64, vp, vp,
+                                    c_int, vp]
+    L.mmx_ds_zoom_batch.restype = c_int
+    L.mmx_ds_gauss_pick_batch.argtypes = [POINTER(DsView), vp, vp, c_int, c_int, vp, vp, vp, c_int, vp, vp, c_int64,
+                                          c_int64, c_int64, c_int64, vp, vp]
+    L.mmx_ds_gauss_pick_batch.restype = c_int
     L.mmx_preprocess_batch.restype = c_int
     L.mmx_preprocess_batch_mode.restype = c_int
     L.mmx_preprocess_batch_generic.restype = c_int

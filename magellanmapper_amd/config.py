@@ -35,6 +35,11 @@ zoom = 1.0
 save_subimg: bool = False
 truth_db_mode = None
 grid_search_profile = None
+#: planar orientations (reference config.py:202-203) and the one in use; ``transformer.transpose_img`` takes its own
+PLANE = ("xy", "xz", "yz")
+plane = None
+#: the atlas profile (a mapping); only its ``"target_size"`` (x, y, z) is read here, by ``transformer.transpose_img``
+atlas_profile = None
 
 
 class ClassifierData:

@@ -285,6 +285,20 @@ def calc_intensity_bounds(image5d, lower=0.5, upper=99.5, dim_channel=4):
     return lows, highs
 
 
+def calc_scaling(image5d, scaled, image5d_shape=None, scaled_shape=None) -> np.ndarray:
+    """``z, y, x`` factors from an image to its rescaled copy (importer.py:1500-1535): shapes of four axes and more
+    lose their time axis first; either array may be ``None`` when its shape is given."""
+    if image5d_shape is None:
+        image5d_shape = image5d.shape
+    if scaled_shape is None:
+        scaled_shape = scaled.shape
+    if len(image5d_shape) >= 4:
+        image5d_shape = image5d_shape[1:4]
+    if len(scaled_shape) >= 4:
+        scaled_shape = scaled_shape[1:4]
+    return np.divide(scaled_shape[:3], image5d_shape[:3])
+
+
 def calc_near_intensity_bounds(near_mins, near_maxs, lows, highs):
     """Near min / max from lists of per-plane ``lows`` / ``highs`` (importer.py:1447-1468; no device): with one
     channel the extremes are APPENDED to the lists given, with several the per-channel minima / maxima come back as

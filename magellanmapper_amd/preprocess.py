@@ -953,6 +953,48 @@ def make_isotropic(roi, scale, res=None, denoise_max_shape=None) -> np.ndarray:
     return np.stack(outs, axis=-1) if dvol.multichannel else outs[0]
 
 
+def rescale_resize(roi, target_size=None, multichannel: bool = False, preserve_range: bool = False, **kwargs) -> np.ndarray:
+    """``cv_nd.rescale_resize`` (reference cv_nd.py:1109-1167) of one ``(z, y, x[, c])`` array on the device: rescaled by
+    the factor ``target_size`` (``skimage.transform.rescale``: extents ``np.round(scale * shape)``, no anti-aliasing
+    unless asked for) or resized to the ``(z, y, x)`` shape ``target_size`` (``resize``: anti-aliased where it shrinks
+    unless told otherwise), as :func:`transformer.downsample` resizes each of its chunks: ``img_as_float``, order 1,
+    'reflect', clipped to the converted array's range; float64, or float32 for a float32 array.  ``order`` in
+    ``{None, 1}``, ``anti_aliasing`` in ``{None, True, False}`` and ``mode="reflect"`` are taken; anything else is a
+    ``NotImplementedError`` naming the argument, raised before any launch (``preserve_range=True`` is
+    :func:`make_isotropic`'s path)."""
+    taken = {"order": (None, 1), "anti_aliasing": (None, True, False), "mode": ("reflect",)}
+    for name, val in kwargs.items():
+        # (same type as well as equal: order=True or anti_aliasing=1 are not the values named above)
+        if name not in taken or not any(type(val) is type(v) and val == v for v in taken[name]):
+            raise NotImplementedError(f"rescale_resize: {name}={val!r} is not built")
+    if preserve_range:
+        raise NotImplementedError("rescale_resize: preserve_range=True is not built (make_isotropic resizes in the "
+                                  "input's range)")
+    from . import transformer
+    roi = np.asarray(roi)
+    if roi.ndim not in (3, 4):
+        raise ValueError("roi must be (z, y, x) or (z, y, x, c)")
+    is_seq = isinstance(target_size, (tuple, list, np.ndarray))
+    if is_seq:
+        if len(target_size) != 3:
+            raise ValueError("target_size must be a factor or a (z, y, x) shape")
+        new = tuple(int(v) for v in target_size)
+    else:
+        if target_size is None:
+            raise ValueError("target_size must be a factor or a (z, y, x) shape")
+        if roi.ndim == 3 and multichannel:
+            raise NotImplementedError("rescale_resize: multichannel=True for a three-axis array (its last axis would be "
+                                      "kept as channels) is not built")
+        if roi.ndim == 4 and not multichannel:
+            raise NotImplementedError("rescale_resize: multichannel=False for a four-axis array (the channel axis would "
+                                      "be rescaled) is not built")
+        new = tuple(int(v) for v in np.round(np.float64(target_size) * np.array(roi.shape[:3])))
+    if min(new) < 1:
+        raise ValueError(f"a {roi.shape[:3]} array resized to {new} is empty")
+    aa = kwargs.get("anti_aliasing")
+    return transformer.resize_chunk(roi, new, is_seq if aa is None else bool(aa))
+
+
 def preprocess_roi(roi, denoise_max_shape, channel: Optional[Sequence[int]] = None,
                    near_max: Optional[Sequence[float]] = None, return_info: bool = False):
     """Saturate + denoise a ``(z, y, x[, c])`` block tile by tile -> float64 array of the same
