@@ -1012,6 +1012,49 @@ int mmx_ds_gauss_pick_batch(const mmx_ds_view* src, const mmx_ds_chunk* d_chunks
                             int64_t n_pick, int64_t dst_sy, int64_t dst_sz, int64_t dst_elems, void* d_out,
                             void* stream);
 
+/* ---- P1: whole-image preprocessing (added to ABI v21 without a version step: a library without it lacks the symbols)
+ * replaces: plot_3d.remap_intensity -> skimage.exposure.equalize_adapthist and plot_3d.saturate_roi as
+ * transformer.preprocess_img runs them over a whole stack (magmap/atlas/transformer.py:353-393, magmap/plot/
+ * plot_3d.py:55-111, 270-317).  Bit-equal to the pinned scikit-image chain; one channel of a resident image per call,
+ * stream-ordered, every buffer the caller's.
+ *
+ * The geometry of one equalisation: the image extent, the kernel (tile) size and the histogram tiles per axis,
+ * nt = ceil(n / k) -- tile i of an axis covers voxels [i k, (i + 1) k), the last one reaching into the trailing
+ * reflect padding -- and the number of bins (at most 16384). */
+typedef struct {
+    int32_t n[3];                     /* z, y, x */
+    int32_t k[3];
+    int32_t nt[3];
+    int32_t nbins;
+    int32_t _pad[2];
+} mmx_eq_geom;                        /* 48 bytes */
+/* A voxel's index ("key") into d_bins: the value (uint8, uint16), value + 32768 (int16), or img_as_uint of a float voxel
+ * (rint(v * 65535) in the voxel's own type, clipped to [0, 65535]).  d_bins[65536]: the histogram bin of every key
+ * (img_as_uint -> rescale_intensity to 14 bits -> // bin size, stated by the host in NumPy), each below nbins --
+ * the caller's precondition, as is the source extent (mmx_ds_* above).
+ * mmx_eq_hist      : d_hist[tiles][nbins] (uint32, zeroed by the call) = np.bincount of every tile; tiles in C order.
+ *                    MMX_ERR_UNSUPPORTED for a tile of 2^31 voxels or more.
+ * mmx_host_eq_maps : (host, no device) clip_histogram + map_histogram of every tile: maps[tiles][nbins] uint16 from
+ *                    hist, the clip limit `clim` and n_pixels = prod(k); entered (may be NULL): per tile 1 when the
+ *                    histogram went into clip_histogram's redistribution loop.
+ * mmx_eq_apply     : the interpolation between the eight neighbouring maps.  d_tiles / h_tiles [nz + ny + nx][2]: per
+ *                    coordinate of each axis the tile whose map stands below and above it (both clamped into
+ *                    [0, nt): the edge padding of the map array); the host copy is checked before the launch.
+ *                    d_coef [nz + ny + nx][2]: the coefficients of those two, 1 - c and c with c = arange(k)[o] / k.
+ *                    d_out: the uint16 result, packed (z, y, x); d_minmax[2] (uint32): its minimum and maximum.
+ * mmx_eq_output    : d_out[i] = d_table[d_levels[i]] for n voxels; d_table[16384] float64 (img_as_float and the final
+ *                    rescale_intensity of every level, stated by the host).
+ * mmx_stretch      : (clip(x, vmin, vmax) - vmin) / (vmax - vmin) in float64 for an (nz, ny, nx) box of `src`, packed
+ *                    into d_out; vmin < vmax (MMX_ERR_ARG otherwise: the caller returns such a channel unchanged). */
+int mmx_eq_hist(const mmx_ds_view* src, const mmx_eq_geom* g, const uint16_t* d_bins, uint32_t* d_hist, void* stream);
+int mmx_host_eq_maps(const uint32_t* hist, int64_t n_tiles, int nbins, int64_t clim, int64_t n_pixels, uint16_t* maps,
+                     uint8_t* entered);
+int mmx_eq_apply(const mmx_ds_view* src, const mmx_eq_geom* g, const uint16_t* d_bins, const uint16_t* d_maps,
+                 const int32_t* d_tiles, const int32_t* h_tiles, const double* d_coef, uint16_t* d_out,
+                 uint32_t* d_minmax, void* stream);
+int mmx_eq_output(const uint16_t* d_levels, int64_t n, const double* d_table, double* d_out, void* stream);
+int mmx_stretch(const mmx_ds_view* src, int nz, int ny, int nx, double vmin, double vmax, double* d_out, void* stream);
+
 /* PMC calibration (tools/pmc_calib.py): one streaming launch over n_elems elements with a known
  * byte count.  kind 0: float copy, 4 B per lane; 1: float copy, 16 B per lane; 2: uint16 read. */
 int mmx_calib_stream(int kind, const void* d_in, void* d_out, int64_t n_elems, void* stream);

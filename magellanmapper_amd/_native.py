@@ -120,6 +120,11 @@ class DsView(Structure):
                 ("stride_z", c_int64), ("stride_y", c_int64), ("stride_x", c_int64)]
 
 
+class EqGeom(Structure):
+    """``mmx_eq_geom``: extent, kernel size, histogram tiles per axis and bins of one equalisation."""
+    _fields_ = [("n", c_int32 * 3), ("k", c_int32 * 3), ("nt", c_int32 * 3), ("nbins", c_int32), ("_pad", c_int32 * 2)]
+
+
 class DetectArgs(Structure):
     """``mmx_detect_args`` (one batch from voxels to the re-scored candidate table: ``mmx_detect_batch``)."""
     _fields_ = [("vol32", POINTER(Volume)), ("vol_exact", POINTER(Volume)), ("d_blocks", c_void_p),
@@ -197,6 +202,7 @@ SYMBOLS = (
     "mmx_host_emit_tables", "mmx_host_prune_region", "mmx_host_prune_parts", "mmx_host_rows_in_boxes", "mmx_host_append_rows", "mmx_host_emit_parts", "mmx_host_merge_parts_by_key", "mmx_host_gather_parts_by_key", "mmx_host_emit_tables_multi", "mmx_host_coloc_flags", "mmx_host_finish_stack", "mmx_copy_rect_h2d", "mmx_host_stage_upload", "mmx_host_stage_upload_pitched", "mmx_event_query",
     "mmx_order_stats_workspace", "mmx_order_stats", "mmx_extract_patches",
     "mmx_ds_zoom_batch", "mmx_ds_gauss_pick_batch",
+    "mmx_eq_hist", "mmx_host_eq_maps", "mmx_eq_apply", "mmx_eq_output", "mmx_stretch",
 )
 KERNEL_KINDS = ("zpass", "ypass", "xpass", "generic", "peaks", "rescore", "overlap_pairs",
                 "close_pairs", "zxpass", "y2pass", "preproc", "coloc", "zxpack", "widepass")
@@ -349,6 +355,15 @@ def lib() -> ctypes.CDLL:
     L.mmx_ds_gauss_pick_batch.argtypes = [POINTER(DsView), vp, vp, c_int, c_int, vp, vp, vp, c_int, vp, vp, c_int64,
                                           c_int64, c_int64, c_int64, vp, vp]
     L.mmx_ds_gauss_pick_batch.restype = c_int
+    L.mmx_eq_hist.argtypes = [POINTER(DsView), POINTER(EqGeom), vp, vp, vp]
+    L.mmx_eq_hist.restype = c_int
+    L.mmx_host_eq_maps.argtypes = [vp, c_int64, c_int, c_int64, c_int64, vp, vp]
+    L.mmx_eq_apply.argtypes = [POINTER(DsView), POINTER(EqGeom), vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mmx_eq_apply.restype = c_int
+    L.mmx_eq_output.argtypes = [vp, c_int64, vp, vp, vp]
+    L.mmx_eq_output.restype = c_int
+    L.mmx_stretch.argtypes = [POINTER(DsView), c_int, c_int, c_int, c_double, c_double, vp, vp]
+    L.mmx_stretch.restype = c_int
     L.mmx_preprocess_batch.restype = c_int
     L.mmx_preprocess_batch_mode.restype = c_int
     L.mmx_preprocess_batch_generic.restype = c_int

@@ -11,6 +11,7 @@ never cached -- because the reference's grid search mutates profiles between cal
 from __future__ import annotations
 
 import logging
+from enum import Enum, auto
 from typing import List, Optional, Sequence
 
 logger = logging.getLogger("magellanmapper_amd")
@@ -40,6 +41,15 @@ PLANE = ("xy", "xz", "yz")
 plane = None
 #: the atlas profile (a mapping); only its ``"target_size"`` (x, y, z) is read here, by ``transformer.transpose_img``
 atlas_profile = None
+
+
+class PreProcessKeys(Enum):
+    """Whole-image pre-processing tasks (reference config.py:251-256); ``transformer.preprocess_img`` runs ``SATURATE``
+    and ``REMAP``, the other two stay in the reference."""
+    SATURATE = auto()
+    DENOISE = auto()
+    REMAP = auto()
+    ROTATE = auto()
 
 
 class ClassifierData:

@@ -1501,3 +1501,59 @@ extern "C" int mmx_host_finish_stack(const mmx_finish_stack_args* a)
     *a->out_rows = kept;
     return MMX_OK;
 }
+
+// ---- whole-image CLAHE: skimage.exposure._adapthist.clip_histogram + map_histogram of every tile (mmx.h: P1).
+// Integer work on tiles x nbins counts between two launches; the serial redistribution loop is kept as written --
+// the `index::step_size` strides, the step recomputed for every index from the bins still under the limit, the early
+// exit of a round that changed nothing -- with the count of such bins carried along instead of recounted.
+extern "C" int mmx_host_eq_maps(const uint32_t* hist, int64_t n_tiles, int nbins, int64_t clim, int64_t n_pixels,
+                                uint16_t* maps, uint8_t* entered)
+{
+    if (!hist || !maps || n_tiles < 1 || nbins < 1 || nbins > 16384 || clim < 1 || n_pixels < 1) return MMX_ERR_ARG;
+    const double scale = 16383.0 / (double)n_pixels;
+    std::vector<int64_t> h((size_t)nbins);
+    for (int64_t t = 0; t < n_tiles; ++t) {
+        const uint32_t* src = hist + t * nbins;
+        int64_t n_excess = 0;
+        for (int b = 0; b < nbins; ++b) {
+            h[(size_t)b] = src[b];
+            if (h[(size_t)b] > clim) { n_excess += h[(size_t)b] - clim; h[(size_t)b] = clim; }
+        }
+        const int64_t bin_incr = n_excess / nbins;
+        const int64_t upper = clim - bin_incr;
+        int64_t n_low = 0;
+        for (int b = 0; b < nbins; ++b)
+            if (h[(size_t)b] < upper) { h[(size_t)b] += bin_incr; ++n_low; }
+        n_excess -= n_low * bin_incr;
+        // (the mask is taken after the raise: a raised bin that reached `upper` is filled up as well)
+        for (int b = 0; b < nbins; ++b)
+            if (h[(size_t)b] >= upper && h[(size_t)b] < clim) { n_excess += h[(size_t)b] - clim; h[(size_t)b] = clim; }
+        if (entered) entered[t] = n_excess > 0;
+        int64_t under = 0;
+        for (int b = 0; b < nbins; ++b) under += h[(size_t)b] < clim;
+        while (n_excess > 0 && under > 0) {     // (no bin under the limit: every round changes nothing and the loop ends)
+            const int64_t prev = n_excess;
+            for (int index = 0; index < nbins; ++index) {
+                const int64_t step = std::max<int64_t>(1, under / n_excess);
+                int64_t raised = 0;
+                for (int64_t j = index; j < nbins; j += step)
+                    if (h[(size_t)j] < clim) {
+                        ++raised;
+                        if (++h[(size_t)j] == clim) --under;
+                    }
+                n_excess -= raised;
+                if (n_excess <= 0) break;
+            }
+            if (prev == n_excess) break;
+        }
+        uint16_t* dst = maps + t * nbins;
+        int64_t cum = 0;
+        for (int b = 0; b < nbins; ++b) {
+            cum += h[(size_t)b];
+            double out = (double)cum * scale;
+            if (out > 16383.0) out = 16383.0;
+            dst[b] = (uint16_t)(int64_t)out;
+        }
+    }
+    return MMX_OK;
+}

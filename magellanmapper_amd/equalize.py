@@ -1,0 +1,503 @@
+"""Whole-image preprocessing on the device: ``saturate`` and ``remap`` of ``mm <img> --proc preprocess=...``.
+
+Mirror of ``plot_3d.saturate_roi`` (reference magmap/plot/plot_3d.py:55-111) and ``plot_3d.remap_intensity`` (:270-317)
+-> ``skimage.exposure.equalize_adapthist`` as ``transformer.preprocess_img`` runs them over a whole stack
+(magmap/atlas/transformer.py:353-393), bit for bit, quirks included.  The passes over the voxels are HIP kernels
+(``csrc/mmx_clahe.hip``); everything that acts on a few thousand values is stated here in NumPy's own expressions and
+uploaded as a table, so that no device arithmetic has to be pinned for it:
+
+* the chain voxel -> ``img_as_uint`` -> 14-bit level -> histogram bin is a function of the raw value for the 8- and
+  16-bit types and of ``img_as_uint(voxel)`` for float voxels: :func:`level_bin_table`, 65536 entries, built once the
+  image's minimum and maximum are known (``mmx_minmax_batch``).  The kernels' share is the table index
+  (:func:`key_of_values`): the value, ``value + 32768`` for int16, ``rint(v * 65535)`` clipped for floats;
+* ``clip_histogram`` / ``map_histogram`` are tiles x nbins integers of work between two launches: a native host
+  function (``mmx_host_eq_maps``), exact by construction (the reference's integer loop, statement by statement);
+* the per-axis interpolation tables (:func:`axis_tables`): which two tiles' maps stand below and above a coordinate,
+  and the coefficients ``arange(k) / k`` and ``1 - arange(k) / k``;
+* ``img_as_float`` and the last ``rescale_intensity`` act on at most 16384 levels: :func:`output_table`, from the
+  measured minimum and maximum of the uint16 result, the constant-image branch included.
+
+The float64 result leaves the device in z-slabs of at most :data:`SLAB_BYTES`, straight into the array given as
+``out`` (``transformer.preprocess_img`` hands the output file's memory map).  Between the tasks of a chain a float64
+single-result image stays on the device.
+
+Stated limits (``NotImplementedError``, from the arguments, ahead of any launch): ``nbins > 16384``; a tile of 2^31
+voxels or more; ``saturate`` of a float32 image unless ``preprocess.FLOAT32_RULES = "numpy2"``; an image that does not
+fit the device beside its working buffers.  A NaN voxel is outside the contract (the reference's result for one is
+whatever the platform's float -> uint16 cast gives).  The fixture pins scikit-image 0.18.3.
+"""
+from __future__ import annotations
+
+import ctypes
+import numbers
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+
+try:
+    import torch
+except ImportError:  # pragma: no cover
+    torch = None
+
+from . import _native as nat
+from . import config
+
+NR_OF_GRAY = 2 ** 14
+#: most bins of an equalisation (a bin per 14-bit level)
+MAX_NBINS = NR_OF_GRAY
+#: bytes of one z-slab of the float64 result on its way to the host
+SLAB_BYTES = 256 << 20
+
+
+# ------------------------------------------------------------------------------------------------- host tables
+def key_of_values(values: np.ndarray) -> np.ndarray:
+    """The table index the kernels form for voxels of ``values``' type (``eq_key`` of csrc/mmx_clahe.hip)."""
+    values = np.asarray(values)
+    dt = values.dtype
+    if dt in (np.uint8, np.uint16):
+        return values.astype(np.int64)
+    if dt == np.int16:
+        return values.astype(np.int64) + 32768
+    if dt.kind == "f":
+        out = np.multiply(values, 65535, dtype=dt)
+        np.rint(out, out=out)
+        np.clip(out, 0, 65535, out=out)
+        return out.astype(np.int64)
+    raise NotImplementedError(f"equalisation of {dt} images is not built")
+
+
+def uint_of_keys(dtype) -> np.ndarray:
+    """``img_as_uint`` of the voxel behind every table index, as scikit-image's ``_convert`` computes it: 65536
+    entries (uint8: the first 256 are read)."""
+    dtype = np.dtype(dtype)
+    out = np.zeros(65536, dtype=np.uint16)
+    if dtype == np.uint8:
+        # _scale(a, 8, 16): an exact upscale by (2**16 - 1) // (2**8 - 1)
+        out[:256] = np.multiply(np.arange(256, dtype=np.uint8), 257, dtype=np.uint16)
+    elif dtype == np.int16:
+        # _scale(a, 15, 16): up to 30 bits in int32, down by 14 bits, then np.maximum(., 0) into uint16
+        b = np.multiply(np.arange(-32768, 32768, dtype=np.int32).astype(np.int16), (2 ** 30 - 1) // (2 ** 15 - 1),
+                        dtype=np.int32)
+        b //= 2 ** 14
+        out[:] = np.maximum(b, 0).astype(np.uint16)
+    elif dtype == np.uint16 or dtype.kind == "f":
+        out[:] = np.arange(65536, dtype=np.uint16)     # (a float voxel's index IS its img_as_uint)
+    else:
+        raise NotImplementedError(f"equalisation of {dtype} images is not built")
+    return out
+
+
+def level_bin_table(dtype, raw_min, raw_max, nbins: int) -> Tuple[np.ndarray, np.ndarray]:
+    """``(levels, bins)``, 65536 uint16 entries each, by table index: the 14-bit level
+    ``np.round(rescale_intensity(img_as_uint(image), out_range=(0, 16383))).astype(np.uint16)`` of a voxel of an image
+    whose raw extremes are ``raw_min`` / ``raw_max`` (``img_as_uint`` is monotonic: the converted extremes are the
+    conversions of these two), and its histogram bin ``level // (1 + 16384 // nbins)``."""
+    dtype = np.dtype(dtype)
+    u = uint_of_keys(dtype)
+    kmin, kmax = (int(key_of_values(np.array([v], dtype=dtype))[0]) for v in (raw_min, raw_max))
+    imin, imax = float(u[kmin]), float(u[kmax])
+    img = np.clip(u.astype(np.float64), imin, imax)
+    if imin != imax:
+        img = (img - imin) / (imax - imin)
+        img = img * (float(NR_OF_GRAY - 1) - 0.0) + 0.0
+    else:
+        img = np.clip(img, 0.0, float(NR_OF_GRAY - 1))
+    levels = np.round(img).astype(np.uint16)
+    lut = np.arange(NR_OF_GRAY)
+    lut //= 1 + NR_OF_GRAY // int(nbins)
+    return levels, lut[levels].astype(np.uint16)
+
+
+def output_table(lmin: int, lmax: int) -> np.ndarray:
+    """``rescale_intensity(img_as_float(image))`` for every uint16 level below 16384 of an image whose ``_clahe`` result
+    has the minimum ``lmin`` and the maximum ``lmax``; a constant image comes back constant (clipped to [0, 1])."""
+    lv = np.arange(NR_OF_GRAY, dtype=np.uint16)
+    img = np.multiply(lv, 1.0 / 65535, dtype=np.float64)
+    imin, imax = float(img[int(lmin)]), float(img[int(lmax)])
+    img = np.clip(img, imin, imax)
+    if imin != imax:
+        img = (img - imin) / (imax - imin)
+        return img * (1.0 - 0.0) + 0.0
+    return np.clip(img, 0.0, 1.0)
+
+
+def resolve_kernel(shape3: Sequence[int], kernel_size) -> Tuple[int, int, int]:
+    """``equalize_adapthist``'s kernel size: ``shape // 8`` by default, a number for every axis, or one per axis."""
+    if kernel_size is None:
+        kernel_size = tuple(int(s) // 8 for s in shape3)
+    elif isinstance(kernel_size, numbers.Number):
+        kernel_size = (kernel_size,) * len(shape3)
+    elif len(kernel_size) != len(shape3):
+        raise ValueError("Incorrect value of `kernel_size`: {}".format(kernel_size))
+    return tuple(int(k) for k in kernel_size)
+
+
+def plan(shape3: Sequence[int], kernel_size, clip_limit, nbins):
+    """``(kernel, tiles per axis, clip count)`` of one equalisation, and every refusal that follows from the
+    arguments alone.  An axis shorter than 8 with the default kernel gives a kernel of 0 and the reference's
+    ``ZeroDivisionError`` (raised by the same expression)."""
+    shape3 = tuple(int(s) for s in shape3)
+    if len(shape3) != 3:
+        raise ValueError("equalize_adapthist takes one (z, y, x) channel")
+    nbins = int(nbins)
+    if nbins > MAX_NBINS:
+        raise NotImplementedError(f"nbins = {nbins}: more bins than the {MAX_NBINS} grey levels are not built")
+    if nbins < 1:
+        raise ValueError("nbins must be positive")
+    k = resolve_kernel(shape3, kernel_size)
+    # (_clahe's padding: the expression that fails for a kernel of 0)
+    pad_end = [(kk - s % kk) % kk + int(np.ceil(kk / 2.)) for kk, s in zip(k, shape3)]
+    if min(k) < 1:
+        raise ValueError(f"kernel_size must be positive, not {k}")
+    n_pixels = int(np.prod(k, dtype=object))
+    if n_pixels >= 2 ** 31:
+        raise NotImplementedError(f"a tile of {n_pixels} voxels (kernel_size {k}): 2^31 and more are not built")
+    del pad_end
+    nt = tuple(-(-s // kk) for s, kk in zip(shape3, k))
+    if clip_limit > 0.0:
+        clim = int(np.clip(clip_limit * np.prod(k, dtype=np.int64), 1, None))
+    else:
+        clim = n_pixels
+    return k, nt, clim
+
+
+def axis_tables(shape3, k, nt) -> Tuple[np.ndarray, np.ndarray]:
+    """``(tiles, coef)``, ``[nz + ny + nx][2]`` each: coordinate ``c`` of an axis lies at offset ``o = (c + k // 2) % k``
+    of interpolation block ``b = (c + k // 2) // k`` of the padded image; the maps below and above it are those of the
+    histogram tiles ``b - 1`` and ``b``, clamped into ``[0, nt)`` (the edge padding of the map array), with the
+    coefficients ``1 - arange(k)[o] / k`` and ``arange(k)[o] / k``."""
+    tiles, coef = [], []
+    for s, kk, n in zip(shape3, k, nt):
+        c = np.arange(int(s), dtype=np.int64) + kk // 2
+        b, o = c // kk, c % kk
+        frac = (np.arange(kk) / kk)[o]
+        tiles.append(np.stack([np.clip(b - 1, 0, n - 1), np.clip(b, 0, n - 1)], axis=1))
+        coef.append(np.stack([1 - frac, frac], axis=1))
+    return (np.ascontiguousarray(np.concatenate(tiles), dtype=np.int32),
+            np.ascontiguousarray(np.concatenate(coef), dtype=np.float64))
+
+
+# --------------------------------------------------------------------------------------------------- the device
+def _free_device_bytes() -> int:
+    return int(torch.cuda.mem_get_info()[0])
+
+
+def _check_fits(need: int, what: str) -> None:
+    free = _free_device_bytes()
+    if need > 0.9 * free:
+        raise NotImplementedError(f"{what} needs {need} bytes on the device beside its working buffers, {free} are "
+                                  f"free: an image that does not fit the device is not built")
+
+
+def _stream() -> int:
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _to_dev(arr: np.ndarray, dev):
+    return torch.from_numpy(np.ascontiguousarray(arr).view(np.uint8).reshape(-1)).to(dev)
+
+
+def _ds_view(dv, channel: int) -> nat.DsView:
+    v = dv.view(channel, False)
+    return nat.DsView(v.d_data, v.dtype, 0, v.stride_z, v.stride_y, v.stride_x)
+
+
+def _as_volume(image, what: str, extra_per_voxel: int):
+    """``(DeviceVolume, owned)`` of a host array or a resident volume, after the fit check."""
+    from .volume import DeviceVolume
+    if isinstance(image, DeviceVolume):
+        if image.z_off or image.y_off or tuple(image.tensor.shape[:3]) != tuple(image.shape[:3]):
+            raise ValueError(f"a DeviceVolume that holds a box of its image cannot be {what}")
+        if image.np_dtype not in nat.NP_TO_MMX:
+            raise NotImplementedError(f"{what}: {image.np_dtype} images are not built")
+        _check_fits(int(np.prod(image.shape[:3], dtype=np.int64)) * extra_per_voxel, what)
+        image.wait_all()
+        return image, False
+    arr = image if isinstance(image, np.ndarray) else np.asarray(image)
+    if arr.dtype not in nat.NP_TO_MMX:
+        raise NotImplementedError(f"{what}: {arr.dtype} images are not built "
+                                  f"({', '.join(str(d) for d in nat.NP_TO_MMX)} are)")
+    if arr.ndim not in (3, 4):
+        raise ValueError("image must be (z, y, x) or (z, y, x, c)")
+    _check_fits(arr.nbytes + int(np.prod(arr.shape[:3], dtype=np.int64)) * extra_per_voxel, what)
+    dv = DeviceVolume(arr, streamed=False)
+    return dv, True
+
+
+def _minmax(dv, channel: int) -> Tuple[float, float]:
+    L = nat.lib()
+    dev = dv.tensor.device
+    nz, ny, nx = (int(v) for v in dv.shape[:3])
+    blocks = np.zeros(1, dtype=nat.BLOCK_DTYPE)
+    blocks[0] = (0, nz, ny, nx, 0, 0, 0)
+    d_blocks = _to_dev(blocks, dev)
+    d_mm = torch.tensor([np.inf, -np.inf], dtype=torch.float64, device=dev)
+    vol = dv.view(channel, False)
+    nat.check(L.mmx_minmax_batch(ctypes.byref(vol), d_blocks.data_ptr(), blocks.ctypes.data, 1, d_mm.data_ptr(),
+                                 _stream()), "mmx_minmax_batch")
+    lo, hi = d_mm.cpu().numpy()
+    return float(lo), float(hi)
+
+
+class _Sink:
+    """Where a float64 channel result goes, z-slab by z-slab: a host array (its own dtype: the assignment casts as
+    NumPy's does), or a float64 tensor that stays on the device for the next task of a chain."""
+
+    def __init__(self, host: Optional[np.ndarray], tensor):
+        self.host, self.tensor = host, tensor
+
+    def put(self, z0: int, z1: int, channel: Optional[int], slab) -> None:
+        if self.tensor is not None:
+            dst = self.tensor[z0:z1] if channel is None else self.tensor[z0:z1, ..., channel]
+            dst.copy_(slab)
+        else:
+            dst = self.host[z0:z1] if channel is None else self.host[z0:z1, ..., channel]
+            dst[...] = slab.cpu().numpy()
+
+
+def _resolve_out(out, shape, dtype) -> np.ndarray:
+    """The host array a result goes into: ``out`` itself, what the factory ``out(shape, dtype)`` makes once the
+    result's dtype is known, or a new array."""
+    if out is None:
+        return np.empty(shape, dtype=dtype)
+    if callable(out):
+        return out(tuple(shape), np.dtype(dtype))
+    if tuple(out.shape) != tuple(shape) or out.dtype != np.dtype(dtype):
+        raise ValueError(f"out must be {tuple(shape)} {np.dtype(dtype)}, not {tuple(out.shape)} {out.dtype}")
+    return out
+
+
+def _slabs(shape3) -> Tuple[int, int]:
+    nz, ny, nx = shape3
+    step = max(1, min(nz, SLAB_BYTES // max(1, ny * nx * 8)))
+    return step, (nz + step - 1) // step
+
+
+def _equalize_channel(dv, channel: int, kernel_size, clip_limit, nbins, sink: _Sink, sink_channel, parts=None) -> None:
+    """One channel through the passes; the float64 result goes to ``sink``."""
+    L = nat.lib()
+    dev = dv.tensor.device
+    shape3 = tuple(int(v) for v in dv.shape[:3])
+    k, nt, clim = plan(shape3, kernel_size, clip_limit, nbins)
+    nbins = int(nbins)
+    n_tiles = int(np.prod(nt))
+    n_vox = int(np.prod(shape3, dtype=np.int64))
+    stream = _stream()
+
+    raw_min, raw_max = _minmax(dv, channel)
+    if dv.np_dtype.kind == "f" and (raw_min < -1.0 or raw_max > 1.0):
+        raise ValueError("Images of type float must be between -1 and 1.")
+    levels, bins = level_bin_table(dv.np_dtype, raw_min, raw_max, nbins)
+    d_bins = _to_dev(bins, dev)
+    src = _ds_view(dv, channel)
+    geom = nat.EqGeom((ctypes.c_int32 * 3)(*shape3), (ctypes.c_int32 * 3)(*k), (ctypes.c_int32 * 3)(*nt), nbins)
+
+    d_hist = torch.empty(n_tiles * nbins, dtype=torch.int32, device=dev)
+    nat.check(L.mmx_eq_hist(ctypes.byref(src), ctypes.byref(geom), d_bins.data_ptr(), d_hist.data_ptr(), stream),
+              "mmx_eq_hist")
+    hist = d_hist.cpu().numpy().view(np.uint32)
+    maps = np.empty(n_tiles * nbins, dtype=np.uint16)
+    entered = np.zeros(n_tiles, dtype=np.uint8)
+    nat.check(L.mmx_host_eq_maps(hist.ctypes.data, n_tiles, nbins, clim, int(np.prod(k)), maps.ctypes.data,
+                                 entered.ctypes.data), "mmx_host_eq_maps")
+    d_maps = _to_dev(maps, dev)
+    tiles, coef = axis_tables(shape3, k, nt)
+    d_tiles, d_coef = _to_dev(tiles, dev), _to_dev(coef, dev)
+    d_out = torch.empty(n_vox, dtype=torch.int16, device=dev)
+    d_mm = torch.empty(2, dtype=torch.int32, device=dev)
+    nat.check(L.mmx_eq_apply(ctypes.byref(src), ctypes.byref(geom), d_bins.data_ptr(), d_maps.data_ptr(),
+                             d_tiles.data_ptr(), tiles.ctypes.data, d_coef.data_ptr(), d_out.data_ptr(),
+                             d_mm.data_ptr(), stream), "mmx_eq_apply")
+    lmin, lmax = (int(v) for v in d_mm.cpu().numpy().view(np.uint32))
+    if parts is not None:
+        parts.update(kernel=k, tiles=nt, clim=clim, levels_table=levels, bins_table=bins,
+                     hist=hist.reshape(n_tiles, nbins).copy(), maps=maps.reshape(n_tiles, nbins).copy(),
+                     entered=entered.astype(bool), clahe=d_out.cpu().numpy().view(np.uint16).reshape(shape3),
+                     minmax=(lmin, lmax))
+    d_table = _to_dev(output_table(lmin, lmax), dev)
+    nz, ny, nx = shape3
+    step, _ = _slabs(shape3)
+    slab = torch.empty(step * ny * nx, dtype=torch.float64, device=dev)
+    for z0 in range(0, nz, step):
+        z1 = min(nz, z0 + step)
+        n = (z1 - z0) * ny * nx
+        nat.check(L.mmx_eq_output(d_out.data_ptr() + 2 * z0 * ny * nx, n, d_table.data_ptr(), slab.data_ptr(), stream),
+                  "mmx_eq_output")
+        sink.put(z0, z1, sink_channel, slab[:n].view(z1 - z0, ny, nx))
+    torch.cuda.current_stream().synchronize()
+
+
+def equalize_adapthist(image, kernel_size=None, clip_limit=0.01, nbins=256, out=None, parts=None):
+    """``skimage.exposure.equalize_adapthist`` of one ``(z, y, x)`` channel -- a NumPy array or a single-channel
+    ``DeviceVolume`` of any of the five voxel types: the float64 result, written into ``out`` when given (an array or
+    a memory map of the image's shape).  ``parts`` (a dict, for tests and tools) receives the intermediates: the tile
+    histograms, the clipped maps, the uint16 image ``_clahe`` returns."""
+    shape = tuple(image.shape)
+    if len(shape) != 3:
+        raise ValueError("equalize_adapthist takes one (z, y, x) channel")
+    plan(shape, kernel_size, clip_limit, nbins)                   # (every refusal, ahead of the device)
+    if out is not None and (tuple(out.shape) != shape or out.dtype != np.float64):
+        raise ValueError(f"out must be {shape} float64, not {tuple(out.shape)} {out.dtype}")
+    dv, owned = _as_volume(image, "equalize_adapthist", 2 + 2)
+    try:
+        host = out if out is not None else np.empty(shape, dtype=np.float64)
+        _equalize_channel(dv, 0, kernel_size, clip_limit, nbins, _Sink(host, None), None, parts)
+    finally:
+        if owned:
+            dv.close()
+    return host
+
+
+def _is_seq(val) -> bool:
+    return isinstance(val, (list, tuple)) or np.ndim(val) != 0
+
+
+def _get_if_within(val, i, default=None):
+    """``libmag.get_if_within``: element ``i`` of a sequence (``default`` beyond its end), a scalar as it is."""
+    if not _is_seq(val):
+        return val
+    if len(val) > i:
+        return val[i]
+    return default
+
+
+def _setup_channels(shape, channel):
+    """``plot_3d.setup_channels`` with the channel axis at 3."""
+    multichannel = len(shape) > 3
+    if multichannel:
+        return True, (range(shape[3]) if channel is None else channel)
+    return False, [0]
+
+
+def _host_copy(image) -> np.ndarray:
+    from .volume import DeviceVolume
+    if isinstance(image, DeviceVolume):
+        image.wait_all()
+        return image.tensor.cpu().numpy()
+    return np.copy(image)
+
+
+def remap_intensity(roi, channel=None, _keep=False, _out=None, **kwargs):
+    """``plot_3d.remap_intensity``: adaptive histogram equalisation of the channels in ``channel`` (``None``: all).
+    ``clip_limit`` defaults to the FIRST processed channel's ``adapt_hist_lim`` and then holds for the later ones;
+    every keyword may be a sequence indexed by the channel NUMBER.  A single-channel image returns the float64
+    result; a multichannel one returns a copy in the IMAGE's dtype with the float64 results stored into it (an
+    integer image keeps 0 and 1) and the other channels untouched."""
+    shape = tuple(roi.shape)
+    multichannel, channels = _setup_channels(shape, channel)
+    todo = []
+    for chl in channels:
+        if "clip_limit" not in kwargs:
+            kwargs["clip_limit"] = config.get_roi_profile(chl)["adapt_hist_lim"]
+        args = {key: _get_if_within(v, chl) for key, v in kwargs.items()}
+        unknown = set(args) - {"kernel_size", "clip_limit", "nbins"}
+        if unknown:
+            raise TypeError(f"equalize_adapthist() got an unexpected keyword argument '{sorted(unknown)[0]}'")
+        args = dict(kernel_size=args.get("kernel_size"), clip_limit=args.get("clip_limit", 0.01),
+                    nbins=args.get("nbins", 256))
+        plan(shape[:3], **args)
+        todo.append((chl, args))
+    dv, owned = _as_volume(roi, "remap_intensity", 2 + 2 + (8 if _keep and not multichannel else 0))
+    try:
+        if not multichannel:
+            if _keep:
+                sink = _Sink(None, torch.empty(shape, dtype=torch.float64, device=dv.tensor.device))
+            else:
+                sink = _Sink(_resolve_out(_out, shape, np.float64), None)
+            _equalize_channel(dv, 0, sink=sink, sink_channel=None, **todo[0][1])
+            return sink.tensor if _keep else sink.host
+        if _out is not None:
+            host = _resolve_out(_out, shape, dv.np_dtype)
+            host[...] = _host_copy(roi)
+        else:
+            host = _host_copy(roi)
+        sink = _Sink(host, None)
+        for chl, args in todo:
+            _equalize_channel(dv, chl, sink=sink, sink_channel=chl, **args)
+        return host
+    finally:
+        if owned:
+            dv.close()
+
+
+def _saturate_dtype_ok(dtype) -> bool:
+    from . import importer
+    return importer._bounds_dtype_ok(dtype)
+
+
+def saturate_roi(roi, clip_vmin=-1, clip_vmax=-1, max_thresh_factor=-1, channel=None, _keep=False, _out=None):
+    """``plot_3d.saturate_roi`` of a whole ``(z, y, x[, c])`` image: per channel ``vmin, vmax = np.percentile(chl,
+    (clip_vmin, clip_vmax))`` (the profile's values for -1; the order statistics by radix select on the device), the
+    channel unchanged where they are equal, otherwise ``vmax = max(vmax, near_max[chl] * max_thresh_factor)`` and
+    ``(np.clip(chl, vmin, vmax) - vmin) / (vmax - vmin)`` in float64.  A multichannel result has the dtype of the
+    first processed channel's result, and channels not named stay zero."""
+    from . import importer
+    shape = tuple(roi.shape)
+    dtype = np.dtype(getattr(roi, "np_dtype", None) or roi.dtype)
+    if dtype == np.float32 and not _saturate_dtype_ok(dtype):
+        raise NotImplementedError('saturate of a float32 image depends on the NumPy release: set '
+                                  'preprocess.FLOAT32_RULES = "numpy2" for the rules the reference pins')
+    if not _saturate_dtype_ok(dtype):
+        raise NotImplementedError(f"saturate of {dtype} images ({importer._BOUNDS_NAMES})")
+    multichannel, channels = _setup_channels(shape, channel)
+    dv, owned = _as_volume(roi, "saturate_roi", 8 * (shape[3] if multichannel else 1) if _keep else 0)
+    try:
+        L = nat.lib()
+        dev = dv.tensor.device
+        nz, ny, nx = (int(v) for v in shape[:3])
+        sink = None
+        for chl in channels:
+            settings = config.get_roi_profile(chl)
+            vmin_pct = settings["clip_vmin"] if clip_vmin == -1 else clip_vmin
+            vmax_pct = settings["clip_vmax"] if clip_vmax == -1 else clip_vmax
+            factor = settings["max_thresh_factor"] if max_thresh_factor == -1 else max_thresh_factor
+            lo, hi = importer._percentiles_of_groups(dv, chl, [(0, nz)], vmin_pct, vmax_pct)
+            vmin, vmax = lo[0], hi[0]
+            stretched = vmin != vmax
+            if stretched:
+                max_thresh = config.near_max[chl] * factor
+                if vmax < max_thresh:
+                    vmax = max_thresh
+            if sink is None:
+                # (the first processed channel decides the result's dtype)
+                res_dtype = np.dtype(np.float64) if stretched else dtype
+                if not multichannel and not stretched:
+                    if _out is not None:
+                        host = _resolve_out(_out, shape, dtype)
+                        host[...] = _host_copy(roi)
+                        return host
+                    return dv.tensor if _keep else _host_copy(roi)
+                if _keep and res_dtype == np.float64:
+                    t = (torch.zeros if multichannel else torch.empty)(shape, dtype=torch.float64, device=dev)
+                    sink = _Sink(None, t)
+                else:
+                    host = _resolve_out(_out, shape, res_dtype)
+                    if multichannel:
+                        host[...] = 0
+                    sink = _Sink(host, None)
+            c_sink = chl if multichannel else None
+            if not stretched:
+                # (an unchanged channel behind a stretched one: stored with NumPy's cast into the result's dtype)
+                src = (dv.tensor[..., chl] if multichannel else dv.tensor).cpu().numpy()
+                if sink.tensor is not None:
+                    sink.put(0, nz, c_sink, torch.from_numpy(np.ascontiguousarray(src, dtype=np.float64)).to(dev))
+                else:
+                    (sink.host[..., chl] if multichannel else sink.host)[...] = src
+                continue
+            step, _ = _slabs((nz, ny, nx))
+            slab = torch.empty(step * ny * nx, dtype=torch.float64, device=dev)
+            v = dv.view(chl, False)
+            for z0 in range(0, nz, step):
+                z1 = min(nz, z0 + step)
+                esize = dv.tensor.element_size()
+                src = nat.DsView(v.d_data + z0 * v.stride_z * esize, v.dtype, 0, v.stride_z, v.stride_y, v.stride_x)
+                nat.check(L.mmx_stretch(ctypes.byref(src), z1 - z0, ny, nx, float(vmin), float(vmax), slab.data_ptr(),
+                                        _stream()), "mmx_stretch")
+                sink.put(z0, z1, c_sink, slab[:(z1 - z0) * ny * nx].view(z1 - z0, ny, nx))
+            torch.cuda.current_stream().synchronize()
+        if sink is None:
+            return None                     # (no channel processed: the reference returns None)
+        return sink.tensor if sink.tensor is not None else sink.host
+    finally:
+        if owned:
+            dv.close()

@@ -285,6 +285,22 @@ def calc_intensity_bounds(image5d, lower=0.5, upper=99.5, dim_channel=4):
     return lows, highs
 
 
+def save_np_image(image, filename, series=None):
+    """Save an image as ``<base>_image5d.npy`` with its ``<base>_meta.yml`` (importer.py:1471-1497): the metadata comes
+    from the settings in :mod:`config`, the near minimum / maximum from :func:`calc_intensity_bounds` of the image."""
+    filename_image5d, filename_info = make_filenames(filename, series)
+    with open(filename_image5d, "wb") as out_file:
+        np.save(out_file, image)
+    lows, highs = calc_intensity_bounds(image)
+    save_image_info(filename_info, [os.path.basename(filename)], [image.shape], config.resolutions,
+                    config.magnification, config.zoom, lows, highs)
+
+
+def roi_to_image5d(roi):
+    """An ROI in image5d format: a time axis in front (importer.py:1537-1547)."""
+    return roi[None]
+
+
 def calc_scaling(image5d, scaled, image5d_shape=None, scaled_shape=None) -> np.ndarray:
     """``z, y, x`` factors from an image to its rescaled copy (importer.py:1500-1535): shapes of four axes and more
     lose their time axis first; either array may be ``None`` when its shape is given."""

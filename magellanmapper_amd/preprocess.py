@@ -1030,3 +1030,7 @@ def preprocess_roi(roi, denoise_max_shape, channel: Optional[Sequence[int]] = No
     if out is None:
         out = np.zeros(dvol.shape, dtype=np.float64)
     return (out, infos) if return_info else out
+
+
+# ---- whole-image tasks of ``transformer.preprocess_img`` (``--proc preprocess=saturate,remap``): :mod:`equalize`
+from .equalize import equalize_adapthist, remap_intensity, saturate_roi  # noqa: E402,F401

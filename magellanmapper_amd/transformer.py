@@ -22,7 +22,11 @@ Host images larger than the device go up one layer of chunks at a time (:data:`L
 is started before the current layer's kernels and waited for only ahead of its own first kernel, so a streamed upload
 (a large read-only memory map cut along z or y) runs beside them; the device then holds two layers, the passes'
 intermediates and the output volume, which is copied out once.  Other sources go up synchronously, layer after layer.
-``rotate_img`` / ``preprocess_img``, ``order=0`` label images and registration stay in the reference.
+
+``preprocess_img`` (reference transformer.py:353-393, ``--proc preprocess=saturate,remap``) runs the whole-image tasks of
+:mod:`equalize` in the order given and writes ``<base>_image5d.npy`` slab by slab; the tasks ``denoise`` and ``rotate``
+are refused by name.  ``rotate_img``, the ``denoise`` task on a whole image, ``order=0`` label images and registration
+stay in the reference.
 """
 from __future__ import annotations
 
@@ -583,3 +587,80 @@ def transpose_img(filename: str, series: Optional[int], plane: Optional[str] = N
     print("saved transposed file to {} with shape {}".format(filename_image5d, image5d_transposed.shape))
     print("time elapsed (s): {}".format(time.time() - time_start))
     return image5d_transposed
+
+
+# ------------------------------------------------------------------------------------------------ preprocess_img
+def _get_enum(s, enum_class):
+    """``libmag.get_enum``: the member named ``s`` (any case), ``None`` when there is none."""
+    if s:
+        try:
+            return enum_class[s.upper()]
+        except (AttributeError, KeyError):
+            pass
+    return None
+
+
+def preprocess_img(image5d, preprocs, channel, out_path):
+    """``transformer.preprocess_img`` (reference transformer.py:353-393): run the whole-image tasks ``preprocs`` (names
+    of ``config.PreProcessKeys``, one or a sequence) on ``image5d[0]`` in the order given, each on the previous result,
+    for ``channel`` (``None``: all), and write ``<out_path base>_image5d.npy`` with its ``_meta.yml`` (the settings in
+    :mod:`config`, the intensity bounds of the result).  ``saturate`` and ``remap`` run on the device
+    (:mod:`equalize`); ``denoise`` and ``rotate`` are a ``NotImplementedError`` before anything runs; a name that is
+    no task is skipped with a warning.  The last task's result goes z-slab by z-slab into the memory map of the output
+    file, which is returned (``(1, z, y, x[, c])``); between tasks a float64 image stays on the device.  ``None``
+    for ``preprocs`` prints and returns ``None``."""
+    import os
+    from . import equalize
+    from .volume import DeviceVolume
+    if preprocs is None:
+        print("No preprocessing tasks to perform, skipping")
+        return None
+    if not (isinstance(preprocs, (list, tuple)) or np.ndim(preprocs) != 0):
+        preprocs = [preprocs]
+    tasks = []
+    for preproc in preprocs:
+        task = _get_enum(preproc, config.PreProcessKeys)
+        if task in (config.PreProcessKeys.DENOISE, config.PreProcessKeys.ROTATE):
+            raise NotImplementedError(f"the whole-image task {task.name.lower()!r} stays in the reference "
+                                      f"(saturate and remap are built)")
+        if task is None:
+            config.logger.warning("No preprocessing task found for: %s", preproc)
+        else:
+            tasks.append(task)
+
+    # a float32 image that leaves as float32 (no task, or `remap` alone on several channels) has its intensity bounds
+    # measured in float32: refused here, ahead of the tasks, unless preprocess.FLOAT32_RULES names the NumPy release
+    if (np.dtype(image5d.dtype) == np.float32 and config.PreProcessKeys.SATURATE not in tasks
+            and (not tasks or image5d.ndim > 4) and not importer._bounds_dtype_ok(np.float32)):
+        raise NotImplementedError(f"percentiles of float32 images ({importer._BOUNDS_NAMES}; float32 once "
+                                  f"preprocess.FLOAT32_RULES names the NumPy release)")
+
+    filename_image5d, filename_info = importer.make_filenames(out_path)
+    made = []
+
+    def make_out(shape, dtype):
+        mm = np.lib.format.open_memmap(filename_image5d, mode="w+", dtype=dtype, shape=(1,) + tuple(shape))
+        made.append(mm)
+        return mm[0]
+
+    roi = image5d[0]
+    for i, task in enumerate(tasks):
+        config.logger.info("Pre-processing task: %s", task)
+        last = i == len(tasks) - 1
+        kw = dict(_out=make_out) if last else dict(_keep=True)
+        if task is config.PreProcessKeys.SATURATE:
+            roi = equalize.saturate_roi(roi, channel=channel, **kw)
+        else:
+            roi = equalize.remap_intensity(roi, channel, **kw)
+        if torch is not None and isinstance(roi, torch.Tensor):
+            roi = DeviceVolume(roi)
+    if not made:
+        # (no task ran, or the last one handed the image through unchanged: the image as it stands)
+        host = roi.tensor.cpu().numpy() if isinstance(roi, DeviceVolume) else roi
+        make_out(host.shape, host.dtype)[...] = host
+    image5d_out = made[-1]
+    image5d_out.flush()
+    lows, highs = importer.calc_intensity_bounds(image5d_out)
+    importer.save_image_info(filename_info, [os.path.basename(out_path)], [image5d_out.shape], config.resolutions,
+                             config.magnification, config.zoom, lows, highs)
+    return image5d_out
