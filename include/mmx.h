@@ -1055,6 +1055,28 @@ int mmx_eq_apply(const mmx_ds_view* src, const mmx_eq_geom* g, const uint16_t* d
 int mmx_eq_output(const uint16_t* d_levels, int64_t n, const double* d_table, double* d_out, void* stream);
 int mmx_stretch(const mmx_ds_view* src, int nz, int ny, int nx, double vmin, double vmax, double* d_out, void* stream);
 
+/* ---- P2: whole-image rotation (added to ABI v21 without a version step: a library without it lacks the symbols)
+ * replaces: cv_nd.rotate_nd as transformer.rotate_img chains it (magmap/cv/cv_nd.py:81-144, magmap/atlas/
+ * transformer.py:326-350) = skimage.transform.rotate(plane, angle, order=order, mode="constant", preserve_range=True,
+ * resize=False) of every plane along `axis` (0: z, 1: y, 2: x) of an (nz, ny, nx) volume of n_chl channels.  Bit-equal to
+ * scikit-image 0.18.  `src` / `dst`: channel 0 of the image through its strides; the channels of a voxel lie at the
+ * n_chl consecutive elements from there (no stride may be shorter than n_chl).  src_elems / dst_elems: elements behind
+ * d_data; a box that reaches beyond either is MMX_ERR_ARG and nothing is launched.
+ * mmx_rotate_minmax : d_bounds[n_planes][2] float64 = every plane's minimum and maximum over all of its channels, any
+ *                     of the five voxel types, one pass.
+ * mmx_rotate_warp   : every voxel of `dst` (a second buffer of the same voxel type: MMX_ERR_ARG for the source itself).
+ *                     matrix[6] (host): the first two rows of rotate's matrix T(center) R T(-center), rounded to float32
+ *                     by the caller for MMX_F32.  Output pixel (tr, tc) reads c = M0 tc + M1 tr + M2, r = M3 tc + M4 tr +
+ *                     M5, nothing fused.  order 1: the bilinear mix of floor / ceil, 0 outside the plane, clipped to
+ *                     d_bounds with exact zeros put back when 0 lies outside the range, cast by truncation; MMX_U8,
+ *                     MMX_U16, MMX_I16, MMX_F64.  order 0: the pixel at scikit-image's round, (index)(v > 0 ? v + .5 :
+ *                     v - .5) with the sum in float64; no clip, d_bounds unused (may be NULL); MMX_F32 as well, with
+ *                     float32 coordinates.  Any other order, and MMX_F32 at order 1: MMX_ERR_UNSUPPORTED. */
+int mmx_rotate_minmax(const mmx_ds_view* src, int64_t src_elems, int nz, int ny, int nx, int n_chl, int axis,
+                      double* d_bounds, void* stream);
+int mmx_rotate_warp(const mmx_ds_view* src, int64_t src_elems, const mmx_ds_view* dst, int64_t dst_elems, int nz, int ny,
+                    int nx, int n_chl, int axis, const double* matrix, int order, const double* d_bounds, void* stream);
+
 /* PMC calibration (tools/pmc_calib.py): one streaming launch over n_elems elements with a known
  * byte count.  kind 0: float copy, 4 B per lane; 1: float copy, 16 B per lane; 2: uint16 read. */
 int mmx_calib_stream(int kind, const void* d_in, void* d_out, int64_t n_elems, void* stream);

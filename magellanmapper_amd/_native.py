@@ -203,6 +203,7 @@ SYMBOLS = (
     "mmx_order_stats_workspace", "mmx_order_stats", "mmx_extract_patches",
     "mmx_ds_zoom_batch", "mmx_ds_gauss_pick_batch",
     "mmx_eq_hist", "mmx_host_eq_maps", "mmx_eq_apply", "mmx_eq_output", "mmx_stretch",
+    "mmx_rotate_minmax", "mmx_rotate_warp",
 )
 KERNEL_KINDS = ("zpass", "ypass", "xpass", "generic", "peaks", "rescore", "overlap_pairs",
                 "close_pairs", "zxpass", "y2pass", "preproc", "coloc", "zxpack", "widepass")
@@ -364,6 +365,11 @@ def lib() -> ctypes.CDLL:
     L.mmx_eq_output.restype = c_int
     L.mmx_stretch.argtypes = [POINTER(DsView), c_int, c_int, c_int, c_double, c_double, vp, vp]
     L.mmx_stretch.restype = c_int
+    L.mmx_rotate_minmax.argtypes = [POINTER(DsView), c_int64, c_int, c_int, c_int, c_int, c_int, vp, vp]
+    L.mmx_rotate_minmax.restype = c_int
+    L.mmx_rotate_warp.argtypes = [POINTER(DsView), c_int64, POINTER(DsView), c_int64, c_int, c_int, c_int, c_int, c_int,
+                                  POINTER(c_double), c_int, vp, vp]
+    L.mmx_rotate_warp.restype = c_int
     L.mmx_preprocess_batch.restype = c_int
     L.mmx_preprocess_batch_mode.restype = c_int
     L.mmx_preprocess_batch_generic.restype = c_int

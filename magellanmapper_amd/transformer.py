@@ -23,10 +23,11 @@ is started before the current layer's kernels and waited for only ahead of its o
 (a large read-only memory map cut along z or y) runs beside them; the device then holds two layers, the passes'
 intermediates and the output volume, which is copied out once.  Other sources go up synchronously, layer after layer.
 
-``preprocess_img`` (reference transformer.py:353-393, ``--proc preprocess=saturate,remap``) runs the whole-image tasks of
-:mod:`equalize` in the order given and writes ``<base>_image5d.npy`` slab by slab; the tasks ``denoise`` and ``rotate``
-are refused by name.  ``rotate_img``, the ``denoise`` task on a whole image, ``order=0`` label images and registration
-stay in the reference.
+``preprocess_img`` (reference transformer.py:353-393, ``--proc preprocess=saturate,remap,rotate``) runs the whole-image
+tasks of :mod:`equalize` and ``rotate_img`` (:mod:`rotate`: the atlas profile's chain of plane rotations, two streaming
+passes per rotation) in the order given and writes ``<base>_image5d.npy`` slab by slab; the task ``denoise`` is refused
+by name, and so is ``rotate`` while no atlas profile is set.  The ``denoise`` task on a whole image, setting up atlas
+profiles, ``order=0`` label images in ``transpose_img`` and registration stay in the reference.
 """
 from __future__ import annotations
 
@@ -600,17 +601,45 @@ def _get_enum(s, enum_class):
     return None
 
 
+def rotate_img(roi, rotate=None, order=None, _keep=False, _out=None):
+    """``transformer.rotate_img`` (reference transformer.py:326-350): ``roi`` (z, y, x[, c]) through the rotations
+    ``rotate["rotation"] = ((angle, axis), ...)`` in order, each on the previous result (``cv_nd.rotate_nd``), at the
+    interpolation ``order`` (``None``: ``rotate["order"]``).  ``rotate=None`` reads ``config.atlas_profile["rotate"]``.
+    The volume stays on the device between the rotations and leaves it once; a host array comes back for a host array,
+    a ``DeviceVolume`` for a ``DeviceVolume``.  ``rotate["resize"]`` true, orders other than 0 and 1 and float32 at
+    order 1 are a ``NotImplementedError`` (:mod:`rotate`).  The one deliberate divergence: ``rotate["rotation"] = None``
+    (the profile's default: no rotation) returns a copy of the image unchanged, where the reference's loop fails on
+    ``None`` with a ``TypeError``."""
+    from . import rotate as rot
+    if rotate is None:
+        prof = getattr(config, "atlas_profile", None)
+        if prof is None:
+            raise NotImplementedError("rotate_img: no atlas profile is set (config.atlas_profile); setting up atlas "
+                                      "profiles stays in the reference: pass the rotate settings or set the profile")
+        rotate = prof["rotate"]
+    if order is None:
+        order = rotate["order"]
+    rotation = rotate["rotation"]
+    if rotation is None:
+        rotation = ()
+    for r in rotation:
+        print("rotating by", r)
+    return rot.rotate_chain(roi, rotation, order, rotate["resize"], "rotate_img", _keep, _out)
+
+
 def preprocess_img(image5d, preprocs, channel, out_path):
     """``transformer.preprocess_img`` (reference transformer.py:353-393): run the whole-image tasks ``preprocs`` (names
     of ``config.PreProcessKeys``, one or a sequence) on ``image5d[0]`` in the order given, each on the previous result,
     for ``channel`` (``None``: all), and write ``<out_path base>_image5d.npy`` with its ``_meta.yml`` (the settings in
-    :mod:`config`, the intensity bounds of the result).  ``saturate`` and ``remap`` run on the device
-    (:mod:`equalize`); ``denoise`` and ``rotate`` are a ``NotImplementedError`` before anything runs; a name that is
-    no task is skipped with a warning.  The last task's result goes z-slab by z-slab into the memory map of the output
-    file, which is returned (``(1, z, y, x[, c])``); between tasks a float64 image stays on the device.  ``None``
-    for ``preprocs`` prints and returns ``None``."""
+    :mod:`config`, the intensity bounds of the result).  ``saturate`` and ``remap`` (:mod:`equalize`) and ``rotate``
+    (:func:`rotate_img`, all channels, the settings of ``config.atlas_profile``) run on the device; ``denoise`` is a
+    ``NotImplementedError`` before anything runs, and so is ``rotate`` without an atlas profile or with settings
+    :func:`rotate_img` refuses; a name that is no task is skipped with a warning.  The last task's result goes z-slab by
+    z-slab into the memory map of the output file, which is returned (``(1, z, y, x[, c])``); between tasks the image
+    stays on the device.  ``None`` for ``preprocs`` prints and returns ``None``."""
     import os
     from . import equalize
+    from . import rotate as rot
     from .volume import DeviceVolume
     if preprocs is None:
         print("No preprocessing tasks to perform, skipping")
@@ -620,18 +649,28 @@ def preprocess_img(image5d, preprocs, channel, out_path):
     tasks = []
     for preproc in preprocs:
         task = _get_enum(preproc, config.PreProcessKeys)
-        if task in (config.PreProcessKeys.DENOISE, config.PreProcessKeys.ROTATE):
+        if task is config.PreProcessKeys.DENOISE:
             raise NotImplementedError(f"the whole-image task {task.name.lower()!r} stays in the reference "
-                                      f"(saturate and remap are built)")
+                                      f"(saturate, remap and rotate are built)")
+        if task is config.PreProcessKeys.ROTATE:
+            prof = getattr(config, "atlas_profile", None)
+            if prof is None:
+                raise NotImplementedError("the whole-image task 'rotate' reads config.atlas_profile, and none is set: "
+                                          "setting up atlas profiles stays in the reference")
+            if prof["rotate"]["rotation"] is not None:
+                # (what can be told ahead of the tasks: the voxel type only where the image arrives as it is)
+                rot.check_args(image5d.dtype if not tasks else np.float64, prof["rotate"]["order"],
+                               prof["rotate"]["resize"], "the whole-image task 'rotate'")
         if task is None:
             config.logger.warning("No preprocessing task found for: %s", preproc)
         else:
             tasks.append(task)
 
-    # a float32 image that leaves as float32 (no task, or `remap` alone on several channels) has its intensity bounds
-    # measured in float32: refused here, ahead of the tasks, unless preprocess.FLOAT32_RULES names the NumPy release
+    # a float32 image that leaves as float32 (no task, `rotate` alone, or `remap` on several channels) has its intensity
+    # bounds measured in float32: refused here, ahead of the tasks, unless preprocess.FLOAT32_RULES names the NumPy release
     if (np.dtype(image5d.dtype) == np.float32 and config.PreProcessKeys.SATURATE not in tasks
-            and (not tasks or image5d.ndim > 4) and not importer._bounds_dtype_ok(np.float32)):
+            and (config.PreProcessKeys.REMAP not in tasks or image5d.ndim > 4)
+            and not importer._bounds_dtype_ok(np.float32)):
         raise NotImplementedError(f"percentiles of float32 images ({importer._BOUNDS_NAMES}; float32 once "
                                   f"preprocess.FLOAT32_RULES names the NumPy release)")
 
@@ -650,6 +689,8 @@ def preprocess_img(image5d, preprocs, channel, out_path):
         kw = dict(_out=make_out) if last else dict(_keep=True)
         if task is config.PreProcessKeys.SATURATE:
             roi = equalize.saturate_roi(roi, channel=channel, **kw)
+        elif task is config.PreProcessKeys.ROTATE:
+            roi = rotate_img(roi, **kw)
         else:
             roi = equalize.remap_intensity(roi, channel, **kw)
         if torch is not None and isinstance(roi, torch.Tensor):

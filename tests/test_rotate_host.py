@@ -1,0 +1,169 @@
+"""Whole-image rotation without a device: the NumPy restatement against the fixture made from the real reference, the
+product's matrix function against the stored matrices bit for bit, every refusal that follows from the arguments, and
+what ``rotation=None`` and a missing atlas profile do."""
+import os
+
+import numpy as np
+import pytest
+
+import rotate_support as sup
+from conftest import load_golden
+from magellanmapper_amd import config, equalize, preprocess, transformer
+from magellanmapper_amd import rotate as rot
+
+
+@pytest.fixture(scope="module")
+def fx():
+    return load_golden("rotate.npz")
+
+
+@pytest.fixture(scope="module")
+def inputs(fx):
+    """Every stored case's input, regenerated from its seed and checked against the stored digest."""
+    out = {}
+    for kind, shape, seed, _, _, _ in sup.CASES:
+        if (kind, shape, seed) not in out:
+            img = sup.make_input(kind, shape, seed)
+            assert sup.sha(img) == str(fx["sha_%s_%s_%d" % (kind, "x".join(str(s) for s in shape), seed)])
+            out[(kind, shape, seed)] = img
+    return out
+
+
+def test_cases_cover_what_they_should():
+    names = [sup.case_name(c) for c in sup.CASES]
+    assert len(set(names)) == len(names)
+    for shape in (sup.SMALL, sup.ROW, sup.COL, sup.TILES):
+        assert {(c[3], c[4]) for c in sup.CASES if c[1] == shape} == {(a, o) for a in range(3) for o in (0, 1)}
+    assert {c[5] for c in sup.CASES} == set(sup.ANGLES)
+    assert {c[0] for c in sup.CASES} == set(sup.KINDS)
+    assert all(c[4] == 0 for c in sup.CASES if c[0] == "f32")
+
+
+@pytest.mark.parametrize("kind", list(sup.KINDS))
+def test_restatement_equals_fixture(fx, inputs, kind):
+    n = 0
+    for case in sup.CASES:
+        if case[0] != kind:
+            continue
+        _, shape, seed, axis, order, angle = case
+        img = inputs[(kind, shape, seed)]
+        want = fx["rot_" + sup.case_name(case)]
+        got = sup.rotate_nd(img, angle, axis, order)
+        assert got.dtype == want.dtype == img.dtype and got.shape == want.shape == img.shape
+        assert np.array_equal(got, want), case
+        n += 1
+    assert n
+
+
+def test_restated_chains_equal_fixture(fx):
+    CHAIN_SEED = sup.CHAIN_SEED
+    src = sup.make_input("u16m", sup.SMALL, CHAIN_SEED)
+    assert sup.sha(src) == str(fx["chain_sha"])
+    for order in (0, 1):
+        assert np.array_equal(sup.rotate_img(src, sup.CHAIN, order), fx["chain_o%d" % order])
+    two = sup.make_input("u16c2", sup.SMALL, CHAIN_SEED + 1)
+    assert sup.sha(two) == str(fx["chain_c2_sha"])
+    assert np.array_equal(sup.rotate_img(two, sup.CHAIN, 1), fx["chain_c2"])
+
+
+def test_matrix_equals_the_stored_matrices_bit_for_bit(fx):
+    keys, vals = fx["mat_keys"], fx["mat_vals"]
+    assert len(keys) >= 30
+    for (rows, cols, angle), want in zip(keys, vals):
+        got = preprocess.rotation_matrix(int(rows), int(cols), float(angle))
+        assert got.dtype == np.float64 and got.shape == (2, 3)
+        assert got.tobytes() == want.tobytes(), (rows, cols, angle)
+        assert sup.rotation_matrix(int(rows), int(cols), float(angle)).tobytes() == want.tobytes()
+    assert rot.rotation_matrix is preprocess.rotation_matrix
+
+
+# ------------------------------------------------------------------------------------------------------- refusals
+def _no_device(monkeypatch):
+    """Any touch of the device fails the test: the refusals below come from the arguments alone."""
+    def boom(*a, **k):
+        raise AssertionError("the device was touched")
+    monkeypatch.setattr(equalize, "_free_device_bytes", boom)
+    monkeypatch.setattr(rot, "rotate_tensor", boom)
+    from magellanmapper_amd import volume
+    monkeypatch.setattr(volume, "_require_gpu", boom)
+
+
+def test_refusals_from_the_arguments(monkeypatch, tmp_path):
+    _no_device(monkeypatch)
+    img = np.zeros((6, 7, 8), dtype=np.uint16)
+    with pytest.raises(NotImplementedError, match="LAPACK"):
+        preprocess.rotate_nd(img, 10, 0, resize=True)
+    for order in (2, 3, 5, -1, True, None, 1.5):
+        with pytest.raises(NotImplementedError, match="order"):
+            preprocess.rotate_nd(img, 10, 0, order=order)
+    with pytest.raises(NotImplementedError, match="float32 images at order 1"):
+        preprocess.rotate_nd(img.astype(np.float32), 10, 1)
+    for dtype in (np.int32, np.uint32, np.float16, np.int8, bool):
+        with pytest.raises(NotImplementedError, match="images are not built"):
+            preprocess.rotate_nd(img.astype(dtype), 10, 2, order=0)
+    with pytest.raises(ValueError, match="axis"):
+        preprocess.rotate_nd(np.zeros((4, 5, 6, 2), dtype=np.uint16), 10, -1, order=0)
+    # the same through rotate_img, whose settings are a profile's
+    with pytest.raises(NotImplementedError, match="LAPACK"):
+        transformer.rotate_img(img, {"rotation": ((5, 1),), "resize": True, "order": 1})
+    with pytest.raises(NotImplementedError, match="order"):
+        transformer.rotate_img(img, {"rotation": ((5, 1),), "resize": False, "order": 1}, order=3)
+    with pytest.raises(NotImplementedError, match="float32"):
+        transformer.rotate_img(img.astype(np.float32), {"rotation": ((5, 1),), "resize": False, "order": 1})
+    # and through the task, before any file is made
+    monkeypatch.setattr(config, "atlas_profile", {"rotate": {"rotation": ((5, 1),), "resize": True, "order": 1}})
+    with pytest.raises(NotImplementedError, match="LAPACK"):
+        transformer.preprocess_img(img[None], "rotate", None, str(tmp_path / "out"))
+    monkeypatch.setattr(config, "atlas_profile", {"rotate": {"rotation": ((5, 1),), "resize": False, "order": 3}})
+    with pytest.raises(NotImplementedError, match="order"):
+        transformer.preprocess_img(img[None], ["saturate", "rotate"], None, str(tmp_path / "out"))
+    monkeypatch.setattr(config, "atlas_profile", {"rotate": {"rotation": ((5, 1),), "resize": False, "order": 1}})
+    with pytest.raises(NotImplementedError, match="float32"):
+        transformer.preprocess_img(img.astype(np.float32)[None], "rotate", None, str(tmp_path / "out"))
+    with pytest.raises(NotImplementedError, match="stays in the reference"):
+        transformer.preprocess_img(img[None], ["rotate", "denoise"], None, str(tmp_path / "out"))
+    assert not os.listdir(tmp_path)
+
+
+def test_image_that_does_not_fit_is_refused(monkeypatch, tmp_path):
+    monkeypatch.setattr(equalize, "_free_device_bytes", lambda: 1 << 20)
+    img = np.zeros((64, 128, 128), dtype=np.uint16)
+    with pytest.raises(NotImplementedError, match="does not fit"):
+        preprocess.rotate_nd(img, 10, 0)
+    with pytest.raises(NotImplementedError, match="does not fit"):
+        transformer.rotate_img(img, {"rotation": sup.CHAIN, "resize": False, "order": 0})
+    monkeypatch.setattr(config, "atlas_profile", {"rotate": {"rotation": sup.CHAIN, "resize": False, "order": 1}})
+    with pytest.raises(NotImplementedError, match="does not fit"):
+        transformer.preprocess_img(img[None], "rotate", None, str(tmp_path / "out"))
+    assert not os.listdir(tmp_path)
+
+
+def test_no_atlas_profile_is_refused_ahead_of_everything(monkeypatch, tmp_path):
+    _no_device(monkeypatch)
+    assert config.atlas_profile is None
+    img = np.zeros((6, 7, 8), dtype=np.uint16)
+    for task in ("rotate", "ROTATE", ["saturate", "rotate"], ["rotate", "remap"]):
+        with pytest.raises(NotImplementedError, match="atlas profiles stays in the reference"):
+            transformer.preprocess_img(img[None], task, None, str(tmp_path / "out"))
+    with pytest.raises(NotImplementedError, match="atlas profiles stays in the reference"):
+        transformer.rotate_img(img)
+    assert not os.listdir(tmp_path)
+    assert config.atlas_profile is None
+
+
+def test_rotation_none_is_refused_nowhere_ahead_of_the_device(monkeypatch):
+    """``rotate["rotation"] = None`` (the profile's default) is no refusal -- the image comes back unchanged, the one
+    deliberate divergence from the reference, whose loop fails on ``None``: no argument is looked at, and the first
+    thing the call does is ask the device for room (the GPU test checks the copy that comes back)."""
+    class Reached(Exception):
+        pass
+
+    def reached():
+        raise Reached()
+    monkeypatch.setattr(equalize, "_free_device_bytes", reached)
+    f32 = np.zeros((4, 5, 6), dtype=np.float32)
+    with pytest.raises(Reached):
+        transformer.rotate_img(f32, {"rotation": None, "resize": True, "order": 7})
+    monkeypatch.setattr(config, "atlas_profile", {"rotate": {"rotation": None, "resize": False, "order": 1}})
+    with pytest.raises(Reached):
+        transformer.rotate_img(f32)
