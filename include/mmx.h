@@ -1077,6 +1077,31 @@ int mmx_rotate_minmax(const mmx_ds_view* src, int64_t src_elems, int nz, int ny,
 int mmx_rotate_warp(const mmx_ds_view* src, int64_t src_elems, const mmx_ds_view* dst, int64_t dst_elems, int nz, int ny,
                     int nx, int n_chl, int axis, const double* matrix, int order, const double* d_bounds, void* stream);
 
+/* ---- P3: whole-image denoise (added to ABI v21 without a version step: a library without it lacks the symbols)
+ * replaces: plot_3d.denoise_roi as transformer.preprocess_img runs it over a whole stack (magmap/plot/plot_3d.py:114-172):
+ * np.clip, skimage.filters.gaussian(sigma 8) -> scipy.ndimage.correlate1d along z, y, x ('nearest' at the image border,
+ * radius 32), den + (den - s * blur), grey erosion with octahedron(1).  Bit-equal, float64 throughout; one channel of a
+ * resident (nz, ny, nx) image per call through `src` (MMX_U8, MMX_U16, MMX_I16, MMX_F64; MMX_ERR_UNSUPPORTED otherwise;
+ * the source extent is the caller's precondition, mmx_ds_* above), stream-ordered, every buffer the caller's: packed
+ * (z, y, x) float64 images of nz ny nx elements.  No axis may exceed 2^30 (MMX_ERR_ARG).
+ * mmx_dn_sum   : d_sums (16 bytes, zeroed by the call): an int64 sum of the voxels for the integer types (exact);
+ *                double[2] = sum x, sum |x| for MMX_F64, summed in no particular order.
+ * mmx_dn_clip  : d_out = clip(src, clip_min, clip_max) (no unsharp mask: nothing is blurred).
+ * mmx_dn_blur  : one correlate pass along `axis` (0: z, 1: y, 2: x) with the half kernel h_weights[0..32] (host):
+ *                out[c] = in[c] w[0], then for k = 32..1: += (in[c - k] + in[c + k]) w[k], indices clamped.  The pass
+ *                along z is the first: d_in NULL, it reads clip(src).  The others read d_in, the previous pass's result
+ *                (d_in == d_out: MMX_ERR_ARG).  `last` nonzero: the pass stores den + (den - strength * blur) with
+ *                den = clip(src) read again; the pass along x is always the last, the one along y when x is not blurred
+ *                (an (M, N, 3) image under scikit-image < 0.19's RGB guess).  Any other combination: MMX_ERR_ARG.
+ * mmx_dn_erode : planes [z0, z1) of the 7-point minimum of d_in (the whole image; a neighbour outside it is skipped),
+ *                packed into d_out. */
+int mmx_dn_sum(const mmx_ds_view* src, int nz, int ny, int nx, void* d_sums, void* stream);
+int mmx_dn_clip(const mmx_ds_view* src, int nz, int ny, int nx, double clip_min, double clip_max, double* d_out,
+                void* stream);
+int mmx_dn_blur(const mmx_ds_view* src, int nz, int ny, int nx, int axis, const double* h_weights, double clip_min,
+                double clip_max, const double* d_in, double* d_out, int last, double strength, void* stream);
+int mmx_dn_erode(const double* d_in, int nz, int ny, int nx, int z0, int z1, double* d_out, void* stream);
+
 /* PMC calibration (tools/pmc_calib.py): one streaming launch over n_elems elements with a known
  * byte count.  kind 0: float copy, 4 B per lane; 1: float copy, 16 B per lane; 2: uint16 read. */
 int mmx_calib_stream(int kind, const void* d_in, void* d_out, int64_t n_elems, void* stream);

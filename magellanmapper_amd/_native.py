@@ -204,6 +204,7 @@ SYMBOLS = (
     "mmx_ds_zoom_batch", "mmx_ds_gauss_pick_batch",
     "mmx_eq_hist", "mmx_host_eq_maps", "mmx_eq_apply", "mmx_eq_output", "mmx_stretch",
     "mmx_rotate_minmax", "mmx_rotate_warp",
+    "mmx_dn_sum", "mmx_dn_clip", "mmx_dn_blur", "mmx_dn_erode",
 )
 KERNEL_KINDS = ("zpass", "ypass", "xpass", "generic", "peaks", "rescore", "overlap_pairs",
                 "close_pairs", "zxpass", "y2pass", "preproc", "coloc", "zxpack", "widepass")
@@ -370,6 +371,15 @@ def lib() -> ctypes.CDLL:
     L.mmx_rotate_warp.argtypes = [POINTER(DsView), c_int64, POINTER(DsView), c_int64, c_int, c_int, c_int, c_int, c_int,
                                   POINTER(c_double), c_int, vp, vp]
     L.mmx_rotate_warp.restype = c_int
+    L.mmx_dn_sum.argtypes = [POINTER(DsView), c_int, c_int, c_int, vp, vp]
+    L.mmx_dn_sum.restype = c_int
+    L.mmx_dn_clip.argtypes = [POINTER(DsView), c_int, c_int, c_int, c_double, c_double, vp, vp]
+    L.mmx_dn_clip.restype = c_int
+    L.mmx_dn_blur.argtypes = [POINTER(DsView), c_int, c_int, c_int, c_int, vp, c_double, c_double, vp, vp, c_int,
+                              c_double, vp]
+    L.mmx_dn_blur.restype = c_int
+    L.mmx_dn_erode.argtypes = [vp, c_int, c_int, c_int, c_int, c_int, vp, vp]
+    L.mmx_dn_erode.restype = c_int
     L.mmx_preprocess_batch.restype = c_int
     L.mmx_preprocess_batch_mode.restype = c_int
     L.mmx_preprocess_batch_generic.restype = c_int

@@ -44,8 +44,8 @@ atlas_profile = None
 
 
 class PreProcessKeys(Enum):
-    """Whole-image pre-processing tasks (reference config.py:251-256); ``transformer.preprocess_img`` runs ``SATURATE``
-    and ``REMAP``, the other two stay in the reference."""
+    """Whole-image pre-processing tasks (reference config.py:251-256); ``transformer.preprocess_img`` runs all four on
+    the device (``DENOISE`` without total-variation denoising and on an image stretched to 0-1 or a float64 one)."""
     SATURATE = auto()
     DENOISE = auto()
     REMAP = auto()

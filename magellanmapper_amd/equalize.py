@@ -1,4 +1,4 @@
-"""Whole-image preprocessing on the device: ``saturate`` and ``remap`` of ``mm <img> --proc preprocess=...``.
+"""Whole-image preprocessing on the device: ``saturate``, ``denoise`` and ``remap`` of ``mm <img> --proc preprocess=...``.
 
 Mirror of ``plot_3d.saturate_roi`` (reference magmap/plot/plot_3d.py:55-111) and ``plot_3d.remap_intensity`` (:270-317)
 -> ``skimage.exposure.equalize_adapthist`` as ``transformer.preprocess_img`` runs them over a whole stack
@@ -20,6 +20,11 @@ uploaded as a table, so that no device arithmetic has to be pinned for it:
 The float64 result leaves the device in z-slabs of at most :data:`SLAB_BYTES`, straight into the array given as
 ``out`` (``transformer.preprocess_img`` hands the output file's memory map).  Between the tasks of a chain a float64
 single-result image stays on the device.
+
+``denoise`` is ``plot_3d.denoise_roi`` (:114-172), :func:`denoise_roi`: the clip, the sigma-8 unsharp mask and the
+grey erosion are the passes of ``csrc/mmx_denoise_img.hip`` between two float64 working buffers; the host's share is the
+erosion gate ``np.mean(channel) > erosion_threshold``, decided from a device sum (:func:`erosion_gate`).  Its limits:
+:func:`denoise_check_args`.
 
 Stated limits (``NotImplementedError``, from the arguments, ahead of any launch): ``nbins > 16384``; a tile of 2^31
 voxels or more; ``saturate`` of a float32 image unless ``preprocess.FLOAT32_RULES = "numpy2"``; an image that does not
@@ -202,7 +207,7 @@ def _ds_view(dv, channel: int) -> nat.DsView:
     return nat.DsView(v.d_data, v.dtype, 0, v.stride_z, v.stride_y, v.stride_x)
 
 
-def _as_volume(image, what: str, extra_per_voxel: int):
+def _as_volume(image, what: str, extra_per_voxel: int, extra_bytes: int = 0):
     """``(DeviceVolume, owned)`` of a host array or a resident volume, after the fit check."""
     from .volume import DeviceVolume
     if isinstance(image, DeviceVolume):
@@ -210,7 +215,7 @@ def _as_volume(image, what: str, extra_per_voxel: int):
             raise ValueError(f"a DeviceVolume that holds a box of its image cannot be {what}")
         if image.np_dtype not in nat.NP_TO_MMX:
             raise NotImplementedError(f"{what}: {image.np_dtype} images are not built")
-        _check_fits(int(np.prod(image.shape[:3], dtype=np.int64)) * extra_per_voxel, what)
+        _check_fits(int(np.prod(image.shape[:3], dtype=np.int64)) * extra_per_voxel + extra_bytes, what)
         image.wait_all()
         return image, False
     arr = image if isinstance(image, np.ndarray) else np.asarray(image)
@@ -219,7 +224,7 @@ def _as_volume(image, what: str, extra_per_voxel: int):
                                   f"({', '.join(str(d) for d in nat.NP_TO_MMX)} are)")
     if arr.ndim not in (3, 4):
         raise ValueError("image must be (z, y, x) or (z, y, x, c)")
-    _check_fits(arr.nbytes + int(np.prod(arr.shape[:3], dtype=np.int64)) * extra_per_voxel, what)
+    _check_fits(arr.nbytes + int(np.prod(arr.shape[:3], dtype=np.int64)) * extra_per_voxel + extra_bytes, what)
     dv = DeviceVolume(arr, streamed=False)
     return dv, True
 
@@ -497,6 +502,177 @@ def saturate_roi(roi, clip_vmin=-1, clip_vmax=-1, max_thresh_factor=-1, channel=
             torch.cuda.current_stream().synchronize()
         if sink is None:
             return None                     # (no channel processed: the reference returns None)
+        return sink.tensor if sink.tensor is not None else sink.host
+    finally:
+        if owned:
+            dv.close()
+
+
+# ------------------------------------------------------------------------------------------------------ denoise
+def erosion_gate(sum_x, sum_abs, n: int, thr) -> str:
+    """Whether ``np.mean(x) > thr`` (``denoise_roi`` erodes iff it holds) as far as the device's sums can tell:
+    ``"erode"``, ``"keep"``, or ``"ask"`` -- only NumPy's own summation of the voxels decides.
+
+    Integer voxels (``sum_abs is None``, ``sum_x`` a Python int): ``np.mean`` adds the voxels as float64 in pairwise
+    order; every partial sum is an integer below 2^53 and therefore exact in any order, so ``float(sum_x) / n`` IS
+    NumPy's mean and the answer is never ``"ask"``.
+
+    float64 voxels (``sum_x``, ``sum_abs``: sum x and sum |x| summed in no particular order): a float64 summation of n
+    values in any order returns ``S (1 + d)`` per addition, so its error is at most ``g(n-1) sum|x|`` with ``g(k) = k u
+    / (1 - k u)``, ``u = 2^-53`` (Higham, Accuracy and Stability of Numerical Algorithms, eq. 4.4).  NumPy's sum and
+    the device's are two such summations of the same values: they differ by at most ``2 g(n-1) sum|x|``, their means by
+    at most that over n plus one rounding of each division, ``2 u |mean| <= 2 u sum|x| / n``:
+    ``|m_device - m_numpy| <= ((n - 1) 2^-52 / (1 - n u) + 2^-52) (sum|x| / n) <= n 2^-52 (sum|x| / n) (1 + 2^-20)``
+    for ``n < 2^32``.  The device's ``sum|x|`` is itself low by a factor of at most ``1 - g(n)``; the band below carries
+    ``(n + 2) (1 + 2^-19)`` for all of it.  Outside the band both means lie on the same side of ``thr``."""
+    n = int(n)
+    thr = float(thr)
+    if sum_abs is None:
+        return "erode" if float(int(sum_x)) / float(n) > thr else "keep"
+    m = float(sum_x) / n
+    band = (n + 2) * 2.0 ** -52 * (float(sum_abs) / n) * (1 + 2.0 ** -19)
+    if abs(m - thr) > band:                    # (False for a NaN or an infinite sum: NumPy decides)
+        return "erode" if m > thr else "keep"
+    return "ask"
+
+
+def denoise_check_args(dtype, channels, what: str):
+    """``[(channel, clip_min, clip_max, unsharp_strength, erosion_threshold)]`` of the channels :func:`denoise_roi`
+    would process, the last two ``0.0`` where the reference's truthiness test skips the step -- and every refusal that
+    follows from the image's dtype and the profiles alone."""
+    dtype = np.dtype(dtype)
+    if dtype == np.float32:
+        raise NotImplementedError(f"{what}: float32 images are not built (under NumPy 2 the reference stays in float32 "
+                                  f"from the clip onward)")
+    if dtype not in nat.NP_TO_MMX:
+        raise NotImplementedError(f"{what}: {dtype} images are not built "
+                                  f"({', '.join(str(d) for d in nat.NP_TO_MMX)} are)")
+    todo = []
+    for chl in channels:
+        settings = config.get_roi_profile(chl)
+        if settings["tot_var_denoise"]:
+            raise NotImplementedError(f"{what}: tot_var_denoise of a whole image (channel {chl}) is not built")
+        lo, hi = settings["clip_min"], settings["clip_max"]
+        if dtype.kind in "iu" and all(isinstance(v, numbers.Integral) for v in (lo, hi)):
+            raise NotImplementedError(f"{what}: integer clip bounds ({lo!r}, {hi!r}) keep an integer image in its own "
+                                      f"type: not built (the result here is float64)")
+        todo.append((chl, float(lo), float(hi), float(settings["unsharp_strength"] or 0.0),
+                     float(settings["erosion_threshold"] or 0.0)))
+    return todo
+
+
+def _denoise_channel(dv, chl: int, lo, hi, strength, thr, bufs, host_view, stats=None):
+    """One channel through the passes: ``(packed float64 image on the device, eroded?)`` -- the unsharp result (or the
+    clipped image) in one of ``bufs``; the erosion is the caller's, on the result's way out."""
+    from . import preprocess
+    L = nat.lib()
+    dev = dv.tensor.device
+    nz, ny, nx = (int(v) for v in dv.shape[:3])
+    n_vox = nz * ny * nx
+    stream = _stream()
+    src = _ds_view(dv, chl)
+    erode = False
+    if thr:
+        d_sums = torch.zeros(2, dtype=torch.int64, device=dev)
+        nat.check(L.mmx_dn_sum(ctypes.byref(src), nz, ny, nx, d_sums.data_ptr(), stream), "mmx_dn_sum")
+        if dv.np_dtype.kind == "f":
+            sx, sa = (float(v) for v in d_sums.view(torch.float64).cpu().numpy())
+            verdict = erosion_gate(sx, sa, n_vox, thr)
+        else:
+            verdict = erosion_gate(int(d_sums[0].item()), None, n_vox, thr)
+        if verdict == "ask":
+            verdict = "erode" if np.mean(host_view()) > thr else "keep"
+        erode = verdict == "erode"
+        if stats is not None:
+            stats.setdefault("verdicts", []).append(verdict)
+    a, b = bufs[0], bufs[1] if len(bufs) > 1 else None
+    if not strength:
+        nat.check(L.mmx_dn_clip(ctypes.byref(src), nz, ny, nx, lo, hi, a.data_ptr(), stream), "mmx_dn_clip")
+        return a, erode
+    w = preprocess.gauss_weights()
+    if w.shape != (33,):
+        raise ValueError("the sigma-8 half kernel has 33 weights")
+    axes = [0, 1] if preprocess.RGB_GUESS and nx == 3 else [0, 1, 2]
+    cur, nxt = None, a
+    for axis in axes:
+        last = axis == axes[-1]
+        nat.check(L.mmx_dn_blur(ctypes.byref(src), nz, ny, nx, axis, w.ctypes.data, lo, hi,
+                                cur.data_ptr() if cur is not None else None, nxt.data_ptr(), int(last), strength,
+                                stream), "mmx_dn_blur")
+        cur, nxt = nxt, (b if nxt is a else a)
+    return cur, erode
+
+
+def denoise_roi(roi, channel=None, _keep=False, _out=None, _stats=None):
+    """``plot_3d.denoise_roi`` of a whole ``(z, y, x[, c])`` image: per channel ``np.clip`` to the profile's ``clip_min``
+    / ``clip_max``, the unsharp mask ``den + (den - unsharp_strength * gaussian(den, 8))`` unless the strength is
+    falsy, and the 7-point grey erosion when ``erosion_threshold`` is truthy and ``np.mean`` of the channel exceeds it
+    (:func:`erosion_gate`).  float64 for every voxel type.  A multichannel result is zero in the channels not named;
+    no channel processed returns ``None``.  A truthy ``tot_var_denoise``, float32 images and an image that does not
+    fit the device beside its two float64 working buffers are a ``NotImplementedError`` (:func:`denoise_check_args`).
+    ``_keep=True`` leaves a float64 tensor on the device for the next task of a chain, otherwise the result leaves z-slab
+    by z-slab, through ``_out`` when given; ``_stats`` (a dict, for tests and tools) receives the gate's verdicts."""
+    shape = tuple(roi.shape)
+    dtype = np.dtype(getattr(roi, "np_dtype", None) or roi.dtype)
+    multichannel, channels = _setup_channels(shape, channel)
+    todo = denoise_check_args(dtype, list(channels), "denoise_roi")
+    if len(shape) not in (3, 4):
+        raise ValueError("image must be (z, y, x) or (z, y, x, c)")
+    if not todo:
+        return None                         # (no channel processed: the reference returns None)
+    nz, ny, nx = (int(v) for v in shape[:3])
+    n_vox = nz * ny * nx
+    blurs = any(t[3] for t in todo)
+    erodes = any(t[4] for t in todo)
+    keep_single = _keep and not multichannel
+    # float64 images kept beside the source: the passes' two (one without a blur), the eroded image when it stays on the
+    # device as the result (it takes the second), every channel of a multichannel result that stays; and the slab the
+    # eroded planes leave through
+    n_bufs = 2 if blurs or (keep_single and erodes) else 1
+    step, _ = _slabs((nz, ny, nx))
+    slab_bytes = step * ny * nx * 8 if erodes and not keep_single else 0
+    dv, owned = _as_volume(roi, "denoise_roi", 8 * n_bufs + (8 * shape[3] if _keep and multichannel else 0), slab_bytes)
+    try:
+        L = nat.lib()
+        dev = dv.tensor.device
+        bufs = [torch.empty(n_vox, dtype=torch.float64, device=dev) for _ in range(n_bufs)]
+        if _keep and multichannel:
+            sink = _Sink(None, torch.zeros(shape, dtype=torch.float64, device=dev))
+        elif not _keep:
+            host = _resolve_out(_out, shape, np.float64)
+            if multichannel:
+                host[...] = 0
+            sink = _Sink(host, None)
+        slab = torch.empty(slab_bytes // 8, dtype=torch.float64, device=dev) if slab_bytes else None
+        result = None
+        for chl, lo, hi, strength, thr in todo:
+            def host_view(chl=chl):
+                # (the view the reference's np.mean would see: NumPy's summation order depends on the layout)
+                arr = dv.tensor.cpu().numpy() if not isinstance(roi, np.ndarray) else roi
+                return arr[..., chl] if multichannel else arr
+            res, erode = _denoise_channel(dv, chl, lo, hi, strength, thr, bufs, host_view, _stats)
+            if keep_single:
+                if erode:
+                    other = bufs[1] if res is bufs[0] else bufs[0]
+                    nat.check(L.mmx_dn_erode(res.data_ptr(), nz, ny, nx, 0, nz, other.data_ptr(), _stream()),
+                              "mmx_dn_erode")
+                    res = other
+                result = res.view(shape)
+                continue
+            c_sink = chl if multichannel else None
+            vol = res.view(nz, ny, nx)
+            for z0 in range(0, nz, step):
+                z1 = min(nz, z0 + step)
+                if erode:
+                    nat.check(L.mmx_dn_erode(res.data_ptr(), nz, ny, nx, z0, z1, slab.data_ptr(), _stream()),
+                              "mmx_dn_erode")
+                    sink.put(z0, z1, c_sink, slab[:(z1 - z0) * ny * nx].view(z1 - z0, ny, nx))
+                else:
+                    sink.put(z0, z1, c_sink, vol[z0:z1])
+            torch.cuda.current_stream().synchronize()
+        if keep_single:
+            torch.cuda.current_stream().synchronize()
+            return result
         return sink.tensor if sink.tensor is not None else sink.host
     finally:
         if owned:

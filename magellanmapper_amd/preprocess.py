@@ -1033,6 +1033,6 @@ def preprocess_roi(roi, denoise_max_shape, channel: Optional[Sequence[int]] = No
 
 
 # ---- whole-image tasks of ``transformer.preprocess_img`` (``--proc preprocess=saturate,remap``): :mod:`equalize`
-from .equalize import equalize_adapthist, remap_intensity, saturate_roi  # noqa: E402,F401
+from .equalize import denoise_roi, equalize_adapthist, remap_intensity, saturate_roi  # noqa: E402,F401
 # ---- whole-image rotation (``cv_nd.rotate_nd``, the chain of ``transformer.rotate_img``): :mod:`rotate`
 from .rotate import rotate_nd, rotation_matrix  # noqa: E402,F401

@@ -631,10 +631,13 @@ def preprocess_img(image5d, preprocs, channel, out_path):
     """``transformer.preprocess_img`` (reference transformer.py:353-393): run the whole-image tasks ``preprocs`` (names
     of ``config.PreProcessKeys``, one or a sequence) on ``image5d[0]`` in the order given, each on the previous result,
     for ``channel`` (``None``: all), and write ``<out_path base>_image5d.npy`` with its ``_meta.yml`` (the settings in
-    :mod:`config`, the intensity bounds of the result).  ``saturate`` and ``remap`` (:mod:`equalize`) and ``rotate``
-    (:func:`rotate_img`, all channels, the settings of ``config.atlas_profile``) run on the device; ``denoise`` is a
-    ``NotImplementedError`` before anything runs, and so is ``rotate`` without an atlas profile or with settings
-    :func:`rotate_img` refuses; a name that is no task is skipped with a warning.  The last task's result goes z-slab by
+    :mod:`config`, the intensity bounds of the result).  ``saturate``, ``denoise`` and ``remap`` (:mod:`equalize`) and
+    ``rotate`` (:func:`rotate_img`, all channels, the settings of ``config.atlas_profile``) run on the device.  Refused
+    with a ``NotImplementedError`` before anything runs: ``denoise`` of an integer image with neither ``saturate`` nor
+    ``remap`` ahead of it (raw counts clipped to the profile's 0-1 bounds: that stays in the reference), of a float32
+    image, or with a truthy ``tot_var_denoise`` in a channel's profile (:func:`equalize.denoise_check_args`); ``rotate``
+    without an atlas profile or with settings :func:`rotate_img` refuses.  A name that is no task is skipped with a
+    warning.  The last task's result goes z-slab by
     z-slab into the memory map of the output file, which is returned (``(1, z, y, x[, c])``); between tasks the image
     stays on the device.  ``None`` for ``preprocs`` prints and returns ``None``."""
     import os
@@ -650,8 +653,16 @@ def preprocess_img(image5d, preprocs, channel, out_path):
     for preproc in preprocs:
         task = _get_enum(preproc, config.PreProcessKeys)
         if task is config.PreProcessKeys.DENOISE:
-            raise NotImplementedError(f"the whole-image task {task.name.lower()!r} stays in the reference "
-                                      f"(saturate, remap and rotate are built)")
+            stretched = any(t in (config.PreProcessKeys.SATURATE, config.PreProcessKeys.REMAP) for t in tasks)
+            if np.dtype(image5d.dtype).kind in "iu" and not stretched:
+                # (np.clip of raw counts to [clip_min, clip_max] gives a two-valued image: nothing anyone runs)
+                raise NotImplementedError(
+                    "the whole-image task 'denoise' of an image that was not stretched to 0-1 stays in the reference "
+                    "(an integer image with neither 'saturate' nor 'remap' ahead of it in the task list)")
+            # (what can be told ahead of the tasks: the voxel type only where the image arrives as it is)
+            _, chls = equalize._setup_channels(tuple(image5d.shape[1:]), channel)
+            equalize.denoise_check_args(np.float64 if stretched else image5d.dtype, list(chls),
+                                        "the whole-image task 'denoise'")
         if task is config.PreProcessKeys.ROTATE:
             prof = getattr(config, "atlas_profile", None)
             if prof is None:
@@ -691,6 +702,8 @@ def preprocess_img(image5d, preprocs, channel, out_path):
             roi = equalize.saturate_roi(roi, channel=channel, **kw)
         elif task is config.PreProcessKeys.ROTATE:
             roi = rotate_img(roi, **kw)
+        elif task is config.PreProcessKeys.DENOISE:
+            roi = equalize.denoise_roi(roi, channel, **kw)
         else:
             roi = equalize.remap_intensity(roi, channel, **kw)
         if torch is not None and isinstance(roi, torch.Tensor):

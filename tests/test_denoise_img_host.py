@@ -1,0 +1,190 @@
+"""Whole-image denoise, the parts that need no device: the oracle against the fixture of the real reference, every
+refusal that follows from the arguments alone, the does-not-fit refusal, and the erosion-gate rule."""
+import os
+
+import numpy as np
+import pytest
+
+import denoise_img_support as sup
+from conftest import load_golden
+from magellanmapper_amd import config, equalize, preprocess, transformer
+from oracle import preprocess_oracle as ppo
+
+
+@pytest.fixture(scope="module")
+def fx():
+    return load_golden("denoise_img.npz")
+
+
+@pytest.fixture()
+def profiles():
+    saved = (config.roi_profile, config.roi_profiles, config.near_max, config.resolutions)
+    yield lambda over: sup.set_profiles(config, config.setup_roi_profiles, over)
+    config.roi_profile, config.roi_profiles, config.near_max, config.resolutions = saved
+
+
+@pytest.mark.parametrize("name", list(sup.CASES))
+def test_oracle_equals_the_fixture(fx, profiles, name, monkeypatch):
+    monkeypatch.setattr(ppo, "GAUSS_WEIGHTS", fx["gauss8_weights"])
+    make, over, channel = sup.CASES[name]
+    img = make()
+    assert sup.sha(img) == str(fx[name + "_sha"])
+    got = ppo.denoise_roi(img, profiles(over), channel)
+    want = fx[name + "_out"]
+    assert got.dtype == want.dtype == np.float64 and got.tobytes() == want.tobytes()
+
+
+def test_fixture_cases_say_what_they_claim(fx):
+    """Erosion on in the default case and off above the mean; a channel not named stays zero."""
+    assert not np.array_equal(fx["f64_default_out"], fx["f64_noero_out"])
+    assert float(fx["f64_default_mean"][0]) > 0.2 and float(fx["f64_noero_mean"][0]) < 0.9
+    assert not fx["two_c1_out"][..., 0].any() and fx["two_c1_out"][..., 1].all()
+    assert np.array_equal(fx["two_c1_out"][..., 1], fx["two_all_out"][..., 1])
+    assert sup.sha(sup.chain_image()) == str(fx["chain_sha"])
+
+
+# ------------------------------------------------------------------------------------------------------- refusals
+def _no_device(monkeypatch):
+    """Any touch of the device fails the test: the refusals below come from the arguments alone."""
+    def boom(*a, **k):
+        raise AssertionError("the device was touched")
+    monkeypatch.setattr(equalize, "_as_volume", boom)
+    monkeypatch.setattr(equalize, "_free_device_bytes", boom)
+    monkeypatch.setattr(equalize.nat, "lib", boom)
+
+
+def test_refusals_from_the_arguments(monkeypatch, profiles, tmp_path):
+    _no_device(monkeypatch)
+    f64 = np.zeros((8, 8, 8), dtype=np.float64)
+    out = str(tmp_path / "out")
+
+    def refused(image, tasks, match, function=True):
+        if function:
+            with pytest.raises(NotImplementedError, match=match):
+                preprocess.denoise_roi(image)
+        with pytest.raises(NotImplementedError, match=match):
+            transformer.preprocess_img(image[None], tasks, None, out)
+
+    profiles([{}])
+    refused(f64.astype(np.float32), "denoise", "float32")
+    refused(f64.astype(np.int32), ["saturate", "denoise"], "int32", function=True)
+    with pytest.raises(NotImplementedError, match="complex128"):
+        preprocess.denoise_roi(f64.astype(np.complex128))
+    # an integer image that was not stretched: the task is refused, the function itself takes integer voxels
+    for tasks in ("denoise", ["rotate", "denoise"], ["denoise", "saturate"]):
+        with pytest.raises(NotImplementedError, match="stays in the reference"):
+            transformer.preprocess_img(f64.astype(np.uint16)[None], tasks, None, out)
+    # total-variation denoising, in any processed channel's profile, whatever comes before the task
+    for tv in (0.01, True):
+        profiles([dict(tot_var_denoise=tv)])
+        refused(f64, "denoise", "tot_var_denoise")
+        refused(f64.astype(np.uint16), ["saturate", "denoise"], "tot_var_denoise")
+        refused(f64.astype(np.float32), ["remap", "denoise", "saturate"], "tot_var_denoise", function=False)
+    profiles([{}, dict(tot_var_denoise=0.01)])
+    two = np.zeros((4, 4, 4, 2))
+    with pytest.raises(NotImplementedError, match="channel 1"):
+        preprocess.denoise_roi(two)
+    with pytest.raises(NotImplementedError, match="channel 1"):
+        transformer.preprocess_img(two[None], ["saturate", "denoise"], None, out)
+    # integer clip bounds would keep an integer image in its type
+    profiles([dict(clip_min=0, clip_max=1)])
+    with pytest.raises(NotImplementedError, match="integer clip bounds"):
+        preprocess.denoise_roi(f64.astype(np.uint8))
+    assert not os.listdir(tmp_path)
+
+
+def test_channels_not_processed_return_none(monkeypatch, profiles):
+    _no_device(monkeypatch)
+    profiles([{}])
+    assert preprocess.denoise_roi(np.zeros((4, 4, 4, 2)), channel=[]) is None
+
+
+def test_unrefused_calls_reach_the_device(monkeypatch, profiles, tmp_path):
+    """What the refusals let through goes on to the device: a float64 image alone, a stretched integer image."""
+    class Reached(Exception):
+        pass
+
+    def reached(*a, **k):
+        raise Reached()
+    monkeypatch.setattr(equalize, "_as_volume", reached)
+    profiles([{}])
+    with pytest.raises(Reached):
+        preprocess.denoise_roi(np.zeros((4, 4, 4), dtype=np.int16))
+    with pytest.raises(Reached):
+        transformer.preprocess_img(np.zeros((1, 4, 4, 4)), "denoise", None, str(tmp_path / "a"))
+    with pytest.raises(Reached):
+        transformer.preprocess_img(np.zeros((1, 4, 4, 4), dtype=np.uint16), ["saturate", "denoise"], None,
+                                   str(tmp_path / "b"))
+
+
+def test_image_that_does_not_fit_is_refused(monkeypatch, profiles):
+    profiles([{}])
+    img = np.zeros((64, 128, 128), dtype=np.uint16)            # 2 MiB of voxels, 2 x 8 MiB of working buffers
+    monkeypatch.setattr(equalize, "_free_device_bytes", lambda: 16 << 20)
+    with pytest.raises(NotImplementedError, match="does not fit"):
+        preprocess.denoise_roi(img)
+    # the need counts the second working buffer only when something is blurred
+    seen = []
+    monkeypatch.setattr(equalize, "_check_fits", lambda need, what: seen.append(need) or (_ for _ in ()).throw(
+        NotImplementedError("does not fit")))
+    n = img.size
+    for over, per_voxel, slab in ((dict(), 16, True), (dict(unsharp_strength=0), 8, True),
+                                  (dict(unsharp_strength=0, erosion_threshold=0), 8, False)):
+        profiles([over])
+        with pytest.raises(NotImplementedError):
+            preprocess.denoise_roi(img)
+        assert seen[-1] == img.nbytes + n * per_voxel + (n * 8 if slab else 0)
+
+
+# ------------------------------------------------------------------------------------------------ the erosion gate
+def _gate_agrees(x, thr):
+    """The gate's answer for sums taken in an order of their own never contradicts NumPy's mean."""
+    truth = bool(np.mean(x) > thr)
+    flat = x.ravel()
+    verdicts = set()
+    for order in (flat, flat[::-1], np.sort(flat), np.sort(flat)[::-1]):
+        sx = sa = 0.0
+        for chunk in np.array_split(order, 7):
+            sx += float(np.sum(chunk))
+            sa += float(np.sum(np.abs(chunk)))
+        v = equalize.erosion_gate(sx, sa, x.size, thr)
+        assert v in ("erode", "keep", "ask")
+        assert v == "ask" or (v == "erode") == truth, (v, truth, thr)
+        verdicts.add(v)
+    return verdicts
+
+
+def test_erosion_gate_float64():
+    rng = np.random.default_rng(5)
+    for i in range(40):
+        n = int(rng.integers(1, 5000))
+        x = rng.random(n) * rng.choice([1e-3, 1.0, 1e6])
+        if i % 3 == 0:
+            x -= x.mean()                                       # (cancellation: the band is set by sum |x|)
+        mean = float(np.mean(x))
+        assert _gate_agrees(x, mean) == {"ask"}
+        assert _gate_agrees(x, float(np.nextafter(mean, 0))) == {"ask"}
+        assert _gate_agrees(x, float(np.nextafter(mean, np.inf))) == {"ask"}
+        for thr in (0.2, mean * (1 + 1e-9) + 1e-300, mean * (1 - 1e-9) - 1e-300, -mean):
+            _gate_agrees(x, thr)
+        # a threshold well clear of the mean is decided without NumPy
+        clear = mean + (1.0 + abs(mean)) * 1e-6
+        assert _gate_agrees(x, clear) == {"keep"} and _gate_agrees(x, mean - (clear - mean)) == {"erode"}
+    assert equalize.erosion_gate(float("nan"), float("nan"), 10, 0.2) == "ask"
+    assert equalize.erosion_gate(float("inf"), float("inf"), 10, 0.2) == "ask"
+
+
+def test_erosion_gate_integers():
+    rng = np.random.default_rng(6)
+    for dtype in (np.uint8, np.uint16, np.int16):
+        info = np.iinfo(dtype)
+        for _ in range(20):
+            x = rng.integers(info.min, int(info.max) + 1, int(rng.integers(1, 4000))).astype(dtype)
+            total = int(x.astype(np.int64).sum())
+            mean = float(np.mean(x))
+            for thr in (mean, float(np.nextafter(mean, 0)), float(np.nextafter(mean, np.inf)), 0.2, 300):
+                v = equalize.erosion_gate(total, None, x.size, thr)
+                assert v == ("erode" if np.mean(x) > thr else "keep")
+    # the largest sums the device takes: 2^32 voxels of 65535 stay below 2^53
+    assert equalize.erosion_gate(65535 << 32, None, 1 << 32, 65534.5) == "erode"
+    assert equalize.erosion_gate(65535 << 32, None, 1 << 32, 65535) == "keep"
