@@ -17,9 +17,10 @@ uploaded as a table, so that no device arithmetic has to be pinned for it:
 * ``img_as_float`` and the last ``rescale_intensity`` act on at most 16384 levels: :func:`output_table`, from the
   measured minimum and maximum of the uint16 result, the constant-image branch included.
 
-The float64 result leaves the device in z-slabs of at most :data:`SLAB_BYTES`, straight into the array given as
-``out`` (``transformer.preprocess_img`` hands the output file's memory map).  Between the tasks of a chain a float64
-single-result image stays on the device.
+How an image comes in (a NumPy array, a torch tensor or a ``DeviceVolume``) and how a result goes out is
+:mod:`device_image`'s: the float64 result leaves the device in z-slabs of at most ``device_image.SLAB_BYTES``, straight
+into the array given as ``out`` (``transformer.preprocess_img`` hands the output file's memory map); between the tasks
+of a chain a float64 single-result image stays on the device.
 
 ``denoise`` is ``plot_3d.denoise_roi`` (:114-172), :func:`denoise_roi`: the clip, the sigma-8 unsharp mask and the
 grey erosion are the passes of ``csrc/mmx_denoise_img.hip`` between two float64 working buffers; the host's share is the
@@ -35,23 +36,18 @@ from __future__ import annotations
 
 import ctypes
 import numbers
-from typing import Optional, Sequence, Tuple
+from typing import Sequence, Tuple
 
 import numpy as np
-
-try:
-    import torch
-except ImportError:  # pragma: no cover
-    torch = None
+import torch
 
 from . import _native as nat
 from . import config
+from . import device_image as dimg
 
 NR_OF_GRAY = 2 ** 14
 #: most bins of an equalisation (a bin per 14-bit level)
 MAX_NBINS = NR_OF_GRAY
-#: bytes of one z-slab of the float64 result on its way to the host
-SLAB_BYTES = 256 << 20
 
 
 # ------------------------------------------------------------------------------------------------- host tables
@@ -183,118 +179,40 @@ def axis_tables(shape3, k, nt) -> Tuple[np.ndarray, np.ndarray]:
 
 
 # --------------------------------------------------------------------------------------------------- the device
-def _free_device_bytes() -> int:
-    return int(torch.cuda.mem_get_info()[0])
-
-
-def _check_fits(need: int, what: str) -> None:
-    free = _free_device_bytes()
-    if need > 0.9 * free:
-        raise NotImplementedError(f"{what} needs {need} bytes on the device beside its working buffers, {free} are "
-                                  f"free: an image that does not fit the device is not built")
-
-
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _to_dev(arr: np.ndarray, dev):
-    return torch.from_numpy(np.ascontiguousarray(arr).view(np.uint8).reshape(-1)).to(dev)
-
-
-def _ds_view(dv, channel: int) -> nat.DsView:
-    v = dv.view(channel, False)
-    return nat.DsView(v.d_data, v.dtype, 0, v.stride_z, v.stride_y, v.stride_x)
-
-
-def _as_volume(image, what: str, extra_per_voxel: int, extra_bytes: int = 0):
-    """``(DeviceVolume, owned)`` of a host array or a resident volume, after the fit check."""
-    from .volume import DeviceVolume
-    if isinstance(image, DeviceVolume):
-        if image.z_off or image.y_off or tuple(image.tensor.shape[:3]) != tuple(image.shape[:3]):
-            raise ValueError(f"a DeviceVolume that holds a box of its image cannot be {what}")
-        if image.np_dtype not in nat.NP_TO_MMX:
-            raise NotImplementedError(f"{what}: {image.np_dtype} images are not built")
-        _check_fits(int(np.prod(image.shape[:3], dtype=np.int64)) * extra_per_voxel + extra_bytes, what)
-        image.wait_all()
-        return image, False
-    arr = image if isinstance(image, np.ndarray) else np.asarray(image)
-    if arr.dtype not in nat.NP_TO_MMX:
-        raise NotImplementedError(f"{what}: {arr.dtype} images are not built "
-                                  f"({', '.join(str(d) for d in nat.NP_TO_MMX)} are)")
-    if arr.ndim not in (3, 4):
-        raise ValueError("image must be (z, y, x) or (z, y, x, c)")
-    _check_fits(arr.nbytes + int(np.prod(arr.shape[:3], dtype=np.int64)) * extra_per_voxel + extra_bytes, what)
-    dv = DeviceVolume(arr, streamed=False)
-    return dv, True
-
-
-def _minmax(dv, channel: int) -> Tuple[float, float]:
+def minmax(volume, channel: int) -> Tuple[float, float]:
+    """The raw minimum and maximum of one channel of a ``DeviceVolume`` that holds its whole image."""
     L = nat.lib()
-    dev = dv.tensor.device
-    nz, ny, nx = (int(v) for v in dv.shape[:3])
+    dev = volume.tensor.device
+    nz, ny, nx = (int(v) for v in volume.shape[:3])
     blocks = np.zeros(1, dtype=nat.BLOCK_DTYPE)
     blocks[0] = (0, nz, ny, nx, 0, 0, 0)
-    d_blocks = _to_dev(blocks, dev)
+    d_blocks = dimg.to_dev(blocks, dev)
     d_mm = torch.tensor([np.inf, -np.inf], dtype=torch.float64, device=dev)
-    vol = dv.view(channel, False)
+    vol = volume.view(channel, False)
     nat.check(L.mmx_minmax_batch(ctypes.byref(vol), d_blocks.data_ptr(), blocks.ctypes.data, 1, d_mm.data_ptr(),
-                                 _stream()), "mmx_minmax_batch")
+                                 dimg.stream()), "mmx_minmax_batch")
     lo, hi = d_mm.cpu().numpy()
     return float(lo), float(hi)
 
 
-class _Sink:
-    """Where a float64 channel result goes, z-slab by z-slab: a host array (its own dtype: the assignment casts as
-    NumPy's does), or a float64 tensor that stays on the device for the next task of a chain."""
-
-    def __init__(self, host: Optional[np.ndarray], tensor):
-        self.host, self.tensor = host, tensor
-
-    def put(self, z0: int, z1: int, channel: Optional[int], slab) -> None:
-        if self.tensor is not None:
-            dst = self.tensor[z0:z1] if channel is None else self.tensor[z0:z1, ..., channel]
-            dst.copy_(slab)
-        else:
-            dst = self.host[z0:z1] if channel is None else self.host[z0:z1, ..., channel]
-            dst[...] = slab.cpu().numpy()
-
-
-def _resolve_out(out, shape, dtype) -> np.ndarray:
-    """The host array a result goes into: ``out`` itself, what the factory ``out(shape, dtype)`` makes once the
-    result's dtype is known, or a new array."""
-    if out is None:
-        return np.empty(shape, dtype=dtype)
-    if callable(out):
-        return out(tuple(shape), np.dtype(dtype))
-    if tuple(out.shape) != tuple(shape) or out.dtype != np.dtype(dtype):
-        raise ValueError(f"out must be {tuple(shape)} {np.dtype(dtype)}, not {tuple(out.shape)} {out.dtype}")
-    return out
-
-
-def _slabs(shape3) -> Tuple[int, int]:
-    nz, ny, nx = shape3
-    step = max(1, min(nz, SLAB_BYTES // max(1, ny * nx * 8)))
-    return step, (nz + step - 1) // step
-
-
-def _equalize_channel(dv, channel: int, kernel_size, clip_limit, nbins, sink: _Sink, sink_channel, parts=None) -> None:
-    """One channel through the passes; the float64 result goes to ``sink``."""
+def _equalize_channel(img, channel: int, kernel_size, clip_limit, nbins, sink, sink_channel, parts=None) -> None:
+    """One channel of the opened image through the passes; the float64 result goes to ``sink`` (a
+    ``device_image.Result``)."""
     L = nat.lib()
-    dev = dv.tensor.device
-    shape3 = tuple(int(v) for v in dv.shape[:3])
+    dev = img.tensor.device
+    shape3 = img.shape[:3]
     k, nt, clim = plan(shape3, kernel_size, clip_limit, nbins)
     nbins = int(nbins)
     n_tiles = int(np.prod(nt))
     n_vox = int(np.prod(shape3, dtype=np.int64))
-    stream = _stream()
+    stream = dimg.stream()
 
-    raw_min, raw_max = _minmax(dv, channel)
-    if dv.np_dtype.kind == "f" and (raw_min < -1.0 or raw_max > 1.0):
+    raw_min, raw_max = minmax(img.volume, channel)
+    if img.np_dtype.kind == "f" and (raw_min < -1.0 or raw_max > 1.0):
         raise ValueError("Images of type float must be between -1 and 1.")
-    levels, bins = level_bin_table(dv.np_dtype, raw_min, raw_max, nbins)
-    d_bins = _to_dev(bins, dev)
-    src = _ds_view(dv, channel)
+    levels, bins = level_bin_table(img.np_dtype, raw_min, raw_max, nbins)
+    d_bins = dimg.to_dev(bins, dev)
+    src = dimg.view(img, channel)
     geom = nat.EqGeom((ctypes.c_int32 * 3)(*shape3), (ctypes.c_int32 * 3)(*k), (ctypes.c_int32 * 3)(*nt), nbins)
 
     d_hist = torch.empty(n_tiles * nbins, dtype=torch.int32, device=dev)
@@ -305,9 +223,9 @@ def _equalize_channel(dv, channel: int, kernel_size, clip_limit, nbins, sink: _S
     entered = np.zeros(n_tiles, dtype=np.uint8)
     nat.check(L.mmx_host_eq_maps(hist.ctypes.data, n_tiles, nbins, clim, int(np.prod(k)), maps.ctypes.data,
                                  entered.ctypes.data), "mmx_host_eq_maps")
-    d_maps = _to_dev(maps, dev)
+    d_maps = dimg.to_dev(maps, dev)
     tiles, coef = axis_tables(shape3, k, nt)
-    d_tiles, d_coef = _to_dev(tiles, dev), _to_dev(coef, dev)
+    d_tiles, d_coef = dimg.to_dev(tiles, dev), dimg.to_dev(coef, dev)
     d_out = torch.empty(n_vox, dtype=torch.int16, device=dev)
     d_mm = torch.empty(2, dtype=torch.int32, device=dev)
     nat.check(L.mmx_eq_apply(ctypes.byref(src), ctypes.byref(geom), d_bins.data_ptr(), d_maps.data_ptr(),
@@ -319,9 +237,9 @@ def _equalize_channel(dv, channel: int, kernel_size, clip_limit, nbins, sink: _S
                      hist=hist.reshape(n_tiles, nbins).copy(), maps=maps.reshape(n_tiles, nbins).copy(),
                      entered=entered.astype(bool), clahe=d_out.cpu().numpy().view(np.uint16).reshape(shape3),
                      minmax=(lmin, lmax))
-    d_table = _to_dev(output_table(lmin, lmax), dev)
+    d_table = dimg.to_dev(output_table(lmin, lmax), dev)
     nz, ny, nx = shape3
-    step, _ = _slabs(shape3)
+    step, _ = dimg.slab_step(shape3, 8)
     slab = torch.empty(step * ny * nx, dtype=torch.float64, device=dev)
     for z0 in range(0, nz, step):
         z1 = min(nz, z0 + step)
@@ -341,16 +259,10 @@ def equalize_adapthist(image, kernel_size=None, clip_limit=0.01, nbins=256, out=
     if len(shape) != 3:
         raise ValueError("equalize_adapthist takes one (z, y, x) channel")
     plan(shape, kernel_size, clip_limit, nbins)                   # (every refusal, ahead of the device)
-    if out is not None and (tuple(out.shape) != shape or out.dtype != np.float64):
-        raise ValueError(f"out must be {shape} float64, not {tuple(out.shape)} {out.dtype}")
-    dv, owned = _as_volume(image, "equalize_adapthist", 2 + 2)
-    try:
-        host = out if out is not None else np.empty(shape, dtype=np.float64)
-        _equalize_channel(dv, 0, kernel_size, clip_limit, nbins, _Sink(host, None), None, parts)
-    finally:
-        if owned:
-            dv.close()
-    return host
+    res = dimg.Result(shape, np.float64, out=out)                 # (a mismatching `out` is refused here)
+    with dimg.open_image(image, "equalize_adapthist", 2 + 2) as img:
+        _equalize_channel(img, 0, kernel_size, clip_limit, nbins, res, None, parts)
+    return res.value()
 
 
 def _is_seq(val) -> bool:
@@ -374,14 +286,6 @@ def _setup_channels(shape, channel):
     return False, [0]
 
 
-def _host_copy(image) -> np.ndarray:
-    from .volume import DeviceVolume
-    if isinstance(image, DeviceVolume):
-        image.wait_all()
-        return image.tensor.cpu().numpy()
-    return np.copy(image)
-
-
 def remap_intensity(roi, channel=None, _keep=False, _out=None, **kwargs):
     """``plot_3d.remap_intensity``: adaptive histogram equalisation of the channels in ``channel`` (``None``: all).
     ``clip_limit`` defaults to the FIRST processed channel's ``adapt_hist_lim`` and then holds for the later ones;
@@ -402,27 +306,17 @@ def remap_intensity(roi, channel=None, _keep=False, _out=None, **kwargs):
                     nbins=args.get("nbins", 256))
         plan(shape[:3], **args)
         todo.append((chl, args))
-    dv, owned = _as_volume(roi, "remap_intensity", 2 + 2 + (8 if _keep and not multichannel else 0))
-    try:
+    with dimg.open_image(roi, "remap_intensity", 2 + 2 + (8 if _keep and not multichannel else 0)) as img:
         if not multichannel:
-            if _keep:
-                sink = _Sink(None, torch.empty(shape, dtype=torch.float64, device=dv.tensor.device))
-            else:
-                sink = _Sink(_resolve_out(_out, shape, np.float64), None)
-            _equalize_channel(dv, 0, sink=sink, sink_channel=None, **todo[0][1])
-            return sink.tensor if _keep else sink.host
-        if _out is not None:
-            host = _resolve_out(_out, shape, dv.np_dtype)
-            host[...] = _host_copy(roi)
-        else:
-            host = _host_copy(roi)
-        sink = _Sink(host, None)
+            res = dimg.Result(shape, np.float64, _keep, _out, device=img.tensor.device)
+            _equalize_channel(img, 0, sink=res, sink_channel=None, **todo[0][1])
+            return res.value()
+        # (a host copy of the image, whatever `_keep` says: the float64 results are stored into its own dtype)
+        res = dimg.Result(shape, img.np_dtype, out=_out)
+        res.host[...] = img.host()
         for chl, args in todo:
-            _equalize_channel(dv, chl, sink=sink, sink_channel=chl, **args)
-        return host
-    finally:
-        if owned:
-            dv.close()
+            _equalize_channel(img, chl, sink=res, sink_channel=chl, **args)
+        return res.value()
 
 
 def _saturate_dtype_ok(dtype) -> bool:
@@ -437,75 +331,60 @@ def saturate_roi(roi, clip_vmin=-1, clip_vmax=-1, max_thresh_factor=-1, channel=
     ``(np.clip(chl, vmin, vmax) - vmin) / (vmax - vmin)`` in float64.  A multichannel result has the dtype of the
     first processed channel's result, and channels not named stay zero."""
     from . import importer
-    shape = tuple(roi.shape)
-    dtype = np.dtype(getattr(roi, "np_dtype", None) or roi.dtype)
+    dtype, shape, _ = dimg.describe(roi)
     if dtype == np.float32 and not _saturate_dtype_ok(dtype):
         raise NotImplementedError('saturate of a float32 image depends on the NumPy release: set '
                                   'preprocess.FLOAT32_RULES = "numpy2" for the rules the reference pins')
     if not _saturate_dtype_ok(dtype):
         raise NotImplementedError(f"saturate of {dtype} images ({importer._BOUNDS_NAMES})")
     multichannel, channels = _setup_channels(shape, channel)
-    dv, owned = _as_volume(roi, "saturate_roi", 8 * (shape[3] if multichannel else 1) if _keep else 0)
-    try:
+    with dimg.open_image(roi, "saturate_roi", 8 * (shape[3] if multichannel else 1) if _keep else 0) as img:
         L = nat.lib()
-        dev = dv.tensor.device
-        nz, ny, nx = (int(v) for v in shape[:3])
-        sink = None
+        dev = img.tensor.device
+        nz, ny, nx = shape[:3]
+        res = None
         for chl in channels:
             settings = config.get_roi_profile(chl)
             vmin_pct = settings["clip_vmin"] if clip_vmin == -1 else clip_vmin
             vmax_pct = settings["clip_vmax"] if clip_vmax == -1 else clip_vmax
             factor = settings["max_thresh_factor"] if max_thresh_factor == -1 else max_thresh_factor
-            lo, hi = importer._percentiles_of_groups(dv, chl, [(0, nz)], vmin_pct, vmax_pct)
+            lo, hi = importer._percentiles_of_groups(img.volume, chl, [(0, nz)], vmin_pct, vmax_pct)
             vmin, vmax = lo[0], hi[0]
             stretched = vmin != vmax
             if stretched:
                 max_thresh = config.near_max[chl] * factor
                 if vmax < max_thresh:
                     vmax = max_thresh
-            if sink is None:
+            if res is None:
                 # (the first processed channel decides the result's dtype)
-                res_dtype = np.dtype(np.float64) if stretched else dtype
                 if not multichannel and not stretched:
-                    if _out is not None:
-                        host = _resolve_out(_out, shape, dtype)
-                        host[...] = _host_copy(roi)
-                        return host
-                    return dv.tensor if _keep else _host_copy(roi)
-                if _keep and res_dtype == np.float64:
-                    t = (torch.zeros if multichannel else torch.empty)(shape, dtype=torch.float64, device=dev)
-                    sink = _Sink(None, t)
-                else:
-                    host = _resolve_out(_out, shape, res_dtype)
-                    if multichannel:
-                        host[...] = 0
-                    sink = _Sink(host, None)
+                    # (unchanged: the image itself for the next task, otherwise a copy of it in its own dtype)
+                    if _keep and _out is None:
+                        return img.tensor
+                    res = dimg.Result(shape, dtype, out=_out)
+                    res.host[...] = img.host()
+                    return res.value()
+                res_dtype = np.dtype(np.float64) if stretched else dtype
+                res = dimg.Result(shape, res_dtype, _keep and res_dtype == np.float64, _out, zero_fill=multichannel,
+                                  device=dev)
             c_sink = chl if multichannel else None
             if not stretched:
                 # (an unchanged channel behind a stretched one: stored with NumPy's cast into the result's dtype)
-                src = (dv.tensor[..., chl] if multichannel else dv.tensor).cpu().numpy()
-                if sink.tensor is not None:
-                    sink.put(0, nz, c_sink, torch.from_numpy(np.ascontiguousarray(src, dtype=np.float64)).to(dev))
-                else:
-                    (sink.host[..., chl] if multichannel else sink.host)[...] = src
+                src = img.tensor[..., chl] if multichannel else img.tensor
+                if res.host is None:
+                    src = torch.from_numpy(np.ascontiguousarray(src.cpu().numpy(), dtype=np.float64)).to(dev)
+                res.put(0, nz, c_sink, src)
                 continue
-            step, _ = _slabs((nz, ny, nx))
+            step, _ = dimg.slab_step((nz, ny, nx), 8)
             slab = torch.empty(step * ny * nx, dtype=torch.float64, device=dev)
-            v = dv.view(chl, False)
             for z0 in range(0, nz, step):
                 z1 = min(nz, z0 + step)
-                esize = dv.tensor.element_size()
-                src = nat.DsView(v.d_data + z0 * v.stride_z * esize, v.dtype, 0, v.stride_z, v.stride_y, v.stride_x)
+                src = dimg.view(img, chl, z0)
                 nat.check(L.mmx_stretch(ctypes.byref(src), z1 - z0, ny, nx, float(vmin), float(vmax), slab.data_ptr(),
-                                        _stream()), "mmx_stretch")
-                sink.put(z0, z1, c_sink, slab[:(z1 - z0) * ny * nx].view(z1 - z0, ny, nx))
+                                        dimg.stream()), "mmx_stretch")
+                res.put(z0, z1, c_sink, slab[:(z1 - z0) * ny * nx].view(z1 - z0, ny, nx))
             torch.cuda.current_stream().synchronize()
-        if sink is None:
-            return None                     # (no channel processed: the reference returns None)
-        return sink.tensor if sink.tensor is not None else sink.host
-    finally:
-        if owned:
-            dv.close()
+        return None if res is None else res.value()     # (no channel processed: the reference returns None)
 
 
 # ------------------------------------------------------------------------------------------------------ denoise
@@ -561,21 +440,21 @@ def denoise_check_args(dtype, channels, what: str):
     return todo
 
 
-def _denoise_channel(dv, chl: int, lo, hi, strength, thr, bufs, host_view, stats=None):
+def _denoise_channel(img, chl: int, lo, hi, strength, thr, bufs, host_view, stats=None):
     """One channel through the passes: ``(packed float64 image on the device, eroded?)`` -- the unsharp result (or the
     clipped image) in one of ``bufs``; the erosion is the caller's, on the result's way out."""
     from . import preprocess
     L = nat.lib()
-    dev = dv.tensor.device
-    nz, ny, nx = (int(v) for v in dv.shape[:3])
+    dev = img.tensor.device
+    nz, ny, nx = img.shape[:3]
     n_vox = nz * ny * nx
-    stream = _stream()
-    src = _ds_view(dv, chl)
+    stream = dimg.stream()
+    src = dimg.view(img, chl)
     erode = False
     if thr:
         d_sums = torch.zeros(2, dtype=torch.int64, device=dev)
         nat.check(L.mmx_dn_sum(ctypes.byref(src), nz, ny, nx, d_sums.data_ptr(), stream), "mmx_dn_sum")
-        if dv.np_dtype.kind == "f":
+        if img.np_dtype.kind == "f":
             sx, sa = (float(v) for v in d_sums.view(torch.float64).cpu().numpy())
             verdict = erosion_gate(sx, sa, n_vox, thr)
         else:
@@ -612,8 +491,7 @@ def denoise_roi(roi, channel=None, _keep=False, _out=None, _stats=None):
     fit the device beside its two float64 working buffers are a ``NotImplementedError`` (:func:`denoise_check_args`).
     ``_keep=True`` leaves a float64 tensor on the device for the next task of a chain, otherwise the result leaves z-slab
     by z-slab, through ``_out`` when given; ``_stats`` (a dict, for tests and tools) receives the gate's verdicts."""
-    shape = tuple(roi.shape)
-    dtype = np.dtype(getattr(roi, "np_dtype", None) or roi.dtype)
+    dtype, shape, _ = dimg.describe(roi)
     multichannel, channels = _setup_channels(shape, channel)
     todo = denoise_check_args(dtype, list(channels), "denoise_roi")
     if len(shape) not in (3, 4):
@@ -629,51 +507,34 @@ def denoise_roi(roi, channel=None, _keep=False, _out=None, _stats=None):
     # device as the result (it takes the second), every channel of a multichannel result that stays; and the slab the
     # eroded planes leave through
     n_bufs = 2 if blurs or (keep_single and erodes) else 1
-    step, _ = _slabs((nz, ny, nx))
+    step, _ = dimg.slab_step((nz, ny, nx), 8)
     slab_bytes = step * ny * nx * 8 if erodes and not keep_single else 0
-    dv, owned = _as_volume(roi, "denoise_roi", 8 * n_bufs + (8 * shape[3] if _keep and multichannel else 0), slab_bytes)
-    try:
+    with dimg.open_image(roi, "denoise_roi", 8 * n_bufs + (8 * shape[3] if _keep and multichannel else 0),
+                         slab_bytes) as img:
         L = nat.lib()
-        dev = dv.tensor.device
+        dev = img.tensor.device
         bufs = [torch.empty(n_vox, dtype=torch.float64, device=dev) for _ in range(n_bufs)]
-        if _keep and multichannel:
-            sink = _Sink(None, torch.zeros(shape, dtype=torch.float64, device=dev))
-        elif not _keep:
-            host = _resolve_out(_out, shape, np.float64)
-            if multichannel:
-                host[...] = 0
-            sink = _Sink(host, None)
+        out = dimg.Result(shape, np.float64, _keep, _out, zero_fill=multichannel, device=dev)
         slab = torch.empty(slab_bytes // 8, dtype=torch.float64, device=dev) if slab_bytes else None
-        result = None
         for chl, lo, hi, strength, thr in todo:
             def host_view(chl=chl):
                 # (the view the reference's np.mean would see: NumPy's summation order depends on the layout)
-                arr = dv.tensor.cpu().numpy() if not isinstance(roi, np.ndarray) else roi
+                arr = img.host()
                 return arr[..., chl] if multichannel else arr
-            res, erode = _denoise_channel(dv, chl, lo, hi, strength, thr, bufs, host_view, _stats)
-            if keep_single:
-                if erode:
-                    other = bufs[1] if res is bufs[0] else bufs[0]
-                    nat.check(L.mmx_dn_erode(res.data_ptr(), nz, ny, nx, 0, nz, other.data_ptr(), _stream()),
+            res, erode = _denoise_channel(img, chl, lo, hi, strength, thr, bufs, host_view, _stats)
+            c_out = chl if multichannel else None
+            if erode and keep_single:
+                other = bufs[1] if res is bufs[0] else bufs[0]
+                nat.check(L.mmx_dn_erode(res.data_ptr(), nz, ny, nx, 0, nz, other.data_ptr(), dimg.stream()),
+                          "mmx_dn_erode")
+                res = other
+            elif erode:
+                for z0 in range(0, nz, step):
+                    z1 = min(nz, z0 + step)
+                    nat.check(L.mmx_dn_erode(res.data_ptr(), nz, ny, nx, z0, z1, slab.data_ptr(), dimg.stream()),
                               "mmx_dn_erode")
-                    res = other
-                result = res.view(shape)
-                continue
-            c_sink = chl if multichannel else None
-            vol = res.view(nz, ny, nx)
-            for z0 in range(0, nz, step):
-                z1 = min(nz, z0 + step)
-                if erode:
-                    nat.check(L.mmx_dn_erode(res.data_ptr(), nz, ny, nx, z0, z1, slab.data_ptr(), _stream()),
-                              "mmx_dn_erode")
-                    sink.put(z0, z1, c_sink, slab[:(z1 - z0) * ny * nx].view(z1 - z0, ny, nx))
-                else:
-                    sink.put(z0, z1, c_sink, vol[z0:z1])
+                    out.put(z0, z1, c_out, slab[:(z1 - z0) * ny * nx].view(z1 - z0, ny, nx))
+            if keep_single or not erode:
+                out.drain(res.view(nz, ny, nx), c_out)      # (kept, single-channel: the working buffer is the result)
             torch.cuda.current_stream().synchronize()
-        if keep_single:
-            torch.cuda.current_stream().synchronize()
-            return result
-        return sink.tensor if sink.tensor is not None else sink.host
-    finally:
-        if owned:
-            dv.close()
+        return out.value()

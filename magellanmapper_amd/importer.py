@@ -30,7 +30,7 @@ import numpy as np
 import yaml
 
 from . import _native as nat
-from . import config
+from . import config, device_image
 from .stack_detect import Image5d
 
 _logger = logging.getLogger("magellanmapper_amd")
@@ -248,11 +248,6 @@ def _as_zyxc(arr, multichannel: bool):
     return arr.reshape(zyx + ((arr.shape[-1],) if multichannel else ()))
 
 
-def _free_device_bytes() -> int:
-    import torch
-    return int(torch.cuda.mem_get_info()[0])
-
-
 def calc_intensity_bounds(image5d, lower=0.5, upper=99.5, dim_channel=4):
     """Percentiles of each channel over the WHOLE image (importer.py:1415-1444): ``(lows, highs)``, one entry per
     channel.  The image -- a NumPy array, a memory map or a ``DeviceVolume`` -- is multichannel when it has more than
@@ -270,10 +265,10 @@ def calc_intensity_bounds(image5d, lower=0.5, upper=99.5, dim_channel=4):
             raise NotImplementedError(f"percentiles of {arr.dtype} images ({_BOUNDS_NAMES})")
         if arr.size == 0:
             raise ValueError("empty image")
-        if arr.nbytes > 0.9 * _free_device_bytes():
+        if arr.nbytes > 0.9 * device_image.free_bytes():
             raise ValueError(
                 f"whole-image bounds need the image on the device at once: {arr.nbytes} bytes do not fit "
-                f"({_free_device_bytes()} free); measure_near_bounds walks a larger image plane by plane")
+                f"({device_image.free_bytes()} free); measure_near_bounds walks a larger image plane by plane")
         dv = DeviceVolume(_as_zyxc(arr, multichannel), streamed=False)
     z0 = dv.z_off
     group = [(z0, z0 + int(dv.tensor.shape[0]))]
@@ -380,7 +375,7 @@ def measure_near_bounds(img, lower=0.5, upper=99.5, assign=False):
         n_chl = arr.shape[3] if arr.ndim == 4 else 1
         lows, highs = [[] for _ in range(n_chl)], [[] for _ in range(n_chl)]
         nz = arr.shape[0]
-        limit = BOUNDS_CHUNK_BYTES if BOUNDS_CHUNK_BYTES is not None else _free_device_bytes() // 3
+        limit = BOUNDS_CHUNK_BYTES if BOUNDS_CHUNK_BYTES is not None else device_image.free_bytes() // 3
         plane_bytes = max(1, arr.nbytes // nz)
         step = nz if arr.nbytes <= limit else max(1, int(limit // plane_bytes))
         starts = list(range(0, nz, step))

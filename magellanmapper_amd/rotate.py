@@ -27,16 +27,11 @@ from typing import Sequence, Tuple
 
 import numpy as np
 
-try:
-    import torch
-except ImportError:  # pragma: no cover
-    torch = None
+import torch
 
 from . import _native as nat
-from . import equalize
-
-#: bytes of one z-slab of a result on its way into a host array handed as the output
-SLAB_BYTES = 256 << 20
+from . import device_image as dimg
+from .volume import DeviceVolume
 
 
 def rotation_matrix(rows: int, cols: int, angle: float) -> np.ndarray:
@@ -78,43 +73,25 @@ def _axis_of(axis, ndim: int) -> int:
     return a
 
 
-def _plane_shape(shape3, axis: int) -> Tuple[int, int]:
+def plane_shape(shape3, axis: int) -> Tuple[int, int]:
     return tuple(int(s) for i, s in enumerate(shape3) if i != axis)
-
-
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _view_of(t) -> Tuple[nat.DsView, int, Tuple[int, int, int], int]:
-    """``(view, elements behind it, (nz, ny, nx), channels)`` of a ``(z, y, x[, c])`` device tensor through its strides;
-    the channels of a voxel have to lie beside each other."""
-    code = nat.NP_TO_MMX[np.dtype(str(t.dtype).replace("torch.", ""))]
-    st = t.stride()
-    n_chl = int(t.shape[3]) if t.ndim == 4 else 1
-    if t.ndim == 4 and n_chl > 1 and int(st[3]) != 1:
-        raise ValueError("the channels of a voxel must lie at consecutive elements")
-    elems = 1 + sum((int(n) - 1) * int(s) for n, s in zip(t.shape, st))
-    # (an axis of one voxel is never stepped along: whatever stride it reports, a zero included, a valid one is passed)
-    sz, sy, sx = (int(s) if int(n) > 1 else max(int(s), n_chl) for n, s in zip(t.shape[:3], st[:3]))
-    view = nat.DsView(int(t.data_ptr()), code, 0, sz, sy, sx)
-    return view, elems, tuple(int(v) for v in t.shape[:3]), n_chl
 
 
 def rotate_tensor(src, dst, angle: float, axis: int, order: int) -> None:
     """One rotation of the ``(z, y, x[, c])`` device tensor ``src`` into ``dst`` (same shape and dtype, another
     buffer; any strides whose channels lie beside each other): the two launches, stream-ordered."""
     L = nat.lib()
-    sv, s_elems, shape3, n_chl = _view_of(src)
-    dv, d_elems, d_shape3, d_chl = _view_of(dst)
-    if shape3 != d_shape3 or n_chl != d_chl or src.dtype != dst.dtype:
+    if tuple(src.shape) != tuple(dst.shape) or src.dtype != dst.dtype:
         raise ValueError("source and destination differ in shape or dtype")
-    rows, cols = _plane_shape(shape3, axis)
+    sv, s_elems, n_chl = dimg.view(src)
+    dv, d_elems, _ = dimg.view(dst)
+    shape3 = tuple(int(v) for v in src.shape[:3])
+    rows, cols = plane_shape(shape3, axis)
     m = rotation_matrix(rows, cols, angle)
     if src.dtype == torch.float32:
         m = m.astype(np.float32).astype(np.float64)
     m = np.ascontiguousarray(m.reshape(-1))
-    stream = _stream()
+    stream = dimg.stream()
     bounds = None
     if order == 1:
         bounds = torch.empty(shape3[axis] * 2, dtype=torch.float64, device=src.device)
@@ -125,17 +102,6 @@ def rotate_tensor(src, dst, angle: float, axis: int, order: int) -> None:
                                 stream), "mmx_rotate_warp")
 
 
-def _into_host(t, out) -> np.ndarray:
-    """A device tensor into a host array, z-slab by z-slab (``out``: the array, or a factory ``out(shape, dtype)``)."""
-    dtype = np.dtype(str(t.dtype).replace("torch.", ""))
-    host = equalize._resolve_out(out, tuple(t.shape), dtype)
-    per_plane = max(1, int(np.prod(t.shape[1:], dtype=np.int64)) * dtype.itemsize)
-    step = max(1, min(int(t.shape[0]), SLAB_BYTES // per_plane))
-    for z0 in range(0, int(t.shape[0]), step):
-        host[z0:z0 + step] = t[z0:z0 + step].cpu().numpy()
-    return host
-
-
 def rotate_chain(image, rotation: Sequence[Tuple[float, int]], order: int = 1, resize: bool = False,
                  what: str = "rotate_img", _keep: bool = False, _out=None):
     """``image`` through the rotations ``((angle, axis), ...)`` in order, each on the previous result; the volume stays
@@ -143,62 +109,38 @@ def rotate_chain(image, rotation: Sequence[Tuple[float, int]], order: int = 1, r
     (a host array comes back), a torch tensor (a tensor on the device comes back) or a ``DeviceVolume`` (a
     ``DeviceVolume`` comes back); never changed.  ``_keep``: the result stays a device tensor whatever came in;
     ``_out``: the host array (or factory) the result is written into."""
-    from .volume import DeviceVolume, _require_gpu
-    resident = isinstance(image, DeviceVolume)
-    is_tensor = torch is not None and isinstance(image, torch.Tensor)
-    if resident:
-        dtype, shape = image.np_dtype, tuple(image.tensor.shape)
-        if image.z_off or image.y_off or tuple(image.tensor.shape[:3]) != tuple(image.shape[:3]):
-            raise ValueError("a DeviceVolume that holds a box of its image cannot be rotated")
-    elif is_tensor:
-        dtype, shape = np.dtype(str(image.dtype).replace("torch.", "")), tuple(image.shape)
-    else:
-        image = image if isinstance(image, np.ndarray) else np.asarray(image)
-        dtype, shape = image.dtype, tuple(image.shape)
+    dtype, shape, on_device = dimg.describe(image)
     rotation = [(float(r[0]), r[1]) for r in rotation]
     if rotation:
         check_args(dtype, order, resize, what)
-    if len(shape) not in (3, 4):
-        raise ValueError("image must be (z, y, x) or (z, y, x, c)")
-    if min(shape) < 1:
-        raise ValueError(f"an image of shape {shape} is empty")
-    rotation = [(angle, _axis_of(axis, len(shape))) for angle, axis in rotation]
-    nbytes = int(np.prod(shape, dtype=np.int64)) * np.dtype(dtype).itemsize
-    on_device = resident or (is_tensor and image.is_cuda)
-    # the source (when it is not there yet) and the destination; a second destination when the source must survive a
-    # chain of several rotations
-    need = nbytes * ((0 if on_device else 1) + (1 if rotation else 0) + (1 if on_device and len(rotation) > 1 else 0))
-    equalize._check_fits(need, what)
 
-    if resident:
-        image.wait_all()
-        cur = image.tensor
-    elif is_tensor:
-        cur = image if image.is_cuda else image.to(_require_gpu())
-    else:
-        cur = torch.from_numpy(np.ascontiguousarray(image)).to(_require_gpu())
-    owned = not on_device           # (`cur` is this call's own upload: a chain may write over it)
-    spare = None
-    for angle, axis in rotation:
-        if spare is None:
-            spare = torch.empty(shape, dtype=cur.dtype, device=cur.device)
-        rotate_tensor(cur, spare, angle, axis, order)
-        if owned:
-            cur, spare = spare, cur
-        else:
-            cur, spare, owned = spare, None, True
-    if not rotation and (on_device or _keep):
-        cur = cur.clone() if on_device else cur
-    if _out is not None:
-        res = _into_host(cur, _out)
-    elif _keep or is_tensor:
-        res = cur if (_keep or image.is_cuda) else cur.cpu()
-    elif resident:
-        res = DeviceVolume(cur)
-    else:
-        res = _into_host(cur, None)
-    torch.cuda.current_stream().synchronize()
-    return res
+    def check_axes():
+        rotation[:] = [(angle, _axis_of(axis, len(shape))) for angle, axis in rotation]
+    # beside the source: the destination; a second one when the source must survive a chain of several rotations
+    nbytes = int(np.prod(shape, dtype=np.int64)) * np.dtype(dtype).itemsize
+    need = nbytes * ((1 if rotation else 0) + (1 if on_device and len(rotation) > 1 else 0))
+    with dimg.open_image(image, what, extra_bytes=need, before_fit=check_axes) as img:
+        cur, owned = img.tensor, img.owned      # (owned: this call's own upload, which a chain may write over)
+        spare = None
+        for angle, axis in rotation:
+            if spare is None:
+                spare = torch.empty(shape, dtype=cur.dtype, device=cur.device)
+            rotate_tensor(cur, spare, angle, axis, order)
+            if owned:
+                cur, spare = spare, cur
+            else:
+                cur, spare, owned = spare, None, True
+        if not rotation and on_device:
+            cur = cur.clone()
+        # what comes back: the array or factory given, the kind that came in, or a device tensor for the next task
+        resident, is_tensor = isinstance(image, DeviceVolume), isinstance(image, torch.Tensor)
+        as_tensor = _out is None and (_keep or resident or is_tensor)
+        res = dimg.Result(shape, dtype, as_tensor, _out)
+        res.drain(cur)
+        torch.cuda.current_stream().synchronize()
+    if _keep or not as_tensor:
+        return res.value()
+    return DeviceVolume(cur) if resident else (cur if on_device else cur.cpu())
 
 
 def rotate_nd(img_np, angle: float, axis: int = 0, order: int = 1, resize: bool = False):
@@ -207,7 +149,6 @@ def rotate_nd(img_np, angle: float, axis: int = 0, order: int = 1, resize: bool 
     back), torch tensor or ``DeviceVolume``.  A 2-D image is wrapped into one plane, as the reference does, so its
     ``axis`` should stay 0.  See the module's docstring for what is refused."""
     ndim = len(img_np.shape)
-    if ndim == 2:
-        if isinstance(img_np, np.ndarray) or (torch is not None and isinstance(img_np, torch.Tensor)):
-            return rotate_chain(img_np[None], [(angle, axis)], order, resize, "rotate_nd")[0]
+    if ndim == 2 and isinstance(img_np, (np.ndarray, torch.Tensor)):
+        return rotate_chain(img_np[None], [(angle, axis)], order, resize, "rotate_nd")[0]
     return rotate_chain(img_np, [(angle, axis)], order, resize, "rotate_nd")

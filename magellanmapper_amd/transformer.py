@@ -23,11 +23,12 @@ is started before the current layer's kernels and waited for only ahead of its o
 (a large read-only memory map cut along z or y) runs beside them; the device then holds two layers, the passes'
 intermediates and the output volume, which is copied out once.  Other sources go up synchronously, layer after layer.
 
-``preprocess_img`` (reference transformer.py:353-393, ``--proc preprocess=saturate,remap,rotate``) runs the whole-image
-tasks of :mod:`equalize` and ``rotate_img`` (:mod:`rotate`: the atlas profile's chain of plane rotations, two streaming
-passes per rotation) in the order given and writes ``<base>_image5d.npy`` slab by slab; the task ``denoise`` is refused
-by name, and so is ``rotate`` while no atlas profile is set.  The ``denoise`` task on a whole image, setting up atlas
-profiles, ``order=0`` label images in ``transpose_img`` and registration stay in the reference.
+``preprocess_img`` (reference transformer.py:353-393, ``--proc preprocess=saturate,denoise,remap,rotate``) runs the
+whole-image tasks of :mod:`equalize` (``saturate``, ``denoise``, ``remap``) and ``rotate_img`` (:mod:`rotate`: the atlas
+profile's chain of plane rotations, two streaming passes per rotation) in the order given and writes
+``<base>_image5d.npy`` slab by slab; ``rotate`` is refused while no atlas profile is set, ``denoise`` for an integer
+image that nothing ahead of it stretched to 0-1.  How an image goes up and a result comes down is :mod:`device_image`'s.
+Setting up atlas profiles, ``order=0`` label images in ``transpose_img`` and registration stay in the reference.
 """
 from __future__ import annotations
 
@@ -36,14 +37,12 @@ import time
 from typing import Dict, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
-
-try:
-    import torch
-except ImportError:  # pragma: no cover
-    torch = None
+import torch
 
 from . import _native as nat
-from . import chunking, config, importer, kernels1d
+from . import chunking, config, equalize, importer, kernels1d
+from . import device_image as dimg
+from . import rotate as rot
 
 #: chunk size of the reference's plan (transformer.py:227), in z, y, x
 MAX_PIXELS = (100, 500, 500)
@@ -206,14 +205,6 @@ def aa_sigmas(in_shape: Sequence[int], out_shape: Sequence[int]) -> np.ndarray:
 
 
 # ------------------------------------------------------------------------------------------------ the device side
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _to_dev(arr: np.ndarray, dev):
-    return torch.from_numpy(np.ascontiguousarray(arr).view(np.uint8).reshape(-1)).to(dev)
-
-
 class _Source:
     """The image, or one layer of it, on the device in FILE orientation, addressed in the orientation of the output:
     per-channel views whose strides are the file's, permuted (a plane swap costs no copy), and whose base is shifted
@@ -225,7 +216,7 @@ class _Source:
         multichannel = tensor.ndim == 4
         st = tensor.stride()
         self.strides = tuple(int(st[axes[a]]) for a in range(3))
-        code = nat.NP_TO_MMX[np.dtype(str(tensor.dtype).replace("torch.", ""))]
+        code = nat.NP_TO_MMX[dimg.np_dtype_of(tensor)]
         base = int(tensor.data_ptr()) - lo * self.strides[0] * tensor.element_size()
         n_chl = tensor.shape[3] if multichannel else 1
         self.views = [nat.Volume(base + c * tensor.element_size(), code, 0, *self.strides) for c in range(n_chl)]
@@ -259,7 +250,7 @@ def _run_batch(src: _Source, raw_dtype: np.dtype, chunks, out_t, antialias: bool
     """One batch: ``chunks`` = ``(origin zyx, in shape, output offset zyx, out shape)`` in the swapped volume."""
     L = nat.lib()
     dev = out_t.device
-    stream = _stream()
+    stream = dimg.stream()
     nb = len(chunks)
     raw_code = nat.NP_TO_MMX[np.dtype(raw_dtype)]
     f32 = raw_code == nat.MMX_F32
@@ -275,7 +266,7 @@ def _run_batch(src: _Source, raw_dtype: np.dtype, chunks, out_t, antialias: bool
     blocks = np.zeros(nb, dtype=nat.BLOCK_DTYPE)
     for i, (o, shp, _, _) in enumerate(chunks):
         blocks[i] = (o[0] * sz + o[1] * sy + o[2] * sx, shp[0], shp[1], shp[2], i, 0, 0)
-    d_blocks = _to_dev(blocks, dev)
+    d_blocks = dimg.to_dev(blocks, dev)
     mm = np.empty((nb, 2))
     mm[:, 0], mm[:, 1] = np.inf, -np.inf
     d_mm = torch.from_numpy(mm).to(dev)
@@ -338,7 +329,7 @@ def _run_batch(src: _Source, raw_dtype: np.dtype, chunks, out_t, antialias: bool
             h_r = np.ascontiguousarray(radii[:, a])
             h_pick = np.ascontiguousarray(np.concatenate(picks), dtype=np.int32)
             buf = torch.empty(nb * slot, dtype=mid_t, device=dev)
-            d_rec, d_w, d_r, d_pick = _to_dev(rec, dev), _to_dev(wts, dev), _to_dev(h_r, dev), _to_dev(h_pick, dev)
+            d_rec, d_w, d_r, d_pick = (dimg.to_dev(h, dev) for h in (rec, wts, h_r, h_pick))
             nat.check(L.mmx_ds_gauss_pick_batch(ctypes.byref(cur), d_rec.data_ptr(), rec.ctypes.data, nb, a,
                                                 d_w.data_ptr(), d_r.data_ptr(), h_r.ctypes.data, pitch,
                                                 d_pick.data_ptr(), h_pick.ctypes.data, len(h_pick), dst_sy, dst_sz,
@@ -365,7 +356,7 @@ def _run_batch(src: _Source, raw_dtype: np.dtype, chunks, out_t, antialias: bool
                       ext[i][2], oshp[0], oshp[1], oshp[2], i, t3[0], t3[1], t3[2], (0, 0))
         h_idx = np.ascontiguousarray(np.concatenate(tabs_i), dtype=np.int32)
         h_wts = np.ascontiguousarray(np.concatenate(tabs_w), dtype=np.float64)
-        d_rec, d_idx, d_wts = _to_dev(rec, dev), _to_dev(h_idx, dev), _to_dev(h_wts, dev)
+        d_rec, d_idx, d_wts = (dimg.to_dev(h, dev) for h in (rec, h_idx, h_wts))
         dst = nat.DsView(out_t.data_ptr(), mid_code, 0, int(ost[0]), int(ost[1]), int(ost[2]))
         nat.check(L.mmx_ds_zoom_batch(ctypes.byref(cur), ctypes.byref(dst), out_t.numel(), d_rec.data_ptr(),
                                       rec.ctypes.data, nb, d_idx.data_ptr(), h_idx.ctypes.data, len(h_idx),
@@ -418,13 +409,12 @@ def downsample(img, rescale: Optional[float] = None, target_size: Optional[Seque
         if img.z_off or img.y_off:
             raise ValueError("a DeviceVolume that holds a box of its image cannot be down-sampled")
         img.wait_all()
-        dtype, fshape, multichannel = img.np_dtype, tuple(img.tensor.shape), img.multichannel
-    else:
-        if not isinstance(img, np.ndarray):
-            img = np.asarray(img)
-        if img.ndim not in (3, 4):
-            raise ValueError("image must be (z, y, x) or (z, y, x, c)")
-        dtype, fshape, multichannel = img.dtype, tuple(img.shape), img.ndim == 4
+    elif not isinstance(img, np.ndarray):
+        img = np.asarray(img)
+    dtype, fshape, _ = dimg.describe(img)
+    if len(fshape) not in (3, 4):
+        raise ValueError("image must be (z, y, x) or (z, y, x, c)")
+    multichannel = len(fshape) == 4
     if np.dtype(dtype) not in nat.NP_TO_MMX:
         raise NotImplementedError(f"down-sampling of {dtype} images is not built "
                                   f"({', '.join(str(d) for d in nat.NP_TO_MMX)} are)")
@@ -461,7 +451,7 @@ def downsample(img, rescale: Optional[float] = None, target_size: Optional[Seque
     else:
         budget = layer_bytes if layer_bytes is not None else LAYER_BYTES
         if budget is None:
-            budget = int(0.6 * torch.cuda.mem_get_info()[0])
+            budget = int(0.6 * dimg.free_bytes())
         if img.nbytes <= budget:
             src = _upload(img, axes, 0, shape3[0], dev, True)
             try:
@@ -610,7 +600,6 @@ def rotate_img(roi, rotate=None, order=None, _keep=False, _out=None):
     order 1 are a ``NotImplementedError`` (:mod:`rotate`).  The one deliberate divergence: ``rotate["rotation"] = None``
     (the profile's default: no rotation) returns a copy of the image unchanged, where the reference's loop fails on
     ``None`` with a ``TypeError``."""
-    from . import rotate as rot
     if rotate is None:
         prof = getattr(config, "atlas_profile", None)
         if prof is None:
@@ -627,55 +616,76 @@ def rotate_img(roi, rotate=None, order=None, _keep=False, _out=None):
     return rot.rotate_chain(roi, rotation, order, rotate["resize"], "rotate_img", _keep, _out)
 
 
+def tasks_ahead(preprocs, dtype):
+    """``[(task, the voxel type it will see)]`` of the names ``preprocs`` on an image of ``dtype``, as far as can be told
+    ahead of running anything: float64 once a ``saturate``, ``remap`` or ``denoise`` stands ahead, the image's own until
+    then (``rotate`` keeps the type).  A name that is no task is skipped with a warning.  Known gaps, left as they are:
+    a multichannel ``remap`` hands on the image's own dtype, and so does ``saturate`` of a flat channel (percentiles
+    equal: unchanged)."""
+    tasks = []
+    for preproc in preprocs:
+        task = _get_enum(preproc, config.PreProcessKeys)
+        if task is None:
+            config.logger.warning("No preprocessing task found for: %s", preproc)
+            continue
+        stays = all(t is config.PreProcessKeys.ROTATE for t, _ in tasks)
+        tasks.append((task, np.dtype(dtype) if stays else np.dtype(np.float64)))
+    return tasks
+
+
+def _check_denoise(dtype, shape, channel) -> None:
+    if dtype.kind in "iu":
+        # (np.clip of raw counts to [clip_min, clip_max] gives a two-valued image: nothing anyone runs)
+        raise NotImplementedError(
+            "the whole-image task 'denoise' of an image that was not stretched to 0-1 stays in the reference "
+            "(an integer image with neither 'saturate' nor 'remap' ahead of it in the task list)")
+    _, chls = equalize._setup_channels(shape, channel)
+    equalize.denoise_check_args(dtype, list(chls), "the whole-image task 'denoise'")
+
+
+def _check_rotate(dtype, shape, channel) -> None:
+    prof = getattr(config, "atlas_profile", None)
+    if prof is None:
+        raise NotImplementedError("the whole-image task 'rotate' reads config.atlas_profile, and none is set: "
+                                  "setting up atlas profiles stays in the reference")
+    if prof["rotate"]["rotation"] is not None:
+        rot.check_args(dtype, prof["rotate"]["order"], prof["rotate"]["resize"], "the whole-image task 'rotate'")
+
+
+#: task -> (what it refuses ahead of everything, from ``(voxel type ahead, (z, y, x[, c]) shape, channel)``; how it runs)
+_TASKS = {
+    config.PreProcessKeys.SATURATE: (None, lambda roi, channel, **kw: equalize.saturate_roi(roi, channel=channel, **kw)),
+    config.PreProcessKeys.DENOISE: (_check_denoise, lambda roi, channel, **kw: equalize.denoise_roi(roi, channel, **kw)),
+    config.PreProcessKeys.REMAP: (None, lambda roi, channel, **kw: equalize.remap_intensity(roi, channel, **kw)),
+    config.PreProcessKeys.ROTATE: (_check_rotate, lambda roi, channel, **kw: rotate_img(roi, **kw)),
+}
+
+
 def preprocess_img(image5d, preprocs, channel, out_path):
     """``transformer.preprocess_img`` (reference transformer.py:353-393): run the whole-image tasks ``preprocs`` (names
     of ``config.PreProcessKeys``, one or a sequence) on ``image5d[0]`` in the order given, each on the previous result,
     for ``channel`` (``None``: all), and write ``<out_path base>_image5d.npy`` with its ``_meta.yml`` (the settings in
     :mod:`config`, the intensity bounds of the result).  ``saturate``, ``denoise`` and ``remap`` (:mod:`equalize`) and
     ``rotate`` (:func:`rotate_img`, all channels, the settings of ``config.atlas_profile``) run on the device.  Refused
-    with a ``NotImplementedError`` before anything runs: ``denoise`` of an integer image with neither ``saturate`` nor
-    ``remap`` ahead of it (raw counts clipped to the profile's 0-1 bounds: that stays in the reference), of a float32
-    image, or with a truthy ``tot_var_denoise`` in a channel's profile (:func:`equalize.denoise_check_args`); ``rotate``
-    without an atlas profile or with settings :func:`rotate_img` refuses.  A name that is no task is skipped with a
-    warning.  The last task's result goes z-slab by
-    z-slab into the memory map of the output file, which is returned (``(1, z, y, x[, c])``); between tasks the image
-    stays on the device.  ``None`` for ``preprocs`` prints and returns ``None``."""
+    with a ``NotImplementedError`` before anything runs, from the voxel type each task will see (:func:`tasks_ahead`):
+    ``denoise`` of an integer image with neither ``saturate`` nor ``remap`` ahead of it (raw counts clipped to the
+    profile's 0-1 bounds: that stays in the reference), of a float32 image, or with a truthy ``tot_var_denoise`` in a
+    channel's profile (:func:`equalize.denoise_check_args`); ``rotate`` without an atlas profile or with settings
+    :func:`rotate_img` refuses.  The last task's result goes z-slab by z-slab into the memory map of the output file,
+    which is returned (``(1, z, y, x[, c])``); between tasks the image stays on the device.  ``None`` for ``preprocs``
+    prints and returns ``None``."""
     import os
-    from . import equalize
-    from . import rotate as rot
-    from .volume import DeviceVolume
     if preprocs is None:
         print("No preprocessing tasks to perform, skipping")
         return None
     if not (isinstance(preprocs, (list, tuple)) or np.ndim(preprocs) != 0):
         preprocs = [preprocs]
     tasks = []
-    for preproc in preprocs:
-        task = _get_enum(preproc, config.PreProcessKeys)
-        if task is config.PreProcessKeys.DENOISE:
-            stretched = any(t in (config.PreProcessKeys.SATURATE, config.PreProcessKeys.REMAP) for t in tasks)
-            if np.dtype(image5d.dtype).kind in "iu" and not stretched:
-                # (np.clip of raw counts to [clip_min, clip_max] gives a two-valued image: nothing anyone runs)
-                raise NotImplementedError(
-                    "the whole-image task 'denoise' of an image that was not stretched to 0-1 stays in the reference "
-                    "(an integer image with neither 'saturate' nor 'remap' ahead of it in the task list)")
-            # (what can be told ahead of the tasks: the voxel type only where the image arrives as it is)
-            _, chls = equalize._setup_channels(tuple(image5d.shape[1:]), channel)
-            equalize.denoise_check_args(np.float64 if stretched else image5d.dtype, list(chls),
-                                        "the whole-image task 'denoise'")
-        if task is config.PreProcessKeys.ROTATE:
-            prof = getattr(config, "atlas_profile", None)
-            if prof is None:
-                raise NotImplementedError("the whole-image task 'rotate' reads config.atlas_profile, and none is set: "
-                                          "setting up atlas profiles stays in the reference")
-            if prof["rotate"]["rotation"] is not None:
-                # (what can be told ahead of the tasks: the voxel type only where the image arrives as it is)
-                rot.check_args(image5d.dtype if not tasks else np.float64, prof["rotate"]["order"],
-                               prof["rotate"]["resize"], "the whole-image task 'rotate'")
-        if task is None:
-            config.logger.warning("No preprocessing task found for: %s", preproc)
-        else:
-            tasks.append(task)
+    for task, dtype in tasks_ahead(preprocs, image5d.dtype):
+        check = _TASKS[task][0]
+        if check is not None:
+            check(dtype, tuple(image5d.shape[1:]), channel)
+        tasks.append(task)
 
     # a float32 image that leaves as float32 (no task, `rotate` alone, or `remap` on several channels) has its intensity
     # bounds measured in float32: refused here, ahead of the tasks, unless preprocess.FLOAT32_RULES names the NumPy release
@@ -697,24 +707,14 @@ def preprocess_img(image5d, preprocs, channel, out_path):
     for i, task in enumerate(tasks):
         config.logger.info("Pre-processing task: %s", task)
         last = i == len(tasks) - 1
-        kw = dict(_out=make_out) if last else dict(_keep=True)
-        if task is config.PreProcessKeys.SATURATE:
-            roi = equalize.saturate_roi(roi, channel=channel, **kw)
-        elif task is config.PreProcessKeys.ROTATE:
-            roi = rotate_img(roi, **kw)
-        elif task is config.PreProcessKeys.DENOISE:
-            roi = equalize.denoise_roi(roi, channel, **kw)
-        else:
-            roi = equalize.remap_intensity(roi, channel, **kw)
-        if torch is not None and isinstance(roi, torch.Tensor):
-            roi = DeviceVolume(roi)
+        roi = _TASKS[task][1](roi, channel, **(dict(_out=make_out) if last else dict(_keep=True)))
     if not made:
-        # (no task ran, or the last one handed the image through unchanged: the image as it stands)
-        host = roi.tensor.cpu().numpy() if isinstance(roi, DeviceVolume) else roi
-        make_out(host.shape, host.dtype)[...] = host
+        # (no task ran: the image as it stands)
+        make_out(roi.shape, roi.dtype)[...] = roi
     image5d_out = made[-1]
     image5d_out.flush()
     lows, highs = importer.calc_intensity_bounds(image5d_out)
     importer.save_image_info(filename_info, [os.path.basename(out_path)], [image5d_out.shape], config.resolutions,
                              config.magnification, config.zoom, lows, highs)
     return image5d_out
+

@@ -78,8 +78,9 @@ class DeviceVolume:
         dev = device or _require_gpu()
         want_stream = STREAM_UPLOAD and streamed is not False
         if isinstance(image, torch.Tensor):
+            from .device_image import np_dtype_of       # (it imports this module: not at the top)
             t = image
-            np_dtype = np.dtype(str(t.dtype).replace("torch.", ""))
+            np_dtype = np_dtype_of(t)
         else:
             arr = np.asarray(image)
             if arr.dtype not in _NP_TO_MMX:

@@ -253,13 +253,13 @@ def test_bounds_match_reference_and_numpy(gpu, name):
 
 
 def test_float32_percentiles_and_oversize_images_are_refused(gpu, monkeypatch):
-    from magellanmapper_amd import importer
+    from magellanmapper_amd import device_image, importer
     vol32 = fixture_volume("f64").astype(np.float32)
     with pytest.raises(NotImplementedError):
         importer.calc_intensity_bounds(vol32[None])
     with pytest.raises(NotImplementedError):
         importer.measure_near_bounds(vol32)
-    monkeypatch.setattr(importer, "_free_device_bytes", lambda: 1000)
+    monkeypatch.setattr(device_image, "free_bytes", lambda: 1000)
     with pytest.raises(ValueError, match="whole-image"):
         importer.calc_intensity_bounds(fixture_volume("u16")[None])
 

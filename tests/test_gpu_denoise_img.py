@@ -8,7 +8,7 @@ import pytest
 import denoise_img_support as sup
 from conftest import load_golden
 from gpu_support import gpu  # noqa: F401
-from magellanmapper_amd import config, equalize, importer, preprocess, transformer
+from magellanmapper_amd import config, device_image, equalize, importer, preprocess, transformer
 from oracle import preprocess_oracle as ppo
 
 pytestmark = pytest.mark.gpu
@@ -138,8 +138,8 @@ def test_slabs_memmap_resident_volume_and_keep(gpu, profiles, over, monkeypatch,
     from magellanmapper_amd.volume import DeviceVolume
     img = sup.f64_image(31, (10, 37, 70))
     want = ppo.denoise_roi(img, profiles([over]))
-    monkeypatch.setattr(equalize, "SLAB_BYTES", 3 * img.shape[1] * img.shape[2] * 8)
-    assert equalize._slabs(img.shape) == (3, 4)
+    monkeypatch.setattr(device_image, "SLAB_BYTES", 3 * img.shape[1] * img.shape[2] * 8)
+    assert device_image.slab_step(img.shape, 8) == (3, 4)
     out = np.lib.format.open_memmap(str(tmp_path / "out.npy"), mode="w+", dtype=np.float64, shape=img.shape)
     got = preprocess.denoise_roi(img, _out=out)
     assert got is out and out.tobytes() == want.tobytes()
@@ -158,7 +158,7 @@ def test_two_channels(gpu, fx, profiles, monkeypatch):
     from magellanmapper_amd.volume import DeviceVolume
     two = sup.f64_image(4, sup.SHAPE2)
     profs = profiles([{}, sup.CHANNEL1])
-    monkeypatch.setattr(equalize, "SLAB_BYTES", 4 * two.shape[1] * two.shape[2] * 8)
+    monkeypatch.setattr(device_image, "SLAB_BYTES", 4 * two.shape[1] * two.shape[2] * 8)
     for channel, key in ((None, "two_all_out"), ([1], "two_c1_out")):
         got = preprocess.denoise_roi(DeviceVolume(two), channel)
         _same(got, fx[key])

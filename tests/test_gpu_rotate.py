@@ -9,7 +9,7 @@ import rotate_support as sup
 from conftest import load_golden
 from gpu_support import gpu  # noqa: F401
 from magellanmapper_amd import _native as nat
-from magellanmapper_amd import config, importer, preprocess, transformer
+from magellanmapper_amd import config, device_image, importer, preprocess, transformer
 
 pytestmark = pytest.mark.gpu
 
@@ -139,7 +139,7 @@ def _call(src_t, dst_t, shape3, n_chl, s_strides, d_strides, axis, order, angle,
     and compares those, the kernels are told the voxels' real type)."""
     import torch
     L = nat.lib()
-    code = nat.MMX_U16 if src_t.dtype == torch.int16 else nat.NP_TO_MMX[np.dtype(str(src_t.dtype).replace("torch.", ""))]
+    code = nat.MMX_U16 if src_t.dtype == torch.int16 else nat.NP_TO_MMX[device_image.np_dtype_of(src_t)]
     es = src_t.element_size()
     sv = nat.DsView(src_t.data_ptr() + src_off * es, code, 0, *s_strides)
     dv = nat.DsView(dst_t.data_ptr() + dst_off * es, code, 0, *d_strides)

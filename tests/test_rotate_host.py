@@ -8,7 +8,7 @@ import pytest
 
 import rotate_support as sup
 from conftest import load_golden
-from magellanmapper_amd import config, equalize, preprocess, transformer
+from magellanmapper_amd import config, device_image, preprocess, transformer
 from magellanmapper_amd import rotate as rot
 
 
@@ -82,7 +82,7 @@ def _no_device(monkeypatch):
     """Any touch of the device fails the test: the refusals below come from the arguments alone."""
     def boom(*a, **k):
         raise AssertionError("the device was touched")
-    monkeypatch.setattr(equalize, "_free_device_bytes", boom)
+    monkeypatch.setattr(device_image, "free_bytes", boom)
     monkeypatch.setattr(rot, "rotate_tensor", boom)
     from magellanmapper_amd import volume
     monkeypatch.setattr(volume, "_require_gpu", boom)
@@ -126,7 +126,7 @@ def test_refusals_from_the_arguments(monkeypatch, tmp_path):
 
 
 def test_image_that_does_not_fit_is_refused(monkeypatch, tmp_path):
-    monkeypatch.setattr(equalize, "_free_device_bytes", lambda: 1 << 20)
+    monkeypatch.setattr(device_image, "free_bytes", lambda: 1 << 20)
     img = np.zeros((64, 128, 128), dtype=np.uint16)
     with pytest.raises(NotImplementedError, match="does not fit"):
         preprocess.rotate_nd(img, 10, 0)
@@ -160,7 +160,7 @@ def test_rotation_none_is_refused_nowhere_ahead_of_the_device(monkeypatch):
 
     def reached():
         raise Reached()
-    monkeypatch.setattr(equalize, "_free_device_bytes", reached)
+    monkeypatch.setattr(device_image, "free_bytes", reached)
     f32 = np.zeros((4, 5, 6), dtype=np.float32)
     with pytest.raises(Reached):
         transformer.rotate_img(f32, {"rotation": None, "resize": True, "order": 7})

@@ -53,7 +53,7 @@ def main() -> None:
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("denoise_imgbench needs a GPU (there is no CPU fallback)")
-    from magellanmapper_amd import _native as nat, config, equalize, preprocess, synth
+    from magellanmapper_amd import _native as nat, config, device_image, equalize, preprocess, synth
     from magellanmapper_amd.volume import DeviceVolume
     from oracle import preprocess_oracle as ppo
     dev = torch.device("cuda", 0)
@@ -125,7 +125,7 @@ def main() -> None:
             vol = DeviceVolume(equalize.saturate_roi(DeviceVolume(u16), _keep=True))
             assert vol.np_dtype == np.float64
         esize = vol.tensor.element_size()
-        src = equalize._ds_view(vol, 0)
+        src = device_image.view(vol, 0)
         buf_a = torch.empty(nvox, dtype=torch.float64, device=dev)
         buf_b = torch.empty(nvox, dtype=torch.float64, device=dev)
         sums = torch.zeros(2, dtype=torch.int64, device=dev)

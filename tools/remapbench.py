@@ -47,7 +47,7 @@ def main() -> None:
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("remapbench needs a GPU (there is no CPU fallback)")
-    from magellanmapper_amd import _native as nat, config, equalize as eq, importer, synth
+    from magellanmapper_amd import _native as nat, config, device_image as dimg, equalize as eq, importer, synth
     from magellanmapper_amd.volume import DeviceVolume
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
@@ -100,10 +100,10 @@ def main() -> None:
             dv = DeviceVolume(t)
             k, nt, clim = eq.plan(shape, None, 0.01, 256)
             n_tiles = int(np.prod(nt))
-            raw_min, raw_max = eq._minmax(dv, 0)
+            raw_min, raw_max = eq.minmax(dv, 0)
             _, bins = eq.level_bin_table(np.uint16, raw_min, raw_max, 256)
-            d_bins = eq._to_dev(bins, dev)
-            src = eq._ds_view(dv, 0)
+            d_bins = dimg.to_dev(bins, dev)
+            src = dimg.view(dv, 0)
             geom = nat.EqGeom((ctypes.c_int32 * 3)(*shape), (ctypes.c_int32 * 3)(*k), (ctypes.c_int32 * 3)(*nt), 256)
             d_hist = torch.empty(n_tiles * 256, dtype=torch.int32, device=dev)
             passes = {}
@@ -116,7 +116,7 @@ def main() -> None:
                 print("%-16s %-8s %-10s %9.3f ms  %7.1f GB/s  (%.2f of the copy)" % (
                     shp, kind, name, ms, passes[name]["gb_s"], passes[name]["of_copy"]))
 
-            p("minmax", 2, lambda: eq._minmax(dv, 0))
+            p("minmax", 2, lambda: eq.minmax(dv, 0))
             p("hist", 2, lambda: nat.check(L.mmx_eq_hist(ctypes.byref(src), ctypes.byref(geom), d_bins.data_ptr(),
                                                          d_hist.data_ptr(), stream), "mmx_eq_hist"))
             hist = d_hist.cpu().numpy().view(np.uint32)
@@ -125,9 +125,9 @@ def main() -> None:
             nat.check(L.mmx_host_eq_maps(hist.ctypes.data, n_tiles, 256, clim, int(np.prod(k)), maps.ctypes.data, None),
                       "mmx_host_eq_maps")
             passes["host_maps_ms"] = round((time.perf_counter() - t0) * 1e3, 3)
-            d_maps = eq._to_dev(maps, dev)
+            d_maps = dimg.to_dev(maps, dev)
             tiles, coef = eq.axis_tables(shape, k, nt)
-            d_tiles, d_coef = eq._to_dev(tiles, dev), eq._to_dev(coef, dev)
+            d_tiles, d_coef = dimg.to_dev(tiles, dev), dimg.to_dev(coef, dev)
             d_out = torch.empty(nvox, dtype=torch.int16, device=dev)
             d_mm = torch.empty(2, dtype=torch.int32, device=dev)
             p("apply", 4, lambda: nat.check(L.mmx_eq_apply(ctypes.byref(src), ctypes.byref(geom), d_bins.data_ptr(),
@@ -135,8 +135,8 @@ def main() -> None:
                                                            d_coef.data_ptr(), d_out.data_ptr(), d_mm.data_ptr(), stream),
                                             "mmx_eq_apply"))
             lmin, lmax = (int(v) for v in d_mm.cpu().numpy().view(np.uint32))
-            d_table = eq._to_dev(eq.output_table(lmin, lmax), dev)
-            step, _ = eq._slabs(shape)
+            d_table = dimg.to_dev(eq.output_table(lmin, lmax), dev)
+            step, _ = dimg.slab_step(shape, 8)
             slab = torch.empty(step * ny * nx, dtype=torch.float64, device=dev)
 
             def output():
@@ -152,12 +152,11 @@ def main() -> None:
                 p("order_stats", 4, lambda: importer._percentiles_of_groups(dv, 0, [(0, nz)], prof["clip_vmin"],
                                                                             prof["clip_vmax"]))
                 lo, hi = importer._percentiles_of_groups(dv, 0, [(0, nz)], prof["clip_vmin"], prof["clip_vmax"])
-                v = dv.view(0, False)
 
                 def stretch():
                     for z0 in range(0, nz, step):
                         z1 = min(nz, z0 + step)
-                        sv = nat.DsView(v.d_data + 2 * z0 * v.stride_z, v.dtype, 0, v.stride_z, v.stride_y, v.stride_x)
+                        sv = dimg.view(dv, 0, z0)
                         nat.check(L.mmx_stretch(ctypes.byref(sv), z1 - z0, ny, nx, float(lo[0]),
                                                 float(max(hi[0], lo[0] + 1)), slab.data_ptr(), stream), "mmx_stretch")
                 p("stretch", 10, stretch)

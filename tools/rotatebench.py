@@ -48,7 +48,7 @@ def main() -> None:
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("rotatebench needs a GPU (there is no CPU fallback)")
-    from magellanmapper_amd import _native as nat, rotate as rot, synth, transformer
+    from magellanmapper_amd import _native as nat, device_image as dimg, rotate as rot, synth, transformer
     from magellanmapper_amd.volume import DeviceVolume
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
@@ -95,8 +95,9 @@ def main() -> None:
             src += 100.0                      # (a range that does not contain 0: the put-back of zeros is live)
         esize = src.element_size()
         dst = torch.empty_like(src)
-        sv, s_elems, shape3, n_chl = rot._view_of(src)
-        dv, d_elems, _, _ = rot._view_of(dst)
+        sv, s_elems, n_chl = dimg.view(src)
+        dv, d_elems, _ = dimg.view(dst)
+        shape3 = shape
         drec = rec["dtypes"][name] = {"minmax": {}, "warp": {}}
 
         def row(ms, runs, nbytes):
@@ -111,7 +112,7 @@ def main() -> None:
             drec["minmax"]["axis%d" % axis] = r = row(ms, runs, esize)
             print("%-8s minmax axis %d           %9.3f ms  %7.1f GB/s  (%.2f of the copy)" % (
                 name, axis, ms, r["gb_s"], r["of_copy"]))
-            rows, cols = rot._plane_shape(shape3, axis)
+            rows, cols = rot.plane_shape(shape3, axis)
             for angle in args.angles:
                 m = np.ascontiguousarray(rot.rotation_matrix(rows, cols, angle).reshape(-1))
                 for order in (0, 1):
